@@ -10,7 +10,11 @@ noise/timestep draw -> add_noise -> CLIP text encoder -> UNet forward -> MSE -> 
 (N>1: bucketed RCCL all-reduce overlapped with backward) -> clip_by_global_norm -> Lion-8bit -> EMA.  Inputs are
 resident in HBM before the timed region.  Rank 0 prints ONE JSON line.
 
-Extra legs (N=1, rank 0 only, outside the timed region):
+--dump-outputs DIR: after the timed steps, rank 0 writes what the last timed step handed back to its caller as DIR/<name>.npy
+(float32): the loss, and a fixed seeded sample of the updated fp32 parameters, EMA and Lion state of the UNet and text encoder.
+Inputs, weights and generator seeds are fixed, so two builds can be compared output for output.
+
+Extra legs (--full only; N=1, rank 0 only, outside the timed region):
   roofline      HIP-event timing (on the launch stream) of every launch of the dominant kernel family,
                 gemm_nt_kernel (MFMA implicit-GEMM conv / linear fwd+dgrad), during one extra step
   cpu_baseline  the CPU oracle (fp32 PyTorch-CPU restatement of the same step, kind "port") timed on the host cores
@@ -107,6 +111,30 @@ def state_digest(stores):
     return h.hexdigest()
 
 
+DUMP_SAMPLE = 1 << 20  # elements kept of a longer buffer: 4 MiB of float32 each, 11 files and at most 44 MiB in all
+
+
+def dump_outputs(path, loss, stores):
+    """--dump-outputs: what the last timed step handed back to its caller - the loss, and the states train_step updated in place (fp32
+    masters, EMA, 8-bit Lion momentum codes and their block scales, fp32 momenta) - as float32 DIR/<store>_<buffer>.npy.  A buffer longer
+    than DUMP_SAMPLE is sampled at sorted positions drawn from a fixed seed, so two runs of one configuration sample the same elements."""
+    import numpy as np
+    import torch
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "loss.npy"), np.array([loss], dtype=np.float32))
+    g = torch.Generator().manual_seed(20240601)
+    for prefix, st in stores:
+        for name in ("master", "ema", "codes", "inv_scale", "mom"):
+            t = getattr(st, name, None)
+            if t is None:
+                continue
+            t = t.detach().reshape(-1)
+            if t.numel() > DUMP_SAMPLE:
+                idx = torch.randint(0, t.numel(), (DUMP_SAMPLE,), generator=g).sort().values
+                t = t.index_select(0, idx.to(t.device))
+            np.save(os.path.join(path, f"{prefix}_{name}.npy"), t.float().cpu().numpy())
+
+
 def _cpu_model():
     try:
         with open("/proc/cpuinfo") as f:
@@ -121,7 +149,7 @@ def _cpu_model():
 def cpu_baseline(weights, cfgs, full=False):
     """The CPU restatement of the reference train_step (oracle/, kind "port": the reference's own Flax/XLA path is not installable
     offline) timed on this box's host cores at BASELINE configs[0]: SD1.5, 512x512 (64x64 latent), batch 1.
-    Default: ONE fp32 step, no warm-up - a bounded sample (~1 min of CPU work) that keeps the default command within minutes.
+    Default (--full): ONE fp32 step, no warm-up - a bounded sample (~1 min of CPU work) that keeps a --full run within minutes.
     full (--cpu-baseline-full): SURVEY.md §8(d)'s protocol - 1 warm-up + 3 timed steps, fp32 and bf16-autocast variants (takes
     ~10 minutes; its result for this round is committed under profiles/)."""
     import torch
@@ -201,10 +229,14 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--config", choices=sorted(CONFIGS), default="sd15_512", help="BASELINE.json configuration (default: configs[1], the metric's)")
     ap.add_argument("--batch", type=int, default=0, help="per-GPU batch (default: 4 for SD1.5 / SD2.1, 2 for SDXL)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy (float32)")
+    ap.add_argument("--full", action="store_true", help="also run the extra legs: roofline and cpu_baseline (a plain run times the steps only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-baseline-full", action="store_true", help="SURVEY 8(d) protocol: 1 warm-up + 3 timed steps, fp32 and bf16 autocast (~10 min)")
+    ap.add_argument("--cpu-baseline-full", action="store_true", help="with --full: SURVEY 8(d) protocol, 1 warm-up + 3 timed steps, fp32 and bf16 autocast (~10 min)")
     ap.add_argument("--no-roofline", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[args.config]
     args.batch = args.batch or cfg["batch"]
 
@@ -361,6 +393,8 @@ def main():
     dt, loss_val, graphed, setup_steps = best["dt"], best["loss"], best["graphed"], best["setup_steps"]
     weights, cfgs = last["weights"], last["cfgs"]
     run, step_fn = last.get("run"), last.get("step_fn")
+    if rank == 0 and args.dump_outputs:  # N > 1 with both exchange modes: the states of the mode timed last (the first one's are freed)
+        dump_outputs(args.dump_outputs, last["loss"], [("unet", last["us"].store), ("text_encoder", last["ts"].store)])
 
     result = None
     if rank == 0:
@@ -398,7 +432,7 @@ def main():
                 raise SystemExit(msg)
             if rank == 0:
                 print(msg + " - reported, not fatal (SDT_BENCH_STRICT=1 makes it fatal)", file=sys.stderr, flush=True)
-    if rank == 0 and world == 1 and not args.no_roofline:
+    if rank == 0 and world == 1 and args.full and not args.no_roofline:
         ops.GEMM_NT_TIMER = ops.KernelTimer()
         ops.GEMM_TN_TIMER = ops.KernelTimer()
         torch.cuda.synchronize()
@@ -431,7 +465,7 @@ def main():
                               "wgrad_kernel": {"kernel": "gemm_tn_kernel + conv_wgrad3_kernel", "achieved": tn["flops"] / (tn["raw_ms"] * 1e-3) / 1e12,
                                                "achieved_calibrated": tn["flops"] / (tn["ms"] * 1e-3) / 1e12,
                                                "kernel_ms_per_step": tn["raw_ms"], "launches_per_step": tn["launches"]}}
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and args.config == "sd15_512":
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and args.config == "sd15_512":
         for o in runs:
             for k in ("reducer", "run", "step_fn", "us", "ts"):
                 o.pop(k, None)

@@ -156,7 +156,7 @@ if os.path.exists(cpu) and os.path.getsize(cpu) > 0:  # tools/refresh_profiles.s
     cb = json.loads(open(cpu).read().strip().splitlines()[-1]).get("cpu_baseline")
     if cb:
         json.dump(cb, open(f"{dst}/{RND}_cpu_baseline.json", "w"), indent=1)
-        L.append("## CPU baseline (the fp32 oracle step on the box's host cores, `bench.py --cpu-baseline-full`)\n")
+        L.append("## CPU baseline (the fp32 oracle step on the box's host cores, `bench.py --full --cpu-baseline-full`)\n")
         L.append(f"{cb['value']:.4f} images/s in fp32 on {cb['cores']} threads of `{cb.get('cpu', '?')}` ({cb.get('sample', '')}); variants: "
                  + ", ".join(f"{k} {v['images_per_sec']:.4f} images/s" for k, v in cb.get("variants", {}).items()) + f" (`profiles/{RND}_cpu_baseline.json`).\n")
 if os.path.exists(f"{dst}/{RND}_pmc_traffic.json") and os.path.exists(f"{root}/tools/operand_bytes.py"):

@@ -6,7 +6,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/${SDT_ROUND:-r03}p
 mkdir -p $O
 if [ "$1" = "part1" ]; then
-  python bench.py > $O/bench_sd15.json 2> $O/bench_sd15.err
+  python bench.py --full > $O/bench_sd15.json 2> $O/bench_sd15.err
   tail -c 400 $O/bench_sd15.json; echo
   rm -rf $O/kstats $O/pmc_fetch $O/pmc_write $O/pmc_mfma $O/markers
   rocprofv3 --kernel-trace --stats -d $O/kstats -o k --output-format csv -- python3 bench.py --steps 20 --warmup 0 --no-cpu-baseline --no-roofline > $O/kstats.log 2>&1
@@ -34,11 +34,11 @@ elif [ "$1" = "markers" ]; then
   find $O/markers -name "*_trace.csv" -delete
   cat $O/phase_times.md
 elif [ "$1" = "cpu" ]; then
-  python bench.py --steps 5 --warmup 2 --no-roofline --cpu-baseline-full > $O/bench_cpu_full.json 2> $O/bench_cpu_full.err
+  python bench.py --full --steps 5 --warmup 2 --no-roofline --cpu-baseline-full > $O/bench_cpu_full.json 2> $O/bench_cpu_full.err
   tail -c 900 $O/bench_cpu_full.json
 else
   for cfg in sd21_768 sdxl_1024; do
-    python bench.py --config $cfg --steps 8 --warmup 2 > $O/bench_$cfg.json 2> $O/bench_$cfg.err
+    python bench.py --full --config $cfg --steps 8 --warmup 2 > $O/bench_$cfg.json 2> $O/bench_$cfg.err
     tail -c 700 $O/bench_$cfg.json; echo
     rm -rf $O/kstats_$cfg
     rocprofv3 --kernel-trace --stats -d $O/kstats_$cfg -o k --output-format csv -- python3 bench.py --config $cfg --steps 8 --warmup 0 --no-roofline --no-cpu-baseline > $O/kstats_$cfg.log 2>&1
