@@ -314,6 +314,12 @@ int sdt_embedding_fwd(const int32_t* ids, const float* tok, const float* pos, ui
 int sdt_embedding_bwd(const int32_t* ids, const uint16_t* dout, float* dtok, float* dpos, int64_t rows, int S, int D,
                       hipStream_t stream);
 
+/* ---- test hooks (not for the training path) ----
+ * Output channels per tile of the 3x3 halo convolution inside sdt_gemm_nt_bf16: 64 (the default) or 128 (the reference of the
+ * bitwise parity test).  Process-wide, not thread-safe; launches already enqueued keep the width they were planned with.
+ * Returns the previous width, or -1 (sdt_last_error) for any other value. */
+int sdt_conv_halo_set_tile_width(int bn);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,7 +32,6 @@ def _stale(target, deps):
 def build_library(force=False, verbose=False):
     hipcc = _hipcc()
     base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wno-unused-result", "-Wno-unused-value"]
-    base += os.environ.get("SDT_HIPCC_EXTRA", "").split()  # developer builds (e.g. -DSDT_ATTN_DBG ablations)
     jobs = []
     for src in SOURCES:
         s = os.path.join(CSRC, src)

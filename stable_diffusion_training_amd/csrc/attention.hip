@@ -161,7 +161,6 @@ struct AttnParams {
   float scale2;  // scale * log2(e)
   float scale;
   int causal;
-  int dbg;  // developer ablation bits, honoured only in -DSDT_ATTN_DBG builds
   // dK/dV with the query range split over workgroups (few keys, many queries: cross-attention): each query chunk writes its partial
   // sums to its own fp32 slab [2][B][Nk][H*D] and attn_kv_finish_kernel adds the slabs in order and rounds them into dk / dv
   float* kv_ws;
@@ -170,11 +169,6 @@ struct AttnParams {
   // whose last chunk is a clamped (overlapping) slice when the key count is not a multiple of the chunk: overlapped keys count twice
   const float* key_w;
 };
-#ifdef SDT_ATTN_DBG
-#define ATTN_DBG(bit) (p.dbg & (bit))
-#else
-#define ATTN_DBG(bit) false
-#endif
 
 // ------------------------------------------------------------------------------------------ forward
 // DPP: image pitch (features); NS = ceil(D/16) k-steps of q.k; NB = ceil(D/32) feature blocks of the output.
@@ -226,8 +220,8 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnParams p) {
   float m_run = NEG_BIG, l_run = 0.f;
   int cur = 0;
   for (int kbase = 0; kbase < kend; kbase += KT, cur ^= 1) {
-    if (!ATTN_DBG(16)) dma_join();
-    if (kbase + KT < kend && !ATTN_DBG(1)) {  // next tile flies under this tile's math
+    dma_join();
+    if (kbase + KT < kend) {  // next tile flies under this tile's math
       dma.issue(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE, wave_u);
       dmav.template issue<MSUM>(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE + I::BYTES, wave_u);
     }
@@ -238,12 +232,10 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnParams p) {
     for (int kt = 0; kt < 2; ++kt) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) st[kt][e] = 0.f;
-      if (!ATTN_DBG(8)) {
 #pragma unroll
       for (int s = 0; s < NS; ++s) {
         const bf16x8_t kf = row_frag<DPP>(k_img, kt * 32 + fr, 2 * s + fh);
         st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], st[kt], 0, 0, 0);
-      }
       }
     }
     // running max on the RAW scores (scale2 > 0), scale folded into the exp2 argument; masks only where needed
@@ -280,8 +272,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnParams p) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) {
         const float arg = fmaf(st[kt][e], p.scale2, mneg);
-        const float pv = ATTN_DBG(2) ? arg : __builtin_amdgcn_exp2f(arg);
-        st[kt][e] = pv;
+        st[kt][e] = __builtin_amdgcn_exp2f(arg);
       }
     if (p.key_w) {  // wave-uniform; the running max stays on the unweighted scores (weights are O(1))
 #pragma unroll
@@ -308,12 +299,10 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnParams p) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) tmp[j] = st[kt][8 * s + j];
         const bf16x8_t pf = cvt_frag(tmp);
-        if (!ATTN_DBG(4)) {
 #pragma unroll
         for (int i = 0; i < NB; ++i) {
           const bf16x8_t vf = tr.frag(v_img, kt * 32 + 16 * s, i);
           o_acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o_acc[i], 0, 0, 0);
-        }
         }
       }
   }
@@ -694,9 +683,6 @@ static int attn_fill(AttnParams* p, const SdtAttnDesc* d, const char* name) {
   p->scale2 = d->scale * 1.4426950408889634f;
   p->causal = d->causal;
   p->key_w = d->key_weight;
-#ifdef SDT_ATTN_DBG
-  p->dbg = getenv("SDT_ATTN_DBG") ? atoi(getenv("SDT_ATTN_DBG")) : 0;
-#endif
   return SDT_OK;
 }
 

@@ -6,7 +6,7 @@
 //      an input) or an im2col view gathered on the fly from an NHWC tensor (strided / asymmetric-pad convs, strided dgrad).
 //  conv3x3_halo_kernel : the same contraction for 3x3 / stride 1 / pad 1 convolutions (fprop and dgrad): a 256-pixel x
 //      128-channel tile whose input halo is staged ONCE per 64-channel chunk for all nine taps.
-//  gemm_tn_kernel      : dW[tap][K1][N] (fp32, atomically accumulated, split over M) += A_g[M,K1]^T * dY[M,N]
+//  gemm_tn_kernel      : dW[tap][K1][N] (fp32 or bf16, written once; split over M) = A_g[M,K1]^T * dY[M,N]
 //      (Linear / conv weight gradients + bias gradients, written straight into the Flax [in,out] / HWIO gradient layout).
 //  conv_wgrad3_kernel  : the weight gradient of a 3x3 / stride 1 / pad 1 convolution, three taps per workgroup.
 //
@@ -14,8 +14,9 @@
 // bank swizzle on the SOURCE address, padding from a 16-byte zero page) into rings whose later stages stay in flight across
 // the barrier (counted s_waitcnt vmcnt + raw s_barrier); row-major images are read with ds_read_b128 ([row][k] fragments) or
 // ds_read_b64_tr_b16 (k-major operands); where hipcc would drain the ring in front of an LDS read it can see, the reads are
-// inline asm with hand-counted lgkmcnt.  Split-K: fp32 atomics into a caller workspace, the last-arriving split finishes the
-// tile and leaves the workspace zero.  Epilogues can accumulate the GroupNorm statistics of what they store (gn_stats).
+// inline asm with hand-counted lgkmcnt.  Split-K: every split publishes its fp32 partial tile to a slab in a caller workspace,
+// the last-arriving split adds them in split order and finishes the tile (split_reduce).  Epilogues can accumulate the
+// GroupNorm statistics of what they store (gn_stats).
 //
 // Reference call sites these replace (all lowered by XLA in the reference): flax nn.Conv / nn.Dense inside
 // diffusers 0.21.4 unet_2d_condition_flax.py, unet_2d_blocks_flax.py, attention_flax.py, resnet_flax.py,
@@ -59,7 +60,7 @@ struct GatherDesc {
 };
 
 struct GemmNtParams {
-  int nst;  // LDS ring depth of this launch (>= NtCfg::NST; nt_ring_depth)
+  int nst;  // LDS ring depth of this launch (NtCfg::NST)
   const bf16_t* A;
   const bf16_t* Bt;
   bf16_t* C;
@@ -83,7 +84,6 @@ struct GemmNtParams {
   int cv_ni, cv_th, cv_tw, cv_ltw, cv_lth;  // (log2 of TW, TH)
   int cv_tiles_x, cv_tiles_y, cv_chunks_per_split;
   FastDiv cv_div_w2, cv_div_himg, cv_div_tx, cv_div_ty;  // / (TW+2), / ((TH+2)(TW+2)), / tiles_x, / tiles_y
-  int dbg;               // developer ablation bits: honoured only by -DSDT_NT_DBG builds (SDT_HIPCC_EXTRA), see NT_DBG below
   // B_KMAJOR kernels: B is [taps][Kc][ldb] (k-major: the Flax kernel layout itself, read through transposing LDS reads) instead of
   // Bt [N][ldb]; b_nseg > 0: its N columns are b_nseg-wide segments, segment s at B + s*b_seg_stride with row pitch ldb
   // (Dense layers that share an input, whose kernels are separate leaves)
@@ -97,15 +97,6 @@ struct GemmNtParams {
   bf16_t* C2;
   GatherDesc g;
 };
-
-// Ablation switches (they produce WRONG results: no waits / no math / no traffic / no epilogue) exist only in developer builds
-// (SDT_HIPCC_EXTRA=-DSDT_NT_DBG, then the SDT_NT_DBG environment variable selects the bits); the shipped library compiles them out
-// and reads no environment variable that can change a result.
-#ifdef SDT_NT_DBG
-#define NT_DBG(bit) (p.dbg & (bit))
-#else
-#define NT_DBG(bit) false
-#endif
 
 // 16 zero bytes every lane may DMA from (padding rows, conv halo, K tail)
 __device__ __attribute__((aligned(16))) unsigned int g_zero16[4] = {0u, 0u, 0u, 0u};
@@ -163,15 +154,13 @@ typedef __attribute__((ext_vector_type(4))) unsigned u32x4_t;
 // S splits, this workgroup is split `me`; slab / tile_cnt: the launch's scratch, group: the (tile, tap) this workgroup adds to.
 template <int NV, int NB, int NT = 256>
 __device__ __forceinline__ bool split_reduce(unsigned char* slab, int* tile_cnt, int S, int me, f32x16_t (&v)[NV], float (&bv)[NB],
-                                             bool bias_lane, int bias_slot0, int group, unsigned char* smem, int tid, int dbg = 0) {
+                                             bool bias_lane, int bias_slot0, int group, unsigned char* smem, int tid) {
+  constexpr int G = NV * 4 < 8 ? NV * 4 : 8;  // 16-byte slab loads in flight per thread (the accumulators fill most of the file)
   if (S == 1) return true;
   constexpr int BYTES = TnSlab<NV, NT>::BYTES;
   unsigned char* base = slab + (size_t)group * S * BYTES;  // wave-uniform: kernel argument + blockIdx arithmetic
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(base, 0, S * BYTES, 0x00020000);
   const int mine = me * BYTES;
-#ifdef SDT_NT_DBG
-  if (!(dbg & 512))
-#endif
 #pragma unroll
   for (int r = 0; r < NV; ++r)
 #pragma unroll
@@ -197,12 +186,8 @@ __device__ __forceinline__ bool split_reduce(unsigned char* slab, int* tile_cnt,
     // nothing rests on the one-workgroup-per-CU cell of that table.  An agent-scope RELEASE fence here (buffer_wbl2 sc1) is what the abstract memory
     // model would ask for on top; it writes back every dirty line of the XCD's L2 - the previous kernels' activations, nothing of
     // this slab, which is not dirty anywhere - and costs 1.1 ms per SD1.5 step (41.3 -> 40.3 ms same-box: (1024, 1280, 5120)
-    // 43.7 -> 37.3 us per launch).  -DSDT_SPLIT_RELEASE_FENCE builds it in; the default is the guide's form, held by
-    // test_split_reduction_handoff_under_uneven_load (every word, hundreds of launches beside a second stream's traffic).
-#ifdef SDT_SPLIT_RELEASE_FENCE
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
+    // 43.7 -> 37.3 us per launch).  The guide's form is held by test_split_reduction_handoff_under_uneven_load (every word,
+    // hundreds of launches beside a second stream's traffic).
     const int old = __hip_atomic_fetch_add(tile_cnt + group, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int last = old == S - 1;
     if (last) __hip_atomic_store(tile_cnt + group, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -210,9 +195,6 @@ __device__ __forceinline__ bool split_reduce(unsigned char* slab, int* tile_cnt,
   }
   __syncthreads();
   if (!*s_last) return false;
-#ifdef SDT_NT_DBG
-  if (dbg & 256) return true;  // developer ablation: the last arriver goes on with its own sums (wrong results)
-#endif
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");  // every wave, ahead of its own loads
 #pragma unroll
   for (int r = 0; r < NV; ++r)
@@ -222,10 +204,6 @@ __device__ __forceinline__ bool split_reduce(unsigned char* slab, int* tile_cnt,
   for (int j = 0; j < NB; ++j) bv[j] = 0.f;
   for (int s = 0; s < S; ++s) {  // fixed order (own slab included): the same sums whoever arrives last
     const int off = s * BYTES;
-#ifndef SPLIT_G
-#define SPLIT_G 8
-#endif
-    constexpr int G = NV * 4 < SPLIT_G ? NV * 4 : SPLIT_G;  // 16-byte loads in flight per thread (the accumulators fill most of the file)
 #pragma unroll
     for (int i0 = 0; i0 < NV * 4; i0 += G) {
       u32x4_t w[G];
@@ -332,25 +310,17 @@ __device__ __forceinline__ long gather_src(const GatherDesc& g, int b, int oy, i
 
 typedef __attribute__((ext_vector_type(4))) short s16x4_t;
 
-#ifndef TN_KB2
-#define TN_KB2 64   // rows of a 128-tile K-step
-#endif
-#ifndef TN_NST2
-#define TN_NST2 2   // ... and ring stages
-#endif
-#ifndef TN_WPS
-#define TN_WPS 2    // waves per SIMD the weight-gradient kernels are built for (= workgroups per CU)
-#endif
 template <int TM>
 struct TnCfg {
+  static constexpr int WPS = 2;                     // waves per SIMD the weight-gradient kernels are built for (= workgroups per CU)
   static constexpr int EDGE = 64 * TM;
-  static constexpr int KB = (TM == 2) ? TN_KB2 : 64;  // rows (reduction indices) per staged tile
+  static constexpr int KB = 64;                     // rows (reduction indices) per staged tile
   static constexpr int RB = EDGE * 2;               // bytes per staged row
   static constexpr int CPR = EDGE / 8;              // 16-byte chunks per row
   static constexpr int RPI = 1024 / RB;             // rows written by one wave-instruction of LDS-DMA
   static constexpr int IPW = KB / (RPI * 4);        // DMA instructions per wave per operand per tile
   static constexpr int TILE_BYTES = KB * RB;
-  static constexpr int NST = (TM == 2) ? TN_NST2 : 4;     // ring stages (A + B each)
+  static constexpr int NST = (TM == 2) ? 2 : 4;     // ring stages (A + B each)
   static constexpr int LDS_BYTES = NST * 2 * TILE_BYTES;
 };
 
@@ -378,19 +348,6 @@ __device__ __forceinline__ void tn_frag_issue(TrFrag& f, unsigned img, int col_b
   const int col = col_base + 16 * (g & 1) + 4 * pp;
   const int chunk = col >> 3, within = (pp & 1) * 8;
   const int r1 = 16 * s + 8 * (g >> 1) + q + row_off, r2 = r1 + 4;
-  const unsigned a1 = img + r1 * RB + ((chunk ^ tn_swz<TM>(r1)) << 4) + within;
-  const unsigned a2 = img + r2 * RB + ((chunk ^ tn_swz<TM>(r2)) << 4) + within;
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.lo) : "v"(a1) : "memory");
-  asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.hi) : "v"(a2) : "memory");
-}
-// the same for v_mfma_f32_16x16x32_bf16: lane l holds B[k = 8 (l >> 4) + j][col_base + (l & 15)], j = 0..7, of the k32-step s
-template <int TM>
-__device__ __forceinline__ void tn_frag_issue16(TrFrag& f, unsigned img, int col_base, int s, int lane) {
-  constexpr int RB = TnCfg<TM>::RB;
-  const int g = lane >> 4, q = (lane & 15) >> 2, pp = lane & 3;
-  const int col = col_base + 4 * pp;
-  const int chunk = col >> 3, within = (pp & 1) * 8;
-  const int r1 = 32 * s + 8 * g + q, r2 = r1 + 4;
   const unsigned a1 = img + r1 * RB + ((chunk ^ tn_swz<TM>(r1)) << 4) + within;
   const unsigned a2 = img + r2 * RB + ((chunk ^ tn_swz<TM>(r2)) << 4) + within;
   asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(f.lo) : "v"(a1) : "memory");
@@ -455,10 +412,9 @@ struct TileCfg {
   static constexpr int NL = EDGE / 32;                    // 16-byte loads per thread per operand (NT kernel)
   static constexpr int TILE_BYTES = EDGE * LDS_ROW_BYTES;  // one operand tile
   static constexpr int LDS_BYTES = 4 * TILE_BYTES;         // TN kernel: 2 buffers x (A + B)
-#ifndef NT_NST1
-#define NT_NST1 3  // 64-tile ring depth: 3 stages = 48 KB, three workgroups per CU (4 stages / two per CU: +0.18 ms per step, 2 stages / five: +0.45)
-#endif
-  static constexpr int NST = (TM == 2) ? 2 : NT_NST1;      // NT kernel: LDS-DMA ring depth; 128-tile: 2 stages so that two blocks share a CU (measured faster than 3 stages alone)
+  // NT kernel: LDS-DMA ring depth.  64-tile: 3 stages = 48 KB, three workgroups per CU (4 stages / two per CU: +0.18 ms per step,
+  // 2 stages / five: +0.45); 128-tile: 2 stages so that two blocks share a CU (measured faster than 3 stages alone)
+  static constexpr int NST = (TM == 2) ? 2 : 3;
   static constexpr int GN_SCRATCH = (TM == 2) ? 49152 : 16384;  // epilogue: GroupNorm partial-sum scratch behind the C tile
   static constexpr int LDS_BYTES_NT = NST * 2 * TILE_BYTES;
   static constexpr int R_NT = (TM == 1) ? 3 : 2;           // K-tiles of global loads kept in flight (register ring)
@@ -477,10 +433,7 @@ struct NtCfg {
   static constexpr int RPP = 256 / CH;                     // rows one pass of the 256 threads stages
   static constexpr int NL = EDGE / RPP;                    // 16-byte loads per thread per operand
   static constexpr int TILE_BYTES = EDGE * ROWB;
-#ifndef NT_K32_NST
-#define NT_K32_NST 3
-#endif
-  static constexpr int NST = (KB == 32) ? NT_K32_NST : TileCfg<TM>::NST;
+  static constexpr int NST = (KB == 32) ? 3 : TileCfg<TM>::NST;
   static constexpr int LDS_BYTES = NST * 2 * TILE_BYTES;
   static constexpr int GN_SCRATCH = (TM == 2) ? 36864 : 16384;  // epilogue: GroupNorm partial-sum scratch behind the C tile
   static_assert(LDS_BYTES >= GN_SCRATCH + 8 * EDGE * 4, "epilogue scratch must fit the ring");
@@ -663,9 +616,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const GemmNtParams p) {
 
   // NST-stage LDS ring: the DMA of tiles t+1 .. t+NST-2 stays in flight ACROSS the barrier (counted vmcnt, raw
   // s_barrier - a __syncthreads() would drain it), so only throughput, not the issue->landed latency, is exposed.
-  // [r4] The depth is a launch parameter (p.nst >= Cfg::NST): a grid that leaves CUs with one workgroup (the text tower, the
-  // time-embedding and 8 x 8 / 16 x 16-level projections: 60 - 250 tiles) gets the LDS the absent neighbours would have used as a
-  // deeper ring, so most of its short reduction is in flight from the prologue on instead of two tiles at a time.
+  // The depth arrives as a launch parameter, always Cfg::NST (a compile-time depth would change the generated loop).
   const int NST = p.nst;
   constexpr int LPT = 2 * NL;  // LDS-DMA instructions each wave issues per tile
   for (int s = 0; s < NST - 1; ++s)
@@ -674,14 +625,13 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const GemmNtParams p) {
   for (int t = t_beg; t < t_end; ++t) {
     const int idx = rd;
     const int ahead = min(NST - 2, t_end - 1 - t);  // younger tiles already issued
-    if (!NT_DBG(1)) wait_vmcnt(ahead * LPT);
+    wait_vmcnt(ahead * LPT);
     __builtin_amdgcn_s_barrier();  // tile t landed for every wave; everyone is done reading the stage the next DMA fills
-    if (t + NST - 1 < t_end && !NT_DBG(4)) {
+    if (t + NST - 1 < t_end) {
       stage(wr);
       if (++wr == NST) wr = 0;
     }
     if (++rd == NST) rd = 0;
-    if (NT_DBG(2)) continue;
     // [r4] every fragment of the K-step goes out at once (asm-owned reads at precomputed addresses), then the MFMAs of K16-step s
     // wait for exactly their own reads (counted lgkmcnt: LDS reads return in order).  Round 3 read, waited lgkmcnt(0) and
     // multiplied once per K16-step - the LDS latency four times per tile beside 32-cycle MFMAs - and rebuilt every address with
@@ -733,12 +683,11 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const GemmNtParams p) {
     });
   }
   __syncthreads();  // all waves done with the ring before the epilogue reuses it
-  if (NT_DBG(64)) return;  // developer ablation (-DSDT_NT_DBG builds only): no epilogue
 
   if (SPLITK) {  // only the split that arrives last at this tile goes on, with the complete sums (split_reduce)
     float nob[1] = {0.f};
     if (!split_reduce<TM * TM, 1>(p.slab, p.tile_cnt, (int)gridDim.y, (int)blockIdx.y, reinterpret_cast<f32x16_t(&)[TM * TM]>(acc), nob,
-                                  false, 0, tile, smem, tid, p.dbg))
+                                  false, 0, tile, smem, tid))
       return;
     __syncthreads();  // (the ticket word in LDS is about to be overwritten by the C tile)
   }
@@ -815,7 +764,7 @@ __global__ void __launch_bounds__(256, 2) gemm_nt_kernel(const GemmNtParams p) {
           }
           v = pack8(f);
         }
-        if (!NT_DBG(128)) *reinterpret_cast<uint4*>(p.C + (long)m * p.ldc + n) = v;
+        *reinterpret_cast<uint4*>(p.C + (long)m * p.ldc + n) = v;
         if (p.gn_stats) gn_accum(gns, gnq, v);
       }
     }
@@ -860,19 +809,15 @@ struct CvCfg {
 
 __device__ __forceinline__ int cv_off(int row, int chunk) { return row * LDS_ROW_BYTES + (((chunk ^ (row >> 1)) & 7) << 4); }
 
-// MF16 (BN = 64 only): the MFMAs are v_mfma_f32_16x16x32_bf16 - a wave's 64 x 64 tile as 4 x 4 tiles, two k32-steps per tap - instead
-// of v_mfma_f32_32x32x16_bf16 (2 x 2 tiles, four k16-steps): same fragments bytes, same accumulator registers; with two workgroups per
-// CU the loop's read / MFMA mix runs 1.17x faster in that shape (tools/mfma_shape_probe.hip: 1667 vs 1434 TFLOP/s).
-template <bool SPLITK, bool BKM, int BN, bool MF16>
+template <bool SPLITK, bool BKM, int BN>
 __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel(const GemmNtParams p) {
-  static_assert(!MF16 || BN == 64, "the 16x16x32 form is built for the 64-channel tile");
   using Cfg = CvCfg<BN>;
   constexpr int HB = Cfg::HB, BPW = Cfg::BPW;
-  constexpr int RT = MF16 ? 16 : 32;                    // rows / columns of one MFMA tile
+  constexpr int RT = 32;                                // rows / columns of one MFMA tile (v_mfma_f32_32x32x16_bf16)
   constexpr int NI = (CV_BM / Cfg::WM) / RT;            // pixel tiles per wave
   constexpr int NJ = 64 / RT;                           // channel tiles per wave (64 channels)
-  constexpr int KS = MF16 ? 2 : 4;                      // MFMA k-steps per 64-channel tap
-  constexpr int KG = MF16 ? 4 : 2;                      // 16-byte k-chunks per k-step
+  constexpr int KS = 4;                                 // MFMA k-steps per 64-channel tap
+  constexpr int KG = 2;                                 // 16-byte k-chunks per k-step
   constexpr int TMB = BN / 64;  // row width of a k-major weight tile in 128-byte units (tn_swz / tn_frag_issue)
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   unsigned char* halo_base = smem;
@@ -951,15 +896,13 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
     hp0[i] = il * HIMG + r * W2 + c;
   }
 
-  constexpr int AE = MF16 ? 4 : 16;  // accumulator registers per MFMA tile
-  typedef __attribute__((ext_vector_type(AE))) float acc_t;
-  acc_t acc[NI][NJ];
+  f32x16_t acc[NI][NJ];
 #pragma unroll
   for (int i = 0; i < NI; ++i)
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
 #pragma unroll
-      for (int e = 0; e < AE; ++e) acc[i][j][e] = 0.f;
+      for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
   const int nchunks = p.Kc / BK;
   int ch_beg = 0, ch_end = nchunks;
@@ -1005,8 +948,7 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
       if (BKM) {
-        if (MF16) tn_frag_issue16<TMB>(tb[j], lds0 + hb_off, wn * 64 + j * RT, s, lane);
-        else tn_frag_issue<TMB>(tb[j], lds0 + hb_off, wn * 64 + j * RT, s, lane);
+        tn_frag_issue<TMB>(tb[j], lds0 + hb_off, wn * 64 + j * RT, s, lane);
       } else {
         const unsigned addr = lds0 + hb_off + brow[j] + ((bkey[j] ^ (KG * s)) << 4);
         asm volatile("ds_read_b128 %0, %1" : "=v"(b[j]) : "v"(addr) : "memory");
@@ -1030,10 +972,7 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
 #pragma unroll
     for (int i = 0; i < NI; ++i)
 #pragma unroll
-      for (int j = 0; j < NJ; ++j) {
-        if constexpr (MF16) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
-        else acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
-      }
+      for (int j = 0; j < NJ; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(b[j], a[i], acc[i][j], 0, 0, 0);
   };
   auto tap_off = [&](int tap) {
     const int kh = tap / 3, kw = tap - 3 * (tap / 3);
@@ -1082,7 +1021,7 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
       set_tap(tap_off(tap + 1 < 9 ? tap + 1 : 0));
       if (tap + 1 < 9) load_frags(ha, BRING + ((tap + 1) % CV_NSTB) * Cfg::B_BYTES, 0, fa[0], fb[0], tfb[0]);
       else if (HB == 2 && more) load_frags(ha_next, BRING, 0, fa[0], fb[0], tfb[0]);
-      if (HB == 2 && tap < 7 && more && !NT_DBG(32)) {  // next chunk's halo: two pieces per tap (the 14th slot repeats piece 12)
+      if (HB == 2 && tap < 7 && more) {  // next chunk's halo: two pieces per tap (the 14th slot repeats piece 12)
         issue_halo(2 * tap < CV_HALO_PIECES ? 2 * tap : CV_HALO_PIECES - 1, (chunk + 1) * BK, hbuf ^ 1);
         issue_halo(2 * tap + 1 < CV_HALO_PIECES ? 2 * tap + 1 : CV_HALO_PIECES - 1, (chunk + 1) * BK, hbuf ^ 1);
       }
@@ -1093,7 +1032,6 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
 #pragma unroll
         for (int j = 0; j < CV_HALO_PIECES; ++j) issue_halo(j, (chunk + 1) * BK, 0);
       }
-      if (NT_DBG(16)) continue;  // developer ablation (SDT_NT_DBG, also bit 32 above): no weight / halo traffic in the loop, wrong results
       if (tap + 3 < 9) issue_b(tap + 3, chunk * BK, tap % CV_NSTB);
       else if (more) issue_b(tap + 3 - 9, (chunk + 1) * BK, tap % CV_NSTB);
       if (HB == 1 && tap == 8 && more) {
@@ -1107,7 +1045,6 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #undef CV_FRAG_WAIT
   __syncthreads();  // ring and halo are free: the epilogue reuses the LDS
-  if (NT_DBG(64)) return;  // developer ablation: no epilogue (wrong results): what the store path costs per tile
 
   // output row (GEMM m) of tile pixel `pix`
   auto out_row = [&](int pix) -> long {
@@ -1119,7 +1056,7 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
 
   if (SPLITK) {  // only the split that arrives last at this tile goes on, with the complete sums (split_reduce)
     float nob[1] = {0.f};
-    constexpr int NV = NI * NJ * AE / 16;  // the accumulators as 16-register groups (the slab is a per-thread register dump)
+    constexpr int NV = NI * NJ;  // the slab is a per-thread register dump
     if (!split_reduce<NV, 1>(p.slab, p.tile_cnt, (int)gridDim.y, (int)blockIdx.y, reinterpret_cast<f32x16_t(&)[NV]>(acc), nob, false, 0,
                                  tile, smem, tid))
       return;
@@ -1138,7 +1075,7 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
     for (int j = 0; j < NJ; ++j) {
       const int ml = wm * (NI * RT) + i * RT + fr;
 #pragma unroll
-      for (int g4 = 0; g4 < AE / 4; ++g4) {  // (D[row = channel][col = pixel]: 32x32: rows 8 g4 + 4 fh + e; 16x16: rows 4 fh + e)
+      for (int g4 = 0; g4 < 4; ++g4) {  // (D[row = channel][col = pixel]: rows 8 g4 + 4 fh + e)
         const int nl = wn * 64 + j * RT + 8 * g4 + 4 * fh;
         float v0 = acc[i][j][4 * g4 + 0], v1 = acc[i][j][4 * g4 + 1], v2 = acc[i][j][4 * g4 + 2], v3 = acc[i][j][4 * g4 + 3];
         if (p.bias && n0 + nl < p.N) {
@@ -1192,7 +1129,7 @@ __global__ void __launch_bounds__(256, CvCfg<BN>::WG_PER_CU) conv3x3_halo_kernel
 struct GemmTnParams {
   const bf16_t* A;   // gathered operand (activations x)
   const bf16_t* B;   // dY [M][ldb]
-  float* dW;         // [taps][K1_out][ldw] fp32, accumulated atomically
+  float* dW;         // [taps][K1_out][ldw] fp32 (or bf16: out_bf16), written once
   int M, K1, N;      // K1 = padded channel count read from A; N = padded column count read from B
   int K1_valid, N_valid;  // logical dims of dW actually written
   int lda, ldb, ldw;
@@ -1423,14 +1360,7 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTnParams& p, const int ti
     const int ahead = min(NST - 2, T - 1 - t);
     wait_vmcnt(ahead * LPT);
     __builtin_amdgcn_s_barrier();
-#if defined(TN_ABL) && (TN_ABL & 1)  // developer timing ablation (compile time only, wrong results): no staging behind the prologue
-    if (t + NST - 1 < T && t < 0) stage((t + NST - 1) % NST);
-#else
     if (t + NST - 1 < T) stage((t + NST - 1) % NST);
-#endif
-#if defined(TN_ABL) && (TN_ABL & 2)  // ... no fragment reads, no MFMAs
-    continue;
-#endif
     const unsigned sa = lds0 + (t % NST) * 2 * TILE_BYTES;
     const unsigned sb = sa + TILE_BYTES;
     unsigned aa[TM][2], ab[TM][2];  // this stage's fragment addresses (K16-step 0)
@@ -1484,9 +1414,6 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTnParams& p, const int ti
   for (int j = 0; j < TM; ++j) bv[j] = bacc[j][0];  // every accumulator row holds the column sum: row 0 = register 0 of lane half 0
   const bool bias_lane = do_bias && fh == 0;
   __syncthreads();  // all waves have left the staging ring (split_reduce reuses its first word)
-#if defined(TN_ABL) && (TN_ABL & 4)  // ... no slab publish, no output
-  if (acc[0][0][0] != 12345.678f) return;
-#endif
   if (!split_reduce<TM * TM, TM>(p.slab, p.tile_cnt, nsplit, me, reinterpret_cast<f32x16_t(&)[TM * TM]>(acc), bv, bias_lane, wn * WE + fr,
                                      tile * ntaps + tap, smem, tid))
     return;
@@ -1509,7 +1436,7 @@ __device__ __forceinline__ void gemm_tn_body(const GemmTnParams& p, const int ti
 // (2,606 -> 2,675 us with 757 -> 399 MB of reads per launch: their re-reads are served by the Infinity Cache and were never what
 // bound them), so those keep the round-robin deal.  A speed hint only: the slab hand-off (split_reduce) assumes nothing about placement.
 template <int TM, int MODE>
-__global__ void __launch_bounds__(256, TN_WPS) gemm_tn_kernel(const GemmTnParams p) {
+__global__ void __launch_bounds__(256, TnCfg<TM>::WPS) gemm_tn_kernel(const GemmTnParams p) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int tiles = p.tiles_k1 * p.tiles_n;
   const int L = MODE == TN_PLAIN ? xcd_remap(blockIdx.x, tiles * p.taps * p.splits) : (int)blockIdx.x;
@@ -1534,16 +1461,13 @@ struct GemmTnGroupParams {
 };
 template <bool CONTIGUOUS>
 __device__ __forceinline__ int tn_group_place(const GemmTnGroupParams& gp) {
-#ifdef TN_PLACE_RR  // developer A/B: round 3's placement everywhere
-  return (int)blockIdx.x < gp.xcd_begin[8] ? (int)blockIdx.x : -1;
-#endif
   if (!CONTIGUOUS) return (int)blockIdx.x < gp.xcd_begin[8] ? (int)blockIdx.x : -1;  // consecutive workgroups dealt over the XCDs
   const int x = blockIdx.x & 7;
   const int L = gp.xcd_begin[x] + (int)(blockIdx.x >> 3);
   return L < gp.xcd_begin[x + 1] ? L : -1;
 }
 template <int TM>
-__global__ void __launch_bounds__(256, TN_WPS) gemm_tn_group_kernel(const GemmTnGroupParams gp) {
+__global__ void __launch_bounds__(256, TnCfg<TM>::WPS) gemm_tn_group_kernel(const GemmTnGroupParams gp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int b = tn_group_place<true>(gp);
   if (b < 0) return;
@@ -1679,14 +1603,7 @@ __device__ __forceinline__ void conv_wgrad3_body(const GemmTnParams& p, const in
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     }
     __builtin_amdgcn_s_barrier();  // ... for every wave; everyone finished chunk t-1, whose stage takes chunk t+2
-#if defined(TN_ABL) && (TN_ABL & 1)  // developer timing ablations (compile time only, wrong results): see gemm_tn_body
-    if (t + 2 < T && t < 0) stage((t + 2) % W3_NST);
-#else
     if (t + 2 < T) stage((t + 2) % W3_NST);
-#endif
-#if defined(TN_ABL) && (TN_ABL & 2)
-    continue;
-#endif
     const unsigned sa = lds0 + (t % W3_NST) * W3_STAGE;
     const unsigned sb = sa + W3_A_BYTES;
     const int x0 = x_chunk;  // x of the chunk's first pixel
@@ -1739,9 +1656,6 @@ __device__ __forceinline__ void conv_wgrad3_body(const GemmTnParams& p, const in
   float bv[1] = {bacc[0]};
   const bool bias_lane = do_bias && fh == 0;
   __syncthreads();
-#if defined(TN_ABL) && (TN_ABL & 4)
-  if (acc[0][0][0] != 12345.678f) return;
-#endif
   if (!split_reduce<6, 1>(p.slab, p.tile_cnt, nsplit, me, reinterpret_cast<f32x16_t(&)[6]>(acc), bv, bias_lane, wn * 32 + fr, tile * 3 + kh, smem, tid)) return;
 #pragma unroll
   for (int kw = 0; kw < 3; ++kw) {
@@ -1827,17 +1741,6 @@ static int fill_gather(GatherDesc* g, const SdtConvGeom* geom, int mode, const c
   return SDT_OK;
 }
 
-#ifdef SDT_NT_DBG
-static int g_nt_dbg = getenv("SDT_NT_DBG") ? atoi(getenv("SDT_NT_DBG")) : 0;
-extern "C" void sdt_dbg_set_nt(int bits) { g_nt_dbg = bits; }  // developer builds only: ablation bits per launch (tools/phase_overlap_probe.py)
-static int nt_dbg_bits() { return g_nt_dbg; }
-#else
-static int nt_dbg_bits() { return 0; }
-#endif
-static int env_int(const char* name, int dflt) {
-  const char* e = getenv(name);
-  return e ? atoi(e) : dflt;
-}
 // Tile order of an NT launch.  Workgroups that share an XCD (and its 4 MB L2) take a contiguous run of tiles (xcd_remap), so the
 // order decides which operand that L2 keeps and which one streams in from the fabric once per tile column / row:
 //   walking M: one column tile of the weights stays hot; the rows are fetched again for every column tile unless all of them fit;
@@ -1845,8 +1748,6 @@ static int env_int(const char* name, int dflt) {
 // Bytes through the fabric under either order, smaller wins (level-0 Dense layers: 16384 x 320 rows against 0.2 - 1.6 MB of weights:
 // 30 - 210 MB walking M, 12 - 24 MB walking N).  Same arithmetic per tile either way: results are identical bit for bit.
 static int nt_tile_order(double a_bytes, double b_bytes, int tiles_m, int tiles_n) {
-  static const int force = env_int("SDT_NT_NFAST", -1);  // developer A/B: 0 / 1
-  if (force == 0 || force == 1) return force;
   const double cap = 2.5 * 1024 * 1024;  // what one XCD's L2 holds of an operand beside the other's stream
   const double walk_m = b_bytes + (a_bytes <= cap ? 8.0 * a_bytes : (double)tiles_n * a_bytes);
   const double walk_n = a_bytes + (b_bytes <= cap ? 8.0 * b_bytes : (double)tiles_m * b_bytes);
@@ -1858,6 +1759,10 @@ struct NtPlan {
   int splits;   // >1 -> split-K through the fp32 workspace
   int ksteps_per_split;
 };
+// split-K targets (workgroups to aim at) and shortest reductions (64-wide K-steps per split) of the two tiles, and the 64-tile
+// window that is split at all: fewer than NT_SPLIT_MAXT1 tiles and at least NT_SPLIT_MINT1 K-steps
+constexpr int NT_SPLIT_WG2 = 400, NT_SPLIT_STEPS2 = 12;
+constexpr int NT_SPLIT_WG1 = 480, NT_SPLIT_STEPS1 = 8, NT_SPLIT_MINT1 = 32, NT_SPLIT_MAXT1 = 160;
 static NtPlan plan_nt(int64_t M, int N, int Kc, int taps) {
   NtPlan pl;
   const long t128 = (long)sdt_ceil_div(M, 128) * sdt_ceil_div(N, 128);
@@ -1870,25 +1775,18 @@ static NtPlan plan_nt(int64_t M, int N, int Kc, int taps) {
     pl.tm = 2;  // >= one 128x128 tile per CU: the big tile (2x the MFMA work per staged byte) wins
   } else if (T >= 48 && t128 >= 16) {
     pl.tm = 2;  // deep reduction, few tiles (16x16 / 8x8 UNet levels): big tiles + split-K beat many small tiles
-    static const int tgt2 = env_int("SDT_NT_SPLIT_WG2", 400), minsteps2 = env_int("SDT_NT_SPLIT_STEPS2", 12);
-    s = (int)((tgt2 + t128 - 1) / t128);
-    if (s > T / minsteps2) s = T / minsteps2;
+    s = (int)((NT_SPLIT_WG2 + t128 - 1) / t128);
+    if (s > T / NT_SPLIT_STEPS2) s = T / NT_SPLIT_STEPS2;
   } else {
     pl.tm = 1;
-    static const int tgt1 = env_int("SDT_NT_SPLIT_WG1", 480), minsteps1 = env_int("SDT_NT_SPLIT_STEPS1", 8);
-    static const int mint1 = env_int("SDT_NT_SPLIT_MINT1", 32), maxt1 = env_int("SDT_NT_SPLIT_MAXT1", 160);
-    if (t64 < maxt1 && T >= mint1) {
-      s = (int)((tgt1 + t64 - 1) / t64);
-      if (s > T / minsteps1) s = T / minsteps1;
+    if (t64 < NT_SPLIT_MAXT1 && T >= NT_SPLIT_MINT1) {
+      s = (int)((NT_SPLIT_WG1 + t64 - 1) / t64);
+      if (s > T / NT_SPLIT_STEPS1) s = T / NT_SPLIT_STEPS1;
     } else if (t64 <= 32 && T >= 8) {
       // a handful of tiles (time-embedding projections, M = batch): the K loop IS the kernel, so cut it short even though every
       // split costs an atomic round trip (measured (4,1280,1280): 13.8 -> 8.5 us; (308,768,768) with 60 tiles gets slower)
       s = T / 4;
     }
-  }
-  {  // developer sweeps: force the tile size (splits then follow the other tile's rule only roughly)
-    static const int force_tm = env_int("SDT_NT_TM", 0);
-    if (force_tm == 1 || force_tm == 2) pl.tm = force_tm;
   }
   if (s > 32) s = 32;
   if (s >= 2) {
@@ -1898,23 +1796,10 @@ static NtPlan plan_nt(int64_t M, int N, int Kc, int taps) {
   return pl;
 }
 
-// Ring depth of an NT launch [r4]: the configuration's own (NtCfg::NST: sized so that two or three workgroups share a CU).  Developer
-// switch SDT_NT_DEEP_RING=1: a grid that leaves every CU fewer workgroups than that gets the LDS the absent neighbours would have used
-// as a deeper ring (<= 8 stages, <= 128 KB, no deeper than the reduction is long) - built to test whether the small launches (text
-// tower, 8 x 8 / 16 x 16 levels) wait on issue->landed latency; they do not (a CU streams ~24 GB/s from HBM however much is in
-// flight), the step did not move, and the default stays the configured depth.  ksteps: 64-wide K-steps of one workgroup's reduction.
-template <int TM, int KB>
-static int nt_ring_depth(long wgs, int ksteps) {
-  using Cfg = NtCfg<TM, KB>;
-  static const int on = env_int("SDT_NT_DEEP_RING", 0);  // measured: no gain on the step (39.48 vs 39.60 ms same-box), so off
-  const int stage = 2 * Cfg::TILE_BYTES, steps = ksteps * (64 / KB);
-  const long per_cu = (wgs + 255) / 256;
-  int nst = (int)(128 * 1024 / per_cu / stage);
-  if (nst > 8) nst = 8;
-  if (nst > steps + 1) nst = steps + 1;
-  if (!on || nst < Cfg::NST) nst = Cfg::NST;
-  return nst;
-}
+// Ring depth of an NT launch: the configuration's own (NtCfg::NST: sized so that two or three workgroups share a CU).  A deeper ring
+// for grids that leave CUs with fewer workgroups (the LDS the absent neighbours would have used, <= 8 stages) was measured and did
+// not move the step (39.48 vs 39.60 ms same-box): the small launches (text tower, 8 x 8 / 16 x 16 levels) do not wait on
+// issue->landed latency (a CU streams ~24 GB/s from HBM however much is in flight).
 #define NT_MAX_LDS (128 * 1024)
 
 template <int TM, bool SPLITK, bool GENERIC, bool BKM>
@@ -1925,14 +1810,11 @@ static void launch_nt2(const GemmNtParams& p, int splits, hipStream_t stream) {
     attr_set = true;
   }
   GemmNtParams q = p;
-  q.nst = nt_ring_depth<TM, 64>((long)p.tiles_m * p.tiles_n * splits, p.ksteps_per_split);
-  hipLaunchKernelGGL((gemm_nt_kernel<TM, SPLITK, GENERIC, BKM>), dim3(p.tiles_m * p.tiles_n, splits), dim3(256), (q.nst * 2 * NtCfg<TM, 64>::TILE_BYTES), stream, q);
+  q.nst = NtCfg<TM, 64>::NST;
+  hipLaunchKernelGGL((gemm_nt_kernel<TM, SPLITK, GENERIC, BKM>), dim3(p.tiles_m * p.tiles_n, splits), dim3(256), (NtCfg<TM, 64>::LDS_BYTES), stream, q);
 }
-// longest reduction (in 64-wide steps) that still runs the 32-wide-step 128-tile kernel (developer sweep: SDT_NT_K32_STEPS, 0 = off)
-static int nt_k32_max_steps() {
-  static const int v = env_int("SDT_NT_K32_STEPS", 20);
-  return v;
-}
+// longest reduction (in 64-wide steps) that still runs the 32-wide-step 128-tile kernel
+constexpr int NT_K32_MAX_STEPS = 20;
 template <int TM>
 static void launch_nt_pack8(const GemmNtParams& p, hipStream_t stream) {
   static bool attr_set = false;
@@ -1941,8 +1823,8 @@ static void launch_nt_pack8(const GemmNtParams& p, hipStream_t stream) {
     attr_set = true;
   }
   GemmNtParams q = p;
-  q.nst = nt_ring_depth<TM, 64>((long)p.tiles_m * p.tiles_n, p.ksteps_per_split);
-  hipLaunchKernelGGL((gemm_nt_kernel<TM, false, false, true, true>), dim3(p.tiles_m * p.tiles_n, 1), dim3(256), (q.nst * 2 * NtCfg<TM, 64>::TILE_BYTES), stream, q);
+  q.nst = NtCfg<TM, 64>::NST;
+  hipLaunchKernelGGL((gemm_nt_kernel<TM, false, false, true, true>), dim3(p.tiles_m * p.tiles_n, 1), dim3(256), (NtCfg<TM, 64>::LDS_BYTES), stream, q);
 }
 // 128-tiles with 32-wide K-steps, three workgroups per CU (NtCfg): unsplit launches with a short reduction
 template <bool BKM>
@@ -1953,8 +1835,8 @@ static void launch_nt_k32(const GemmNtParams& p, hipStream_t stream) {
     attr_set = true;
   }
   GemmNtParams q = p;
-  q.nst = nt_ring_depth<2, 32>((long)p.tiles_m * p.tiles_n, p.ksteps_per_split);
-  hipLaunchKernelGGL((gemm_nt_kernel<2, false, false, BKM, false, 32>), dim3(p.tiles_m * p.tiles_n, 1), dim3(256), (q.nst * 2 * NtCfg<2, 32>::TILE_BYTES), stream, q);
+  q.nst = NtCfg<2, 32>::NST;
+  hipLaunchKernelGGL((gemm_nt_kernel<2, false, false, BKM, false, 32>), dim3(p.tiles_m * p.tiles_n, 1), dim3(256), (NtCfg<2, 32>::LDS_BYTES), stream, q);
 }
 template <int TM, bool SPLITK>
 static void launch_nt(const GemmNtParams& p, int splits, bool b_kmajor, hipStream_t stream) {
@@ -1989,16 +1871,19 @@ struct TnPlan {
   int splits, rows_per_split;
   int64_t cnt_bytes, ws_bytes;    // counters, then splits x groups slabs (0 when the reduction is not split)
 };
+// [r4] conv_wgrad3_kernel from 256 output pixels (four 64-pixel chunks) on: the 8 x 8 level at batch 4 used to fall to the nine-tap
+// kernel (900 workgroups of four K-steps each, one tap per workgroup): its launches 90.7 -> 75.8 us (four problems) and 219.5 -> 150.9 us (eight)
+constexpr int WGRAD3_MIN_M = 256;
+// split targets (workgroups) and shortest split (rows of M): conv_wgrad3_kernel (same-box sweep of the target: 192 / 256 / 384 ->
+// 50.3 / 50.1 / 49.9 ms per step), gemm_tn_kernel
+constexpr int WGRAD3_WG = 384, WGRAD3_MIN_ROWS = 512;
+constexpr int TN_TARGET_WG = 384, TN_MIN_ROWS = 1024;
 static TnPlan plan_tn(const GatherDesc& g, int gather_mode, int64_t M, int K1, int N, int taps, int n_seg, int target_override = 0) {
   TnPlan pl;
-  static const int w3 = env_int("SDT_WGRAD3", 1);
-  // [r4] from 256 output pixels (four 64-pixel chunks) on: the 8 x 8 level at batch 4 used to fall to the nine-tap kernel (900 workgroups
-  // of four K-steps each, one tap per workgroup): its launches 90.7 -> 75.8 us (four problems) and 219.5 -> 150.9 us (eight)
-  static const int w3_min_m = env_int("SDT_WGRAD3_MIN_M", 256);
   const int W = g.OW;
   const bool wok = W >= 8 && W % 8 == 0;
-  pl.w3 = w3 && gather_mode == GATHER_FPROP && taps == 9 && g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad_t == 1 &&
-          g.pad_l == 1 && g.IH == g.OH && g.IW == g.OW && wok && n_seg == 0 && M % BK == 0 && M >= w3_min_m;
+  pl.w3 = gather_mode == GATHER_FPROP && taps == 9 && g.KH == 3 && g.KW == 3 && g.stride == 1 && g.pad_t == 1 &&
+          g.pad_l == 1 && g.IH == g.OH && g.IW == g.OW && wok && n_seg == 0 && M % BK == 0 && M >= WGRAD3_MIN_M;
   long base_wg;
   int target, min_rows, slab_bytes;
   if (pl.w3) {
@@ -2006,26 +1891,20 @@ static TnPlan plan_tn(const GatherDesc& g, int gather_mode, int64_t M, int K1, i
     pl.tiles_k1 = sdt_ceil_div(K1, 128); pl.tiles_n = sdt_ceil_div(N, 64);
     pl.groups = pl.tiles_k1 * pl.tiles_n * 3;
     base_wg = pl.groups;
-    static const int t3 = env_int("SDT_WGRAD3_WG", 384);  // (same-box sweep: 192 / 256 / 384 -> 50.3 / 50.1 / 49.9 ms per step)
-    static const int r3 = env_int("SDT_WGRAD3_MIN_ROWS", 512);
-    target = t3; min_rows = r3; slab_bytes = TnSlab<6>::BYTES;
+    target = WGRAD3_WG; min_rows = WGRAD3_MIN_ROWS; slab_bytes = TnSlab<6>::BYTES;
   } else {
-    const long wg128 = (long)sdt_ceil_div(K1, 128) * sdt_ceil_div(N, 128) * taps;
     // 128-tiles stage half the bytes per FLOP: worth their tile-quantisation waste once there are enough of them
     // (measured: (16384,320,2560) 105 -> 68 us, (16384,320,320)x9 126 -> 100 us; small-M weights stay on 64-tiles)
-    static const int force_tm = env_int("SDT_TN_TM", 0);  // developer sweeps
     // [r3] 128-tiles wherever both dimensions fill one: since the Dense weight gradients are issued in groups (sdt_gemm_tn_wgrad_group)
     // a launch no longer depends on ONE problem's tile count to fill the chip, and half the staged bytes per FLOP wins everywhere
-    // (same-box: 43.5 -> 42.7 ms per SD1.5 step against the round-2 rule wg128 >= 512 || (wg128 >= 48 && M >= 4096))
-    (void)wg128;
-    pl.tm = force_tm ? force_tm : ((K1 >= 128 && N >= 128) ? 2 : 1);
+    // (same-box: 43.5 -> 42.7 ms per SD1.5 step against the round-2 rule on the count of 128-tiles x taps, wg128 >= 512 ||
+    // (wg128 >= 48 && M >= 4096))
+    pl.tm = (K1 >= 128 && N >= 128) ? 2 : 1;
     const int edge = 64 * pl.tm;
     pl.tiles_k1 = sdt_ceil_div(K1, edge); pl.tiles_n = sdt_ceil_div(N, edge);
     pl.groups = pl.tiles_k1 * pl.tiles_n * taps;
     base_wg = pl.groups;
-    static const int tt = env_int("SDT_TN_TARGET_WG", 384);
-    static const int tr = env_int("SDT_TN_MIN_ROWS", 1024);
-    target = tt > 0 ? tt : 384; min_rows = tr >= BK ? tr : 1024;
+    target = TN_TARGET_WG; min_rows = TN_MIN_ROWS;
     slab_bytes = pl.tm == 2 ? TnSlab<4>::BYTES : TnSlab<1>::BYTES;
   }
   if (target_override > 0) target = target_override;
@@ -2057,16 +1936,21 @@ static TnPlan plan_tn(const GatherDesc& g, int gather_mode, int64_t M, int K1, i
 struct ConvHaloPlan {
   int ni, th, tw, tiles_x, tiles_y, tiles_m, tiles_n, splits, chunks_per_split;
 };
-// output channels per halo-convolution tile: 64 (two workgroups per CU; the default: 5-17 % less device time per launch,
-// -1.05 ms per SD1.5 step same-box) or 128 (one per CU; SDT_HALO_BN=128, kept as the reference of the bitwise parity test)
-static int conv_halo_bn() {  // (read per call: the parity test runs both in one process)
-  return env_int("SDT_HALO_BN", 64) == 128 ? 128 : 64;
+// output channels per halo-convolution tile: 64 (two workgroups per CU; 5-17 % less device time per launch, -1.05 ms per SD1.5
+// step same-box) or 128 (one per CU; kept as the reference of the bitwise parity test, which selects it through
+// sdt_conv_halo_set_tile_width)
+static int g_conv_halo_bn = 64;
+static int conv_halo_bn() { return g_conv_halo_bn; }
+extern "C" int sdt_conv_halo_set_tile_width(int bn) {
+  SDT_CHECK_ARG(bn == 64 || bn == 128, "sdt_conv_halo_set_tile_width: width %d is neither 64 nor 128", bn);
+  const int prev = g_conv_halo_bn;
+  g_conv_halo_bn = bn;
+  return prev;
 }
 static int conv_halo_splits(long tiles, int chunks) {
   // one workgroup per CU (152 KB of LDS; two at BN = 64): as many channel-chunk splits as still fit the 256 CUs in ONE round (a 257th
   // workgroup would wait for a whole tile time); measured: 240 workgroups beat 160 by 10-14 %, 280 lose 20 %
-  static const int cus1 = env_int("SDT_CONV_HALO_WG", 256);
-  const int cus = cus1 * (conv_halo_bn() == 64 ? 2 : 1);  // (two 64-channel workgroups share a CU)
+  const int cus = 256 * (conv_halo_bn() == 64 ? 2 : 1);  // (two 64-channel workgroups share a CU)
   if (chunks < 2 || tiles * 2 > cus) return 1;
   int s = (int)(cus / tiles);
   if (s > chunks) s = chunks;
@@ -2074,11 +1958,9 @@ static int conv_halo_splits(long tiles, int chunks) {
   return s < 1 ? 1 : s;
 }
 static bool conv_halo_plan(const GatherDesc& g, int64_t M, int N, int Kc, int taps, int batch, ConvHaloPlan* pl) {
-  static const int enabled = env_int("SDT_CONV_HALO", 1);
-  // (round 2 kept the 8x8 levels, 256 pixels = one tile, on the generic split-K path; with the slab hand-off back to the write-through
-  //  form, round 3, the halo kernel's split over channel chunks wins there too: -0.3 ms per step same-box)
-  static const int min_px = env_int("SDT_CONV_HALO_MINPX", 256);
-  if (!enabled || M < min_px) return false;
+  // from 256 output pixels on (round 2 kept the 8x8 levels, 256 pixels = one tile, on the generic split-K path; with the slab hand-off
+  // back to the write-through form, round 3, the halo kernel's split over channel chunks wins there too: -0.3 ms per step same-box)
+  if (M < 256) return false;
   if (!(g.mode == GATHER_FPROP || g.mode == GATHER_DGRAD) || taps != 9 || g.KH != 3 || g.KW != 3 || g.stride != 1 ||
       g.pad_t != 1 || g.pad_l != 1 || g.IH != g.OH || g.IW != g.OW || Kc % BK != 0)
     return false;
@@ -2099,38 +1981,21 @@ static bool conv_halo_plan(const GatherDesc& g, int64_t M, int N, int Kc, int ta
   return true;
 }
 static int ilog2(int v) { int l = 0; while ((1 << l) < v) ++l; return l; }
-template <bool SPLITK, bool BKM, int BN, bool MF16>
+template <bool SPLITK, bool BKM, int BN>
 static void launch_conv_halo3(const GemmNtParams& p, int splits, hipStream_t stream) {
   static bool attr_set = false;
   if (!attr_set) {
-    hipFuncSetAttribute((const void*)conv3x3_halo_kernel<SPLITK, BKM, BN, MF16>, hipFuncAttributeMaxDynamicSharedMemorySize, CvCfg<BN>::LDS_BYTES);
+    hipFuncSetAttribute((const void*)conv3x3_halo_kernel<SPLITK, BKM, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, CvCfg<BN>::LDS_BYTES);
     attr_set = true;
   }
-  hipLaunchKernelGGL((conv3x3_halo_kernel<SPLITK, BKM, BN, MF16>), dim3(p.tiles_m * p.tiles_n, splits), dim3(256), CvCfg<BN>::LDS_BYTES, stream, p);
+  hipLaunchKernelGGL((conv3x3_halo_kernel<SPLITK, BKM, BN>), dim3(p.tiles_m * p.tiles_n, splits), dim3(256), CvCfg<BN>::LDS_BYTES, stream, p);
 }
-// MFMA shape of the 64-channel tiling: v_mfma_f32_16x16x32_bf16 (SDT_HALO_MFMA=16) or v_mfma_f32_32x32x16_bf16 (32); a larger value
-// is a threshold: the small shape for row-major weights (input gradients) with at least that many input channels
-// (the measured-slower 16x16x32 instantiations are built only with -DSDT_HALO_MF16: tools/mfma_shape_probe.hip)
-#ifdef SDT_HALO_MF16
-static bool conv_halo_mf16(bool b_kmajor, int Kc) {
-  const int m = env_int("SDT_HALO_MFMA", 32);
-  if (m == 16) return true;
-  if (m <= 32) return false;
-  return !b_kmajor && Kc >= m;
-}
-#endif
 template <bool SPLITK>
 static void launch_conv_halo(const GemmNtParams& p, int splits, bool b_kmajor, hipStream_t stream) {
   if (conv_halo_bn() == 64) {
-#ifdef SDT_HALO_MF16
-    if (conv_halo_mf16(b_kmajor, p.Kc)) {
-      if (b_kmajor) launch_conv_halo3<SPLITK, true, 64, true>(p, splits, stream); else launch_conv_halo3<SPLITK, false, 64, true>(p, splits, stream);
-      return;
-    }
-#endif
-    if (b_kmajor) launch_conv_halo3<SPLITK, true, 64, false>(p, splits, stream); else launch_conv_halo3<SPLITK, false, 64, false>(p, splits, stream);
+    if (b_kmajor) launch_conv_halo3<SPLITK, true, 64>(p, splits, stream); else launch_conv_halo3<SPLITK, false, 64>(p, splits, stream);
   } else {
-    if (b_kmajor) launch_conv_halo3<SPLITK, true, 128, false>(p, splits, stream); else launch_conv_halo3<SPLITK, false, 128, false>(p, splits, stream);
+    if (b_kmajor) launch_conv_halo3<SPLITK, true, 128>(p, splits, stream); else launch_conv_halo3<SPLITK, false, 128>(p, splits, stream);
   }
 }
 static int conv_halo_slab_bytes() { return conv_halo_bn() == 64 ? TnSlab<4>::BYTES : TnSlab<8>::BYTES; }
@@ -2242,7 +2107,6 @@ int sdt_gemm_nt_bf16(const uint16_t* A, const uint16_t* Bt, uint16_t* C, const f
     p.cv_div_ty = make_fastdiv((unsigned)hp.tiles_y);
     p.tiles_m = hp.tiles_m; p.tiles_n = hp.tiles_n;
     p.nfast = nt_tile_order(2.0 * geom->batch * p.g.IH * p.g.IW * Kc, 2.0 * taps * (double)Kc * N, hp.tiles_m, hp.tiles_n);
-    p.dbg = nt_dbg_bits();
     const int64_t htiles = (int64_t)hp.tiles_m * hp.tiles_n;
     if (hp.splits > 1 && workspace && workspace_bytes >= nt_workspace_need(htiles, hp.splits, conv_halo_slab_bytes())) {
       p.cv_chunks_per_split = hp.chunks_per_split;
@@ -2267,7 +2131,6 @@ int sdt_gemm_nt_bf16(const uint16_t* A, const uint16_t* Bt, uint16_t* C, const f
   p.nfast = nt_tile_order(gather_mode == GATHER_PLAIN ? 2.0 * M * taps * Kc : 2.0 * geom->batch * p.g.IH * p.g.IW * Kc, 2.0 * taps * (double)Kc * N,
                           p.tiles_m, p.tiles_n);
   p.ksteps_per_split = pl.ksteps_per_split;
-  p.dbg = nt_dbg_bits();
   // 3x3 forward convolution of an 8-channel input (conv_in): eight taps per K-step (gemm_nt_kernel PACK8); the tile plan is the
   // unpacked shape's, so sdt_gemm_nt_gn_parts and the workspace query need not know
   if (pl.splits == 1 && gather_mode == GATHER_FPROP && b_kmajor && Kc == 8 && lda == 8 && taps == 9 && p.g.KH == 3 && p.g.KW == 3 &&
@@ -2281,7 +2144,7 @@ int sdt_gemm_nt_bf16(const uint16_t* A, const uint16_t* Bt, uint16_t* C, const f
     p.tile_cnt = reinterpret_cast<int*>(workspace);
     p.slab = (unsigned char*)workspace + nt_ws_counter_bytes((int64_t)p.tiles_m * p.tiles_n);
     if (pl.tm == 2) launch_nt<2, true>(p, pl.splits, b_kmajor != 0, stream); else launch_nt<1, true>(p, pl.splits, b_kmajor != 0, stream);
-  } else if (pl.tm == 2 && taps * sdt_ceil_div(Kc, BK) <= nt_k32_max_steps() && !(gather_mode == GATHER_DGRAD && p.g.stride != 1)) {
+  } else if (pl.tm == 2 && taps * sdt_ceil_div(Kc, BK) <= NT_K32_MAX_STEPS && !(gather_mode == GATHER_DGRAD && p.g.stride != 1)) {
     if (b_kmajor) launch_nt_k32<true>(p, stream); else launch_nt_k32<false>(p, stream);
   } else {
     if (pl.tm == 2) launch_nt<2, false>(p, 1, b_kmajor != 0, stream); else launch_nt<1, false>(p, 1, b_kmajor != 0, stream);
@@ -2294,7 +2157,7 @@ int sdt_gemm_nt_bf16(const uint16_t* A, const uint16_t* Bt, uint16_t* C, const f
 // ---- transformer feed-forward with the GEGLU fused into the GEMM epilogues (GemmNtParams.geglu_f) -----------------------------
 static bool ff_geglu_plan_ok(int64_t M, int N, int K) {
   const NtPlan pl = plan_nt(M, N, K, 1);
-  return pl.tm == 2 && pl.splits == 1 && sdt_ceil_div(K, BK) <= nt_k32_max_steps();
+  return pl.tm == 2 && pl.splits == 1 && sdt_ceil_div(K, BK) <= NT_K32_MAX_STEPS;
 }
 static bool ff_geglu_ok(int64_t M, int F, int K) {
   if (M <= 0 || M >= (1L << 31) || F <= 0 || K <= 0 || F % 64 || K % 8 || (int64_t)M * 2 * F >= (1LL << 31)) return 0;
@@ -2307,8 +2170,8 @@ static void launch_ff_geglu(const GemmNtParams& p, hipStream_t stream) {
     attr_set = true;
   }
   GemmNtParams q = p;
-  q.nst = nt_ring_depth<2, 32>((long)p.tiles_m * p.tiles_n, p.ksteps_per_split);
-  hipLaunchKernelGGL((gemm_nt_kernel<2, false, false, true, false, 32, 1>), dim3(p.tiles_m * p.tiles_n, 1), dim3(256), (q.nst * 2 * NtCfg<2, 32>::TILE_BYTES), stream, q);
+  q.nst = NtCfg<2, 32>::NST;
+  hipLaunchKernelGGL((gemm_nt_kernel<2, false, false, true, false, 32, 1>), dim3(p.tiles_m * p.tiles_n, 1), dim3(256), (NtCfg<2, 32>::LDS_BYTES), stream, q);
 }
 static void ff_geglu_fill(GemmNtParams* p, int64_t M, int N, int K) {
   memset(p, 0, sizeof(*p));
@@ -2409,8 +2272,7 @@ struct TnGroupItem {
 // workgroups the problems of one grouped launch aim at together: a few rounds of the chip's 512 resident workgroups, shared by
 // the problems in proportion (each problem's reduction is split less than it would be alone: less slab traffic per result)
 static int tn_group_target(int n) {
-  static const int total = env_int("SDT_TN_GROUP_WG", 1024);
-  int t = total / (n > 0 ? n : 1);
+  int t = 1024 / (n > 0 ? n : 1);
   return t < 48 ? 48 : t;
 }
 static int64_t tn_slab_bytes(const TnPlan& pl) { return pl.tm == 2 ? TnSlab<4>::BYTES : TnSlab<1>::BYTES; }
@@ -2441,7 +2303,7 @@ static int tn_group_fill(const SdtTnProblem* q, int n, TnGroupItem* items, const
 // runs of equal work, one per XCD (GemmTnGroupParams).  Work of a workgroup = its K-steps + a fixed cost (prologue latency, slab
 // publish, epilogue) expressed in K-steps.  Returns the grid size: 8 x the longest run.
 static int tn_group_cut(GemmTnGroupParams* gp) {
-  static const int fixed = env_int("SDT_TN_WG_FIXED_STEPS", 6);
+  constexpr int fixed = 6;  // K-steps
   double w[TN_GROUP_MAX], total = 0.0;
   for (int i = 0; i < gp->n; ++i) {
     const int cnt = gp->wg_end[i] - (i ? gp->wg_end[i - 1] : 0);

@@ -3,7 +3,8 @@ RCCL (xGMI) that overlaps the remaining backward.
 
 The reference gets the same semantics implicitly: a (N,1) mesh, batch sharded on "data_parallel", everything else
 replicated (training_utils.py:35-37, 446-483, 835-932) so GSPMD inserts the gradient all-reduce for the global-batch
-mean (:709).  Here the flat fp32 gradient buffer of each ParamStore is cut into contiguous buckets; a bucket is
+mean (:709).  Here the flat gradient buffers of each ParamStore (bf16 for the quantised kernel leaves, fp32 for the rest:
+ParamStore.grad_view) are cut into contiguous buckets; a bucket is
 launched on a side stream as soon as the backward has enqueued the weight-gradient kernels of all its leaves
 (ParamStore leaves are laid out in forward order, so buckets complete back to front).  Clipping needs the REDUCED
 gradient, so the optimizer sweep waits for the last bucket (reducer.finish()).
@@ -38,9 +39,6 @@ import torch
 import torch.distributed as dist
 
 from . import _lib
-
-
-_SKIP_SELF = os.environ.get("SDT_DP_SKIP_SELF") == "1"  # developer probe (tools/dp_graph_probe.sh): see GradReducer._reduce
 
 
 class _Done:
@@ -84,7 +82,7 @@ class GradReducer:
         self.stores = list(stores)
         self.overlap = overlap
         self.shard = bool(shard) and self.active
-        self.skip_self = bool(skip_self or _SKIP_SELF) and self.world == 1
+        self.skip_self = bool(skip_self) and self.world == 1
         self.buckets = []  # dict(store, a, b, need, pending, launched, scatter)
         self._owner = {}
         for si, st in enumerate(self.stores):

@@ -11,7 +11,6 @@ order: the flat gradient buffer is laid out in that order, so backward completes
 Activations are NHWC bf16 with channels padded to a multiple of 8 (4-channel latents / 3-channel pixels -> 8).
 """
 import math
-import os
 
 import torch
 
@@ -76,9 +75,6 @@ def _per_block(v, n):
 
 def _pad8(c):
     return (c + 7) // 8 * 8
-
-
-_GROUP_SHARED = os.environ.get("SDT_GROUP_SHARED", "1") != "0"  # developer A/B: 0 = every block projects temb / the context itself
 
 
 # ----------------------------------------------------------------------------- parameter specs (forward order)
@@ -316,7 +312,7 @@ def _time_emb_projections(st, temb_act):
     out = {}
     for width, names in groups.items():
         a = next(acts)
-        y = ops.linear_multi(a, st, tuple(n + "/time_emb_proj" for n in names)) if len(names) > 1 and _GROUP_SHARED else None
+        y = ops.linear_multi(a, st, tuple(n + "/time_emb_proj" for n in names)) if len(names) > 1 else None
         if y is not None:
             for n, rb in zip(names, ops.col_slices(y, len(names))):
                 out[n] = rb
@@ -339,7 +335,7 @@ def _context_projections(st, ctx):
     out = {}
     for width, names in groups.items():
         a = next(acts)
-        y = ops.linear_multi(a, st, tuple(n + t for n in names for t in ("/to_k", "/to_v"))) if len(names) > 1 and _GROUP_SHARED else None
+        y = ops.linear_multi(a, st, tuple(n + t for n in names for t in ("/to_k", "/to_v"))) if len(names) > 1 else None
         if y is not None:
             for n, kv in zip(names, ops.col_slices(y, len(names))):
                 out[n] = _PackedKV(kv)

@@ -2,9 +2,10 @@
 backward ONLY launch kernels of libsdtrain_hip.so through the C ABI (include/sdt.h) on the current HIP stream.
 PyTorch supplies device memory, the stream and the autograd tape; none of its compute kernels are on the path.
 
-Activations: bf16, NHWC / (rows, channels), channel counts multiples of 8.  Weight gradients are accumulated
-straight into the owning ParamStore's flat fp32 gradient buffer (the all-reduce payload) as a side effect of
-backward; `store.grad_ready(path)` lets the data-parallel reducer launch a bucket as soon as it is complete.
+Activations: bf16, NHWC / (rows, channels), channel counts multiples of 8.  Weight gradients are written
+straight into the owning ParamStore's flat gradient buffers (the all-reduce payload: bf16 for the quantised kernel
+leaves, fp32 for everything else; ParamStore.grad_view) as a side effect of backward; `store.grad_ready(path)` lets
+the data-parallel reducer launch a bucket as soon as it is complete.
 """
 import os
 
@@ -274,8 +275,8 @@ def _tn_workspace(need, device):
 # of launched: nothing on the input-gradient chain waits for it, each alone is a 10 - 25 us launch of 25 - 100 tiles, and a dozen
 # of them as one launch fill the chip.  The queue is flushed when it holds WGRAD_GROUP_LIMIT jobs and when the context closes
 # (before the gradient exchange / optimizer); store.grad_ready fires at the flush.  Outside the context nothing is deferred.
-WGRAD_GROUP_LIMIT = int(os.environ.get("SDT_WGRAD_GROUP", "32"))  # 0: never defer (developer A/B)
-CONV_GROUP_LIMIT = int(os.environ.get("SDT_CONV_WGRAD_GROUP", "8"))
+WGRAD_GROUP_LIMIT = 32
+CONV_GROUP_LIMIT = 8
 WGRAD_DUMP = bool(os.environ.get("SDT_WGRAD_DUMP"))
 _WGRAD_QUEUE = None
 _CONV_QUEUE = []  # deferred convolution weight gradients (sdt_conv_wgrad_group): (problem, tensors kept alive, store, paths, flops)
@@ -286,7 +287,7 @@ class wgrad_grouping:
     def __enter__(self):
         global _WGRAD_QUEUE
         self.prev = _WGRAD_QUEUE
-        _WGRAD_QUEUE = [] if WGRAD_GROUP_LIMIT > 0 else None
+        _WGRAD_QUEUE = []
         return self
 
     def __exit__(self, *exc):

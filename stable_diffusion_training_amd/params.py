@@ -1,8 +1,9 @@
 """Flat, HBM-resident parameter / gradient / optimizer-state storage for one trained model.
 
 Mirrors what the reference keeps in a flax TrainState + optax state (training_utils.py:383-387, 420-425;
-lion_quant.py:12-17) but laid out for the MI355X: ONE contiguous fp32 master buffer, ONE fp32 gradient buffer
-(the RCCL all-reduce payload, bucketed by contiguous ranges), int8 codes + fp32 inverse scales for the
+lion_quant.py:12-17) but laid out for the MI355X: ONE contiguous fp32 master buffer, the gradient as a bf16 buffer for
+the quantised kernel leaves (grad16) and an fp32 one for the rest (grad) (together the RCCL all-reduce payload, bucketed by
+contiguous ranges), int8 codes + fp32 inverse scales for the
 quantised leaves, fp32 momentum for the rest, optional fp32 EMA, and ONE bf16 compute copy W in the Flax layout itself that
 every GEMM reads (forward as a k-major operand, input gradient as a row-major one): a mirror of the master, element for
 element, written by the optimizer sweep.  Leaves are grouped into four contiguous segments by
@@ -12,7 +13,6 @@ Leaf naming / layouts are the diffusers-Flax ones: conv kern
 `create_mask` keeps the reference's exact-path-component semantics (training_utils.py:116-131).
 """
 import math
-import os
 from dataclasses import dataclass
 
 import torch
@@ -151,11 +151,11 @@ class ParamStore:
         # again: 2 B instead of 4 B per parameter through the wgrad stores, the norm pass, the optimizer sweep and the gradient
         # exchange.  Everything else (biases, norm parameters, embeddings, unquantised kernels: [quant_total, total)) stays
         # fp32 in `grad`.  A store with a quantised leaf that is NOT a matrix kernel (its gradient is accumulated in fp32 by the
-        # norm / embedding kernels) keeps the whole buffer fp32 (SDT_GRAD_BF16=0 does the same: developer A/B).
+        # norm / embedding kernels) keeps the whole buffer fp32 (grad_bf16=False does the same).
         self.grad16 = None
         self.g32_base = 0
         if trainable:
-            bf16_ok = (grad_bf16 and self.quant_total > 0 and os.environ.get("SDT_GRAD_BF16", "1") != "0"
+            bf16_ok = (grad_bf16 and self.quant_total > 0
                        and all(lf.w_off != -1 for lf in self.leaves.values() if lf.quantised))
             if bf16_ok:
                 self.grad16 = torch.zeros(self.quant_total, dtype=torch.bfloat16, device=dev)

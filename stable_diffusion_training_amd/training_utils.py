@@ -178,7 +178,7 @@ def assemble_context(hs, batch, strip_bos_eos_token):
     return e.view(batch, -1, d)
 
 
-_FUSED_NORM = __import__("os").environ.get("SDT_FUSED_NORM", "1") != "0"  # developer A/B: 0 = always the pass over the gradient buffer
+_FUSED_NORM = True  # False: always the pass over the gradient buffer (same bits)
 
 
 def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, batch, train_rng,

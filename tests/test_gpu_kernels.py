@@ -264,25 +264,30 @@ def test_conv2d_fwd_bwd(dev, B, H, W, Cin, Cout, k, stride, pad):
     (2, 32, 32, 640, 1280, False),    # split over channel chunks (slab reduction)
     (3, 16, 24, 64, 128, False),      # ragged image group
     (1, 8, 128, 128, 72, False)])     # 64-wide tiles per row, ragged channels
-def test_halo_conv_tile_widths_agree_bitwise(dev, monkeypatch, B, H, W, Cin, Cout, exact):
+def test_halo_conv_tile_widths_agree_bitwise(dev, B, H, W, Cin, Cout, exact):
     """conv3x3_halo_kernel<BN = 64> (256 x 64 tiles, one halo buffer, two workgroups per CU) against <BN = 128> (one workgroup per
     CU): every output element is the same chain of MFMAs over (chunk, tap, k) in both, so forward and input gradient must agree
     bit for bit wherever neither splits the reduction (a split changes the summation order: tolerance there), with the fused
-    row bias, residual and GroupNorm statistics."""
-    from stable_diffusion_training_amd import ops
+    row bias, residual and GroupNorm statistics.  The width is chosen through the library's test hook
+    (sdt_conv_halo_set_tile_width)."""
+    from stable_diffusion_training_amd import _lib, ops
+    lib = _lib.load()
     fs = FakeStore([("c/kernel", (3, 3, Cin, Cout)), ("c/bias", (Cout,))], dev, seed=Cin)
     x = rnd((B, H, W, Cin), dev, 1).requires_grad_(True)
     rb, res, dy = rnd((B, Cout), dev, 2), rnd((B, H, W, Cout), dev, 3), rnd((B, H, W, Cout), dev, 4)
 
     def run(bn):
-        monkeypatch.setenv("SDT_HALO_BN", str(bn))
-        x.grad = None
-        gn = 32 if Cout % 32 == 0 else 0
-        out = ops.conv2d(x, fs.st, "c", rowbias=rb, residual=res, gn_groups=gn)
-        y, stats = out if gn else (out, None)
-        y.backward(dy)
-        torch.cuda.synchronize()
-        return y.detach().clone(), None if stats is None else stats.clone(), x.grad.clone()
+        assert lib.sdt_conv_halo_set_tile_width(bn) in (64, 128)
+        try:
+            x.grad = None
+            gn = 32 if Cout % 32 == 0 else 0
+            out = ops.conv2d(x, fs.st, "c", rowbias=rb, residual=res, gn_groups=gn)
+            y, stats = out if gn else (out, None)
+            y.backward(dy)
+            torch.cuda.synchronize()
+            return y.detach().clone(), None if stats is None else stats.clone(), x.grad.clone()
+        finally:
+            lib.sdt_conv_halo_set_tile_width(64)
 
     y0, s0, g0 = run(128)
     wq = fs.w["c/kernel"].to(dev).to(BF).float().permute(3, 2, 0, 1)

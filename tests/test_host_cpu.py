@@ -62,15 +62,41 @@ def test_planner_queries_of_the_round_three_paths(lib):
     assert lib.sdt_stream_wait_event_external is not None
 
 
+def _dynamic_imports(path):
+    """Names of the undefined (imported) symbols in the .dynsym table of a 64-bit little-endian ELF shared object."""
+    import struct
+    blob = open(path, "rb").read()
+    assert blob[:4] == b"\x7fELF" and blob[4] == 2 and blob[5] == 1, "expected a 64-bit little-endian ELF file"
+    shoff, = struct.unpack_from("<Q", blob, 0x28)
+    shentsize, shnum = struct.unpack_from("<HH", blob, 0x3A)
+    sections = [struct.unpack_from("<IIQQQQIIQQ", blob, shoff + i * shentsize) for i in range(shnum)]
+    names = set()
+    for _, sh_type, _, _, off, size, link, _, _, entsize in sections:
+        if sh_type != 11:  # SHT_DYNSYM
+            continue
+        str_off = sections[link][4]
+        for k in range(size // entsize):
+            st_name, _, _, st_shndx = struct.unpack_from("<IBBH", blob, off + k * entsize)
+            if st_shndx == 0 and st_name:  # SHN_UNDEF
+                names.add(blob[str_off + st_name: blob.index(b"\0", str_off + st_name)].decode())
+    return names
+
+
 def test_default_build_has_no_wrong_result_switches(lib):
-    """The timing ablations (SDT_NT_DBG, SDT_ATTN_DBG: kernels that skip waits / math / stores) and the measured-slower
-    16x16x32 halo variant (SDT_HALO_MFMA) exist only in developer builds (SDT_HIPCC_EXTRA=-DSDT_NT_DBG ...): the shipped library
-    does not even contain the variable names, so no stray environment variable can corrupt a training run."""
-    if os.environ.get("SDT_HIPCC_EXTRA"):
-        pytest.skip("developer build")
+    """The library reads no environment variable: planning is a function of the problem shape alone, and the timing ablations
+    (kernels that skip waits / math / stores) and the measured-slower 16x16x32 halo variant are gone, so no stray environment
+    variable can change a result or corrupt a training run."""
     blob = open(_lib.LIB_PATH, "rb").read()
-    for name in (b"SDT_NT_DBG", b"SDT_ATTN_DBG", b"SDT_HALO_MFMA"):
+    for name in (b"SDT_NT_DBG", b"SDT_ATTN_DBG", b"SDT_HALO_MFMA", b"SDT_HALO_BN",
+                 b"SDT_NT_SPLIT_WG1", b"SDT_NT_SPLIT_WG2", b"SDT_NT_SPLIT_STEPS1", b"SDT_NT_SPLIT_STEPS2", b"SDT_NT_SPLIT_MINT1",
+                 b"SDT_NT_SPLIT_MAXT1", b"SDT_NT_TM", b"SDT_NT_DEEP_RING", b"SDT_NT_NFAST", b"SDT_NT_K32_STEPS",
+                 b"SDT_WGRAD3", b"SDT_WGRAD3_MIN_M", b"SDT_WGRAD3_WG", b"SDT_WGRAD3_MIN_ROWS", b"SDT_TN_TM", b"SDT_TN_TARGET_WG",
+                 b"SDT_TN_MIN_ROWS", b"SDT_TN_GROUP_WG", b"SDT_TN_WG_FIXED_STEPS",
+                 b"SDT_CONV_HALO", b"SDT_CONV_HALO_MINPX", b"SDT_CONV_HALO_WG"):
         assert name not in blob, f"{name.decode()} is readable by the default build"
+    imports = _dynamic_imports(_lib.LIB_PATH)
+    assert any(n.startswith("hip") for n in imports), "no HIP imports found: bad ELF parse"
+    assert not {"getenv", "secure_getenv"} & imports, "the library imports getenv"
 
 
 def test_no_cpu_fallback_when_no_device(lib):

@@ -29,4 +29,4 @@ for _ in range(steps):
     out = step(us, ts, ue, te, batch, rng, vae, sched)
 torch.cuda.synchronize()
 dt = (time.perf_counter() - t0) / steps
-print(f"{H}x{W}: {1e3 * dt:.2f} ms/step, {4 / dt:.1f} images/sec, loss {float(out[4]['loss']):.4f}  (SDT_CONV_HALO={os.environ.get('SDT_CONV_HALO', '1')})", flush=True)
+print(f"{H}x{W}: {1e3 * dt:.2f} ms/step, {4 / dt:.1f} images/sec, loss {float(out[4]['loss']):.4f}", flush=True)

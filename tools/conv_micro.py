@@ -1,5 +1,5 @@
-"""Developer micro-benchmark: 3x3 stride-1 convolution forward per shape of the SD1.5 step (B=4); SDT_CONV_HALO=0/1 selects
-the generic gather kernel or the halo-staged kernel (read once per process)."""
+"""Developer micro-benchmark: 3x3 stride-1 convolution forward per shape of the SD1.5 step (B=4), through the kernel the planner
+picks (the halo-staged kernel wherever it applies).  A/B of two builds: tools/build_variant.sh + SDT_LIB."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
