@@ -2,7 +2,10 @@
 shape-keyed step table -> train_step -> loss CSV -> per-chunk save_model (+ -EMA) -> training-state file for resume.
 One process per GPU:  python -m torch.distributed.run --nproc-per-node N examples/train_synthetic.py config.json
 (single GPU: python examples/train_synthetic.py config.json).  config.json holds the reference's model_properties.json keys
-(model_properties_example.json) plus "batches_per_chunk"; "model_path" is a diffusers-Flax pipeline directory."""
+(model_properties_example.json) plus "batches_per_chunk"; "model_path" is a diffusers-Flax pipeline directory.
+--micro-batches K (or "micro_batches" in the config): every step accumulates the gradient over K micro-batches of
+batch_size / (world * K) samples - the step over the global batch_size with the activation memory of one micro-batch."""
+import argparse
 import json
 import os
 import shutil
@@ -37,6 +40,9 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     if world > 1 and not dist.is_initialized():
         dist.init_process_group("nccl", rank=rank, world_size=world, device_id=dev, pg_options=dp.rccl_group_options())
     training_config = tu.TrainingConfig.from_dict(config_dict)
+    micro_batches = int(config_dict.get("micro_batches", 1))
+    if config_dict["batch_size"] % (world * micro_batches):
+        raise ValueError(f'batch_size {config_dict["batch_size"]} is not a multiple of world size x micro_batches ({world} x {micro_batches})')
     if models is None:
         models = tu.load_models(training_config)
         tokenizer = models["tokenizer"]
@@ -59,7 +65,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     reducer = dp.GradReducer([unet_state.store, text_encoder_state.store]) if world > 1 else None
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
-        reducer=reducer, per_device_batch=config_dict["batch_size"] // world)
+        reducer=reducer, per_device_batch=config_dict["batch_size"] // (world * micro_batches), micro_batches=micro_batches)
     resume = config_dict.get("resume_training_state")
     if resume and os.path.exists(resume):
         tu.load_training_state(resume, unet_state, text_encoder_state, train_rngs, rank=rank, world=world)
@@ -135,6 +141,12 @@ def main(config_dict, models=None, tokenizer=None, log=print):
 
 
 if __name__ == "__main__":
-    with open(sys.argv[1] if len(sys.argv) > 1 else "model_properties.json") as f:
+    ap = argparse.ArgumentParser()
+    ap.add_argument("config", nargs="?", default="model_properties.json")
+    ap.add_argument("--micro-batches", type=int, default=None, help="gradient accumulation over K micro-batches per step")
+    args = ap.parse_args()
+    with open(args.config) as f:
         cfg = json.load(f)
+    if args.micro_batches is not None:
+        cfg["micro_batches"] = args.micro_batches
     main(cfg)

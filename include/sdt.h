@@ -102,6 +102,17 @@ int sdt_sqnorm_accumulate(const float* g, int64_t n, double* out_sq, void* works
 /* the same over a bf16 gradient buffer (the kernel leaves' gradients, ABI 5): squares of the stored values, exact in double */
 int sdt_sqnorm_accumulate_bf16(const uint16_t* g, int64_t n, double* out_sq, void* workspace, int64_t workspace_bytes, hipStream_t stream);
 int64_t sdt_sqnorm_workspace_bytes(void);
+/* Micro-batch gradient accumulation into an fp32 buffer, element-wise over n, in float32 (ParamStore.accumulate):
+ *   SDT_ACC_INIT acc = widen(g) | SDT_ACC_ADD acc += widen(g) | SDT_ACC_FINISH acc = (acc + widen(g)) * scale | SDT_ACC_SCALE acc *= scale
+ * g: float32 (g_bf16 = 0, 16-byte aligned) or bf16 (g_bf16 = 1, 8-byte aligned); unused (may be NULL) by SDT_ACC_SCALE.  acc: 16-byte
+ * aligned.  out_sq != NULL: *out_sq += sum acc_final^2 in double, bit-identical to sdt_sqnorm_accumulate run over acc afterwards (same
+ * partition and ordered sum); workspace as for sdt_sqnorm_accumulate (may be NULL without out_sq). */
+#define SDT_ACC_INIT 0
+#define SDT_ACC_ADD 1
+#define SDT_ACC_FINISH 2
+#define SDT_ACC_SCALE 3
+int sdt_grad_accumulate(float* acc, const void* g, int g_bf16, int64_t n, int mode, float scale, double* out_sq, void* workspace,
+                        int64_t workspace_bytes, hipStream_t stream);
 /* fused clip(by *sqnorm, may be NULL) + 8-bit blockwise Lion + decay + update (+EMA) (+bf16 mirror of the new parameters,
  * w_bf16[i] = bf16(p[i]), the compute copy the next forward reads; NULL to skip); in place.
  * thresholds: device float[128], the decision thresholds of _quantize (lion_quant.py:52-59): thresholds[c] = the smallest

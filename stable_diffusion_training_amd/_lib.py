@@ -51,6 +51,7 @@ SIGNATURES = {
     "sdt_timestep_embedding": [_P, _P, _I, _I, _I, _F, _P],
     "sdt_sqnorm_accumulate": [_P, _L, _P, _P, _L, _P],
     "sdt_sqnorm_accumulate_bf16": [_P, _L, _P, _P, _L, _P],
+    "sdt_grad_accumulate": [_P, _P, _I, _L, _I, _F, _P, _P, _L, _P],
     "sdt_lion8_step": [_P, _P, _I, _P, _P, _P, _P, _L, _I, _P, _P, _D, _D, _D, _D, _D, _D, _P],
     "sdt_lion32_step": [_P, _P, _P, _P, _P, _L, _P, _D, _D, _D, _D, _D, _D, _P],
     "sdt_lion8_quantize": [_P, _P, _P, _L, _I, _P, _P],

@@ -95,6 +95,79 @@ __global__ void __launch_bounds__(256) sqnorm_kernel(const void* __restrict__ gv
   if (threadIdx.x == 0) *out += (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]);
 }
 
+// Micro-batch gradient accumulation (include/sdt.h sdt_grad_accumulate): acc (fp32) <- init / add / finish / scale of the step's
+// gradient g (bf16 or fp32, widened exactly), element-wise, in one HBM-bound sweep: init 6 B (bf16 g) per element, add and finish
+// 10 B, scale 8 B.  With NORM the sweep also adds sum acc_final^2 to *out exactly as sqnorm_kernel does over the finished buffer -
+// same grid (the caller passes sqnorm_kernel's), same float4 walk and d0 / d1 alternation, same per-workgroup partials and ordered
+// last-arriver sum - so the squared norm is bit-identical to sdt_sqnorm_accumulate run over acc afterwards.
+template <bool G16, int MODE, bool NORM>
+__global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict__ acc, const void* __restrict__ gv, long n, float scale,
+                                                              double* __restrict__ out, int* counter, double* __restrict__ part) {
+  const long nv = n >> 2;
+  double d0 = 0.0, d1 = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+    float4 v = {0.f, 0.f, 0.f, 0.f};
+    if (MODE != SDT_ACC_SCALE) {
+      if (G16) {
+        const uint2 h = reinterpret_cast<const uint2*>(gv)[i];
+        v.x = __uint_as_float(h.x << 16); v.y = __uint_as_float(h.x & 0xffff0000u);
+        v.z = __uint_as_float(h.y << 16); v.w = __uint_as_float(h.y & 0xffff0000u);
+      } else {
+        v = reinterpret_cast<const float4*>(gv)[i];
+      }
+    }
+    if (MODE != SDT_ACC_INIT) {
+      const float4 a = reinterpret_cast<const float4*>(acc)[i];
+      if (MODE == SDT_ACC_SCALE) {
+        v.x = a.x * scale; v.y = a.y * scale; v.z = a.z * scale; v.w = a.w * scale;
+      } else {
+        v.x = a.x + v.x; v.y = a.y + v.y; v.z = a.z + v.z; v.w = a.w + v.w;
+        if (MODE == SDT_ACC_FINISH) {
+          v.x = v.x * scale; v.y = v.y * scale; v.z = v.z * scale; v.w = v.w * scale;
+        }
+      }
+    }
+    reinterpret_cast<float4*>(acc)[i] = v;
+    if (NORM) {
+      d0 = fma((double)v.x, (double)v.x, d0);
+      d1 = fma((double)v.y, (double)v.y, d1);
+      d0 = fma((double)v.z, (double)v.z, d0);
+      d1 = fma((double)v.w, (double)v.w, d1);
+    }
+  }
+  double dacc = d0 + d1;
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // the < 4 elements behind the last float4
+    const long j = (nv << 2) + threadIdx.x;
+    float v = 0.f;
+    if (MODE != SDT_ACC_SCALE) v = G16 ? bf2f(reinterpret_cast<const bf16_t*>(gv)[j]) : reinterpret_cast<const float*>(gv)[j];
+    if (MODE == SDT_ACC_SCALE) v = acc[j] * scale;
+    else if (MODE != SDT_ACC_INIT) v = acc[j] + v;
+    if (MODE == SDT_ACC_FINISH) v = v * scale;
+    acc[j] = v;
+    dacc += (double)v * (double)v;
+  }
+  if (!NORM) return;
+  for (int o = 32; o > 0; o >>= 1) dacc += __shfl_xor(dacc, o, 64);
+  __shared__ double dsc[16];
+  __shared__ int s_last;
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) dsc[w] = dacc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += dsc[i];
+    sdt_store_wt(part + blockIdx.x, t);
+  }
+  if (!sdt_arrive_last<true>(counter, (int)gridDim.x, &s_last)) return;
+  double t = 0.0;
+  for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t += sdt_load_wt(part + i);
+  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) dsc[w] = t;
+  __syncthreads();
+  if (threadIdx.x == 0) *out += (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]);
+}
+
 // *out += sum of n doubles, added in a fixed order (contiguous chunk per workgroup, strided over the threads, the sqnorm_kernel's
 // tree): the squared-norm partials the weight-gradient kernels wrote to their slots (include/sdt.h sdt_gemm_tn_wgrad sq_slots).
 __global__ void __launch_bounds__(256) sum_f64_kernel(const double* __restrict__ x, long n, double* __restrict__ out, int* counter,
@@ -296,6 +369,48 @@ int sdt_sqnorm_accumulate_bf16(const uint16_t* g, int64_t n, double* out_sq, voi
   hipLaunchKernelGGL(sqnorm_kernel<true>, dim3(sdt_grid_1d(n >> 2, 256 * 8, SQNORM_MAX_BLOCKS)), dim3(256), 0, stream, (const void*)g, (long)n, out_sq,
                      reinterpret_cast<int*>(workspace), reinterpret_cast<double*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
   SDT_LAUNCH_CHECK("sdt_sqnorm_accumulate_bf16");
+  return SDT_OK;
+}
+
+int sdt_grad_accumulate(float* acc, const void* g, int g_bf16, int64_t n, int mode, float scale, double* out_sq, void* workspace,
+                        int64_t workspace_bytes, hipStream_t stream) {
+  SDT_CHECK_ARG(mode >= SDT_ACC_INIT && mode <= SDT_ACC_SCALE, "sdt_grad_accumulate: unknown mode %d", mode);
+  SDT_CHECK_ARG(acc && (g || mode == SDT_ACC_SCALE) && n >= 0, "sdt_grad_accumulate: null pointer or negative n");
+  SDT_CHECK_ARG(((uintptr_t)acc & 15) == 0, "sdt_grad_accumulate: acc must be 16-byte aligned");
+  SDT_CHECK_ARG(mode == SDT_ACC_SCALE || ((uintptr_t)g & (g_bf16 ? 7 : 15)) == 0,
+                "sdt_grad_accumulate: g must be %d-byte aligned", g_bf16 ? 8 : 16);
+  SDT_CHECK_ARG(!out_sq || (workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= sdt_sqnorm_workspace_bytes()),
+                "sdt_grad_accumulate: workspace of sdt_sqnorm_workspace_bytes() needed with out_sq");
+  if (n == 0) return SDT_OK;
+  const dim3 grid(sdt_grid_1d(n >> 2, 256 * 8, SQNORM_MAX_BLOCKS)), block(256);  // sqnorm_kernel's grid: the same partition of the norm
+  int* counter = reinterpret_cast<int*>(workspace);
+  double* part = workspace ? reinterpret_cast<double*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES) : nullptr;
+#define LAUNCH_ACC(G, M, N) \
+  hipLaunchKernelGGL((grad_accumulate_kernel<G, M, N>), grid, block, 0, stream, acc, g, (long)n, scale, out_sq, counter, part)
+#define LAUNCH_ACC_N(G, M)   \
+  do {                       \
+    if (out_sq)              \
+      LAUNCH_ACC(G, M, true); \
+    else                     \
+      LAUNCH_ACC(G, M, false); \
+  } while (0)
+#define LAUNCH_ACC_M(G)                                       \
+  do {                                                        \
+    switch (mode) {                                           \
+      case SDT_ACC_INIT: LAUNCH_ACC_N(G, SDT_ACC_INIT); break;     \
+      case SDT_ACC_ADD: LAUNCH_ACC_N(G, SDT_ACC_ADD); break;       \
+      case SDT_ACC_FINISH: LAUNCH_ACC_N(G, SDT_ACC_FINISH); break; \
+      default: LAUNCH_ACC_N(G, SDT_ACC_SCALE); break;              \
+    }                                                         \
+  } while (0)
+  if (g_bf16 && mode != SDT_ACC_SCALE)
+    LAUNCH_ACC_M(true);
+  else
+    LAUNCH_ACC_M(false);
+#undef LAUNCH_ACC_M
+#undef LAUNCH_ACC_N
+#undef LAUNCH_ACC
+  SDT_LAUNCH_CHECK("sdt_grad_accumulate");
   return SDT_OK;
 }
 

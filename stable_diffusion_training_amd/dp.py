@@ -111,6 +111,8 @@ class GradReducer:
         # compute stream's queue (where it would sit behind the whole backward), and the dispatcher favours it
         self.comm_stream = torch.cuda.Stream(priority=-1) if (self.cuda and overlap) else None
         self.capture = None  # an ExchangePlan while a step is being captured
+        self.bucket_bytes = bucket_bytes
+        self.hold = False    # micro-batch accumulation: gradients stay home until exchange_accumulated()
         # sharded optimizer on the device: the all-gather of the bf16 mirrors runs on the communication stream and the NEXT step waits
         # for it only where it first reads trained weights (wait_gathered, behind its VAE encode) - not at the end of this step
         self.defer_gather = self.shard and self.cuda and self.comm_stream is not None and os.environ.get("SDT_DP_DEFER_GATHER", "1") != "0"
@@ -121,7 +123,7 @@ class GradReducer:
     def _make_cb(self, si):
         def cb(path):
             key = (si, path)
-            if key in self._seen or not self.active:
+            if key in self._seen or not self.active or self.hold:
                 return
             self._seen.add(key)
             for bi in self._owner.get(key, ()):
@@ -131,7 +133,10 @@ class GradReducer:
                     self._launch(bk)
         return cb
 
-    def begin_step(self):
+    def begin_step(self, hold=False):
+        """hold: a step that accumulates micro-batches (train_step micro_batches > 1) - no bucket is launched while the backward runs;
+        the fp32 sums are exchanged once, after the last micro-batch (exchange_accumulated)."""
+        self.hold = hold
         self._seen.clear()
         self._handles.clear()
         for bk in self.buckets:
@@ -202,6 +207,44 @@ class GradReducer:
                     view.mul_(inv)
         self._handles.clear()
         self._shard_norms()
+
+    def exchange_accumulated(self):
+        """Micro-batch accumulation: all-reduce (mean over the ranks) every store's fp32 gradient sum ParamStore.gacc in buckets of
+        bucket_bytes, after the last micro-batch's add pass - the float32 exchange the reference's GSPMD all-reduce performs.  Nothing
+        overlaps the backward here (out of scope); captured, graph A ends after the last add pass and the exchange runs between the
+        two graphs like the per-bucket one (run_exchange)."""
+        if not self.active:
+            return
+        if self.shard:
+            raise ValueError("micro-batch accumulation is not supported with the sharded optimizer")
+        items = []
+        for st in self.stores:
+            per = max(self.bucket_bytes // 4, 4) // 4 * 4
+            for a in range(0, st.total, per):
+                b = min(a + per, st.total)
+                items.append((dict(store=st, a=a, b=b, scatter=False), st.gacc[a:b]))
+        if self.capture is not None:  # one completion point for all of them: the end of graph A's last add pass
+            ev = None
+            if self.capture.events:
+                ev = self.capture.new_event()
+                _lib.call("sdt_event_record", ev, 1, torch.cuda.current_stream().cuda_stream)
+            for i, (bk, view) in enumerate(items):
+                self.capture.items.append((ev if i == 0 else None, view, bk))
+            self.capture.split()
+            return
+        cs = self.comm_stream if self.comm_stream is not None else torch.cuda.current_stream()
+        cs.wait_stream(torch.cuda.current_stream())
+        if self.comm_stream is not None:
+            self._stamp_begin()
+        with torch.cuda.stream(cs):
+            handles = [(self._reduce(bk, view), view) for bk, view in items]
+            for h, view in handles:
+                h.wait()
+                if not self.native_avg:
+                    view.mul_(1.0 / self.world)
+        if self.comm_stream is not None:
+            self._stamp_end()
+        torch.cuda.current_stream().wait_stream(cs)
 
     # ---- sharded optimizer: norm of the scattered part, the pieces each rank sweeps, the mirror all-gather, state gather
     def _shard_norms(self):

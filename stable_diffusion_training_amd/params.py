@@ -179,6 +179,11 @@ class ParamStore:
         self.sharded = False
         self.state_whole = True
         self._written = None  # armed by zero_grad(): paths whose gradient has been written this step (note_written)
+        # micro-batch accumulation (accumulate): fp32 sum of the micro-batches' gradients, [0, total) in master order; allocated on the
+        # first step that accumulates (3.9 GB for SD1.5), transient (no checkpoint holds it)
+        self.gacc = None
+        self._acc_norm = False   # the last finish / scale pass left the squared norm of gacc in self.sqnorm
+        self._grad_is_acc = False  # the last optimizer step consumed gacc: exports / grad_norm report it
 
     # ------------------------------------------------------------------ views
     def p(self, path):
@@ -256,6 +261,7 @@ class ParamStore:
         """Write a whole float32 gradient (master order, length `total`): the kernel leaves' part is rounded to bf16 where the store keeps
         it so (tests, host-side gradient injection)."""
         flat = flat.to(self.device)
+        self._grad_is_acc = False
         if self.grad16 is not None:
             self.grad16.copy_(flat[: self.quant_total])
         self.grad[: self.total - self.g32_base].copy_(flat[self.g32_base: self.total])
@@ -270,7 +276,10 @@ class ParamStore:
         return self._whole_grad()
 
     def _whole_grad(self):
-        """The gradient as one float32 buffer in master order (exports / tests): the bf16 part widened exactly."""
+        """The gradient as one float32 buffer in master order (exports / tests): the bf16 part widened exactly.  After an accumulated
+        step: the mean gradient of its micro-batches, the one the optimizer consumed (gacc)."""
+        if self._grad_is_acc:
+            return self.gacc[: self.total]
         if self.grad16 is None:
             return self.grad[: self.total]
         return torch.cat([self.grad16.float(), self.grad[: self.total - self.g32_base]])
@@ -398,7 +407,8 @@ class ParamStore:
     def note_written(self, path):
         """ops reports every gradient leaf its backward kernels have produced.  Kernel / bias gradients are WRITTEN, not
         accumulated (one writer per step, no zero fill): a leaf consumed twice between two zero_grad() calls - tied weights, two
-        text-encoder calls, micro-batch accumulation - would silently keep only its last contribution, so that is refused."""
+        text-encoder calls - would silently keep only its last contribution, so that is refused.  Micro-batches each start with
+        zero_grad() and are summed by accumulate()."""
         w = self._written
         if w is None:
             return
@@ -408,8 +418,8 @@ class ParamStore:
         w.add(path)
 
     def zero_grad(self, everything=False):
-        """Start of a step: clear the accumulated-into leaves (one launch).  everything=True clears the whole buffer.
-        Arms the single-use check (note_written) until the optimizer step."""
+        """Start of a step (of every micro-batch of an accumulated step): clear the accumulated-into leaves (one launch).
+        everything=True clears the whole buffer.  Arms the single-use check (note_written) until the optimizer step."""
         self._written = set()
         if everything:
             self.grad.zero_()
@@ -422,16 +432,51 @@ class ParamStore:
             if n:
                 _lib.call("sdt_zero_ranges", buf.data_ptr(), dev.data_ptr(), n, torch.cuda.current_stream().cuda_stream)
 
-    def optimizer_step(self, *, lr, wd, b1=0.9, b2=0.99, max_norm=1.0, ema_rate=0.0, stream=None, shard=None, sq_partials=None):
+    ACC_MODES = {"init": 0, "add": 1, "finish": 2, "scale": 3}  # include/sdt.h SDT_ACC_*
+
+    def accumulate(self, mode, scale=1.0, norm=False, stream=None):
+        """Micro-batch accumulation of the gradient into gacc (fp32, allocated on first use), one fused pass per buffer:
+        "init" gacc = g, "add" gacc += g, "finish" gacc = (gacc + g) * scale, "scale" gacc *= scale (after a data-parallel exchange of
+        gacc).  norm (finish / scale): self.sqnorm = sum gacc^2, bit-identical to sqnorm_accumulate's pass over gacc - optimizer_step
+        (grad_source="acc") then clips with it and skips its own pass.  Two launches, [0, quant_total) from the bf16 grad16 and
+        [g32_base, total) from the fp32 grad (one over [0, total) when the store keeps every gradient in fp32)."""
+        m = self.ACC_MODES[mode]
+        if norm and mode not in ("finish", "scale"):
+            raise ValueError(f"accumulate: norm needs the final pass (finish / scale), not {mode!r}")
+        s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
+        if self.gacc is None:
+            self.gacc = torch.empty(max(self.total, 4), dtype=torch.float32, device=self.device)
+        sq = None
+        if norm:
+            self.sqnorm.zero_()
+            sq = self.sqnorm.data_ptr()
+        ws = self.sq_ws.data_ptr() if norm else None
+        acc = self.gacc.data_ptr()
+        if self.grad16 is not None and self.quant_total:
+            _lib.call("sdt_grad_accumulate", acc, self.grad16.data_ptr(), 1, self.quant_total, m, scale, sq, ws, self.sq_ws.numel(), s)
+        if self.total > self.g32_base:
+            _lib.call("sdt_grad_accumulate", acc + 4 * self.g32_base, self.grad.data_ptr(), 0, self.total - self.g32_base, m, scale, sq,
+                      ws, self.sq_ws.numel(), s)
+        self._acc_norm = norm
+
+    def optimizer_step(self, *, lr, wd, b1=0.9, b2=0.99, max_norm=1.0, ema_rate=0.0, stream=None, shard=None, sq_partials=None,
+                       grad_source="grad"):
         """clip_by_global_norm(max_norm) -> Lion (8-bit / fp32 momentum) -> decay -> -lr -> apply (-> EMA).
         training_utils.py:379-387 + :732 + :735-746, fused; no host synchronisation (the norm stays on device).
         max_norm None: no clipping (the bare lion_8bit transformation, lion_quant.py:159-211).
         shard: None, or (pieces, sq_done) from dp.GradReducer (sharded optimizer): pieces = [(a, b, quantised, decayed)] element
         ranges this rank updates (its slices of the quantised buckets + the replicated non-quantised segments); sq_done: the
         squared norm of the sharded part is already in self.sqnorm, all-reduced over the ranks - only the replicated part is
-        added here."""
+        added here.
+        grad_source="acc": the step consumes the accumulated gradient gacc (accumulate) instead of grad / grad16; its squared norm is
+        the one the last finish / scale pass computed (or a pass over gacc when that pass ran without norm)."""
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         sq_ptr = None
+        from_acc = grad_source == "acc"
+        if grad_source not in ("grad", "acc"):
+            raise ValueError(f"optimizer_step: grad_source must be 'grad' or 'acc', not {grad_source!r}")
+        if from_acc and (shard is not None or self.gacc is None):
+            raise ValueError("optimizer_step(grad_source='acc'): needs accumulate() first, and the sharded optimizer does not take it")
         if shard is None:
             pieces = [(a, b, q, d) for (q, d, a, b) in self.segments]
             norm_ranges = [(0, self.total)]
@@ -442,7 +487,13 @@ class ParamStore:
         else:
             pieces, _ = shard
             norm_ranges = [(a, b) for (a, b, q, d) in pieces if not q]
-        if max_norm is not None:
+        if max_norm is not None and from_acc:
+            if not self._acc_norm:  # the last accumulate() pass ran without norm
+                self.sqnorm.zero_()
+                _lib.call("sdt_sqnorm_accumulate", self.gacc.data_ptr(), self.total, self.sqnorm.data_ptr(), self.sq_ws.data_ptr(),
+                          self.sq_ws.numel(), s)
+            sq_ptr = self.sqnorm.data_ptr()
+        elif max_norm is not None:
             if shard is None:
                 self.sqnorm.zero_()
                 if sq_partials is not None and sq_partials[1]:
@@ -461,17 +512,23 @@ class ParamStore:
             ema_ptr = self.ema.data_ptr() + 4 * a if ema_on else None
             wd_eff = wd if decay else 0.0
             if quant:
-                g16 = self.grad16 is not None
-                _lib.call("sdt_lion8_step", self.master.data_ptr() + 4 * a, self.grad16.data_ptr() + 2 * a if g16 else self.grad.data_ptr() + 4 * a,
-                          int(g16), self.codes.data_ptr() + a, self.inv_scale.data_ptr() + 4 * (a // self.block_size), ema_ptr,
-                          self.w.data_ptr() + 2 * a, n, self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, lr,
+                g16 = self.grad16 is not None and not from_acc
+                if from_acc:
+                    gp = self.gacc.data_ptr() + 4 * a
+                else:
+                    gp = self.grad16.data_ptr() + 2 * a if g16 else self.grad.data_ptr() + 4 * a
+                _lib.call("sdt_lion8_step", self.master.data_ptr() + 4 * a, gp, int(g16), self.codes.data_ptr() + a,
+                          self.inv_scale.data_ptr() + 4 * (a // self.block_size), ema_ptr, self.w.data_ptr() + 2 * a, n, self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, lr,
                           wd_eff, b1, b2, ema_rate if ema_on else 0.0, s)
             else:
-                _lib.call("sdt_lion32_step", self.master.data_ptr() + 4 * a, self.grad.data_ptr() + 4 * (a - self.g32_base),
+                gp = self.gacc.data_ptr() + 4 * a if from_acc else self.grad.data_ptr() + 4 * (a - self.g32_base)
+                _lib.call("sdt_lion32_step", self.master.data_ptr() + 4 * a, gp,
                           self.mom.data_ptr() + 4 * (a - self.quant_total), ema_ptr, self.w.data_ptr() + 2 * a, n, sq_ptr,
                           max_norm, lr, wd_eff, b1, b2, ema_rate if ema_on else 0.0, s)
         self.count += 1
         self._written = None
+        self._grad_is_acc = from_acc
+        self._acc_norm = False
         if shard is not None and self.sharded:
             self.state_whole = False
 

@@ -184,13 +184,17 @@ _FUSED_NORM = True  # False: always the pass over the gradient buffer (same bits
 def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, batch, train_rng,
                frozen_vae_state, frozen_noise_scheduler_state, strip_bos_eos_token=True, offset_noise_magnitude=0.0,
                min_snr_gamma_magnitude=0.0, perturbation_noise_magnitude=0.0, ema_rate=0.0, *, rand=None, reducer=None,
-               vae_scale=0.18215, aux=None):
+               vae_scale=0.18215, aux=None, micro_batches=1):
     """One DDPM training step on this rank's shard of the batch (training_utils.py:504-762), in place.
 
     batch: {"pixel_values": f32 (B,3,H,W) NCHW device tensor, "input_ids": i32 (B*k,77), "attention_mask": unused}.
     train_rng: a torch.Generator on the device (the reference threads a JAX key; joint distribution only matters).
     rand: optional dict of explicit draws for parity tests (posterior_eps NHWC, noise NCHW, timesteps[, offset_noise,
     perturb_noise]) - the reference's threefry stream is not reproducible outside JAX.
+    micro_batches: K > 1 accumulates the gradient over K micro-batches of len(batch) / K samples (ParamStore.accumulate): each runs
+    the forward and backward on its slice of `batch` and `rand` (without rand=, its draws come from train_rng in the order a plain
+    step of that size takes them), and the optimizer steps once on the fp32 mean - the step over the whole batch, with the
+    activation memory of one micro-batch.  metrics["loss"] is the mean of the micro-batch losses.  K = 1 is the plain step.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
     us, ts = unet_state.store, text_encoder_state.store
     vae_store, vae_cfg = frozen_vae_state.params, frozen_vae_state.call
@@ -198,113 +202,163 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     dev = us.device
     stream = torch.cuda.current_stream().cuda_stream
     rand = rand or {}
-    px = batch["pixel_values"]
-    B, C_in, H, W = px.shape
+    K = micro_batches
+    N = batch["pixel_values"].shape[0]
+    if not isinstance(K, int) or K < 1 or N % K:
+        raise ValueError(f"micro_batches={micro_batches!r} must be a positive integer that divides the batch ({N})")
+    if K > 1 and aux is not None:
+        raise ValueError("aux= taps record a single forward pass: not available with micro_batches > 1")
+    if K > 1 and reducer is not None and reducer.shard:
+        raise ValueError("micro_batches > 1 is not supported with the sharded optimizer (GradReducer(shard=True))")
+    B = N // K
     L = vae_cfg["latent_channels"]
 
-    ops.gn_arena_begin(dev)  # GroupNorm statistics accumulated by producer epilogues: one memset per step
     if reducer is not None:
-        reducer.begin_step()
+        reducer.begin_step(hold=K > 1)  # accumulating: no bucket leaves before the last micro-batch (exchange_accumulated)
 
-    # VAE encode -> posterior sample -> NCHW * 0.18215           (training_utils.py:574-586)
-    pix = torch.empty(B, H, W, 8, dtype=torch.bfloat16, device=dev)
-    _lib.call("sdt_nchw_f32_to_nhwc_bf16", px.data_ptr(), pix.data_ptr(), B, C_in, H, W, 8, stream)
-    with trace.phase("vae_encode"):
-        moments = nets.vae_encode_moments(vae_store, vae_cfg, pix)
-    h, w = moments.shape[1], moments.shape[2]
-    eps = rand.get("posterior_eps")
-    if eps is None:
-        eps = torch.randn(B, h, w, L, device=dev, generator=train_rng)
-    latents = torch.empty(B, L, h, w, dtype=torch.float32, device=dev)
-    _lib.call("sdt_vae_posterior_sample", moments.data_ptr(), eps.data_ptr(), latents.data_ptr(), B, L, h, w,
-              moments.shape[3], vae_scale, stream)
+    def forward_backward(k, fused_norm):
+        """Micro-batch k (the whole batch when K = 1): VAE encode, draws, CLIP, UNet, MSE, backward into grad / grad16.
+        Returns (loss (1,), squared-norm slots of the two stores or None)."""
+        if K == 1:
+            mb, rnd = batch, rand
+        else:
+            sl = slice(k * B, (k + 1) * B)
+            kc = batch["input_ids"].shape[0] // N  # text-encoder rows per sample
+            mb = {n: v[sl] for n, v in batch.items() if n in ("pixel_values", "text_embeds", "time_ids")}
+            mb["input_ids"] = batch["input_ids"][k * B * kc: (k + 1) * B * kc]
+            rnd = {n: v[sl] for n, v in rand.items()}
+        px = mb["pixel_values"]
+        _, C_in, H, W = px.shape
 
-    # The frozen VAE is all the step has read so far: the trained weights are first touched here.  With the sharded optimizer the
-    # all-gather of the bf16 mirrors the previous step's owners wrote is still running beside the VAE encode (dp.GradReducer.wait_gathered)
-    if reducer is not None:
-        reducer.wait_gathered()
-    with trace.phase("prepare_weights"):
-        us.prepare()
-        ts.prepare()
-        us.zero_grad()
-        ts.zero_grad()
+        ops.gn_arena_begin(dev)  # GroupNorm statistics accumulated by producer epilogues: one memset per (micro-)batch
 
-    # noise, timesteps                                            (training_utils.py:590-624)
-    noise = rand.get("noise")
-    if noise is None:
-        noise = torch.randn(B, L, h, w, device=dev, generator=train_rng)
-    if offset_noise_magnitude:
-        off = rand.get("offset_noise")
-        if off is None:
-            off = torch.randn(B, L, 1, 1, device=dev, generator=train_rng)
-        noise = noise + off * offset_noise_magnitude
-    if perturbation_noise_magnitude:
-        pn = rand.get("perturb_noise")
-        if pn is None:
-            pn = torch.randn(B, L, h, w, device=dev, generator=train_rng)
-        noise = noise + perturbation_noise_magnitude * pn
-    noise = noise.contiguous()
-    timesteps = rand.get("timesteps")
-    if timesteps is None:
-        timesteps = torch.randint(0, sched.num_train_timesteps, (B,), device=dev, generator=train_rng)
-    timesteps = timesteps.to(torch.int32).contiguous()
+        # VAE encode -> posterior sample -> NCHW * 0.18215           (training_utils.py:574-586)
+        pix = torch.empty(B, H, W, 8, dtype=torch.bfloat16, device=dev)
+        _lib.call("sdt_nchw_f32_to_nhwc_bf16", px.data_ptr(), pix.data_ptr(), B, C_in, H, W, 8, stream)
+        with trace.phase("vae_encode"):
+            moments = nets.vae_encode_moments(vae_store, vae_cfg, pix)
+        h, w = moments.shape[1], moments.shape[2]
+        eps = rnd.get("posterior_eps")
+        if eps is None:
+            eps = torch.randn(B, h, w, L, device=dev, generator=train_rng)
+        latents = torch.empty(B, L, h, w, dtype=torch.float32, device=dev)
+        _lib.call("sdt_vae_posterior_sample", moments.data_ptr(), eps.data_ptr(), latents.data_ptr(), B, L, h, w,
+                  moments.shape[3], vae_scale, stream)
 
-    # forward diffusion (+ v target)                              (training_utils.py:628-633, 688-701)
-    noisy, target, noisy_nchw = sched.add_noise_and_target(sched_state, latents, noise, timesteps, cpad=8,
-                                                           want_noisy_nchw=aux is not None)
+        # The frozen VAE is all the step has read so far: the trained weights are first touched here.  With the sharded optimizer the
+        # all-gather of the bf16 mirrors the previous step's owners wrote is still running beside the VAE encode (dp.GradReducer.wait_gathered)
+        if k == 0 and reducer is not None:
+            reducer.wait_gathered()
+        with trace.phase("prepare_weights"):
+            if k == 0:
+                us.prepare()
+                ts.prepare()
+            us.zero_grad()
+            ts.zero_grad()
 
-    # text encoder + context assembly                             (training_utils.py:635-674)
-    ids = batch["input_ids"]
-    with trace.phase("text_encoder_forward"):
-        hs = text_encoder_state.apply_fn(ts, text_encoder_state.config, ids if ids.dtype == torch.int32 else ids.to(torch.int32))
-    ctx = assemble_context(hs, B, strip_bos_eos_token)
+        # noise, timesteps                                            (training_utils.py:590-624)
+        noise = rnd.get("noise")
+        if noise is None:
+            noise = torch.randn(B, L, h, w, device=dev, generator=train_rng)
+        if offset_noise_magnitude:
+            off = rnd.get("offset_noise")
+            if off is None:
+                off = torch.randn(B, L, 1, 1, device=dev, generator=train_rng)
+            noise = noise + off * offset_noise_magnitude
+        if perturbation_noise_magnitude:
+            pn = rnd.get("perturb_noise")
+            if pn is None:
+                pn = torch.randn(B, L, h, w, device=dev, generator=train_rng)
+            noise = noise + perturbation_noise_magnitude * pn
+        noise = noise.contiguous()
+        timesteps = rnd.get("timesteps")
+        if timesteps is None:
+            timesteps = torch.randint(0, sched.num_train_timesteps, (B,), device=dev, generator=train_rng)
+        timesteps = timesteps.to(torch.int32).contiguous()
 
-    # UNet                                                        (training_utils.py:678-684)
-    added = None
-    if unet_state.config.get("addition_embed_type") == "text_time":
-        # SDXL micro-conditioning.  Beyond the reference (its call passes no added_cond_kwargs): the batch carries the pooled text
-        # embedding and the six size / crop ids as explicit inputs (SURVEY.md §8(d) note on configs[4])
-        added = {"text_embeds": batch["text_embeds"], "time_ids": batch["time_ids"]}
-    with trace.phase("unet_forward"):
-        pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added)
+        # forward diffusion (+ v target)                              (training_utils.py:628-633, 688-701)
+        noisy, target, noisy_nchw = sched.add_noise_and_target(sched_state, latents, noise, timesteps, cpad=8,
+                                                               want_noisy_nchw=aux is not None)
 
-    # MSE (+ min-SNR), forward and d loss / d pred in one launch  (training_utils.py:704-709)
-    wts = None
-    if min_snr_gamma_magnitude:
-        wts = _min_snr_weights(sched_state, timesteps, min_snr_gamma_magnitude, sched.prediction_type)
-    loss = torch.zeros(1, dtype=torch.float32, device=dev)
-    dpred = torch.empty_like(pred)
-    C_out = unet_state.config["out_channels"]
-    rws = ops.reduce_workspace(_lib.load().sdt_reduce_workspace_bytes(), dev)
-    _lib.call("sdt_mse_loss_fwd_bwd", pred.data_ptr(), target.data_ptr(), None if wts is None else wts.data_ptr(),
-              loss.data_ptr(), dpred.data_ptr(), B, C_out, h, w, pred.shape[3], rws.data_ptr(), rws.numel(), stream)
-    if aux is not None:
-        aux.update(latents=latents, noisy=noisy_nchw, ctx=ctx.detach(), pred=pred.detach(), target=target, moments=moments)
+        # text encoder + context assembly                             (training_utils.py:635-674)
+        ids = mb["input_ids"]
+        with trace.phase("text_encoder_forward"):
+            hs = text_encoder_state.apply_fn(ts, text_encoder_state.config, ids if ids.dtype == torch.int32 else ids.to(torch.int32))
+        ctx = assemble_context(hs, B, strip_bos_eos_token)
 
-    # reverse mode through UNet and text encoder                  (training_utils.py:719-729)
-    # one process: the norm clip_by_global_norm needs is that of the gradients as the weight-gradient kernels write them - they leave
-    # its partial sums behind (ops.sq_begin / sq_end), and the 4-byte-per-parameter pass over the finished buffer is not needed
-    fused_norm = reducer is None and _FUSED_NORM and dev.type == "cuda"
-    if fused_norm:
-        ops.sq_begin(us)
-        ops.sq_begin(ts)
-    with trace.phase("backward_unet_text"), ops.wgrad_grouping():  # Dense weight gradients are issued a dozen per launch
-        pred.backward(dpred)
-    sq_u = ops.sq_end(us) if fused_norm else None
-    sq_t = ops.sq_end(ts) if fused_norm else None
+        # UNet                                                        (training_utils.py:678-684)
+        added = None
+        if unet_state.config.get("addition_embed_type") == "text_time":
+            # SDXL micro-conditioning.  Beyond the reference (its call passes no added_cond_kwargs): the batch carries the pooled text
+            # embedding and the six size / crop ids as explicit inputs (SURVEY.md §8(d) note on configs[4])
+            added = {"text_embeds": mb["text_embeds"], "time_ids": mb["time_ids"]}
+        with trace.phase("unet_forward"):
+            pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added)
 
-    # data-parallel mean of the gradients (implicit all-reduce under GSPMD in the reference)
-    if reducer is not None:
-        with trace.phase("grad_exchange_finish"):
-            reducer.finish()
-            loss = reducer.mean_scalar(loss)
+        # MSE (+ min-SNR), forward and d loss / d pred in one launch  (training_utils.py:704-709)
+        wts = None
+        if min_snr_gamma_magnitude:
+            wts = _min_snr_weights(sched_state, timesteps, min_snr_gamma_magnitude, sched.prediction_type)
+        loss = torch.zeros(1, dtype=torch.float32, device=dev)
+        dpred = torch.empty_like(pred)
+        C_out = unet_state.config["out_channels"]
+        rws = ops.reduce_workspace(_lib.load().sdt_reduce_workspace_bytes(), dev)
+        _lib.call("sdt_mse_loss_fwd_bwd", pred.data_ptr(), target.data_ptr(), None if wts is None else wts.data_ptr(),
+                  loss.data_ptr(), dpred.data_ptr(), B, C_out, h, w, pred.shape[3], rws.data_ptr(), rws.numel(), stream)
+        if aux is not None:
+            aux.update(latents=latents, noisy=noisy_nchw, ctx=ctx.detach(), pred=pred.detach(), target=target, moments=moments)
+
+        # reverse mode through UNet and text encoder                  (training_utils.py:719-729)
+        if fused_norm:
+            ops.sq_begin(us)
+            ops.sq_begin(ts)
+        with trace.phase("backward_unet_text"), ops.wgrad_grouping():  # Dense weight gradients are issued a dozen per launch
+            pred.backward(dpred)
+        sq_u = ops.sq_end(us) if fused_norm else None
+        sq_t = ops.sq_end(ts) if fused_norm else None
+        return loss, sq_u, sq_t
+
+    if K == 1:
+        # one process: the norm clip_by_global_norm needs is that of the gradients as the weight-gradient kernels write them - they leave
+        # its partial sums behind (ops.sq_begin / sq_end), and the 4-byte-per-parameter pass over the finished buffer is not needed
+        loss, sq_u, sq_t = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda")
+        grad_source = "grad"
+        # data-parallel mean of the gradients (implicit all-reduce under GSPMD in the reference)
+        if reducer is not None:
+            with trace.phase("grad_exchange_finish"):
+                reducer.finish()
+                loss = reducer.mean_scalar(loss)
+    else:
+        # K micro-batches summed in fp32 (ParamStore.gacc) and scaled by 1/K: the mean gradient of the whole batch, as the loss is a
+        # per-sample mean and nothing in the VAE / CLIP / UNet mixes samples.  One process: the last pass (finish) also scales and
+        # takes the squared norm.  Data parallel: the last pass is an add, the fp32 sums are all-reduced, then scale + norm.
+        exchange = reducer is not None and reducer.active
+        losses = []
+        for k in range(K):
+            losses.append(forward_backward(k, False)[0])
+            mode = "init" if k == 0 else ("finish" if k == K - 1 and not exchange else "add")
+            with trace.phase("grad_accumulate"):
+                for st in (us, ts):
+                    st.accumulate(mode, 1.0 / K if mode == "finish" else 1.0, norm=mode == "finish")
+        loss = torch.cat(losses).mean(0, keepdim=True)
+        sq_u = sq_t = None
+        grad_source = "acc"
+        if exchange:
+            with trace.phase("grad_exchange_finish"):
+                reducer.exchange_accumulated()
+                loss = reducer.mean_scalar(loss)
+            with trace.phase("grad_accumulate"):
+                for st in (us, ts):
+                    st.accumulate("scale", 1.0 / K, norm=True)
 
     # clip -> Lion(8-bit) -> decay -> -lr -> apply -> EMA         (training_utils.py:732-746)
     ur = ema_rate if (ema_rate and unet_ema_params is not None) else 0.0
     tr = ema_rate if (ema_rate and text_encoder_ema_params is not None) else 0.0
     with trace.phase("optimizer_clip_lion8_ema"):
-        us.optimizer_step(ema_rate=ur, shard=None if reducer is None else reducer.shard_pieces(us), sq_partials=sq_u, **unet_state.hyper)
-        ts.optimizer_step(ema_rate=tr, shard=None if reducer is None else reducer.shard_pieces(ts), sq_partials=sq_t, **text_encoder_state.hyper)
+        us.optimizer_step(ema_rate=ur, shard=None if reducer is None else reducer.shard_pieces(us), sq_partials=sq_u,
+                          grad_source=grad_source, **unet_state.hyper)
+        ts.optimizer_step(ema_rate=tr, shard=None if reducer is None else reducer.shard_pieces(ts), sq_partials=sq_t,
+                          grad_source=grad_source, **text_encoder_state.hyper)
         if reducer is not None:
             reducer.after_optimizer()  # sharded optimizer: all-gather the bf16 weight mirrors the owners have just written
 
@@ -449,14 +503,19 @@ class _GraphedStep:
 
 def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params,
                                      frozen_vae, frozen_schedulers, training_config: TrainingConfig, reducer=None,
-                                     per_device_batch=None, use_graph=None, step_overrides=None):
+                                     per_device_batch=None, use_graph=None, step_overrides=None, micro_batches=1):
     """training_utils.py:765-983: table {pixel_values.shape: step callable}.  Keys are the bucket shapes
     (B, 3, bucket[0], bucket[1]) of every (image_area_root, minimum_axis_length) pair.  Nothing is compiled up front:
     with use_graph (the default; SDT_GRAPH=0 turns it off) each shape captures its step into HIP graphs on its third call:
     one graph for a single process; with an active reducer, graph A (forward + backward) and graph B (optimizer) around
-    the bucketed all-reduce, which stays outside the graphs and overlaps graph A bucket by bucket (dp.ExchangePlan)."""
+    the bucketed all-reduce, which stays outside the graphs and overlaps graph A bucket by bucket (dp.ExchangePlan).
+    micro_batches=K: every step accumulates K micro-batches of per_device_batch (train_step micro_batches); the keys are then the
+    batch the loader delivers, (K * per_device_batch, 3, H, W), and one graph (graph A: through the last micro-batch's add pass, with
+    a reducer) holds all K forward / backward passes."""
     import os
     B = per_device_batch or training_config.batch_size
+    if not isinstance(micro_batches, int) or micro_batches < 1:
+        raise ValueError(f"micro_batches={micro_batches!r} must be a positive integer")
     kw = dict(strip_bos_eos_token=training_config.strip_bos_eos_token,
               offset_noise_magnitude=training_config.offset_noise_magnitude,
               min_snr_gamma_magnitude=training_config.min_snr_gamma_magnitude,
@@ -468,10 +527,10 @@ def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_pa
         use_graph = env != "0" and unet_state.store.device.type == "cuda"
 
     def bound(us, ts, ue, te, batch, rng, vae, sched, **extra):
-        return train_step(us, ts, ue, te, batch, rng, vae, sched, reducer=reducer, **kw, **extra)
+        return train_step(us, ts, ue, te, batch, rng, vae, sched, reducer=reducer, micro_batches=micro_batches, **kw, **extra)
 
     table = {}
     for area_root, min_axis in zip(training_config.image_area_root, training_config.minimum_axis_length):
         for bucket in calculate_resolution_array(area_root ** 2, min_axis, 64):
-            table[(B, 3, int(bucket[0]), int(bucket[1]))] = _GraphedStep(bound, reducer=reducer) if use_graph else bound
+            table[(micro_batches * B, 3, int(bucket[0]), int(bucket[1]))] = _GraphedStep(bound, reducer=reducer) if use_graph else bound
     return table
