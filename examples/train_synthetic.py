@@ -4,7 +4,9 @@ One process per GPU:  python -m torch.distributed.run --nproc-per-node N example
 (single GPU: python examples/train_synthetic.py config.json).  config.json holds the reference's model_properties.json keys
 (model_properties_example.json) plus "batches_per_chunk"; "model_path" is a diffusers-Flax pipeline directory.
 --micro-batches K (or "micro_batches" in the config): every step accumulates the gradient over K micro-batches of
-batch_size / (world * K) samples - the step over the global batch_size with the activation memory of one micro-batch."""
+batch_size / (world * K) samples - the step over the global batch_size with the activation memory of one micro-batch.
+An SDXL directory (text_encoder_2/) trains both text towers in SDXL mode: the loader emits ids for two towers and time_ids, the
+pooled text embedding comes from the towers, and the saves are SDXL pipeline directories."""
 import argparse
 import json
 import os
@@ -16,7 +18,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.distributed as dist
 
-from stable_diffusion_training_amd import dp
+from stable_diffusion_training_amd import dp, nets
 from stable_diffusion_training_amd import training_utils as tu
 from stable_diffusion_training_amd.checkpoint import gather_rng_states
 from stable_diffusion_training_amd.streamer import DataLoader
@@ -46,6 +48,11 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     if models is None:
         models = tu.load_models(training_config)
         tokenizer = models["tokenizer"]
+        if "tokenizer_2" in models:  # SDXL: save_model writes both
+            tokenizer = (tokenizer, models["tokenizer_2"])
+    te_cfg = models["text_encoder"]["config"]
+    sdxl = nets.sdxl_conditioning(te_cfg)  # an SDXL directory: two towers, pooled embedding from the text encoder
+    vocab = te_cfg["towers"][0]["vocab_size"] if "towers" in te_cfg else te_cfg["vocab_size"]
     dataloader = DataLoader(
         tokenizer_obj=tokenizer, config=None, ramdisk_path=config_dict.get("ramdisk_path"),
         training_batch_size=config_dict["batch_size"], repeat_batch=config_dict["repeat_batch"],
@@ -54,8 +61,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         numb_of_worker_thread=config_dict.get("numb_of_dataloader_worker_thread", 1),
         queue_get_timeout=config_dict.get("queue_get_timeout", 60), chunk_number=config_dict["chunk_number"],
         seed=config_dict["master_seed"], context_concatenation_multiplier=config_dict["context_window_concatenation_count"],
-        batches_per_chunk=config_dict.get("batches_per_chunk", 100), vocab_size=models["text_encoder"]["config"]["vocab_size"],
-        rank=rank, world_size=world, device=dev)
+        batches_per_chunk=config_dict.get("batches_per_chunk", 100), vocab_size=vocab,
+        rank=rank, world_size=world, device=dev, text_towers=2 if sdxl else 1)
     dataloader._print_debug = bool(config_dict.get("DEBUG"))
 
     train_rngs = torch.Generator(device=dev)
@@ -65,7 +72,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     reducer = dp.GradReducer([unet_state.store, text_encoder_state.store]) if world > 1 else None
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
-        reducer=reducer, per_device_batch=config_dict["batch_size"] // (world * micro_batches), micro_batches=micro_batches)
+        reducer=reducer, per_device_batch=config_dict["batch_size"] // (world * micro_batches), micro_batches=micro_batches,
+        step_overrides=dict(vae_scale=models["vae"]["config"].get("scaling_factor", 0.13025)) if sdxl else None)
     resume = config_dict.get("resume_training_state")
     if resume and os.path.exists(resume):
         tu.load_training_state(resume, unet_state, text_encoder_state, train_rngs, rank=rank, world=world)
@@ -106,8 +114,9 @@ def main(config_dict, models=None, tokenizer=None, log=print):
             if current_batch is None:
                 continue
             w = config_dict["text_encoder_context_window"]
-            current_batch["input_ids"] = current_batch["input_ids"].reshape(-1, w)
-            current_batch["attention_mask"] = current_batch["attention_mask"].reshape(-1, w)
+            rows = (-1, 2, w) if sdxl else (-1, w)  # SDXL: (B*k, 2, 77), one row of ids per tower
+            current_batch["input_ids"] = current_batch["input_ids"].reshape(rows)
+            current_batch["attention_mask"] = current_batch["attention_mask"].reshape(rows)
             (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, train_metric, train_rngs) = \
                 train_step_funcs[current_batch["pixel_values"].shape](
                     unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, current_batch, train_rngs,

@@ -165,6 +165,18 @@ typedef struct SdtNormGradJob {
 } SdtNormGradJob;
 int sdt_norm_param_grads_group(const SdtNormGradJob* jobs, int n, hipStream_t stream);
 int sdt_norm_param_grads_group_max(void);
+/* CLIP pooled output with its final LayerNorm (transformers CLIPTextTransformer.forward pooling: pooled_output =
+ * last_hidden_state[arange(R), p]; CLIPTextModelWithProjection then applies text_projection to it - SDXL's pooled text embedding).
+ * ids int32 (R*windows, S), x bf16 (R*windows, S, D): the last encoder layer's output BEFORE final_layer_norm.  Pool row r reads
+ * row r*windows (the first caption window of sample r).  p(r): eos_id < 0 - the first position of the largest id (transformers'
+ * rule for configs whose eos_token_id is 2); eos_id >= 0 - the first position where ids == eos_id (0 if there is none).
+ * fwd: pooled bf16 (R, D) = LayerNorm(x[r*windows, p(r)]; gamma, beta, eps) in fp32; mean_rstd f32 (R, 2) and pos int32 (R) are kept
+ * for the backward.  bwd: dx bf16 (R*windows, S, D) is written whole - zero except the pooled positions; dgamma / dbeta (f32 [D]) +=
+ * the sums over the R rows, added in row order by one workgroup (NULL for a frozen norm).  D <= 2048, multiple of 8. */
+int sdt_clip_pool_fwd(const int32_t* ids, const uint16_t* x, const float* gamma, const float* beta, uint16_t* pooled, float* mean_rstd,
+                      int32_t* pos, int R, int windows, int S, int D, int eos_id, float eps, hipStream_t stream);
+int sdt_clip_pool_bwd(const uint16_t* x, const uint16_t* dpooled, const float* gamma, const float* mean_rstd, const int32_t* pos,
+                      uint16_t* dx, float* dgamma, float* dbeta, int R, int windows, int S, int D, hipStream_t stream);
 
 /* ================= dense contractions (flax nn.Dense / nn.Conv and their transposes) */
 /* C[M,N] = A_g[M, taps*Kc] * Bt[N, taps*Kc]^T (+bias[N] f32) (+rowbias[m/rows_per_batch][N] bf16) (+residual).

@@ -61,6 +61,8 @@ SIGNATURES = {
     "sdt_layernorm_fwd": [_P, _P, _P, _P, _P, _L, _I, _F, _P],
     "sdt_layernorm_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _L, _I, _I, _P, _L, _P],
     "sdt_norm_param_grads_group": [_P, _I, _P],
+    "sdt_clip_pool_fwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
+    "sdt_clip_pool_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P],
     "sdt_sum_n_bf16": [_P, _I, _P, _L, _P],
     "sdt_event_create": [_P],
     "sdt_event_destroy": [_P],

@@ -238,21 +238,27 @@ def _model_config(model_object_dict, key):
 
 # ----------------------------------------------------------------------------- the reference's two entry points
 def save_model(model_object_dict, tokenizer_object, unet_params, text_encoder_params, vae_params, output_dir):
-    """training_utils.py:986-1025: write a FlaxStableDiffusionPipeline directory.  The scheduler entry is the reference's
-    hard-coded DDIM placeholder (scaled_linear, v_prediction, :998-1004), whatever the run trained with."""
+    """training_utils.py:986-1025: write a FlaxStableDiffusionPipeline directory (a FlaxStableDiffusionXLPipeline one when the text
+    encoder has two towers: _save_sdxl).  The scheduler entry is the reference's hard-coded DDIM placeholder (scaled_linear,
+    v_prediction, :998-1004), whatever the run trained with."""
     os.makedirs(output_dir, exist_ok=True)
     dv = {"_diffusers_version": DIFFUSERS_VERSION}
     _write_submodel(output_dir, "unet", _model_config(model_object_dict, "unet"),
                     {"_class_name": "FlaxUNet2DConditionModel", **dv}, UNET_WEIGHTS, unet_params)
     _write_submodel(output_dir, "vae", _model_config(model_object_dict, "vae"),
                     {"_class_name": "FlaxAutoencoderKL", **dv}, UNET_WEIGHTS, vae_params)
-    _write_submodel(output_dir, "text_encoder", _model_config(model_object_dict, "text_encoder"),
-                    {"architectures": ["CLIPTextModel"], "model_type": "clip_text_model"}, CLIP_WEIGHTS, text_encoder_params)
+    te_cfg = _model_config(model_object_dict, "text_encoder")
+    if "towers" not in te_cfg:
+        _write_submodel(output_dir, "text_encoder", te_cfg,
+                        {"architectures": ["CLIPTextModel"], "model_type": "clip_text_model"}, CLIP_WEIGHTS, text_encoder_params)
     os.makedirs(os.path.join(output_dir, "scheduler"), exist_ok=True)
     _write_json(os.path.join(output_dir, "scheduler", "scheduler_config.json"),
                 {"_class_name": "FlaxDDIMScheduler", **dv, "beta_start": 0.00085, "beta_end": 0.012,
                  "beta_schedule": "scaled_linear", "num_train_timesteps": 1000, "prediction_type": "v_prediction",
                  "set_alpha_to_one": True, "steps_offset": 0, "trained_betas": None})
+    if "towers" in te_cfg:  # SDXL: the one two-tower store is written as the pipeline's two text encoders
+        _save_sdxl(output_dir, dv, te_cfg, tokenizer_object, text_encoder_params)
+        return
     index = {"_class_name": "FlaxStableDiffusionPipeline", **dv,
              "scheduler": ["diffusers", "FlaxDDIMScheduler"], "text_encoder": ["transformers", "FlaxCLIPTextModel"],
              "tokenizer": ["transformers", "CLIPTokenizer"], "unet": ["diffusers", "FlaxUNet2DConditionModel"],
@@ -265,10 +271,59 @@ def save_model(model_object_dict, tokenizer_object, unet_params, text_encoder_pa
     print("f model saved ")  # the reference's message, verbatim (training_utils.py:1025)
 
 
+# keys of a tower config that describe how this project runs it, not the transformers model: not written to config.json
+_RUN_KEYS = ("hidden_layer", "with_projection")
+SDXL_PIPELINE = "FlaxStableDiffusionXLPipeline"
+
+
+def _tower_json(cfg):
+    return {k: v for k, v in cfg.items() if k not in _RUN_KEYS}
+
+
+def _save_sdxl(output_dir, dv, te_cfg, tokenizer_object, text_encoder_params):
+    """The rest of save_model for a two-tower text encoder: text_encoder/ (CLIPTextModel) and text_encoder_2/
+    (CLIPTextModelWithProjection, with text_projection) split out of the store by their prefixes, and the XL pipeline index.
+    tokenizer_object: None, one tokenizer, or (tokenizer, tokenizer_2)."""
+    tree = params_to_tree(text_encoder_params)
+    index = {"_class_name": SDXL_PIPELINE, **dv, "scheduler": ["diffusers", "FlaxDDIMScheduler"],
+             "unet": ["diffusers", "FlaxUNet2DConditionModel"], "vae": ["diffusers", "FlaxAutoencoderKL"],
+             "tokenizer": ["transformers", "CLIPTokenizer"], "tokenizer_2": ["transformers", "CLIPTokenizer"]}
+    for tower, prefix in zip(te_cfg["towers"], te_cfg["prefixes"]):
+        sub = prefix.rstrip("/")
+        arch = "CLIPTextModelWithProjection" if tower.get("with_projection") else "CLIPTextModel"
+        _write_submodel(output_dir, sub, _tower_json(tower), {"architectures": [arch], "model_type": "clip_text_model"},
+                        CLIP_WEIGHTS, tree[sub])
+        index[sub] = ["transformers", "Flax" + arch]
+    toks = tokenizer_object if isinstance(tokenizer_object, (tuple, list)) else (tokenizer_object, None)
+    for name, tok in zip(("tokenizer", "tokenizer_2"), toks):
+        if tok is not None:
+            tok.save_pretrained(os.path.join(output_dir, name))
+    _write_json(os.path.join(output_dir, "model_index.json"), index)
+    print("f model saved ")
+
+
+def is_sdxl_dir(root):
+    """An SDXL pipeline directory: a text_encoder_2/ sub-folder, or an XL pipeline index."""
+    if os.path.isdir(os.path.join(root, "text_encoder_2")):
+        return True
+    idx = os.path.join(root, "model_index.json")
+    if os.path.exists(idx):
+        with open(idx) as f:
+            return json.load(f).get("_class_name") == SDXL_PIPELINE
+    return False
+
+
+def sdxl_text_config(cfg1, cfg2):
+    """The SDXL-mode two-tower config (nets.dual_clip_config(sdxl_conditioning=True)) of the two text encoders' config.json
+    contents: CLIP-L and bigG with their own widths, activations, projection_dim and eos_token_id."""
+    t1 = {k: v for k, v in cfg1.items() if k not in ("projection_dim", "eos_token_id")}  # CLIP-L: no projection, no pooling
+    return nets.dual_clip_config(t1, dict(cfg2), sdxl_conditioning=True)
+
+
 def load_models(training_config, load_tokenizer=True):
     """training_utils.py:177-250: read the pipeline directory at training_config.model_path.  Returns the dict
     on_device_model_training_state() takes: {"unet": {"unet_params", "config"}, "vae": {...}, "text_encoder": {...},
-    "tokenizer": CLIPTokenizer | None}; parameter trees are flat {"path/with/slashes": float32 tensor} on the host (the
+    "tokenizer": CLIPTokenizer | None} (+ "tokenizer_2" for SDXL); parameter trees are flat {"path/with/slashes": float32 tensor} on the host (the
     reference loads fp32 masters and computes in bf16, :209-222)."""
     root = training_config.model_path
 
@@ -283,14 +338,26 @@ def load_models(training_config, load_tokenizer=True):
     unet_cfg = _read_config(os.path.join(root, "unet", "config.json"), nets._UNET_DEFAULTS)
     vae_cfg = _read_config(os.path.join(root, "vae", "config.json"))
     clip_cfg = _read_config(os.path.join(root, "text_encoder", "config.json"))
-    tokenizer = None
+    te_params = weights("text_encoder", CLIP_WEIGHTS)
+    sdxl = is_sdxl_dir(root)
+    if sdxl:  # both towers in one store, under the sub-folder names (nets.dual_clip_config), in SDXL mode
+        clip_cfg = sdxl_text_config(clip_cfg, _read_config(os.path.join(root, "text_encoder_2", "config.json")))
+        te_params = {**{"text_encoder/" + p: v for p, v in te_params.items()},
+                     **{"text_encoder_2/" + p: v for p, v in weights("text_encoder_2", CLIP_WEIGHTS).items()}}
+    tokenizer = tokenizer_2 = None
     if load_tokenizer and os.path.isdir(os.path.join(root, "tokenizer")):
         from transformers import CLIPTokenizer
         tokenizer = CLIPTokenizer.from_pretrained(root, subfolder="tokenizer")
-    return {"unet": {"unet_params": weights("unet", UNET_WEIGHTS), "config": unet_cfg},
-            "vae": {"vae_params": weights("vae", UNET_WEIGHTS), "config": vae_cfg},
-            "text_encoder": {"text_encoder_params": weights("text_encoder", CLIP_WEIGHTS), "config": clip_cfg},
-            "tokenizer": tokenizer}
+    if load_tokenizer and sdxl and os.path.isdir(os.path.join(root, "tokenizer_2")):
+        from transformers import CLIPTokenizer
+        tokenizer_2 = CLIPTokenizer.from_pretrained(root, subfolder="tokenizer_2")
+    out = {"unet": {"unet_params": weights("unet", UNET_WEIGHTS), "config": unet_cfg},
+           "vae": {"vae_params": weights("vae", UNET_WEIGHTS), "config": vae_cfg},
+           "text_encoder": {"text_encoder_params": te_params, "config": clip_cfg},
+           "tokenizer": tokenizer}
+    if sdxl:
+        out["tokenizer_2"] = tokenizer_2
+    return out
 
 
 # ----------------------------------------------------------------------------- optimizer / RNG state (not in the reference)

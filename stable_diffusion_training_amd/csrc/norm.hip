@@ -596,6 +596,153 @@ __global__ void __launch_bounds__(256) partial_reduce_group_kernel(const PrGroup
   partial_rows_reduce<LN_PR_COLS>(gp.partial[lo], gp.dgamma[lo], gp.dbeta[lo], gp.nrows[lo], gp.C[lo], local, red);
 }
 
+// ---------------------------------------------------------------- CLIP pooled output (final LayerNorm at the EOS token)
+// transformers CLIPTextTransformer: pooled = final_layer_norm(x)[r, p(r)], p(r) = argmax(ids[r]) (configs with eos_token_id == 2) or
+// the first position holding eos_token_id.  LayerNorm is row-wise, so only the R pooled rows are normalised.  One wave per pooled row;
+// the row of x that pool row r reads is r * win (win = caption windows per sample: the first window of each sample is pooled).
+__device__ __forceinline__ int clip_pool_position(const int* __restrict__ ids, int S, int eos_id) {
+  const int lane = threadIdx.x & 63;
+  int best = 0x7fffffff, bval = -0x7fffffff - 1;  // (value, position): the first occurrence of the key that wins
+  for (int s = lane; s < S; s += 64) {
+    const int v = ids[s];
+    if (eos_id < 0) {
+      if (v > bval) { bval = v; best = s; }  // s increases: ties keep the earlier position
+    } else if (v == eos_id && s < best) {
+      best = s;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const int ov = __shfl_xor(bval, o, 64), op = __shfl_xor(best, o, 64);
+    if (eos_id < 0) {
+      if (ov > bval || (ov == bval && op < best)) { bval = ov; best = op; }
+    } else if (op < best) {
+      best = op;
+    }
+  }
+  return best == 0x7fffffff ? 0 : best;  // no EOS in the row: position 0, as argmax over an all-false mask
+}
+
+__global__ void __launch_bounds__(64) clip_pool_fwd_kernel(const int* __restrict__ ids, const bf16_t* __restrict__ x,
+                                                           const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                           bf16_t* __restrict__ pooled, float* __restrict__ mean_rstd,
+                                                           int* __restrict__ pos, int win, int S, int D, int eos_id, float eps) {
+  const int r = blockIdx.x, lane = threadIdx.x;
+  const long row = (long)r * win;
+  const int p = clip_pool_position(ids + row * S, S, eos_id);
+  const bf16_t* xr = x + (row * S + p) * D;
+  const int Dv = D >> 3;
+  float f[LN_MAXV][8];
+  float s = 0.f;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) {
+    const int cv = lane + 64 * j;
+    if (cv < Dv) {
+      unpack8(*reinterpret_cast<const uint4*>(xr + cv * 8), f[j]);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) s += f[j][e];
+    }
+  }
+  const float mean = wave_sum(s) / D;
+  float q = 0.f;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) {
+    if (lane + 64 * j < Dv) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float d = f[j][e] - mean; q += d * d; }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(q) / D + eps);
+  if (lane == 0) {
+    mean_rstd[2 * r] = mean;
+    mean_rstd[2 * r + 1] = rstd;
+    pos[r] = p;
+  }
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) {
+    const int cv = lane + 64 * j;
+    if (cv < Dv) {
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = (f[j][e] - mean) * rstd * gamma[cv * 8 + e] + beta[cv * 8 + e];
+      *reinterpret_cast<uint4*>(pooled + (long)r * D + cv * 8) = pack8(o);
+    }
+  }
+}
+
+// dx over the whole (R*win, S, D) input: zero except row (r*win, p(r)), which gets the LayerNorm backward of dpooled[r].
+// Workgroup = one (row, 8-position slab); waves of 64 lanes stride the slab's D/8 vectors.
+#define CP_SLAB 8
+__global__ void __launch_bounds__(256) clip_pool_dx_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dpooled,
+                                                           const float* __restrict__ gamma, const float* __restrict__ mean_rstd,
+                                                           const int* __restrict__ pos, bf16_t* __restrict__ dx, int win, int S,
+                                                           int D) {
+  const int row = blockIdx.y, s0 = blockIdx.x * CP_SLAB;
+  const int Dv = D >> 3;
+  const bool pooled_row = row % win == 0;
+  const int r = row / win;
+  const int p = pooled_row ? pos[r] : -1;
+  const uint4 zero = make_uint4(0u, 0u, 0u, 0u);
+  for (int s = s0; s < s0 + CP_SLAB && s < S; ++s) {
+    if (s == p) continue;
+    bf16_t* d = dx + ((long)row * S + s) * D;
+    for (int cv = threadIdx.x; cv < Dv; cv += 256) *reinterpret_cast<uint4*>(d + cv * 8) = zero;
+  }
+  if (p < s0 || p >= s0 + CP_SLAB || threadIdx.x >= 64) return;
+  // wave 0: LayerNorm backward of the pooled row, dx = rstd * (g - mean(g) - xhat * mean(g * xhat)), g = dy * gamma
+  const int lane = threadIdx.x;
+  const bf16_t* xr = x + ((long)row * S + p) * D;
+  const float mean = mean_rstd[2 * r], rstd = mean_rstd[2 * r + 1];
+  float xh[LN_MAXV][8], g[LN_MAXV][8];
+  float sg = 0.f, sgx = 0.f;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) {
+    const int cv = lane + 64 * j;
+    if (cv < Dv) {
+      float dy[8];
+      unpack8(*reinterpret_cast<const uint4*>(xr + cv * 8), xh[j]);
+      unpack8(*reinterpret_cast<const uint4*>(dpooled + (long)r * D + cv * 8), dy);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        xh[j][e] = (xh[j][e] - mean) * rstd;
+        g[j][e] = dy[e] * gamma[cv * 8 + e];
+        sg += g[j][e];
+        sgx += g[j][e] * xh[j][e];
+      }
+    }
+  }
+  const float mg = wave_sum(sg) / D, mgx = wave_sum(sgx) / D;
+#pragma unroll
+  for (int j = 0; j < LN_MAXV; ++j) {
+    const int cv = lane + 64 * j;
+    if (cv < Dv) {
+      float o[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) o[e] = rstd * (g[j][e] - mg - xh[j][e] * mgx);
+      *reinterpret_cast<uint4*>(dx + ((long)row * S + p) * D + cv * 8) = pack8(o);
+    }
+  }
+}
+
+// dgamma[c] += sum_r dpooled[r][c] * xhat[r][c], dbeta[c] += sum_r dpooled[r][c]: ONE workgroup, one thread per column, the R pooled
+// rows added in order r = 0, 1, ... (R = batch x 1 is small): no cross-workgroup sum, bitwise reproducible.
+__global__ void __launch_bounds__(256) clip_pool_param_grad_kernel(const bf16_t* __restrict__ x, const bf16_t* __restrict__ dpooled,
+                                                                   const float* __restrict__ mean_rstd, const int* __restrict__ pos,
+                                                                   float* __restrict__ dgamma, float* __restrict__ dbeta, int R,
+                                                                   int win, int S, int D) {
+  for (int c = threadIdx.x; c < D; c += 256) {
+    float sg = 0.f, sb = 0.f;
+    for (int r = 0; r < R; ++r) {
+      const float dy = bf2f(dpooled[(long)r * D + c]);
+      const float xv = bf2f(x[(((long)r * win) * S + pos[r]) * D + c]);
+      sg += dy * ((xv - mean_rstd[2 * r]) * mean_rstd[2 * r + 1]);
+      sb += dy;
+    }
+    dgamma[c] += sg;
+    dbeta[c] += sb;
+  }
+}
+
 // ================================================================== C ABI
 // pixel rows per block for `total_blocks` blocks over the batch, but at least two row-iterations per thread (TY rows are in flight
 // per iteration); low-resolution, wide-channel tensors (8x8x1280) are latency-bound, so they get many small blocks
@@ -785,6 +932,34 @@ int sdt_norm_param_grads_group(const SdtNormGradJob* jobs, int n, hipStream_t st
   }
   hipLaunchKernelGGL(partial_reduce_group_kernel, dim3(wg), dim3(256), 0, stream, gp);
   SDT_LAUNCH_CHECK("sdt_norm_param_grads_group");
+  return SDT_OK;
+}
+
+int sdt_clip_pool_fwd(const int32_t* ids, const uint16_t* x, const float* gamma, const float* beta, uint16_t* pooled, float* mean_rstd,
+                      int32_t* pos, int R, int windows, int S, int D, int eos_id, float eps, hipStream_t stream) {
+  SDT_CHECK_ARG(ids && x && gamma && beta && pooled && mean_rstd && pos, "sdt_clip_pool_fwd: null pointer");
+  SDT_CHECK_ARG(R >= 1 && windows >= 1 && S >= 1 && R <= 65535, "sdt_clip_pool_fwd: bad shape R=%d windows=%d S=%d", R, windows, S);
+  SDT_CHECK_ARG(D > 0 && D % 8 == 0 && D <= 8 * 64 * LN_MAXV, "sdt_clip_pool_fwd: D=%d must be a multiple of 8 and <= %d", D, 8 * 64 * LN_MAXV);
+  SDT_CHECK_ARG((((uintptr_t)x | (uintptr_t)pooled) & 15) == 0, "sdt_clip_pool_fwd: misaligned pointer");
+  hipLaunchKernelGGL(clip_pool_fwd_kernel, dim3(R), dim3(64), 0, stream, (const int*)ids, (const bf16_t*)x, gamma, beta,
+                     (bf16_t*)pooled, mean_rstd, (int*)pos, windows, S, D, eos_id, eps);
+  SDT_LAUNCH_CHECK("sdt_clip_pool_fwd");
+  return SDT_OK;
+}
+
+int sdt_clip_pool_bwd(const uint16_t* x, const uint16_t* dpooled, const float* gamma, const float* mean_rstd, const int32_t* pos,
+                      uint16_t* dx, float* dgamma, float* dbeta, int R, int windows, int S, int D, hipStream_t stream) {
+  SDT_CHECK_ARG(x && dpooled && gamma && mean_rstd && pos && dx && ((dgamma == nullptr) == (dbeta == nullptr)),
+                "sdt_clip_pool_bwd: null pointer");
+  SDT_CHECK_ARG(R >= 1 && windows >= 1 && S >= 1 && (long)R * windows <= 65535, "sdt_clip_pool_bwd: bad shape R=%d windows=%d S=%d", R, windows, S);
+  SDT_CHECK_ARG(D > 0 && D % 8 == 0 && D <= 8 * 64 * LN_MAXV, "sdt_clip_pool_bwd: D=%d must be a multiple of 8 and <= %d", D, 8 * 64 * LN_MAXV);
+  SDT_CHECK_ARG((((uintptr_t)x | (uintptr_t)dpooled | (uintptr_t)dx) & 15) == 0, "sdt_clip_pool_bwd: misaligned pointer");
+  hipLaunchKernelGGL(clip_pool_dx_kernel, dim3(sdt_ceil_div(S, CP_SLAB), R * windows), dim3(256), 0, stream, (const bf16_t*)x,
+                     (const bf16_t*)dpooled, gamma, mean_rstd, (const int*)pos, (bf16_t*)dx, windows, S, D);
+  if (dgamma)
+    hipLaunchKernelGGL(clip_pool_param_grad_kernel, dim3(1), dim3(256), 0, stream, (const bf16_t*)x, (const bf16_t*)dpooled, mean_rstd,
+                       (const int*)pos, dgamma, dbeta, R, windows, S, D);
+  SDT_LAUNCH_CHECK("sdt_clip_pool_bwd");
   return SDT_OK;
 }
 

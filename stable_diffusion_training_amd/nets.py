@@ -266,15 +266,61 @@ def clip_text_spec(cfg, prefix=""):
         s.dense(b + "/mlp/fc1", d, f)
         s.dense(b + "/mlp/fc2", f, d)
     s.norm(prefix + "text_model/final_layer_norm", d)
+    if cfg.get("with_projection"):  # transformers FlaxCLIPTextModelWithProjection: Dense(projection_dim, use_bias=False)
+        s.dense(prefix + "text_projection", d, cfg["projection_dim"], bias=False)
     return list(s)
 
 
-def dual_clip_config(first="clip_l", second="openclip_bigg"):
+def dual_clip_config(first="clip_l", second="openclip_bigg", sdxl_conditioning=False):
     """SDXL conditions its UNet on the hidden states of two text towers concatenated along the feature axis (768 + 1280 = 2048 =
     cross_attention_dim).  The reference's train_step holds ONE text-encoder state (training_utils.py:635-640) and cannot drive
     SDXL (SURVEY.md §8(d) note); here both towers live in one parameter store under the diffusers sub-folder names, so the
-    step's signature, optimizer sweep and gradient exchange are unchanged."""
-    return dict(towers=[clip_config(first), clip_config(second)], prefixes=["text_encoder/", "text_encoder_2/"])
+    step's signature, optimizer sweep and gradient exchange are unchanged.  first / second: CLIP_CONFIGS names or config dicts.
+
+    sdxl_conditioning=True: SDXL's own conditioning (sdxl_text_forward).  Each tower's context is hidden_states[-2] (hidden_layer=-2:
+    the residual stream entering the last layer, no final LayerNorm), and the second tower also yields the pooled text embedding,
+    text_projection(final_layer_norm(x) at the EOS token) - it gains the text_projection leaf (with_projection, projection_dim =
+    its width unless given) and eos_token_id (2 unless given: the argmax rule of SDXL's released configs)."""
+    towers = [dict(t) if isinstance(t, dict) else clip_config(t) for t in (first, second)]
+    cfg = dict(towers=towers, prefixes=["text_encoder/", "text_encoder_2/"])
+    if sdxl_conditioning:
+        for t in towers:
+            t["hidden_layer"] = -2
+        towers[1]["with_projection"] = True
+        towers[1].setdefault("projection_dim", towers[1]["hidden_size"])
+        towers[1].setdefault("eos_token_id", 2)
+        cfg["sdxl_conditioning"] = True
+    return cfg
+
+
+def sdxl_conditioning(cfg):
+    """True for a two-tower text-encoder config in SDXL mode (dual_clip_config(sdxl_conditioning=True), or an SDXL checkpoint)."""
+    return bool(cfg.get("sdxl_conditioning")) and "towers" in cfg
+
+
+def _context_layers(tower):
+    """Encoder layers the context passes through: hidden_states[hidden_layer] (hidden_states[0] is the embedding output)."""
+    n = tower["num_hidden_layers"]
+    hl = tower.get("hidden_layer", -1)
+    k = n + 1 + hl if hl < 0 else hl
+    if not 1 <= k <= n:
+        raise ValueError(f"hidden_layer={hl} selects no encoder layer of a {n}-layer tower")
+    return k
+
+
+def unused_text_leaves(cfg):
+    """Leaves an SDXL-mode forward never reads: the layers after the context of a tower without the pooled output, and that tower's
+    final LayerNorm (CLIP-L).  Their gradients must be zero every step (ParamStore.mark_unused)."""
+    if not sdxl_conditioning(cfg):
+        return []
+    out = []
+    for t, pre in zip(cfg["towers"], cfg["prefixes"]):
+        if t.get("with_projection"):
+            continue
+        k = _context_layers(t)
+        dead = tuple(f"{pre}text_model/encoder/layers/{i}/" for i in range(k, t["num_hidden_layers"])) + (pre + "text_model/final_layer_norm/",)
+        out += [p for p, _ in clip_text_spec(t, pre) if p.startswith(dead)]
+    return out
 
 
 def init_params(spec, seed=0):
@@ -550,6 +596,13 @@ def clip_text_forward(st, cfg, input_ids, anchor=None, prefix=""):
     if "towers" in cfg:
         hs = [clip_text_forward(st, c, input_ids[:, i].contiguous(), anchor, cfg["prefixes"][i]) for i, c in enumerate(cfg["towers"])]
         return ops.concat_channels(hs[0], hs[1])
+    x, _ = _clip_encoder(st, cfg, input_ids, anchor, prefix, cfg["num_hidden_layers"])
+    return ops.layer_norm(x, st, prefix + "text_model/final_layer_norm", cfg["layer_norm_eps"])
+
+
+def _clip_encoder(st, cfg, input_ids, anchor, prefix, n_layers, tap=None):
+    """Embeddings and the first n_layers encoder layers.  tap = k: also returns an alias of the residual stream after k layers
+    (hidden_states[k]; ops.fanout sums the two gradients), else None."""
     Bk, S = input_ids.shape
     d, heads, eps = cfg["hidden_size"], cfg["num_attention_heads"], cfg["layer_norm_eps"]
     if anchor is None:
@@ -557,7 +610,10 @@ def clip_text_forward(st, cfg, input_ids, anchor=None, prefix=""):
     x = ops.embedding(input_ids.contiguous(), st, prefix + "text_model/embeddings/token_embedding/embedding",
                       prefix + "text_model/embeddings/position_embedding/embedding", S, anchor)
     act = ops.quick_gelu if cfg["hidden_act"] == "quick_gelu" else ops.gelu_erf
-    for i in range(cfg["num_hidden_layers"]):
+    tapped = None
+    for i in range(n_layers):
+        if i == tap:
+            x, tapped = ops.fanout(x, 2)
         L = f"{prefix}text_model/encoder/layers/{i}"
         h, x = ops.layer_norm(x, st, L + "/layer_norm1", eps, skip=True)
         qkv = ops.linear_multi(h, st, tuple(f"{L}/self_attn/{n}" for n in ("q_proj", "k_proj", "v_proj")))
@@ -569,4 +625,38 @@ def clip_text_forward(st, cfg, input_ids, anchor=None, prefix=""):
         x = ops.linear(o, st, L + "/self_attn/out_proj", residual=x)
         h, x = ops.layer_norm(x, st, L + "/layer_norm2", eps, skip=True)
         x = ops.linear(act(ops.linear(h, st, L + "/mlp/fc1")), st, L + "/mlp/fc2", residual=x)
-    return ops.layer_norm(x, st, prefix + "text_model/final_layer_norm", eps)
+    if tap == n_layers:
+        tapped = x
+    return x, tapped
+
+
+def sdxl_text_forward(st, cfg, input_ids, windows=1, anchor=None):
+    """SDXL's text conditioning (diffusers StableDiffusionXLPipeline.encode_prompt; the original SDXL trainer's embedders) on a
+    dual_clip_config(sdxl_conditioning=True) store.  input_ids int32 (B*windows, 2, S), one row of ids per tower.
+    Returns (context (B*windows, S, D1 + D2) bf16, pooled (B, projection_dim) bf16):
+      * context: each tower's hidden_states[hidden_layer] (-2: the input of its last layer, no final LayerNorm), concatenated;
+      * pooled: the second tower's text_projection(final_layer_norm(last layer output) at the EOS token) of the FIRST caption
+        window of each sample (ops.clip_pool; eos_token_id == 2 selects the first largest id, as transformers does).
+    The first tower stops at its context: its later layers and final LayerNorm are not run (unused_text_leaves)."""
+    if not sdxl_conditioning(cfg):
+        raise ValueError("sdxl_text_forward needs a two-tower config in SDXL mode (dual_clip_config(..., sdxl_conditioning=True))")
+    if input_ids.dim() != 3 or input_ids.shape[1] != 2 or input_ids.shape[0] % windows:
+        raise ValueError(f"input_ids must be (B*{windows}, 2, S), got {tuple(input_ids.shape)}")
+    if hasattr(st, "mark_unused"):
+        st.mark_unused(unused_text_leaves(cfg))
+    ctxs, pooled = [], None
+    for i, (t, pre) in enumerate(zip(cfg["towers"], cfg["prefixes"])):
+        ids = input_ids[:, i].contiguous()
+        k = _context_layers(t)
+        if not t.get("with_projection"):
+            x, _ = _clip_encoder(st, t, ids, anchor, pre, k)
+            ctxs.append(x)
+            continue
+        x, c = _clip_encoder(st, t, ids, anchor, pre, t["num_hidden_layers"], tap=k)
+        ctxs.append(c)
+        eos = t.get("eos_token_id", 2)
+        p, _ = ops.clip_pool(x, ids, st, pre + "text_model/final_layer_norm", -1 if eos == 2 else eos, t["layer_norm_eps"], windows)
+        pooled = ops.linear(p, st, pre + "text_projection")
+    if pooled is None:
+        raise ValueError("SDXL mode: one tower must carry the text projection (with_projection)")
+    return ops.concat_channels(ctxs[0], ctxs[1]), pooled

@@ -718,6 +718,54 @@ def layer_norm(x, store, name, eps=1e-5, skip=False):
     return _LayerNorm.apply(x, store, name, eps, skip)
 
 
+class _ClipPool(Function):
+    """CLIP's pooled output: the final LayerNorm `name` applied to the EOS-token row of x only (sdt_clip_pool_fwd / _bwd)."""
+
+    @staticmethod
+    def forward(ctx, x, ids, store, name, eos_id, eps, windows):
+        _check(x, "clip_pool input")
+        rows, S, D = x.shape
+        if ids.dtype != torch.int32 or not ids.is_contiguous() or tuple(ids.shape) != (rows, S):
+            raise _lib.SdtError(f"clip_pool: ids must be contiguous int32 {(rows, S)}, got {ids.dtype} {tuple(ids.shape)}")
+        if rows % windows:
+            raise _lib.SdtError(f"clip_pool: {rows} rows are not a whole number of {windows}-window samples")
+        R = rows // windows
+        pooled = torch.empty(R, D, dtype=BF16, device=x.device)
+        mr = torch.empty(R, 2, dtype=torch.float32, device=x.device)
+        pos = torch.empty(R, dtype=torch.int32, device=x.device)
+        call("sdt_clip_pool_fwd", ids.data_ptr(), x.data_ptr(), store.p(name + "/scale").data_ptr(), store.p(name + "/bias").data_ptr(),
+             pooled.data_ptr(), mr.data_ptr(), pos.data_ptr(), R, windows, S, D, int(eos_id), float(eps), _stream())
+        ctx.save_for_backward(x, mr, pos)
+        ctx.meta = (store, name, R, windows)
+        ctx.mark_non_differentiable(pos)
+        ctx.set_materialize_grads(False)
+        return pooled, pos
+
+    @staticmethod
+    def backward(ctx, dpooled, dpos=None):
+        x, mr, pos = ctx.saved_tensors
+        store, name, R, windows = ctx.meta
+        if dpooled is None:
+            return None, None, None, None, None, None, None
+        dpooled = dpooled.contiguous()
+        _, S, D = x.shape
+        dx = torch.empty_like(x)
+        dg = store.g(name + "/scale").data_ptr() if store.trainable else None
+        db = store.g(name + "/bias").data_ptr() if store.trainable else None
+        call("sdt_clip_pool_bwd", x.data_ptr(), dpooled.data_ptr(), store.p(name + "/scale").data_ptr(), mr.data_ptr(), pos.data_ptr(),
+             dx.data_ptr(), dg, db, R, windows, S, D, _stream())
+        if store.trainable:
+            _ready(store, name + "/scale", name + "/bias")
+        return dx, None, None, None, None, None, None
+
+
+def clip_pool(x, ids, store, name, eos_id, eps=1e-5, windows=1):
+    """x (R*windows, S, D) bf16: the last encoder layer's output; ids int32 (R*windows, S).  Returns (pooled (R, D) bf16, positions
+    int32 (R,)): LayerNorm `name` (its dgamma / dbeta are added into the store's gradient) of row r*windows at its EOS position -
+    eos_id < 0: the first largest id (transformers' rule for eos_token_id == 2), else the first id equal to eos_id."""
+    return _ClipPool.apply(x, ids, store, name, eos_id, eps, windows)
+
+
 class _Fanout(Function):
     """n aliases of x for n consumers; the n gradients are summed by ONE launch (fp32 accumulation) instead of the
     autograd engine's chain of n-1 binary adds."""

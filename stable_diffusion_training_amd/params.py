@@ -179,6 +179,7 @@ class ParamStore:
         self.sharded = False
         self.state_whole = True
         self._written = None  # armed by zero_grad(): paths whose gradient has been written this step (note_written)
+        self._unused = set()  # leaves no backward writes (mark_unused): cleared with the accumulated-into leaves every step
         # micro-batch accumulation (accumulate): fp32 sum of the micro-batches' gradients, [0, total) in master order; allocated on the
         # first step that accumulates (3.9 GB for SD1.5), transient (no checkpoint holds it)
         self.gacc = None
@@ -371,10 +372,10 @@ class ParamStore:
         fill per step."""
         written = set()
         for p, lf in self.leaves.items():
-            if lf.w_off >= 0:
+            if lf.w_off >= 0 and p not in self._unused:
                 written.add(p)
                 b = p[: -len("kernel")] + "bias"
-                if b in self.leaves:
+                if b in self.leaves and b not in self._unused:
                     written.add(b)
         # everything that is not a written leaf: accumulated-into leaves AND the alignment gaps between leaves (the global-norm
         # and optimizer sweeps run over whole segments, gaps included, so gaps must hold zeros whatever the buffer held before)
@@ -403,6 +404,19 @@ class ParamStore:
                         flat += [c, min(chunk, ub - c)]
             tables.append((buf, torch.tensor(flat, dtype=torch.int64).to(self.device) if flat else None, len(flat) // 2))
         self._zero = tables
+
+    def mark_unused(self, paths):
+        """Leaves the forward never reads (an SDXL-mode text encoder stops CLIP-L before its last layer: nets.unused_text_leaves).
+        No kernel writes their gradients, so zero_grad() clears them with the accumulated-into leaves and they stay exactly zero;
+        newly marked leaves are cleared at once.  Idempotent."""
+        new = [p for p in paths if p not in self._unused]
+        if not new:
+            return
+        self._unused.update(new)
+        self._zero = None
+        if self.grad is not None:
+            for p in new:
+                self.g(p).zero_()
 
     def note_written(self, path):
         """ops reports every gradient leaf its backward kernels have produced.  Kernel / bias gradients are WRITTEN, not

@@ -46,10 +46,37 @@ class StableDiffusionPipeline:
         ids[:, 0] = v - 2
         return ids
 
+    def _sdxl_conditioning(self, prompt_ids, neg_prompt_ids, height, width):
+        """SDXL (diffusers StableDiffusionXLPipeline.encode_prompt / _get_add_time_ids): prompt_ids (B, 2, 77) through the SDXL-mode
+        text encoder (nets.sdxl_text_forward) -> context [negative | prompt] and added_cond {text_embeds: pooled, time_ids: (H, W, 0, 0,
+        H, W)} for the doubled batch.  neg_prompt_ids None: the negative context and pooled embedding are zeros
+        (force_zeros_for_empty_prompt, the SDXL base default)."""
+        dev = self.device
+        B = prompt_ids.shape[0]
+        if prompt_ids.dim() != 3 or prompt_ids.shape[1] != 2:
+            raise ValueError(f"SDXL prompt_ids must be (B, 2, 77), one row per text tower; got {tuple(prompt_ids.shape)}")
+        self.unet.prepare()
+        self.text_encoder.prepare()
+        ids = prompt_ids.to(device=dev, dtype=torch.int32)
+        if neg_prompt_ids is not None:
+            ids = torch.cat([neg_prompt_ids.to(device=dev, dtype=torch.int32), ids])
+        ctx, pooled = nets.sdxl_text_forward(self.text_encoder, self.text_encoder_config, ids.contiguous())
+        if neg_prompt_ids is None:
+            zc = torch.zeros(2 * B, *ctx.shape[1:], dtype=ctx.dtype, device=dev)
+            zp = torch.zeros(2 * B, *pooled.shape[1:], dtype=pooled.dtype, device=dev)
+            zc[B:].copy_(ctx)
+            zp[B:].copy_(pooled)
+            ctx, pooled = zc, zp
+        tid = torch.zeros(2 * B, 6, dtype=torch.int32, device=dev)
+        tid[:, 0::4].fill_(height)
+        tid[:, 1::4].fill_(width)
+        return ctx.detach(), {"text_embeds": pooled.detach(), "time_ids": tid}
+
     @torch.no_grad()
     def generate(self, prompt_ids, num_inference_steps=50, height=512, width=512, guidance_scale=7.5, latents=None,
                  neg_prompt_ids=None, generator=None, return_latents=False):
-        """_generate (:160-254).  prompt_ids int (B,77) device tensor; latents optional f32 (B,C,h,w) initial noise; returns the
+        """_generate (:160-254).  prompt_ids int (B,77) device tensor ((B,2,77) for an SDXL-mode text encoder: _sdxl_conditioning;
+        pass scaling_factor=0.13025 for the SDXL VAE); latents optional f32 (B,C,h,w) initial noise; returns the
         image (B,H,W,3) float32 in [0,1] on the device (and the final latents when return_latents)."""
         if height % 8 != 0 or width % 8 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
@@ -62,12 +89,18 @@ class StableDiffusionPipeline:
             latents = torch.randn(B, C, h, w, device=dev, dtype=torch.float32, generator=generator)
         elif tuple(latents.shape) != (B, C, h, w):
             raise ValueError(f"Unexpected latents shape, got {tuple(latents.shape)}, expected {(B, C, h, w)}")
-        if neg_prompt_ids is None:
-            neg_prompt_ids = self._uncond_ids(B, prompt_ids.shape[-1])
-        self.unet.prepare()
-        self.text_encoder.prepare()
-        ids = torch.cat([neg_prompt_ids.to(device=dev, dtype=torch.int32), prompt_ids.to(device=dev, dtype=torch.int32)])
-        context = nets.clip_text_forward(self.text_encoder, self.text_encoder_config, ids).detach()  # [negative | prompt] (:191)
+        added = None
+        if nets.sdxl_conditioning(self.text_encoder_config):
+            context, added = self._sdxl_conditioning(prompt_ids, neg_prompt_ids, height, width)
+        elif self.unet_config.get("addition_embed_type") == "text_time":
+            raise ValueError("a text_time (SDXL) UNet samples with an SDXL-mode text encoder (nets.dual_clip_config(sdxl_conditioning=True))")
+        else:
+            if neg_prompt_ids is None:
+                neg_prompt_ids = self._uncond_ids(B, prompt_ids.shape[-1])
+            self.unet.prepare()
+            self.text_encoder.prepare()
+            ids = torch.cat([neg_prompt_ids.to(device=dev, dtype=torch.int32), prompt_ids.to(device=dev, dtype=torch.int32)])
+            context = nets.clip_text_forward(self.text_encoder, self.text_encoder_config, ids).detach()  # [negative | prompt] (:191)
 
         lat = (latents.to(device=dev, dtype=torch.float32) * self.scheduler.init_noise_sigma).contiguous().clone()
         cpad = (C + 7) // 8 * 8
@@ -78,7 +111,7 @@ class StableDiffusionPipeline:
         for t in self.scheduler.set_timesteps(num_inference_steps):
             t_dev.fill_(int(t))
             ops.gn_arena_begin(dev)
-            pred = nets.unet_forward(self.unet, self.unet_config, x_in, t_dev, context)
+            pred = nets.unet_forward(self.unet, self.unet_config, x_in, t_dev, context, added)
             ops.gn_arena_end(dev)
             self.scheduler.cfg_step(pred, lat, x_in, t, guidance_scale)  # guidance + x_t -> x_{t-1} + next UNet input
 

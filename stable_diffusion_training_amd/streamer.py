@@ -17,7 +17,7 @@ class DataLoader:
     def __init__(self, tokenizer_obj=None, config=None, ramdisk_path=None, training_batch_size=8, repeat_batch=10,
                  maximum_resolution_areas=(512 ** 2,), bucket_lower_bound_resolutions=(256,), numb_of_worker_thread=1,
                  queue_get_timeout=60, chunk_number=0, seed=0, context_concatenation_multiplier=1, *,
-                 batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu"):
+                 batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu", text_towers=1):
         if len(maximum_resolution_areas) != len(bucket_lower_bound_resolutions):
             raise ValueError("number of elements in maximum_resolution_areas and bucket_lower_bound_resolutions is not match!")
         if training_batch_size % world_size:
@@ -27,6 +27,9 @@ class DataLoader:
         self.chunk_number, self.seed = chunk_number, seed
         self.k, self.vocab_size, self.context_window = context_concatenation_multiplier, vocab_size, context_window
         self.rank, self.world_size, self.device = rank, world_size, torch.device(device)
+        if text_towers not in (1, 2):
+            raise ValueError(f"text_towers={text_towers!r}: 1 (SD1.x / 2.x) or 2 (SDXL)")
+        self.text_towers = text_towers
         self.buckets = [tuple(int(v) for v in b) for area, lo in zip(maximum_resolution_areas, bucket_lower_bound_resolutions)
                         for b in calculate_resolution_array(area, lo, 64)]
         self._batches_per_chunk = batches_per_chunk
@@ -59,7 +62,9 @@ class DataLoader:
     # ---- batches
     def grab_next_batch(self):
         """dict(pixel_values f32 (B,3,bucket[0],bucket[1]) in [-1,1], input_ids / attention_mask int32 (B, k*77)) for this
-        rank's shard, or "end_of_batch" when the chunk is exhausted (training.py:195-199)."""
+        rank's shard, or "end_of_batch" when the chunk is exhausted (training.py:195-199).  text_towers=2 (SDXL): input_ids /
+        attention_mask (B, k*2*77), which reshape to (B*k, 2, 77) - one row per tower - and time_ids int32 (B, 6) = (bucket height,
+        width, 0, 0, height, width): the uncropped size micro-conditioning."""
         if self._cursor >= len(self._plan):
             return "end_of_batch"
         b0, b1 = self._plan[self._cursor]
@@ -68,11 +73,14 @@ class DataLoader:
         per_rank = self.training_batch_size // self.world_size
         g = torch.Generator().manual_seed((int(self.seed) * 1_000_003 + int(self.chunk_number)) * 1_000_003 + index * 64 + self.rank)
         px = torch.rand(per_rank, 3, b0, b1, generator=g) * 2 - 1
-        ids = torch.randint(0, self.vocab_size - 2, (per_rank, self.k, self.context_window), generator=g, dtype=torch.int32)
-        ids[:, :, 0] = self.vocab_size - 2   # <|startoftext|>
-        ids[:, :, -1] = self.vocab_size - 1  # <|endoftext|>
-        ids = ids.reshape(per_rank, self.k * self.context_window)
+        shape = (per_rank, self.k, self.context_window) if self.text_towers == 1 else (per_rank, self.k, 2, self.context_window)
+        ids = torch.randint(0, self.vocab_size - 2, shape, generator=g, dtype=torch.int32)
+        ids[..., 0] = self.vocab_size - 2   # <|startoftext|>
+        ids[..., -1] = self.vocab_size - 1  # <|endoftext|>
+        ids = ids.reshape(per_rank, -1)
         batch = {"pixel_values": px, "input_ids": ids, "attention_mask": torch.ones_like(ids)}
+        if self.text_towers == 2:
+            batch["time_ids"] = torch.tensor([[b0, b1, 0, 0, b0, b1]] * per_rank, dtype=torch.int32)
         if self.device.type != "cpu":
             batch = {k: v.to(self.device, non_blocking=True) for k, v in batch.items()}
         if self._print_debug:

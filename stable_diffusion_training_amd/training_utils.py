@@ -123,6 +123,7 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
         out["text_encoder_state"] = make(nets.clip_text_spec(m["config"]), m["text_encoder_params"], m["config"],
                                          nets.clip_text_forward, text_encoder_learning_rate,
                                          quantize_text_encoder_state, with_text_encoder_ema)
+        out["text_encoder_state"].store.mark_unused(nets.unused_text_leaves(m["config"]))
     return out
 
 
@@ -188,6 +189,9 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     """One DDPM training step on this rank's shard of the batch (training_utils.py:504-762), in place.
 
     batch: {"pixel_values": f32 (B,3,H,W) NCHW device tensor, "input_ids": i32 (B*k,77), "attention_mask": unused}.
+    A `text_time` (SDXL) UNet also reads "time_ids" i32 (B,6) - (H, W, 0, 0, H, W) when absent - and "text_embeds" (B,1280), unless the
+    text encoder is in SDXL mode (nets.dual_clip_config(sdxl_conditioning=True)): then input_ids are (B*k,2,77) (or (B, k*2*77)), the
+    towers compute the pooled embedding (nets.sdxl_text_forward; from each sample's first window) and a text_embeds entry is refused.
     train_rng: a torch.Generator on the device (the reference threads a JAX key; joint distribution only matters).
     rand: optional dict of explicit draws for parity tests (posterior_eps NHWC, noise NCHW, timesteps[, offset_noise,
     perturb_noise]) - the reference's threefry stream is not reproducible outside JAX.
@@ -196,6 +200,11 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     step of that size takes them), and the optimizer steps once on the fp32 mean - the step over the whole batch, with the
     activation memory of one micro-batch.  metrics["loss"] is the mean of the micro-batch losses.  K = 1 is the plain step.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
+    text_time = unet_state.config.get("addition_embed_type") == "text_time"
+    sdxl = text_time and nets.sdxl_conditioning(text_encoder_state.config)
+    if sdxl and "text_embeds" in batch:
+        raise ValueError("the text encoder is in SDXL mode and computes the pooled text embedding itself: a batch in that mode must "
+                         "not carry text_embeds")
     us, ts = unet_state.store, text_encoder_state.store
     vae_store, vae_cfg = frozen_vae_state.params, frozen_vae_state.call
     sched, sched_state = frozen_noise_scheduler_state.call, frozen_noise_scheduler_state.params
@@ -282,16 +291,28 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
 
         # text encoder + context assembly                             (training_utils.py:635-674)
         ids = mb["input_ids"]
+        ids = ids if ids.dtype == torch.int32 else ids.to(torch.int32)
+        pooled = None
         with trace.phase("text_encoder_forward"):
-            hs = text_encoder_state.apply_fn(ts, text_encoder_state.config, ids if ids.dtype == torch.int32 else ids.to(torch.int32))
+            if sdxl:  # both towers' hidden_states[-2] as the context, bigG's projected EOS embedding as text_embeds
+                ids = ids.reshape(-1, 2, ids.shape[-1] if ids.dim() == 3 else 77)
+                hs, pooled = nets.sdxl_text_forward(ts, text_encoder_state.config, ids, windows=ids.shape[0] // B)
+            else:
+                hs = text_encoder_state.apply_fn(ts, text_encoder_state.config, ids)
         ctx = assemble_context(hs, B, strip_bos_eos_token)
 
         # UNet                                                        (training_utils.py:678-684)
         added = None
-        if unet_state.config.get("addition_embed_type") == "text_time":
-            # SDXL micro-conditioning.  Beyond the reference (its call passes no added_cond_kwargs): the batch carries the pooled text
-            # embedding and the six size / crop ids as explicit inputs (SURVEY.md §8(d) note on configs[4])
-            added = {"text_embeds": mb["text_embeds"], "time_ids": mb["time_ids"]}
+        if text_time:
+            # SDXL micro-conditioning.  Beyond the reference (its call passes no added_cond_kwargs): the pooled text embedding comes from
+            # the text encoder in SDXL mode, otherwise from the batch; time_ids = (orig h, w, crop top, left, target h, w) default to the
+            # uncropped pixel size (SURVEY.md §8(d) note on configs[4])
+            tid = mb.get("time_ids")
+            if tid is None:
+                tid = torch.zeros(B, 6, dtype=torch.int32, device=dev)
+                tid[:, 0::4].fill_(H)
+                tid[:, 1::4].fill_(W)
+            added = {"text_embeds": pooled if sdxl else mb["text_embeds"], "time_ids": tid}
         with trace.phase("unet_forward"):
             pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added)
 
@@ -307,6 +328,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                   loss.data_ptr(), dpred.data_ptr(), B, C_out, h, w, pred.shape[3], rws.data_ptr(), rws.numel(), stream)
         if aux is not None:
             aux.update(latents=latents, noisy=noisy_nchw, ctx=ctx.detach(), pred=pred.detach(), target=target, moments=moments)
+            if pooled is not None:
+                aux["text_embeds"] = pooled.detach()
 
         # reverse mode through UNet and text encoder                  (training_utils.py:719-729)
         if fused_norm:
