@@ -6,7 +6,11 @@ One process per GPU:  python -m torch.distributed.run --nproc-per-node N example
 --micro-batches K (or "micro_batches" in the config): every step accumulates the gradient over K micro-batches of
 batch_size / (world * K) samples - the step over the global batch_size with the activation memory of one micro-batch.
 An SDXL directory (text_encoder_2/) trains both text towers in SDXL mode: the loader emits ids for two towers and time_ids, the
-pooled text embedding comes from the towers, and the saves are SDXL pipeline directories."""
+pooled text embedding comes from the towers, and the saves are SDXL pipeline directories.
+Schedules: "lr_scheduler" (constant, constant_with_warmup, linear, cosine, cosine_with_restarts, polynomial) takes its counts from the
+optional keys lr_warmup_steps, lr_num_training_steps, lr_num_cycles, lr_power and lr_end; "ema_warmup": true warms the EMA rate up to
+ema_rate (diffusers EMAModel), with the optional ema_inv_gamma, ema_power, ema_min_decay, ema_update_after_step and
+ema_use_warmup_power (the 1 - (1 + s / inv_gamma) ** -power form).  Both advance once per optimizer step."""
 import argparse
 import json
 import os
@@ -29,6 +33,27 @@ def delete_file_or_folder(path):
         shutil.rmtree(path, ignore_errors=True)
     elif os.path.exists(path):
         os.remove(path)
+
+
+def schedule_kwargs(config_dict):
+    """on_device_model_training_state's lr_schedule / ema_schedule from the optional config keys (absent keys: the defaults)."""
+    lr = {arg: config_dict[key] for key, arg in (("lr_warmup_steps", "num_warmup_steps"), ("lr_num_training_steps", "num_training_steps"),
+                                                 ("lr_num_cycles", "num_cycles"), ("lr_power", "power"), ("lr_end", "lr_end"))
+          if config_dict.get(key) is not None}
+    ema = None
+    if config_dict.get("ema_warmup"):
+        ema = {arg: config_dict[key] for key, arg in (("ema_inv_gamma", "inv_gamma"), ("ema_power", "power"), ("ema_min_decay", "min_decay"),
+                                                      ("ema_update_after_step", "update_after_step"),
+                                                      ("ema_use_warmup_power", "use_ema_warmup"))
+               if config_dict.get(key) is not None}
+        ema["kind"] = "warmup"
+    return dict(lr_schedule=lr or None, ema_schedule=ema)
+
+
+def current_lr(state):
+    """The learning rate of the store's last optimizer step (the schedule's value, or the constant rate)."""
+    sched = state.store.schedule
+    return sched[0].rate(max(state.step - 1, 0)) if sched else state.hyper["lr"]
 
 
 def main(config_dict, models=None, tokenizer=None, log=print):
@@ -68,7 +93,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     train_rngs = torch.Generator(device=dev)
     train_rngs.manual_seed(config_dict["master_seed"] * 1009 + rank)  # different noise / timesteps on every shard
     (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers,
-     model_object_dict) = tu.on_device_model_training_state(training_config, models, device=dev)
+     model_object_dict) = tu.on_device_model_training_state(training_config, models, device=dev, **schedule_kwargs(config_dict))
     reducer = dp.GradReducer([unet_state.store, text_encoder_state.store]) if world > 1 else None
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
@@ -129,7 +154,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
                 start = time.time()
                 train_metrics = []
                 if rank == 0:
-                    log(f'at steps {count}, avg loss for {config_dict["loss_logging_interval"]} steps: {loss}, took {elapsed} second(s)')
+                    log(f'at steps {count}, avg loss for {config_dict["loss_logging_interval"]} steps: {loss}, took {elapsed} second(s), '
+                        f'unet lr {current_lr(unet_state):.4e}')
                     with open(config_dict["loss_csv"], "a") as f:
                         f.write(f'\n{count},{config_dict["loss_logging_interval"]},{loss},{elapsed},{config_dict["chunk_steps"]},{config_dict["master_seed"]}')
         rng_states = gather_rng_states(train_rngs)  # every rank resumes ITS noise / timestep stream (collective)

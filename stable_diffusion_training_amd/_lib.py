@@ -54,6 +54,9 @@ SIGNATURES = {
     "sdt_grad_accumulate": [_P, _P, _I, _L, _I, _F, _P, _P, _L, _P],
     "sdt_lion8_step": [_P, _P, _I, _P, _P, _P, _P, _L, _I, _P, _P, _D, _D, _D, _D, _D, _D, _P],
     "sdt_lion32_step": [_P, _P, _P, _P, _P, _L, _P, _D, _D, _D, _D, _D, _D, _P],
+    "sdt_opt_schedule_select": [_P, _P, _L, _P, _L, _P, _P],
+    "sdt_lion8_step_scheduled": [_P, _P, _I, _P, _P, _P, _P, _L, _I, _P, _P, _D, _P, _D, _D, _D, _P],
+    "sdt_lion32_step_scheduled": [_P, _P, _P, _P, _P, _L, _P, _D, _P, _D, _D, _D, _P],
     "sdt_lion8_quantize": [_P, _P, _P, _L, _I, _P, _P],
     "sdt_lion8_dequantize": [_P, _P, _P, _L, _I, _P],
     "sdt_groupnorm_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _I, _P, _L, _P],

@@ -446,7 +446,7 @@ def load_training_state(path, unet_state, text_encoder_state, train_rng=None, ra
                     raise ValueError(f"{path}: {name}.{b} present in only one of file / state")
                 if dst is not None:
                     dst.copy_(f.get_tensor(f"{name}.{b}"))
-            store.count = int(meta[f"{name}.count"])
+            store.set_step(int(meta[f"{name}.count"]))  # with a schedule: the device step counter resumes too
             if store.device.type == "cuda":
                 store.prepare(full=True)  # the masters changed under the bf16 compute copies
             store.state_whole = True      # every rank loaded the whole buffers (sharded optimizer: nothing to gather before a save)

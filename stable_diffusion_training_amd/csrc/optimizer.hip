@@ -206,15 +206,22 @@ __device__ __forceinline__ float clip_grad(float g, float gnorm, float max_norm,
 
 // LPB lanes cooperate on one quantisation block of BS = 4*LPB elements; each lane owns a float4.
 #define LION_SLICES 4
-template <int LPB, bool G16>
+// SCHED: neg_lr, ema_r and ema_rm come from the device block `cur` that opt_schedule_select_kernel wrote for this step (the by-value
+// arguments are ignored); the instantiations without it are the by-value sweeps.
+template <int LPB, bool G16, bool SCHED>
 __global__ void __launch_bounds__(256) lion8_kernel(float* __restrict__ p, const void* __restrict__ g,
                                                     int8_t* __restrict__ codes, float* __restrict__ inv_scale,
                                                     float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n4,
                                                     const double* __restrict__ sqnorm, const float* __restrict__ thr,
                                                     float max_norm, float neg_lr, float wd, float c1, float c1m, float c2,
-                                                    float c2m, float ema_r, float ema_rm) {
+                                                    float c2m, float ema_r, float ema_rm, const float* __restrict__ cur) {
   __shared__ float deq_tab[256];
   __shared__ float thr_tab[132];
+  if (SCHED) {
+    neg_lr = cur[0];
+    ema_r = cur[1];
+    ema_rm = cur[2];
+  }
   lion_load_tables(deq_tab, thr_tab, thr);
   float gnorm = 0.f;
   bool do_clip = false;
@@ -289,12 +296,18 @@ __global__ void __launch_bounds__(256) lion8_kernel(float* __restrict__ p, const
   }
 }
 
+template <bool SCHED>  // as lion8_kernel
 __global__ void __launch_bounds__(256) lion32_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ mom, float* __restrict__ ema,
                                                      bf16_t* __restrict__ w_bf16, long n,
                                                      const double* __restrict__ sqnorm, float max_norm, float neg_lr,
                                                      float wd, float c1, float c1m, float c2, float c2m, float ema_r,
-                                                     float ema_rm) {
+                                                     float ema_rm, const float* __restrict__ cur) {
+  if (SCHED) {
+    neg_lr = cur[0];
+    ema_r = cur[1];
+    ema_rm = cur[2];
+  }
   float gnorm = 0.f;
   bool do_clip = false;
   if (sqnorm) {
@@ -339,6 +352,51 @@ __global__ void __launch_bounds__(256) lion8_dequantize_kernel(const int8_t* __r
                                                                float* __restrict__ x, long n, int bs) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
     x[i] = lion_deq((int)codes[i]) / inv_scale[i / bs];
+}
+
+// Per-step optimizer scalars (include/sdt.h sdt_opt_schedule_select): one lane reads the store's step counter t, copies entry
+// min(t, n - 1) of each host-built table into the 16-byte block the scheduled sweeps read, and advances the counter.  Launched once
+// per store and optimizer step, ahead of the sweeps on the same stream, so a replayed graph picks each step's values in turn.
+__global__ void __launch_bounds__(64) opt_schedule_select_kernel(int64_t* __restrict__ step, const float* __restrict__ lr_tab, long n_lr,
+                                                                  const float* __restrict__ ema_tab, long n_ema, float* __restrict__ cur) {
+  if (threadIdx.x != 0) return;
+  const int64_t t = *step;
+  const long tc = t > 0 ? (long)t : 0;
+  const long i = tc < n_lr - 1 ? tc : n_lr - 1;
+  const long j = tc < n_ema - 1 ? tc : n_ema - 1;
+  cur[0] = lr_tab[i];
+  cur[1] = ema_tab[2 * j];
+  cur[2] = ema_tab[2 * j + 1];
+  cur[3] = 0.f;
+  *step = t + 1;
+}
+
+template <bool SCHED>
+static void launch_lion8(int lpb, int g_bf16, dim3 grid, hipStream_t stream, float* p, const void* g, int8_t* codes, float* inv_scale,
+                         float* ema, uint16_t* w_bf16, long n4, const double* sqnorm, const float* thresholds, float max_norm,
+                         float neg_lr, float wd, float c1, float c1m, float c2, float c2m, float er, float erm, const float* cur) {
+  const dim3 block(256);
+#define LAUNCH_L8B(L, H)                                                                                                     \
+  hipLaunchKernelGGL((lion8_kernel<L, H, SCHED>), grid, block, 0, stream, p, g, codes, inv_scale, ema, (bf16_t*)w_bf16, n4, \
+                     sqnorm, thresholds, max_norm, neg_lr, wd, c1, c1m, c2, c2m, er, erm, cur)
+#define LAUNCH_L8(L)      \
+  do {                    \
+    if (g_bf16)           \
+      LAUNCH_L8B(L, true); \
+    else                  \
+      LAUNCH_L8B(L, false); \
+  } while (0)
+  switch (lpb) {
+    case 1: LAUNCH_L8(1); break;
+    case 2: LAUNCH_L8(2); break;
+    case 4: LAUNCH_L8(4); break;
+    case 8: LAUNCH_L8(8); break;
+    case 16: LAUNCH_L8(16); break;
+    case 32: LAUNCH_L8(32); break;
+    default: LAUNCH_L8(64); break;
+  }
+#undef LAUNCH_L8
+#undef LAUNCH_L8B
 }
 
 extern "C" {
@@ -425,47 +483,43 @@ int sdt_sum_f64_accumulate(const double* x, int64_t n, double* out, void* worksp
   return SDT_OK;
 }
 
+#define LION8_CHECK_ARGS(NAME)                                                                                                   \
+  SDT_CHECK_ARG(p && g && codes && inv_scale && thresholds, NAME ": null pointer");                                              \
+  SDT_CHECK_ARG(n >= 0 && block_size >= 4 && block_size <= 256 && (block_size & (block_size - 1)) == 0,                         \
+                NAME ": block_size must be a power of two in [4,256] (got %d)", block_size);                                     \
+  SDT_CHECK_ARG(n % block_size == 0, NAME ": n=%ld not a multiple of block_size=%d (lion_quant.py:70 reshape)", (long)n, block_size); \
+  SDT_CHECK_ARG((((uintptr_t)p | (uintptr_t)ema) & 15) == 0 && ((uintptr_t)g & (g_bf16 ? 7 : 15)) == 0 && ((uintptr_t)codes & 3) == 0 && \
+                    ((uintptr_t)w_bf16 & 7) == 0,                                                                                \
+                NAME ": misaligned buffer")
+
 int sdt_lion8_step(float* p, const void* g, int g_bf16, int8_t* codes, float* inv_scale, float* ema, uint16_t* w_bf16, int64_t n,
                    int block_size, const double* sqnorm, const float* thresholds, double max_norm, double lr, double wd,
                    double b1, double b2, double ema_rate, hipStream_t stream) {
-  SDT_CHECK_ARG(p && g && codes && inv_scale && thresholds, "sdt_lion8_step: null pointer");
-  SDT_CHECK_ARG(n >= 0 && block_size >= 4 && block_size <= 256 && (block_size & (block_size - 1)) == 0,
-                "sdt_lion8_step: block_size must be a power of two in [4,256] (got %d)", block_size);
-  SDT_CHECK_ARG(n % block_size == 0, "sdt_lion8_step: n=%ld not a multiple of block_size=%d (lion_quant.py:70 reshape)",
-                (long)n, block_size);
-  SDT_CHECK_ARG((((uintptr_t)p | (uintptr_t)ema) & 15) == 0 && ((uintptr_t)g & (g_bf16 ? 7 : 15)) == 0 && ((uintptr_t)codes & 3) == 0 &&
-                    ((uintptr_t)w_bf16 & 7) == 0,
-                "sdt_lion8_step: misaligned buffer");
+  LION8_CHECK_ARGS("sdt_lion8_step");
   if (n == 0) return SDT_OK;
   const long n4 = n >> 2;
-  const int lpb = block_size >> 2;
   const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
   const float er = (float)ema_rate, erm = (float)(1.0 - ema_rate);
-  dim3 grid(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)), block(256);
-#define LAUNCH_L8B(L, H)                                                                                             \
-  hipLaunchKernelGGL((lion8_kernel<L, H>), grid, block, 0, stream, p, g, codes, inv_scale, ema, (bf16_t*)w_bf16, \
-                     n4, sqnorm, thresholds, (float)max_norm, (float)(-lr), (float)wd, c1, c1m, c2, c2m, er, erm)
-#define LAUNCH_L8(L)      \
-  do {                    \
-    if (g_bf16)           \
-      LAUNCH_L8B(L, true); \
-    else                  \
-      LAUNCH_L8B(L, false); \
-  } while (0)
-  switch (lpb) {
-    case 1: LAUNCH_L8(1); break;
-    case 2: LAUNCH_L8(2); break;
-    case 4: LAUNCH_L8(4); break;
-    case 8: LAUNCH_L8(8); break;
-    case 16: LAUNCH_L8(16); break;
-    case 32: LAUNCH_L8(32); break;
-    default: LAUNCH_L8(64); break;
-  }
-#undef LAUNCH_L8
-#undef LAUNCH_L8B
+  launch_lion8<false>(block_size >> 2, g_bf16, dim3(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)), stream, p, g, codes, inv_scale, ema,
+                      w_bf16, n4, sqnorm, thresholds, (float)max_norm, (float)(-lr), (float)wd, c1, c1m, c2, c2m, er, erm, nullptr);
   SDT_LAUNCH_CHECK("sdt_lion8_step");
   return SDT_OK;
 }
+
+int sdt_lion8_step_scheduled(float* p, const void* g, int g_bf16, int8_t* codes, float* inv_scale, float* ema, uint16_t* w_bf16,
+                             int64_t n, int block_size, const double* sqnorm, const float* thresholds, double max_norm, const float* cur,
+                             double wd, double b1, double b2, hipStream_t stream) {
+  LION8_CHECK_ARGS("sdt_lion8_step_scheduled");
+  SDT_CHECK_ARG(cur && ((uintptr_t)cur & 15) == 0, "sdt_lion8_step_scheduled: cur must be a 16-byte aligned device block");
+  if (n == 0) return SDT_OK;
+  const long n4 = n >> 2;
+  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
+  launch_lion8<true>(block_size >> 2, g_bf16, dim3(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)), stream, p, g, codes, inv_scale, ema,
+                     w_bf16, n4, sqnorm, thresholds, (float)max_norm, 0.f, (float)wd, c1, c1m, c2, c2m, 0.f, 0.f, cur);
+  SDT_LAUNCH_CHECK("sdt_lion8_step_scheduled");
+  return SDT_OK;
+}
+#undef LION8_CHECK_ARGS
 
 int sdt_lion32_step(float* p, const float* g, float* mom, float* ema, uint16_t* w_bf16, int64_t n,
                     const double* sqnorm, double max_norm, double lr, double wd, double b1, double b2, double ema_rate,
@@ -474,9 +528,34 @@ int sdt_lion32_step(float* p, const float* g, float* mom, float* ema, uint16_t* 
   if (n == 0) return SDT_OK;
   const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
   const float er = (float)ema_rate, erm = (float)(1.0 - ema_rate);
-  hipLaunchKernelGGL(lion32_kernel, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, mom, ema,
-                     (bf16_t*)w_bf16, (long)n, sqnorm, (float)max_norm, (float)(-lr), (float)wd, c1, c1m, c2, c2m, er, erm);
+  hipLaunchKernelGGL(lion32_kernel<false>, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, mom, ema,
+                     (bf16_t*)w_bf16, (long)n, sqnorm, (float)max_norm, (float)(-lr), (float)wd, c1, c1m, c2, c2m, er, erm,
+                     (const float*)nullptr);
   SDT_LAUNCH_CHECK("sdt_lion32_step");
+  return SDT_OK;
+}
+
+int sdt_lion32_step_scheduled(float* p, const float* g, float* mom, float* ema, uint16_t* w_bf16, int64_t n, const double* sqnorm,
+                              double max_norm, const float* cur, double wd, double b1, double b2, hipStream_t stream) {
+  SDT_CHECK_ARG(p && g && mom && n >= 0, "sdt_lion32_step_scheduled: null pointer or negative n");
+  SDT_CHECK_ARG(cur && ((uintptr_t)cur & 15) == 0, "sdt_lion32_step_scheduled: cur must be a 16-byte aligned device block");
+  if (n == 0) return SDT_OK;
+  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
+  hipLaunchKernelGGL(lion32_kernel<true>, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, mom, ema,
+                     (bf16_t*)w_bf16, (long)n, sqnorm, (float)max_norm, 0.f, (float)wd, c1, c1m, c2, c2m, 0.f, 0.f, cur);
+  SDT_LAUNCH_CHECK("sdt_lion32_step_scheduled");
+  return SDT_OK;
+}
+
+int sdt_opt_schedule_select(int64_t* step, const float* lr_tab, int64_t n_lr, const float* ema_tab, int64_t n_ema, float* cur,
+                            hipStream_t stream) {
+  SDT_CHECK_ARG(step && lr_tab && ema_tab && cur, "sdt_opt_schedule_select: null pointer");
+  SDT_CHECK_ARG(n_lr >= 1 && n_ema >= 1, "sdt_opt_schedule_select: every table needs at least one entry (n_lr=%ld, n_ema=%ld)",
+                (long)n_lr, (long)n_ema);
+  SDT_CHECK_ARG(((uintptr_t)step & 7) == 0 && ((uintptr_t)cur & 15) == 0 && ((uintptr_t)ema_tab & 7) == 0,
+                "sdt_opt_schedule_select: misaligned step counter, table or block");
+  hipLaunchKernelGGL(opt_schedule_select_kernel, dim3(1), dim3(64), 0, stream, step, lr_tab, (long)n_lr, ema_tab, (long)n_ema, cur);
+  SDT_LAUNCH_CHECK("sdt_opt_schedule_select");
   return SDT_OK;
 }
 

@@ -30,9 +30,9 @@ def lion_8bit(learning_rate, b1=0.9, b2=0.99, mu_scale_dtype=None, block_size=64
               excluded_layer_mask=None):
     """lion_quant.py:159-211: chain(scale_by_lion_8bit, add_decayed_weights(weight_decay, mask), scale_by_learning_rate).
     mask: {path: bool}, True = decay; excluded_layer_mask: {path: bool}, True = quantise that leaf's momentum (the reference's
-    argument name notwithstanding, lion_quant.py:203-205).  mu_scale_dtype is accepted and ignored (fp32 scales)."""
-    if callable(learning_rate):
-        raise NotImplementedError("learning-rate schedules: pass the current value (the reference trains at a constant rate)")
+    argument name notwithstanding, lion_quant.py:203-205).  mu_scale_dtype is accepted and ignored (fp32 scales).
+    learning_rate: a float or optax's ScalarOrSchedule callable, evaluated on the host as learning_rate(count) for each update (count:
+    the updates taken before this one, as optax's scale_by_schedule) and applied by value."""
     holder = {}
 
     def _store(params):
@@ -63,7 +63,8 @@ def lion_8bit(learning_rate, b1=0.9, b2=0.99, mu_scale_dtype=None, block_size=64
         st.load(params, init_ema=False)
         for p in st.leaves:
             st.g(p).copy_(updates[p])
-        st.optimizer_step(lr=float(learning_rate), wd=float(weight_decay), b1=b1, b2=b2, max_norm=None)
+        lr = learning_rate(st.count) if callable(learning_rate) else learning_rate
+        st.optimizer_step(lr=float(lr), wd=float(weight_decay), b1=b1, b2=b2, max_norm=None)
         new = st.export("master")
         return {p: new[p] - params[p].to(torch.float32) for p in params}, _state(st)
 

@@ -185,6 +185,10 @@ class ParamStore:
         self.gacc = None
         self._acc_norm = False   # the last finish / scale pass left the squared norm of gacc in self.sqnorm
         self._grad_is_acc = False  # the last optimizer step consumed gacc: exports / grad_norm report it
+        # scheduled lr / EMA rate (set_schedule): device step counter, tables, the 16-byte block of the current step's scalars
+        self.schedule = None       # (lr_schedule.LRSchedule, lr_schedule.EMASchedule) installed, or None: by-value scalars
+        self._sched = None         # dict(step, lr_tab, ema_tab, cur) device tensors; kept for the store's life once allocated
+        self._captured = False     # an optimizer step of this store has been captured into a graph (tables must not move)
 
     # ------------------------------------------------------------------ views
     def p(self, path):
@@ -473,6 +477,48 @@ class ParamStore:
                       ws, self.sq_ws.numel(), s)
         self._acc_norm = norm
 
+    # ------------------------------------------------------------------ scheduled lr / EMA rate
+    def set_schedule(self, *, lr, ema):
+        """Install per-step optimizer scalars (lr_schedule.LRSchedule lr, lr_schedule.EMASchedule ema): from now on every optimizer
+        step picks -lr_t and (r_t, 1 - r_t) on the device (sdt_opt_schedule_select), with t the device step counter, which starts at
+        self.count and advances with every step - eager or replayed.  optimizer_step's lr must then be lr.base_lr and a running EMA's
+        ema_rate must be ema.ema_rate (the schedule's scale and cap).  A later call rewrites the tables in place when they fit (the
+        tail is padded with the last entry, which is what the clamped index reads anyway), so graphs that captured this store's step
+        keep valid addresses; a schedule that does not fit is refused once such a graph exists."""
+        if not self.trainable:
+            raise ValueError("set_schedule: the store is not trained")
+        lt = torch.from_numpy(lr.table())
+        et = torch.from_numpy(ema.table().reshape(-1))
+        sc = self._sched
+        if sc is None or lt.numel() > sc["lr_tab"].numel() or et.numel() > sc["ema_tab"].numel():
+            if self._captured:
+                raise RuntimeError("set_schedule: a graph has captured this store's optimizer step and reads its schedule tables; a "
+                                   f"schedule of {lt.numel()} / {et.numel() // 2} steps does not fit the installed tables "
+                                   f"({sc['lr_tab'].numel()} / {sc['ema_tab'].numel() // 2}): set it before the first capture")
+            dev = self.device
+            sc = self._sched = dict(step=torch.zeros(1, dtype=torch.int64, device=dev),
+                                    lr_tab=torch.empty(lt.numel(), dtype=torch.float32, device=dev),
+                                    ema_tab=torch.empty(et.numel(), dtype=torch.float32, device=dev),
+                                    cur=torch.zeros(4, dtype=torch.float32, device=dev))
+        pad_l, pad_e = sc["lr_tab"].numel() - lt.numel(), sc["ema_tab"].numel() - et.numel()
+        if pad_l:
+            lt = torch.cat([lt, lt[-1:].expand(pad_l)])
+        if pad_e:
+            et = torch.cat([et, et[-2:].repeat(pad_e // 2)])
+        sc["lr_tab"].copy_(lt)
+        sc["ema_tab"].copy_(et)
+        self.schedule = (lr, ema)
+        self.set_step(self.count)
+
+    def set_step(self, n):
+        """Set the step count (the number of optimizer steps taken): the host count and, with a schedule, the device counter that
+        selects the step's scalars (load_training_state resumes with it)."""
+        if isinstance(n, bool) or int(n) != n or n < 0:
+            raise ValueError(f"set_step: a step count is a non-negative integer (got {n!r})")
+        self.count = int(n)
+        if self._sched is not None:
+            self._sched["step"].fill_(self.count)
+
     def optimizer_step(self, *, lr, wd, b1=0.9, b2=0.99, max_norm=1.0, ema_rate=0.0, stream=None, shard=None, sq_partials=None,
                        grad_source="grad"):
         """clip_by_global_norm(max_norm) -> Lion (8-bit / fp32 momentum) -> decay -> -lr -> apply (-> EMA).
@@ -483,7 +529,10 @@ class ParamStore:
         squared norm of the sharded part is already in self.sqnorm, all-reduced over the ranks - only the replicated part is
         added here.
         grad_source="acc": the step consumes the accumulated gradient gacc (accumulate) instead of grad / grad16; its squared norm is
-        the one the last finish / scale pass computed (or a pass over gacc when that pass ran without norm)."""
+        the one the last finish / scale pass computed (or a pass over gacc when that pass ran without norm).
+        With a schedule installed (set_schedule) lr and ema_rate name the schedule's base rate and cap, and the step's values come from
+        the device: one sdt_opt_schedule_select launch, then the _scheduled sweeps.  Whether the EMA runs is still decided by ema_rate
+        (0: off), not by the scheduled r_t (r_t = 0 means EMA := parameters)."""
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         sq_ptr = None
         from_acc = grad_source == "acc"
@@ -519,6 +568,19 @@ class ParamStore:
         else:
             max_norm = 1.0
         ema_on = self.ema is not None and ema_rate
+        sc = self._sched if self.schedule is not None else None
+        if sc is not None:
+            lrs, emas = self.schedule
+            if lr != lrs.base_lr:
+                raise ValueError(f"optimizer_step: lr={lr!r} but the installed schedule scales {lrs.base_lr!r} (set_schedule again to "
+                                 "change the base rate)")
+            if ema_on and ema_rate != emas.ema_rate:
+                raise ValueError(f"optimizer_step: ema_rate={ema_rate!r} but the installed EMA schedule is built for {emas.ema_rate!r}")
+            if torch.cuda.is_current_stream_capturing():
+                self._captured = True
+            cur = sc["cur"].data_ptr()
+            _lib.call("sdt_opt_schedule_select", sc["step"].data_ptr(), sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(),
+                      sc["ema_tab"].data_ptr(), sc["ema_tab"].numel() // 2, cur, s)
         for (a, b, quant, decay) in pieces:
             n = b - a
             if n == 0:
@@ -531,14 +593,24 @@ class ParamStore:
                     gp = self.gacc.data_ptr() + 4 * a
                 else:
                     gp = self.grad16.data_ptr() + 2 * a if g16 else self.grad.data_ptr() + 4 * a
-                _lib.call("sdt_lion8_step", self.master.data_ptr() + 4 * a, gp, int(g16), self.codes.data_ptr() + a,
-                          self.inv_scale.data_ptr() + 4 * (a // self.block_size), ema_ptr, self.w.data_ptr() + 2 * a, n, self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, lr,
-                          wd_eff, b1, b2, ema_rate if ema_on else 0.0, s)
+                if sc is not None:
+                    _lib.call("sdt_lion8_step_scheduled", self.master.data_ptr() + 4 * a, gp, int(g16), self.codes.data_ptr() + a,
+                              self.inv_scale.data_ptr() + 4 * (a // self.block_size), ema_ptr, self.w.data_ptr() + 2 * a, n,
+                              self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, cur, wd_eff, b1, b2, s)
+                else:
+                    _lib.call("sdt_lion8_step", self.master.data_ptr() + 4 * a, gp, int(g16), self.codes.data_ptr() + a,
+                              self.inv_scale.data_ptr() + 4 * (a // self.block_size), ema_ptr, self.w.data_ptr() + 2 * a, n, self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, lr,
+                              wd_eff, b1, b2, ema_rate if ema_on else 0.0, s)
             else:
                 gp = self.gacc.data_ptr() + 4 * a if from_acc else self.grad.data_ptr() + 4 * (a - self.g32_base)
-                _lib.call("sdt_lion32_step", self.master.data_ptr() + 4 * a, gp,
-                          self.mom.data_ptr() + 4 * (a - self.quant_total), ema_ptr, self.w.data_ptr() + 2 * a, n, sq_ptr,
-                          max_norm, lr, wd_eff, b1, b2, ema_rate if ema_on else 0.0, s)
+                if sc is not None:
+                    _lib.call("sdt_lion32_step_scheduled", self.master.data_ptr() + 4 * a, gp,
+                              self.mom.data_ptr() + 4 * (a - self.quant_total), ema_ptr, self.w.data_ptr() + 2 * a, n, sq_ptr,
+                              max_norm, cur, wd_eff, b1, b2, s)
+                else:
+                    _lib.call("sdt_lion32_step", self.master.data_ptr() + 4 * a, gp,
+                              self.mom.data_ptr() + 4 * (a - self.quant_total), ema_ptr, self.w.data_ptr() + 2 * a, n, sq_ptr,
+                              max_norm, lr, wd_eff, b1, b2, ema_rate if ema_on else 0.0, s)
         self.count += 1
         self._written = None
         self._grad_is_acc = from_acc

@@ -17,6 +17,7 @@ import torch
 
 from . import _lib, nets, ops, trace
 from .checkpoint import load_models, load_training_state, save_model, save_training_state  # noqa: F401  (reference names)
+from .lr_schedule import resolve as resolve_schedule
 from .params import EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
 from .schedulers import DDPMScheduler
 
@@ -101,17 +102,23 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                                  u_net_learning_rate=1e-6, text_encoder_learning_rate=1e-6,
                                  excluded_layer_pattern_from_weight_decay=(), excluded_layer_from_quantization=(),
                                  lion_8bit_block_size=None, quantize_unet_state=False, quantize_text_encoder_state=False,
-                                 with_unet_ema=False, with_text_encoder_ema=False, device="cuda"):
+                                 with_unet_ema=False, with_text_encoder_ema=False, device="cuda", lr_scheduler="constant",
+                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0):
     """training_utils.py:281-427.  lr = learning_rate / adam_to_lion_scale_factor, wd = 1e-2 * scale, b1=.9, b2=.99,
-    chain(clip_by_global_norm(1), lion_8bit | lion).  Builds the flat HBM stores and loads the weights."""
+    chain(clip_by_global_norm(1), lion_8bit | lion).  Builds the flat HBM stores and loads the weights.
+    lr_scheduler / lr_schedule / ema_schedule / ema_rate: the per-step schedules of lr_schedule.resolve, installed in each trained store
+    (ParamStore.set_schedule; the lr schedule scales each store's own rate).  "constant" without an EMA schedule installs nothing."""
     out = {"unet_state": None, "text_encoder_state": None}
 
     def make(spec, weights, cfg, fn, lr, quant, ema):
+        hyper = dict(lr=lr / adam_to_lion_scale_factor, wd=1e-2 * adam_to_lion_scale_factor, b1=0.9, b2=0.99, max_norm=1.0)
+        sched = resolve_schedule(lr_scheduler, hyper["lr"], ema_rate, lr_schedule=lr_schedule, ema_schedule=ema_schedule)
         store = ParamStore(spec, device=device, quantise=quant, quant_excluded=tuple(excluded_layer_from_quantization),
                            wd_excluded=tuple(excluded_layer_pattern_from_weight_decay),
                            block_size=lion_8bit_block_size or 16, with_ema=ema)
         store.load(weights)
-        hyper = dict(lr=lr / adam_to_lion_scale_factor, wd=1e-2 * adam_to_lion_scale_factor, b1=0.9, b2=0.99, max_norm=1.0)
+        if sched is not None:
+            store.set_schedule(lr=sched[0], ema=sched[1])
         return TrainState(fn, store, cfg, hyper)
 
     if train_unet:
@@ -127,11 +134,16 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
     return out
 
 
-def on_device_model_training_state(training_config: TrainingConfig, models=None, device="cuda"):
+def on_device_model_training_state(training_config: TrainingConfig, models=None, device="cuda", *, lr_schedule=None,
+                                   ema_schedule=None):
     """training_utils.py:430-501.  `models`: load_models' result - host weight trees + configs
     ({"unet": {"unet_params", "config"}, "vae": {"vae_params", "config"}, "text_encoder": {...}}); None reads the
     diffusers directory at training_config.model_path (checkpoint.load_models).  Note the reference passes NEITHER learning
-    rate from the config (:432-442) - the effective lr is the 1e-6 default / 7 - which is mirrored here."""
+    rate from the config (:432-442) - the effective lr is the 1e-6 default / 7 - which is mirrored here.
+    training_config.lr_scheduler names the learning-rate schedule (lr_schedule.LR_SCHEDULES); its step counts come as
+    lr_schedule=dict(num_warmup_steps=, num_training_steps=, num_cycles=, power=, lr_end=), and
+    ema_schedule=dict(kind="warmup", update_after_step=, use_ema_warmup=, inv_gamma=, power=, min_decay=) warms the EMA rate up to
+    training_config.ema_rate (lr_schedule.resolve; ValueError for a name without the counts it needs)."""
     _lib.require_device()
     if models is None:
         models = load_models(training_config)
@@ -143,7 +155,8 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
         quantize_unet_state=training_config.quantize_unet_state,
         quantize_text_encoder_state=training_config.quantize_text_encoder_state,
         with_unet_ema=training_config.accumulate_unet_ema, with_text_encoder_ema=training_config.accumulate_text_encoder_ema,
-        device=device)
+        device=device, lr_scheduler=training_config.lr_scheduler, lr_schedule=lr_schedule, ema_schedule=ema_schedule,
+        ema_rate=training_config.ema_rate)
     vae_cfg = models["vae"]["config"]
     vae_store = ParamStore(nets.vae_encoder_spec(vae_cfg), device=device, trainable=False)
     vae_store.load(models["vae"]["vae_params"])
