@@ -80,6 +80,23 @@ int sdt_add_noise_velocity(const float* latents, const float* noise, const int32
 int sdt_ddim_cfg_step(const uint16_t* pred_nhwc, float* latents_nchw, uint16_t* next_input_nhwc, int B, int C, int H, int W,
                       int cpad, float guidance_scale, float alpha_prod_t, float alpha_prod_prev, int prediction_type,
                       hipStream_t stream);
+/* Guidance rescale (diffusers rescale_noise_cfg, arXiv:2305.08891 §3.4): factors[b] (B floats) = guidance_rescale *
+ * std(tx_b) / std(cfg_b) + (1 - guidance_rescale) with cfg = un + guidance_scale * (tx - un) over the C real channels x H x W
+ * of sample b, std unbiased (N - 1); 1 where std(cfg_b) == 0.  pred_nhwc as in sdt_ddim_cfg_step, cpad a multiple of 8.  One
+ * workgroup per sample, double accumulation, no atomics: bitwise reproducible.  guidance_rescale in [0, 1]. */
+int sdt_cfg_rescale_factors(const uint16_t* pred_nhwc, float* factors, int B, int C, int H, int W, int cpad, float guidance_scale,
+                            float guidance_rescale, hipStream_t stream);
+/* One step of the other samplers (DDIM with trailing / linspace timesteps, a zero-SNR step or guidance rescale; DPM-Solver++
+ * orders 1 and 2, diffusers scheduling_dpmsolver_multistep_flax.py) with classifier-free guidance:
+ *   m = (pred[0:B] + guidance_scale * (pred[B:2B] - pred[0:B])) * rescale_factors[b]   (factor 1 when rescale_factors is NULL)
+ *   x0, eps from m and the latents x by prediction_type (0 epsilon, 1 sample, 2 v_prediction) with alpha_s, sigma_s of the
+ *   current timestep; latents <- c_x*x + c_x0*x0 + c_eps*eps + c_d1*(x0 - x0_history)   (the host folds each sampler into the
+ *   four coefficients).  x0_history_nchw (f32 (B,C,H,W), optional): read only when c_d1 != 0, then overwritten with this x0.
+ * next_input_nhwc as in sdt_ddim_cfg_step.  Refused: epsilon with alpha_s == 0, sample with sigma_s == 0, non-finite
+ * coefficients, c_d1 != 0 without a history, cpad not a multiple of 8. */
+int sdt_sampler_cfg_step(const uint16_t* pred_nhwc, float* latents_nchw, uint16_t* next_input_nhwc, float* x0_history_nchw,
+                         const float* rescale_factors, int B, int C, int H, int W, int cpad, float guidance_scale, float alpha_s,
+                         float sigma_s, int prediction_type, float c_x, float c_x0, float c_eps, float c_d1, hipStream_t stream);
 /* latents (B,L,H,W) f32 = (mean + exp(0.5*clip(logvar,-30,20))*eps)*scale from moments bf16 (B,H,W,moment_stride) */
 int sdt_vae_posterior_sample(const uint16_t* moments_nhwc, const float* eps_nhwc, float* latents_nchw, int B, int L,
                              int H, int W, int moment_stride, float scale, hipStream_t stream);

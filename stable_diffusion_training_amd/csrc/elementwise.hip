@@ -67,6 +67,99 @@ __global__ void __launch_bounds__(256) ddim_cfg_step_kernel(const bf16_t* __rest
   }
 }
 
+// diffusers' rescale_noise_cfg factor per sample b (arXiv:2305.08891 §3.4): cfg = un + g*(tx - un) over the C real channels of
+// the (h,w) map, f_b = phi * std(tx_b) / std(cfg_b) + (1 - phi), std unbiased (N - 1); f_b = 1 when std(cfg_b) == 0.  One
+// workgroup per sample, a fixed pixel-to-thread map and a fixed reduction tree (wave shuffle, then the 4 wave totals in order):
+// no atomics, so the factors are the same bits on every launch.  pred bf16 NHWC (2B,h,w,cpad), cpad % 8 == 0.
+__global__ void __launch_bounds__(256) cfg_rescale_factors_kernel(const uint4* __restrict__ pred, float* __restrict__ factors,
+                                                                  int B, int C, int HW, int cpad, float guidance, float phi) {
+  __shared__ double s_part[4][4];
+  const int b = blockIdx.x, nv = cpad / 8;
+  const long total = (long)B * HW;
+  double st = 0.0, st2 = 0.0, sc = 0.0, sc2 = 0.0;  // sums of tx, tx^2, cfg, cfg^2
+  for (int p = threadIdx.x; p < HW; p += 256) {
+    const long i = (long)b * HW + p;
+    for (int v = 0; v < nv; ++v) {
+      float un[8], tx[8];
+      unpack8(pred[i * nv + v], un);
+      unpack8(pred[(i + total) * nv + v], tx);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        if (v * 8 + e < C) {
+          const double t = tx[e], m = un[e] + guidance * (tx[e] - un[e]);
+          st += t; st2 += t * t; sc += m; sc2 += m * m;
+        }
+      }
+    }
+  }
+  double r[4] = {st, st2, sc, sc2};
+#pragma unroll
+  for (int k = 0; k < 4; ++k)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) r[k] += __shfl_xor(r[k], o, 64);
+  const int w = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0)
+    for (int k = 0; k < 4; ++k) s_part[w][k] = r[k];
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t[4];
+    for (int k = 0; k < 4; ++k) t[k] = ((s_part[0][k] + s_part[1][k]) + s_part[2][k]) + s_part[3][k];
+    const double n = (double)C * HW;
+    const double var_t = fmax((t[1] - t[0] * t[0] / n) / (n - 1.0), 0.0), var_c = fmax((t[3] - t[2] * t[2] / n) / (n - 1.0), 0.0);
+    factors[b] = var_c > 0.0 ? (float)(phi * sqrt(var_t / var_c) + (1.0 - phi)) : 1.0f;
+  }
+}
+
+// The update of the DDIM paths sdt_ddim_cfg_step does not serve (trailing / linspace timesteps, a t with alpha_prod 0, guidance
+// rescale) and of DPM-Solver++(2M) (diffusers scheduling_dpmsolver_multistep_flax.py, algorithm dpmsolver++, midpoint), per pixel:
+//   m = (un + g*(tx - un)) * f_b              f_b from cfg_rescale_factors_kernel, or 1 when `factors` is null
+//   x0, eps from m and x by ptype with (sa, sb) = (alpha_s, sigma_s) of the current timestep (as ddim_cfg_step_kernel)
+//   x <- c_x*x + c_x0*x0 + c_eps*eps + c_d1*(x0 - x0_prev)
+// The host folds each sampler into the four coefficients (schedulers.py).  hist (f32 NCHW, optional) is the x0 of the previous
+// step: read only when c_d1 != 0 (its first use may find it unwritten), then overwritten with this step's x0.  pred / x_next
+// bf16 NHWC (2B,h,w,cpad) as uint4 (8 channels), padding channels of x_next written as zero.
+__global__ void __launch_bounds__(256) sampler_cfg_step_kernel(const uint4* __restrict__ pred, float* __restrict__ lat,
+                                                               uint4* __restrict__ x_next, float* __restrict__ hist,
+                                                               const float* __restrict__ factors, int B, int C, int HW, int cpad,
+                                                               float guidance, float sa, float sb, int ptype, float c_x, float c_x0,
+                                                               float c_eps, float c_d1) {
+  const long total = (long)B * HW;
+  const int nv = cpad / 8;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / HW), p = (int)(i % HW);
+    const float f = factors ? factors[b] : 1.0f;
+    for (int v = 0; v < nv; ++v) {
+      float un[8], tx[8], nx[8];
+      unpack8(pred[i * nv + v], un);
+      unpack8(pred[(i + total) * nv + v], tx);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int c = v * 8 + e;
+        nx[e] = 0.f;
+        if (c < C) {
+          const long off = ((long)b * C + c) * HW + p;
+          const float m = (un[e] + guidance * (tx[e] - un[e])) * f;
+          const float x = lat[off];
+          float x0, eps;
+          if (ptype == 0) { x0 = (x - sb * m) / sa; eps = m; }
+          else if (ptype == 1) { x0 = m; eps = (x - sa * x0) / sb; }
+          else { x0 = sa * x - sb * m; eps = sa * m + sb * x; }
+          float y = c_x * x + c_x0 * x0 + c_eps * eps;
+          if (hist) {
+            if (c_d1 != 0.f) y += c_d1 * (x0 - hist[off]);
+            hist[off] = x0;
+          }
+          nx[e] = y;
+          lat[off] = y;
+        }
+      }
+      const uint4 o = pack8(nx);
+      x_next[i * nv + v] = o;
+      x_next[(i + total) * nv + v] = o;
+    }
+  }
+}
+
 // moments bf16 NHWC (B,h,w,mstride) with mean = ch [0,L), logvar = ch [L,2L); eps f32 NHWC (B,h,w,L)
 // -> latents f32 NCHW (B,L,h,w) = (mean + exp(0.5*clip(logvar,-30,20))*eps) * scale
 __global__ void __launch_bounds__(256) posterior_sample_kernel(const bf16_t* __restrict__ mom, const float* __restrict__ eps,
@@ -577,6 +670,42 @@ int sdt_ddim_cfg_step(const uint16_t* pred_nhwc, float* latents_nchw, uint16_t* 
                      latents_nchw, (bf16_t*)next_input_nhwc, B, C, H * W, cpad, guidance_scale, sqrtf(alpha_prod_t),
                      sqrtf(1.0f - alpha_prod_t), sqrtf(alpha_prod_prev), sqrtf(1.0f - alpha_prod_prev), prediction_type);
   SDT_LAUNCH_CHECK("sdt_ddim_cfg_step");
+  return SDT_OK;
+}
+
+int sdt_cfg_rescale_factors(const uint16_t* pred_nhwc, float* factors, int B, int C, int H, int W, int cpad, float guidance_scale,
+                            float guidance_rescale, hipStream_t stream) {
+  SDT_CHECK_ARG(pred_nhwc && factors, "sdt_cfg_rescale_factors: null pointer");
+  SDT_CHECK_ARG(((uintptr_t)pred_nhwc & 15) == 0, "sdt_cfg_rescale_factors: pred_nhwc misaligned (16 bytes)");
+  SDT_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && cpad >= C && cpad % 8 == 0 && (long)C * H * W >= 2,
+                "sdt_cfg_rescale_factors: bad shape B=%d C=%d H=%d W=%d cpad=%d (cpad a multiple of 8, C*H*W >= 2)", B, C, H, W, cpad);
+  SDT_CHECK_ARG(guidance_rescale >= 0.f && guidance_rescale <= 1.f && std::isfinite(guidance_scale),
+                "sdt_cfg_rescale_factors: guidance_rescale %g must lie in [0, 1], guidance_scale finite", guidance_rescale);
+  hipLaunchKernelGGL(cfg_rescale_factors_kernel, dim3(B), dim3(256), 0, stream, (const uint4*)pred_nhwc, factors, B, C, H * W, cpad,
+                     guidance_scale, guidance_rescale);
+  SDT_LAUNCH_CHECK("sdt_cfg_rescale_factors");
+  return SDT_OK;
+}
+
+int sdt_sampler_cfg_step(const uint16_t* pred_nhwc, float* latents_nchw, uint16_t* next_input_nhwc, float* x0_history_nchw,
+                         const float* rescale_factors, int B, int C, int H, int W, int cpad, float guidance_scale, float alpha_s,
+                         float sigma_s, int prediction_type, float c_x, float c_x0, float c_eps, float c_d1, hipStream_t stream) {
+  SDT_CHECK_ARG(pred_nhwc && latents_nchw && next_input_nhwc, "sdt_sampler_cfg_step: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)pred_nhwc | (uintptr_t)next_input_nhwc) & 15) == 0, "sdt_sampler_cfg_step: pred / next input misaligned (16 bytes)");
+  SDT_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && cpad >= C && cpad % 8 == 0,
+                "sdt_sampler_cfg_step: bad shape B=%d C=%d H=%d W=%d cpad=%d (cpad a multiple of 8)", B, C, H, W, cpad);
+  SDT_CHECK_ARG(prediction_type >= 0 && prediction_type <= 2, "sdt_sampler_cfg_step: prediction_type %d (0 epsilon, 1 sample, 2 v_prediction)", prediction_type);
+  SDT_CHECK_ARG(alpha_s >= 0.f && alpha_s <= 1.f && sigma_s >= 0.f && sigma_s <= 1.f, "sdt_sampler_cfg_step: alpha_s / sigma_s must lie in [0, 1]");
+  SDT_CHECK_ARG(!(prediction_type == 0 && alpha_s == 0.f) && !(prediction_type == 1 && sigma_s == 0.f),
+                "sdt_sampler_cfg_step: %s prediction needs %s > 0", prediction_type == 0 ? "epsilon" : "sample",
+                prediction_type == 0 ? "alpha_s" : "sigma_s");
+  SDT_CHECK_ARG(std::isfinite(guidance_scale) && std::isfinite(c_x) && std::isfinite(c_x0) && std::isfinite(c_eps) && std::isfinite(c_d1),
+                "sdt_sampler_cfg_step: guidance scale and coefficients must be finite");
+  SDT_CHECK_ARG(c_d1 == 0.f || x0_history_nchw, "sdt_sampler_cfg_step: c_d1 != 0 needs the x0 history");
+  hipLaunchKernelGGL(sampler_cfg_step_kernel, dim3(sdt_grid_1d((long)B * H * W, 256)), dim3(256), 0, stream, (const uint4*)pred_nhwc,
+                     latents_nchw, (uint4*)next_input_nhwc, x0_history_nchw, rescale_factors, B, C, H * W, cpad, guidance_scale,
+                     alpha_s, sigma_s, prediction_type, c_x, c_x0, c_eps, c_d1);
+  SDT_LAUNCH_CHECK("sdt_sampler_cfg_step");
   return SDT_OK;
 }
 

@@ -1,6 +1,7 @@
 """Sampling / validation path: the reference's FlaxStableDiffusionPipeline._generate
 (models/pipeline_flax_stable_diffusion.py:160-254) on the same HIP operators train_step uses - CLIP text encoder, UNet
-forward, the fused classifier-free-guidance + DDIM update (`sdt_ddim_cfg_step`), VAE decoder.  The reference uses this
+forward, the fused classifier-free-guidance + DDIM update (`sdt_ddim_cfg_step`; DPM-Solver++, trailing / linspace timesteps and
+guidance rescale: `sdt_sampler_cfg_step`), VAE decoder.  The reference uses this
 class during training only as the checkpoint container (training_utils.py:1007-1023); sampling is how a run is eyeballed.
 
 No CPU fallback: every tensor op here is a libsdtrain_hip.so launch or torch device plumbing."""
@@ -33,7 +34,8 @@ class StableDiffusionPipeline:
             vae_params = flatten_tree(vae_params)
         self.vae_decoder.load(vae_params)
         self.vae_decoder.prepare()
-        # the reference's placeholder (training_utils.py:998-1004); pass a DDIMScheduler built for the trained schedule instead
+        # the reference's placeholder (training_utils.py:998-1004); pass a DDIMScheduler or DPMSolverMultistepScheduler built for the
+        # trained schedule instead (a zero-terminal-SNR v-prediction model: timestep_spacing="trailing" or "linspace")
         self.scheduler = scheduler or DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
                                                     num_train_timesteps=1000, prediction_type="v_prediction")
         self.scaling_factor = scaling_factor
@@ -74,12 +76,16 @@ class StableDiffusionPipeline:
 
     @torch.no_grad()
     def generate(self, prompt_ids, num_inference_steps=50, height=512, width=512, guidance_scale=7.5, latents=None,
-                 neg_prompt_ids=None, generator=None, return_latents=False):
+                 neg_prompt_ids=None, generator=None, return_latents=False, guidance_rescale=0.0):
         """_generate (:160-254).  prompt_ids int (B,77) device tensor ((B,2,77) for an SDXL-mode text encoder: _sdxl_conditioning;
         pass scaling_factor=0.13025 for the SDXL VAE); latents optional f32 (B,C,h,w) initial noise; returns the
-        image (B,H,W,3) float32 in [0,1] on the device (and the final latents when return_latents)."""
+        image (B,H,W,3) float32 in [0,1] on the device (and the final latents when return_latents).  guidance_rescale in [0, 1]
+        rescales the guided prediction (epsilon or v) per sample towards the std of the text prediction (diffusers
+        rescale_noise_cfg, arXiv:2305.08891 §3.4; 0.7 there); 0 leaves it as it is and launches nothing extra."""
         if height % 8 != 0 or width % 8 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
+        if not 0.0 <= guidance_rescale <= 1.0:
+            raise ValueError(f"guidance_rescale {guidance_rescale} must lie in [0, 1]")
         dev = self.device
         stream = torch.cuda.current_stream().cuda_stream
         B = prompt_ids.shape[0]
@@ -113,7 +119,7 @@ class StableDiffusionPipeline:
             ops.gn_arena_begin(dev)
             pred = nets.unet_forward(self.unet, self.unet_config, x_in, t_dev, context, added)
             ops.gn_arena_end(dev)
-            self.scheduler.cfg_step(pred, lat, x_in, t, guidance_scale)  # guidance + x_t -> x_{t-1} + next UNet input
+            self.scheduler.cfg_step(pred, lat, x_in, t, guidance_scale, guidance_rescale)  # guidance + x_t -> x_{t-1} + next input
 
         z = torch.empty(B, h, w, cpad, dtype=torch.bfloat16, device=dev)
         scaled = lat * (1.0 / self.scaling_factor)

@@ -3,8 +3,10 @@
 Mirrors the reference's FlaxDDPMScheduler surface for the train path (schedulers/scheduling_ddpm_flax.py:96-124,
 281-297; schedulers/scheduling_utils_flax.py:193-343): same constructor arguments, `create_state()`,
 `add_noise(state, ...)`, `get_velocity(state, ...)`; including the repo-specific "zero_snr_scaled_linear" schedule
-(scheduling_utils_flax.py:286-295 + rescale_betas :222-263).  DDIMScheduler is the sampler's side.
-The per-element arithmetic runs in the fused HIP kernel `sdt_add_noise_velocity`.
+(scheduling_utils_flax.py:286-295 + rescale_betas :222-263).  DDIMScheduler and DPMSolverMultistepScheduler are the sampler's
+side: host tables and per-step coefficients, the update fused with classifier-free guidance in
+`sdt_ddim_cfg_step` / `sdt_sampler_cfg_step`.  The per-element arithmetic of training runs in the fused HIP kernel
+`sdt_add_noise_velocity`.
 """
 import math
 from dataclasses import dataclass
@@ -93,40 +95,220 @@ class DDPMScheduler:
             self.prediction_type = keep
 
 
-class DDIMScheduler:
+_PTYPE = {"epsilon": 0, "sample": 1, "v_prediction": 2}
+SPACINGS = ("leading", "trailing", "linspace")
+
+
+def _check_prediction_type(prediction_type):
+    if prediction_type not in _PTYPE:
+        raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon`, `sample` or `v_prediction`")
+
+
+def _check_spacing(timestep_spacing):
+    if timestep_spacing not in SPACINGS:
+        raise ValueError(f"timestep_spacing {timestep_spacing!r} must be one of {', '.join(SPACINGS)}")
+
+
+def _check_visits(prediction_type, alphas_cumprod, timesteps):
+    """An epsilon model cannot be sampled at a timestep with alpha_prod 0 (a zero-terminal-SNR schedule at t = T - 1): x0 would
+    be (x - eps) / 0.  arXiv:2305.08891 samples such schedules with v-prediction."""
+    if prediction_type == "epsilon" and np.any(alphas_cumprod[np.asarray(timesteps)] == 0):
+        raise ValueError("epsilon prediction cannot be sampled at a timestep whose alpha_prod is 0 (zero terminal SNR): "
+                         "use v_prediction, or a spacing that does not visit it")
+
+
+def _check_rescale(guidance_rescale):
+    if not 0.0 <= guidance_rescale <= 1.0:
+        raise ValueError(f"guidance_rescale {guidance_rescale} must lie in [0, 1]")
+
+
+def trailing_timesteps(num_train_timesteps, num_inference_steps):
+    """round(arange(T, 0, -T/n)) - 1 (diffusers' "trailing", arXiv:2305.08891 Table 2): starts at T - 1.  For some n the float
+    step leaves an (n+1)-th entry near 0 (-1 after the shift); the first n are the table."""
+    T, n = num_train_timesteps, num_inference_steps
+    return (np.round(np.arange(T, 0, -T / n))[:n] - 1).astype(np.int32)
+
+
+def sampling_tables(alphas_cumprod):
+    """alpha = sqrt(ac), sigma = sqrt(1 - ac), lambda = log alpha - log sigma, all float32; lambda = -inf where ac == 0."""
+    alpha = np.sqrt(alphas_cumprod).astype(_F)
+    sigma = np.sqrt((_F(1) - alphas_cumprod).astype(_F)).astype(_F)
+    with np.errstate(divide="ignore"):
+        lam = (np.log(alpha) - np.log(sigma)).astype(_F)
+    return alpha, sigma, lam
+
+
+class _CfgStep:
+    """The launch shared by the samplers' new paths: guidance (+ rescale factors) and the coefficient update of
+    `sdt_sampler_cfg_step`.  The rescale costs one `sdt_cfg_rescale_factors` launch, only when guidance_rescale > 0."""
+    _factors = None
+
+    def _rescale_factors(self, pred_nhwc, B, C, h, w, guidance_scale, guidance_rescale, stream):
+        if guidance_rescale == 0.0:
+            return None
+        if self._factors is None or self._factors.numel() != B or self._factors.device != pred_nhwc.device:
+            self._factors = torch.empty(B, dtype=torch.float32, device=pred_nhwc.device)
+        _lib.call("sdt_cfg_rescale_factors", pred_nhwc.data_ptr(), self._factors.data_ptr(), B, C, h, w, pred_nhwc.shape[3],
+                  float(guidance_scale), float(guidance_rescale), stream)
+        return self._factors
+
+    def _launch(self, pred_nhwc, latents_nchw, next_input_nhwc, history, guidance_scale, guidance_rescale, coeffs):
+        B, C, h, w = latents_nchw.shape
+        stream = torch.cuda.current_stream().cuda_stream
+        f = self._rescale_factors(pred_nhwc, B, C, h, w, guidance_scale, guidance_rescale, stream)
+        alpha_s, sigma_s, c_x, c_x0, c_eps, c_d1 = (float(c) for c in coeffs)
+        _lib.call("sdt_sampler_cfg_step", pred_nhwc.data_ptr(), latents_nchw.data_ptr(), next_input_nhwc.data_ptr(),
+                  None if history is None else history.data_ptr(), None if f is None else f.data_ptr(), B, C, h, w,
+                  pred_nhwc.shape[3], float(guidance_scale), alpha_s, sigma_s, _PTYPE[self.prediction_type], c_x, c_x0, c_eps,
+                  c_d1, stream)
+
+
+class DDIMScheduler(_CfgStep):
     """Deterministic (eta = 0) DDIM sampler: the reference's FlaxDDIMScheduler (schedulers/scheduling_ddim_flax.py: create_state
     :127-147, set_timesteps :165-186, step :199-284) as the reference constructs it (training_utils.py:998-1004) and steps it
     (models/pipeline_flax_stable_diffusion.py:218-232, 235-240): evenly spaced
     timesteps (arange(n) * (T // n))[::-1] + steps_offset, init_noise_sigma 1, alpha_prod_prev = 1 past the last step when
-    set_alpha_to_one, no clipping.  The update itself is fused with classifier-free guidance in `sdt_ddim_cfg_step`."""
+    set_alpha_to_one, no clipping.  The update itself is fused with classifier-free guidance in `sdt_ddim_cfg_step`.
+
+    timestep_spacing "trailing" / "linspace" (diffusers 0.21.4; arXiv:2305.08891 samples zero-terminal-SNR models from T - 1),
+    a step at a timestep with alpha_prod 0, and guidance_rescale > 0 run through `sdt_sampler_cfg_step` instead; the previous
+    timestep stays t - T // n for every spacing, as in diffusers."""
     init_noise_sigma = 1.0
-    _PTYPE = {"epsilon": 0, "sample": 1, "v_prediction": 2}
+    _PTYPE = _PTYPE
 
     def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
-                 set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon"):
-        if prediction_type not in self._PTYPE:
-            raise ValueError(f"prediction_type given as {prediction_type} must be one of `epsilon`, `sample` or `v_prediction`")
+                 set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon", timestep_spacing="leading"):
+        _check_prediction_type(prediction_type)
+        _check_spacing(timestep_spacing)
         self.num_train_timesteps, self.steps_offset = num_train_timesteps, steps_offset
         self.set_alpha_to_one, self.prediction_type = set_alpha_to_one, prediction_type
+        self.timestep_spacing = timestep_spacing
         betas = make_betas(beta_schedule, beta_start, beta_end, num_train_timesteps)
         self.alphas_cumprod = np.cumprod((_F(1) - betas).astype(_F), dtype=_F)
         self.final_alpha_cumprod = _F(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
 
     def set_timesteps(self, num_inference_steps):
         self.num_inference_steps = num_inference_steps
-        ratio = self.num_train_timesteps // num_inference_steps
-        self.timesteps = ((np.arange(0, num_inference_steps) * ratio).round()[::-1] + self.steps_offset).astype(np.int32)
+        T, n = self.num_train_timesteps, num_inference_steps
+        if self.timestep_spacing == "leading":
+            ratio = T // n
+            self.timesteps = ((np.arange(0, n) * ratio).round()[::-1] + self.steps_offset).astype(np.int32)
+        elif self.timestep_spacing == "trailing":
+            self.timesteps = trailing_timesteps(T, n)
+        else:
+            self.timesteps = np.round(np.linspace(0, T - 1, n))[::-1].astype(np.int32)
+        _check_visits(self.prediction_type, self.alphas_cumprod, self.timesteps)
         return self.timesteps
 
     def alpha_products(self, timestep):
         prev = int(timestep) - self.num_train_timesteps // self.num_inference_steps
         return float(self.alphas_cumprod[int(timestep)]), float(self.alphas_cumprod[prev] if prev >= 0 else self.final_alpha_cumprod)
 
-    def cfg_step(self, pred_nhwc, latents_nchw, next_input_nhwc, timestep, guidance_scale):
+    def step_coefficients(self, timestep):
+        """(alpha_s, sigma_s, c_x, c_x0, c_eps, c_d1) of `sdt_sampler_cfg_step` for the DDIM step at `timestep`, float32:
+        x_prev = sqrt(a_prev) * x0 + sqrt(1 - a_prev) * eps."""
+        a_t, a_prev = (_F(a) for a in self.alpha_products(timestep))
+        return (np.sqrt(a_t), np.sqrt(_F(1) - a_t), _F(0), np.sqrt(a_prev), np.sqrt(_F(1) - a_prev), _F(0))
+
+    def cfg_step(self, pred_nhwc, latents_nchw, next_input_nhwc, timestep, guidance_scale, guidance_rescale=0.0):
         """pred_nhwc (2B,h,w,cpad) bf16 = UNet output for [unconditional | text]; updates latents_nchw (B,C,h,w) f32 in place
-        and writes the next doubled UNet input."""
+        and writes the next doubled UNet input.  guidance_rescale in [0, 1] (diffusers rescale_noise_cfg)."""
+        _check_rescale(guidance_rescale)
         B, C, h, w = latents_nchw.shape
         a_t, a_prev = self.alpha_products(timestep)
-        _lib.call("sdt_ddim_cfg_step", pred_nhwc.data_ptr(), latents_nchw.data_ptr(), next_input_nhwc.data_ptr(), B, C, h, w,
-                  pred_nhwc.shape[3], float(guidance_scale), a_t, a_prev, self._PTYPE[self.prediction_type],
-                  torch.cuda.current_stream().cuda_stream)
+        if self.timestep_spacing == "leading" and guidance_rescale == 0.0 and a_t > 0.0:
+            _lib.call("sdt_ddim_cfg_step", pred_nhwc.data_ptr(), latents_nchw.data_ptr(), next_input_nhwc.data_ptr(), B, C, h, w,
+                      pred_nhwc.shape[3], float(guidance_scale), a_t, a_prev, self._PTYPE[self.prediction_type],
+                      torch.cuda.current_stream().cuda_stream)
+            return
+        _check_visits(self.prediction_type, self.alphas_cumprod, [int(timestep)])
+        self._launch(pred_nhwc, latents_nchw, next_input_nhwc, None, guidance_scale, guidance_rescale,
+                     self.step_coefficients(timestep))
+
+
+class DPMSolverMultistepScheduler(_CfgStep):
+    """DPM-Solver++(2M) (arXiv:2211.01095), deterministic: diffusers 0.21.4 FlaxDPMSolverMultistepScheduler
+    (scheduling_dpmsolver_multistep_flax.py) with algorithm_type "dpmsolver++" and solver_type "midpoint", the sampler the
+    reference's pipeline also accepts (models/pipeline_flax_stable_diffusion.py:32, 96-109).  Host side in float32: the
+    alpha / sigma / lambda tables, the timestep table and the per-step coefficients (step_coefficients); the update runs in
+    `sdt_sampler_cfg_step`, which keeps the previous step's x0 in `x0_history` (f32 (B,C,h,w), allocated by the first step
+    after set_timesteps).
+
+    Step i goes from s0 = timesteps[i] to t = timesteps[i+1] (t = 0 after the last: like diffusers, the loop ends at the noise
+    level of t = 0).  On a zero-terminal-SNR schedule lambda(T-1) = -inf: h = +inf, exp(-h) = 0 at the first step and
+    1 / r0 = 0 at the second, which IEEE arithmetic gives without forming 0 * inf."""
+    init_noise_sigma = 1.0
+
+    def __init__(self, num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
+                 prediction_type="epsilon", solver_order=2, lower_order_final=True, timestep_spacing="linspace", steps_offset=0):
+        _check_prediction_type(prediction_type)
+        _check_spacing(timestep_spacing)
+        if solver_order not in (1, 2):
+            raise ValueError(f"solver_order {solver_order}: DPM-Solver++ is served with order 1 or 2")
+        self.num_train_timesteps, self.prediction_type = num_train_timesteps, prediction_type
+        self.solver_order, self.lower_order_final = solver_order, lower_order_final
+        self.timestep_spacing, self.steps_offset = timestep_spacing, steps_offset
+        betas = make_betas(beta_schedule, beta_start, beta_end, num_train_timesteps)
+        self.alphas_cumprod = np.cumprod((_F(1) - betas).astype(_F), dtype=_F)
+        self.alpha_t, self.sigma_t, self.lambda_t = sampling_tables(self.alphas_cumprod)
+        self.timesteps, self.x0_history, self._step = None, None, 0
+
+    def set_timesteps(self, num_inference_steps):
+        """Resets the solver state and returns the timestep table (repeated entries dropped, the first kept)."""
+        T, n = self.num_train_timesteps, num_inference_steps
+        if n < 1:
+            raise ValueError(f"num_inference_steps {n} must be positive")
+        if self.timestep_spacing == "linspace":
+            ts = np.round(np.linspace(0, T - 1, n + 1))[::-1][:-1]
+        elif self.timestep_spacing == "leading":
+            ts = (np.arange(0, n + 1) * (T // (n + 1))).round()[::-1][:-1] + self.steps_offset
+        else:
+            ts = trailing_timesteps(T, n)
+        ts = ts.astype(np.int32)
+        _, first = np.unique(ts, return_index=True)
+        ts = ts[np.sort(first)]
+        _check_visits(self.prediction_type, self.alphas_cumprod, ts)
+        self.timesteps, self.num_inference_steps = ts, len(ts)
+        self.x0_history, self._step = None, 0
+        return self.timesteps
+
+    def step_coefficients(self, i):
+        """(alpha_s0, sigma_s0, c_x, c_x0, c_eps, c_d1) of step i, float32:
+        first order  x_t = (sigma_t/sigma_s0) x - alpha_t (e^-h - 1) x0_i
+        second order x_t = (sigma_t/sigma_s0) x - alpha_t (e^-h - 1) x0_i - 1/2 alpha_t (e^-h - 1) (1/r0) (x0_i - x0_{i-1})
+        with h = lambda_t - lambda_s0, r0 = (lambda_s0 - lambda_s1) / h."""
+        ts, n = self.timesteps, self.num_inference_steps
+        s0 = int(ts[i])
+        t = int(ts[i + 1]) if i + 1 < n else 0
+        a, s, lam = self.alpha_t, self.sigma_t, self.lambda_t
+        first = self.solver_order == 1 or i == 0 or (self.lower_order_final and i == n - 1 and n < 15)
+        with np.errstate(divide="ignore", invalid="ignore", over="ignore"):
+            h = lam[t] - lam[s0]
+            ah = a[t] * (np.exp(-h) - _F(1))
+            c_x, c_x0, c_d1 = s[t] / s[s0], -ah, _F(0)
+            if not first:
+                r0 = (lam[s0] - lam[int(ts[i - 1])]) / h
+                c_d1 = -(_F(0.5) * ah) * (_F(1) / r0)
+        out = tuple(_F(c) for c in (a[s0], s[s0], c_x, c_x0, _F(0), c_d1))
+        if not all(np.isfinite(out)):
+            raise ValueError(f"DPM-Solver++ step {i} ({s0} -> {t}) has non-finite coefficients {out}")
+        return out
+
+    def cfg_step(self, pred_nhwc, latents_nchw, next_input_nhwc, timestep, guidance_scale, guidance_rescale=0.0):
+        """pred_nhwc (2B,h,w,cpad) bf16 = UNet output for [unconditional | text]; updates latents_nchw (B,C,h,w) f32 in place
+        and writes the next doubled UNet input.  Steps must come in the order of set_timesteps."""
+        _check_rescale(guidance_rescale)
+        if self.timesteps is None:
+            raise ValueError("call set_timesteps before cfg_step")
+        i = self._step
+        if i >= self.num_inference_steps or int(timestep) != int(self.timesteps[i]):
+            want = "none (the table is done)" if i >= self.num_inference_steps else int(self.timesteps[i])
+            raise ValueError(f"timestep {int(timestep)} out of order: the next one is {want}")
+        coeffs = self.step_coefficients(i)
+        if self.x0_history is None:
+            self.x0_history = torch.zeros(latents_nchw.shape, dtype=torch.float32, device=latents_nchw.device)
+        elif self.x0_history.shape != latents_nchw.shape or self.x0_history.device != latents_nchw.device:
+            raise ValueError(f"latents {tuple(latents_nchw.shape)} changed within one sequence (started with "
+                             f"{tuple(self.x0_history.shape)}): call set_timesteps first")
+        self._launch(pred_nhwc, latents_nchw, next_input_nhwc, self.x0_history, guidance_scale, guidance_rescale, coeffs)
+        self._step = i + 1

@@ -1,4 +1,10 @@
-"""Developer tool: wall time of the sampling path at SD1.5 size (512x512, classifier-free guidance, DDIM), random-init weights."""
+"""Developer tool: wall time of the sampling path at SD1.5 size (512x512, classifier-free guidance), random-init weights.
+
+    python tools/sample_bench.py [STEPS] [--scheduler ddim|dpmpp] [--spacing leading|trailing|linspace] [--guidance-rescale PHI]
+
+DDIM with leading spacing (the default) is the pipeline's default sampler; dpmpp is DPM-Solver++(2M), linspace spacing unless
+--spacing says otherwise."""
+import argparse
 import os
 import sys
 import time
@@ -9,24 +15,36 @@ import torch
 import bench
 from stable_diffusion_training_amd import nets
 from stable_diffusion_training_amd.pipeline import StableDiffusionPipeline
-from stable_diffusion_training_amd.schedulers import DDIMScheduler
+from stable_diffusion_training_amd.schedulers import DDIMScheduler, DPMSolverMultistepScheduler
+
+ap = argparse.ArgumentParser()
+ap.add_argument("steps", nargs="?", type=int, default=20)
+ap.add_argument("--scheduler", choices=("ddim", "dpmpp"), default="ddim")
+ap.add_argument("--spacing", choices=("leading", "trailing", "linspace"), default=None)
+ap.add_argument("--guidance-rescale", type=float, default=0.0)
+args = ap.parse_args()
+steps = args.steps
+sched_kw = dict(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear")
+if args.spacing:
+    sched_kw["timestep_spacing"] = args.spacing
+scheduler = DDIMScheduler(**sched_kw) if args.scheduler == "ddim" else DPMSolverMultistepScheduler(**sched_kw)
+name = {"ddim": "DDIM", "dpmpp": "DPM-Solver++"}[args.scheduler]
 
 dev = torch.device("cuda", 0)
-steps = int(sys.argv[1]) if len(sys.argv) > 1 else 20
 tc, cfgs, weights, (us, ts, ue, te, vae, sched, objs) = bench.build_states(dev, 4, ema=False)
 w_vae = dict(weights["vae"])
 w_vae.update(nets.init_params(nets.vae_decoder_spec(cfgs["vae"]), 5))
-pipe = StableDiffusionPipeline(us, ts, w_vae, cfgs["unet"], cfgs["clip"], cfgs["vae"],
-                               scheduler=DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear"))
+pipe = StableDiffusionPipeline(us, ts, w_vae, cfgs["unet"], cfgs["clip"], cfgs["vae"], scheduler=scheduler)
 for B in (1, 4):
     ids = bench.synthetic_batch(dev, B, 0)["input_ids"]
     g = torch.Generator(device=dev)
     g.manual_seed(1)
-    pipe.generate(ids, num_inference_steps=2, generator=g)  # warm-up: workspaces, kernel attributes
+    pipe.generate(ids, num_inference_steps=2, generator=g, guidance_rescale=args.guidance_rescale)  # warm-up: workspaces, kernel attributes
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    img = pipe.generate(ids, num_inference_steps=steps, generator=g)
+    img = pipe.generate(ids, num_inference_steps=steps, generator=g, guidance_rescale=args.guidance_rescale)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
-    print(f"batch {B}: {steps} DDIM steps + decode  {dt:.3f} s  ({dt / B:.3f} s/image, {1e3 * dt / steps:.1f} ms/step incl. decode)  "
-          f"image {tuple(img.shape)} mean {float(img.mean()):.3f}", flush=True)
+    print(f"batch {B}: {steps} {name} steps ({scheduler.timestep_spacing}, rescale {args.guidance_rescale:g}) + decode  {dt:.3f} s  "
+          f"({dt / B:.3f} s/image, {1e3 * dt / steps:.1f} ms/step incl. decode)  image {tuple(img.shape)} mean {float(img.mean()):.3f}",
+          flush=True)
