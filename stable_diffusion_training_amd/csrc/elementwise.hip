@@ -243,7 +243,10 @@ __device__ __forceinline__ float act_bwd(float x, float dy) {
   }
   if (ACT == ACT_QUICK_GELU) {
     float s = sigmoidf_(1.702f * x);
-    return dy * s * (1.f + 1.702f * x * (1.f - s));
+    // |x| > 2e38: 1.702 * x overflows and inf * (1 - s) = inf * 0 (or dy * 0 * -inf) is NaN; s is exactly 0 or 1 from |x| ~ 52 on,
+    // so the clamped x gives the same bits for every input that was finite before
+    const float xc = fminf(fmaxf(x, -1.0e38f), 1.0e38f);
+    return dy * s * (1.f + 1.702f * xc * (1.f - s));
   }
   float cdf = 0.5f * (1.f + erff(x * 0.70710678118654752f));
   float pdf = 0.3989422804014327f * __expf(-0.5f * x * x);

@@ -115,7 +115,11 @@ __device__ __forceinline__ float gelu_tanh_grad(float x) {
   float u = k * (x + 0.044715f * x * x * x);
   float th = tanhf(u);
   float du = k * (1.f + 3.f * 0.044715f * x * x);
-  return 0.5f * (1.f + th) + 0.5f * x * (1.f - th * th) * du;
+  // |x| > 5e19: x * x overflows, du = inf, and 1 - th * th is 0 long before that (tanhf saturates at |u| ~ 9): the product
+  // would be 0 * inf = NaN for a finite gate whose derivative is 0 or 1.  The saturated tail has no second term.
+  const float sech2 = 1.f - th * th;
+  const float tail = sech2 == 0.f ? 0.f : 0.5f * x * sech2 * du;
+  return 0.5f * (1.f + th) + tail;
 }
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 __device__ __forceinline__ float siluf_(float x) { return x * sigmoidf_(x); }

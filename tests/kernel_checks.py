@@ -1,0 +1,699 @@
+"""Element-wise checkers for the kernel tests (tests/test_gpu_kernel_exact.py; proved on the CPU by tests/test_kernel_checks_cpu.py).
+
+The contraction kernels are "bf16 in, fp32 accumulate, round once per documented rounding point".  With small-integer operands
+every product and every partial sum is an integer below 2^24, so fp32 accumulation is exact in any order, tiling or split, and the
+result is unique: the fp32 accumulator equals the float64 reference and the bf16 output is its RNE rounding, bit for bit.  This
+module holds the operand generators, the expectations (float64 reference followed by the kernels' rounding points), the bitwise
+comparison with a report that names the tile edge, guarded allocations, per-slice error norms, and the case tables that the GPU
+file and the CPU proof share."""
+import math
+
+import torch
+
+BF = torch.bfloat16
+LIMIT = 1 << 24  # integers up to here are exact in fp32
+
+_INT_VIEW = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32, torch.float64: torch.int64,
+             torch.int8: torch.int8, torch.int32: torch.int32}
+# what an untouched output element holds: NaN patterns for the float types, so that an element the kernel never wrote also fails
+# the value comparison
+SENTINEL = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.float64: 0x7FF5A5A5A5A5A5A5, torch.int8: 0x5A}
+
+
+def bits(t):
+    """The integer view of a tensor's bit patterns."""
+    return t.contiguous().view(_INT_VIEW[t.dtype])
+
+
+# ------------------------------------------------------------------------------------------------ operands
+def exact_ints(shape, lo, hi, seed, dtype=BF, device="cpu"):
+    """Seeded integers in [lo, hi], exactly representable in bf16 (|v| <= 256)."""
+    assert -256 <= lo <= hi <= 256
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    return torch.randint(lo, hi + 1, tuple(shape), generator=g).to(dtype).to(device)
+
+
+def rne_bf16(x64):
+    """RNE rounding of float64 values that fp32 holds exactly (integers below 2^24): fp32 -> bf16 is torch's RNE cast."""
+    x32 = x64.to(torch.float32)
+    assert torch.equal(x32.double(), x64), "value not exact in fp32: the expectation would round twice"
+    return x32.to(BF)
+
+
+def abs_sum_bound(a_absmax, b_absmax, terms):
+    return a_absmax * b_absmax * terms
+
+
+# ------------------------------------------------------------------------------------------------ expectations
+def epilogue_nt(acc64, bias=None, rowbias=None, residual=None, rows_per_batch=0):
+    """The rounding points of the sdt_gemm_nt_bf16 epilogues, in order (gemm.hip gemm_nt_kernel "---- epilogue", lines 695-767,
+    and conv3x3_halo_kernel's, lines 1066-1111):
+      1. v = acc (+ bias[n], fp32) -> bf16 (pack2bf into the LDS C tile, gemm.hip:707-715 / 1081-1088);
+      2. only with a row bias or a residual: widen, (+ rowbias[m / rows_per_batch][n]) (+ residual[m][n]) in fp32 -> bf16
+         (gemm.hip:752-765 / 1102-1115).
+    With integer operands both sums are exact, so the result is unique."""
+    v = acc64 if bias is None else acc64 + bias.double()[None, :]
+    v = rne_bf16(v)
+    if rowbias is None and residual is None:
+        return v
+    f = v.double()
+    if rowbias is not None:
+        f = f + rowbias.double().repeat_interleave(rows_per_batch, 0)[: f.shape[0]]
+    if residual is not None:
+        f = f + residual.double()
+    return rne_bf16(f)
+
+
+def expect_gemm_nt(a, b, bias=None, rowbias=None, residual=None, rows_per_batch=0):
+    """a [M][K], b [K][N] (any dtype, integer valued) -> the bf16 output sdt_gemm_nt_bf16 must produce, bit for bit."""
+    return epilogue_nt(a.double() @ b.double(), bias, rowbias, residual, rows_per_batch)
+
+
+def conv_ref64(x, w, stride, pad):
+    """float64 NHWC convolution as one matrix product per tap: x (B,H,W,Cin), w (kh,kw,Cin,Cout) HWIO, pad ((top, bottom),
+    (left, right)).  The same operation as F.conv2d (the CPU proof compares the two); written with matmul so that it runs in
+    float64 on any device."""
+    (pt, pb), (pl, pr) = pad
+    B, H, W, Cin = x.shape
+    kh, kw, _, Cout = w.shape
+    OH, OW = (H + pt + pb - kh) // stride + 1, (W + pl + pr - kw) // stride + 1
+    xp = torch.nn.functional.pad(x.double(), (0, 0, pl, pr, pt, pb))
+    y = torch.zeros(B * OH * OW, Cout, dtype=torch.float64, device=x.device)
+    for i in range(kh):
+        for j in range(kw):
+            xs = xp[:, i: i + stride * (OH - 1) + 1: stride, j: j + stride * (OW - 1) + 1: stride, :]
+            y = y + xs.reshape(-1, Cin) @ w[i, j].double()
+    return y.view(B, OH, OW, Cout)
+
+
+def conv_dgrad_ref64(dy, w, in_hw, stride, pad):
+    """float64 input gradient of conv_ref64: dx (B,H,W,Cin) from dy (B,OH,OW,Cout)."""
+    (pt, pb), (pl, pr) = pad
+    B, OH, OW, Cout = dy.shape
+    kh, kw, Cin, _ = w.shape
+    H, W = in_hw
+    dxp = torch.zeros(B, H + pt + pb, W + pl + pr, Cin, dtype=torch.float64, device=dy.device)
+    for i in range(kh):
+        for j in range(kw):
+            t = (dy.double().reshape(-1, Cout) @ w[i, j].double().t()).view(B, OH, OW, Cin)
+            dxp[:, i: i + stride * (OH - 1) + 1: stride, j: j + stride * (OW - 1) + 1: stride, :] += t
+    return dxp[:, pt: pt + H, pl: pl + W, :]
+
+
+def conv_wgrad_ref64(x, dy, khw, stride, pad):
+    """float64 weight gradient of conv_ref64: dW (kh,kw,Cin,Cout)."""
+    (pt, pb), (pl, pr) = pad
+    kh, kw = khw
+    B, OH, OW, Cout = dy.shape
+    Cin = x.shape[-1]
+    xp = torch.nn.functional.pad(x.double(), (0, 0, pl, pr, pt, pb))
+    out = torch.empty(kh, kw, Cin, Cout, dtype=torch.float64, device=x.device)
+    for i in range(kh):
+        for j in range(kw):
+            xs = xp[:, i: i + stride * (OH - 1) + 1: stride, j: j + stride * (OW - 1) + 1: stride, :]
+            out[i, j] = xs.reshape(-1, Cin).t() @ dy.double().reshape(-1, Cout)
+    return out
+
+
+def expect_gn_parts(y, rows_of_tile, groups, tile_cols):
+    """The partial statistics rows include/sdt.h:231-236 assigns to the epilogues, from the stored bf16 output y [rows][N] of ONE
+    image: rows_of_tile is a list (one entry per output row tile r, in the kernel's tile order) of row-index tensors.  Row 2r takes,
+    for every group, the columns of the group that lie in the column tile the group STARTS in; row 2r+1 takes the columns that lie
+    in the next column tile (a group is at most one tile wide); slots nobody contributes to are written as zero.
+    Returns float64 [2 * len(rows_of_tile)][groups][2] = {sum, sum of squares}."""
+    N = y.shape[1]
+    cpg = N // groups
+    out = torch.zeros(2 * len(rows_of_tile), groups, 2, dtype=torch.float64)
+    yd = y.double().cpu()
+    for r, rows in enumerate(rows_of_tile):
+        blk = yd[rows.cpu()]
+        for g in range(groups):
+            lo, hi = g * cpg, (g + 1) * cpg
+            cut = min(hi, (lo // tile_cols + 1) * tile_cols)
+            for side, (a, b) in enumerate(((lo, cut), (cut, hi))):
+                if a < b:
+                    out[2 * r + side, g, 0] = blk[:, a:b].sum()
+                    out[2 * r + side, g, 1] = (blk[:, a:b] ** 2).sum()
+    return out
+
+
+def gn_dense_operands(M, N, Kc):
+    """a [M][Kc], b [Kc][N] in -1..1 and an fp32 bias in -1..1: the operands of the GroupNorm-statistics cases."""
+    return exact_ints((M, Kc), -1, 1, 11), exact_ints((Kc, N), -1, 1, 12), exact_ints((N,), -1, 1, 13, dtype=torch.float32)
+
+
+def gn_halo_operands(B, H, W, Cin, Cout):
+    return exact_ints((B, H, W, Cin), -1, 1, 21), exact_ints((3, 3, Cin, Cout), -1, 1, 22), exact_ints((Cout,), -1, 1, 23, dtype=torch.float32)
+
+
+# ------------------------------------------------------------------------------------------------ comparison
+def _coords(flat_idx, shape):
+    return [tuple(int(v) for v in c) for c in torch.stack(torch.unravel_index(flat_idx, shape), -1).tolist()]
+
+
+def mismatch_report(got, want, what, tile=None, limit=6):
+    """None when got and want hold the same bits; otherwise a message: the count, the first coordinates with both values, the
+    bounding box, and (tile = (rows, cols) of an output tile over the last two dimensions flattened to [rows][cols]) which
+    tiles and which rows / columns inside a tile the mismatches fall on."""
+    assert got.shape == want.shape and got.dtype == want.dtype, f"{what}: {tuple(got.shape)} {got.dtype} vs {tuple(want.shape)} {want.dtype}"
+    bad = bits(got) != bits(want)
+    n = int(bad.sum())
+    if n == 0:
+        return None
+    idx = bad.reshape(-1).nonzero().reshape(-1).cpu()
+    shape = tuple(got.shape)
+    first = _coords(idx[:limit], shape)
+    gc, wc = got.reshape(-1).cpu(), want.reshape(-1).cpu()
+    lines = [f"{what}: {n} of {got.numel()} elements differ"]
+    for c, i in zip(first, idx[:limit].tolist()):
+        lines.append(f"  at {c}: got {gc[i].item()!r} (0x{int(bits(gc[i:i + 1])[0]) & ((1 << (8 * got.element_size())) - 1):x}), want {wc[i].item()!r}")
+    allc = torch.stack(torch.unravel_index(idx, shape), -1)
+    lines.append(f"  bounding box: {tuple(int(v) for v in allc.min(0).values)} .. {tuple(int(v) for v in allc.max(0).values)}")
+    if tile is not None:
+        cols = shape[-1]
+        r, c = idx // cols, idx % cols
+        tr, tc = tile
+        tiles = sorted({(int(a), int(b)) for a, b in zip((r // tr).tolist(), (c // tc).tolist())})
+        lines.append(f"  output tiles ({tr} x {tc}) hit: {tiles[:8]}{' ...' if len(tiles) > 8 else ''} ({len(tiles)} tiles)")
+        lines.append(f"  rows inside a tile: {sorted(set((r % tr).tolist()))[:16]}; columns inside a tile: {sorted(set((c % tc).tolist()))[:16]}")
+    return "\n".join(lines)
+
+
+def assert_equal_bits(got, want, what, tile=None):
+    msg = mismatch_report(got, want, what, tile)
+    assert msg is None, msg
+
+
+# ------------------------------------------------------------------------------------------------ guarded allocations
+class Guarded:
+    """A payload [rows][ld], ld = width + pad (pad = 16 elements unless the ABI has no pitch for this operand: pad = 0), inside one
+    arena: front guard >= 4 KiB, back guard >= 128 rows of ld elements (one full tile of rows).  Base pointers are 16-byte aligned.
+    Outputs (data = None): every element holds SENTINEL; check() asserts afterwards that every guard element still does.
+    Inputs (data given): the guards hold `guard` (NaN: an out-of-range element that reaches the arithmetic surfaces in the
+    result) and check() asserts that the call left the whole arena alone."""
+
+    def __init__(self, rows, width, dtype, device, data=None, guard=float("nan"), pad=16, back_rows=128):
+        self.rows, self.width, self.ld, self.dtype = rows, width, width + pad, dtype
+        es = torch.empty(0, dtype=dtype).element_size()
+        self.front = -(-4096 // es)
+        while (self.front * es) % 16:
+            self.front += 1
+        back = max(back_rows * self.ld, self.front)
+        self.arena = torch.empty(self.front + rows * self.ld + back, dtype=dtype, device=device)
+        self.is_input = data is not None
+        if self.is_input:
+            if dtype.is_floating_point:
+                self.arena.fill_(guard)
+            else:
+                self.arena.fill_(int(guard))
+            self.t.copy_(data.reshape(rows, width).to(dtype))
+            self.before = self.arena.clone()
+        else:
+            s = SENTINEL[dtype]
+            iv = _INT_VIEW[dtype]
+            top = 1 << (8 * es)
+            self.arena.view(iv).fill_(s - top if s >= top // 2 else s)
+        assert self.ptr % 16 == 0
+
+    @property
+    def t(self):
+        """The payload as a strided [rows][width] view."""
+        return self.arena[self.front: self.front + self.rows * self.ld].view(self.rows, self.ld)[:, : self.width]
+
+    @property
+    def ptr(self):
+        return self.arena.data_ptr() + self.front * self.arena.element_size()
+
+    def guard_report(self, what):
+        """None, or a message naming where the arena outside the payload (inputs: anywhere) was changed."""
+        if self.is_input:
+            bad = bits(self.arena) != bits(self.before)
+        else:
+            ref = torch.empty_like(self.arena)
+            s = SENTINEL[self.dtype]
+            top = 1 << (8 * self.arena.element_size())
+            ref.view(_INT_VIEW[self.dtype]).fill_(s - top if s >= top // 2 else s)
+            bad = bits(self.arena) != bits(ref)
+            bad[self.front: self.front + self.rows * self.ld].view(self.rows, self.ld)[:, : self.width] = False
+        n = int(bad.sum())
+        if n == 0:
+            return None
+        idx = bad.nonzero().reshape(-1).cpu().tolist()
+        where = []
+        for i in idx[:6]:
+            if i < self.front:
+                where.append(f"front guard, {self.front - i} elements before the base")
+            elif i >= self.front + self.rows * self.ld:
+                j = i - self.front - self.rows * self.ld
+                where.append(f"back guard, row {self.rows + j // self.ld} column {j % self.ld}")
+            else:
+                j = i - self.front
+                where.append(f"{'payload' if j % self.ld < self.width else 'pad'} row {j // self.ld} column {j % self.ld}")
+        return f"{what}: {n} guarded elements changed ({'input' if self.is_input else 'output'} arena, ld {self.ld}, width {self.width}): " + "; ".join(where)
+
+    def check(self, what):
+        msg = self.guard_report(what)
+        assert msg is None, msg
+
+
+# ------------------------------------------------------------------------------------------------ per-slice norms
+def per_slice_rel(got, ref, dims, mag=None):
+    """Relative L2 error of every slice: the norm runs over `dims`, one figure per index of the remaining dimensions.
+    mag (optional, same shape): per element, the sum of the magnitudes of the terms the reference value is the sum of.  The
+    denominator is then max(||ref||, 2^-9 ||mag||) over the slice: a slice computed from bf16-rounded factors carries an absolute
+    error of the order of one bf16 rounding (2^-9) of its terms whatever the terms add up to, so where the reference has
+    cancelled below that (exactly zero for query 0 of a causal problem) "relative to the reference" is not defined by the
+    arithmetic and the error is measured against the rounding of the terms instead."""
+    g, r = got.double(), ref.double()
+    num = ((g - r) ** 2).sum(dims).sqrt()
+    den = (r ** 2).sum(dims).sqrt()
+    if mag is not None:
+        den = torch.maximum(den, 2.0 ** -9 * (mag.double() ** 2).sum(dims).sqrt())
+    return num / den.clamp_min(1e-300)
+
+
+def floor_binds(ref, dims, mag):
+    """Per slice: whether per_slice_rel measures against the floor 2^-9 ||mag|| instead of ||ref||."""
+    return (ref.double() ** 2).sum(dims).sqrt() < 2.0 ** -9 * (mag.double() ** 2).sum(dims).sqrt()
+
+
+def worst_slices(rel, k=3):
+    """[(index tuple, error)] of the k worst slices of a per_slice_rel result."""
+    flat = rel.reshape(-1)
+    v, i = flat.topk(min(k, flat.numel()))
+    return [(c, float(e)) for c, e in zip(_coords(i.cpu(), tuple(rel.shape)), v.tolist())]
+
+
+# ------------------------------------------------------------------------------------------------ selector attention
+def selector_case(B, H, Nq, Nk, D, causal, seed, c=32.0, vmax=8, domax=3):
+    """Inputs whose attention is exactly a gather.  Key j of (b, h) carries the code c * (+-1 per bit of s(j)) on the first
+    ceil(log2 Nk) head dimensions (s a seeded permutation), query i the code of its target key t(i): the matching key beats every
+    other by at least 2 c^2 / sqrt(D) logits, every other probability underflows to 0 in fp32, P is one-hot.  Non-causal:
+    t(i) = p(i mod Nk) for a seeded permutation p; causal: t(i) seeded in [0, i], the diagonal included (t(0) = 0).
+    Returns dict(q, k, v, dout: bf16 (B, N, H*D); target: int64 (B, H, Nq); nbits)."""
+    nb = max(1, math.ceil(math.log2(max(Nk, 2))))
+    assert nb <= D
+    g = torch.Generator().manual_seed(seed)
+    q = torch.zeros(B, Nq, H, D)
+    k = torch.zeros(B, Nk, H, D)
+    target = torch.empty(B, H, Nq, dtype=torch.int64)
+    sh = torch.arange(nb)
+    for b in range(B):
+        for h in range(H):
+            s = torch.randperm(Nk, generator=g)
+            if causal:
+                t = (torch.rand(Nq, generator=g) * (torch.arange(Nq).clamp_max(Nk - 1) + 1)).long().clamp_max(Nk - 1)
+                t = torch.minimum(t, torch.arange(Nq).clamp_max(Nk - 1))
+                if Nq > 1:
+                    t[Nq - 1] = min(Nq, Nk) - 1  # the diagonal itself at least once
+            else:
+                t = torch.randperm(Nk, generator=g)[torch.arange(Nq) % Nk]
+            target[b, h] = t
+            k[b, :, h, :nb] = (((s[:, None] >> sh) & 1) * 2 - 1).float() * c
+            q[b, :, h, :nb] = (((s[t][:, None] >> sh) & 1) * 2 - 1).float() * c
+    v = torch.randint(-vmax, vmax + 1, (B, Nk, H * D), generator=g).float()
+    do = torch.randint(-domax, domax + 1, (B, Nq, H * D), generator=g).float()
+    return dict(q=q.reshape(B, Nq, H * D).to(BF), k=k.reshape(B, Nk, H * D).to(BF), v=v.to(BF), dout=do.to(BF), target=target, nbits=nb, c=c)
+
+
+def selector_expect(case, B, H, Nq, Nk, D, scale, key_weight=None):
+    """out (bf16), lse2 (float64, log2 domain: attention.hip:8-9), dv (bf16) of a selector case; dq and dk are zero by value."""
+    t = case["target"]
+    v4 = case["v"].view(B, Nk, H, D)
+    do4 = case["dout"].view(B, Nq, H, D).double()
+    out = torch.empty(B, Nq, H, D, dtype=BF)
+    dv = torch.zeros(B, Nk, H, D, dtype=torch.float64)
+    for b in range(B):
+        for h in range(H):
+            out[b, :, h] = v4[b, t[b, h], h]
+            dv[b, :, h].index_add_(0, t[b, h], do4[b, :, h])
+    logit = case["nbits"] * case["c"] ** 2 * float(torch.tensor(scale, dtype=torch.float32))
+    lse2 = torch.full((B, H, Nq), logit * 1.4426950408889634, dtype=torch.float64)
+    if key_weight is not None:
+        lse2 = lse2 + torch.log2(key_weight.double().cpu())[t]
+    return out.reshape(B, Nq, H * D), lse2, rne_bf16(dv).reshape(B, Nk, H * D)
+
+
+def selector_min_gap(case, B, H, Nq, Nk, D, scale):
+    """Smallest logit gap between the target key and the runner-up, and the largest logit (float64)."""
+    q4, k4 = case["q"].view(B, Nq, H, D).double(), case["k"].view(B, Nk, H, D).double()
+    gap, top = float("inf"), 0.0
+    for b in range(B):
+        for h in range(H):
+            s = (q4[b, :, h] @ k4[b, :, h].t()) * scale
+            win = s.gather(1, case["target"][b, h][:, None])
+            s2 = s.scatter(1, case["target"][b, h][:, None], float("-inf"))
+            if Nk > 1:
+                gap = min(gap, float((win[:, 0] - s2.max(1).values).min()))
+            top = max(top, float(win.max()))
+    return gap, top
+
+
+def attention_msum(D):
+    """Whether the forward kernel takes the softmax row sum from a ones column of the P.V MFMAs (the sum of the ROUNDED
+    probabilities) instead of an fp32 sum of the unrounded ones: D <= NB * 32 - 8 for the head dim's instantiation
+    (attention.hip:174-176, 702, 745-750)."""
+    nb = 2 if D <= 64 else 3 if D <= 96 else 4 if D <= 128 else 5
+    return D <= nb * 32 - 8
+
+
+def attention_ref_and_emulation(q, k, v, do, H, scale, causal=False, key_weight=None):
+    """float64 attention (forward and the three gradients) and a torch emulation of the kernels' rounding points, head by head on
+    the tensors' device.  q, do (B, Nq, H*D), k, v (B, Nk, H*D) bf16.  The emulation computes in float64 and rounds where the
+    kernels round:
+      forward (attention.hip:222-328): keys in tiles of 64; the probabilities are formed UNNORMALISED against the running row
+        maximum, Pt = exp2(s * scale2 - m * scale2) (:268-276) (* w), and m is only raised - for all 32 queries of a wave at once -
+        when some row's tile maximum exceeds it by more than 2^8 (:258-267), so Pt may exceed 1; Pt is rounded to bf16 for the P.V
+        product (:301); the row sum l adds the unrounded Pt in fp32 (:286-291) or, for head dims with a spare padded feature, the
+        rounded ones through a ones column (:310, attention_msum); O = bf16(acc / l) (:323); lse2 = fp32(m * scale2 + log2 l) (:314).
+      backward (:371-390, :414-437, :455; :547-582, :622-627): delta = sum_d dO * O with the STORED bf16 O; P = exp2(s * scale2 -
+        lse2) from the stored fp32 lse2; dS = P (dP - delta) rounded to bf16 before dS.K and dS^T.Q; P rounded to bf16 before
+        P^T.dO; dQ = bf16(scale * acc), dK likewise, dV = bf16(acc).
+    Left out: fp32 accumulation order, the hardware exp2.
+    Returns (ref, emu, mag): dicts of float64 tensors o, dq, dk, dv in the input layout; mag holds, per element, the sum of the
+    magnitudes of the terms before any cancellation (o: P |V|; dv: P^T |dO|; dq: scale * (P (|dP| + |delta|)) |K|; dk likewise
+    with |Q|) - the denominator floor of per_slice_rel for rows that are the result of cancellation."""
+    B, Nq, C = q.shape
+    Nk, D = k.shape[1], C // H
+    dev = q.device
+    names = ("o", "dq", "dk", "dv")
+    ref = {n: torch.empty(B, (Nq if n in ("o", "dq") else Nk), C, dtype=torch.float64, device=dev) for n in names}
+    emu = {n: torch.empty_like(t) for n, t in ref.items()}
+    mag = {n: torch.empty_like(t) for n, t in ref.items()}
+    r16 = lambda t: t.to(torch.float32).to(BF).double()
+    f32 = lambda x: torch.tensor(x, dtype=torch.float32)
+    scale_f = float(f32(scale))
+    scale2 = float(f32(scale) * f32(1.4426950408889634))  # attention.hip:683, an fp32 product
+    msum = attention_msum(D)
+    NEG = -1.0e30
+    allowed = None
+    if causal:
+        allowed = torch.arange(Nk, device=dev)[None, :] <= torch.arange(Nq, device=dev)[:, None]
+    w = None if key_weight is None else key_weight.double().to(dev)
+    nw = -(-Nq // 32)
+    for b in range(B):
+        for h in range(H):
+            sl = slice(h * D, (h + 1) * D)
+            qh, kh, vh, doh = (t[b, :, sl].double() for t in (q, k, v, do))
+            sr = qh @ kh.t()  # raw scores (exact: bf16 products, a sum far below 2^53)
+            s = sr * scale
+            if w is not None:
+                s = s + torch.log(w)
+            if allowed is not None:
+                s = s.masked_fill(~allowed, float("-inf"))
+            p = torch.softmax(s, -1)
+            del s
+            dp = doh @ vh.t()
+            # ---- float64 reference and term magnitudes
+            o = p @ vh
+            delta = (doh * o).sum(-1, keepdim=True)
+            ds = p * (dp - delta)
+            ref["o"][b, :, sl], ref["dv"][b, :, sl] = o, p.t() @ doh
+            ref["dq"][b, :, sl], ref["dk"][b, :, sl] = (ds @ kh) * scale, (ds.t() @ qh) * scale
+            am = p * (dp.abs() + delta.abs())
+            mag["o"][b, :, sl], mag["dv"][b, :, sl] = p @ vh.abs(), p.t() @ doh.abs()
+            mag["dq"][b, :, sl], mag["dk"][b, :, sl] = (am @ kh.abs()) * scale, (am.t() @ qh.abs()) * scale
+            del p, ds, am
+            # ---- forward as the kernel runs it
+            st = sr if allowed is None else sr.masked_fill(~allowed, NEG)
+            m = torch.full((Nq,), NEG, dtype=torch.float64, device=dev)
+            l = torch.zeros(Nq, dtype=torch.float64, device=dev)
+            acc = torch.zeros(Nq, D, dtype=torch.float64, device=dev)
+            for kb in range(0, Nk, 64):
+                t = st[:, kb: kb + 64]
+                mx = t.max(1).values
+                trig = (mx - m) * scale2 > 8.0
+                trig = torch.nn.functional.pad(trig, (0, nw * 32 - Nq)).view(nw, 32).any(1).repeat_interleave(32)[:Nq]
+                m_new = torch.where(trig, torch.maximum(m, mx), m)
+                alpha = torch.exp2((m - m_new) * scale2)
+                m, l, acc = m_new, l * alpha, acc * alpha[:, None]
+                pt = torch.exp2(t * scale2 - (m * scale2)[:, None])
+                if w is not None:
+                    pt = pt * w[kb: kb + 64]
+                ptb = r16(pt)
+                l = l + (ptb if msum else pt).sum(1)
+                acc = acc + ptb @ vh[kb: kb + 64]
+            ob = r16(acc / l[:, None])
+            lse2 = (m * scale2 + torch.log2(l)).to(torch.float32).double()
+            # ---- backward
+            pbw = torch.exp2(sr * scale2 - lse2[:, None])
+            if allowed is not None:
+                pbw = pbw.masked_fill(~allowed, 0.0)
+            if w is not None:
+                pbw = pbw * w
+            dsb = r16(pbw * (dp - (doh * ob).sum(-1, keepdim=True)))
+            pb = r16(pbw)
+            emu["o"][b, :, sl], emu["dv"][b, :, sl] = ob, r16(pb.t() @ doh)
+            emu["dq"][b, :, sl], emu["dk"][b, :, sl] = r16((dsb @ kh) * scale_f), r16((dsb.t() @ qh) * scale_f)
+            del sr, st, dp, pbw, dsb, pb
+    return ref, emu, mag
+
+
+# ------------------------------------------------------------------------------------------------ norms
+def _silu_and_grad(z):
+    s = torch.sigmoid(z)
+    return z * s, s * (1 + z * (1 - s))
+
+
+def norm_ref_and_emulation(x, gamma, beta, dy, groups, eps, silu):
+    """float64 GroupNorm (groups > 0: x (B, HW, C), statistics per image and group) or LayerNorm (groups = 0: x (M, C), per row),
+    forward and backward, and an emulation of the kernels' rounding points (norm.hip): the statistics, the normalisation and the
+    gradient formula are evaluated in fp32 and y / dx are rounded to bf16 ONCE when stored (gn_apply_kernel :189-195,
+    gn_bwd_apply_kernel :392-407, ln_fwd_kernel :449-450, ln_bwd_kernel :523-531); dgamma / dbeta are fp32 sums of fp32 terms
+    (gn_bwd_stats_kernel :246-250, partial_reduce_kernel).  The emulation therefore runs the same formulas in torch fp32 (torch's
+    own summation order) and rounds y and dx to bf16.
+    Returns (ref, emu, terms): ref / emu dicts of y, dx, dgamma, dbeta (ref float64); terms: per channel, sum |terms| of dgamma
+    and dbeta (float64) - the denominator of their per-channel error."""
+    out = []
+    for dt in (torch.float64, torch.float32):
+        xf, dyf, g, b = x.to(dt), dy.to(dt), gamma.to(dt), beta.to(dt)
+        if groups:
+            B, HW, C = xf.shape
+            xg = xf.view(B, HW, groups, C // groups)
+            red = (1, 3)
+        else:
+            xg, red = xf, (1,)
+        mean = xg.mean(red, keepdim=True)
+        var = (xg * xg).mean(red, keepdim=True) - mean * mean
+        rstd = torch.rsqrt(var + eps)
+        xh = ((xg - mean) * rstd).view(xf.shape)
+        z = xh * g + b
+        if silu:
+            y, dact = _silu_and_grad(z)
+            dz = dyf * dact
+        else:
+            y, dz = z, dyf
+        dxh = dz * g
+        sh = xg.shape
+        m1 = dxh.view(sh).mean(red, keepdim=True)
+        m2 = (dxh * xh).view(sh).mean(red, keepdim=True)
+        dx = (rstd * (dxh.view(sh) - m1 - xh.view(sh) * m2)).view(xf.shape)
+        lead = tuple(range(xf.dim() - 1))
+        res = dict(y=y, dx=dx, dgamma=(dz * xh).sum(lead), dbeta=dz.sum(lead))
+        if dt == torch.float64:
+            terms = dict(dgamma=(dz * xh).abs().sum(lead), dbeta=dz.abs().sum(lead))
+        out.append(res)
+    ref, emu = out
+    emu = dict(y=emu["y"].to(BF).double(), dx=emu["dx"].to(BF).double(), dgamma=emu["dgamma"].double(), dbeta=emu["dbeta"].double())
+    return ref, emu, terms
+
+
+# ------------------------------------------------------------------------------------------------ activations
+def act_ref64(kind, x):
+    """float64 value and derivative of the activations (x float64): 'silu', 'quick_gelu', 'gelu_erf', 'gelu_tanh'.  The tails are
+    written without cancellation (erfc, sigmoid) so that the reference is accurate where the fp32 kernels are not."""
+    if kind == "silu":
+        s = torch.sigmoid(x)
+        return x * s, s * (1 + x * (1 - s))
+    if kind == "quick_gelu":
+        s = torch.sigmoid(1.702 * x)
+        return x * s, s * (1 + 1.702 * x * (1 - s))
+    if kind == "gelu_erf":
+        cdf = 0.5 * torch.special.erfc(-x * 0.7071067811865476)
+        pdf = 0.3989422804014327 * torch.exp(-0.5 * x * x)
+        return x * cdf, cdf + x * pdf
+    if kind == "gelu_tanh":
+        k = 0.7978845608028654
+        u = k * (x + 0.044715 * x * x * x)
+        s = torch.sigmoid(2 * u)                 # 0.5 * (1 + tanh u)
+        sech2 = 4 * s * (1 - s)                  # 1 - tanh(u)^2
+        du = k * (1 + 3 * 0.044715 * x * x)
+        return x * s, s + 0.5 * x * sech2 * du
+    raise ValueError(kind)
+
+
+def bf16_ulp(v):
+    """One bf16 unit in the last place at the magnitude of v (float64 tensor of bf16-representable values; 2^-133 below the normals)."""
+    e = torch.floor(torch.log2(v.abs().clamp_min(2.0 ** -126)))
+    return torch.exp2(e - 7)
+
+
+def all_bf16_patterns():
+    """All 65536 bf16 bit patterns (already a multiple of 8) as a bf16 tensor."""
+    return torch.arange(65536, dtype=torch.int32).to(torch.int16).view(BF)
+
+
+def act_bound_violations(got, ref64, x64, dy_abs):
+    """Indices where a finite activation result misses  |got - RNE_bf16(ref)| <= max(1 bf16 ulp of RNE_bf16(ref),
+    8 * 2^-24 * max(|x|, 1) * |dy|)  (both terms derived in DESIGN.md "kernel test tolerances"); evaluated in float64."""
+    want = ref64.to(torch.float32).to(BF).double()
+    bound = torch.maximum(bf16_ulp(want), 8 * 2.0 ** -24 * x64.abs().clamp_min(1.0) * dy_abs)
+    err = (got.double() - want).abs()
+    return (~(err <= bound)).nonzero().reshape(-1)
+
+
+# ------------------------------------------------------------------------------------------------ case tables
+# sdt_gemm_nt_bf16, plain rows: (id, M, N, Kc, taps, b_kmajor, b_nseg, bias, rows_per_batch (0 = no row bias), residual, workspace,
+# split, tile edge) - `split` is what sdt_gemm_nt_workspace_bytes must say (> 0 or == 0), the tile edge (64 / 128) is the kernel's
+# output tile, named in a failure report; every case runs with ldc, ldres, ld_rowbias = N + 16
+# and lda = taps * Kc + 16.  Branches of plan_nt / sdt_gemm_nt_bf16 (gemm.hip:1766-1797, 2123-2151):
+GEMM_PLAIN_CASES = [
+    ("t64_m1_n8_k8", 1, 8, 8, 1, 0, 0, True, 0, False, False, False, 64),           # 64-tiles at their smallest: M = 1, N = 8, Kc = 8
+    ("t64_m5_kmajor", 5, 72, 40, 1, 1, 0, True, 0, True, False, False, 64),          # 64-tiles, k-major B, N % 64 == 8, Kc % 64 == 40
+    ("t64_m63_rowbias", 63, 136, 72, 1, 0, 0, True, 21, True, False, False, 64),     # 64-tiles, row bias of 3 batches, Kc % 32 == 8
+    ("t64_m65", 65, 200, 104, 1, 1, 0, False, 13, False, False, False, 64),          # 64-tiles, M % 64 == 1, N % 128 == 72, row bias only
+    ("t64_m127", 127, 64, 64, 1, 0, 0, False, 0, True, False, False, 64),            # 64-tiles, one short row, residual only
+    ("t64_m129", 129, 320, 320, 1, 1, 0, True, 43, True, False, False, 64),          # 64-tiles, M % 128 == 1 on three row tiles
+    ("t64_taps3", 130, 72, 40, 3, 0, 0, True, 0, True, False, False, 64),            # plain rows with taps = 3: the shared-input dgrad
+    ("t64_taps2_kmajor", 70, 136, 72, 2, 1, 0, True, 0, False, False, False, 64),    # ... with a k-major B
+    ("t64_nseg", 300, 192, 72, 1, 1, 64, True, 0, True, False, False, 64),           # three 64-wide column segments (b_nseg)
+    ("k32_m33025", 33025, 136, 72, 1, 1, 0, True, 6605, True, False, False, 128),     # 128-tiles, 32-wide K-steps, a large M % 128 == 1, all epilogue terms
+    ("k32_rowmajor", 33025, 136, 72, 1, 0, 0, True, 0, True, False, False, 128),      # ... with a row-major Bt
+    ("t128_k64", 4097, 1096, 1320, 1, 1, 0, True, 0, True, False, False, 128),        # 128-tiles, 64-wide K-steps (T = 21 > 20), N % 128 == 72, Kc % 64 == 40
+    ("t128_k64_rowmajor", 4097, 1096, 1320, 1, 0, 0, False, 241, False, False, False, 128),
+    ("t128_nosplit", 512, 520, 3080, 1, 1, 0, True, 0, True, False, True, 128),       # a split-K shape WITHOUT workspace: unsplit 128-tiles
+    ("splitk128", 512, 520, 3080, 1, 1, 0, True, 128, True, True, True, 128),         # split-K, 128-tiles (T = 49, 20 tiles)
+    ("splitk64", 200, 72, 4104, 1, 1, 0, True, 0, True, True, True, 64),             # split-K, 64-tiles (8 tiles, T = 65, Kc % 64 == 8)
+    ("splitk64_rowmajor", 200, 72, 4104, 1, 0, 0, True, 50, True, True, True, 64),
+    ("splitk64_few", 5, 1280, 1280, 1, 1, 0, True, 0, False, True, True, 64),        # a handful of tiles (time-embedding shape): T / 4 splits
+]
+
+# sdt_gemm_nt_bf16, gathered rows (fprop and dgrad): geometries of tests/test_gpu_kernels.py CONV_CASES (the CPU proof asserts
+# membership), each with the kernel it is for
+CONV_EXACT_CASES = [
+    # B, H, W, Cin, Cout, k, stride, pad
+    (2, 16, 16, 64, 64, 3, 1, 1),                    # halo 16 x 16 tile = one image, unsplit or split by the planner
+    (2, 16, 16, 64, 128, 3, 2, 1),                   # stride 2: generic gather; its dgrad is the GENERIC kernel
+    (2, 16, 16, 64, 64, 3, 2, ((0, 1), (0, 1))),     # the VAE's asymmetric padding
+    (2, 256, 256, 64, 128, 3, 2, ((0, 1), (0, 1))),  # gathered rows through the 32-wide-step 128-tile kernel
+    (2, 8, 8, 128, 64, 1, 1, 0),                     # 1x1 (plain rows)
+    (2, 12, 20, 8, 32, 3, 1, 1),                     # conv_in pack-8 path, 64-tiles
+    (4, 64, 64, 8, 320, 3, 1, 1),                    # conv_in pack-8 path, 128-tiles, ragged channel tile
+    (2, 16, 16, 320, 8, 3, 1, 1),                    # conv_out: N = 8
+    (3, 8, 8, 2560, 1280, 3, 1, 1),                  # halo 8 x 8 x four images, ragged image group (3 of 4), split, the largest reduction: 9 * 2560
+    (2, 64, 64, 320, 320, 3, 1, 1),                  # halo 4 x 64 tiles, N = 2.5 / 5 channel tiles, split
+    (1, 8, 128, 128, 128, 3, 1, 1),                  # halo 4 x 64, two tiles per row
+    (2, 32, 32, 640, 1280, 3, 1, 1),                 # halo 8 x 32 tiles, split over channel chunks
+    (2, 36, 28, 64, 64, 3, 1, 1),                    # not tileable: the generic path
+    (2, 24, 40, 64, 64, 3, 1, 1),                    # halo 8 x 8, two of the four image slots empty
+    (3, 16, 24, 64, 128, 3, 1, 1),                   # halo 8 x 8, ragged image group (3 of 4)
+    (1, 32, 48, 128, 64, 3, 1, 1),                   # halo 16 x 16, 2 x 3 tiles per image
+    (1, 256, 320, 64, 128, 3, 1, 1),                 # halo 4 x 64, 320 tiles, unsplit
+]
+
+# weight gradients.  Dense (sdt_gemm_tn_wgrad plain, and the same problems through sdt_gemm_tn_wgrad_group):
+# (id, M, K1, N, K1_valid, N_valid, n_seg, split) - split: sdt_gemm_tn_workspace_bytes > 0
+WGRAD_DENSE_CASES = [
+    ("t64_small", 100, 64, 136, 64, 136, 0, False),          # 64-tiles (K1 < 128), ragged N
+    ("t64_valid", 77, 72, 72, 68, 70, 0, False),             # K1_valid < K1, N_valid < N
+    ("t128", 300, 320, 320, 320, 320, 0, False),             # 128-tiles, 2.5 tiles each way, unsplit (M < 2 * 1024)
+    ("t128_valid", 1000, 136, 264, 130, 260, 0, False),
+    ("t128_split", 16384, 320, 320, 320, 320, 0, True),      # split reduction over M
+    ("t64_split", 4096, 64, 72, 64, 72, 0, True),
+    ("t128_seg", 2048, 320, 960, 320, 960, 320, True),       # three 320-wide segments (to_q / to_k / to_v), split
+    ("t64_seg", 130, 72, 192, 72, 192, 64, False),
+]
+# convolutions (sdt_gemm_tn_wgrad in fprop-gather mode and sdt_conv_wgrad_group): (B, H, W, Cin, Cout, k, stride, pad, kernel)
+WGRAD_CONV_CASES = [
+    (1, 96, 96, 64, 64, 3, 1, 1, "three-tap, 96 wide (a chunk is 2/3 of a row), split"),
+    (2, 48, 48, 128, 64, 3, 1, 1, "three-tap, 48 wide, split"),
+    (4, 24, 24, 64, 136, 3, 1, 1, "three-tap, 24 wide, ragged channel tile, split"),
+    (8, 12, 12, 64, 64, 3, 1, 1, "nine-tap (12 wide is not a multiple of 8), split"),
+    (4, 8, 8, 128, 72, 3, 1, 1, "three-tap at its smallest, one pass"),
+    (4, 64, 64, 64, 64, 3, 1, 1, "three-tap, 64 wide, split"),
+    (2, 16, 16, 64, 128, 3, 2, 1, "nine-tap, stride 2 (row walk), one pass"),
+    (16, 4, 4, 64, 64, 3, 1, 1, "nine-tap generic (fewer than 64 pixels per image), one pass"),
+    (2, 12, 20, 8, 32, 3, 1, 1, "nine-tap, 8 input channels, one pass"),
+]
+# (a case whose description ends in "split" must get scratch from sdt_gemm_tn_workspace_bytes, the others none)
+
+# GroupNorm statistics from the epilogues: operands in -1..1, Kc <= 64, so that the fp32 sums and sums of squares of the bf16 outputs
+# stay below 2^24 (asserted by the CPU proof on the very operands).  Dense: (M, N, Kc, rows_per_batch, groups); halo: conv geometry + groups
+GN_DENSE_CASES = [
+    (512, 320, 64, 256, 32),     # 64-tiles: groups of 10 columns straddle the tile edges at 64, 128, ...
+    (33024, 160, 64, 16512, 32),  # 128-tiles (32-wide K-steps), ragged second channel tile, 129 row tiles per image
+]
+GN_HALO_CASES = [
+    (2, 64, 64, 64, 320, 32),    # 4 x 64 tiles, N = 2.5 / 5 channel tiles: groups of 10 straddle
+    (1, 32, 32, 64, 96, 32),     # 8 x 32 tiles, groups of 3 over a ragged channel tile
+    (2, 32, 48, 64, 64, 32),     # 16 x 16 tiles, one channel tile
+]
+
+# attention, selector inputs: the shapes of test_attention_fwd_bwd / test_attention_key_weights.
+# (B, H, Nq, Nk, D, causal, packed, key_weights)
+ATTN_SELECTOR_CASES = [
+    (2, 8, 256, 256, 40, False, False, False),
+    (1, 8, 1024, 1024, 40, False, True, False),
+    (2, 8, 64, 77, 160, False, False, True),     # head dim 160, ragged Nk, key weights of the clamped chunks
+    (2, 8, 256, 77, 80, False, False, False),
+    (2, 5, 144, 144, 64, False, False, False),
+    (3, 12, 77, 77, 64, True, False, False),     # causal, ragged
+    (1, 3, 77, 77, 16, True, False, False),      # causal, head dim 16
+    (1, 2, 200, 333, 128, False, True, False),   # head dim 128, ragged Nq and Nk, packed k|v
+    (1, 5, 9216, 9216, 64, False, False, False),  # the long self-attention
+    (2, 8, 2048, 77, 40, False, True, True),     # few keys: the query-split dK/dV pass, packed, synthetic key weights
+    (1, 4, 1100, 100, 64, False, False, False),  # query-split, ragged
+    (4, 8, 1024, 77, 80, False, False, True),    # query-split, head dim 80, key weights
+    (1, 8, 144, 231, 80, False, True, True),
+]
+
+
+def halo_tile(H, W, Cin, M, k, stride, pad):
+    """(images, rows, columns) of the tile conv_halo_plan (gemm.hip:1960-1982) gives a 3x3 / stride 1 / pad 1 convolution, or None
+    where it declines.  A mirror of the planner: it decides which cases run at both tile widths and names the tile in a report.  The
+    CPU proof holds it to the library (sdt_gemm_nt_gn_parts) for every convolution case."""
+    if k != 3 or stride != 1 or norm_pad(pad) != ((1, 1), (1, 1)) or Cin % 64 or M < 256:
+        return None
+    if W % 64 == 0 and H % 4 == 0:
+        return (1, 4, 64)
+    if W == 32 and H % 8 == 0:
+        return (1, 8, 32)
+    if W % 16 == 0 and H % 16 == 0:
+        return (1, 16, 16)
+    if W % 8 == 0 and H % 8 == 0:
+        return (4, 8, 8)
+    return None
+
+
+def norm_pad(pad):
+    return ((pad, pad), (pad, pad)) if isinstance(pad, int) else pad
+
+
+def conv_out_hw(H, W, k, stride, pad):
+    (pt, pb), (pl, pr) = norm_pad(pad)
+    return (H + pt + pb - k) // stride + 1, (W + pl + pr - k) // stride + 1
+
+
+def exact_reductions():
+    """(what, |a|max, |b|max, terms) of every exact contraction the GPU file runs: sum |a||b| <= |a|max |b|max terms must stay below
+    2^24 (the CPU proof asserts it).  Operand ranges: GEMM_RANGE for forward / input-gradient operands, WGRAD_RANGE for the weight
+    gradients (their reduction runs over M)."""
+    out = []
+    for c in GEMM_PLAIN_CASES:
+        out.append((f"gemm {c[0]}", GEMM_RANGE, GEMM_RANGE, c[4] * c[3]))
+    for B, H, W, Cin, Cout, k, stride, pad in CONV_EXACT_CASES:
+        out.append((f"conv fprop {(B, H, W, Cin, Cout)}", GEMM_RANGE, GEMM_RANGE, k * k * Cin))
+        out.append((f"conv dgrad {(B, H, W, Cin, Cout)}", GEMM_RANGE, GEMM_RANGE, k * k * Cout))
+    for c in WGRAD_DENSE_CASES:
+        out.append((f"wgrad {c[0]}", WGRAD_RANGE, WGRAD_RANGE, c[1]))
+    for B, H, W, Cin, Cout, k, stride, pad, _ in WGRAD_CONV_CASES:
+        OH, OW = conv_out_hw(H, W, k, stride, pad)
+        out.append((f"conv wgrad {(B, H, W, Cin, Cout)}", WGRAD_RANGE, WGRAD_RANGE, B * OH * OW))
+    for B, H, Nq, Nk, D, *_ in ATTN_SELECTOR_CASES:
+        out.append((f"attention dV {(B, H, Nq, Nk, D)}", 3, 1, Nq))
+    return out
+
+
+GEMM_RANGE = 3   # operands of the forward / input-gradient contractions: integers in -3..3
+WGRAD_RANGE = 3  # operands of the weight gradients
+EPI_RANGE = 5    # bias, row bias, residual: integers in -5..5
