@@ -172,7 +172,8 @@ __global__ void __launch_bounds__(256) posterior_sample_kernel(const bf16_t* __r
     const int b = (int)(bp / HW), p = (int)(bp % HW);
     const float mean = bf2f(mom[bp * mstride + c]);
     float lv = bf2f(mom[bp * mstride + L + c]);
-    lv = fminf(fmaxf(lv, -30.f), 20.f);
+    // jnp.clip keeps a NaN (fminf / fmaxf would return the bound and hand back a finite latent for a NaN log-variance)
+    lv = lv < -30.f ? -30.f : (lv > 20.f ? 20.f : lv);
     const float v = (mean + __expf(0.5f * lv) * eps[i]) * scale;
     lat[((long)b * L + c) * HW + p] = v;
   }

@@ -5,10 +5,17 @@ every product and every partial sum is an integer below 2^24, so fp32 accumulati
 result is unique: the fp32 accumulator equals the float64 reference and the bf16 output is its RNE rounding, bit for bit.  This
 module holds the operand generators, the expectations (float64 reference followed by the kernels' rounding points), the bitwise
 comparison with a report that names the tile edge, guarded allocations, per-slice error norms, and the case tables that the GPU
-file and the CPU proof share."""
+file and the CPU proof share.
+
+The second half serves tests/test_gpu_reduce_optim_exact.py: exact scalar sums with a report that names the missing partial, tail
+element or overwritten destination, mirrors of the reduction launchers' partitions, the optimizer references (oracle/lion8.py itself),
+the posterior-sample and timestep-embedding bounds, and the case tables with the bound that makes each of them exact."""
 import math
 
+import numpy as np
 import torch
+
+from oracle import lion8 as LION_ORACLE  # the float32 restatement of lion_quant.py the project trusts: the ONLY optimizer reference
 
 BF = torch.bfloat16
 LIMIT = 1 << 24  # integers up to here are exact in fp32
@@ -697,3 +704,314 @@ def exact_reductions():
 GEMM_RANGE = 3   # operands of the forward / input-gradient contractions: integers in -3..3
 WGRAD_RANGE = 3  # operands of the weight gradients
 EPI_RANGE = 5    # bias, row bias, residual: integers in -5..5
+
+
+# ================================================================================================ reductions, optimizer sweeps, loss kernels
+# (tests/test_gpu_reduce_optim_exact.py; their proof on the CPU: tests/test_kernel_checks_cpu.py)
+CNT_BYTES = 65536  # arrival counters at the head of every reduction workspace (include/sdt.h)
+
+
+def counters_report(ws_bytes, what="workspace"):
+    """None when the 64 KiB counter area (uint8 tensor, any device) is zero; otherwise which int32 counters are not."""
+    c = ws_bytes[:CNT_BYTES].cpu().view(torch.int32)
+    nz = c.nonzero().reshape(-1)
+    if nz.numel() == 0:
+        return None
+    return f"{what}: {nz.numel()} arrival counters not reset, first: counter {int(nz[0])} = {int(c[nz[0]])}"
+
+
+def sum_report(got, want, what, init=0.0, parts=None, tail=None):
+    """Comparison of one exact scalar sum (float64 values of what the kernel stored and of the reference `init + total`).  None when
+    equal; otherwise a message that names what the difference equals: the partial of ONE workgroup (parts: float64 tensor, the sum of
+    each workgroup's share under the kernel's partition), ONE tail element's term (tail: float64 tensor of the terms behind the last
+    vector), or the destination's previous value (a store where an accumulation belongs)."""
+    got, want = float(got), float(want)
+    if got == want:
+        return None
+    diff = want - got
+    hints = []
+    if init != 0.0 and diff == init:
+        hints.append(f"the difference is the destination's previous value {init!r}: stored with = where += belongs")
+    if parts is not None:
+        hit = (parts.double() == diff).nonzero().reshape(-1)
+        if diff != 0 and hit.numel():
+            hints.append(f"the difference is the partial of workgroup {hit[:4].tolist()} of {parts.numel()}")
+    if tail is not None:
+        t = tail.double().reshape(-1)
+        for k in range(1, t.numel() + 1):  # the last k tail elements missing
+            if diff == float(t[-k:].sum()) and diff != 0:
+                hints.append(f"the difference is the term of the last {k} of the {t.numel()} tail elements (n & 3)")
+                break
+        hit = (t == diff).nonzero().reshape(-1)
+        if diff != 0 and hit.numel() and not hints:
+            hints.append(f"the difference is the term of tail element {hit.tolist()}")
+    return f"{what}: got {got!r}, want {want!r} (want - got = {diff!r})" + ("; " + "; ".join(hints) if hints else "")
+
+
+def sqnorm_partition(n):
+    """(grid, float4s) of sqnorm_kernel / grad_accumulate_kernel (optimizer.hip): one workgroup per 2048 float4s, at most 2048
+    workgroups, a grid-stride loop beyond; the n & 3 tail belongs to workgroup 0."""
+    nv = n >> 2
+    return max(1, min(2048, -(-nv // 2048))), nv
+
+
+def sqnorm_parts(x64sq, n):
+    """float64 partial of every workgroup under sqnorm_partition (x64sq: the n squared terms, float64)."""
+    grid, nv = sqnorm_partition(n)
+    parts = torch.zeros(grid, dtype=torch.float64)
+    if nv:
+        v = x64sq[: nv * 4].view(nv, 4).sum(1)
+        wg = (torch.arange(nv) // 256) % grid
+        parts.index_add_(0, wg, v)
+    parts[0] += x64sq[nv * 4:].sum()
+    return parts
+
+
+def sum_f64_partition(n):
+    """(grid, per) of sum_f64_kernel: ceil(n / 4096) workgroups, at most 2048; workgroup b sums [b * per, (b + 1) * per)."""
+    grid = max(1, min(2048, -(-n // 4096)))
+    return grid, -(-n // grid)
+
+
+def colsum_plan(batch, rows, N, want_blocks):
+    """colsum_launch (elementwise.hip): (ncb, nby, rpb, want).  want_blocks: 256 for sdt_colsum_accumulate, 512 for the batched form."""
+    ncb = -(-(-(-N // 8)) // 32)
+    nby = (rows + 63) // 64
+    want = (want_blocks + ncb * batch - 1) // (ncb * batch)
+    nby = min(nby, want)
+    rpb = (rows + nby - 1) // nby
+    return ncb, -(-rows // rpb), rpb, want
+
+
+# ---- case tables: every one carries the bound that makes its sums exact (asserted by the CPU proof)
+SQNORM_RANGE = 3  # integers in -3..3: every square, partial and total is an integer far below 2^53
+SQNORM_SIZES = [1, 2, 3, 4, 5, 7, 8191, 8192, 8193, (1 << 20) + 3, (1 << 24) + 8192 * 3 + 5]  # the last: capped grid, second stride pass
+ACC_SIZES = SQNORM_SIZES[:-1]
+SUMF64_RANGE = 1 << 20  # integer-valued doubles in +-2^20: n * 2^20 < 2^53
+SUMF64_SIZES = [1, 255, 256, 257, 511, 512, 513, 4096, 4097, (1 << 20) + 1, 2048 * 4096 + 4099]  # the last: per > 4096
+
+# sdt_mse_loss_fwd_bwd: (id, B, C, H, W, cpad, weight, dpred, loss_accum before).  pred and target integers in -1..1 (diff^2 <= 4),
+# weights in {0.5, 1, 2}: sum w diff^2 <= 8 * B*C*H*W must stay below 2^24 and, for the power-of-two counts, so must
+# loss_before * count + that sum (then loss_before + sum / count is exact too).
+MSE_WMAX, MSE_DIFF2 = 2.0, 4
+MSE_CASES = [
+    ("one_wg", 2, 4, 8, 8, 8, True, True, 3.0),
+    ("one_wg_noweight", 2, 4, 8, 8, 4, False, True, 3.0),
+    ("one_wg_nodpred", 2, 4, 8, 8, 16, True, False, 3.0),
+    ("cap_512_wg", 2, 4, 256, 256, 4, True, True, 3.0),
+    ("cap_512_wg_nodpred_noweight", 2, 4, 256, 256, 8, False, False, 3.0),
+    ("stride_2_passes", 4, 4, 256, 256, 16, True, True, 3.0),
+    ("stride_b8", 8, 4, 128, 256, 8, True, True, 1.0),
+    # counts that are not powers of two: loss within 2 fp32 ulps (1 / count and t * inv_count round), loss_accum starts at 0
+    ("c3", 2, 3, 8, 9, 8, True, True, 0.0),
+    ("c3_unpadded", 5, 3, 7, 11, 3, False, True, 0.0),
+    ("c9", 3, 9, 5, 7, 16, True, True, 0.0),
+    ("c9_unpadded", 2, 9, 16, 16, 9, True, True, 0.0),
+]
+
+# column sums: (N, ld, rows, batch, range).  |value| <= range, rows * range < 2^24.
+COLSUM_CASES = [
+    (8, 8, 1, 1, 200), (8, 24, 1 << 20, 1, 3), (8, 16, 65537, 2, 50), (248, 264, 7, 2, 200), (250, 256, 63, 1, 200), (256, 256, 64, 5, 200),
+    (256, 272, 65, 5, 200), (264, 280, 65537, 1, 50), (1280, 1296, 4096, 2, 100), (2560, 2560, 65, 1, 200), (2560, 2576, 4096, 1, 100),
+    (1280, 1280, 63, 5, 200), (2556, 2560, 7, 1, 200),
+]
+
+# embeddings: (D, sequences, id pattern, vocabulary); S = 77, dout in -3..3, tables preloaded with integers in -100..100
+EMB_S = 77
+EMB_CASES = [(48, 1, "distinct", 1000), (48, 12, "distinct", 1000), (768, 12, "clip", 1000), (1280, 5, "equal_last", 300), (1280, 1, "clip", 300),
+             (768, 3, "equal_first", 300)]
+
+
+def embedding_ids(pattern, nseq, vocab, seed):
+    """int32 (nseq * 77,) ids: 'distinct' - no id twice, ids 0 and vocab - 1 among them; 'equal_first' / 'equal_last' - row 0 / the last
+    row of the table everywhere; 'clip' - per sequence a begin token, a few words, then one padding id (the last row) to the end."""
+    rows = nseq * EMB_S
+    g = torch.Generator().manual_seed(seed)
+    if pattern == "distinct":
+        ids = torch.randperm(vocab - 2, generator=g)[: rows - 2] + 1
+        ids = torch.cat([torch.tensor([vocab - 1]), ids, torch.tensor([0])])
+    elif pattern == "equal_first":
+        ids = torch.zeros(rows, dtype=torch.int64)
+    elif pattern == "equal_last":
+        ids = torch.full((rows,), vocab - 1, dtype=torch.int64)
+    else:
+        ids = torch.full((nseq, EMB_S), vocab - 1, dtype=torch.int64)
+        ids[:, 0] = vocab - 2
+        for s in range(nseq):
+            k = 3 + (5 * s) % 9
+            ids[s, 1: 1 + k] = torch.randint(0, 4, (k,), generator=g) if s % 2 else torch.randint(0, vocab - 2, (k,), generator=g)
+        ids = ids.reshape(-1)
+    return ids.to(torch.int32)
+
+
+# optimizer sweeps
+LION_BLOCK_SIZES = [4, 8, 16, 32, 64, 128, 256]
+LION32_SIZES = [1, 3, 1023, 1024, 1025, (1 << 20) + 5]
+LION_HP = dict(lr=1e-3, b1=0.9, b2=0.99, ema_rate=0.999)
+
+
+def lion8_sizes(bs):
+    """One block; the buffer's end inside a wave, on a 1024-float4 slice boundary, one block past it; 2^20 + one block."""
+    return [bs, 4096 - bs, 4096, 4096 + bs, (1 << 20) + bs]
+
+
+def lion8_reference_step(p, g, codes, inv, ema, bs, max_norm, wd, hp=LION_HP):
+    """One carried step of oracle.lion8 on flat float32 arrays: (p, codes [blocks][bs], inv [blocks][1], ema, bf16(p),
+    sum of squares handed to the kernel).  max_norm None: no clip (the kernel gets a NULL sqnorm)."""
+    state = {"count": 0, "mu": {"x": (codes.reshape(-1, bs), inv.reshape(-1, 1))}}
+    sq = float(np.sum(np.asarray(g, np.float64) * np.asarray(g, np.float64)))
+    newp, st, _ = LION_ORACLE.lion_step({"x": p}, {"x": g}, state, lr=hp["lr"], wd=wd, b1=hp["b1"], b2=hp["b2"], block_size=bs, clip=max_norm)
+    c, i = st["mu"]["x"]
+    e = None if ema is None else LION_ORACLE.ema_update({"x": ema}, newp, hp["ema_rate"])["x"]
+    return newp["x"], c, i, e, torch.from_numpy(newp["x"]).to(BF), sq
+
+
+def lion32_reference_step(p, g, mom, ema, max_norm, wd, hp=LION_HP):
+    state = {"count": 0, "mu": {"x": mom}}
+    sq = float(np.sum(np.asarray(g, np.float64) * np.asarray(g, np.float64)))
+    newp, st, _ = LION_ORACLE.lion_step({"x": p}, {"x": g}, state, lr=hp["lr"], wd=wd, b1=hp["b1"], b2=hp["b2"], clip=max_norm)
+    e = None if ema is None else LION_ORACLE.ema_update({"x": ema}, newp, hp["ema_rate"])["x"]
+    return newp["x"], st["mu"]["x"], e, torch.from_numpy(newp["x"]).to(BF), sq
+
+
+def grads_with_exact_norm(n, seed):
+    """(g float32 [n], max_norm): multiples of 2^-4 (exact in bf16) whose norm is EXACTLY max_norm = M * 2^-4, M an integer that is not
+    a power of two: random a_i in -15..15 behind a reserve of leading elements that are set to 15s and 1s so that sum a_i^2 = M^2.  The
+    squares sum to an integer below 2^53 in any order.  M is chosen (for n >= 256) so that (g / norm) * max_norm != g in float32 for at
+    least n / 32 elements (the round trip returns most small integers unchanged): the two branches of optax's clip give different bits."""
+    gen = torch.Generator().manual_seed(seed)
+    a = torch.randint(-15, 16, (n,), generator=gen)
+    reserve = n // 2 if n >= 64 else n - 1
+    a[:reserve] = 0
+    S = int((a * a).sum())
+    af = a.float().numpy() / np.float32(16)
+    for M in range(math.isqrt(S) + 1, math.isqrt(S) + 400):
+        q, r = divmod(M * M - S, 225)
+        if q + r > reserve or M & (M - 1) == 0:
+            continue
+        mx = np.float32(M / 16.0)
+        if n >= 256 and np.count_nonzero(((af / mx).astype(np.float32) * mx).astype(np.float32) != af) < n // 32:
+            continue
+        a[:q], a[q: q + r] = 15, 1
+        assert int((a * a).sum()) == M * M
+        return a.float().numpy() / np.float32(16), M / 16.0
+    assert n < 64, "no exact norm found"
+    a[:] = 0
+    a[0] = 3
+    return a.float().numpy() / np.float32(16), 3.0 / 16
+
+
+def lion_state_report(codes, inv, want_codes, want_inv, what):
+    """None, or where the 8-bit state differs from the oracle's: codes [blocks][bs] by block and element, inverse scales by block -
+    naming a scale that is the oracle's scale of a NEIGHBOURING block (the store that went to the wrong block or was skipped)."""
+    msgs = []
+    bad = np.argwhere(codes != want_codes)
+    if bad.size:
+        b, e = bad[0]
+        msgs.append(f"{len(bad)} codes differ, first: block {b} element {e}: got {int(codes[b, e])}, want {int(want_codes[b, e])}")
+    gi, wi = inv.reshape(-1), want_inv.reshape(-1)
+    badi = np.flatnonzero(gi.view(np.int32) != wi.view(np.int32))
+    if badi.size:
+        b = int(badi[0])
+        m = f"{badi.size} inverse scales differ, first: block {b}: got {gi[b]!r}, want {wi[b]!r}"
+        for o in (-1, 1):
+            if 0 <= b + o < wi.size and gi[b].view(np.int32) == wi[b + o].view(np.int32):
+                m += f" (the oracle's scale of block {b + o})"
+        msgs.append(m)
+    return None if not msgs else f"{what}: " + "; ".join(msgs)
+
+
+# ---- VAE posterior sample
+POST_EPS = (0.0, 1.0, -1.0, 3.5, -3.5)
+POST_SCALE = 0.18215
+LV_HI, LV_LO = 0x41A0, 0xC1F0  # the bf16 patterns of 20 and -30
+
+
+def posterior_ref64(mean, lv, eps, scale=POST_SCALE):
+    return (mean.double() + torch.exp(0.5 * lv.double().clamp(-30.0, 20.0)) * eps.double()) * float(torch.tensor(scale, dtype=torch.float32))
+
+
+def posterior_emulation(mean, lv, eps, scale=POST_SCALE):
+    """The kernel's rounding points (posterior_sample_kernel): h = fl32(0.5 lv) (exact), a = fl32(h * fl32(log2 e)), e = fl32(2^a) with an
+    exact exp2, then fl32(fl32(mean + e * eps) * scale) with one rounding for the multiply-add (the file is built with contraction)."""
+    f32 = lambda t: t.to(torch.float32).double()
+    a = f32(f32(0.5 * lv.double().clamp(-30.0, 20.0)) * float(torch.tensor(1.4426950408889634, dtype=torch.float32)))
+    e = f32(torch.exp2(a))
+    return f32(f32(mean.double() + e * eps.double()) * float(torch.tensor(scale, dtype=torch.float32)))
+
+
+def posterior_term_magnitude(mean, lv, eps, scale=POST_SCALE):
+    return (mean.double().abs() + torch.exp(0.5 * lv.double().clamp(-30.0, 20.0)) * eps.double().abs()) * scale
+
+
+def posterior_clip_report(got, lv_bits, eps_idx):
+    """got: float32 latents, one per (logvar pattern, eps) pair; lv_bits: the bf16 pattern (0..65535) of each; eps_idx: which eps.
+    Every pattern >= 20 (+inf included) must hold the bits of the pattern 20 with the same eps, every pattern <= -30 (-inf included)
+    those of -30; NaN patterns must give NaN.  None, or the first offending pattern of each rule."""
+    v = lv_bits.to(torch.int32).to(torch.int16).view(BF).double()
+    gb = bits(got)
+    msgs = []
+    for name, sel, anchor in ((">= 20", v >= 20.0, LV_HI), ("<= -30", v <= -30.0, LV_LO)):
+        for k in range(len(POST_EPS)):
+            m = sel & (eps_idx == k)
+            ref = gb[(lv_bits == anchor) & (eps_idx == k)]
+            assert ref.numel() == 1
+            bad = m & (gb != ref)
+            if bad.any():
+                i = int(bad.nonzero()[0])
+                msgs.append(f"logvar pattern 0x{int(lv_bits[i]):04x} ({float(v[i])!r}) with eps {POST_EPS[k]}: got {float(got[i])!r}, the clipped "
+                            f"value gives {float(got[(lv_bits == anchor) & (eps_idx == k)][0])!r} ({int(bad.sum())} patterns {name} differ)")
+                break
+    nan = torch.isnan(v)
+    bad = nan & ~torch.isnan(got.double())
+    if bad.any():
+        i = int(bad.nonzero()[0])
+        msgs.append(f"NaN logvar pattern 0x{int(lv_bits[i]):04x} gave the number {float(got[i])!r} ({int(bad.sum())} of {int(nan.sum())} NaN patterns)")
+    return None if not msgs else "posterior sample: " + "; ".join(msgs)
+
+
+# ---- timestep embedding
+def timestep_ref64(t, dim, flip, shift):
+    half = dim // 2
+    inc = math.log(10000.0) / (half - shift)
+    e = t.double()[:, None] * torch.exp(torch.arange(half, dtype=torch.float64) * -inc)[None]
+    return torch.cat([torch.cos(e), torch.sin(e)], -1) if flip else torch.cat([torch.sin(e), torch.cos(e)], -1)
+
+
+def timestep_report(got, t, dim, flip, shift):
+    """|got - ref| <= 1/2 bf16 ulp(ref) + 2^-22 max(t, 1) for every element (the bound: DESIGN.md §7a); None, or the first violations -
+    and whether the result would pass with its sin and cos halves exchanged."""
+    ref = timestep_ref64(t, dim, flip, shift)
+    bound = 0.5 * bf16_ulp(ref) + 2.0 ** -22 * t.double().clamp_min(1.0)[:, None]
+    err = (got.double() - ref).abs()
+    bad = ~(err <= bound)
+    if not bad.any():
+        return None
+    half = dim // 2
+    sw = torch.cat([got[:, half:], got[:, :half]], -1).double()
+    swapped = bool(((sw - ref).abs() <= bound).all())
+    c = _coords(bad.reshape(-1).nonzero().reshape(-1)[:4], tuple(got.shape))
+    return (f"timestep embedding dim {dim} flip {flip} shift {shift}: {int(bad.sum())} of {got.numel()} elements miss the bound, first at (row, column) {c}: "
+            f"got {[float(got[i]) for i in c]}, want {[float(ref[i]) for i in c]}" + ("; the sin and cos halves are exchanged" if swapped else ""))
+
+
+# ---- parameter preparation: (name, batch, R, C, Rp, Cp, src offset alignment remainder)
+PREP_LEAVES = [("interior", 1, 256, 320, 256, 320, 0), ("padded", 1, 130, 72, 136, 72, 0), ("conv", 9, 4, 320, 8, 320, 0), ("small", 1, 33, 48, 40, 48, 0),
+               ("odd_offset", 1, 64, 64, 64, 64, 2), ("interior_after_odd", 1, 128, 64, 128, 64, 0)]
+
+
+def exact_case_bounds():
+    """(what, bound on the largest partial or total, limit) for every exact reduction of tests/test_gpu_reduce_optim_exact.py."""
+    out = []
+    for n in SQNORM_SIZES:
+        out.append((f"sqnorm n={n}", n * SQNORM_RANGE ** 2 + (1 << 30), 1 << 53))
+    for n in SUMF64_SIZES:
+        out.append((f"sum_f64 n={n}", n * SUMF64_RANGE + (1 << 30), 1 << 53))
+    for name, B, C, H, W, cpad, wt, dp, l0 in MSE_CASES:
+        cnt = B * C * H * W
+        out.append((f"mse {name}", MSE_WMAX * MSE_DIFF2 * cnt + (l0 * cnt if cnt & (cnt - 1) == 0 else 0), LIMIT))
+    for N, ld, rows, batch, r in COLSUM_CASES:
+        out.append((f"colsum {(N, rows, batch)}", rows * r + 1000, LIMIT))
+    for D, nseq, pat, vocab in EMB_CASES:
+        out.append((f"embedding {(D, nseq, pat)}", 3 * nseq * EMB_S + 100, LIMIT))
+    return out

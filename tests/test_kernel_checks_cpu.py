@@ -1,7 +1,12 @@
 """The proof that tests/test_gpu_kernel_exact.py would fail on a subtly wrong kernel, without breaking a kernel on a GPU: start from
 a correct expectation, plant the defects a whole-tensor norm cannot see (one element off by one bf16 ulp, one unwritten row, one
 column that lost its product term, one store outside the output) and assert that the checkers of tests/kernel_checks.py report each
-at the right coordinates.  Plus the arithmetic the exact tests rest on: every exact case keeps sum |a||b| below 2^24."""
+at the right coordinates.  Plus the arithmetic the exact tests rest on: every exact case keeps sum |a||b| below 2^24.
+The same for tests/test_gpu_reduce_optim_exact.py (second half of this file): a missing workgroup partial, a dropped tail element, = for
++=, a non-zero counter, a code off by one, a neighbour's inverse scale, an unclipped log-variance, exchanged sin / cos halves."""
+import math
+
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -395,3 +400,262 @@ def test_norm_emulation_reference():
             assert (ref[n] - t).abs().max() < 1e-11, n
         assert ((emu["dgamma"] - ref["dgamma"]).abs() / terms["dgamma"]).max() < 1e-6
         assert kc.per_slice_rel(emu["y"], ref["y"], (len(shape) - 1,)).max() < 4e-3
+
+
+# ================================================================================================ reductions, optimizer sweeps, loss kernels
+# (the checkers of tests/test_gpu_reduce_optim_exact.py: each fault it exists for, planted into a correct result)
+def _sq_case(n=8192 * 5 + 3):
+    x = kc.exact_ints((n,), -kc.SQNORM_RANGE, kc.SQNORM_RANGE, 3, dtype=torch.float32)
+    sq = x.double() ** 2
+    return n, sq, kc.sqnorm_parts(sq, n), sq[(n >> 2) << 2:]
+
+
+def test_sum_report_names_a_missing_workgroup_partial():
+    n, sq, parts, tail = _sq_case()
+    init = 12345.0
+    want = init + float(sq.sum())
+    assert parts.numel() == 5 and float(parts.sum()) == float(sq.sum())
+    assert kc.sum_report(want, want, "out", init, parts, tail) is None
+    parts[3] += 0.5  # (make the partial unique so that the report can only name this one)
+    msg = kc.sum_report(want - float(parts[3]) + 0.5, want + 0.5, "out", init, parts, tail)
+    assert msg is not None and "partial of workgroup [3] of 5" in msg
+    # one workgroup of 2048 is far below what a 1e-6 relative check of the norm sees
+    assert float(parts[3]) / want < 0.25 and (1 / 2048) ** 0.5 > 1e-6
+
+
+def test_sum_report_names_a_dropped_tail_element():
+    n, sq, parts, tail = _sq_case()
+    assert tail.numel() == 3
+    sq[-1] = 9.0
+    tail = sq[(n >> 2) << 2:]
+    want = float(sq.sum())
+    msg = kc.sum_report(want - 9.0, want, "out", 0.0, None, tail)
+    assert msg is not None and "last 1 of the 3 tail elements" in msg
+    msg = kc.sum_report(want - float(tail.sum()), want, "out", 0.0, None, tail)
+    assert "last 3 of the 3 tail elements" in msg
+    assert 9.0 / want < 1e-4  # invisible to a relative tolerance on the norm
+
+
+def test_sum_report_names_a_store_where_an_accumulation_belongs():
+    n, sq, parts, tail = _sq_case()
+    s = float(sq.sum())
+    msg = kc.sum_report(s, 12345.0 + s, "out", 12345.0, parts, tail)
+    assert msg is not None and "= where += belongs" in msg
+    db0, colsum = kc.exact_ints((264,), -5, 5, 1, dtype=torch.float32), kc.exact_ints((264,), -100, 100, 2, dtype=torch.float32)
+    rep = kc.mismatch_report(colsum, db0 + colsum, "db")
+    assert rep is not None and f"{int((db0 != 0).sum())} of 264" in rep
+
+
+def test_nonzero_counter_is_reported():
+    ws = torch.zeros(kc.CNT_BYTES + 4096, dtype=torch.uint8)
+    ws[kc.CNT_BYTES:] = 0xFF  # the slabs may hold anything
+    assert kc.counters_report(ws) is None
+    ws[4 * 17] = 1
+    assert "counter 17 = 1" in kc.counters_report(ws)
+
+
+def _lion_state(bs=16, nblk=40):
+    rs = np.random.RandomState(0)
+    return kc.LION_ORACLE.block_quantize((rs.standard_normal(nblk * bs) * 10.0 ** rs.uniform(-3, 0, nblk).repeat(bs)).astype(np.float32), bs)
+
+
+def test_one_code_off_by_one_and_a_neighbours_scale_are_reported():
+    codes, inv = _lion_state()
+    assert kc.lion_state_report(codes.copy(), inv.copy(), codes, inv, "s") is None
+    c = codes.copy()
+    c[7, 5] += 1
+    assert "1 codes differ, first: block 7 element 5" in kc.lion_state_report(c, inv, codes, inv, "s")
+    i = inv.copy()
+    i[12] = inv[11]  # what a store by the wrong lane, or a skipped store after the neighbour's, leaves behind
+    msg = kc.lion_state_report(codes, i, codes, inv, "s")
+    assert "1 inverse scales differ, first: block 12" in msg and "(the oracle's scale of block 11)" in msg
+    i = inv.copy()
+    i[3] = np.nextafter(i[3], np.float32(0))  # one ulp: what a reciprocal instead of a division would do
+    assert "block 3" in kc.lion_state_report(codes, i, codes, inv, "s")
+
+
+def test_optimizer_references_are_the_oracles_own_functions():
+    from oracle import lion8
+    assert kc.LION_ORACLE is lion8
+    bs, n = 16, 256
+    rs = np.random.RandomState(1)
+    p, g = rs.standard_normal(n).astype(np.float32), (3 * rs.standard_normal(n)).astype(np.float32)
+    codes, inv = lion8.block_quantize(np.zeros(n, np.float32), bs)
+    got = kc.lion8_reference_step(p, g, codes, inv, p.copy(), bs, 1.0, 0.07)
+    newp, st, gn = lion8.lion_step({"x": p}, {"x": g}, {"count": 0, "mu": {"x": (codes, inv)}}, lr=kc.LION_HP["lr"], wd=0.07, b1=0.9, b2=0.99, block_size=bs, clip=1.0)
+    assert np.array_equal(got[0], newp["x"]) and np.array_equal(got[1], st["mu"]["x"][0]) and np.array_equal(got[2], st["mu"]["x"][1])
+    assert np.array_equal(got[3], lion8.ema_update({"x": p}, newp, kc.LION_HP["ema_rate"])["x"])
+    assert np.float32(np.sqrt(got[5])) == gn and torch.equal(got[4], torch.from_numpy(newp["x"]).to(BF))
+    m32 = kc.lion32_reference_step(p, g, np.zeros(n, np.float32), None, None, 0.0)
+    newp, st, _ = lion8.lion_step({"x": p}, {"x": g}, {"count": 0, "mu": {"x": np.zeros(n, np.float32)}}, lr=kc.LION_HP["lr"], wd=0.0, b1=0.9, b2=0.99, clip=None)
+    assert np.array_equal(m32[0], newp["x"]) and np.array_equal(m32[1], st["mu"]["x"]) and m32[2] is None
+
+
+def test_gradients_with_a_norm_exactly_at_the_threshold():
+    from oracle import lion8
+    for n in (1, 3, 4, 256, 4096 - 4, 4096 + 256, (1 << 20) + 5):
+        g, mx = kc.grads_with_exact_norm(n, n)
+        assert g.dtype == np.float32 and g.shape == (n,) and float(np.sum(g.astype(np.float64) ** 2)) == mx * mx
+        assert np.array_equal(torch.from_numpy(g).to(BF).float().numpy(), g) and float(np.float32(mx)) == mx
+        clipped, norm = lion8.clip_by_global_norm({"x": g}, mx)
+        assert float(norm) == mx  # not below: optax's else branch
+        if n >= 256:  # ... whose result differs from the untouched gradient: taking the wrong branch shows
+            assert (clipped["x"] != g).sum() >= n // 32
+    assert not (np.float32(1.0) < np.float32(1.0))
+
+
+def _posterior_inputs():
+    pat = torch.arange(65536, dtype=torch.int32)
+    lv_bits, eps_idx = pat.repeat_interleave(len(kc.POST_EPS)), torch.arange(len(kc.POST_EPS)).repeat(65536)
+    lv = lv_bits.to(torch.int16).view(BF)
+    return lv_bits, eps_idx, lv, torch.zeros_like(lv), torch.tensor(kc.POST_EPS)[eps_idx]
+
+
+def test_unclipped_logvar_and_a_number_for_nan_are_reported():
+    lv_bits, eps_idx, lv, mean, eps = _posterior_inputs()
+    good = kc.posterior_emulation(mean, lv, eps).float()
+    assert kc.posterior_clip_report(good, lv_bits, eps_idx) is None
+    sc = float(torch.tensor(kc.POST_SCALE, dtype=torch.float32))
+    for lo, what in ((-40.0, "<= -30"), (-30.0, None)):  # a clip at -40 instead of -30; the right bound
+        bad = ((mean.double() + torch.exp(0.5 * lv.double().clamp(lo, 20.0)) * eps.double()) * sc).float()
+        msg = kc.posterior_clip_report(bad, lv_bits, eps_idx)
+        assert (msg is None) == (what is None)
+        if what:
+            assert what in msg and "0xc1f1" in msg and "eps 1.0" in msg  # the first pattern below -30, the first eps that shows it
+    # fminf(fmaxf(NaN, -30), 20) = -30: a finite latent for a NaN log-variance
+    nan_as_lo = torch.where(torch.isnan(lv.double()), torch.full_like(lv, -30.0), lv)
+    msg = kc.posterior_clip_report(kc.posterior_emulation(mean, nan_as_lo, eps).float(), lv_bits, eps_idx)
+    assert "NaN logvar pattern 0x7f81 gave the number" in msg
+    # the float64 reference keeps NaN, as jnp.clip and oracle.nets.vae_sample_latents do
+    from oracle import nets as onets
+    m = torch.tensor([[[[0.5, float("nan")]]]])
+    assert torch.isnan(onets.vae_sample_latents(m, torch.ones(1, 1, 1, 1))).all()
+    assert torch.isnan(kc.posterior_ref64(mean[:1], torch.tensor([float("nan")]), eps[:1])).all()
+    # the emulation is the float64 reference up to fp32 roundings
+    fin = ~torch.isnan(lv.double())
+    rel = (good[fin].double() - kc.posterior_ref64(mean[fin], lv[fin], eps[fin])).abs() / kc.posterior_term_magnitude(mean[fin], lv[fin], eps[fin]).clamp_min(1e-300)
+    assert 1e-8 < rel.max() < 2e-6
+
+
+def test_exchanged_sin_and_cos_halves_are_reported():
+    from oracle import nets as onets
+    t = torch.tensor([0, 1, 64, 999, 1024, 4096], dtype=torch.int32)
+    for dim, flip, shift in ((320, True, 0.0), (256, True, 0.0), (100, False, 1.0)):
+        e = onets.timestep_embedding(t, dim, flip, shift).to(BF)
+        assert kc.timestep_report(e, t, dim, int(flip), shift) is None
+        half = dim // 2
+        msg = kc.timestep_report(torch.cat([e[:, half:], e[:, :half]], -1), t, dim, int(flip), shift)
+        assert msg is not None and "halves are exchanged" in msg and "first at (row, column) [(0, 0)" in msg
+        one = e.clone()
+        one.view(torch.int16)[3, 7] += 2  # two bf16 ulps on one element
+        msg = kc.timestep_report(one, t, dim, int(flip), shift)
+        assert "1 of" in msg and "(3, 7)" in msg and "exchanged" not in msg
+    ref = torch.cos(t.double()[:, None] * torch.exp(torch.arange(160, dtype=torch.float64) * -math.log(10000.0) / 160))
+    assert (kc.timestep_ref64(t, 320, True, 0.0)[:, :160] - ref).abs().max() < 1e-11
+
+
+def test_guards_around_in_place_operands_are_reported():
+    for dtype in (torch.float64, torch.float32, torch.int8):
+        g = kc.Guarded(1, 5, dtype, "cpu", pad=0, back_rows=0)
+        g.t.copy_(torch.ones(1, 5).to(dtype))
+        g.check("in place")
+        g.t.mul_(2)  # the payload may change
+        g.check("in place")
+        g.arena[g.front + 5] = 1  # the element a tail store one too wide would hit
+        assert "back guard, row 1 column 0" in g.guard_report("in place")
+        g = kc.Guarded(1, 1, dtype, "cpu", pad=0, back_rows=0)
+        g.arena[g.front - 1] = 1  # the word in front of *out_sq
+        assert "front guard, 1 elements before the base" in g.guard_report("out_sq")
+
+
+def test_reduction_case_tables_are_exact_and_take_every_path(lib):
+    rows = kc.exact_case_bounds()
+    assert len(rows) > 45
+    for what, bound, limit in rows:
+        assert bound < limit, what
+    # squared norms: only a tail, one workgroup, many, the capped grid with a second stride pass
+    grids = [kc.sqnorm_partition(n) for n in kc.SQNORM_SIZES]
+    assert [g for g, _ in grids[:9]] == [1] * 9 and grids[9][0] == 128 and grids[10][0] == 2048 and grids[10][1] > 2048 * 2048
+    assert {n & 3 for n in kc.SQNORM_SIZES} == {0, 1, 2, 3} and lib.sdt_sqnorm_workspace_bytes() == kc.CNT_BYTES + 2048 * 8
+    parts = kc.sqnorm_parts(torch.ones(8192 * 3 + 2, dtype=torch.float64), 8192 * 3 + 2)
+    assert parts.tolist() == [8194.0, 8192.0, 8192.0]
+    g, per = kc.sum_f64_partition(kc.SUMF64_SIZES[-1])
+    assert g == 2048 and per > 4096 and [kc.sum_f64_partition(n)[0] for n in kc.SUMF64_SIZES[:9]] == [1] * 8 + [2]
+    # MSE: one workgroup, exactly the cap of 512, beyond it; the exact cases have power-of-two counts
+    wgs = {name: -(-B * H * W // 256) for name, B, C, H, W, *_ in kc.MSE_CASES}
+    assert wgs["one_wg"] == 1 and wgs["cap_512_wg"] == 512 and wgs["stride_2_passes"] == 1024 and wgs["c3_unpadded"] == 2
+    assert {(C, cpad) for _, B, C, H, W, cpad, *_ in kc.MSE_CASES} >= {(4, 4), (4, 8), (4, 16), (3, 3), (3, 8), (9, 9), (9, 16)}
+    assert lib.sdt_reduce_workspace_bytes() >= kc.CNT_BYTES + 512 * 4
+    for name, B, C, H, W, cpad, wt, dp, l0 in kc.MSE_CASES:
+        cnt = B * C * H * W
+        assert (l0 != 0) == (cnt & (cnt - 1) == 0), name
+    # column sums: the planner's branches, by its own formulas
+    seen = set()
+    for N, ld, rows_, batch, r in kc.COLSUM_CASES:
+        assert ld >= N and ld % 8 == 0 and rows_ * r < kc.LIMIT
+        for b, want_blocks in ((1, 256), (batch, 512)):
+            ncb, nby, rpb, want = kc.colsum_plan(b, rows_, N, want_blocks)
+            assert nby * rpb >= rows_ > (nby - 1) * rpb and nby <= (rows_ + 63) // 64
+            assert lib.sdt_colsum_workspace_bytes(b, rows_, N) >= kc.CNT_BYTES + ncb * b * nby * 256 * 4
+            seen |= {"one row block"} if nby == 1 else set()
+            seen |= {"nby == want"} if nby == want and nby > 1 else set()
+            seen |= {"ragged last row block"} if rows_ % rpb else set()
+            seen |= {"N % 8"} if N % 8 else set()
+            seen |= {"ld > N"} if ld > N else set()
+    assert seen == {"one row block", "nby == want", "ragged last row block", "N % 8", "ld > N"}
+    assert {c[0] for c in kc.COLSUM_CASES} >= {8, 248, 256, 264, 1280, 2560} and {c[2] for c in kc.COLSUM_CASES} >= {1, 7, 63, 64, 65, 4096, 65537, 1 << 20}
+    assert {c[3] for c in kc.COLSUM_CASES} == {1, 2, 5}
+    dy = kc.exact_ints((5 * 64, 256), -200, 200, 256 + 64 + 5).double().view(5, 64, 256).sum(1)
+    assert int(((dy.abs() >= 256) & (dy.abs() < 512) & (dy.abs() % 4 == 2)).sum()) > 3  # results on bf16 ties
+    # embeddings
+    for D, nseq, pat, vocab in kc.EMB_CASES:
+        ids = kc.embedding_ids(pat, nseq, vocab, D + nseq)
+        assert ids.numel() == nseq * kc.EMB_S and ids.min() >= 0 and ids.max() == (0 if pat == "equal_first" else vocab - 1) and ids.unique().numel() < vocab
+        if pat == "distinct":
+            assert ids.unique().numel() == ids.numel() and ids.min() == 0
+        if pat == "clip":
+            assert (ids.view(nseq, -1)[:, -60:] == vocab - 1).all() and ids.unique().numel() > 3
+    assert {c[0] for c in kc.EMB_CASES} == {48, 768, 1280} and {c[1] for c in kc.EMB_CASES} >= {1, 12}
+    # optimizer sizes: the end of the buffer inside a wave, on and just past a slice of 1024 float4s
+    for bs in kc.LION_BLOCK_SIZES:
+        s = kc.lion8_sizes(bs)
+        assert all(n % bs == 0 for n in s) and s[0] == bs and s[2] == 4096 and s[1] < 4096 < s[3] and s[4] > 1 << 20
+    assert kc.LION_BLOCK_SIZES == [4 << i for i in range(7)] and kc.LION32_SIZES == [1, 3, 1023, 1024, 1025, (1 << 20) + 5]
+    # parameter preparation: which leaves take the vectorised interior path
+    vec = {name: R >= 64 and C >= 64 and not (R | C | Rp | Cp) & 3 and rem == 0 for name, b, R, C, Rp, Cp, rem in kc.PREP_LEAVES}
+    assert vec == {"interior": True, "padded": False, "conv": False, "small": False, "odd_offset": False, "interior_after_odd": True}
+
+
+def test_documented_refusals_of_the_reduction_and_optimizer_entry_points(lib):
+    """cpad < C, moment_stride < 2L, n % block_size, a misaligned acc, a workspace that is too small: -1, a message, nothing written
+    (every check runs before the first device call, so guarded host buffers stand in)."""
+    mk = lambda dt: kc.Guarded(8, 64, dt, "cpu")
+    A, B_, O, I8, D64, WS = mk(torch.float32), mk(BF), mk(torch.float32), mk(torch.int8), mk(torch.float64), mk(torch.float32)
+    big = 1 << 20
+    cases = [
+        ("add_noise cpad < C", lambda: lib.sdt_add_noise_velocity(A.ptr, A.ptr, A.ptr, A.ptr, B_.ptr, None, None, 1, 4, 2, 2, 3, None), b"bad shape"),
+        ("ddim cpad < C", lambda: lib.sdt_ddim_cfg_step(B_.ptr, O.ptr, B_.ptr, 1, 4, 2, 2, 3, 7.5, 0.5, 0.6, 0, None), b"bad shape"),
+        ("mse cpad < C", lambda: lib.sdt_mse_loss_fwd_bwd(B_.ptr, A.ptr, None, O.ptr, None, 1, 4, 2, 2, 3, WS.ptr, big, None), b"bad args"),
+        ("mse workspace too small", lambda: lib.sdt_mse_loss_fwd_bwd(B_.ptr, A.ptr, None, O.ptr, None, 1, 4, 2, 2, 4, WS.ptr, lib.sdt_reduce_workspace_bytes() - 1, None), b"workspace"),
+        ("posterior moment_stride < 2L", lambda: lib.sdt_vae_posterior_sample(B_.ptr, A.ptr, O.ptr, 1, 4, 2, 2, 7, 0.18215, None), b"bad args"),
+        ("sqnorm workspace too small", lambda: lib.sdt_sqnorm_accumulate(A.ptr, 64, D64.ptr, WS.ptr, lib.sdt_sqnorm_workspace_bytes() - 1, None), b"workspace"),
+        ("sqnorm misaligned g", lambda: lib.sdt_sqnorm_accumulate(A.ptr + 4, 64, D64.ptr, WS.ptr, big, None), b"16-byte aligned"),
+        ("sqnorm_bf16 misaligned g", lambda: lib.sdt_sqnorm_accumulate_bf16(B_.ptr + 4, 64, D64.ptr, WS.ptr, big, None), b"8-byte aligned"),
+        ("sum_f64 without workspace", lambda: lib.sdt_sum_f64_accumulate(D64.ptr, 8, D64.ptr, None, 0, None), b"workspace"),
+        ("grad_accumulate misaligned acc", lambda: lib.sdt_grad_accumulate(O.ptr + 4, A.ptr, 0, 64, 1, 1.0, None, None, 0, None), b"acc must be 16-byte aligned"),
+        ("grad_accumulate out_sq without workspace", lambda: lib.sdt_grad_accumulate(O.ptr, A.ptr, 0, 64, 1, 1.0, D64.ptr, None, 0, None), b"workspace"),
+        ("grad_accumulate unknown mode", lambda: lib.sdt_grad_accumulate(O.ptr, A.ptr, 0, 64, 4, 1.0, None, None, 0, None), b"unknown mode"),
+        ("lion8 n % block_size", lambda: lib.sdt_lion8_step(O.ptr, A.ptr, 0, I8.ptr, O.ptr, None, None, 40, 16, None, A.ptr, 1.0, 1e-3, 0.0, 0.9, 0.99, 0.999, None), b"not a multiple of block_size"),
+        ("lion8 block_size 512", lambda: lib.sdt_lion8_step(O.ptr, A.ptr, 0, I8.ptr, O.ptr, None, None, 512, 512, None, A.ptr, 1.0, 1e-3, 0.0, 0.9, 0.99, 0.999, None), b"power of two"),
+        ("lion8 misaligned p", lambda: lib.sdt_lion8_step(O.ptr + 4, A.ptr, 0, I8.ptr, O.ptr, None, None, 64, 16, None, A.ptr, 1.0, 1e-3, 0.0, 0.9, 0.99, 0.999, None), b"misaligned"),
+        ("lion8_quantize n % block_size", lambda: lib.sdt_lion8_quantize(A.ptr, I8.ptr, O.ptr, 40, 16, A.ptr, None), b"bad args"),
+        ("colsum ld % 8", lambda: lib.sdt_colsum_accumulate(B_.ptr, O.ptr, 8, 60, 60, WS.ptr, big, None), b"multiple of 8"),
+        ("colsum workspace too small", lambda: lib.sdt_colsum_accumulate(B_.ptr, O.ptr, 8, 64, 80, WS.ptr, kc.CNT_BYTES, None), b"workspace"),
+    ]
+    for what, fn, msg in cases:
+        rc = fn()
+        assert rc == -1, f"{what}: returned {rc}"
+        assert msg in lib.sdt_last_error(), f"{what}: message {lib.sdt_last_error()!r}"
+    for g in (A, B_, O, I8, D64, WS):
+        ref = kc.Guarded(8, 64, g.dtype, "cpu")
+        assert torch.equal(kc.bits(g.arena), kc.bits(ref.arena)), "a refused call wrote into a buffer"
