@@ -93,7 +93,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     train_rngs = torch.Generator(device=dev)
     train_rngs.manual_seed(config_dict["master_seed"] * 1009 + rank)  # different noise / timesteps on every shard
     (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers,
-     model_object_dict) = tu.on_device_model_training_state(training_config, models, device=dev, **schedule_kwargs(config_dict))
+     model_object_dict) = tu.on_device_model_training_state(training_config, models, device=dev, optimizer=config_dict.get("optimizer", "lion"),
+                                                           **schedule_kwargs(config_dict))
     reducer = dp.GradReducer([unet_state.store, text_encoder_state.store]) if world > 1 else None
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
@@ -179,9 +180,13 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("config", nargs="?", default="model_properties.json")
     ap.add_argument("--micro-batches", type=int, default=None, help="gradient accumulation over K micro-batches per step")
+    ap.add_argument("--optimizer", choices=("lion", "adamw"), default=None,
+                    help="lion (the reference's, default) or adamw: learning rates taken as given, 8-bit moments where the config quantises")
     args = ap.parse_args()
     with open(args.config) as f:
         cfg = json.load(f)
     if args.micro_batches is not None:
         cfg["micro_batches"] = args.micro_batches
+    if args.optimizer is not None:
+        cfg["optimizer"] = args.optimizer
     main(cfg)

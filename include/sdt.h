@@ -160,6 +160,30 @@ int sdt_lion8_step_scheduled(float* p, const void* g, int g_bf16, int8_t* codes,
                              double wd, double b1, double b2, hipStream_t stream);
 int sdt_lion32_step_scheduled(float* p, const float* g, float* mom, float* ema, uint16_t* w_bf16, int64_t n, const double* sqnorm,
                               double max_norm, const float* cur, double wd, double b1, double b2, hipStream_t stream);
+/* AdamW with decoupled weight decay and bias correction, as a second optimizer beside Lion (not in the reference, whose
+ * adam_to_lion_scale_factor only translates an Adam recipe).  All element arithmetic is float32 with every operation rounded
+ * separately, division and square root correctly rounded; gc is the clipped gradient (same clip as the Lion sweeps):
+ *   m' = b1 m + (1 - b1) gc;  v' = b2 v + (1 - b2) (gc gc);  s' = sqrtf(v');  u = (m' k1) / (s' k2 + eps);  if wd != 0: u = u + wd p;
+ *   p' = p + neg_lr u;  ema' = r ema + (1 - r) p';  w_bf16 = bf16(p').
+ * sdt_adamw_select: one lane, once per store and step, ahead of the sweeps on the same stream.  t = *step (steps taken before this
+ *   one).  prods: two doubles {P1, P2}, 8-byte aligned, 1.0 before the first step; the kernel stores P1 = P1 * b1, P2 = P2 * b2 (running
+ *   products in double, no pow) and *step = t + 1.  cur: the step's scalar block, 32 bytes, 16-byte aligned, eight floats
+ *     {neg_lr, r, 1 - r, 0, k1, k2, 0, 0},  k1 = (float)(1 / (1 - P1)),  k2 = (float)(1 / sqrt(1 - P2))  (formed in double),
+ *   the first four laid out as sdt_opt_schedule_select's block.  lr_tab / ema_tab (both or neither): the tables of
+ *   sdt_opt_schedule_select, entry min(t, n - 1); NULL: neg_lr = (float)(-lr), r = (float)ema_rate, 1 - r = (float)(1.0 - ema_rate).
+ * sdt_adamw8_step: the 8-bit sweep.  m' and the ROOT s' are stored through the block codec, each with its own int8 codes and per-block
+ *   inverse scales: inv = 1 / (absmax <= 0 ? 1 : absmax), code = sign(x inv) c(|x inv|) with c the threshold table of sdt_lion8_step and
+ *   NO offset, deq = ((code / 127)^5) / inv; the step reads m = deq(m codes), s = deq(s codes), v = s s.  Initial state: codes 0, inverse
+ *   scales 1.  Refusals as sdt_lion8_step (null pointer, block size, n not a multiple of it, misalignment), made before any HIP call.
+ * sdt_adamw32_step: the same with float32 m and v stored as they are.
+ * b1, b2 are rounded to float32 here, 1 - b1 and 1 - b2 formed in double and rounded, as the Lion launchers do. */
+int sdt_adamw_select(int64_t* step, double* prods, const float* lr_tab, int64_t n_lr, const float* ema_tab, int64_t n_ema, double lr,
+                     double ema_rate, double b1, double b2, float* cur, hipStream_t stream);
+int sdt_adamw8_step(float* p, const void* g, int g_bf16, int8_t* m_codes, float* m_inv_scale, int8_t* s_codes, float* s_inv_scale,
+                    float* ema, uint16_t* w_bf16, int64_t n, int block_size, const double* sqnorm, const float* thresholds,
+                    double max_norm, const float* cur, double wd, double b1, double b2, double eps, hipStream_t stream);
+int sdt_adamw32_step(float* p, const float* g, float* m, float* v, float* ema, uint16_t* w_bf16, int64_t n, const double* sqnorm,
+                     double max_norm, const float* cur, double wd, double b1, double b2, double eps, hipStream_t stream);
 int sdt_lion8_quantize(const float* x, int8_t* codes, float* inv_scale, int64_t n, int block_size, const float* thresholds,
                        hipStream_t stream);
 int sdt_lion8_dequantize(const int8_t* codes, const float* inv_scale, float* x, int64_t n, int block_size,

@@ -59,6 +59,9 @@ SIGNATURES = {
     "sdt_opt_schedule_select": [_P, _P, _L, _P, _L, _P, _P],
     "sdt_lion8_step_scheduled": [_P, _P, _I, _P, _P, _P, _P, _L, _I, _P, _P, _D, _P, _D, _D, _D, _P],
     "sdt_lion32_step_scheduled": [_P, _P, _P, _P, _P, _L, _P, _D, _P, _D, _D, _D, _P],
+    "sdt_adamw_select": [_P, _P, _P, _L, _P, _L, _D, _D, _D, _D, _P, _P],
+    "sdt_adamw8_step": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _D, _P, _D, _D, _D, _D, _P],
+    "sdt_adamw32_step": [_P, _P, _P, _P, _P, _P, _L, _P, _D, _P, _D, _D, _D, _D, _P],
     "sdt_lion8_quantize": [_P, _P, _P, _L, _I, _P, _P],
     "sdt_lion8_dequantize": [_P, _P, _P, _L, _I, _P],
     "sdt_groupnorm_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _I, _P, _L, _P],

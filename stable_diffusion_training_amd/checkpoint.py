@@ -367,10 +367,20 @@ def _layout_digest(store):
         lf = store.leaves[p]
         h.update(f"{p}:{lf.shape}:{lf.offset}:{int(lf.quantised)}:{int(lf.decayed)};".encode())
     h.update(f"bs={store.block_size};total={store.total}".encode())
+    opt = _optimizer_of(store)
+    if opt != "lion":  # only then: the digests (and files) of Lion stores stay what they were before there was a choice
+        h.update(f";optimizer={opt}".encode())
     return h.hexdigest()
 
 
+def _optimizer_of(store):
+    return getattr(store, "optimizer", "lion")
+
+
 _STATE_BUFFERS = ("master", "codes", "inv_scale", "mom", "ema")
+# AdamW stores: codes / scales of the second moment's root and the fp32 second moments.  The step counter and the running products of
+# the betas are rebuilt from the count (ParamStore.set_step).
+_ADAMW_BUFFERS = ("codes2", "inv_scale2", "mom2")
 # -2: flat-buffer layout of round 2 (8-element leaf alignment, segment ends at multiples of 2048, time_emb_proj / cross-attention
 # to_k / to_v grouped per width).  -1 files (round 1) hold the same tensors at other offsets and cannot be re-dealt.
 STATE_FORMAT = "sdt-training-state-2"
@@ -388,10 +398,12 @@ def save_training_state(path, unet_state, text_encoder_state, train_rng=None, rn
     for name, st in (("unet", unet_state), ("text_encoder", text_encoder_state)):
         store = st.store if hasattr(st, "store") else st
         store._gather()  # sharded optimizer: raises unless GradReducer.gather_state() (collective, all ranks) made the state whole
-        for b in _STATE_BUFFERS:
+        for b in _STATE_BUFFERS + (_ADAMW_BUFFERS if _optimizer_of(store) == "adamw" else ()):
             t = getattr(store, b)
             if t is not None:
                 tensors[f"{name}.{b}"] = t.detach().cpu().contiguous()
+        if _optimizer_of(store) != "lion":  # absent: Lion (its files are byte for byte what they were)
+            meta[f"{name}.optimizer"] = _optimizer_of(store)
         meta[f"{name}.count"] = str(int(store.count))
         meta[f"{name}.layout"] = _layout_digest(store)
     if rng_states is not None:
@@ -435,12 +447,16 @@ def load_training_state(path, unet_state, text_encoder_state, train_rng=None, ra
         keys = set(f.keys())
         for name, st in (("unet", unet_state), ("text_encoder", text_encoder_state)):
             store = st.store if hasattr(st, "store") else st
+            saved_opt, opt = meta.get(f"{name}.optimizer", "lion"), _optimizer_of(store)
+            if saved_opt != opt:
+                raise ValueError(f"{path}: {name} state was saved by the {saved_opt} optimizer and this state is built for {opt}: their "
+                                 "moments are different quantities; build the state with the optimizer that wrote the file")
             if meta.get(f"{name}.layout") != _layout_digest(store):
                 raise ValueError(f"{path}: {name} state was saved for a different parameter layout / quantisation setting "
                                  f"(layout version {STATE_FORMAT}; digest {meta.get(f'{name}.layout', '?')[:12]} != {_layout_digest(store)[:12]}: "
                                  "model config, quantisation / weight-decay exclusion lists and quant_block_size must match)")
             store.begin_external_write()  # sharded optimizer: a mirror all-gather of the last step may still be in flight
-            for b in _STATE_BUFFERS:
+            for b in _STATE_BUFFERS + (_ADAMW_BUFFERS if opt == "adamw" else ()):
                 dst = getattr(store, b)
                 if (dst is not None) != (f"{name}.{b}" in keys):
                     raise ValueError(f"{path}: {name}.{b} present in only one of file / state")

@@ -371,6 +371,185 @@ __global__ void __launch_bounds__(64) opt_schedule_select_kernel(int64_t* __rest
   *step = t + 1;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- AdamW
+// Second optimizer (include/sdt.h "AdamW"): decoupled-decay Adam with bias correction, every operation a separately rounded float32
+// one (division and square root correctly rounded).  The 8-bit sweep keeps the first moment m and the ROOT s = sqrt(v) of the second
+// one in the block codec WITHOUT the reference's offset: code = sign(x) * c(|x|) with the same threshold table (a function of the
+// magnitude alone), deq = (code / 127)^5, so zero <-> code 0 and a parameter whose gradient is exactly zero moves by decay alone.
+__device__ __forceinline__ float adamw_deq(int code) {
+  float t = (float)code / 127.0f;
+  float t2 = t * t;
+  float t4 = t2 * t2;
+  return t4 * t;
+}
+__device__ __forceinline__ int adamw_quant_tab(float x, const float* __restrict__ thr) {  // as lion_quant_tab, a = |x|
+  const float a = fabsf(x);
+  const float q = __builtin_amdgcn_exp2f(0.2f * __builtin_amdgcn_logf(a)) * 127.0f;
+  const float r = rintf(q);
+  int c = (int)fminf(fmaxf(r, 0.f), 127.f);
+  if (fabsf(q - r) > 0.5f - 2.5e-4f) c += (a >= thr[c + 1] ? 1 : 0) - (a < thr[c] ? 1 : 0);
+  return x < 0.f ? -c : c;
+}
+__device__ __forceinline__ void adamw_load_tables(float* deq_tab, float* thr_tab, const float* __restrict__ thr) {
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) deq_tab[i] = adamw_deq(i - 128);
+  for (int i = threadIdx.x; i < 129; i += blockDim.x) thr_tab[i] = i < 128 ? thr[i] : __builtin_inff();
+  __syncthreads();
+}
+
+// Per-step scalars of an AdamW store (include/sdt.h sdt_adamw_select): one lane.  t = *step; the running products P1 = b1^(t+1),
+// P2 = b2^(t+1) are carried in double by one multiplication per step (no pow: the host reproduces them with the same products);
+// cur = {neg_lr, ema_r, ema_rm, 0, k1, k2, 0, 0} with k1 = 1 / (1 - P1), k2 = 1 / sqrt(1 - P2) formed in double and rounded once.
+__global__ void __launch_bounds__(64) adamw_select_kernel(int64_t* __restrict__ step, double* __restrict__ prods,
+                                                           const float* __restrict__ lr_tab, long n_lr, const float* __restrict__ ema_tab,
+                                                           long n_ema, float neg_lr, float ema_r, float ema_rm, double b1, double b2,
+                                                           float* __restrict__ cur) {
+  if (threadIdx.x != 0) return;
+  const int64_t t = *step;
+  if (lr_tab) {
+    const long tc = t > 0 ? (long)t : 0;
+    const long i = tc < n_lr - 1 ? tc : n_lr - 1;
+    const long j = tc < n_ema - 1 ? tc : n_ema - 1;
+    neg_lr = lr_tab[i];
+    ema_r = ema_tab[2 * j];
+    ema_rm = ema_tab[2 * j + 1];
+  }
+  const double p1 = prods[0] * b1, p2 = prods[1] * b2;
+  prods[0] = p1;
+  prods[1] = p2;
+  cur[0] = neg_lr;
+  cur[1] = ema_r;
+  cur[2] = ema_rm;
+  cur[3] = 0.f;
+  cur[4] = (float)(1.0 / (1.0 - p1));
+  cur[5] = (float)(1.0 / sqrt(1.0 - p2));
+  cur[6] = 0.f;
+  cur[7] = 0.f;
+  *step = t + 1;
+}
+
+// lion8_kernel's skeleton (LPB lanes per block, one contiguous window of LION_SLICES x 256 float4s per workgroup, non-temporal 16-byte
+// traffic, tables in LDS, each inverse scale written once by its block's first lane) with two code streams and two scale streams.
+template <int LPB, bool G16>
+__global__ void __launch_bounds__(256) adamw8_kernel(float* __restrict__ p, const void* __restrict__ g, int8_t* __restrict__ m_codes,
+                                                     float* __restrict__ m_inv, int8_t* __restrict__ s_codes, float* __restrict__ s_inv,
+                                                     float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n4,
+                                                     const double* __restrict__ sqnorm, const float* __restrict__ thr, float max_norm,
+                                                     float wd, float c1, float c1m, float c2, float c2m, float eps,
+                                                     const float* __restrict__ cur) {
+  __shared__ float deq_tab[256];
+  __shared__ float thr_tab[132];
+  const float neg_lr = cur[0], ema_r = cur[1], ema_rm = cur[2], k1 = cur[4], k2 = cur[5];
+  adamw_load_tables(deq_tab, thr_tab, thr);
+  float gnorm = 0.f;
+  bool do_clip = false;
+  if (sqnorm) {
+    gnorm = (float)sqrt(*sqnorm);
+    do_clip = !(gnorm < max_norm);
+  }
+  typedef float f4v __attribute__((ext_vector_type(4)));
+  typedef unsigned u2v __attribute__((ext_vector_type(2)));
+  const long i_end = min(n4, ((long)blockIdx.x + 1) * (LION_SLICES * 256));
+  for (long i = (long)blockIdx.x * (LION_SLICES * 256) + threadIdx.x; i < i_end; i += 256) {
+    f4v gv;
+    if (G16) {
+      const u2v h = __builtin_nontemporal_load(&reinterpret_cast<const u2v*>(g)[i]);
+      gv.x = __uint_as_float(h.x << 16); gv.y = __uint_as_float(h.x & 0xffff0000u);
+      gv.z = __uint_as_float(h.y << 16); gv.w = __uint_as_float(h.y & 0xffff0000u);
+    } else {
+      gv = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(g)[i]);
+    }
+    const f4v pv = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(p)[i]);
+    const unsigned cwm = __builtin_nontemporal_load(&reinterpret_cast<const unsigned*>(m_codes)[i]);
+    const unsigned cws = __builtin_nontemporal_load(&reinterpret_cast<const unsigned*>(s_codes)[i]);
+    const long blk = i / LPB;
+    const float minv = m_inv[blk], sinv = s_inv[blk];
+    float gg[4] = {gv.x, gv.y, gv.z, gv.w};
+    float pp[4] = {pv.x, pv.y, pv.z, pv.w};
+    float mn[4], sn[4];
+    float mmax = 0.f, smax = 0.f;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int cm = (int)(int8_t)((cwm >> (8 * j)) & 0xff);
+      const int cs = (int)(int8_t)((cws >> (8 * j)) & 0xff);
+      const float mf = deq_tab[cm + 128] / minv;
+      const float sf = deq_tab[cs + 128] / sinv;
+      const float vf = sf * sf;
+      const float gc = clip_grad(gg[j], gnorm, max_norm, do_clip);
+      mn[j] = c1 * mf + c1m * gc;
+      const float vn = c2 * vf + c2m * (gc * gc);
+      sn[j] = sqrtf(vn);
+      mmax = fmaxf(mmax, fabsf(mn[j]));
+      smax = fmaxf(smax, sn[j]);
+      float u = (mn[j] * k1) / (sn[j] * k2 + eps);
+      if (wd != 0.f) u = u + wd * pp[j];
+      pp[j] = pp[j] + neg_lr * u;
+    }
+#pragma unroll
+    for (int o = 1; o < LPB; o <<= 1) {
+      mmax = fmaxf(mmax, __shfl_xor(mmax, o, 64));
+      smax = fmaxf(smax, __shfl_xor(smax, o, 64));
+    }
+    const float nminv = 1.0f / ((mmax <= 0.f) ? 1.0f : mmax);
+    const float nsinv = 1.0f / ((smax <= 0.f) ? 1.0f : smax);
+    unsigned ncm = 0, ncs = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      ncm |= ((unsigned)(adamw_quant_tab(mn[j] * nminv, thr_tab) & 0xff)) << (8 * j);
+      ncs |= ((unsigned)(adamw_quant_tab(sn[j] * nsinv, thr_tab) & 0xff)) << (8 * j);
+    }
+    __builtin_nontemporal_store(ncm, &reinterpret_cast<unsigned*>(m_codes)[i]);
+    __builtin_nontemporal_store(ncs, &reinterpret_cast<unsigned*>(s_codes)[i]);
+    if ((i % LPB) == 0) {
+      m_inv[blk] = nminv;
+      s_inv[blk] = nsinv;
+    }
+    {
+      const f4v o = {pp[0], pp[1], pp[2], pp[3]};
+      __builtin_nontemporal_store(o, &reinterpret_cast<f4v*>(p)[i]);
+    }
+    if (ema) {
+      f4v ev = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(ema)[i]);
+      ev.x = ema_r * ev.x + ema_rm * pp[0];
+      ev.y = ema_r * ev.y + ema_rm * pp[1];
+      ev.z = ema_r * ev.z + ema_rm * pp[2];
+      ev.w = ema_r * ev.w + ema_rm * pp[3];
+      __builtin_nontemporal_store(ev, &reinterpret_cast<f4v*>(ema)[i]);
+    }
+    if (w_bf16) {
+      const u2v o = {pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
+      __builtin_nontemporal_store(o, &reinterpret_cast<u2v*>(w_bf16)[i]);
+    }
+  }
+}
+
+__global__ void __launch_bounds__(256) adamw32_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n,
+                                                      const double* __restrict__ sqnorm, float max_norm, float wd, float c1, float c1m,
+                                                      float c2, float c2m, float eps, const float* __restrict__ cur) {
+  const float neg_lr = cur[0], ema_r = cur[1], ema_rm = cur[2], k1 = cur[4], k2 = cur[5];
+  float gnorm = 0.f;
+  bool do_clip = false;
+  if (sqnorm) {
+    gnorm = (float)sqrt(*sqnorm);
+    do_clip = !(gnorm < max_norm);
+  }
+  const long i_end = min(n, ((long)blockIdx.x + 1) * 1024);  // a contiguous 1024-element slice per workgroup (see lion8_kernel)
+  for (long i = (long)blockIdx.x * 1024 + threadIdx.x; i < i_end; i += 256) {
+    const float gc = clip_grad(g[i], gnorm, max_norm, do_clip);
+    float pv = p[i];
+    const float mn = c1 * m[i] + c1m * gc;
+    const float vn = c2 * v[i] + c2m * (gc * gc);
+    m[i] = mn;
+    v[i] = vn;
+    float u = (mn * k1) / (sqrtf(vn) * k2 + eps);
+    if (wd != 0.f) u = u + wd * pv;
+    pv = pv + neg_lr * u;
+    p[i] = pv;
+    if (ema) ema[i] = ema_r * ema[i] + ema_rm * pv;
+    if (w_bf16) w_bf16[i] = f2bf(pv);
+  }
+}
+
 template <bool SCHED>
 static void launch_lion8(int lpb, int g_bf16, dim3 grid, hipStream_t stream, float* p, const void* g, int8_t* codes, float* inv_scale,
                          float* ema, uint16_t* w_bf16, long n4, const double* sqnorm, const float* thresholds, float max_norm,
@@ -556,6 +735,72 @@ int sdt_opt_schedule_select(int64_t* step, const float* lr_tab, int64_t n_lr, co
                 "sdt_opt_schedule_select: misaligned step counter, table or block");
   hipLaunchKernelGGL(opt_schedule_select_kernel, dim3(1), dim3(64), 0, stream, step, lr_tab, (long)n_lr, ema_tab, (long)n_ema, cur);
   SDT_LAUNCH_CHECK("sdt_opt_schedule_select");
+  return SDT_OK;
+}
+
+int sdt_adamw_select(int64_t* step, double* prods, const float* lr_tab, int64_t n_lr, const float* ema_tab, int64_t n_ema, double lr,
+                     double ema_rate, double b1, double b2, float* cur, hipStream_t stream) {
+  SDT_CHECK_ARG(step && prods && cur, "sdt_adamw_select: null pointer");
+  SDT_CHECK_ARG((lr_tab != nullptr) == (ema_tab != nullptr), "sdt_adamw_select: lr_tab and ema_tab come together or not at all");
+  SDT_CHECK_ARG(!lr_tab || (n_lr >= 1 && n_ema >= 1), "sdt_adamw_select: every table needs at least one entry (n_lr=%ld, n_ema=%ld)",
+                (long)n_lr, (long)n_ema);
+  SDT_CHECK_ARG(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0, "sdt_adamw_select: b1 and b2 must lie in [0, 1) (got %g, %g)", b1, b2);
+  SDT_CHECK_ARG((((uintptr_t)step | (uintptr_t)prods | (uintptr_t)ema_tab) & 7) == 0 && ((uintptr_t)cur & 15) == 0,
+                "sdt_adamw_select: misaligned step counter, products, table or block");
+  hipLaunchKernelGGL(adamw_select_kernel, dim3(1), dim3(64), 0, stream, step, prods, lr_tab, (long)n_lr, ema_tab, (long)n_ema,
+                     (float)(-lr), (float)ema_rate, (float)(1.0 - ema_rate), b1, b2, cur);
+  SDT_LAUNCH_CHECK("sdt_adamw_select");
+  return SDT_OK;
+}
+
+int sdt_adamw8_step(float* p, const void* g, int g_bf16, int8_t* m_codes, float* m_inv_scale, int8_t* s_codes, float* s_inv_scale,
+                    float* ema, uint16_t* w_bf16, int64_t n, int block_size, const double* sqnorm, const float* thresholds,
+                    double max_norm, const float* cur, double wd, double b1, double b2, double eps, hipStream_t stream) {
+  SDT_CHECK_ARG(p && g && m_codes && m_inv_scale && s_codes && s_inv_scale && thresholds && cur, "sdt_adamw8_step: null pointer");
+  SDT_CHECK_ARG(n >= 0 && block_size >= 4 && block_size <= 256 && (block_size & (block_size - 1)) == 0,
+                "sdt_adamw8_step: block_size must be a power of two in [4,256] (got %d)", block_size);
+  SDT_CHECK_ARG(n % block_size == 0, "sdt_adamw8_step: n=%ld not a multiple of block_size=%d", (long)n, block_size);
+  SDT_CHECK_ARG((((uintptr_t)p | (uintptr_t)ema | (uintptr_t)cur) & 15) == 0 && ((uintptr_t)g & (g_bf16 ? 7 : 15)) == 0 &&
+                    (((uintptr_t)m_codes | (uintptr_t)s_codes) & 3) == 0 && ((uintptr_t)w_bf16 & 7) == 0,
+                "sdt_adamw8_step: misaligned buffer");
+  if (n == 0) return SDT_OK;
+  const long n4 = n >> 2;
+  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
+  const dim3 grid(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)), block(256);
+#define LAUNCH_A8B(L, H)                                                                                                          \
+  hipLaunchKernelGGL((adamw8_kernel<L, H>), grid, block, 0, stream, p, g, m_codes, m_inv_scale, s_codes, s_inv_scale, ema,       \
+                     (bf16_t*)w_bf16, n4, sqnorm, thresholds, (float)max_norm, (float)wd, c1, c1m, c2, c2m, (float)eps, cur)
+#define LAUNCH_A8(L)       \
+  do {                     \
+    if (g_bf16)            \
+      LAUNCH_A8B(L, true);  \
+    else                   \
+      LAUNCH_A8B(L, false); \
+  } while (0)
+  switch (block_size >> 2) {
+    case 1: LAUNCH_A8(1); break;
+    case 2: LAUNCH_A8(2); break;
+    case 4: LAUNCH_A8(4); break;
+    case 8: LAUNCH_A8(8); break;
+    case 16: LAUNCH_A8(16); break;
+    case 32: LAUNCH_A8(32); break;
+    default: LAUNCH_A8(64); break;
+  }
+#undef LAUNCH_A8
+#undef LAUNCH_A8B
+  SDT_LAUNCH_CHECK("sdt_adamw8_step");
+  return SDT_OK;
+}
+
+int sdt_adamw32_step(float* p, const float* g, float* m, float* v, float* ema, uint16_t* w_bf16, int64_t n, const double* sqnorm,
+                     double max_norm, const float* cur, double wd, double b1, double b2, double eps, hipStream_t stream) {
+  SDT_CHECK_ARG(p && g && m && v && cur && n >= 0, "sdt_adamw32_step: null pointer or negative n");
+  SDT_CHECK_ARG(((uintptr_t)cur & 15) == 0, "sdt_adamw32_step: cur must be a 16-byte aligned device block");
+  if (n == 0) return SDT_OK;
+  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
+  hipLaunchKernelGGL(adamw32_kernel, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)w_bf16, (long)n,
+                     sqnorm, (float)max_norm, (float)wd, c1, c1m, c2, c2m, (float)eps, cur);
+  SDT_LAUNCH_CHECK("sdt_adamw32_step");
   return SDT_OK;
 }
 

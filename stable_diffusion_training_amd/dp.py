@@ -345,7 +345,9 @@ class GradReducer:
         if not self.shard:
             return
         self.wait_gathered()
-        self._gather_buffers(lambda st: [(st.master, 1), (st.ema, 1), (st.codes, 1), (st.inv_scale, st.block_size)])
+        # (AdamW stores: also the codes and scales of the second moment's root; None for Lion stores and skipped)
+        self._gather_buffers(lambda st: [(st.master, 1), (st.ema, 1), (st.codes, 1), (st.inv_scale, st.block_size),
+                                         (st.codes2, 1), (st.inv_scale2, st.block_size)])
         for st in self.stores:
             st.state_whole = True
 

@@ -46,6 +46,19 @@ def _ceil(a, b):
 # Segment ends (and the bucket boundaries of the sharded optimizer) are multiples of this many elements, so that any bucket cut
 # into 1, 2, 4 or 8 equal slices gives slices that are whole quantisation blocks (block sizes up to 256) and 64-element aligned
 SEG_ALIGN = 8 * 256
+OPTIMIZERS = ("lion", "adamw")
+
+
+def adam_products(n, b1, b2):
+    """(b1^n, b2^n) as n sequential float64 products from 1.0 - what sdt_adamw_select has carried on the device after n steps, bit for
+    bit (one IEEE multiplication per step, no pow).  Stops once both have underflowed to 0."""
+    p1 = p2 = 1.0
+    for _ in range(int(n)):
+        p1 *= b1
+        p2 *= b2
+        if p1 == 0.0 and p2 == 0.0:
+            break
+    return p1, p2
 
 
 @dataclass
@@ -83,11 +96,21 @@ class EmaView:
 
 class ParamStore:
     def __init__(self, spec, *, device, quantise=True, quant_excluded=(), wd_excluded=(), block_size=16,
-                 with_ema=False, trainable=True, quant_mask=None, decay_mask=None, grad_bf16=True):
+                 with_ema=False, trainable=True, quant_mask=None, decay_mask=None, grad_bf16=True, optimizer="lion",
+                 adam_betas=(0.9, 0.999)):
         """spec: ordered list of (path, shape) in forward-execution order.  quant_mask / decay_mask: explicit {path: bool}
         trees (True = quantise / decay) in place of the exclusion patterns (lion_quant.lion_8bit takes masks).
         grad_bf16=False keeps every gradient float32 (lion_quant's GradientTransformation facade: its caller hands in float32 updates
-        and must get the arithmetic of lion_quant.py on exactly those)."""
+        and must get the arithmetic of lion_quant.py on exactly those).
+        optimizer: "lion" (the reference's, the default) or "adamw" (include/sdt.h "AdamW": a second set of state buffers - codes2 /
+        inv_scale2 hold the root of the second moment of the quantised leaves, mom2 the second moment of the others - and the device
+        step counter, the two running products of adam_betas and the step's scalar block; a Lion store has None for all of them)."""
+        if optimizer not in OPTIMIZERS:
+            raise ValueError(f"ParamStore: optimizer must be one of {OPTIMIZERS}, not {optimizer!r}")
+        self.optimizer = optimizer
+        self.adam_betas = tuple(float(b) for b in adam_betas)
+        if optimizer == "adamw" and not all(0.0 <= b < 1.0 for b in self.adam_betas):
+            raise ValueError(f"ParamStore: adam_betas must lie in [0, 1), got {adam_betas!r}")
         self.device = torch.device(device)
         self.block_size = block_size
         self.trainable = trainable
@@ -161,15 +184,26 @@ class ParamStore:
                 self.grad16 = torch.zeros(self.quant_total, dtype=torch.bfloat16, device=dev)
                 self.g32_base = self.quant_total
             self.grad = torch.zeros(max(self.total - self.g32_base, 4), dtype=torch.float32, device=dev)
-            self.codes = torch.full((max(self.quant_total, 4),), 3, dtype=torch.int8, device=dev)  # quant(0) == 3
+            adamw = optimizer == "adamw"
+            # Lion: quant(0) == 3 (the codec's offset); AdamW's codec has no offset: zero is code 0
+            self.codes = torch.full((max(self.quant_total, 4),), 0 if adamw else 3, dtype=torch.int8, device=dev)
             self.inv_scale = torch.ones(max(self.quant_total // block_size, 1), dtype=torch.float32, device=dev)
             self.mom = torch.zeros(max(self.total - self.quant_total, 4), dtype=torch.float32, device=dev)
             self.sqnorm = torch.zeros(1, dtype=torch.float64, device=dev)
             # arrival counter + per-workgroup double partials of the gradient-norm pass (ordered sum, no atomics; zeroed once)
             self.sq_ws = torch.zeros(_lib.load().sdt_sqnorm_workspace_bytes() if dev.type == "cuda" else 8, dtype=torch.uint8, device=dev)
             self.ema = torch.zeros(self.total, dtype=torch.float32, device=dev) if with_ema else None
+            self.codes2 = self.inv_scale2 = self.mom2 = self.adam_step = self.adam_prod = self.adam_cur = None
+            if adamw:
+                self.codes2 = torch.zeros_like(self.codes)
+                self.inv_scale2 = torch.ones_like(self.inv_scale)
+                self.mom2 = torch.zeros_like(self.mom)
+                self.adam_step = torch.zeros(1, dtype=torch.int64, device=dev)     # steps taken, advanced by sdt_adamw_select
+                self.adam_prod = torch.ones(2, dtype=torch.float64, device=dev)    # b1^t, b2^t as running products
+                self.adam_cur = torch.zeros(8, dtype=torch.float32, device=dev)    # the step's scalars (include/sdt.h)
         else:
             self.grad = self.codes = self.inv_scale = self.mom = self.sqnorm = self.ema = self.sq_ws = None
+            self.codes2 = self.inv_scale2 = self.mom2 = self.adam_step = self.adam_prod = self.adam_cur = None
         self.count = 0
         self._prep = None
         self._zero = None
@@ -301,20 +335,30 @@ class ParamStore:
         host = buf.detach().cpu().numpy()
         return {p: host[lf.offset: lf.offset + lf.numel].reshape(lf.shape) for p, lf in self.leaves.items()}
 
-    def export_momentum(self):
-        """{path: (codes int8 [n/bs,bs], inv_scale f32 [n/bs,1])} for quantised leaves, f32 array otherwise."""
+    def export_momentum(self, which="m"):
+        """{path: (codes int8 [n/bs,bs], inv_scale f32 [n/bs,1])} for quantised leaves, f32 array otherwise.
+        AdamW stores: which="m" the first moment, which="s" the second one - for quantised leaves the codes and scales of its ROOT
+        (the codec has no offset: value = (code / 127)^5 / inv_scale), for the others the fp32 second moment itself."""
         self._gather()
+        if which not in ("m", "s") or (which == "s" and self.optimizer != "adamw"):
+            raise ValueError(f"export_momentum: which={which!r} (a {self.optimizer} store has {'m and s' if self.optimizer == 'adamw' else 'm only'})")
+        codes, inv, mom = (self.codes, self.inv_scale, self.mom) if which == "m" else (self.codes2, self.inv_scale2, self.mom2)
         out = {}
         bs = self.block_size
         for p, lf in self.leaves.items():
             if lf.quantised:
-                c = self.codes[lf.offset: lf.offset + lf.numel].view(-1, bs).clone()
-                s = self.inv_scale[lf.offset // bs: (lf.offset + lf.numel) // bs].view(-1, 1).clone()
+                c = codes[lf.offset: lf.offset + lf.numel].view(-1, bs).clone()
+                s = inv[lf.offset // bs: (lf.offset + lf.numel) // bs].view(-1, 1).clone()
                 out[p] = (c, s)
             else:
                 o = lf.offset - self.quant_total
-                out[p] = self.mom[o: o + lf.numel].view(lf.shape).clone()
+                out[p] = mom[o: o + lf.numel].view(lf.shape).clone()
         return out
+
+    def state_bytes(self):
+        """Bytes of optimizer state this store holds (moments only: codes, scales and fp32 moments; no masters, EMA or gradients)."""
+        bufs = (self.codes, self.inv_scale, self.mom, self.codes2, self.inv_scale2, self.mom2)
+        return sum(t.numel() * t.element_size() for t in bufs if t is not None)
 
     # ------------------------------------------------------------------ bf16 compute copies
     def _build_prep(self):
@@ -518,9 +562,13 @@ class ParamStore:
         self.count = int(n)
         if self._sched is not None:
             self._sched["step"].fill_(self.count)
+        if self.optimizer == "adamw" and self.trainable:
+            # the device carries b1^t and b2^t as running float64 products: rebuild them with the same n multiplications
+            self.adam_step.fill_(self.count)
+            self.adam_prod.copy_(torch.tensor(adam_products(self.count, *self.adam_betas), dtype=torch.float64))
 
-    def optimizer_step(self, *, lr, wd, b1=0.9, b2=0.99, max_norm=1.0, ema_rate=0.0, stream=None, shard=None, sq_partials=None,
-                       grad_source="grad"):
+    def optimizer_step(self, *, lr, wd, b1=None, b2=None, max_norm=1.0, ema_rate=0.0, stream=None, shard=None, sq_partials=None,
+                       grad_source="grad", eps=None):
         """clip_by_global_norm(max_norm) -> Lion (8-bit / fp32 momentum) -> decay -> -lr -> apply (-> EMA).
         training_utils.py:379-387 + :732 + :735-746, fused; no host synchronisation (the norm stays on device).
         max_norm None: no clipping (the bare lion_8bit transformation, lion_quant.py:159-211).
@@ -532,7 +580,24 @@ class ParamStore:
         the one the last finish / scale pass computed (or a pass over gacc when that pass ran without norm).
         With a schedule installed (set_schedule) lr and ema_rate name the schedule's base rate and cap, and the step's values come from
         the device: one sdt_opt_schedule_select launch, then the _scheduled sweeps.  Whether the EMA runs is still decided by ema_rate
-        (0: off), not by the scheduled r_t (r_t = 0 means EMA := parameters)."""
+        (0: off), not by the scheduled r_t (r_t = 0 means EMA := parameters).
+        b1 / b2 default to 0.9 / 0.99 (Lion) or the store's adam_betas (AdamW, whose running products are built from them: other values
+        are refused).  AdamW stores (optimizer="adamw"): the same clip-norm passes, one sdt_adamw_select (bias corrections from the device
+        step counter, lr / EMA scalars by value or from the schedule's tables), then the sdt_adamw8_step / sdt_adamw32_step sweeps;
+        eps (default 1e-8) is theirs alone - a Lion store refuses it."""
+        adamw = self.optimizer == "adamw"
+        if adamw:
+            b1 = self.adam_betas[0] if b1 is None else b1
+            b2 = self.adam_betas[1] if b2 is None else b2
+            if (float(b1), float(b2)) != self.adam_betas:
+                raise ValueError(f"optimizer_step: b1={b1!r}, b2={b2!r} but the store carries the running products of adam_betas="
+                                 f"{self.adam_betas!r} (set them when the store is built)")
+            eps = 1e-8 if eps is None else eps
+        else:
+            if eps is not None:
+                raise ValueError("optimizer_step: eps belongs to AdamW; this store's optimizer is Lion (ParamStore(optimizer='adamw'))")
+            b1 = 0.9 if b1 is None else b1
+            b2 = 0.99 if b2 is None else b2
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         sq_ptr = None
         from_acc = grad_source == "acc"
@@ -579,15 +644,42 @@ class ParamStore:
             if torch.cuda.is_current_stream_capturing():
                 self._captured = True
             cur = sc["cur"].data_ptr()
-            _lib.call("sdt_opt_schedule_select", sc["step"].data_ptr(), sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(),
-                      sc["ema_tab"].data_ptr(), sc["ema_tab"].numel() // 2, cur, s)
+            if not adamw:
+                _lib.call("sdt_opt_schedule_select", sc["step"].data_ptr(), sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(),
+                          sc["ema_tab"].data_ptr(), sc["ema_tab"].numel() // 2, cur, s)
+        if adamw:
+            if torch.cuda.is_current_stream_capturing():
+                self._captured = True
+            # one counter for both: adam_step indexes the schedule's tables too (the schedule's own counter and block stay unused)
+            cur = self.adam_cur.data_ptr()
+            tabs = (None, 0, None, 0) if sc is None else (sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(), sc["ema_tab"].data_ptr(),
+                                                          sc["ema_tab"].numel() // 2)
+            _lib.call("sdt_adamw_select", self.adam_step.data_ptr(), self.adam_prod.data_ptr(), *tabs, lr, ema_rate if ema_on else 0.0,
+                      b1, b2, cur, s)
         for (a, b, quant, decay) in pieces:
             n = b - a
             if n == 0:
                 continue
             ema_ptr = self.ema.data_ptr() + 4 * a if ema_on else None
             wd_eff = wd if decay else 0.0
-            if quant:
+            if adamw:
+                if quant:
+                    g16 = self.grad16 is not None and not from_acc
+                    if from_acc:
+                        gp = self.gacc.data_ptr() + 4 * a
+                    else:
+                        gp = self.grad16.data_ptr() + 2 * a if g16 else self.grad.data_ptr() + 4 * a
+                    blk = 4 * (a // self.block_size)
+                    _lib.call("sdt_adamw8_step", self.master.data_ptr() + 4 * a, gp, int(g16), self.codes.data_ptr() + a,
+                              self.inv_scale.data_ptr() + blk, self.codes2.data_ptr() + a, self.inv_scale2.data_ptr() + blk, ema_ptr,
+                              self.w.data_ptr() + 2 * a, n, self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, cur, wd_eff,
+                              b1, b2, eps, s)
+                else:
+                    gp = self.gacc.data_ptr() + 4 * a if from_acc else self.grad.data_ptr() + 4 * (a - self.g32_base)
+                    o = 4 * (a - self.quant_total)
+                    _lib.call("sdt_adamw32_step", self.master.data_ptr() + 4 * a, gp, self.mom.data_ptr() + o, self.mom2.data_ptr() + o,
+                              ema_ptr, self.w.data_ptr() + 2 * a, n, sq_ptr, max_norm, cur, wd_eff, b1, b2, eps, s)
+            elif quant:
                 g16 = self.grad16 is not None and not from_acc
                 if from_acc:
                     gp = self.gacc.data_ptr() + 4 * a

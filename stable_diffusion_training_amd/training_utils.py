@@ -103,19 +103,34 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                                  excluded_layer_pattern_from_weight_decay=(), excluded_layer_from_quantization=(),
                                  lion_8bit_block_size=None, quantize_unet_state=False, quantize_text_encoder_state=False,
                                  with_unet_ema=False, with_text_encoder_ema=False, device="cuda", lr_scheduler="constant",
-                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0):
+                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0, optimizer="lion"):
     """training_utils.py:281-427.  lr = learning_rate / adam_to_lion_scale_factor, wd = 1e-2 * scale, b1=.9, b2=.99,
     chain(clip_by_global_norm(1), lion_8bit | lion).  Builds the flat HBM stores and loads the weights.
     lr_scheduler / lr_schedule / ema_schedule / ema_rate: the per-step schedules of lr_schedule.resolve, installed in each trained store
-    (ParamStore.set_schedule; the lr schedule scales each store's own rate).  "constant" without an EMA schedule installs nothing."""
+    (ParamStore.set_schedule; the lr schedule scales each store's own rate).  "constant" without an EMA schedule installs nothing.
+    optimizer: "lion" (the reference's), "adamw", or dict(name=, b1=, b2=, eps=, weight_decay=).  AdamW (8-bit block-quantised or fp32
+    moments by the same quantize_* switches) takes the learning rates AS GIVEN - an Adam recipe needs no translation, so
+    adam_to_lion_scale_factor does not apply - with wd=1e-2, b1=.9, b2=.999, eps=1e-8 unless the dict says otherwise."""
     out = {"unet_state": None, "text_encoder_state": None}
+    opt = {"name": optimizer} if isinstance(optimizer, str) else dict(optimizer)
+    unknown = set(opt) - {"name", "b1", "b2", "eps", "weight_decay"}
+    if unknown or opt.get("name") not in ("lion", "adamw"):
+        raise ValueError(f"optimizer: 'lion', 'adamw' or dict(name=, b1=, b2=, eps=, weight_decay=), not {optimizer!r}")
+    if opt["name"] == "lion" and len(opt) > 1:
+        raise ValueError("optimizer: Lion's hyper-parameters are the reference's (adam_to_lion_scale_factor); the dict form is AdamW's")
+    adamw = opt["name"] == "adamw"
 
     def make(spec, weights, cfg, fn, lr, quant, ema):
-        hyper = dict(lr=lr / adam_to_lion_scale_factor, wd=1e-2 * adam_to_lion_scale_factor, b1=0.9, b2=0.99, max_norm=1.0)
+        if adamw:
+            hyper = dict(lr=lr, wd=opt.get("weight_decay", 1e-2), b1=opt.get("b1", 0.9), b2=opt.get("b2", 0.999),
+                         eps=opt.get("eps", 1e-8), max_norm=1.0)
+        else:
+            hyper = dict(lr=lr / adam_to_lion_scale_factor, wd=1e-2 * adam_to_lion_scale_factor, b1=0.9, b2=0.99, max_norm=1.0)
+        okw = dict(optimizer="adamw", adam_betas=(hyper["b1"], hyper["b2"])) if adamw else {}
         sched = resolve_schedule(lr_scheduler, hyper["lr"], ema_rate, lr_schedule=lr_schedule, ema_schedule=ema_schedule)
         store = ParamStore(spec, device=device, quantise=quant, quant_excluded=tuple(excluded_layer_from_quantization),
                            wd_excluded=tuple(excluded_layer_pattern_from_weight_decay),
-                           block_size=lion_8bit_block_size or 16, with_ema=ema)
+                           block_size=lion_8bit_block_size or 16, with_ema=ema, **okw)
         store.load(weights)
         if sched is not None:
             store.set_schedule(lr=sched[0], ema=sched[1])
@@ -135,7 +150,7 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
 
 
 def on_device_model_training_state(training_config: TrainingConfig, models=None, device="cuda", *, lr_schedule=None,
-                                   ema_schedule=None):
+                                   ema_schedule=None, optimizer="lion"):
     """training_utils.py:430-501.  `models`: load_models' result - host weight trees + configs
     ({"unet": {"unet_params", "config"}, "vae": {"vae_params", "config"}, "text_encoder": {...}}); None reads the
     diffusers directory at training_config.model_path (checkpoint.load_models).  Note the reference passes NEITHER learning
@@ -143,7 +158,8 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
     training_config.lr_scheduler names the learning-rate schedule (lr_schedule.LR_SCHEDULES); its step counts come as
     lr_schedule=dict(num_warmup_steps=, num_training_steps=, num_cycles=, power=, lr_end=), and
     ema_schedule=dict(kind="warmup", update_after_step=, use_ema_warmup=, inv_gamma=, power=, min_decay=) warms the EMA rate up to
-    training_config.ema_rate (lr_schedule.resolve; ValueError for a name without the counts it needs)."""
+    training_config.ema_rate (lr_schedule.resolve; ValueError for a name without the counts it needs).
+    optimizer: create_lion_optimizer_states' (TrainingConfig has no field for it)."""
     _lib.require_device()
     if models is None:
         models = load_models(training_config)
@@ -156,7 +172,7 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
         quantize_text_encoder_state=training_config.quantize_text_encoder_state,
         with_unet_ema=training_config.accumulate_unet_ema, with_text_encoder_ema=training_config.accumulate_text_encoder_ema,
         device=device, lr_scheduler=training_config.lr_scheduler, lr_schedule=lr_schedule, ema_schedule=ema_schedule,
-        ema_rate=training_config.ema_rate)
+        ema_rate=training_config.ema_rate, optimizer=optimizer)
     vae_cfg = models["vae"]["config"]
     vae_store = ParamStore(nets.vae_encoder_spec(vae_cfg), device=device, trainable=False)
     vae_store.load(models["vae"]["vae_params"])
