@@ -10,7 +10,10 @@ pooled text embedding comes from the towers, and the saves are SDXL pipeline dir
 Schedules: "lr_scheduler" (constant, constant_with_warmup, linear, cosine, cosine_with_restarts, polynomial) takes its counts from the
 optional keys lr_warmup_steps, lr_num_training_steps, lr_num_cycles, lr_power and lr_end; "ema_warmup": true warms the EMA rate up to
 ema_rate (diffusers EMAModel), with the optional ema_inv_gamma, ema_power, ema_min_decay, ema_update_after_step and
-ema_use_warmup_power (the 1 - (1 + s / inv_gamma) ** -power form).  Both advance once per optimizer step."""
+ema_use_warmup_power (the 1 - (1 + s / inv_gamma) ** -power form).  Both advance once per optimizer step.
+--cache-latents DIR (or "cache_latents" in the config): every chunk the run will visit is encoded once with the frozen VAE into a latent
+cache under DIR (latent_cache.build: one record per batch, at the batch composition it is trained at), the VAE's device store is
+dropped, and the steps train from the cache's readers without a VAE."""
 import argparse
 import json
 import os
@@ -22,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.distributed as dist
 
-from stable_diffusion_training_amd import dp, nets
+from stable_diffusion_training_amd import dp, latent_cache, nets
 from stable_diffusion_training_amd import training_utils as tu
 from stable_diffusion_training_amd.checkpoint import gather_rng_states
 from stable_diffusion_training_amd.streamer import DataLoader
@@ -105,6 +108,24 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         tu.load_training_state(resume, unet_state, text_encoder_state, train_rngs, rank=rank, world=world)
         log(f"resumed optimizer / RNG state from {resume} at step {unet_state.step}")
 
+    vae_params = frozen_vae.params  # what save_model writes as the VAE
+    cache_dir = config_dict.get("cache_latents")
+    if cache_dir:
+        # encode every chunk this run visits, once, then train without the VAE: only its host tree stays, for the saves
+        visits, n = [], config_dict["chunk_number"]
+        for _ in range(config_dict["chunk_limit"]):
+            n = 0 if n >= config_dict["chunk_limit"] else n
+            visits.append(n)
+            n += 1
+        for n in dict.fromkeys(visits):
+            dataloader.chunk_number = n
+            dataloader.create_training_dataframe()
+            dataloader.dispatch_worker()
+            count = latent_cache.build(dataloader, frozen_vae, os.path.join(cache_dir, f"rank{rank}", f"chunk{n}"))
+            log(f"cached the latent moments of chunk {n}: {count} batches")
+        vae_params, frozen_vae = frozen_vae.params.full_tree, None
+        torch.cuda.empty_cache()
+
     if rank == 0 and not os.path.isfile(config_dict["loss_csv"]):
         with open(config_dict["loss_csv"], "w") as f:
             f.write("steps, step_size, loss, time, chunk, seed\n")
@@ -113,7 +134,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         base = config_dict["model_path"].split("@")[0] + ("-EMA" if ema else "")
         up = unet_ema_params if (ema and config_dict["accumulate_unet_ema"]) else unet_state.params
         tp = text_encoder_ema_params if (ema and config_dict["accumulate_text_encoder_ema"]) else text_encoder_state.params
-        tu.save_model(model_object_dict, tokenizer, up, tp, frozen_vae.params, f'{base}@{config_dict["chunk_steps"]}')
+        tu.save_model(model_object_dict, tokenizer, up, tp, vae_params, f'{base}@{config_dict["chunk_steps"]}')
         delete_file_or_folder(f'{base}@{config_dict["chunk_steps"] - config_dict["keep_trained_model_buffer"]}')
 
     losses = []
@@ -125,16 +146,19 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         dataloader.prepare_training_dataframe()
         dataloader.create_training_dataframe()
         dataloader.dispatch_worker()
+        batches = dataloader
+        if cache_dir:
+            batches = latent_cache.Reader(os.path.join(cache_dir, f"rank{rank}", f'chunk{config_dict["chunk_number"]}'), device=dev)
         if reducer is not None:
             reducer.gather_state()  # sharded optimizer: whole state on every rank before the rank-0 save (collective; no-op otherwise)
         if rank == 0:  # pre-flight save (training.py:149-184): fail before the chunk, not after it
-            tu.save_model(model_object_dict, tokenizer, unet_state.params, text_encoder_state.params, frozen_vae.params,
+            tu.save_model(model_object_dict, tokenizer, unet_state.params, text_encoder_state.params, vae_params,
                           config_dict["test_save_path"])
             delete_file_or_folder(config_dict["test_save_path"])
         start = time.time()
         train_metrics = []
         for count in range(int(dataloader._bulk_batch_count + dataloader._first_batch_count)):
-            current_batch = dataloader.grab_next_batch()
+            current_batch = batches.grab_next_batch()
             if current_batch == "end_of_batch":
                 break
             if current_batch is None:
@@ -142,9 +166,10 @@ def main(config_dict, models=None, tokenizer=None, log=print):
             w = config_dict["text_encoder_context_window"]
             rows = (-1, 2, w) if sdxl else (-1, w)  # SDXL: (B*k, 2, 77), one row of ids per tower
             current_batch["input_ids"] = current_batch["input_ids"].reshape(rows)
-            current_batch["attention_mask"] = current_batch["attention_mask"].reshape(rows)
+            if "attention_mask" in current_batch:  # unused by the step, and not kept by a latent cache
+                current_batch["attention_mask"] = current_batch["attention_mask"].reshape(rows)
             (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, train_metric, train_rngs) = \
-                train_step_funcs[current_batch["pixel_values"].shape](
+                train_step_funcs[tu.step_key(current_batch)](
                     unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, current_batch, train_rngs,
                     frozen_vae, frozen_schedulers)
             train_metrics.append(train_metric["loss"])  # device scalars: reading them below is the only synchronisation
@@ -182,6 +207,8 @@ if __name__ == "__main__":
     ap.add_argument("--micro-batches", type=int, default=None, help="gradient accumulation over K micro-batches per step")
     ap.add_argument("--optimizer", choices=("lion", "adamw"), default=None,
                     help="lion (the reference's, default) or adamw: learning rates taken as given, 8-bit moments where the config quantises")
+    ap.add_argument("--cache-latents", metavar="DIR", default=None,
+                    help="encode the run's chunks once into a latent cache under DIR, drop the VAE and train from the cache")
     args = ap.parse_args()
     with open(args.config) as f:
         cfg = json.load(f)
@@ -189,4 +216,6 @@ if __name__ == "__main__":
         cfg["micro_batches"] = args.micro_batches
     if args.optimizer is not None:
         cfg["optimizer"] = args.optimizer
+    if args.cache_latents is not None:
+        cfg["cache_latents"] = args.cache_latents
     main(cfg)

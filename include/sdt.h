@@ -100,6 +100,20 @@ int sdt_sampler_cfg_step(const uint16_t* pred_nhwc, float* latents_nchw, uint16_
 /* latents (B,L,H,W) f32 = (mean + exp(0.5*clip(logvar,-30,20))*eps)*scale from moments bf16 (B,H,W,moment_stride) */
 int sdt_vae_posterior_sample(const uint16_t* moments_nhwc, const float* eps_nhwc, float* latents_nchw, int B, int L,
                              int H, int W, int moment_stride, float scale, hipStream_t stream);
+/* The front of a training step from cached posterior moments, in one launch and with the bits of the chain it replaces
+ * (sdt_vae_posterior_sample, the fp32 noise mixing of train_step, sdt_add_noise_velocity):
+ *   x0 = (mean + exp(0.5*clip(logvar,-30,20))*eps)*scale;  n = noise [+ offset[b][c]*offset_mag] [+ perturb_mag*perturb];
+ *   noisy = sqrt(acp[t])*x0 + sqrt(1-acp[t])*n;  target = n (prediction_type 0) or sqrt(acp[t])*n - sqrt(1-acp[t])*x0 (2).
+ * moments bf16 (B,H,W,moment_stride >= 2L), eps f32 (B,H,W,L), noise / perturb f32 (B,L,H,W), offset f32 (B,L); offset and
+ * perturb may be NULL (their magnitude must then be 0).  noisy_nhwc_bf16 (B,H,W,cpad) zero padded; target_nchw f32 (B,L,H,W),
+ * NULL allowed only for epsilon without offset or perturbation noise (the target is the noise input); latents_nchw and
+ * noisy_nchw f32 (B,L,H,W) optional.  16-byte loads / stores where moment_stride % 8 == 0 and L % 4 == 0 / cpad % 8 == 0 and the
+ * base is aligned, a scalar path otherwise. */
+int sdt_latent_noise_target(const uint16_t* moments_nhwc, const float* eps_nhwc, const float* noise_nchw, const float* offset,
+                            const float* perturb_nchw, const int32_t* timesteps, const float* alphas_cumprod,
+                            uint16_t* noisy_nhwc_bf16, float* target_nchw, float* latents_nchw, float* noisy_nchw, int B, int L,
+                            int H, int W, int moment_stride, int cpad, float scale, float offset_mag, float perturb_mag,
+                            int prediction_type, hipStream_t stream);
 /* loss_accum += mean(w_b*(target-pred)^2); dpred = d loss / d pred (bf16 NHWC, cpad channels).
  * REDUCTION WORKSPACES (this call, sdt_sqnorm_accumulate, sdt_colsum_*): sums that cross workgroups use no float atomics - each
  * workgroup stores a partial, the one that arrives last adds them in a fixed order, so results are bitwise reproducible.  They

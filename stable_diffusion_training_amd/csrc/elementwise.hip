@@ -179,6 +179,81 @@ __global__ void __launch_bounds__(256) posterior_sample_kernel(const bf16_t* __r
   }
 }
 
+// The front of a training step from cached posterior moments in one launch: posterior_sample_kernel, the noise mixing that
+// train_step does with torch element-wise kernels in between (noise + offset[b][c] * offset_mag, then + perturb_mag * perturb:
+// separate fp32 multiplies and adds) and add_noise_kernel.  One thread per latent pixel, channels in groups of 8.
+// The results carry the bits of that chain, so every rounding point is spelled out instead of left to contraction: the two
+// kernels above compile to  x0 = fl(fma(e, eps, mean) * scale),  noisy = fma(sa, x0, fl(so * n)),  velocity = fl(sa * n) - fl(so * x0).
+// VEC_IN: a pixel's moments by 16-byte loads (mstride % 8 == 0, L % 4 == 0, 16-byte aligned base: the log-variances then start at
+// a 16- or 8-byte boundary of the row); VEC_OUT: the bf16 row by 16-byte stores (cpad % 8 == 0, aligned base).
+template <bool VEC_IN, bool VEC_OUT>
+__global__ void __launch_bounds__(256) latent_noise_target_kernel(
+    const bf16_t* __restrict__ mom, const float* __restrict__ eps, const float* __restrict__ noise, const float* __restrict__ offset,
+    const float* __restrict__ perturb, const int* __restrict__ t, const float* __restrict__ acp, bf16_t* __restrict__ noisy_nhwc,
+    float* __restrict__ target, float* __restrict__ lat_nchw, float* __restrict__ noisy_nchw, int B, int L, int HW, int mstride,
+    int cpad, float scale, float offset_mag, float perturb_mag, int ptype) {
+#pragma clang fp contract(off)
+  const long total = (long)B * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / HW), p = (int)(i % HW);
+    const float a = acp[t[b]];
+    const float sa = sqrtf(a), so = sqrtf(1.0f - a);
+    const bf16_t* row = mom + i * mstride;
+    for (int c0 = 0; c0 < cpad; c0 += 8) {
+      float nz[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (c0 < L) {
+        float mean[8], lv[8];
+        if (VEC_IN) {
+          // mean: columns [c0, c0 + 8) (the row holds them: c0 + 8 <= roundup8(2L) <= mstride); log-variance: columns from L + c0,
+          // which sit at dword 0 or 2 of an aligned vector; the vector after it is read only where it holds a channel below L
+          unpack8(*reinterpret_cast<const uint4*>(row + c0), mean);
+          const int s = (L + c0) & 7;
+          const uint4 va = *reinterpret_cast<const uint4*>(row + L + c0 - s);
+          uint4 v = va;
+          if (s) {
+            uint4 vb = make_uint4(0u, 0u, 0u, 0u);
+            if (c0 + 4 < L) vb = *reinterpret_cast<const uint4*>(row + L + c0 - s + 8);
+            v = make_uint4(va.z, va.w, vb.x, vb.y);
+          }
+          unpack8(v, lv);
+        } else {
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const bool in = c0 + j < L;
+            mean[j] = in ? bf2f(row[c0 + j]) : 0.f;
+            lv[j] = in ? bf2f(row[L + c0 + j]) : 0.f;
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int c = c0 + j;
+          if (c < L) {
+            const long off = ((long)b * L + c) * HW + p;
+            float l = lv[j];
+            l = l < -30.f ? -30.f : (l > 20.f ? 20.f : l);  // keeps a NaN, as posterior_sample_kernel
+            const float x0 = __fmaf_rn(__expf(0.5f * l), eps[i * L + c], mean[j]) * scale;
+            float n = noise[off];
+            if (offset) n = n + offset[b * L + c] * offset_mag;
+            if (perturb) n = n + perturb_mag * perturb[off];
+            const float v = __fmaf_rn(sa, x0, so * n);
+            nz[j] = v;
+            if (lat_nchw) lat_nchw[off] = x0;
+            if (noisy_nchw) noisy_nchw[off] = v;
+            if (target) target[off] = ptype == 2 ? sa * n - so * x0 : n;
+          }
+        }
+      }
+      if (VEC_OUT) {
+        *reinterpret_cast<uint4*>(noisy_nhwc + i * cpad + c0) = pack8(nz);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (c0 + j < cpad) noisy_nhwc[i * cpad + c0 + j] = f2bf(nz[j]);
+      }
+    }
+  }
+}
+
 // pred bf16 NHWC (B,h,w,cpad), target f32 NCHW (B,C,h,w), w f32 (B) or null.
 // loss_sum += sum w*(t-p)^2 * inv_count ; dpred (bf16 NHWC cpad) = -2*w*(t-p)*inv_count
 __global__ void __launch_bounds__(256) mse_kernel(const bf16_t* __restrict__ pred, const float* __restrict__ target,
@@ -720,6 +795,33 @@ int sdt_vae_posterior_sample(const uint16_t* moments_nhwc, const float* eps_nhwc
   hipLaunchKernelGGL(posterior_sample_kernel, dim3(sdt_grid_1d((long)B * H * W * L, 256)), dim3(256), 0, stream,
                      (const bf16_t*)moments_nhwc, eps_nhwc, latents_nchw, B, L, H * W, moment_stride, scale);
   SDT_LAUNCH_CHECK("sdt_vae_posterior_sample");
+  return SDT_OK;
+}
+
+int sdt_latent_noise_target(const uint16_t* moments_nhwc, const float* eps_nhwc, const float* noise_nchw, const float* offset,
+                            const float* perturb_nchw, const int32_t* timesteps, const float* alphas_cumprod,
+                            uint16_t* noisy_nhwc_bf16, float* target_nchw, float* latents_nchw, float* noisy_nchw, int B, int L,
+                            int H, int W, int moment_stride, int cpad, float scale, float offset_mag, float perturb_mag,
+                            int prediction_type, hipStream_t stream) {
+  SDT_CHECK_ARG(moments_nhwc && eps_nhwc && noise_nchw && timesteps && alphas_cumprod && noisy_nhwc_bf16,
+                "sdt_latent_noise_target: null pointer");
+  SDT_CHECK_ARG(B > 0 && L > 0 && H > 0 && W > 0 && cpad >= L && moment_stride >= 2 * L,
+                "sdt_latent_noise_target: bad shape B=%d L=%d H=%d W=%d moment_stride=%d cpad=%d (cpad >= L, moment_stride >= 2L)", B, L,
+                H, W, moment_stride, cpad);
+  SDT_CHECK_ARG(prediction_type == 0 || prediction_type == 2,
+                "sdt_latent_noise_target: prediction_type %d (0 epsilon, 2 v_prediction)", prediction_type);
+  SDT_CHECK_ARG(offset || offset_mag == 0.f, "sdt_latent_noise_target: offset_mag %g needs the offset noise", offset_mag);
+  SDT_CHECK_ARG(perturb_nchw || perturb_mag == 0.f, "sdt_latent_noise_target: perturb_mag %g needs the perturbation noise", perturb_mag);
+  SDT_CHECK_ARG(target_nchw || (prediction_type == 0 && !offset && !perturb_nchw),
+                "sdt_latent_noise_target: the target may be NULL only for epsilon without offset or perturbation noise (it is the noise)");
+  const bool vin = moment_stride % 8 == 0 && L % 4 == 0 && ((uintptr_t)moments_nhwc & 15) == 0;
+  const bool vout = cpad % 8 == 0 && ((uintptr_t)noisy_nhwc_bf16 & 15) == 0;
+  auto kern = vin ? (vout ? latent_noise_target_kernel<true, true> : latent_noise_target_kernel<true, false>)
+                  : (vout ? latent_noise_target_kernel<false, true> : latent_noise_target_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(sdt_grid_1d((long)B * H * W, 256)), dim3(256), 0, stream, (const bf16_t*)moments_nhwc, eps_nhwc,
+                     noise_nchw, offset, perturb_nchw, timesteps, alphas_cumprod, (bf16_t*)noisy_nhwc_bf16, target_nchw, latents_nchw,
+                     noisy_nchw, B, L, H * W, moment_stride, cpad, scale, offset_mag, perturb_mag, prediction_type);
+  SDT_LAUNCH_CHECK("sdt_latent_noise_target");
   return SDT_OK;
 }
 

@@ -182,6 +182,12 @@ def gn_arena_end(device):
         a[2] = False
 
 
+def gn_arena_active(device):
+    """Whether a step's arena is open on this device (gn_arena_begin without its gn_arena_end)."""
+    a = _GN_ARENA.get(device)
+    return a is not None and a[2]
+
+
 def _arena_zeros(n, device):
     """n zero fp32 elements: a slice of the per-step arena (one memset per step) while a step is open, else a fresh tensor."""
     a = _GN_ARENA.get(device)

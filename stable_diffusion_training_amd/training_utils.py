@@ -19,7 +19,7 @@ from . import _lib, nets, ops, trace
 from .checkpoint import load_models, load_training_state, save_model, save_training_state  # noqa: F401  (reference names)
 from .lr_schedule import resolve as resolve_schedule
 from .params import EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
-from .schedulers import DDPMScheduler
+from .schedulers import _PTYPE, DDPMScheduler
 
 
 @dataclass
@@ -208,6 +208,65 @@ def assemble_context(hs, batch, strip_bos_eos_token):
     return e.view(batch, -1, d)
 
 
+def encode_latent_moments(frozen_vae, pixel_values):
+    """The pixel front of a step: f32 NCHW (B,3,H,W) device pixels -> the frozen VAE's posterior moments, bf16 NHWC (B,H/8,W/8,2L)
+    (mean | log-variance), which is what a latent cache stores (latent_cache.build) and what train_step samples from.  Inside a step
+    the GroupNorm statistics go to the step's arena; called on its own it opens and closes one."""
+    vae_store, vae_cfg = frozen_vae.params, frozen_vae.call
+    dev = vae_store.device
+    B, C_in, H, W = pixel_values.shape
+    own_arena = not ops.gn_arena_active(dev)
+    if own_arena:
+        ops.gn_arena_begin(dev)
+    try:
+        pix = torch.empty(B, H, W, 8, dtype=torch.bfloat16, device=dev)
+        _lib.call("sdt_nchw_f32_to_nhwc_bf16", pixel_values.data_ptr(), pix.data_ptr(), B, C_in, H, W, 8,
+                  torch.cuda.current_stream().cuda_stream)
+        with trace.phase("vae_encode"):
+            return nets.vae_encode_moments(vae_store, vae_cfg, pix)
+    finally:
+        if own_arena:
+            ops.gn_arena_end(dev)
+
+
+def step_key(batch, downscale=8):
+    """The key of dp_compile_all_unique_resolution's table for a loader batch of either kind: pixel_values' shape (B,3,H,W), or
+    the shape of the pixels that cached latent_moments (B,h,w,2L) were encoded from, (B,3,h*downscale,w*downscale)."""
+    if "pixel_values" in batch:
+        return tuple(int(n) for n in batch["pixel_values"].shape)
+    B, h, w, _ = batch["latent_moments"].shape
+    return (int(B), 3, int(h) * downscale, int(w) * downscale)
+
+
+def _check_batch(batch, unet_cfg, frozen_vae_state, device):
+    """ValueError for a batch train_step cannot run, before any kernel.  Returns whether the batch holds cached moments."""
+    has_px, has_mom = "pixel_values" in batch, "latent_moments" in batch
+    if has_px and has_mom:
+        raise ValueError("a batch holds either pixel_values or latent_moments, not both")
+    if not has_px and not has_mom:
+        raise ValueError("a batch needs pixel_values (f32 (B,3,H,W)) or latent_moments (bf16 (B,h,w,2L))")
+    if has_px:
+        if frozen_vae_state is None:
+            raise ValueError("pixel_values need the frozen VAE: frozen_vae_state is None (only latent_moments train without it)")
+        return False
+    m = batch["latent_moments"]
+    if not torch.is_tensor(m) or m.dtype != torch.bfloat16 or m.dim() != 4:
+        raise ValueError(f"latent_moments must be a bfloat16 (B,h,w,2L) tensor, not {getattr(m, 'dtype', type(m))} "
+                         f"{tuple(getattr(m, 'shape', ()))}")
+    if m.device.type != device.type or (device.index is not None and m.device.index != device.index):
+        raise ValueError(f"latent_moments live on {m.device}, the step runs on {device}")
+    if m.shape[3] % 2:
+        raise ValueError(f"latent_moments' last dimension holds mean | log-variance and must be even, not {m.shape[3]}")
+    if not m.is_contiguous():
+        raise ValueError("latent_moments must be contiguous")
+    if m.shape[3] // 2 != unet_cfg["in_channels"]:
+        raise ValueError(f"latent_moments hold {m.shape[3] // 2} latent channels, the UNet's in_channels is {unet_cfg['in_channels']}")
+    if unet_cfg.get("addition_embed_type") == "text_time" and "time_ids" not in batch:
+        raise ValueError("a text_time (SDXL) UNet's default time_ids come from the pixel size, which cached latent_moments no longer "
+                         "carry: the batch must hold time_ids")
+    return True
+
+
 _FUSED_NORM = True  # False: always the pass over the gradient buffer (same bits)
 
 
@@ -218,6 +277,11 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     """One DDPM training step on this rank's shard of the batch (training_utils.py:504-762), in place.
 
     batch: {"pixel_values": f32 (B,3,H,W) NCHW device tensor, "input_ids": i32 (B*k,77), "attention_mask": unused}.
+    Instead of pixel_values a batch may hold "latent_moments": the bf16 (B,h,w,2L) contiguous device tensor encode_latent_moments
+    gives for those pixels (latent_cache keeps them on disk).  The step then skips the VAE - frozen_vae_state may be None - and its
+    front is one launch (sdt_latent_noise_target); the draws, and with the same moments every bit of the result, are the pixel
+    step's.  ValueError for both keys or neither, pixel_values without a VAE, moments of another dtype / layout / channel count, and
+    for a text_time UNet without time_ids (their default needs the pixel size).
     A `text_time` (SDXL) UNet also reads "time_ids" i32 (B,6) - (H, W, 0, 0, H, W) when absent - and "text_embeds" (B,1280), unless the
     text encoder is in SDXL mode (nets.dual_clip_config(sdxl_conditioning=True)): then input_ids are (B*k,2,77) (or (B, k*2*77)), the
     towers compute the pooled embedding (nets.sdxl_text_forward; from each sample's first window) and a text_embeds entry is refused.
@@ -235,13 +299,14 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         raise ValueError("the text encoder is in SDXL mode and computes the pooled text embedding itself: a batch in that mode must "
                          "not carry text_embeds")
     us, ts = unet_state.store, text_encoder_state.store
-    vae_store, vae_cfg = frozen_vae_state.params, frozen_vae_state.call
     sched, sched_state = frozen_noise_scheduler_state.call, frozen_noise_scheduler_state.params
     dev = us.device
+    cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev)
+    image_key = "latent_moments" if cached else "pixel_values"
     stream = torch.cuda.current_stream().cuda_stream
     rand = rand or {}
     K = micro_batches
-    N = batch["pixel_values"].shape[0]
+    N = batch[image_key].shape[0]
     if not isinstance(K, int) or K < 1 or N % K:
         raise ValueError(f"micro_batches={micro_batches!r} must be a positive integer that divides the batch ({N})")
     if K > 1 and aux is not None:
@@ -249,7 +314,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     if K > 1 and reducer is not None and reducer.shard:
         raise ValueError("micro_batches > 1 is not supported with the sharded optimizer (GradReducer(shard=True))")
     B = N // K
-    L = vae_cfg["latent_channels"]
+    L = batch["latent_moments"].shape[3] // 2 if cached else frozen_vae_state.call["latent_channels"]
 
     if reducer is not None:
         reducer.begin_step(hold=K > 1)  # accumulating: no bucket leaves before the last micro-batch (exchange_accumulated)
@@ -262,26 +327,27 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         else:
             sl = slice(k * B, (k + 1) * B)
             kc = batch["input_ids"].shape[0] // N  # text-encoder rows per sample
-            mb = {n: v[sl] for n, v in batch.items() if n in ("pixel_values", "text_embeds", "time_ids")}
+            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids")}
             mb["input_ids"] = batch["input_ids"][k * B * kc: (k + 1) * B * kc]
             rnd = {n: v[sl] for n, v in rand.items()}
-        px = mb["pixel_values"]
-        _, C_in, H, W = px.shape
 
         ops.gn_arena_begin(dev)  # GroupNorm statistics accumulated by producer epilogues: one memset per (micro-)batch
 
         # VAE encode -> posterior sample -> NCHW * 0.18215           (training_utils.py:574-586)
-        pix = torch.empty(B, H, W, 8, dtype=torch.bfloat16, device=dev)
-        _lib.call("sdt_nchw_f32_to_nhwc_bf16", px.data_ptr(), pix.data_ptr(), B, C_in, H, W, 8, stream)
-        with trace.phase("vae_encode"):
-            moments = nets.vae_encode_moments(vae_store, vae_cfg, pix)
+        if cached:
+            moments = mb["latent_moments"]
+            H = W = None  # the pixel size is not known (and not needed: a text_time batch carries its time_ids)
+        else:
+            H, W = mb["pixel_values"].shape[2:]
+            moments = encode_latent_moments(frozen_vae_state, mb["pixel_values"])
         h, w = moments.shape[1], moments.shape[2]
         eps = rnd.get("posterior_eps")
         if eps is None:
             eps = torch.randn(B, h, w, L, device=dev, generator=train_rng)
-        latents = torch.empty(B, L, h, w, dtype=torch.float32, device=dev)
-        _lib.call("sdt_vae_posterior_sample", moments.data_ptr(), eps.data_ptr(), latents.data_ptr(), B, L, h, w,
-                  moments.shape[3], vae_scale, stream)
+        if not cached:
+            latents = torch.empty(B, L, h, w, dtype=torch.float32, device=dev)
+            _lib.call("sdt_vae_posterior_sample", moments.data_ptr(), eps.data_ptr(), latents.data_ptr(), B, L, h, w,
+                      moments.shape[3], vae_scale, stream)
 
         # The frozen VAE is all the step has read so far: the trained weights are first touched here.  With the sharded optimizer the
         # all-gather of the bf16 mirrors the previous step's owners wrote is still running beside the VAE encode (dp.GradReducer.wait_gathered)
@@ -298,16 +364,19 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         noise = rnd.get("noise")
         if noise is None:
             noise = torch.randn(B, L, h, w, device=dev, generator=train_rng)
+        off = pn = None
         if offset_noise_magnitude:
             off = rnd.get("offset_noise")
             if off is None:
                 off = torch.randn(B, L, 1, 1, device=dev, generator=train_rng)
-            noise = noise + off * offset_noise_magnitude
+            if not cached:
+                noise = noise + off * offset_noise_magnitude
         if perturbation_noise_magnitude:
             pn = rnd.get("perturb_noise")
             if pn is None:
                 pn = torch.randn(B, L, h, w, device=dev, generator=train_rng)
-            noise = noise + perturbation_noise_magnitude * pn
+            if not cached:
+                noise = noise + perturbation_noise_magnitude * pn
         noise = noise.contiguous()
         timesteps = rnd.get("timesteps")
         if timesteps is None:
@@ -315,8 +384,28 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         timesteps = timesteps.to(torch.int32).contiguous()
 
         # forward diffusion (+ v target)                              (training_utils.py:628-633, 688-701)
-        noisy, target, noisy_nchw = sched.add_noise_and_target(sched_state, latents, noise, timesteps, cpad=8,
-                                                               want_noisy_nchw=aux is not None)
+        if cached:
+            # posterior sample, the mixing above, add_noise and the target in one launch, with the bits of the pixel path's chain
+            if sched.prediction_type not in ("epsilon", "v_prediction"):
+                raise ValueError(f"Unknown prediction type {sched.prediction_type}")  # training_utils.py:697-701
+            cpad = -(-L // 8) * 8
+            eps = eps.contiguous()
+            off = None if off is None else off.contiguous()
+            pn = None if pn is None else pn.contiguous()
+            noisy = torch.empty(B, h, w, cpad, dtype=torch.bfloat16, device=dev)
+            plain = sched.prediction_type == "epsilon" and off is None and pn is None  # the target is the noise as drawn
+            target = noise if plain else torch.empty(B, L, h, w, dtype=torch.float32, device=dev)
+            latents = torch.empty(B, L, h, w, dtype=torch.float32, device=dev) if aux is not None else None
+            noisy_nchw = torch.empty(B, L, h, w, dtype=torch.float32, device=dev) if aux is not None else None
+            ptr = lambda t: None if t is None else t.data_ptr()
+            _lib.call("sdt_latent_noise_target", moments.data_ptr(), eps.data_ptr(), noise.data_ptr(), ptr(off), ptr(pn),
+                      timesteps.data_ptr(), sched_state.alphas_cumprod.data_ptr(), noisy.data_ptr(), None if plain else target.data_ptr(),
+                      ptr(latents), ptr(noisy_nchw), B, L, h, w, moments.shape[3], cpad, vae_scale,
+                      offset_noise_magnitude if off is not None else 0.0, perturbation_noise_magnitude if pn is not None else 0.0,
+                      _PTYPE[sched.prediction_type], stream)
+        else:
+            noisy, target, noisy_nchw = sched.add_noise_and_target(sched_state, latents, noise, timesteps, cpad=8,
+                                                                   want_noisy_nchw=aux is not None)
 
         # text encoder + context assembly                             (training_utils.py:635-674)
         ids = mb["input_ids"]
