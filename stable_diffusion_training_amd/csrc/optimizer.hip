@@ -8,15 +8,21 @@
 // Algorithmic bytes per parameter: g 4r + p 4r/4w + code 1r/1w + scale (4r/4w)/block (+ema 4r/4w, +bf16 2w).
 // This translation unit is compiled with -ffp-contract=off so that every multiply/add rounds
 // separately, as the NumPy float32 oracle (and XLA elementwise f32) does.
+#include <type_traits>
+
 #include "sdt_common.h"
 
 #define LION_OFFSET 3.7398995e-09f  // lion_quant.py:49
 
-__device__ __forceinline__ float lion_deq(int code) {  // lion_quant.py:61-64
+// The 8-bit block codec.  OFFSET: the reference's form (Lion's momentum), which shifts every value by LION_OFFSET.  Without it
+// (AdamW's moments) code = sign(x) * c(|x|) with the same threshold table (a function of the magnitude alone) and
+// deq = (code / 127)^5, so zero <-> code 0 and a parameter whose gradient is exactly zero moves by decay alone.
+template <bool OFFSET>
+__device__ __forceinline__ float codec_deq(int code) {  // lion_quant.py:61-64
   float t = (float)code / 127.0f;
   float t2 = t * t;
   float t4 = t2 * t2;
-  return t4 * t - LION_OFFSET;
+  return OFFSET ? t4 * t - LION_OFFSET : t4 * t;
 }
 // _quantize (lion_quant.py:52-59): code = rint(sign(x + offset) * |x + offset|^(1/5) * 127).
 // The same integer without powf: _quantize is a monotone step function of a = |x + offset|, described exactly by the 127
@@ -24,8 +30,9 @@ __device__ __forceinline__ float lion_deq(int code) {  // lion_quant.py:61-64
 // power / multiply / rint of the definition, lion_codec.quantization_thresholds).  v_log_f32 / v_exp_f32 give the code to
 // well within one unit; two threshold reads settle it: thr[c] <= a < thr[c + 1].  Bit-exact against the host definition at
 // every rounding boundary, and no device/host pow ulp disagreement (the HBM-bound sweep was VALU-bound on powf).
-__device__ __forceinline__ int lion_quant_tab(float x, const float* __restrict__ thr) {
-  const float xo = x + LION_OFFSET;
+template <bool OFFSET>
+__device__ __forceinline__ int codec_quant(float x, const float* __restrict__ thr) {
+  const float xo = OFFSET ? x + LION_OFFSET : x;
   const float a = fabsf(xo);
   const float q = __builtin_amdgcn_exp2f(0.2f * __builtin_amdgcn_logf(a)) * 127.0f;
   const float r = rintf(q);
@@ -35,53 +42,40 @@ __device__ __forceinline__ int lion_quant_tab(float x, const float* __restrict__
   if (fabsf(q - r) > 0.5f - 2.5e-4f) c += (a >= thr[c + 1] ? 1 : 0) - (a < thr[c] ? 1 : 0);
   return xo < 0.f ? -c : c;
 }
-__device__ __forceinline__ void lion_load_tables(float* deq_tab, float* thr_tab, const float* __restrict__ thr) {
-  // exact lion_deq() of every int8 code (the /127 and the 5th power done once) and the codec thresholds, in LDS
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) deq_tab[i] = lion_deq(i - 128);
+template <bool OFFSET>
+__device__ __forceinline__ void codec_load_tables(float* deq_tab, float* thr_tab, const float* __restrict__ thr) {
+  // exact codec_deq() of every int8 code (the /127 and the 5th power done once) and the codec thresholds, in LDS
+  for (int i = threadIdx.x; i < 256; i += blockDim.x) deq_tab[i] = codec_deq<OFFSET>(i - 128);
   for (int i = threadIdx.x; i < 129; i += blockDim.x) thr_tab[i] = i < 128 ? thr[i] : __builtin_inff();
   __syncthreads();
 }
 
-// Sum of squares in double: every product of two floats is exact in double and the running sum carries ~1e-16 relative
-// error, so the float32 norm the optimizer kernels derive from it is the float32 rounding of the true norm - the value
-// optax.global_norm rounds to - and the clipped gradients (g / norm) match the host definition bit for bit.  The pass is
-// HBM-bound (4 B per parameter); four double FMAs per 16 bytes are far below the fp64 vector rate.
-// Workgroups store their double partial sums to `part`; the one that arrives last adds them in workgroup order into *out (no
-// float / double atomics: the norm, and with it every clipped gradient, is bitwise reproducible).
-// G16: the buffer holds bf16 values (the kernel leaves' gradients [r4]): four per 8 bytes, widened exactly.
-template <bool G16>
-__global__ void __launch_bounds__(256) sqnorm_kernel(const void* __restrict__ gv, long n, double* __restrict__ out, int* counter,
-                                                     double* __restrict__ part) {
-  const long nv = n >> 2;
-  double d0 = 0.0, d1 = 0.0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-    float4 v;
-    if (G16) {
-      const uint2 h = reinterpret_cast<const uint2*>(gv)[i];
-      v.x = __uint_as_float(h.x << 16); v.y = __uint_as_float(h.x & 0xffff0000u);
-      v.z = __uint_as_float(h.y << 16); v.w = __uint_as_float(h.y & 0xffff0000u);
-    } else {
-      v = reinterpret_cast<const float4*>(gv)[i];
-    }
-    d0 = fma((double)v.x, (double)v.x, d0);
-    d1 = fma((double)v.y, (double)v.y, d1);
-    d0 = fma((double)v.z, (double)v.z, d0);
-    d1 = fma((double)v.w, (double)v.w, d1);
-  }
-  double dacc = d0 + d1;
-  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
-    const float v = G16 ? bf2f(reinterpret_cast<const bf16_t*>(gv)[(nv << 2) + threadIdx.x]) : reinterpret_cast<const float*>(gv)[(nv << 2) + threadIdx.x];
-    dacc += (double)v * (double)v;
-  }
+// ------------------------------------------------------------------------------------------------- ordered sums in double
+// One float4 of the norm walk: d0 takes x and z, d1 takes y and w.  Every kernel that feeds a squared norm walks its buffer with
+// this, so two of them over the same values and grid produce the same bits.
+__device__ __forceinline__ void sq_accumulate(const f32x4_t v, double& d0, double& d1) {
+  d0 = fma((double)v.x, (double)v.x, d0);
+  d1 = fma((double)v.y, (double)v.y, d1);
+  d0 = fma((double)v.z, (double)v.z, d0);
+  d1 = fma((double)v.w, (double)v.w, d1);
+}
+
+// *out += the sum of every thread's dacc over the whole grid (256 threads per workgroup), in a fixed order.  Workgroups store
+// their double partial sums to `part`; the one that arrives last adds them in workgroup order into *out (no float / double atomics:
+// the result is bitwise reproducible).  PAIRWISE: the workgroup's partial is the tree over its four waves instead of their
+// sequential sum - the association each caller has always had.  Returns in every workgroup but the last early: call it last.
+template <bool PAIRWISE>
+__device__ __forceinline__ void ordered_sum_f64(double dacc, double* __restrict__ out, int* counter, double* __restrict__ part) {
   for (int o = 32; o > 0; o >>= 1) dacc += __shfl_xor(dacc, o, 64);
   __shared__ double dsc[16];
   __shared__ int s_last;
-  const int w = threadIdx.x >> 6;
+  const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
   if ((threadIdx.x & 63) == 0) dsc[w] = dacc;
   __syncthreads();
   if (threadIdx.x == 0) {
     double t = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += dsc[i];
+    if (PAIRWISE) t = (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]);
+    else for (int i = 0; i < nw; ++i) t += dsc[i];
     sdt_store_wt(part + blockIdx.x, t);
   }
   if (!sdt_arrive_last<true>(counter, (int)gridDim.x, &s_last)) return;
@@ -95,45 +89,65 @@ __global__ void __launch_bounds__(256) sqnorm_kernel(const void* __restrict__ gv
   if (threadIdx.x == 0) *out += (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]);
 }
 
+// Sum of squares in double: every product of two floats is exact in double and the running sum carries ~1e-16 relative
+// error, so the float32 norm the optimizer kernels derive from it is the float32 rounding of the true norm - the value
+// optax.global_norm rounds to - and the clipped gradients (g / norm) match the host definition bit for bit.  The pass is
+// HBM-bound (4 B per parameter); four double FMAs per 16 bytes are far below the fp64 vector rate.
+// G16: the buffer holds bf16 values (the kernel leaves' gradients [r4]): four per 8 bytes, widened exactly.
+template <bool G16>
+__global__ void __launch_bounds__(256) sqnorm_kernel(const void* __restrict__ gv, long n, double* __restrict__ out, int* counter,
+                                                     double* __restrict__ part) {
+  const long nv = n >> 2;
+  double d0 = 0.0, d1 = 0.0;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+    f32x4_t v;
+    if (G16) {
+      const uint2 h = reinterpret_cast<const uint2*>(gv)[i];
+      v = unpack4(h.x, h.y);
+    } else {
+      v = reinterpret_cast<const f32x4_t*>(gv)[i];
+    }
+    sq_accumulate(v, d0, d1);
+  }
+  double dacc = d0 + d1;
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const float v = G16 ? bf2f(reinterpret_cast<const bf16_t*>(gv)[(nv << 2) + threadIdx.x]) : reinterpret_cast<const float*>(gv)[(nv << 2) + threadIdx.x];
+    dacc += (double)v * (double)v;
+  }
+  ordered_sum_f64<false>(dacc, out, counter, part);
+}
+
 // Micro-batch gradient accumulation (include/sdt.h sdt_grad_accumulate): acc (fp32) <- init / add / finish / scale of the step's
 // gradient g (bf16 or fp32, widened exactly), element-wise, in one HBM-bound sweep: init 6 B (bf16 g) per element, add and finish
 // 10 B, scale 8 B.  With NORM the sweep also adds sum acc_final^2 to *out exactly as sqnorm_kernel does over the finished buffer -
-// same grid (the caller passes sqnorm_kernel's), same float4 walk and d0 / d1 alternation, same per-workgroup partials and ordered
-// last-arriver sum - so the squared norm is bit-identical to sdt_sqnorm_accumulate run over acc afterwards.
+// same grid (the caller passes sqnorm_kernel's), same sq_accumulate walk, same ordered_sum_f64 - so the squared norm is
+// bit-identical to sdt_sqnorm_accumulate run over acc afterwards.
 template <bool G16, int MODE, bool NORM>
 __global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict__ acc, const void* __restrict__ gv, long n, float scale,
                                                               double* __restrict__ out, int* counter, double* __restrict__ part) {
   const long nv = n >> 2;
   double d0 = 0.0, d1 = 0.0;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
-    float4 v = {0.f, 0.f, 0.f, 0.f};
+    f32x4_t v = {0.f, 0.f, 0.f, 0.f};
     if (MODE != SDT_ACC_SCALE) {
       if (G16) {
         const uint2 h = reinterpret_cast<const uint2*>(gv)[i];
-        v.x = __uint_as_float(h.x << 16); v.y = __uint_as_float(h.x & 0xffff0000u);
-        v.z = __uint_as_float(h.y << 16); v.w = __uint_as_float(h.y & 0xffff0000u);
+        v = unpack4(h.x, h.y);
       } else {
-        v = reinterpret_cast<const float4*>(gv)[i];
+        v = reinterpret_cast<const f32x4_t*>(gv)[i];
       }
     }
     if (MODE != SDT_ACC_INIT) {
-      const float4 a = reinterpret_cast<const float4*>(acc)[i];
+      const f32x4_t a = reinterpret_cast<const f32x4_t*>(acc)[i];
       if (MODE == SDT_ACC_SCALE) {
-        v.x = a.x * scale; v.y = a.y * scale; v.z = a.z * scale; v.w = a.w * scale;
+        v = a * scale;
       } else {
-        v.x = a.x + v.x; v.y = a.y + v.y; v.z = a.z + v.z; v.w = a.w + v.w;
-        if (MODE == SDT_ACC_FINISH) {
-          v.x = v.x * scale; v.y = v.y * scale; v.z = v.z * scale; v.w = v.w * scale;
-        }
+        v = a + v;
+        if (MODE == SDT_ACC_FINISH) v = v * scale;
       }
     }
-    reinterpret_cast<float4*>(acc)[i] = v;
-    if (NORM) {
-      d0 = fma((double)v.x, (double)v.x, d0);
-      d1 = fma((double)v.y, (double)v.y, d1);
-      d0 = fma((double)v.z, (double)v.z, d0);
-      d1 = fma((double)v.w, (double)v.w, d1);
-    }
+    reinterpret_cast<f32x4_t*>(acc)[i] = v;
+    if (NORM) sq_accumulate(v, d0, d1);
   }
   double dacc = d0 + d1;
   if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // the < 4 elements behind the last float4
@@ -146,30 +160,11 @@ __global__ void __launch_bounds__(256) grad_accumulate_kernel(float* __restrict_
     acc[j] = v;
     dacc += (double)v * (double)v;
   }
-  if (!NORM) return;
-  for (int o = 32; o > 0; o >>= 1) dacc += __shfl_xor(dacc, o, 64);
-  __shared__ double dsc[16];
-  __shared__ int s_last;
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) dsc[w] = dacc;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    double t = 0.0;
-    for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += dsc[i];
-    sdt_store_wt(part + blockIdx.x, t);
-  }
-  if (!sdt_arrive_last<true>(counter, (int)gridDim.x, &s_last)) return;
-  double t = 0.0;
-  for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t += sdt_load_wt(part + i);
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) dsc[w] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) *out += (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]);
+  if (NORM) ordered_sum_f64<false>(dacc, out, counter, part);
 }
 
-// *out += sum of n doubles, added in a fixed order (contiguous chunk per workgroup, strided over the threads, the sqnorm_kernel's
-// tree): the squared-norm partials the weight-gradient kernels wrote to their slots (include/sdt.h sdt_gemm_tn_wgrad sq_slots).
+// *out += sum of n doubles, added in a fixed order (contiguous chunk per workgroup, strided over the threads, then ordered_sum_f64):
+// the squared-norm partials the weight-gradient kernels wrote to their slots (include/sdt.h sdt_gemm_tn_wgrad sq_slots).
 __global__ void __launch_bounds__(256) sum_f64_kernel(const double* __restrict__ x, long n, double* __restrict__ out, int* counter,
                                                       double* __restrict__ part) {
   const long per = (n + gridDim.x - 1) / gridDim.x;
@@ -181,154 +176,218 @@ __global__ void __launch_bounds__(256) sum_f64_kernel(const double* __restrict__
     d1 += x[i + 256];
   }
   if (i < hi) d0 += x[i];
-  double dacc = d0 + d1;
-  for (int o = 32; o > 0; o >>= 1) dacc += __shfl_xor(dacc, o, 64);
-  __shared__ double dsc[16];
-  __shared__ int s_last;
-  const int w = threadIdx.x >> 6;
-  if ((threadIdx.x & 63) == 0) dsc[w] = dacc;
-  __syncthreads();
-  if (threadIdx.x == 0) sdt_store_wt(part + blockIdx.x, (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]));
-  if (!sdt_arrive_last<true>(counter, (int)gridDim.x, &s_last)) return;
-  double t = 0.0;
-  for (int j = threadIdx.x; j < (int)gridDim.x; j += 256) t += sdt_load_wt(part + j);
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) dsc[w] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) *out += (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]);
+  ordered_sum_f64<true>(d0 + d1, out, counter, part);
 }
 
+// ------------------------------------------------------------------------------------------------------- the sweeps
 // clip factor semantics of optax.clip_by_global_norm: g if norm < max else (g / norm) * max
-__device__ __forceinline__ float clip_grad(float g, float gnorm, float max_norm, bool do_clip) {
-  return do_clip ? (g / gnorm) * max_norm : g;
+struct Clip {
+  float gnorm, max_norm;
+  bool on;
+  __device__ __forceinline__ float operator()(float g) const { return on ? (g / gnorm) * max_norm : g; }
+};
+__device__ __forceinline__ Clip clip_prologue(const double* __restrict__ sqnorm, float max_norm) {  // sqnorm null: no clipping
+  Clip c = {0.f, max_norm, false};
+  if (sqnorm) {
+    c.gnorm = (float)sqrt(*sqnorm);
+    c.on = !(c.gnorm < max_norm);
+  }
+  return c;
 }
 
-// LPB lanes cooperate on one quantisation block of BS = 4*LPB elements; each lane owns a float4.
+// Update rules.  step() takes the clipped gradient gc and the NS decoded state values, writes the new state values and returns the
+// update direction u; the sweeps around it apply p <- p + neg_lr * (u + wd * p).  Every operation rounds separately, in this order.
+struct LionRule {  // lion_quant.py:133-154; one state stream, the momentum, coded with the reference's offset
+  static constexpr int NS = 1;
+  static constexpr bool OFFSET = true;
+  float c1, c1m, c2, c2m;
+  __device__ __forceinline__ float step(float gc, const float* st, float* ns) const {
+    const float cc = c1m * gc + c1 * st[0];  // lion_quant.py:141-143
+    ns[0] = c2m * gc + c2 * st[0];           // lion_quant.py:105-107
+    return (cc > 0.f) ? 1.f : ((cc < 0.f) ? -1.f : 0.f);
+  }
+};
+// Second optimizer (include/sdt.h "AdamW"): decoupled-decay Adam with bias correction (division and square root correctly rounded).
+// Two state streams, m and the second moment.  ROOT: the second stream holds s = sqrt(v) (the 8-bit sweep, whose codec resolves the
+// root far better than v itself); without it the stream holds v (the fp32 sweep).  k1 = 1 / (1 - b1^t), k2 = 1 / sqrt(1 - b2^t).
+template <bool ROOT>
+struct AdamwRule {
+  static constexpr int NS = 2;
+  static constexpr bool OFFSET = false;
+  float c1, c1m, c2, c2m, eps, k1, k2;
+  __device__ __forceinline__ float step(float gc, const float* st, float* ns) const {
+    ns[0] = c1 * st[0] + c1m * gc;
+    const float vn = c2 * (ROOT ? st[1] * st[1] : st[1]) + c2m * (gc * gc);
+    const float sn = sqrtf(vn);
+    ns[1] = ROOT ? sn : vn;
+    return (ns[0] * k1) / (sn * k2 + eps);
+  }
+};
+
+__device__ __forceinline__ float decay_apply(float p, float u, float wd, float neg_lr) {
+  if (wd != 0.f) u = u + wd * p;  // add_decayed_weights
+  return p + neg_lr * u;          // _scale_by_learning_rate, apply_updates
+}
+// Scheduled sweeps: neg_lr, ema_r and ema_rm come from the device block `cur` that a select kernel wrote for this step; with
+// cur == nullptr the by-value arguments stand.
+__device__ __forceinline__ void scheduled_scalars(const float* __restrict__ cur, float& neg_lr, float& ema_r, float& ema_rm) {
+  if (cur) {
+    neg_lr = cur[0];
+    ema_r = cur[1];
+    ema_rm = cur[2];
+  }
+}
+
+// The 8-bit sweep.  LPB lanes cooperate on one quantisation block of BS = 4*LPB elements; each lane owns a float4.  Rule::NS code
+// streams and as many scale streams; each inverse scale is written once by its block's first lane.
 #define LION_SLICES 4
-// SCHED: neg_lr, ema_r and ema_rm come from the device block `cur` that opt_schedule_select_kernel wrote for this step (the by-value
-// arguments are ignored); the instantiations without it are the by-value sweeps.
-template <int LPB, bool G16, bool SCHED>
+template <class Rule, int LPB, bool G16>
+__device__ __forceinline__ void sweep8_body(const Rule rule, float* p, const void* g, int8_t* const (&codes)[Rule::NS],
+                                            float* const (&inv_scale)[Rule::NS], float* ema, bf16_t* w_bf16, long n4,
+                                            const double* sqnorm, const float* thr, float max_norm, float neg_lr, float wd, float ema_r,
+                                            float ema_rm) {
+  constexpr int NS = Rule::NS;
+  __shared__ float deq_tab[256];
+  __shared__ float thr_tab[132];
+  codec_load_tables<Rule::OFFSET>(deq_tab, thr_tab, thr);
+  const Clip clip = clip_prologue(sqnorm, max_norm);
+  // n4 is a multiple of LPB and consecutive lanes hold consecutive float4s, so the LPB lanes of a block stay together.
+  // A workgroup sweeps LION_SLICES consecutive slices of 256 float4s and the grid covers the buffer once: the resident
+  // workgroups then work on ONE contiguous window of each of the streams (a capped grid striding over the whole buffers
+  // ran the sweep at 4.1 instead of 5.9 TB/s), and every byte is touched once per step, so all of it moves non-temporally.
+  typedef unsigned u2v __attribute__((ext_vector_type(2)));
+  const long i_end = min(n4, ((long)blockIdx.x + 1) * (LION_SLICES * 256));
+  for (long i = (long)blockIdx.x * (LION_SLICES * 256) + threadIdx.x; i < i_end; i += 256) {
+    f32x4_t gv;
+    if (G16) {  // bf16 gradient (8 bytes per float4 of parameters), widened exactly: what optax sees of a bf16 cotangent
+      const u2v h = __builtin_nontemporal_load(&reinterpret_cast<const u2v*>(g)[i]);
+      gv = unpack4(h.x, h.y);
+    } else {
+      gv = __builtin_nontemporal_load(&reinterpret_cast<const f32x4_t*>(g)[i]);
+    }
+    f32x4_t pv = __builtin_nontemporal_load(&reinterpret_cast<const f32x4_t*>(p)[i]);
+    const long blk = i / LPB;
+    unsigned cw[NS], ncw[NS];
+    float inv[NS], ninv[NS], amax[NS], sn[NS][4];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) cw[k] = __builtin_nontemporal_load(&reinterpret_cast<const unsigned*>(codes[k])[i]);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      inv[k] = inv_scale[k][blk];
+      amax[k] = 0.f;
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float st[NS], ns[NS];
+#pragma unroll
+      for (int k = 0; k < NS; ++k) st[k] = deq_tab[(int)(int8_t)((cw[k] >> (8 * j)) & 0xff) + 128] / inv[k];  // lion_quant.py:88-91
+      const float u = rule.step(clip(gv[j]), st, ns);
+#pragma unroll
+      for (int k = 0; k < NS; ++k) {
+        sn[k][j] = ns[k];
+        amax[k] = fmaxf(amax[k], fabsf(ns[k]));
+      }
+      pv[j] = decay_apply(pv[j], u, wd, neg_lr);
+    }
+#pragma unroll
+    for (int o = 1; o < LPB; o <<= 1) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k) amax[k] = fmaxf(amax[k], __shfl_xor(amax[k], o, 64));
+    }
+#pragma unroll
+    for (int k = 0; k < NS; ++k) {
+      ninv[k] = 1.0f / ((amax[k] <= 0.f) ? 1.0f : amax[k]);  // lion_quant.py:72-76
+      ncw[k] = 0;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) ncw[k] |= ((unsigned)(codec_quant<Rule::OFFSET>(sn[k][j] * ninv[k], thr_tab) & 0xff)) << (8 * j);
+    }
+    // stores apart from the quantisation: a store the compiler sinks into the codec's branches comes out without its non-temporal hint
+#pragma unroll
+    for (int k = 0; k < NS; ++k) __builtin_nontemporal_store(ncw[k], &reinterpret_cast<unsigned*>(codes[k])[i]);
+    if ((i % LPB) == 0) {
+#pragma unroll
+      for (int k = 0; k < NS; ++k) inv_scale[k][blk] = ninv[k];
+    }
+    __builtin_nontemporal_store(pv, &reinterpret_cast<f32x4_t*>(p)[i]);
+    if (ema) {
+      const f32x4_t ev = __builtin_nontemporal_load(&reinterpret_cast<const f32x4_t*>(ema)[i]);
+      __builtin_nontemporal_store(ema_r * ev + ema_rm * pv, &reinterpret_cast<f32x4_t*>(ema)[i]);
+    }
+    if (w_bf16) {
+      const u2v o = {pack2bf(pv.x, pv.y), pack2bf(pv.z, pv.w)};
+      __builtin_nontemporal_store(o, &reinterpret_cast<u2v*>(w_bf16)[i]);
+    }
+  }
+}
+
+// The fp32-state sweep: a contiguous 1024-element slice per workgroup (see sweep8_body), Rule::NS state buffers.
+template <class Rule>
+__device__ __forceinline__ void sweep32_body(const Rule rule, float* p, const float* g, float* const (&state)[Rule::NS], float* ema,
+                                             bf16_t* w_bf16, long n, const double* sqnorm, float max_norm, float neg_lr, float wd,
+                                             float ema_r, float ema_rm) {
+  constexpr int NS = Rule::NS;
+  const Clip clip = clip_prologue(sqnorm, max_norm);
+  const long i_end = min(n, ((long)blockIdx.x + 1) * 1024);
+  for (long i = (long)blockIdx.x * 1024 + threadIdx.x; i < i_end; i += 256) {
+    float st[NS], ns[NS];
+#pragma unroll
+    for (int k = 0; k < NS; ++k) st[k] = state[k][i];
+    const float u = rule.step(clip(g[i]), st, ns);
+#pragma unroll
+    for (int k = 0; k < NS; ++k) state[k][i] = ns[k];
+    const float pv = decay_apply(p[i], u, wd, neg_lr);
+    p[i] = pv;
+    if (ema) ema[i] = ema_r * ema[i] + ema_rm * pv;
+    if (w_bf16) w_bf16[i] = f2bf(pv);
+  }
+}
+
+template <int LPB, bool G16>
 __global__ void __launch_bounds__(256) lion8_kernel(float* __restrict__ p, const void* __restrict__ g,
                                                     int8_t* __restrict__ codes, float* __restrict__ inv_scale,
                                                     float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n4,
                                                     const double* __restrict__ sqnorm, const float* __restrict__ thr,
                                                     float max_norm, float neg_lr, float wd, float c1, float c1m, float c2,
                                                     float c2m, float ema_r, float ema_rm, const float* __restrict__ cur) {
-  __shared__ float deq_tab[256];
-  __shared__ float thr_tab[132];
-  if (SCHED) {
-    neg_lr = cur[0];
-    ema_r = cur[1];
-    ema_rm = cur[2];
-  }
-  lion_load_tables(deq_tab, thr_tab, thr);
-  float gnorm = 0.f;
-  bool do_clip = false;
-  if (sqnorm) {
-    gnorm = (float)sqrt(*sqnorm);
-    do_clip = !(gnorm < max_norm);
-  }
-  // n4 is a multiple of LPB and consecutive lanes hold consecutive float4s, so the LPB lanes of a block stay together.
-  // A workgroup sweeps LION_SLICES consecutive slices of 256 float4s and the grid covers the buffer once: the resident
-  // workgroups then work on ONE contiguous window of each of the seven streams (a capped grid striding over the whole buffers
-  // ran the sweep at 4.1 instead of 5.9 TB/s), and every byte is touched once per step, so all of it moves non-temporally.
-  typedef float f4v __attribute__((ext_vector_type(4)));
-  typedef unsigned u2v __attribute__((ext_vector_type(2)));
-  const long i_end = min(n4, ((long)blockIdx.x + 1) * (LION_SLICES * 256));
-  for (long i = (long)blockIdx.x * (LION_SLICES * 256) + threadIdx.x; i < i_end; i += 256) {
-    f4v gv;
-    if (G16) {  // bf16 gradient (8 bytes per float4 of parameters), widened exactly: what optax sees of a bf16 cotangent
-      const u2v h = __builtin_nontemporal_load(&reinterpret_cast<const u2v*>(g)[i]);
-      gv.x = __uint_as_float(h.x << 16); gv.y = __uint_as_float(h.x & 0xffff0000u);
-      gv.z = __uint_as_float(h.y << 16); gv.w = __uint_as_float(h.y & 0xffff0000u);
-    } else {
-      gv = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(g)[i]);
-    }
-    const f4v pv = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(p)[i]);
-    const unsigned cw = __builtin_nontemporal_load(&reinterpret_cast<const unsigned*>(codes)[i]);
-    const long blk = i / LPB;
-    const float inv = inv_scale[blk];
-    float gg[4] = {gv.x, gv.y, gv.z, gv.w};
-    float pp[4] = {pv.x, pv.y, pv.z, pv.w};
-    float mn[4];
-    float amax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int c = (int)(int8_t)((cw >> (8 * j)) & 0xff);
-      float mf = deq_tab[c + 128] / inv;                    // lion_quant.py:88-91
-      float gc = clip_grad(gg[j], gnorm, max_norm, do_clip);
-      float cc = c1m * gc + c1 * mf;                        // lion_quant.py:141-143
-      float u = (cc > 0.f) ? 1.f : ((cc < 0.f) ? -1.f : 0.f);
-      mn[j] = c2m * gc + c2 * mf;                           // lion_quant.py:105-107
-      amax = fmaxf(amax, fabsf(mn[j]));
-      if (wd != 0.f) u = u + wd * pp[j];                    // add_decayed_weights
-      u = neg_lr * u;                                       // _scale_by_learning_rate
-      pp[j] = pp[j] + u;                                    // apply_updates
-    }
-#pragma unroll
-    for (int o = 1; o < LPB; o <<= 1) amax = fmaxf(amax, __shfl_xor(amax, o, 64));
-    const float ninv = 1.0f / ((amax <= 0.f) ? 1.0f : amax);  // lion_quant.py:72-76
-    unsigned ncw = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      int q = lion_quant_tab(mn[j] * ninv, thr_tab);
-      ncw |= ((unsigned)(q & 0xff)) << (8 * j);
-    }
-    __builtin_nontemporal_store(ncw, &reinterpret_cast<unsigned*>(codes)[i]);
-    if ((i % LPB) == 0) inv_scale[blk] = ninv;
-    {
-      const f4v o = {pp[0], pp[1], pp[2], pp[3]};
-      __builtin_nontemporal_store(o, &reinterpret_cast<f4v*>(p)[i]);
-    }
-    if (ema) {
-      f4v ev = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(ema)[i]);
-      ev.x = ema_r * ev.x + ema_rm * pp[0];
-      ev.y = ema_r * ev.y + ema_rm * pp[1];
-      ev.z = ema_r * ev.z + ema_rm * pp[2];
-      ev.w = ema_r * ev.w + ema_rm * pp[3];
-      __builtin_nontemporal_store(ev, &reinterpret_cast<f4v*>(ema)[i]);
-    }
-    if (w_bf16) {
-      const u2v o = {pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
-      __builtin_nontemporal_store(o, &reinterpret_cast<u2v*>(w_bf16)[i]);
-    }
-  }
+  scheduled_scalars(cur, neg_lr, ema_r, ema_rm);
+  int8_t* const cs[1] = {codes};
+  float* const is[1] = {inv_scale};
+  sweep8_body<LionRule, LPB, G16>(LionRule{c1, c1m, c2, c2m}, p, g, cs, is, ema, w_bf16, n4, sqnorm, thr, max_norm, neg_lr, wd, ema_r,
+                                  ema_rm);
 }
 
-template <bool SCHED>  // as lion8_kernel
 __global__ void __launch_bounds__(256) lion32_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ mom, float* __restrict__ ema,
                                                      bf16_t* __restrict__ w_bf16, long n,
                                                      const double* __restrict__ sqnorm, float max_norm, float neg_lr,
                                                      float wd, float c1, float c1m, float c2, float c2m, float ema_r,
                                                      float ema_rm, const float* __restrict__ cur) {
-  if (SCHED) {
-    neg_lr = cur[0];
-    ema_r = cur[1];
-    ema_rm = cur[2];
-  }
-  float gnorm = 0.f;
-  bool do_clip = false;
-  if (sqnorm) {
-    gnorm = (float)sqrt(*sqnorm);
-    do_clip = !(gnorm < max_norm);
-  }
-  const long i_end = min(n, ((long)blockIdx.x + 1) * 1024);  // a contiguous 1024-element slice per workgroup (see lion8_kernel)
-  for (long i = (long)blockIdx.x * 1024 + threadIdx.x; i < i_end; i += 256) {
-    float gc = clip_grad(g[i], gnorm, max_norm, do_clip);
-    float mf = mom[i];
-    float pv = p[i];
-    float cc = c1m * gc + c1 * mf;
-    float u = (cc > 0.f) ? 1.f : ((cc < 0.f) ? -1.f : 0.f);
-    mom[i] = c2m * gc + c2 * mf;
-    if (wd != 0.f) u = u + wd * pv;
-    u = neg_lr * u;
-    pv = pv + u;
-    p[i] = pv;
-    if (ema) ema[i] = ema_r * ema[i] + ema_rm * pv;
-    if (w_bf16) w_bf16[i] = f2bf(pv);
-  }
+  scheduled_scalars(cur, neg_lr, ema_r, ema_rm);
+  float* const st[1] = {mom};
+  sweep32_body(LionRule{c1, c1m, c2, c2m}, p, g, st, ema, w_bf16, n, sqnorm, max_norm, neg_lr, wd, ema_r, ema_rm);
+}
+
+// cur = {neg_lr, ema_r, ema_rm, 0, k1, k2, 0, 0}, written by adamw_select_kernel for this step (never null here)
+template <int LPB, bool G16>
+__global__ void __launch_bounds__(256) adamw8_kernel(float* __restrict__ p, const void* __restrict__ g, int8_t* __restrict__ m_codes,
+                                                     float* __restrict__ m_inv, int8_t* __restrict__ s_codes, float* __restrict__ s_inv,
+                                                     float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n4,
+                                                     const double* __restrict__ sqnorm, const float* __restrict__ thr, float max_norm,
+                                                     float wd, float c1, float c1m, float c2, float c2m, float eps,
+                                                     const float* __restrict__ cur) {
+  int8_t* const cs[2] = {m_codes, s_codes};
+  float* const is[2] = {m_inv, s_inv};
+  sweep8_body<AdamwRule<true>, LPB, G16>(AdamwRule<true>{c1, c1m, c2, c2m, eps, cur[4], cur[5]}, p, g, cs, is, ema, w_bf16, n4, sqnorm,
+                                         thr, max_norm, cur[0], wd, cur[1], cur[2]);
+}
+
+__global__ void __launch_bounds__(256) adamw32_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                                      float* __restrict__ v, float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n,
+                                                      const double* __restrict__ sqnorm, float max_norm, float wd, float c1, float c1m,
+                                                      float c2, float c2m, float eps, const float* __restrict__ cur) {
+  float* const st[2] = {m, v};
+  sweep32_body(AdamwRule<false>{c1, c1m, c2, c2m, eps, cur[4], cur[5]}, p, g, st, ema, w_bf16, n, sqnorm, max_norm, cur[0], wd, cur[1],
+               cur[2]);
 }
 
 __global__ void __launch_bounds__(256) lion8_quantize_kernel(const float* __restrict__ x, int8_t* __restrict__ codes,
@@ -336,13 +395,13 @@ __global__ void __launch_bounds__(256) lion8_quantize_kernel(const float* __rest
                                                              const float* __restrict__ thr) {
   __shared__ float deq_tab[256];
   __shared__ float thr_tab[132];
-  lion_load_tables(deq_tab, thr_tab, thr);
+  codec_load_tables<true>(deq_tab, thr_tab, thr);
   for (long b = (long)blockIdx.x * blockDim.x + threadIdx.x; b < nblocks; b += (long)gridDim.x * blockDim.x) {
     const float* xb = x + b * bs;
     float amax = 0.f;
     for (int j = 0; j < bs; ++j) amax = fmaxf(amax, fabsf(xb[j]));
     float inv = 1.0f / ((amax <= 0.f) ? 1.0f : amax);
-    for (int j = 0; j < bs; ++j) codes[b * bs + j] = (int8_t)lion_quant_tab(xb[j] * inv, thr_tab);
+    for (int j = 0; j < bs; ++j) codes[b * bs + j] = (int8_t)codec_quant<true>(xb[j] * inv, thr_tab);
     inv_scale[b] = inv;
   }
 }
@@ -351,7 +410,7 @@ __global__ void __launch_bounds__(256) lion8_dequantize_kernel(const int8_t* __r
                                                                const float* __restrict__ inv_scale,
                                                                float* __restrict__ x, long n, int bs) {
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    x[i] = lion_deq((int)codes[i]) / inv_scale[i / bs];
+    x[i] = codec_deq<true>((int)codes[i]) / inv_scale[i / bs];
 }
 
 // Per-step optimizer scalars (include/sdt.h sdt_opt_schedule_select): one lane reads the store's step counter t, copies entry
@@ -369,31 +428,6 @@ __global__ void __launch_bounds__(64) opt_schedule_select_kernel(int64_t* __rest
   cur[2] = ema_tab[2 * j + 1];
   cur[3] = 0.f;
   *step = t + 1;
-}
-
-// ---------------------------------------------------------------------------------------------------------------- AdamW
-// Second optimizer (include/sdt.h "AdamW"): decoupled-decay Adam with bias correction, every operation a separately rounded float32
-// one (division and square root correctly rounded).  The 8-bit sweep keeps the first moment m and the ROOT s = sqrt(v) of the second
-// one in the block codec WITHOUT the reference's offset: code = sign(x) * c(|x|) with the same threshold table (a function of the
-// magnitude alone), deq = (code / 127)^5, so zero <-> code 0 and a parameter whose gradient is exactly zero moves by decay alone.
-__device__ __forceinline__ float adamw_deq(int code) {
-  float t = (float)code / 127.0f;
-  float t2 = t * t;
-  float t4 = t2 * t2;
-  return t4 * t;
-}
-__device__ __forceinline__ int adamw_quant_tab(float x, const float* __restrict__ thr) {  // as lion_quant_tab, a = |x|
-  const float a = fabsf(x);
-  const float q = __builtin_amdgcn_exp2f(0.2f * __builtin_amdgcn_logf(a)) * 127.0f;
-  const float r = rintf(q);
-  int c = (int)fminf(fmaxf(r, 0.f), 127.f);
-  if (fabsf(q - r) > 0.5f - 2.5e-4f) c += (a >= thr[c + 1] ? 1 : 0) - (a < thr[c] ? 1 : 0);
-  return x < 0.f ? -c : c;
-}
-__device__ __forceinline__ void adamw_load_tables(float* deq_tab, float* thr_tab, const float* __restrict__ thr) {
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) deq_tab[i] = adamw_deq(i - 128);
-  for (int i = threadIdx.x; i < 129; i += blockDim.x) thr_tab[i] = i < 128 ? thr[i] : __builtin_inff();
-  __syncthreads();
 }
 
 // Per-step scalars of an AdamW store (include/sdt.h sdt_adamw_select): one lane.  t = *step; the running products P1 = b1^(t+1),
@@ -427,155 +461,65 @@ __global__ void __launch_bounds__(64) adamw_select_kernel(int64_t* __restrict__ 
   *step = t + 1;
 }
 
-// lion8_kernel's skeleton (LPB lanes per block, one contiguous window of LION_SLICES x 256 float4s per workgroup, non-temporal 16-byte
-// traffic, tables in LDS, each inverse scale written once by its block's first lane) with two code streams and two scale streams.
-template <int LPB, bool G16>
-__global__ void __launch_bounds__(256) adamw8_kernel(float* __restrict__ p, const void* __restrict__ g, int8_t* __restrict__ m_codes,
-                                                     float* __restrict__ m_inv, int8_t* __restrict__ s_codes, float* __restrict__ s_inv,
-                                                     float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n4,
-                                                     const double* __restrict__ sqnorm, const float* __restrict__ thr, float max_norm,
-                                                     float wd, float c1, float c1m, float c2, float c2m, float eps,
-                                                     const float* __restrict__ cur) {
-  __shared__ float deq_tab[256];
-  __shared__ float thr_tab[132];
-  const float neg_lr = cur[0], ema_r = cur[1], ema_rm = cur[2], k1 = cur[4], k2 = cur[5];
-  adamw_load_tables(deq_tab, thr_tab, thr);
-  float gnorm = 0.f;
-  bool do_clip = false;
-  if (sqnorm) {
-    gnorm = (float)sqrt(*sqnorm);
-    do_clip = !(gnorm < max_norm);
-  }
-  typedef float f4v __attribute__((ext_vector_type(4)));
-  typedef unsigned u2v __attribute__((ext_vector_type(2)));
-  const long i_end = min(n4, ((long)blockIdx.x + 1) * (LION_SLICES * 256));
-  for (long i = (long)blockIdx.x * (LION_SLICES * 256) + threadIdx.x; i < i_end; i += 256) {
-    f4v gv;
-    if (G16) {
-      const u2v h = __builtin_nontemporal_load(&reinterpret_cast<const u2v*>(g)[i]);
-      gv.x = __uint_as_float(h.x << 16); gv.y = __uint_as_float(h.x & 0xffff0000u);
-      gv.z = __uint_as_float(h.y << 16); gv.w = __uint_as_float(h.y & 0xffff0000u);
-    } else {
-      gv = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(g)[i]);
-    }
-    const f4v pv = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(p)[i]);
-    const unsigned cwm = __builtin_nontemporal_load(&reinterpret_cast<const unsigned*>(m_codes)[i]);
-    const unsigned cws = __builtin_nontemporal_load(&reinterpret_cast<const unsigned*>(s_codes)[i]);
-    const long blk = i / LPB;
-    const float minv = m_inv[blk], sinv = s_inv[blk];
-    float gg[4] = {gv.x, gv.y, gv.z, gv.w};
-    float pp[4] = {pv.x, pv.y, pv.z, pv.w};
-    float mn[4], sn[4];
-    float mmax = 0.f, smax = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int cm = (int)(int8_t)((cwm >> (8 * j)) & 0xff);
-      const int cs = (int)(int8_t)((cws >> (8 * j)) & 0xff);
-      const float mf = deq_tab[cm + 128] / minv;
-      const float sf = deq_tab[cs + 128] / sinv;
-      const float vf = sf * sf;
-      const float gc = clip_grad(gg[j], gnorm, max_norm, do_clip);
-      mn[j] = c1 * mf + c1m * gc;
-      const float vn = c2 * vf + c2m * (gc * gc);
-      sn[j] = sqrtf(vn);
-      mmax = fmaxf(mmax, fabsf(mn[j]));
-      smax = fmaxf(smax, sn[j]);
-      float u = (mn[j] * k1) / (sn[j] * k2 + eps);
-      if (wd != 0.f) u = u + wd * pp[j];
-      pp[j] = pp[j] + neg_lr * u;
-    }
-#pragma unroll
-    for (int o = 1; o < LPB; o <<= 1) {
-      mmax = fmaxf(mmax, __shfl_xor(mmax, o, 64));
-      smax = fmaxf(smax, __shfl_xor(smax, o, 64));
-    }
-    const float nminv = 1.0f / ((mmax <= 0.f) ? 1.0f : mmax);
-    const float nsinv = 1.0f / ((smax <= 0.f) ? 1.0f : smax);
-    unsigned ncm = 0, ncs = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      ncm |= ((unsigned)(adamw_quant_tab(mn[j] * nminv, thr_tab) & 0xff)) << (8 * j);
-      ncs |= ((unsigned)(adamw_quant_tab(sn[j] * nsinv, thr_tab) & 0xff)) << (8 * j);
-    }
-    __builtin_nontemporal_store(ncm, &reinterpret_cast<unsigned*>(m_codes)[i]);
-    __builtin_nontemporal_store(ncs, &reinterpret_cast<unsigned*>(s_codes)[i]);
-    if ((i % LPB) == 0) {
-      m_inv[blk] = nminv;
-      s_inv[blk] = nsinv;
-    }
-    {
-      const f4v o = {pp[0], pp[1], pp[2], pp[3]};
-      __builtin_nontemporal_store(o, &reinterpret_cast<f4v*>(p)[i]);
-    }
-    if (ema) {
-      f4v ev = __builtin_nontemporal_load(&reinterpret_cast<const f4v*>(ema)[i]);
-      ev.x = ema_r * ev.x + ema_rm * pp[0];
-      ev.y = ema_r * ev.y + ema_rm * pp[1];
-      ev.z = ema_r * ev.z + ema_rm * pp[2];
-      ev.w = ema_r * ev.w + ema_rm * pp[3];
-      __builtin_nontemporal_store(ev, &reinterpret_cast<f4v*>(ema)[i]);
-    }
-    if (w_bf16) {
-      const u2v o = {pack2bf(pp[0], pp[1]), pack2bf(pp[2], pp[3])};
-      __builtin_nontemporal_store(o, &reinterpret_cast<u2v*>(w_bf16)[i]);
-    }
+// ----------------------------------------------------------------------------------------------------------- host side
+// The float scalars every sweep and select launch derives from the entry points' doubles.
+struct HostScalars {
+  float c1, c1m, c2, c2m, neg_lr, er, erm;
+};
+static HostScalars host_scalars(double b1, double b2, double lr = 0.0, double ema_rate = 0.0) {
+  return {(float)b1, (float)(1.0 - b1), (float)b2, (float)(1.0 - b2), (float)(-lr), (float)ema_rate, (float)(1.0 - ema_rate)};
+}
+
+// launch(LPB, G16), both as integral constants, for the 8-bit sweep of `block_size` elements per block
+template <class F>
+static void dispatch_sweep8(int block_size, int g_bf16, F&& launch) {
+  auto with_g = [&](auto lpb) {
+    if (g_bf16)
+      launch(lpb, std::true_type{});
+    else
+      launch(lpb, std::false_type{});
+  };
+  switch (block_size >> 2) {
+    case 1: with_g(std::integral_constant<int, 1>{}); break;
+    case 2: with_g(std::integral_constant<int, 2>{}); break;
+    case 4: with_g(std::integral_constant<int, 4>{}); break;
+    case 8: with_g(std::integral_constant<int, 8>{}); break;
+    case 16: with_g(std::integral_constant<int, 16>{}); break;
+    case 32: with_g(std::integral_constant<int, 32>{}); break;
+    default: with_g(std::integral_constant<int, 64>{}); break;
   }
 }
 
-__global__ void __launch_bounds__(256) adamw32_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
-                                                      float* __restrict__ v, float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n,
-                                                      const double* __restrict__ sqnorm, float max_norm, float wd, float c1, float c1m,
-                                                      float c2, float c2m, float eps, const float* __restrict__ cur) {
-  const float neg_lr = cur[0], ema_r = cur[1], ema_rm = cur[2], k1 = cur[4], k2 = cur[5];
-  float gnorm = 0.f;
-  bool do_clip = false;
-  if (sqnorm) {
-    gnorm = (float)sqrt(*sqnorm);
-    do_clip = !(gnorm < max_norm);
-  }
-  const long i_end = min(n, ((long)blockIdx.x + 1) * 1024);  // a contiguous 1024-element slice per workgroup (see lion8_kernel)
-  for (long i = (long)blockIdx.x * 1024 + threadIdx.x; i < i_end; i += 256) {
-    const float gc = clip_grad(g[i], gnorm, max_norm, do_clip);
-    float pv = p[i];
-    const float mn = c1 * m[i] + c1m * gc;
-    const float vn = c2 * v[i] + c2m * (gc * gc);
-    m[i] = mn;
-    v[i] = vn;
-    float u = (mn * k1) / (sqrtf(vn) * k2 + eps);
-    if (wd != 0.f) u = u + wd * pv;
-    pv = pv + neg_lr * u;
-    p[i] = pv;
-    if (ema) ema[i] = ema_r * ema[i] + ema_rm * pv;
-    if (w_bf16) w_bf16[i] = f2bf(pv);
-  }
+// The refusals of the three 8-bit sweeps, made before any HIP call.  adamw: the second code / scale stream and cur are required too.
+static int check_sweep8_args(const char* name, bool adamw, const float* p, const void* g, int g_bf16, const int8_t* codes,
+                             const float* inv_scale, const int8_t* codes2, const float* inv_scale2, const float* ema,
+                             const uint16_t* w_bf16, int64_t n, int block_size, const float* thresholds, const float* cur) {
+  SDT_CHECK_ARG(p && g && codes && inv_scale && thresholds && (!adamw || (codes2 && inv_scale2 && cur)), "%s: null pointer", name);
+  SDT_CHECK_ARG(n >= 0 && block_size >= 4 && block_size <= 256 && (block_size & (block_size - 1)) == 0,
+                "%s: block_size must be a power of two in [4,256] (got %d)", name, block_size);
+  SDT_CHECK_ARG(n % block_size == 0, "%s: n=%ld not a multiple of block_size=%d%s", name, (long)n, block_size,
+                adamw ? "" : " (lion_quant.py:70 reshape)");
+  SDT_CHECK_ARG((((uintptr_t)p | (uintptr_t)ema | (uintptr_t)cur) & 15) == 0 && ((uintptr_t)g & (g_bf16 ? 7 : 15)) == 0 &&
+                    (((uintptr_t)codes | (uintptr_t)codes2) & 3) == 0 && ((uintptr_t)w_bf16 & 7) == 0,
+                "%s: misaligned buffer", name);
+  return SDT_OK;
 }
 
-template <bool SCHED>
-static void launch_lion8(int lpb, int g_bf16, dim3 grid, hipStream_t stream, float* p, const void* g, int8_t* codes, float* inv_scale,
-                         float* ema, uint16_t* w_bf16, long n4, const double* sqnorm, const float* thresholds, float max_norm,
-                         float neg_lr, float wd, float c1, float c1m, float c2, float c2m, float er, float erm, const float* cur) {
-  const dim3 block(256);
-#define LAUNCH_L8B(L, H)                                                                                                     \
-  hipLaunchKernelGGL((lion8_kernel<L, H, SCHED>), grid, block, 0, stream, p, g, codes, inv_scale, ema, (bf16_t*)w_bf16, n4, \
-                     sqnorm, thresholds, max_norm, neg_lr, wd, c1, c1m, c2, c2m, er, erm, cur)
-#define LAUNCH_L8(L)      \
-  do {                    \
-    if (g_bf16)           \
-      LAUNCH_L8B(L, true); \
-    else                  \
-      LAUNCH_L8B(L, false); \
-  } while (0)
-  switch (lpb) {
-    case 1: LAUNCH_L8(1); break;
-    case 2: LAUNCH_L8(2); break;
-    case 4: LAUNCH_L8(4); break;
-    case 8: LAUNCH_L8(8); break;
-    case 16: LAUNCH_L8(16); break;
-    case 32: LAUNCH_L8(32); break;
-    default: LAUNCH_L8(64); break;
-  }
-#undef LAUNCH_L8
-#undef LAUNCH_L8B
+static void launch_lion8(float* p, const void* g, int g_bf16, int8_t* codes, float* inv_scale, float* ema, uint16_t* w_bf16, int64_t n,
+                         int block_size, const double* sqnorm, const float* thresholds, double max_norm, double wd,
+                         const HostScalars& h, const float* cur, hipStream_t stream) {
+  const long n4 = n >> 2;
+  dispatch_sweep8(block_size, g_bf16, [&](auto lpb, auto g16) {
+    hipLaunchKernelGGL((lion8_kernel<decltype(lpb)::value, decltype(g16)::value>), dim3(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)),
+                       dim3(256), 0, stream, p, g, codes, inv_scale, ema, (bf16_t*)w_bf16, n4, sqnorm, thresholds, (float)max_norm,
+                       h.neg_lr, (float)wd, h.c1, h.c1m, h.c2, h.c2m, h.er, h.erm, cur);
+  });
+}
+
+static void launch_lion32(float* p, const float* g, float* mom, float* ema, uint16_t* w_bf16, int64_t n, const double* sqnorm,
+                          double max_norm, double wd, const HostScalars& h, const float* cur, hipStream_t stream) {
+  hipLaunchKernelGGL(lion32_kernel, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, mom, ema, (bf16_t*)w_bf16, (long)n,
+                     sqnorm, (float)max_norm, h.neg_lr, (float)wd, h.c1, h.c1m, h.c2, h.c2m, h.er, h.erm, cur);
 }
 
 extern "C" {
@@ -662,25 +606,15 @@ int sdt_sum_f64_accumulate(const double* x, int64_t n, double* out, void* worksp
   return SDT_OK;
 }
 
-#define LION8_CHECK_ARGS(NAME)                                                                                                   \
-  SDT_CHECK_ARG(p && g && codes && inv_scale && thresholds, NAME ": null pointer");                                              \
-  SDT_CHECK_ARG(n >= 0 && block_size >= 4 && block_size <= 256 && (block_size & (block_size - 1)) == 0,                         \
-                NAME ": block_size must be a power of two in [4,256] (got %d)", block_size);                                     \
-  SDT_CHECK_ARG(n % block_size == 0, NAME ": n=%ld not a multiple of block_size=%d (lion_quant.py:70 reshape)", (long)n, block_size); \
-  SDT_CHECK_ARG((((uintptr_t)p | (uintptr_t)ema) & 15) == 0 && ((uintptr_t)g & (g_bf16 ? 7 : 15)) == 0 && ((uintptr_t)codes & 3) == 0 && \
-                    ((uintptr_t)w_bf16 & 7) == 0,                                                                                \
-                NAME ": misaligned buffer")
-
 int sdt_lion8_step(float* p, const void* g, int g_bf16, int8_t* codes, float* inv_scale, float* ema, uint16_t* w_bf16, int64_t n,
                    int block_size, const double* sqnorm, const float* thresholds, double max_norm, double lr, double wd,
                    double b1, double b2, double ema_rate, hipStream_t stream) {
-  LION8_CHECK_ARGS("sdt_lion8_step");
+  if (int rc = check_sweep8_args("sdt_lion8_step", false, p, g, g_bf16, codes, inv_scale, nullptr, nullptr, ema, w_bf16, n, block_size,
+                                 thresholds, nullptr))
+    return rc;
   if (n == 0) return SDT_OK;
-  const long n4 = n >> 2;
-  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
-  const float er = (float)ema_rate, erm = (float)(1.0 - ema_rate);
-  launch_lion8<false>(block_size >> 2, g_bf16, dim3(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)), stream, p, g, codes, inv_scale, ema,
-                      w_bf16, n4, sqnorm, thresholds, (float)max_norm, (float)(-lr), (float)wd, c1, c1m, c2, c2m, er, erm, nullptr);
+  launch_lion8(p, g, g_bf16, codes, inv_scale, ema, w_bf16, n, block_size, sqnorm, thresholds, max_norm, wd,
+               host_scalars(b1, b2, lr, ema_rate), nullptr, stream);
   SDT_LAUNCH_CHECK("sdt_lion8_step");
   return SDT_OK;
 }
@@ -688,28 +622,23 @@ int sdt_lion8_step(float* p, const void* g, int g_bf16, int8_t* codes, float* in
 int sdt_lion8_step_scheduled(float* p, const void* g, int g_bf16, int8_t* codes, float* inv_scale, float* ema, uint16_t* w_bf16,
                              int64_t n, int block_size, const double* sqnorm, const float* thresholds, double max_norm, const float* cur,
                              double wd, double b1, double b2, hipStream_t stream) {
-  LION8_CHECK_ARGS("sdt_lion8_step_scheduled");
+  if (int rc = check_sweep8_args("sdt_lion8_step_scheduled", false, p, g, g_bf16, codes, inv_scale, nullptr, nullptr, ema, w_bf16, n,
+                                 block_size, thresholds, nullptr))
+    return rc;
   SDT_CHECK_ARG(cur && ((uintptr_t)cur & 15) == 0, "sdt_lion8_step_scheduled: cur must be a 16-byte aligned device block");
   if (n == 0) return SDT_OK;
-  const long n4 = n >> 2;
-  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
-  launch_lion8<true>(block_size >> 2, g_bf16, dim3(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)), stream, p, g, codes, inv_scale, ema,
-                     w_bf16, n4, sqnorm, thresholds, (float)max_norm, 0.f, (float)wd, c1, c1m, c2, c2m, 0.f, 0.f, cur);
+  launch_lion8(p, g, g_bf16, codes, inv_scale, ema, w_bf16, n, block_size, sqnorm, thresholds, max_norm, wd, host_scalars(b1, b2), cur,
+               stream);
   SDT_LAUNCH_CHECK("sdt_lion8_step_scheduled");
   return SDT_OK;
 }
-#undef LION8_CHECK_ARGS
 
 int sdt_lion32_step(float* p, const float* g, float* mom, float* ema, uint16_t* w_bf16, int64_t n,
                     const double* sqnorm, double max_norm, double lr, double wd, double b1, double b2, double ema_rate,
                     hipStream_t stream) {
   SDT_CHECK_ARG(p && g && mom && n >= 0, "sdt_lion32_step: null pointer or negative n");
   if (n == 0) return SDT_OK;
-  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
-  const float er = (float)ema_rate, erm = (float)(1.0 - ema_rate);
-  hipLaunchKernelGGL(lion32_kernel<false>, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, mom, ema,
-                     (bf16_t*)w_bf16, (long)n, sqnorm, (float)max_norm, (float)(-lr), (float)wd, c1, c1m, c2, c2m, er, erm,
-                     (const float*)nullptr);
+  launch_lion32(p, g, mom, ema, w_bf16, n, sqnorm, max_norm, wd, host_scalars(b1, b2, lr, ema_rate), nullptr, stream);
   SDT_LAUNCH_CHECK("sdt_lion32_step");
   return SDT_OK;
 }
@@ -719,9 +648,7 @@ int sdt_lion32_step_scheduled(float* p, const float* g, float* mom, float* ema, 
   SDT_CHECK_ARG(p && g && mom && n >= 0, "sdt_lion32_step_scheduled: null pointer or negative n");
   SDT_CHECK_ARG(cur && ((uintptr_t)cur & 15) == 0, "sdt_lion32_step_scheduled: cur must be a 16-byte aligned device block");
   if (n == 0) return SDT_OK;
-  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
-  hipLaunchKernelGGL(lion32_kernel<true>, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, mom, ema,
-                     (bf16_t*)w_bf16, (long)n, sqnorm, (float)max_norm, 0.f, (float)wd, c1, c1m, c2, c2m, 0.f, 0.f, cur);
+  launch_lion32(p, g, mom, ema, w_bf16, n, sqnorm, max_norm, wd, host_scalars(b1, b2), cur, stream);
   SDT_LAUNCH_CHECK("sdt_lion32_step_scheduled");
   return SDT_OK;
 }
@@ -747,8 +674,9 @@ int sdt_adamw_select(int64_t* step, double* prods, const float* lr_tab, int64_t 
   SDT_CHECK_ARG(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0, "sdt_adamw_select: b1 and b2 must lie in [0, 1) (got %g, %g)", b1, b2);
   SDT_CHECK_ARG((((uintptr_t)step | (uintptr_t)prods | (uintptr_t)ema_tab) & 7) == 0 && ((uintptr_t)cur & 15) == 0,
                 "sdt_adamw_select: misaligned step counter, products, table or block");
-  hipLaunchKernelGGL(adamw_select_kernel, dim3(1), dim3(64), 0, stream, step, prods, lr_tab, (long)n_lr, ema_tab, (long)n_ema,
-                     (float)(-lr), (float)ema_rate, (float)(1.0 - ema_rate), b1, b2, cur);
+  const HostScalars h = host_scalars(b1, b2, lr, ema_rate);
+  hipLaunchKernelGGL(adamw_select_kernel, dim3(1), dim3(64), 0, stream, step, prods, lr_tab, (long)n_lr, ema_tab, (long)n_ema, h.neg_lr,
+                     h.er, h.erm, b1, b2, cur);
   SDT_LAUNCH_CHECK("sdt_adamw_select");
   return SDT_OK;
 }
@@ -756,38 +684,17 @@ int sdt_adamw_select(int64_t* step, double* prods, const float* lr_tab, int64_t 
 int sdt_adamw8_step(float* p, const void* g, int g_bf16, int8_t* m_codes, float* m_inv_scale, int8_t* s_codes, float* s_inv_scale,
                     float* ema, uint16_t* w_bf16, int64_t n, int block_size, const double* sqnorm, const float* thresholds,
                     double max_norm, const float* cur, double wd, double b1, double b2, double eps, hipStream_t stream) {
-  SDT_CHECK_ARG(p && g && m_codes && m_inv_scale && s_codes && s_inv_scale && thresholds && cur, "sdt_adamw8_step: null pointer");
-  SDT_CHECK_ARG(n >= 0 && block_size >= 4 && block_size <= 256 && (block_size & (block_size - 1)) == 0,
-                "sdt_adamw8_step: block_size must be a power of two in [4,256] (got %d)", block_size);
-  SDT_CHECK_ARG(n % block_size == 0, "sdt_adamw8_step: n=%ld not a multiple of block_size=%d", (long)n, block_size);
-  SDT_CHECK_ARG((((uintptr_t)p | (uintptr_t)ema | (uintptr_t)cur) & 15) == 0 && ((uintptr_t)g & (g_bf16 ? 7 : 15)) == 0 &&
-                    (((uintptr_t)m_codes | (uintptr_t)s_codes) & 3) == 0 && ((uintptr_t)w_bf16 & 7) == 0,
-                "sdt_adamw8_step: misaligned buffer");
+  if (int rc = check_sweep8_args("sdt_adamw8_step", true, p, g, g_bf16, m_codes, m_inv_scale, s_codes, s_inv_scale, ema, w_bf16, n,
+                                 block_size, thresholds, cur))
+    return rc;
   if (n == 0) return SDT_OK;
   const long n4 = n >> 2;
-  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
-  const dim3 grid(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)), block(256);
-#define LAUNCH_A8B(L, H)                                                                                                          \
-  hipLaunchKernelGGL((adamw8_kernel<L, H>), grid, block, 0, stream, p, g, m_codes, m_inv_scale, s_codes, s_inv_scale, ema,       \
-                     (bf16_t*)w_bf16, n4, sqnorm, thresholds, (float)max_norm, (float)wd, c1, c1m, c2, c2m, (float)eps, cur)
-#define LAUNCH_A8(L)       \
-  do {                     \
-    if (g_bf16)            \
-      LAUNCH_A8B(L, true);  \
-    else                   \
-      LAUNCH_A8B(L, false); \
-  } while (0)
-  switch (block_size >> 2) {
-    case 1: LAUNCH_A8(1); break;
-    case 2: LAUNCH_A8(2); break;
-    case 4: LAUNCH_A8(4); break;
-    case 8: LAUNCH_A8(8); break;
-    case 16: LAUNCH_A8(16); break;
-    case 32: LAUNCH_A8(32); break;
-    default: LAUNCH_A8(64); break;
-  }
-#undef LAUNCH_A8
-#undef LAUNCH_A8B
+  const HostScalars h = host_scalars(b1, b2);
+  dispatch_sweep8(block_size, g_bf16, [&](auto lpb, auto g16) {
+    hipLaunchKernelGGL((adamw8_kernel<decltype(lpb)::value, decltype(g16)::value>), dim3(sdt_grid_1d(n4, 256 * LION_SLICES, 1 << 30)),
+                       dim3(256), 0, stream, p, g, m_codes, m_inv_scale, s_codes, s_inv_scale, ema, (bf16_t*)w_bf16, n4, sqnorm,
+                       thresholds, (float)max_norm, (float)wd, h.c1, h.c1m, h.c2, h.c2m, (float)eps, cur);
+  });
   SDT_LAUNCH_CHECK("sdt_adamw8_step");
   return SDT_OK;
 }
@@ -797,9 +704,9 @@ int sdt_adamw32_step(float* p, const float* g, float* m, float* v, float* ema, u
   SDT_CHECK_ARG(p && g && m && v && cur && n >= 0, "sdt_adamw32_step: null pointer or negative n");
   SDT_CHECK_ARG(((uintptr_t)cur & 15) == 0, "sdt_adamw32_step: cur must be a 16-byte aligned device block");
   if (n == 0) return SDT_OK;
-  const float c1 = (float)b1, c1m = (float)(1.0 - b1), c2 = (float)b2, c2m = (float)(1.0 - b2);
+  const HostScalars h = host_scalars(b1, b2);
   hipLaunchKernelGGL(adamw32_kernel, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)w_bf16, (long)n,
-                     sqnorm, (float)max_norm, (float)wd, c1, c1m, c2, c2m, (float)eps, cur);
+                     sqnorm, (float)max_norm, (float)wd, h.c1, h.c1m, h.c2, h.c2m, (float)eps, cur);
   SDT_LAUNCH_CHECK("sdt_adamw32_step");
   return SDT_OK;
 }

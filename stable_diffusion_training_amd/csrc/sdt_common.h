@@ -25,6 +25,11 @@ __device__ __forceinline__ unsigned pack2bf(float lo, float hi) {
   const sdt_f32x2_t f = {lo, hi};
   return __builtin_bit_cast(unsigned, __builtin_convertvector(f, sdt_bf16x2_t));
 }
+__device__ __forceinline__ f32x4_t unpack4(unsigned lo, unsigned hi) {  // four bf16 values in 8 bytes, widened exactly
+  const f32x4_t f = {__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16),
+                     __uint_as_float(hi & 0xffff0000u)};
+  return f;
+}
 __device__ __forceinline__ void unpack8(const uint4& v, float* f) {
   f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xffff0000u);
   f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xffff0000u);

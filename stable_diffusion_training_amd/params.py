@@ -633,6 +633,7 @@ class ParamStore:
         else:
             max_norm = 1.0
         ema_on = self.ema is not None and ema_rate
+        er = ema_rate if ema_on else 0.0
         sc = self._sched if self.schedule is not None else None
         if sc is not None:
             lrs, emas = self.schedule
@@ -654,55 +655,47 @@ class ParamStore:
             cur = self.adam_cur.data_ptr()
             tabs = (None, 0, None, 0) if sc is None else (sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(), sc["ema_tab"].data_ptr(),
                                                           sc["ema_tab"].numel() // 2)
-            _lib.call("sdt_adamw_select", self.adam_step.data_ptr(), self.adam_prod.data_ptr(), *tabs, lr, ema_rate if ema_on else 0.0,
-                      b1, b2, cur, s)
+            _lib.call("sdt_adamw_select", self.adam_step.data_ptr(), self.adam_prod.data_ptr(), *tabs, lr, er, b1, b2, cur, s)
+
+        def piece(a, quant):
+            """Pointers of the piece that starts at element a: master, gradient (+ whether it is bf16), EMA, bf16 mirror."""
+            g16 = quant and self.grad16 is not None and not from_acc
+            if from_acc:
+                gp = self.gacc.data_ptr() + 4 * a
+            elif g16:
+                gp = self.grad16.data_ptr() + 2 * a
+            else:
+                gp = self.grad.data_ptr() + 4 * (a - self.g32_base)  # g32_base is 0 when the fp32 buffer holds every gradient
+            return (self.master.data_ptr() + 4 * a, gp, int(g16), self.ema.data_ptr() + 4 * a if ema_on else None,
+                    self.w.data_ptr() + 2 * a)
+
         for (a, b, quant, decay) in pieces:
             n = b - a
             if n == 0:
                 continue
-            ema_ptr = self.ema.data_ptr() + 4 * a if ema_on else None
+            mp, gp, g16, ema_ptr, wp = piece(a, quant)
             wd_eff = wd if decay else 0.0
-            if adamw:
-                if quant:
-                    g16 = self.grad16 is not None and not from_acc
-                    if from_acc:
-                        gp = self.gacc.data_ptr() + 4 * a
-                    else:
-                        gp = self.grad16.data_ptr() + 2 * a if g16 else self.grad.data_ptr() + 4 * a
-                    blk = 4 * (a // self.block_size)
-                    _lib.call("sdt_adamw8_step", self.master.data_ptr() + 4 * a, gp, int(g16), self.codes.data_ptr() + a,
-                              self.inv_scale.data_ptr() + blk, self.codes2.data_ptr() + a, self.inv_scale2.data_ptr() + blk, ema_ptr,
-                              self.w.data_ptr() + 2 * a, n, self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, cur, wd_eff,
-                              b1, b2, eps, s)
-                else:
-                    gp = self.gacc.data_ptr() + 4 * a if from_acc else self.grad.data_ptr() + 4 * (a - self.g32_base)
-                    o = 4 * (a - self.quant_total)
-                    _lib.call("sdt_adamw32_step", self.master.data_ptr() + 4 * a, gp, self.mom.data_ptr() + o, self.mom2.data_ptr() + o,
-                              ema_ptr, self.w.data_ptr() + 2 * a, n, sq_ptr, max_norm, cur, wd_eff, b1, b2, eps, s)
+            blk = 4 * (a // self.block_size)  # the 8-bit streams: one code per element, one float scale per block
+            o = 4 * (a - self.quant_total)    # the fp32 state buffers start behind the quantised segments
+            thr = self.thresholds.data_ptr()
+            if adamw and quant:
+                _lib.call("sdt_adamw8_step", mp, gp, g16, self.codes.data_ptr() + a, self.inv_scale.data_ptr() + blk,
+                          self.codes2.data_ptr() + a, self.inv_scale2.data_ptr() + blk, ema_ptr, wp, n, self.block_size, sq_ptr, thr,
+                          max_norm, cur, wd_eff, b1, b2, eps, s)
+            elif adamw:
+                _lib.call("sdt_adamw32_step", mp, gp, self.mom.data_ptr() + o, self.mom2.data_ptr() + o, ema_ptr, wp, n, sq_ptr, max_norm,
+                          cur, wd_eff, b1, b2, eps, s)
+            elif quant and sc is not None:
+                _lib.call("sdt_lion8_step_scheduled", mp, gp, g16, self.codes.data_ptr() + a, self.inv_scale.data_ptr() + blk, ema_ptr, wp,
+                          n, self.block_size, sq_ptr, thr, max_norm, cur, wd_eff, b1, b2, s)
             elif quant:
-                g16 = self.grad16 is not None and not from_acc
-                if from_acc:
-                    gp = self.gacc.data_ptr() + 4 * a
-                else:
-                    gp = self.grad16.data_ptr() + 2 * a if g16 else self.grad.data_ptr() + 4 * a
-                if sc is not None:
-                    _lib.call("sdt_lion8_step_scheduled", self.master.data_ptr() + 4 * a, gp, int(g16), self.codes.data_ptr() + a,
-                              self.inv_scale.data_ptr() + 4 * (a // self.block_size), ema_ptr, self.w.data_ptr() + 2 * a, n,
-                              self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, cur, wd_eff, b1, b2, s)
-                else:
-                    _lib.call("sdt_lion8_step", self.master.data_ptr() + 4 * a, gp, int(g16), self.codes.data_ptr() + a,
-                              self.inv_scale.data_ptr() + 4 * (a // self.block_size), ema_ptr, self.w.data_ptr() + 2 * a, n, self.block_size, sq_ptr, self.thresholds.data_ptr(), max_norm, lr,
-                              wd_eff, b1, b2, ema_rate if ema_on else 0.0, s)
+                _lib.call("sdt_lion8_step", mp, gp, g16, self.codes.data_ptr() + a, self.inv_scale.data_ptr() + blk, ema_ptr, wp, n,
+                          self.block_size, sq_ptr, thr, max_norm, lr, wd_eff, b1, b2, er, s)
+            elif sc is not None:
+                _lib.call("sdt_lion32_step_scheduled", mp, gp, self.mom.data_ptr() + o, ema_ptr, wp, n, sq_ptr, max_norm, cur, wd_eff, b1,
+                          b2, s)
             else:
-                gp = self.gacc.data_ptr() + 4 * a if from_acc else self.grad.data_ptr() + 4 * (a - self.g32_base)
-                if sc is not None:
-                    _lib.call("sdt_lion32_step_scheduled", self.master.data_ptr() + 4 * a, gp,
-                              self.mom.data_ptr() + 4 * (a - self.quant_total), ema_ptr, self.w.data_ptr() + 2 * a, n, sq_ptr,
-                              max_norm, cur, wd_eff, b1, b2, s)
-                else:
-                    _lib.call("sdt_lion32_step", self.master.data_ptr() + 4 * a, gp,
-                              self.mom.data_ptr() + 4 * (a - self.quant_total), ema_ptr, self.w.data_ptr() + 2 * a, n, sq_ptr,
-                              max_norm, lr, wd_eff, b1, b2, ema_rate if ema_on else 0.0, s)
+                _lib.call("sdt_lion32_step", mp, gp, self.mom.data_ptr() + o, ema_ptr, wp, n, sq_ptr, max_norm, lr, wd_eff, b1, b2, er, s)
         self.count += 1
         self._written = None
         self._grad_is_acc = from_acc
