@@ -37,13 +37,24 @@ __device__ __attribute__((aligned(16))) unsigned int g_attn_zero16[4] = {0u, 0u,
 // MFMAs also deliver the softmax row sum (forward kernel, head dims with spare padding)
 __device__ __attribute__((aligned(16))) unsigned int g_attn_one16[4] = {0x3f80u, 0u, 0u, 0u};
 
+// LDS-DMA, asm-owned.  hipcc treats an in-flight global_load_lds as a pending LDS write and drains it (s_waitcnt vmcnt(0)) in front
+// of the first LDS read it can see behind it - in the dK/dV loop that is the top of the tile body, so every wave sat out the whole
+// flight of the NEXT tile's DMA before it touched the current one.  A DMA the compiler cannot see is ordered by hand instead:
+// dma_join() (vmcnt(0), then the barrier) before any read of the image it fills.  M0 carries the wave's LDS destination and is
+// restored; lds_wave_base must be wave-uniform.  (hipcc's own vmcnt(N) for its loads stays safe: the counter retires in order and
+// extra younger operations only make such a wait longer.)
+__device__ __forceinline__ unsigned lds_offset_of(const void* p) {
+  return (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)p;
+}
 __device__ __forceinline__ void glds16(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 16, 0, 0);
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_offset_of(lds_wave_base)) : "memory");
 }
 __device__ __forceinline__ void glds4(const void* gsrc, void* lds_wave_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)gsrc,
-                                   (__attribute__((address_space(3))) void*)lds_wave_base, 4, 0, 0);
+  unsigned keep;
+  asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dword %1, off\n\ts_mov_b32 m0, %0"
+               : "=&s"(keep) : "v"(gsrc), "s"(lds_offset_of(lds_wave_base)) : "memory");
 }
 
 __device__ __forceinline__ bf16x8_t cvt_frag(const float* p) {
@@ -72,7 +83,7 @@ template <int DPP>
 struct TileDma {
   static constexpr int IPW = Img<DPP>::IPW, CPR = Img<DPP>::CPR;
   int row[IPW];  // token row inside the tile
-  int col[IPW];  // first feature of the lane's chunk, -1 when it lies in the zero padding, -2 for the ones chunk
+  int col[IPW];  // first feature of the lane's chunk, -1 when it lies in the zero padding, -2 for the ones chunk (init's ones_chunk)
   __device__ __forceinline__ void init(int wave, int lane, int D, int ones_chunk = -1) {
 #pragma unroll
     for (int i = 0; i < IPW; ++i) {
@@ -83,32 +94,36 @@ struct TileDma {
       col[i] = (c * 8 < D) ? c * 8 : (c == ones_chunk ? -2 : -1);
     }
   }
-  // Tiles are issued in token order, KT apart: the lane's source pointers are kept and ADVANCED (one 64-bit add per piece per
-  // tile) instead of being rebuilt from (token, stride, column) with a 64-bit multiply-add each time - the attention loops are
-  // VALU-issue bound and the address arithmetic was a fifth of their vector instructions.
+  // Tiles are issued in token order, KT apart: the lane's source pointers are kept and ADVANCED instead of being rebuilt from
+  // (token, stride, column) every tile.  Which source a piece has - a real column, the zero page or the ones chunk - is known at
+  // bind(): a padded lane's pointer stands at its page and never moves, so a full tile (every tile but a tensor's ragged last one)
+  // is one DMA and one pointer add per piece, with no selects - the attention loops are VALU-issue bound and the per-tile source
+  // selection was a quarter of the forward's vector instructions.
   const bf16_t* ptr[IPW];
-  long step;
+  unsigned step;  // bytes per tile (KT rows); pointers at a page do not advance
   // src: the (batch, head) base of the tensor; tok0: first token of the first tile that will be issued
   __device__ __forceinline__ void bind(const bf16_t* src, long ld, int tok0) {
-    step = (long)KT * ld;
-#pragma unroll
-    for (int i = 0; i < IPW; ++i) ptr[i] = src + ((long)(tok0 + row[i]) * ld + (col[i] > 0 ? col[i] : 0));
-  }
-  // issues the tile the pointers stand at (its first token is tok_base: only the bounds test uses it) and advances them;
-  // img: wave-uniform image base
-  template <bool ONES = false>
-  __device__ __forceinline__ void issue(int tok_base, int ntok, unsigned char* img, int wave_u) {
-    const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_attn_zero16);
-    const bf16_t* one = reinterpret_cast<const bf16_t*>(g_attn_one16);
-    const bool full = tok_base + KT <= ntok;  // wave-uniform: only the last tile of a tensor tests tokens
 #pragma unroll
     for (int i = 0; i < IPW; ++i) {
-      const bool tok_ok = full || tok_base + row[i] < ntok;
-      const bool ok = col[i] >= 0 && tok_ok;
-      const bf16_t* pad = (ONES && col[i] == -2 && tok_ok) ? one : zero;
-      glds16(ok ? ptr[i] : pad, img + (wave_u * IPW + i) * 1024);
-      ptr[i] += step;
+      const bf16_t* page = reinterpret_cast<const bf16_t*>(col[i] == -2 ? g_attn_one16 : g_attn_zero16);
+      ptr[i] = col[i] >= 0 ? src + ((long)(tok0 + row[i]) * ld + col[i]) : page;
     }
+    step = (unsigned)(KT * ld * sizeof(bf16_t));
+  }
+  // issues the tile the pointers stand at (its first token is tok_base: only the ragged tile's bounds test uses it) and advances
+  // them; img: wave-uniform image base.  Rows past the tensor's end come from the zero page (the ones column included).
+  __device__ __forceinline__ void issue(int tok_base, int ntok, unsigned char* img, int wave_u) {
+    if (tok_base + KT <= ntok) {  // wave-uniform
+#pragma unroll
+      for (int i = 0; i < IPW; ++i) glds16(ptr[i], img + (wave_u * IPW + i) * 1024);
+    } else {
+      const bf16_t* zero = reinterpret_cast<const bf16_t*>(g_attn_zero16);
+#pragma unroll
+      for (int i = 0; i < IPW; ++i) glds16(tok_base + row[i] < ntok ? ptr[i] : zero, img + (wave_u * IPW + i) * 1024);
+    }
+#pragma unroll
+    for (int i = 0; i < IPW; ++i)
+      ptr[i] = reinterpret_cast<const bf16_t*>(reinterpret_cast<const unsigned char*>(ptr[i]) + (col[i] >= 0 ? step : 0u));
   }
 };
 
@@ -144,9 +159,14 @@ struct TrLane {
   }
 };
 
-// all of this wave's LDS-DMA has landed, then every wave's (the barrier); also closes the reads of the previous tile
+// all of this wave's LDS-DMA has landed, then every wave's (the barrier); also closes the reads of the previous tile.
+// The asm wait is the one that counts (the DMA is asm-owned).  The builtin behind it is for hipcc's own bookkeeping: it drops it
+// where it has no load of its own in flight, and otherwise learns here that its loads (the Q / K fragments fetched ahead of the loop,
+// key weights) have landed - without it, it waits for them with a vmcnt(0) of its own INSIDE the tile body, behind the issue of the
+// next tile's DMA, on every tile.
 __device__ __forceinline__ void dma_join() {
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0), nothing else
   __syncthreads();
 }
 
@@ -169,6 +189,22 @@ struct AttnParams {
   // whose last chunk is a clamped (overlapping) slice when the key count is not a multiple of the chunk: overlapped keys count twice
   const float* key_w;
 };
+
+// Runs the tile loop `tiles(masked, weighted, from, to)` over the tiles [from, to) of a tensor of n tokens (tile starts from + j * KT)
+// with the wave-uniform choice of the body made OUTSIDE the loop: key weights -> the masked, weighted body; always_mask (causal, or
+// a ragged block on the other axis) -> the masked body; otherwise the full tiles run the plain body and only the ragged last tile
+// the masked one.  Choosing per tile inside one loop made the accumulators phis of three bodies, which hipcc resolved with a second
+// copy of them (32 - 64 registers) and a register move per accumulator and tile.
+template <typename F>
+__device__ __forceinline__ void attn_tile_loops(F& tiles, bool weighted, bool always_mask, int from, int to, int n) {
+  if (weighted) {
+    tiles(std::true_type{}, std::true_type{}, from, to);  // (cross-attention with repeated text keys: few, small tiles)
+  } else {
+    const int split = always_mask ? from : min(to, from + (n > from ? (n - from) / KT * KT : 0));  // first tile that is not full
+    tiles(std::false_type{}, std::false_type{}, from, split);
+    tiles(std::true_type{}, std::false_type{}, split, to);
+  }
+}
 
 // ------------------------------------------------------------------------------------------ forward
 // DPP: image pitch (features); NS = ceil(D/16) k-steps of q.k; NB = ceil(D/32) feature blocks of the output.
@@ -202,7 +238,7 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnParams p) {
   dma.bind(kb, p.ldk, 0);
   dmav.bind(vb, p.ldv, 0);
   dma.issue(0, p.Nk, smem, wave_u);
-  dmav.template issue<MSUM>(0, p.Nk, smem + I::BYTES, wave_u);
+  dmav.issue(0, p.Nk, smem + I::BYTES, wave_u);
 
   bf16x8_t qf[NS];
 #pragma unroll
@@ -219,93 +255,97 @@ __global__ void __launch_bounds__(256) attn_fwd_kernel(const AttnParams p) {
     for (int e = 0; e < 16; ++e) o_acc[i][e] = 0.f;
   float m_run = NEG_BIG, l_run = 0.f;
   int cur = 0;
-  for (int kbase = 0; kbase < kend; kbase += KT, cur ^= 1) {
-    dma_join();
-    if (kbase + KT < kend) {  // next tile flies under this tile's math
-      dma.issue(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE, wave_u);
-      dmav.template issue<MSUM>(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE + I::BYTES, wave_u);
-    }
-    const unsigned char* k_img = smem + cur * STAGE;
-    const unsigned char* v_img = k_img + I::BYTES;
-    f32x16_t st[2];
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt) {
-#pragma unroll
-      for (int e = 0; e < 16; ++e) st[kt][e] = 0.f;
-#pragma unroll
-      for (int s = 0; s < NS; ++s) {
-        const bf16x8_t kf = row_frag<DPP>(k_img, kt * 32 + fr, 2 * s + fh);
-        st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], st[kt], 0, 0, 0);
+  // One tile LOOP per straight-line body, the wave-uniform choice (mask, key weights) made outside it (attn_tile_loops): a test
+  // between the exponentials and the P.V products ends the basic block there and nothing is scheduled across it - no MFMA ran
+  // beside the softmax.
+  auto tiles = [&](auto masked, auto weighted, int kfrom, int kto) {
+    constexpr bool MASK = decltype(masked)::value, KW = decltype(weighted)::value;
+    for (int kbase = kfrom; kbase < kto; kbase += KT, cur ^= 1) {
+      dma_join();
+      if (kbase + KT < kend) {  // next tile flies under this tile's math
+        dma.issue(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE, wave_u);
+        dmav.issue(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE + I::BYTES, wave_u);
       }
-    }
-    // running max on the RAW scores (scale2 > 0), scale folded into the exp2 argument; masks only where needed
-    const bool need_mask = (kbase + KT > p.Nk) || p.causal;  // wave-uniform
-    float mx = NEG_BIG;
-    if (need_mask) {
+      const unsigned char* k_img = smem + cur * STAGE;
+      const unsigned char* v_img = k_img + I::BYTES;
+      f32x16_t st[2];
+#pragma unroll
+      for (int kt = 0; kt < 2; ++kt) {
+#pragma unroll
+        for (int e = 0; e < 16; ++e) st[kt][e] = 0.f;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const bf16x8_t kf = row_frag<DPP>(k_img, kt * 32 + fr, 2 * s + fh);
+          st[kt] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[s], st[kt], 0, 0, 0);
+        }
+      }
+      // running max on the RAW scores (scale2 > 0), scale folded into the exp2 argument; masks only where needed
+      float mx = NEG_BIG;
+      if (MASK) {
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int key = kbase + kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh;
+            if (key >= p.Nk || (p.causal && key > qi)) st[kt][e] = NEG_BIG;
+          }
+      }
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int key = kbase + kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh;
-          if (key >= p.Nk || (p.causal && key > qi)) st[kt][e] = NEG_BIG;
-        }
-    }
+        for (int e = 0; e < 16; ++e) mx = fmaxf(mx, st[kt][e]);
+      mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+      if (__any((mx - m_run) * p.scale2 > RESCALE_LOG2)) {  // wave-uniform; always taken on the first tile (m_run = -big)
+        const float m_new = fmaxf(m_run, mx);
+        const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale2);
+        m_run = m_new;
+        l_run *= alpha;
 #pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
+        for (int i = 0; i < NB; ++i)
 #pragma unroll
-      for (int e = 0; e < 16; ++e) mx = fmaxf(mx, st[kt][e]);
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    if (__any((mx - m_run) * p.scale2 > RESCALE_LOG2)) {  // wave-uniform; always taken on the first tile (m_run = -big)
-      const float m_new = fmaxf(m_run, mx);
-      const float alpha = __builtin_amdgcn_exp2f((m_run - m_new) * p.scale2);
-      m_run = m_new;
-      l_run *= alpha;
-#pragma unroll
-      for (int i = 0; i < NB; ++i)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) o_acc[i][e] *= alpha;
-    }
-    const float mneg = -m_run * p.scale2;
-    float psum = 0.f;
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const float arg = fmaf(st[kt][e], p.scale2, mneg);
-        st[kt][e] = __builtin_amdgcn_exp2f(arg);
+          for (int e = 0; e < 16; ++e) o_acc[i][e] *= alpha;
       }
-    if (p.key_w) {  // wave-uniform; the running max stays on the unweighted scores (weights are O(1))
+      const float mneg = -m_run * p.scale2;
+      float kwv[2][16];
+      if (KW) {  // the running max stays on the unweighted scores (weights are O(1)); one batch of loads ahead of the exponentials
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+          for (int e = 0; e < 16; ++e) {
+            const int key = kbase + kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh;
+            kwv[kt][e] = p.key_w[min(key, p.Nk - 1)];
+          }
+      }
+      // P = exp2(...) and O^T += V^T P^T, eight keys (one k-step of the product) at a time: the products of one group run
+      // beside the exponentials of the next
+      float psum = 0.f;
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt)
 #pragma unroll
-        for (int e = 0; e < 16; ++e) {
-          const int key = kbase + kt * 32 + (e & 3) + 8 * (e >> 2) + 4 * fh;
-          st[kt][e] *= p.key_w[min(key, p.Nk - 1)];
+        for (int s = 0; s < 2; ++s) {
+          float tmp[8];
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            const int e = 8 * s + j;
+            float pv = __builtin_amdgcn_exp2f(fmaf(st[kt][e], p.scale2, mneg));
+            if (KW) pv *= kwv[kt][e];
+            if (!MSUM) psum += pv;
+            tmp[j] = pv;
+          }
+          const bf16x8_t pf = cvt_frag(tmp);
+#pragma unroll
+          for (int i = 0; i < NB; ++i) {
+            const bf16x8_t vf = tr.frag(v_img, kt * 32 + 16 * s, i);
+            o_acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o_acc[i], 0, 0, 0);
+          }
+          // groups stay in program order: the matrix pipe works through this group's products while the next group's
+          // exponentials issue; left free, hipcc hoists every group's V reads and exponentials to the top (+40 registers)
+          __builtin_amdgcn_sched_barrier(0);
         }
+      if (!MSUM) l_run += psum;
     }
-    if (!MSUM) {
-#pragma unroll
-      for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-        for (int e = 0; e < 16; ++e) psum += st[kt][e];
-      l_run += psum;
-    }
-    // O^T += V^T P^T
-#pragma unroll
-    for (int kt = 0; kt < 2; ++kt)
-#pragma unroll
-      for (int s = 0; s < 2; ++s) {
-        float tmp[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) tmp[j] = st[kt][8 * s + j];
-        const bf16x8_t pf = cvt_frag(tmp);
-#pragma unroll
-        for (int i = 0; i < NB; ++i) {
-          const bf16x8_t vf = tr.frag(v_img, kt * 32 + 16 * s, i);
-          o_acc[i] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, o_acc[i], 0, 0, 0);
-        }
-      }
-  }
+  };
+  attn_tile_loops(tiles, p.key_w != nullptr, p.causal != 0, 0, kend, p.Nk);
   float l_tot;
   if (MSUM) l_tot = __shfl(o_acc[NB - 1][12], fr, 64);  // ones-column row sum: accumulator row 24 lives in lanes 0..31
   else l_tot = l_run + __shfl_xor(l_run, 32, 64);
@@ -395,18 +435,17 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const AttnParams p) {
     for (int e = 0; e < 16; ++e) dq_acc[i][e] = 0.f;
 
   int cur = 0;
-  for (int kbase = 0; kbase < kend; kbase += KT, cur ^= 1) {
-    dma_join();
-    if (kbase + KT < kend) {
-      dma.issue(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE, wave_u);
-      dmav.issue(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE + I::BYTES, wave_u);
-    }
-    const unsigned char* k_img = smem + cur * STAGE;
-    const unsigned char* v_img = k_img + I::BYTES;
-    const bool need_mask = (kbase + KT > p.Nk) || p.causal || (q0 + 128 > p.Nq);  // wave-uniform
-    // two straight-line tile bodies, the wave-uniform choice made once per tile (see attn_bwd_dkv_kernel)
-    auto tile = [&](auto masked, auto weighted) {
-      constexpr bool MASK = decltype(masked)::value, KW = decltype(weighted)::value;
+  // straight-line tile bodies, one loop each (attn_tile_loops; see attn_bwd_dkv_kernel)
+  auto tiles = [&](auto masked, auto weighted, int kfrom, int kto) {
+    constexpr bool MASK = decltype(masked)::value, KW = decltype(weighted)::value;
+    for (int kbase = kfrom; kbase < kto; kbase += KT, cur ^= 1) {
+      dma_join();
+      if (kbase + KT < kend) {
+        dma.issue(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE, wave_u);
+        dmav.issue(kbase + KT, p.Nk, smem + (cur ^ 1) * STAGE + I::BYTES, wave_u);
+      }
+      const unsigned char* k_img = smem + cur * STAGE;
+      const unsigned char* v_img = k_img + I::BYTES;
 #pragma unroll
       for (int kt = 0; kt < 2; ++kt) {
         f32x16_t st, dpt;
@@ -438,11 +477,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const AttnParams p) {
           }
         }
       }
-    };
-    if (p.key_w) tile(std::true_type{}, std::true_type{});  // (cross-attention with repeated text keys: few, small tiles)
-    else if (need_mask) tile(std::true_type{}, std::false_type{});
-    else tile(std::false_type{}, std::false_type{});
-  }
+    }
+  };
+  attn_tile_loops(tiles, p.key_w != nullptr, p.causal || q0 + 128 > p.Nq, 0, kend, p.Nk);
   if (qi < p.Nq) {
     bf16_t* ob = p.dq + (long)b * p.bsdq + (long)qi * p.lddq + h * p.D;
 #pragma unroll
@@ -523,19 +560,19 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const AttnParams p) {
     for (int e = 0; e < 16; ++e) { dk_acc[i][e] = 0.f; dv_acc[i][e] = 0.f; }
 
   int cur = 0;
-  for (int qbase = qstart; qbase < qend; qbase += KT, cur ^= 1) {
-    dma_join();
-    if (qbase + KT < qend) stage(qbase + KT, smem + (cur ^ 1) * STAGE);
-    const unsigned char* q_img = smem + cur * STAGE;
-    const unsigned char* do_img = q_img + I::BYTES;
-    const float* lse_s = reinterpret_cast<const float*>(q_img + 2 * I::BYTES);
-    const float* dlt_s = lse_s + KT;
-    const bool need_mask = (qbase + KT > p.Nq) || (k0 + 128 > p.Nk) || p.causal;  // wave-uniform
-    // The tile body exists twice - with and without the boundary / causal mask - and the wave-uniform choice is made ONCE per
-    // tile: a test inside the per-element loop cuts the unrolled body into 32 three-instruction basic blocks (fma - exp - mul
-    // with a branch each), which nothing can be scheduled across (every exp latency exposed, no MFMA beside the VALU work).
-    auto tile = [&](auto masked, auto weighted) {
-      constexpr bool MASK = decltype(masked)::value, KW = decltype(weighted)::value;
+  // The tile body exists with and without the boundary / causal mask (and the key weights), and the wave-uniform choice is made
+  // outside the tile loop (attn_tile_loops): a test inside the per-element loop cuts the unrolled body into 32 three-instruction
+  // basic blocks (fma - exp - mul with a branch each), which nothing can be scheduled across (every exp latency exposed, no MFMA
+  // beside the VALU work).
+  auto tiles = [&](auto masked, auto weighted, int qfrom, int qto) {
+    constexpr bool MASK = decltype(masked)::value, KW = decltype(weighted)::value;
+    for (int qbase = qfrom; qbase < qto; qbase += KT, cur ^= 1) {
+      dma_join();
+      if (qbase + KT < qend) stage(qbase + KT, smem + (cur ^ 1) * STAGE);
+      const unsigned char* q_img = smem + cur * STAGE;
+      const unsigned char* do_img = q_img + I::BYTES;
+      const float* lse_s = reinterpret_cast<const float*>(q_img + 2 * I::BYTES);
+      const float* dlt_s = lse_s + KT;
 #pragma unroll
       for (int qt = 0; qt < 2; ++qt) {
         f32x16_t sa, dpa;
@@ -583,11 +620,9 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const AttnParams p) {
           }
         }
       }
-    };
-    if (p.key_w) tile(std::true_type{}, std::true_type{});  // (cross-attention with repeated text keys: few, small tiles)
-    else if (need_mask) tile(std::true_type{}, std::false_type{});
-    else tile(std::false_type{}, std::false_type{});
-  }
+    }
+  };
+  attn_tile_loops(tiles, p.key_w != nullptr, p.causal || k0 + 128 > p.Nk, qstart, qend, p.Nq);
   if (QSPLIT) {  // this query chunk's partial sums go to its OWN fp32 slab (plain stores, one writer per element: no atomics, no
     // zero fill); attn_kv_finish_kernel adds the slabs in chunk order
     if (ki < p.Nk) {
@@ -674,6 +709,8 @@ static int attn_fill(AttnParams* p, const SdtAttnDesc* d, const char* name) {
                 "%s: bad shape B=%d H=%d Nq=%d Nk=%d D=%d", name, d->B, d->H, d->Nq, d->Nk, d->D);
   SDT_CHECK_ARG(d->D % 8 == 0 && d->D <= 160, "%s: head dim %d must be a multiple of 8 and <= 160", name, d->D);
   SDT_CHECK_ARG(d->ldq % 8 == 0 && d->ldk % 8 == 0 && d->ldv % 8 == 0 && d->ldo % 8 == 0, "%s: row strides must be multiples of 8", name);
+  SDT_CHECK_ARG(d->ldq < (1 << 24) && d->ldk < (1 << 24) && d->ldv < (1 << 24) && d->ldo < (1 << 24) && d->ld_dout < (1 << 24),
+                "%s: row strides must be below 2^24 elements (a tile's byte step is kept in 32 bits)", name);
   p->B = d->B; p->H = d->H; p->Nq = d->Nq; p->Nk = d->Nk; p->D = d->D;
   p->ldq = d->ldq; p->ldk = d->ldk; p->ldv = d->ldv; p->ldo = d->ldo;
   p->bsq = (long)d->Nq * d->ldq; p->bsk = (long)d->Nk * d->ldk; p->bsv = (long)d->Nk * d->ldv; p->bso = (long)d->Nq * d->ldo;
