@@ -25,7 +25,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.distributed as dist
 
-from stable_diffusion_training_amd import dp, latent_cache, nets
+from stable_diffusion_training_amd import dp, latent_cache, lora, nets
 from stable_diffusion_training_amd import training_utils as tu
 from stable_diffusion_training_amd.checkpoint import gather_rng_states
 from stable_diffusion_training_amd.streamer import DataLoader
@@ -55,7 +55,7 @@ def schedule_kwargs(config_dict):
 
 def current_lr(state):
     """The learning rate of the store's last optimizer step (the schedule's value, or the constant rate)."""
-    sched = state.store.schedule
+    sched = state.opt_store.schedule
     return sched[0].rate(max(state.step - 1, 0)) if sched else state.hyper["lr"]
 
 
@@ -93,11 +93,17 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         rank=rank, world_size=world, device=dev, text_towers=2 if sdxl else 1)
     dataloader._print_debug = bool(config_dict.get("DEBUG"))
 
+    lora_cfg = None
+    if config_dict.get("lora_rank"):  # LoRA: rank-r adapters on the UNet's attention projections, frozen text encoder, alpha = rank
+        if world > 1:
+            raise ValueError("lora_rank: adapter training runs on one GPU (train_step refuses a reducer with adapter states)")
+        r = int(config_dict["lora_rank"])
+        lora_cfg = dict(unet=lora.LoraConfig(r, float(config_dict.get("lora_alpha", r))), text_encoder="frozen")
     train_rngs = torch.Generator(device=dev)
     train_rngs.manual_seed(config_dict["master_seed"] * 1009 + rank)  # different noise / timesteps on every shard
     (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers,
      model_object_dict) = tu.on_device_model_training_state(training_config, models, device=dev, optimizer=config_dict.get("optimizer", "lion"),
-                                                           **schedule_kwargs(config_dict))
+                                                           **schedule_kwargs(config_dict), lora=lora_cfg)
     reducer = dp.GradReducer([unet_state.store, text_encoder_state.store]) if world > 1 else None
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
@@ -132,8 +138,10 @@ def main(config_dict, models=None, tokenizer=None, log=print):
 
     def save(ema):
         base = config_dict["model_path"].split("@")[0] + ("-EMA" if ema else "")
-        up = unet_ema_params if (ema and config_dict["accumulate_unet_ema"]) else unet_state.params
-        tp = text_encoder_ema_params if (ema and config_dict["accumulate_text_encoder_ema"]) else text_encoder_state.params
+        # (a model without an EMA view - accumulate_*_ema off, or a text encoder frozen under LoRA - is saved as it stands)
+        up = unet_ema_params if (ema and config_dict["accumulate_unet_ema"] and unet_ema_params is not None) else unet_state.params
+        tp = (text_encoder_ema_params if (ema and config_dict["accumulate_text_encoder_ema"] and text_encoder_ema_params is not None)
+              else text_encoder_state.params)
         tu.save_model(model_object_dict, tokenizer, up, tp, vae_params, f'{base}@{config_dict["chunk_steps"]}')
         delete_file_or_folder(f'{base}@{config_dict["chunk_steps"] - config_dict["keep_trained_model_buffer"]}')
 
@@ -193,6 +201,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
                 save(ema=True)
             state_path = config_dict["model_path"].split("@")[0] + "-state.safetensors"
             tu.save_training_state(state_path, unet_state, text_encoder_state, rng_states=rng_states)
+            if unet_state.adapter is not None:  # the adapter alone (the saves above hold the base with the adapter folded in)
+                unet_state.adapter.save(config_dict["model_path"].split("@")[0] + "-lora.npz")
         config_dict["model_path"] = f'{config_dict["model_path"].split("@")[0]}@{config_dict["chunk_steps"]}'  # training.py:301-304
         config_dict["chunk_number"] += 1
         config_dict["chunk_steps"] += 1
@@ -209,6 +219,8 @@ if __name__ == "__main__":
                     help="lion (the reference's, default) or adamw: learning rates taken as given, 8-bit moments where the config quantises")
     ap.add_argument("--cache-latents", metavar="DIR", default=None,
                     help="encode the run's chunks once into a latent cache under DIR, drop the VAE and train from the cache")
+    ap.add_argument("--lora", metavar="RANK", type=int, default=None,
+                    help="train rank-RANK LoRA adapters on the UNet's attention projections (frozen base and text encoder) instead of every weight")
     args = ap.parse_args()
     with open(args.config) as f:
         cfg = json.load(f)
@@ -216,6 +228,8 @@ if __name__ == "__main__":
         cfg["micro_batches"] = args.micro_batches
     if args.optimizer is not None:
         cfg["optimizer"] = args.optimizer
+    if args.lora is not None:
+        cfg["lora_rank"] = args.lora
     if args.cache_latents is not None:
         cfg["cache_latents"] = args.cache_latents
     main(cfg)

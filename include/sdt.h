@@ -409,6 +409,36 @@ int sdt_embedding_fwd(const int32_t* ids, const float* tok, const float* pos, ui
 int sdt_embedding_bwd(const int32_t* ids, const uint16_t* dout, float* dtok, float* dpos, int64_t rows, int S, int D,
                       hipStream_t stream);
 
+/* ---- LoRA: low-rank adapters in weight space (no reference counterpart; DESIGN.md "LoRA") ----
+ * An adapted Dense kernel W0 [K][N] (fp32 master of a frozen store) carries A [K][r] and B [r][N] (fp32 leaves of the adapter's
+ * own store).  Before a step the merge writes the bf16 mirror W = RNE(W0 + s * A * B) the GEMMs read; after its backward the
+ * ordinary weight-gradient kernels have left dW (bf16) in the adapter's scratch, and the projection writes the factors' gradients.
+ * Both calls serve one job table in one launch (tile0_* are running tile counts, as sdt_param_prepare's tile0: 64 x 64 tiles of
+ * W for the merge; ceil(K/64) row stripes of dA followed by ceil(N/64) column stripes of dB for the projection).  jobs_host and
+ * jobs_device hold the same n jobs: the host copy is checked (r in {4, 8, 16, 32, 64, 128}; K, N positive multiples of 8; offsets
+ * non-negative multiples of 8 elements; tile counts running) and sizes the grid, the kernels read the device copy.  n == 0 launches
+ * nothing and returns SDT_OK.  A and B are rounded to bf16 (RNE) as they are loaded, products are accumulated in fp32 by
+ * mfma_f32_16x16x32_bf16 with r padded by zero lanes; no atomics: one writer and one summation order per element. */
+typedef struct SdtLoraJob {
+  int64_t w0_off;         /* W0 in w0_base (elements) */
+  int64_t a_off, b_off;   /* A, B in ab_base: the adapter store's master, or its EMA buffer */
+  int64_t w_off, f_off;   /* destinations of the merge in w_bf16 / f32_dst */
+  int64_t dw_off;         /* dW [K][N] bf16 in dw_base */
+  int64_t ga_off, gb_off; /* dA, dB in grad_base */
+  int32_t K, N, r;
+  float scale;            /* s = alpha / r */
+  int32_t tile0_merge, tile0_project, tiles_da, reserved;
+} SdtLoraJob;
+int sdt_lora_job_size(void);
+/* v = W0 + s * (bf16(A) * bf16(B)) in fp32 (one product rounding, one sum rounding); w_bf16 (or NULL) receives RNE(v) with 16-byte
+ * stores - the training mirror - and f32_dst (or NULL) v itself - an adapter folded into a checkpoint; at least one is given. */
+int sdt_lora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, const SdtLoraJob* jobs_host,
+                   const void* jobs_device, int n, hipStream_t stream);
+/* dA[k][q] = s * sum_n dW[k][n] * bf16(B[q][n]) and dB[q][n] = s * sum_k bf16(A[k][q]) * dW[k][n], WRITTEN as fp32: the gradient of
+ * the function the merge evaluated.  dW is read twice (once per factor: 4 B per adapted parameter). */
+int sdt_lora_project(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
+                     const void* jobs_device, int n, hipStream_t stream);
+
 /* ---- test hooks (not for the training path) ----
  * Output channels per tile of the 3x3 halo convolution inside sdt_gemm_nt_bf16: 64 (the default) or 128 (the reference of the
  * bitwise parity test).  Process-wide, not thread-safe; launches already enqueued keep the width they were planned with.

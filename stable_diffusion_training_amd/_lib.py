@@ -39,6 +39,11 @@ class SdtTnProblem(ctypes.Structure):
                 ("N_valid", _I), ("lda", _I), ("ldb", _I), ("ldw", _I), ("n_seg", _I), ("seg_stride", _L), ("sq_slots", _P), ("dw_bf16", _I)]
 
 
+class SdtLoraJob(ctypes.Structure):
+    _fields_ = [(n, _L) for n in ("w0_off", "a_off", "b_off", "w_off", "f_off", "dw_off", "ga_off", "gb_off")] + [
+        ("K", _I), ("N", _I), ("r", _I), ("scale", _F), ("tile0_merge", _I), ("tile0_project", _I), ("tiles_da", _I), ("reserved", _I)]
+
+
 GATHER_PLAIN, GATHER_FPROP, GATHER_DGRAD = 0, 1, 2
 ACT_SILU, ACT_QUICK_GELU, ACT_GELU_ERF = 0, 1, 2
 
@@ -104,6 +109,8 @@ SIGNATURES = {
     "sdt_cast_f32_to_bf16": [_P, _P, _L, _P],
     "sdt_transpose_bf16": [_P, _P, _I, _I, _I, _P],
     "sdt_param_prepare": [_P, _P, _P, _P, _I, _I, _P],
+    "sdt_lora_merge": [_P, _P, _P, _P, _P, _P, _I, _P],
+    "sdt_lora_project": [_P, _P, _P, _P, _P, _I, _P],
     "sdt_embedding_fwd": [_P, _P, _P, _P, _L, _I, _I, _P],
     "sdt_embedding_bwd": [_P, _P, _P, _P, _L, _I, _I, _P],
     "sdt_ff_geglu_fwd": [_P, _P, _P, _P, _P, _L, _I, _I, _P],
@@ -115,7 +122,7 @@ WS_QUERY = {"sdt_gemm_nt_workspace_bytes": [_L, _I, _I, _I], "sdt_gemm_tn_worksp
             "sdt_groupnorm_fwd_workspace_bytes": [_I, _I, _I, _I], "sdt_attention_bwd_workspace_bytes": [_P],
             "sdt_gemm_tn_wgrad_group_workspace_bytes": [_P, _I], "sdt_conv_wgrad_group_workspace_bytes": [_P, _I], "sdt_reduce_workspace_bytes": [], "sdt_sqnorm_workspace_bytes": [], "sdt_colsum_workspace_bytes": [_I, _L, _I],
             "sdt_wgrad_sq_slots": [_I, _I, _I]}
-NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_last_error": ctypes.c_char_p}
+NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_lora_job_size": _I, "sdt_last_error": ctypes.c_char_p}
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libsdtrain_hip.so")
 if os.environ.get("SDT_LIB"):  # developer A/B of two builds on one box (tools/ab_libs.sh): another in-tree build of the same sources
@@ -153,6 +160,8 @@ def load():
         fn.restype = res
     if lib.sdt_param_prepare_desc_size() != ctypes.sizeof(SdtPrepDesc):
         raise SdtError("SdtPrepDesc layout mismatch between _lib.py and the library")
+    if lib.sdt_lora_job_size() != ctypes.sizeof(SdtLoraJob):
+        raise SdtError("SdtLoraJob layout mismatch between _lib.py and the library")
     _lib = lib
     return lib
 

@@ -183,8 +183,12 @@ def params_to_tree(params):
         params = params.store
     if isinstance(params, ParamStore) and getattr(params, "full_tree", None) is not None:
         flat = flatten_tree(params.full_tree)  # frozen VAE: the device store holds the encoder half only
+    elif isinstance(params, EmaView) and getattr(params.store, "lora_of", None) is not None:
+        flat = params.store.lora_of.folded(source="ema")  # the EMA of a LoRA adapter, folded into its frozen base
     elif isinstance(params, EmaView):
         flat = params.store.export_host("ema")
+    elif isinstance(params, ParamStore) and getattr(params, "adapter", None) is not None:
+        flat = params.adapter.folded()  # a frozen base with its LoRA adapter folded in: an ordinary checkpoint
     elif isinstance(params, ParamStore):
         flat = params.export_host("master")
     elif isinstance(params, dict):
@@ -388,6 +392,20 @@ _OLD_FORMATS = {"sdt-training-state-1": "the flat-buffer layout changed after th
                                         "re-export the weights with save_model from the build that wrote the file and restart the optimizer state"}
 
 
+def _stepping_store(st):
+    """The store of a state whose buffers a training-state file holds: the state's own store, the store of its LoRA adapter (the frozen
+    base under it is not written: it is the checkpoint the run started from), or None for a frozen model without an adapter."""
+    store = st.store if hasattr(st, "store") else st
+    ad = getattr(st, "adapter", None)
+    if ad is not None:
+        return ad.store, ad
+    return (store if getattr(store, "trainable", True) else None), None
+
+
+def _lora_meta(ad):
+    return f"rank={ad.cfg.rank};alpha={float(ad.cfg.alpha)!r};targets={','.join(ad.cfg.targets)}"
+
+
 def save_training_state(path, unet_state, text_encoder_state, train_rng=None, rng_states=None):
     """Everything train_step mutates, so that load_training_state + the same batches continue the run: fp32 masters, 8-bit
     Lion codes + per-block scales, fp32 momenta of the unquantised leaves, EMA, step counts, and the sampling generator(s).
@@ -396,7 +414,12 @@ def save_training_state(path, unet_state, text_encoder_state, train_rng=None, rn
     from safetensors.torch import save_file
     tensors, meta = {}, {"format": STATE_FORMAT}
     for name, st in (("unet", unet_state), ("text_encoder", text_encoder_state)):
-        store = st.store if hasattr(st, "store") else st
+        store, ad = _stepping_store(st)
+        if store is None:  # frozen, no adapter: nothing of it changes
+            meta[f"{name}.frozen"] = "1"
+            continue
+        if ad is not None:  # LoRA: the adapter store's master, moments, EMA and count
+            meta[f"{name}.lora"] = _lora_meta(ad)
         store._gather()  # sharded optimizer: raises unless GradReducer.gather_state() (collective, all ranks) made the state whole
         for b in _STATE_BUFFERS + (_ADAMW_BUFFERS if _optimizer_of(store) == "adamw" else ()):
             t = getattr(store, b)
@@ -446,7 +469,14 @@ def load_training_state(path, unet_state, text_encoder_state, train_rng=None, ra
             raise ValueError(f"{path}: not a training-state file (format {fmt!r}, expected {STATE_FORMAT})")
         keys = set(f.keys())
         for name, st in (("unet", unet_state), ("text_encoder", text_encoder_state)):
-            store = st.store if hasattr(st, "store") else st
+            store, ad = _stepping_store(st)
+            if (store is None) != (meta.get(f"{name}.frozen") == "1"):
+                raise ValueError(f"{path}: {name} is frozen in only one of file / state")
+            if store is None:
+                continue
+            if meta.get(f"{name}.lora") != (None if ad is None else _lora_meta(ad)):
+                raise ValueError(f"{path}: {name} state was saved with LoRA settings {meta.get(f'{name}.lora')!r}, this state has "
+                                 f"{None if ad is None else _lora_meta(ad)!r}")
             saved_opt, opt = meta.get(f"{name}.optimizer", "lion"), _optimizer_of(store)
             if saved_opt != opt:
                 raise ValueError(f"{path}: {name} state was saved by the {saved_opt} optimizer and this state is built for {opt}: their "
@@ -465,6 +495,8 @@ def load_training_state(path, unet_state, text_encoder_state, train_rng=None, ra
             store.set_step(int(meta[f"{name}.count"]))  # with a schedule: the device step counter resumes too
             if store.device.type == "cuda":
                 store.prepare(full=True)  # the masters changed under the bf16 compute copies
+                if ad is not None:
+                    ad.merge()            # ... and under the merged mirrors of the adapted leaves
             store.state_whole = True      # every rank loaded the whole buffers (sharded optimizer: nothing to gather before a save)
         if train_rng is not None:
             saved_world = int(meta.get("train_rng.world", "0"))

@@ -1,0 +1,255 @@
+"""Low-rank adapters (LoRA) trained in weight space on a frozen base (DESIGN.md "LoRA"; include/sdt.h "LoRA").
+
+An adapted Dense kernel W0 [K, N] of a frozen ParamStore carries two trained leaves A [K, r] and B [r, N] in a ParamStore of the
+adapter's own.  Every GEMM of the model reads one bf16 mirror (ParamStore.w), so the adapter never enters the forward / input-gradient
+chain: before a step ONE launch writes w[leaf] = bf16(W0 + s * A @ B) for every adapted leaf (s = alpha / rank, the sum rounded once from
+fp32), the step runs as it stands - merged GEMMs, packed attention, HIP graphs - the ordinary weight-gradient kernels leave dW (bf16)
+of the adapted leaves in the adapter's scratch, and ONE launch projects dA = s * dW @ B^T, dB = s * A^T @ dW into the gradient buffer
+of the adapter's store, which then takes the optimizer step like any other store (Lion / AdamW, 8-bit or fp32 moments, EMA, schedules,
+clipping, checkpoints, micro-batch accumulation).
+"""
+import bisect
+import json
+import math
+from dataclasses import dataclass
+
+import numpy as np
+import torch
+
+from . import _lib
+from .params import ParamStore
+
+RANKS = (4, 8, 16, 32, 64, 128)
+UNET_TARGETS = ("to_q", "to_k", "to_v", "to_out_0")
+CLIP_TARGETS = ("q_proj", "k_proj", "v_proj", "out_proj")
+
+
+@dataclass(frozen=True)
+class LoraConfig:
+    """rank in RANKS; the delta is (alpha / rank) * A @ B; targets are matched against path components (as params.create_mask does);
+    seed draws A (B starts at zero)."""
+    rank: int
+    alpha: float
+    targets: tuple = UNET_TARGETS
+    seed: int = 0
+
+    def __post_init__(self):
+        object.__setattr__(self, "targets", tuple(self.targets))
+        if isinstance(self.rank, bool) or self.rank not in RANKS:
+            raise ValueError(f"LoraConfig: rank must be one of {RANKS}, not {self.rank!r}")
+        if not self.targets or not all(isinstance(t, str) and t for t in self.targets):
+            raise ValueError(f"LoraConfig: targets must be a non-empty tuple of path components, not {self.targets!r}")
+        if not math.isfinite(float(self.alpha)):
+            raise ValueError(f"LoraConfig: alpha must be finite, not {self.alpha!r}")
+
+    @property
+    def scale(self):
+        return float(self.alpha) / self.rank
+
+
+def select_leaves(spec, cfg):
+    """The kernel paths of `spec` ([(path, shape)], forward order) that `cfg` adapts: '/kernel' leaves with a path component equal to a
+    target.  ValueError for a convolution (4-D) kernel, for a Dense kernel whose dims are not multiples of 8 (its bf16 mirror is a
+    zero-padded copy) and when nothing matches."""
+    out = []
+    for path, shape in spec:
+        if not path.endswith("/kernel") or not any(t in path.split("/")[:-1] for t in cfg.targets):
+            continue
+        shape = tuple(shape)
+        if len(shape) != 2:
+            raise ValueError(f"LoRA: target matches {path} {shape}, which is not a Dense kernel (convolutions are not adapted)")
+        if shape[0] % 8 or shape[1] % 8:
+            raise ValueError(f"LoRA: {path} {shape} is a padded leaf (dims not multiples of 8) and cannot carry an adapter")
+        out.append(path)
+    if not out:
+        raise ValueError(f"LoRA: no Dense kernel matches the targets {cfg.targets!r}")
+    return out
+
+
+def adapter_spec(spec, cfg):
+    """[(<dense path>/lora_a, (K, r)), (<dense path>/lora_b, (r, N))] for the adapted kernels of `spec`, in its order."""
+    shapes = dict((p, tuple(s)) for p, s in spec)
+    out = []
+    for path in select_leaves(spec, cfg):
+        K, N = shapes[path]
+        dense = path[: -len("/kernel")]
+        out += [(dense + "/lora_a", (K, cfg.rank)), (dense + "/lora_b", (cfg.rank, N))]
+    return out
+
+
+def scratch_runs(leaves, adapted):
+    """The compact layout of the dW scratch: ([(start, end, base)], size).  A merged launch (ops.linear_multi) writes its whole group at
+    the masters' relative offsets, and a group is a run of same-shape Dense kernels laid out back to back.  So every maximal such run
+    that holds an adapted leaf gets one slot of its own length at `base`, and master element e of the run [start, end) lives at scratch
+    element base + e - start: inside a run the masters' distances are kept, a group or a single leaf never straddles two runs, and runs
+    without an adapted leaf take no room.  A run that is only partly adapted gets room for all of it (the extra gradients are computed
+    and ignored).  Starts, ends and bases are multiples of 8 elements."""
+    dense = sorted((lf for lf in leaves.values() if lf.path.endswith("/kernel") and lf.batch == 1 and (lf.R, lf.C) == (lf.Rp, lf.Cp)),
+                   key=lambda lf: lf.offset)
+    runs, size = [], 0
+    i = 0
+    while i < len(dense):
+        j = i
+        while (j + 1 < len(dense) and dense[j + 1].shape == dense[i].shape
+               and dense[j + 1].offset == dense[j].offset + dense[j].numel):
+            j += 1
+        if any(lf.path in adapted for lf in dense[i: j + 1]):
+            start, end = dense[i].offset, dense[j].offset + dense[j].numel
+            runs.append((start, end, size))
+            size += (end - start + 7) // 8 * 8
+        i = j + 1
+    return runs, size
+
+
+class LoraAdapter:
+    """What attach() hangs on a frozen store: the trained A / B leaves (self.store), the bf16 dW scratch and the job table."""
+
+    def __init__(self, base, cfg, store_kwargs):
+        if base.trainable:
+            raise ValueError("LoRA: the base store must be frozen (ParamStore(trainable=False)); a trained store takes no adapter")
+        if getattr(base, "adapter", None) is not None:
+            raise ValueError("LoRA: the store already carries an adapter")
+        self.base, self.cfg, self.source = base, cfg, "master"
+        base_spec = [(p, base.leaves[p].shape) for p in base.order]
+        self.paths = select_leaves(base_spec, cfg)
+        for p in self.paths:
+            lf = base.leaves[p]
+            if (lf.R, lf.C) != (lf.Rp, lf.Cp) or lf.w_off != lf.offset:
+                raise ValueError(f"LoRA: {p} is a padded leaf and cannot carry an adapter")
+        self.adapted = {p: (p[: -len("kernel")] + "lora_a", p[: -len("kernel")] + "lora_b") for p in self.paths}
+        kw = dict(store_kwargs)
+        kw.setdefault("device", base.device)
+        self.store = ParamStore(adapter_spec(base_spec, cfg), trainable=True, **kw)
+        self.store.lora_of = self  # (checkpoint.params_to_tree folds an EmaView of this store into the base)
+        if self.store.grad16 is not None or self.store.g32_base:
+            raise ValueError("LoRA: the adapter store must keep its gradients in float32")
+        self.runs, size = scratch_runs(base.leaves, self.adapted)
+        self._run_starts = [r[0] for r in self.runs]
+        dev = base.device
+        # dW of every adapted leaf (and of the non-adapted members of a merged group, computed and ignored): scratch_runs' layout
+        self.scratch = torch.zeros(size, dtype=torch.bfloat16, device=dev)
+        jobs, tm, tp = [], 0, 0
+        for p in self.paths:
+            lf = base.leaves[p]
+            la, lb = (self.store.leaves[q] for q in self.adapted[p])
+            K, N = lf.shape
+            ta = (K + 63) // 64
+            jobs.append(_lib.SdtLoraJob(lf.offset, la.offset, lb.offset, lf.w_off, lf.offset, self.scratch_offset(lf.offset, lf.offset + lf.numel), la.offset, lb.offset,
+                                        K, N, cfg.rank, cfg.scale, tm, tp, ta, 0))
+            tm += ta * ((N + 63) // 64)
+            tp += ta + (N + 63) // 64
+        self.jobs_host = (_lib.SdtLoraJob * len(jobs))(*jobs)
+        self.jobs_dev = torch.frombuffer(bytearray(bytes(self.jobs_host)), dtype=torch.uint8).to(dev)
+        self.init_weights()
+        base.adapter = self
+        if dev.type == "cuda":
+            self.merge()
+
+    # ------------------------------------------------------------------ parameters
+    def init_weights(self):
+        """A: Kaiming-uniform (a = sqrt(5): U(-1/sqrt(K), 1/sqrt(K))) drawn on the host from cfg.seed in leaf order; B: zero."""
+        g = torch.Generator().manual_seed(int(self.cfg.seed))
+        tree = {}
+        for p in self.paths:
+            a, b = self.adapted[p]
+            K, r = self.store.leaves[a].shape
+            tree[a] = (torch.rand(K, r, generator=g) * 2 - 1) / math.sqrt(K)
+            tree[b] = torch.zeros(self.store.leaves[b].shape)
+        self.store.load(tree)
+
+    def scratch_offset(self, a, b):
+        """The scratch element of master element a; [a, b) must lie inside one run of scratch_runs."""
+        i = bisect.bisect_right(self._run_starts, a) - 1
+        if i < 0 or a > b or b > self.runs[i][1]:
+            raise _lib.SdtError(f"LoRA: gradient range [{a}, {b}) lies outside the runs the adapter's scratch holds")
+        start, _, base = self.runs[i]
+        return base + a - start
+
+    def scratch_view(self, a, b):
+        """bf16 view of the dW scratch for master elements [a, b) (ops: the weight-gradient destination of an adapted leaf / group)."""
+        o = self.scratch_offset(a, b)
+        return self.scratch[o: o + b - a]
+
+    def takes(self, wpaths):
+        return any(p in self.adapted for p in wpaths)
+
+    # ------------------------------------------------------------------ launches
+    def _stream(self):
+        return torch.cuda.current_stream().cuda_stream
+
+    def merge(self, source=None):
+        """w[leaf] = bf16(W0 + s * A @ B) for every adapted leaf (one launch), A / B from the adapter store's master or its EMA.
+        The choice sticks: source=None (ParamStore.prepare, so StableDiffusionPipeline.generate) merges what was merged last; train_step
+        merges "master"."""
+        source = self.source if source is None else source
+        if source not in ("master", "ema"):
+            raise ValueError(f"merge: source must be 'master' or 'ema', not {source!r}")
+        ab = self.store.master if source == "master" else self.store.ema
+        if ab is None:
+            raise ValueError("merge(source='ema'): the adapter store keeps no EMA")
+        self.source = source
+        _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.jobs_host,
+                  self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
+
+    def project(self):
+        """dA, dB of every adapted leaf from the dW scratch into the adapter store's gradient (one launch; written, not accumulated)."""
+        from . import ops
+        _lib.call("sdt_lora_project", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), self.jobs_host,
+                  self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
+        for p in self.paths:
+            ops._ready(self.store, *self.adapted[p])
+
+    def folded(self, source="master"):
+        """{path: fp32 tensor} of the base with the adapter folded in (W0 + s * A @ B by the merge kernel's fp32 output: its bf16
+        rounding is the training-time mirror bit for bit) - what save_model writes as an ordinary checkpoint."""
+        ab = self.store.master if source == "master" else self.store.ema
+        if ab is None:
+            raise ValueError("folded(source='ema'): the adapter store keeps no EMA")
+        buf = self.base.master.clone()
+        _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), self.jobs_host,
+                  self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
+        return {p: buf[lf.offset: lf.offset + lf.numel].view(lf.shape) for p, lf in self.base.leaves.items()}
+
+    # ------------------------------------------------------------------ adapter file
+    def _meta(self):
+        return dict(rank=int(self.cfg.rank), alpha=float(self.cfg.alpha), targets=list(self.cfg.targets),
+                    base_shapes={p: list(self.base.leaves[p].shape) for p in self.paths})
+
+    def save(self, path, which="master"):
+        """One .npz: the A / B leaves (fp32) and __meta__ (JSON: rank, alpha, targets, the adapted base kernels' shapes)."""
+        tree = self.store.export_host(which)
+        with open(path, "wb") as f:
+            np.savez(f, __meta__=np.frombuffer(json.dumps(self._meta()).encode(), dtype=np.uint8), **{p: np.asarray(v) for p, v in tree.items()})
+
+    def load(self, path):
+        """Inverse of save().  ValueError naming the mismatch for a file of another rank, another alpha, other targets or other base shapes."""
+        with np.load(path) as z:
+            if "__meta__" not in z.files:
+                raise ValueError(f"{path}: not an adapter file (no __meta__)")
+            meta = json.loads(bytes(z["__meta__"]).decode())
+            mine = self._meta()
+            if meta["rank"] != mine["rank"]:
+                raise ValueError(f"{path}: adapter of rank {meta['rank']}, this adapter has rank {mine['rank']}")
+            if list(meta["targets"]) != mine["targets"]:
+                raise ValueError(f"{path}: adapter for targets {meta['targets']}, this adapter has targets {mine['targets']}")
+            if float(meta["alpha"]) != mine["alpha"]:
+                raise ValueError(f"{path}: adapter trained with alpha {meta['alpha']}, this adapter has alpha {mine['alpha']} (the factors "
+                                 "mean another delta under another scale: attach with the file's alpha)")
+            if meta["base_shapes"] != mine["base_shapes"]:
+                a, b = meta["base_shapes"], mine["base_shapes"]
+                bad = sorted(set(a) ^ set(b)) or [p for p in b if a[p] != b[p]]
+                raise ValueError(f"{path}: adapter for other base shapes ({len(bad)} kernels differ, first {bad[0]}: "
+                                 f"{a.get(bad[0])} in the file, {b.get(bad[0])} here)")
+            tree = {p: torch.from_numpy(np.array(z[p])) for p in self.store.order}
+        self.store.load(tree)
+        if self.base.device.type == "cuda":
+            self.merge()
+
+
+def attach(base_store, cfg, **store_kwargs):
+    """Hang a LoRA adapter on the frozen `base_store`.  store_kwargs configure the adapter's own ParamStore (quantise, quant_excluded,
+    wd_excluded, block_size, with_ema, optimizer, adam_betas).  ValueError: a trained base, a target that matches a convolution or a
+    padded kernel, no matching leaf, an invalid rank."""
+    if not isinstance(cfg, LoraConfig):
+        raise ValueError(f"attach: cfg must be a LoraConfig, not {type(cfg).__name__}")
+    return LoraAdapter(base_store, cfg, store_kwargs)

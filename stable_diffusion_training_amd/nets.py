@@ -373,6 +373,10 @@ def _context_projections(st, ctx):
     value = to_v(context)): one GEMM per channel width where those kernels are laid out back to back (unet_spec), the blocks
     reading their [k|v] as a column slice of its output; otherwise each block gets an alias of the context and projects it
     itself.  Returns {"<block>/attn2": _PackedKV or context alias}."""
+    if getattr(st, "adapter", None) is not None and not ctx.requires_grad:
+        # a frozen text encoder hands over a context without a tape: the to_k / to_v backward - the only producer of those adapters'
+        # weight gradients - would never run.  Anchor it here, as unet_forward anchors x
+        ctx = ctx.detach().requires_grad_(True)
     groups = {}
     for p in st.leaves:
         if p.endswith("/attn2/to_k/kernel"):
@@ -606,7 +610,8 @@ def _clip_encoder(st, cfg, input_ids, anchor, prefix, n_layers, tap=None):
     Bk, S = input_ids.shape
     d, heads, eps = cfg["hidden_size"], cfg["num_attention_heads"], cfg["layer_norm_eps"]
     if anchor is None:
-        anchor = torch.zeros(1, device=input_ids.device, requires_grad=st.trainable)
+        # (a frozen tower that carries a LoRA adapter still needs its backward: the adapted leaves' weight gradients come from it)
+        anchor = torch.zeros(1, device=input_ids.device, requires_grad=st.trainable or getattr(st, "adapter", None) is not None)
     x = ops.embedding(input_ids.contiguous(), st, prefix + "text_model/embeddings/token_embedding/embedding",
                       prefix + "text_model/embeddings/position_embedding/embedding", S, anchor)
     act = ops.quick_gelu if cfg["hidden_act"] == "quick_gelu" else ops.gelu_erf

@@ -430,6 +430,25 @@ def colsum(dy, db, M, N, ld):
     call("sdt_colsum_accumulate", dy.data_ptr(), db.data_ptr(), M, N, ld, ws.data_ptr(), ws.numel(), _stream())
 
 
+def _wgrad_dest(store, wpaths):
+    """Where the weight gradient of the Dense kernels `wpaths` (one leaf, or the leaves of a merged launch) goes: None when there is
+    none (a frozen store), else (view, with_bias, book) - view(a, b): the destination of master elements [a, b); with_bias: the biases'
+    gradients are produced too; book: the store the launch reports to (squared-norm slots, single-use check, reducer) or None.
+    A trained store answers with its own gradient buffers.  A frozen store with a LoRA adapter (lora.attach) answers with the adapter's
+    bf16 dW scratch for an adapted leaf - a group that spans adapted and other leaves takes the scratch whole, the extra gradients
+    are computed and ignored - without biases and without bookkeeping: adapter.project() reports the adapter's own leaves."""
+    if store.trainable:
+        return store.grad_view, True, store
+    ad = getattr(store, "adapter", None)
+    if ad is not None and ad.takes(wpaths):
+        return ad.scratch_view, False, None
+    return None
+
+
+def _leaf_grad(view, lf):
+    return view(lf.offset, lf.offset + lf.numel).view(lf.shape)
+
+
 # ----------------------------------------------------------------------------------------- Linear
 class _Linear(Function):
     """flax nn.Dense: y = x @ kernel (+ bias) (+ residual), kernel [in,out] (bf16 compute, fp32 accumulate)."""
@@ -476,9 +495,12 @@ class _Linear(Function):
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             gemm_nt(dy, W, dx, M, lf.Rp, lf.Cp, 1, lf.Cp, lf.Cp, 0)
-        if store.trainable:
-            wgrad_dense(x, dy, store.g(wpath), M, lf.Rp, lf.Cp, lf.R, lf.C, lf.Rp, lf.Cp,
-                        dbias=store.g(bpath) if bpath is not None else None, store=store, paths=(wpath, bpath))
+        dest = _wgrad_dest(store, (wpath,))
+        if dest is not None:
+            view, with_bias, book = dest
+            wgrad_dense(x, dy, _leaf_grad(view, lf), M, lf.Rp, lf.Cp, lf.R, lf.C, lf.Rp, lf.Cp,
+                        dbias=store.g(bpath) if (bpath is not None and with_bias) else None, store=book,
+                        paths=(wpath, bpath) if book is not None else ())
         return dx, (dy if has_res else None), None, None, None, None
 
 
@@ -528,14 +550,16 @@ class _LinearMulti(Function):
             dx = torch.empty_like(x)
             W = store.w[lf.w_off: lf.w_off + n * K * N]                  # n x [K][N]: reduction segment t = leaf t
             gemm_nt(dy, W, dx, M, K, N, n, n * N, N, K * N)
-        if store.trainable:
-            g0 = store.grad_view(lf.offset, lf.offset + n * K * N)
+        dest = _wgrad_dest(store, wpaths)
+        if dest is not None:
+            view, with_bias, book = dest
+            g0 = view(lf.offset, lf.offset + n * K * N)
             db = None
-            if bpaths is not None:
+            if bpaths is not None and with_bias:
                 b0 = store.leaves[bpaths[0]]
                 db = store.grad_view(b0.offset, b0.offset + n * N)
             wgrad_dense(x, dy, g0, M, K, n * N, K, n * N, K, n * N, dbias=db, n_seg=N, seg_stride=lfs[1].offset - lf.offset,
-                        store=store, paths=tuple(wpaths) + tuple(bpaths or ()))
+                        store=book, paths=(tuple(wpaths) + tuple(bpaths or ())) if book is not None else ())
         return dx, None, None, None
 
 
@@ -936,18 +960,22 @@ class _FeedForwardGeglu(Function):
         gemm_nt(dy, W2, df, M, l2.Rp, l2.Cp, 1, l2.Cp, l2.Cp, 0)
         dh = torch.empty_like(h)
         call("sdt_geglu_bwd", h.data_ptr(), df.data_ptr(), dh.data_ptr(), M, F, _stream())
-        if store.trainable:
-            b2 = n2 + "/bias" if store.has(n2 + "/bias") else None
-            wgrad_dense(f, dy, store.g(n2 + "/kernel"), M, l2.Rp, l2.Cp, l2.R, l2.C, l2.Rp, l2.Cp,
-                        dbias=store.g(b2) if b2 is not None else None, store=store, paths=(n2 + "/kernel", b2))
+        dest = _wgrad_dest(store, (n2 + "/kernel",))
+        if dest is not None:
+            view, with_bias, book = dest
+            b2 = n2 + "/bias" if (with_bias and store.has(n2 + "/bias")) else None
+            wgrad_dense(f, dy, _leaf_grad(view, l2), M, l2.Rp, l2.Cp, l2.R, l2.C, l2.Rp, l2.Cp,
+                        dbias=store.g(b2) if b2 is not None else None, store=book, paths=(n2 + "/kernel", b2) if book is not None else ())
         dx = None
         if ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)
             gemm_nt(dh, W1, dx, M, l1.Rp, l1.Cp, 1, l1.Cp, l1.Cp, 0)
-        if store.trainable:
-            b1 = n1 + "/bias" if store.has(n1 + "/bias") else None
-            wgrad_dense(x, dh, store.g(n1 + "/kernel"), M, l1.Rp, l1.Cp, l1.R, l1.C, l1.Rp, l1.Cp,
-                        dbias=store.g(b1) if b1 is not None else None, store=store, paths=(n1 + "/kernel", b1))
+        dest = _wgrad_dest(store, (n1 + "/kernel",))
+        if dest is not None:
+            view, with_bias, book = dest
+            b1 = n1 + "/bias" if (with_bias and store.has(n1 + "/bias")) else None
+            wgrad_dense(x, dh, _leaf_grad(view, l1), M, l1.Rp, l1.Cp, l1.R, l1.C, l1.Rp, l1.Cp,
+                        dbias=store.g(b1) if b1 is not None else None, store=book, paths=(n1 + "/kernel", b1) if book is not None else ())
         return dx, (dy if has_res else None), None, None, None
 
 

@@ -223,6 +223,7 @@ class ParamStore:
         self.schedule = None       # (lr_schedule.LRSchedule, lr_schedule.EMASchedule) installed, or None: by-value scalars
         self._sched = None         # dict(step, lr_tab, ema_tab, cur) device tensors; kept for the store's life once allocated
         self._captured = False     # an optimizer step of this store has been captured into a graph (tables must not move)
+        self.adapter = None        # lora.attach: a frozen store's low-rank adapter; prepare() then ends with its merge into W
 
     # ------------------------------------------------------------------ views
     def p(self, path):
@@ -405,6 +406,8 @@ class ParamStore:
                 # sharded optimizer: the all-gathered bf16 mirror is current on every rank, the fp32 master only on the owner of
                 # the slice; the padded copy is the same bf16 values re-pitched (pad lanes stay zero)
                 self.w[lf.w_off: lf.w_off + lf.batch * lf.Rp * lf.Cp].view(lf.batch, lf.Rp, lf.Cp)[:, :lf.R, :lf.C].copy_(mirror)
+        if self.adapter is not None:
+            self.adapter.merge()  # W of the adapted leaves = bf16(W0 + s * A @ B) (lora.py)
 
     def wmat(self, path):
         """(W view [batch,Rp,Cp], leaf) of a kernel leaf: the bf16 compute copy, Flax layout."""

@@ -15,7 +15,7 @@ from typing import Any, Callable
 import numpy as np
 import torch
 
-from . import _lib, nets, ops, trace
+from . import _lib, lora as lora_mod, nets, ops, trace
 from .checkpoint import load_models, load_training_state, save_model, save_training_state  # noqa: F401  (reference names)
 from .lr_schedule import resolve as resolve_schedule
 from .params import EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
@@ -83,15 +83,26 @@ class FrozenModel:
 
 @dataclass
 class TrainState:
-    """Stand-in for flax TrainState (training_utils.py:383-387): apply_fn + params + optimizer, all in `store`."""
+    """Stand-in for flax TrainState (training_utils.py:383-387): apply_fn + params + optimizer, all in `store`.
+    LoRA (lora=): `store` stays the network's - frozen - weight store, `adapter` is the lora.LoraAdapter whose own store holds the trained
+    leaves and takes the optimizer step (None with an empty hyper: a frozen text encoder that only runs its forward)."""
     apply_fn: Callable
     store: ParamStore
     config: dict
     hyper: dict = field(default_factory=dict)
+    adapter: Any = None
+
+    @property
+    def opt_store(self):
+        """The store that takes the optimizer step: the weight store itself, the adapter's store, or None (frozen, no adapter)."""
+        if self.adapter is not None:
+            return self.adapter.store
+        return self.store if self.store.trainable else None
 
     @property
     def step(self):
-        return self.store.count
+        st = self.opt_store
+        return self.store.count if st is None else st.count
 
     @property
     def params(self):
@@ -103,15 +114,31 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                                  excluded_layer_pattern_from_weight_decay=(), excluded_layer_from_quantization=(),
                                  lion_8bit_block_size=None, quantize_unet_state=False, quantize_text_encoder_state=False,
                                  with_unet_ema=False, with_text_encoder_ema=False, device="cuda", lr_scheduler="constant",
-                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0, optimizer="lion"):
+                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0, optimizer="lion", lora=None):
     """training_utils.py:281-427.  lr = learning_rate / adam_to_lion_scale_factor, wd = 1e-2 * scale, b1=.9, b2=.99,
     chain(clip_by_global_norm(1), lion_8bit | lion).  Builds the flat HBM stores and loads the weights.
     lr_scheduler / lr_schedule / ema_schedule / ema_rate: the per-step schedules of lr_schedule.resolve, installed in each trained store
     (ParamStore.set_schedule; the lr schedule scales each store's own rate).  "constant" without an EMA schedule installs nothing.
     optimizer: "lion" (the reference's), "adamw", or dict(name=, b1=, b2=, eps=, weight_decay=).  AdamW (8-bit block-quantised or fp32
     moments by the same quantize_* switches) takes the learning rates AS GIVEN - an Adam recipe needs no translation, so
-    adam_to_lion_scale_factor does not apply - with wd=1e-2, b1=.9, b2=.999, eps=1e-8 unless the dict says otherwise."""
+    adam_to_lion_scale_factor does not apply - with wd=1e-2, b1=.9, b2=.999, eps=1e-8 unless the dict says otherwise.
+    lora: None, or dict(unet=lora.LoraConfig, text_encoder=lora.LoraConfig | None | "frozen").  The base stores are then built frozen
+    (trainable=False) and loaded once; every setting above (quantisation, decay and quantisation exclusions, EMA, optimizer, rates and
+    schedules) configures the ADAPTER's store of that model instead (TrainState.adapter.store), which is the one that steps.  A text
+    encoder without a LoraConfig only runs its forward.  Mixed modes - one model fully fine-tuned, the other adapted - are refused."""
     out = {"unet_state": None, "text_encoder_state": None}
+    if lora is not None:
+        if not isinstance(lora, dict) or set(lora) - {"unet", "text_encoder"}:
+            raise ValueError(f"lora: None or dict(unet=LoraConfig, text_encoder=LoraConfig | None | 'frozen'), not {lora!r}")
+        te_l = lora.get("text_encoder")
+        te_l = None if te_l == "frozen" else te_l
+        if not isinstance(lora.get("unet"), lora_mod.LoraConfig) or not (te_l is None or isinstance(te_l, lora_mod.LoraConfig)):
+            raise ValueError("lora: unet must be a LoraConfig and text_encoder a LoraConfig, None or 'frozen' - a fully fine-tuned UNet "
+                             "beside an adapted text encoder (or the reverse) is not supported")
+        if not (train_unet and train_text_encoder):
+            raise ValueError("lora: needs both states (train_unet and train_text_encoder); the text encoder is frozen by "
+                             "text_encoder='frozen'")
+        lora = {"unet": lora["unet"], "text_encoder": te_l}
     opt = {"name": optimizer} if isinstance(optimizer, str) else dict(optimizer)
     unknown = set(opt) - {"name", "b1", "b2", "eps", "weight_decay"}
     if unknown or opt.get("name") not in ("lion", "adamw"):
@@ -120,7 +147,7 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
         raise ValueError("optimizer: Lion's hyper-parameters are the reference's (adam_to_lion_scale_factor); the dict form is AdamW's")
     adamw = opt["name"] == "adamw"
 
-    def make(spec, weights, cfg, fn, lr, quant, ema):
+    def make(spec, weights, cfg, fn, lr, quant, ema, which):
         if adamw:
             hyper = dict(lr=lr, wd=opt.get("weight_decay", 1e-2), b1=opt.get("b1", 0.9), b2=opt.get("b2", 0.999),
                          eps=opt.get("eps", 1e-8), max_norm=1.0)
@@ -128,6 +155,17 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
             hyper = dict(lr=lr / adam_to_lion_scale_factor, wd=1e-2 * adam_to_lion_scale_factor, b1=0.9, b2=0.99, max_norm=1.0)
         okw = dict(optimizer="adamw", adam_betas=(hyper["b1"], hyper["b2"])) if adamw else {}
         sched = resolve_schedule(lr_scheduler, hyper["lr"], ema_rate, lr_schedule=lr_schedule, ema_schedule=ema_schedule)
+        if lora is not None:
+            base = ParamStore(spec, device=device, trainable=False)
+            base.load(weights)
+            if lora[which] is None:
+                return TrainState(fn, base, cfg, {})
+            adapter = lora_mod.attach(base, lora[which], quantise=quant, quant_excluded=tuple(excluded_layer_from_quantization),
+                                      wd_excluded=tuple(excluded_layer_pattern_from_weight_decay),
+                                      block_size=lion_8bit_block_size or 16, with_ema=ema, **okw)
+            if sched is not None:
+                adapter.store.set_schedule(lr=sched[0], ema=sched[1])
+            return TrainState(fn, base, cfg, hyper, adapter)
         store = ParamStore(spec, device=device, quantise=quant, quant_excluded=tuple(excluded_layer_from_quantization),
                            wd_excluded=tuple(excluded_layer_pattern_from_weight_decay),
                            block_size=lion_8bit_block_size or 16, with_ema=ema, **okw)
@@ -139,18 +177,18 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
     if train_unet:
         m = models["unet"]
         out["unet_state"] = make(nets.unet_spec(m["config"]), m["unet_params"], m["config"], nets.unet_forward,
-                                 u_net_learning_rate, quantize_unet_state, with_unet_ema)
+                                 u_net_learning_rate, quantize_unet_state, with_unet_ema, "unet")
     if train_text_encoder:
         m = models["text_encoder"]
         out["text_encoder_state"] = make(nets.clip_text_spec(m["config"]), m["text_encoder_params"], m["config"],
                                          nets.clip_text_forward, text_encoder_learning_rate,
-                                         quantize_text_encoder_state, with_text_encoder_ema)
+                                         quantize_text_encoder_state, with_text_encoder_ema, "text_encoder")
         out["text_encoder_state"].store.mark_unused(nets.unused_text_leaves(m["config"]))
     return out
 
 
 def on_device_model_training_state(training_config: TrainingConfig, models=None, device="cuda", *, lr_schedule=None,
-                                   ema_schedule=None, optimizer="lion"):
+                                   ema_schedule=None, optimizer="lion", lora=None):
     """training_utils.py:430-501.  `models`: load_models' result - host weight trees + configs
     ({"unet": {"unet_params", "config"}, "vae": {"vae_params", "config"}, "text_encoder": {...}}); None reads the
     diffusers directory at training_config.model_path (checkpoint.load_models).  Note the reference passes NEITHER learning
@@ -159,7 +197,10 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
     lr_schedule=dict(num_warmup_steps=, num_training_steps=, num_cycles=, power=, lr_end=), and
     ema_schedule=dict(kind="warmup", update_after_step=, use_ema_warmup=, inv_gamma=, power=, min_decay=) warms the EMA rate up to
     training_config.ema_rate (lr_schedule.resolve; ValueError for a name without the counts it needs).
-    optimizer: create_lion_optimizer_states' (TrainingConfig has no field for it)."""
+    optimizer: create_lion_optimizer_states' (TrainingConfig has no field for it).
+    lora: create_lion_optimizer_states' - dict(unet=lora.LoraConfig(rank, alpha), text_encoder=LoraConfig | None | "frozen") trains low-rank
+    adapters on frozen base weights.  The tuple keeps its shape: the states' `store` are the frozen weight stores, `adapter` the adapters,
+    and the EMA views wrap the adapters' stores (None for a text encoder without an adapter)."""
     _lib.require_device()
     if models is None:
         models = load_models(training_config)
@@ -172,7 +213,7 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
         quantize_text_encoder_state=training_config.quantize_text_encoder_state,
         with_unet_ema=training_config.accumulate_unet_ema, with_text_encoder_ema=training_config.accumulate_text_encoder_ema,
         device=device, lr_scheduler=training_config.lr_scheduler, lr_schedule=lr_schedule, ema_schedule=ema_schedule,
-        ema_rate=training_config.ema_rate, optimizer=optimizer)
+        ema_rate=training_config.ema_rate, optimizer=optimizer, lora=lora)
     vae_cfg = models["vae"]["config"]
     vae_store = ParamStore(nets.vae_encoder_spec(vae_cfg), device=device, trainable=False)
     vae_store.load(models["vae"]["vae_params"])
@@ -185,8 +226,8 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
                           num_train_timesteps=1000, prediction_type=training_config.prediction_type)  # :223-230
     frozen_sched = FrozenModel(call=sched, params=sched.create_state(device))
     unet_state, te_state = states["unet_state"], states["text_encoder_state"]
-    unet_ema = EmaView(unet_state.store) if training_config.accumulate_unet_ema else None
-    te_ema = EmaView(te_state.store) if training_config.accumulate_text_encoder_ema else None
+    unet_ema = EmaView(unet_state.opt_store) if training_config.accumulate_unet_ema else None
+    te_ema = EmaView(te_state.opt_store) if (training_config.accumulate_text_encoder_ema and te_state.opt_store is not None) else None
     model_object_dict = {"unet": unet_state.config, "vae": vae_cfg, "text_encoder": te_state.config, "schedulers": sched}
     return unet_state, te_state, unet_ema, te_ema, frozen_vae, frozen_sched, model_object_dict
 
@@ -292,6 +333,11 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     the forward and backward on its slice of `batch` and `rand` (without rand=, its draws come from train_rng in the order a plain
     step of that size takes them), and the optimizer steps once on the fp32 mean - the step over the whole batch, with the
     activation memory of one micro-batch.  metrics["loss"] is the mean of the micro-batch losses.  K = 1 is the plain step.
+    LoRA states (TrainState.adapter): the step merges the adapters into the bf16 mirrors instead of preparing the stores, runs the same
+    forward and backward - the weight-gradient kernels write dW of the adapted leaves into the adapters' scratch, every other weight
+    gradient is skipped - projects dW onto the factors (adapter.project) and steps the adapters' stores; a text encoder without an
+    adapter only runs its forward.  A reducer is refused (ValueError): the data-parallel exchange would have to be built over the adapter
+    stores.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
     text_time = unet_state.config.get("addition_embed_type") == "text_time"
     sdxl = text_time and nets.sdxl_conditioning(text_encoder_state.config)
@@ -299,6 +345,17 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         raise ValueError("the text encoder is in SDXL mode and computes the pooled text embedding itself: a batch in that mode must "
                          "not carry text_embeds")
     us, ts = unet_state.store, text_encoder_state.store
+    adapters = [a for a in (getattr(unet_state, "adapter", None), getattr(text_encoder_state, "adapter", None)) if a is not None]
+    lora = bool(adapters)
+    if lora:
+        if us.trainable or ts.trainable or unet_state.adapter is None:
+            raise ValueError("LoRA: mixed modes are not supported - the UNet carries the adapter and both base stores are frozen "
+                             "(a text encoder trains through an adapter of its own or not at all)")
+        if reducer is not None:
+            raise ValueError("LoRA: data-parallel training of adapter states is not supported yet - the follow-up is to build the "
+                             "GradReducer over the adapter stores (TrainState.adapter.store) instead of the frozen weight stores")
+    # the stores that are zeroed, accumulated into and stepped: the weight stores themselves, or the adapters' own
+    opt_stores = [a.store for a in adapters] if lora else [us, ts]
     sched, sched_state = frozen_noise_scheduler_state.call, frozen_noise_scheduler_state.params
     dev = us.device
     cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev)
@@ -354,11 +411,14 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         if k == 0 and reducer is not None:
             reducer.wait_gathered()
         with trace.phase("prepare_weights"):
-            if k == 0:
+            if k == 0 and lora:
+                for ad in adapters:  # the frozen mirrors stay as the load left them: only the adapted leaves are rewritten
+                    ad.merge("master")
+            elif k == 0:
                 us.prepare()
                 ts.prepare()
-            us.zero_grad()
-            ts.zero_grad()
+            for st in opt_stores:
+                st.zero_grad()
 
         # noise, timesteps                                            (training_utils.py:590-624)
         noise = rnd.get("noise")
@@ -455,6 +515,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             ops.sq_begin(ts)
         with trace.phase("backward_unet_text"), ops.wgrad_grouping():  # Dense weight gradients are issued a dozen per launch
             pred.backward(dpred)
+        for ad in adapters:  # (the grouped weight gradients have been flushed: dW of every adapted leaf is in the scratch)
+            ad.project()
         sq_u = ops.sq_end(us) if fused_norm else None
         sq_t = ops.sq_end(ts) if fused_norm else None
         return loss, sq_u, sq_t
@@ -462,7 +524,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     if K == 1:
         # one process: the norm clip_by_global_norm needs is that of the gradients as the weight-gradient kernels write them - they leave
         # its partial sums behind (ops.sq_begin / sq_end), and the 4-byte-per-parameter pass over the finished buffer is not needed
-        loss, sq_u, sq_t = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda")
+        loss, sq_u, sq_t = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora)
         grad_source = "grad"
         # data-parallel mean of the gradients (implicit all-reduce under GSPMD in the reference)
         if reducer is not None:
@@ -479,7 +541,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             losses.append(forward_backward(k, False)[0])
             mode = "init" if k == 0 else ("finish" if k == K - 1 and not exchange else "add")
             with trace.phase("grad_accumulate"):
-                for st in (us, ts):
+                for st in opt_stores:
                     st.accumulate(mode, 1.0 / K if mode == "finish" else 1.0, norm=mode == "finish")
         loss = torch.cat(losses).mean(0, keepdim=True)
         sq_u = sq_t = None
@@ -489,12 +551,20 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                 reducer.exchange_accumulated()
                 loss = reducer.mean_scalar(loss)
             with trace.phase("grad_accumulate"):
-                for st in (us, ts):
+                for st in opt_stores:
                     st.accumulate("scale", 1.0 / K, norm=True)
 
     # clip -> Lion(8-bit) -> decay -> -lr -> apply -> EMA         (training_utils.py:732-746)
     ur = ema_rate if (ema_rate and unet_ema_params is not None) else 0.0
     tr = ema_rate if (ema_rate and text_encoder_ema_params is not None) else 0.0
+    if lora:
+        with trace.phase("optimizer_clip_lion8_ema"):  # the norm by the ordinary pass over the adapters' few MB
+            for state, rate in ((unet_state, ur), (text_encoder_state, tr)):
+                if state.adapter is not None:
+                    state.adapter.store.optimizer_step(ema_rate=rate, grad_source=grad_source, **state.hyper)
+        ops.gn_arena_end(dev)
+        return (unet_state, text_encoder_state, unet_ema_params if ur else None, text_encoder_ema_params if tr else None,
+                {"loss": loss[0]}, train_rng)
     with trace.phase("optimizer_clip_lion8_ema"):
         us.optimizer_step(ema_rate=ur, shard=None if reducer is None else reducer.shard_pieces(us), sq_partials=sq_u,
                           grad_source=grad_source, **unet_state.hyper)
@@ -512,6 +582,13 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
 # Other threads keep making HIP calls while a step is captured (RCCL's watchdog polls events, loaders pin memory): only the
 # capturing thread's own unsafe calls should fail the capture.
 _CAPTURE_MODE = "thread_local"
+
+
+def _stepping_stores(*states):
+    """The stores whose optimizer steps a train_step of these states takes (TrainState.opt_store): their host step counts follow the
+    replays of a captured step."""
+    stores = [getattr(st, "opt_store", st.store) for st in states]
+    return [st for st in stores if st is not None]
 
 
 class _GraphedStep:
@@ -552,8 +629,8 @@ class _GraphedStep:
             if self.disabled:
                 return
         # capturing executed nothing on the device, but the host-side step counters moved: undo, replay() re-applies
-        us.store.count -= 1
-        ts.store.count -= 1
+        for st in _stepping_stores(us, ts):
+            st.count -= 1
         self.graph = g
 
     def _capture_split(self, g, us, ts, ue, te, rng, vae, sched):
@@ -636,8 +713,8 @@ class _GraphedStep:
                 # current only on the owners of the slices, so exports must raise until GradReducer.gather_state() (ParamStore._gather)
                 us.store.state_whole = False
                 ts.store.state_whole = False
-        us.store.count += 1
-        ts.store.count += 1
+        for st in _stepping_stores(us, ts):
+            st.count += 1
         o = self.out
         return o[0], o[1], o[2], o[3], {"loss": o[4]["loss"].clone()}, o[5]
 
