@@ -94,11 +94,14 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     dataloader._print_debug = bool(config_dict.get("DEBUG"))
 
     lora_cfg = None
+    if config_dict.get("lora_dora") and not config_dict.get("lora_rank"):
+        raise ValueError("lora_dora: DoRA is a LoRA adapter with a trained magnitude - give lora_rank (--lora RANK --dora)")
     if config_dict.get("lora_rank"):  # LoRA: rank-r adapters on the UNet's attention projections, frozen text encoder, alpha = rank
         if world > 1:
             raise ValueError("lora_rank: adapter training runs on one GPU (train_step refuses a reducer with adapter states)")
         r = int(config_dict["lora_rank"])
-        lora_cfg = dict(unet=lora.LoraConfig(r, float(config_dict.get("lora_alpha", r))), text_encoder="frozen")
+        lora_cfg = dict(unet=lora.LoraConfig(r, float(config_dict.get("lora_alpha", r)), dora=bool(config_dict.get("lora_dora", False))),
+                        text_encoder="frozen")
     train_rngs = torch.Generator(device=dev)
     train_rngs.manual_seed(config_dict["master_seed"] * 1009 + rank)  # different noise / timesteps on every shard
     (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers,
@@ -221,7 +224,11 @@ if __name__ == "__main__":
                     help="encode the run's chunks once into a latent cache under DIR, drop the VAE and train from the cache")
     ap.add_argument("--lora", metavar="RANK", type=int, default=None,
                     help="train rank-RANK LoRA adapters on the UNet's attention projections (frozen base and text encoder) instead of every weight")
+    ap.add_argument("--dora", action="store_true",
+                    help="with --lora: DoRA - also train a per-output-feature magnitude of every adapted kernel (weight-decomposed LoRA)")
     args = ap.parse_args()
+    if args.dora and args.lora is None:
+        ap.error("--dora needs --lora RANK")
     with open(args.config) as f:
         cfg = json.load(f)
     if args.micro_batches is not None:
@@ -230,6 +237,8 @@ if __name__ == "__main__":
         cfg["optimizer"] = args.optimizer
     if args.lora is not None:
         cfg["lora_rank"] = args.lora
+    if args.dora:
+        cfg["lora_dora"] = True
     if args.cache_latents is not None:
         cfg["cache_latents"] = args.cache_latents
     main(cfg)

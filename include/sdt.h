@@ -439,6 +439,52 @@ int sdt_lora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16,
 int sdt_lora_project(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
                      const void* jobs_device, int n, hipStream_t stream);
 
+/* ---- DoRA: weight-decomposed LoRA (Liu et al. 2024, arXiv:2402.09353), in weight space (DESIGN.md "DoRA") ----
+ * An adapted kernel carries a third trained leaf, the magnitude m [N] (one per output feature, in the adapter's store beside A and B).
+ * With v[k][n] = W0[k][n] + s * sum_q bf16(A[k][q]) * bf16(B[q][n]) exactly as sdt_lora_merge forms it (fp32 MFMA accumulation, one
+ * product rounding, one sum rounding):
+ *   q[n] = sum_k v[k][n]^2   fp32, each square rounded, one fixed order: every thread of the stripe's workgroup adds the rows it owns top
+ *                            to bottom, one thread adds the 32 partials of a column in row order; no atomics, one writer
+ *   c[n] = sqrt(q[n])        correctly rounded to fp32
+ *   g[n] = m[n] / c[n]       correctly rounded IEEE division; 0 when c[n] == 0 (a zero column gives zeros and a zero gradient, no NaN)
+ *   W'[k][n] = fl32(v * g)   into f32_dst, RNE_bf16 of that same value into w_bf16: the mirror is the RNE rounding of the folded
+ *                            checkpoint bit for bit, as for LoRA
+ * sqrt and the two divisions are evaluated in double and rounded once; with 53 >= 2 * 24 + 2 bits that second rounding cannot change
+ * the result, so c, g and dm are the correctly rounded fp32 values whatever the compiler makes of fp32 sqrt and '/'.
+ * Backward: THE NORM IS HELD CONSTANT (the paper's section 4.3; peft and kohya do the same) - the one place where the gradient
+ * written is deliberately not the gradient of the function that was evaluated: c is treated as a constant of the step.
+ * With G = dW' (bf16, in the scratch) and P[q][n] = sum_k bf16(A[k][q]) * G[k][n] (the fp32 accumulator of the dB stripe):
+ *   dB[q][n] = fl(fl(s * P[q][n]) * g[n])
+ *   dA[k][q] = s * sum_n G[k][n] * bf16(fl32(bf16(B[q][n]) * g[n]))     the scale goes onto the B fragment as it is loaded: one
+ *                                                                       more bf16 rounding point
+ *   u[n]     = sum_k G[k][n] * W0[k][n] + s * sum_q bf16(B[q][n]) * P[q][n]     (= sum_k G v without forming v again)
+ *   dm[n]    = u[n] / c[n], 0 when c[n] == 0
+ * all WRITTEN (not accumulated) as fp32, one writer per element, no atomics.
+ * The calls take the SdtLoraJob table (unchanged, 96 bytes) and a parallel table of n SdtDoraJob; both host copies are checked
+ * (sdt_lora_merge's checks; N equal in both tables; DoRA offsets non-negative multiples of 8; stripe0_merge the running count of
+ * ceil(N/64) column stripes).  stat_base: an fp32 buffer the adapter owns; leaf i holds c at stat_off and g at stat_off + N. */
+typedef struct SdtDoraJob {
+  int64_t m_off;   /* m [N] in ab_base (merge) / m_base (init) */
+  int64_t gm_off;  /* dm [N] in grad_base */
+  int64_t stat_off; /* c [N], then g [N], in stat_base */
+  int32_t N;       /* the job's N again: a table built for other leaves is refused */
+  int32_t stripe0_merge; /* running count of the merge's 64-column stripes */
+} SdtDoraJob;
+int sdt_dora_job_size(void);
+/* One workgroup per 64-column stripe walks K twice: the column sums of squares, then W' (the second read of W0 mostly hits L2).
+ * Publishes c and g; destinations as sdt_lora_merge. */
+int sdt_dora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, float* stat_base,
+                   const SdtLoraJob* jobs_host, const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n,
+                   hipStream_t stream);
+/* m[n] = c[n] by the merge's own reduction (m_base may be ab_base): a merge that follows finds g == 1.0f in every column. */
+int sdt_dora_init_magnitude(const float* w0_base, const float* ab_base, float* m_base, const SdtLoraJob* jobs_host,
+                            const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n, hipStream_t stream);
+/* dA, dB, dm as above from the c and g the last sdt_dora_merge published.  Beyond sdt_lora_project the dB stripes read W0 where they
+ * stage dW: 4 B more per adapted parameter. */
+int sdt_dora_project(const uint16_t* dw_base, const float* w0_base, const float* ab_base, float* grad_base, const float* stat_base,
+                     const SdtLoraJob* jobs_host, const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n,
+                     hipStream_t stream);
+
 /* ---- test hooks (not for the training path) ----
  * Output channels per tile of the 3x3 halo convolution inside sdt_gemm_nt_bf16: 64 (the default) or 128 (the reference of the
  * bitwise parity test).  Process-wide, not thread-safe; launches already enqueued keep the width they were planned with.

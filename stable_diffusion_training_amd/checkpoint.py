@@ -403,7 +403,7 @@ def _stepping_store(st):
 
 
 def _lora_meta(ad):
-    return f"rank={ad.cfg.rank};alpha={float(ad.cfg.alpha)!r};targets={','.join(ad.cfg.targets)}"
+    return f"rank={ad.cfg.rank};alpha={float(ad.cfg.alpha)!r};targets={','.join(ad.cfg.targets)}" + (";dora=1" if ad.cfg.dora else "")
 
 
 def save_training_state(path, unet_state, text_encoder_state, train_rng=None, rng_states=None):

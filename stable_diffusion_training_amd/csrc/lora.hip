@@ -12,13 +12,21 @@ namespace {
 
 constexpr int LT = 64;  // merge: output tile; project: rows of a dA stripe / columns of a dB stripe
 
-__device__ __forceinline__ const SdtLoraJob& find_job(const SdtLoraJob* jobs, int n, int tile, bool project) {
+// index of the last of n jobs whose first tile - first(i), a running count - is <= tile
+template <class First>
+__device__ __forceinline__ int find_index(int n, int tile, First first) {
   int lo = 0, hi = n - 1;
-  while (lo < hi) {  // last job whose first tile is <= tile
+  while (lo < hi) {
     const int mid = (lo + hi + 1) >> 1;
-    if ((project ? jobs[mid].tile0_project : jobs[mid].tile0_merge) <= tile) lo = mid; else hi = mid - 1;
+    if (first(mid) <= tile) lo = mid; else hi = mid - 1;
   }
-  return jobs[lo];
+  return lo;
+}
+__device__ __forceinline__ int find_job_index(const SdtLoraJob* jobs, int n, int tile, bool project) {
+  return find_index(n, tile, [=](int i) { return project ? jobs[i].tile0_project : jobs[i].tile0_merge; });
+}
+__device__ __forceinline__ const SdtLoraJob& find_job(const SdtLoraJob* jobs, int n, int tile, bool project) {
+  return jobs[find_job_index(jobs, n, tile, project)];
 }
 
 // 8 consecutive float32 at p (16-byte aligned) rounded to a bf16 fragment; ok = false gives zero lanes
@@ -49,17 +57,10 @@ __device__ __forceinline__ bf16x8_t frag_from_f32_strided(const float* p, long s
 }
 
 // ---- merge: one 64 x 64 tile of one leaf per workgroup; wave w owns rows 16w .. 16w+15 and the four 16-column blocks ---------
-__global__ void __launch_bounds__(256) lora_merge_kernel(const float* __restrict__ w0_base, const float* __restrict__ ab_base,
-                                                         bf16_t* __restrict__ w_dst, float* __restrict__ f_dst,
-                                                         const SdtLoraJob* __restrict__ jobs, int njobs) {
-  __shared__ float tile[LT][LT + 4];
-  const SdtLoraJob d = find_job(jobs, njobs, blockIdx.x, false);
-  const int tl = blockIdx.x - d.tile0_merge;
-  const int tc = (d.N + LT - 1) / LT;
-  const int r0 = (tl / tc) * LT, c0 = (tl % tc) * LT;
+// bf16(A) * bf16(B) of the tile at (r0, c0), unscaled fp32 accumulators, into `tile` (the caller synchronises before reading it)
+__device__ __forceinline__ void ab_tile(const SdtLoraJob& d, const float* __restrict__ A, const float* __restrict__ B, int r0, int c0,
+                                        float (*tile)[LT + 4]) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
-  const float* A = ab_base + d.a_off;  // [K][r]
-  const float* B = ab_base + d.b_off;  // [r][N]
   const int r = d.r;
   f32x4_t acc[4];
 #pragma unroll
@@ -80,35 +81,200 @@ __global__ void __launch_bounds__(256) lora_merge_kernel(const float* __restrict
   for (int c = 0; c < 4; ++c)
 #pragma unroll
     for (int i = 0; i < 4; ++i) tile[16 * wave + 4 * lq + i][16 * c + l15] = acc[c][i];
-  __syncthreads();
+}
+
+// v[0..7] = W0 + s * tile for run g (0..511) of the tile at (r0, c0): row g >> 3, 8 columns from 8 (g & 7); e = the run's element
+// in the leaf.  False when the run lies outside the leaf (N is a multiple of 8: a run is whole or absent).
+__device__ __forceinline__ bool merged_run(const SdtLoraJob& d, const float* __restrict__ w0_base, const float (*tile)[LT + 4], int g,
+                                           int r0, int c0, float* v, long& e) {
+  const int row = r0 + (g >> 3), col = c0 + (g & 7) * 8;
+  if (row >= d.K || col >= d.N) return false;
+  e = (long)row * d.N + col;
+  const float* src = w0_base + d.w0_off + e;
+  const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
+  const float* t = &tile[g >> 3][(g & 7) * 8];
   const float s = d.scale;
+  v[0] = x0.x + s * t[0]; v[1] = x0.y + s * t[1]; v[2] = x0.z + s * t[2]; v[3] = x0.w + s * t[3];
+  v[4] = x1.x + s * t[4]; v[5] = x1.y + s * t[5]; v[6] = x1.z + s * t[6]; v[7] = x1.w + s * t[7];
+  return true;
+}
+
+__device__ __forceinline__ void store_run(const SdtLoraJob& d, bf16_t* __restrict__ w_dst, float* __restrict__ f_dst, long e, const float* v) {
+  if (w_dst) *reinterpret_cast<uint4*>(w_dst + d.w_off + e) = pack8(v);  // 16-byte bf16 store
+  if (f_dst) {
+    float* o = f_dst + d.f_off + e;
+    *reinterpret_cast<float4*>(o) = float4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<float4*>(o + 4) = float4{v[4], v[5], v[6], v[7]};
+  }
+}
+
+__global__ void __launch_bounds__(256) lora_merge_kernel(const float* __restrict__ w0_base, const float* __restrict__ ab_base,
+                                                         bf16_t* __restrict__ w_dst, float* __restrict__ f_dst,
+                                                         const SdtLoraJob* __restrict__ jobs, int njobs) {
+  __shared__ float tile[LT][LT + 4];
+  const SdtLoraJob d = find_job(jobs, njobs, blockIdx.x, false);
+  const int tl = blockIdx.x - d.tile0_merge;
+  const int tc = (d.N + LT - 1) / LT;
+  const int r0 = (tl / tc) * LT, c0 = (tl % tc) * LT;
+  ab_tile(d, ab_base + d.a_off, ab_base + d.b_off, r0, c0, tile);
+  __syncthreads();
 #pragma unroll
-  for (int it = 0; it < 2; ++it) {  // 512 runs of 8 columns: 16-byte bf16 stores
-    const int g = threadIdx.x + 256 * it;
-    const int row = r0 + (g >> 3), col = c0 + (g & 7) * 8;
-    if (row >= d.K || col >= d.N) continue;  // N is a multiple of 8: a run is whole or absent
-    const long e = (long)row * d.N + col;
-    const float* src = w0_base + d.w0_off + e;
-    const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
-    const float* t = &tile[g >> 3][(g & 7) * 8];
+  for (int it = 0; it < 2; ++it) {  // 512 runs of 8 columns
     float v[8];
-    v[0] = x0.x + s * t[0]; v[1] = x0.y + s * t[1]; v[2] = x0.z + s * t[2]; v[3] = x0.w + s * t[3];
-    v[4] = x1.x + s * t[4]; v[5] = x1.y + s * t[5]; v[6] = x1.z + s * t[6]; v[7] = x1.w + s * t[7];
-    if (w_dst) *reinterpret_cast<uint4*>(w_dst + d.w_off + e) = pack8(v);
-    if (f_dst) {
-      float* o = f_dst + d.f_off + e;
-      *reinterpret_cast<float4*>(o) = float4{v[0], v[1], v[2], v[3]};
-      *reinterpret_cast<float4*>(o + 4) = float4{v[4], v[5], v[6], v[7]};
+    long e;
+    if (merged_run(d, w0_base, tile, threadIdx.x + 256 * it, r0, c0, v, e)) store_run(d, w_dst, f_dst, e, v);
+  }
+}
+
+// ---- DoRA merge (include/sdt.h "DoRA"): one 64-column stripe of one leaf per workgroup.  First walk over K: v tiles as above, every
+// thread sums v^2 of its 8 columns over the rows it owns (row t >> 3 and 32 below it, of every 64-row block, top to bottom), the 32
+// partials of a column are added in row order by one thread: one fixed order, no atomics.  c = sqrt(q) and g = m / c are formed in
+// double and rounded once (53 >= 2 * 24 + 2 bits: the double rounding cannot change the result of either operation, so both are the
+// correctly rounded fp32 values).  INIT: c is written into m and nothing else happens.  Second walk: the same v tiles, times g.
+template <bool INIT>
+__global__ void __launch_bounds__(256) dora_merge_kernel(const float* __restrict__ w0_base, const float* __restrict__ ab_base,
+                                                         bf16_t* __restrict__ w_dst, float* __restrict__ f_dst, float* __restrict__ stat_base,
+                                                         float* m_dst, const SdtLoraJob* __restrict__ jobs,
+                                                         const SdtDoraJob* __restrict__ dj, int njobs) {
+  __shared__ float tile[LT][LT + 4];
+  __shared__ float red[32][LT];
+  __shared__ float gcol[LT];
+  const int job = find_index(njobs, blockIdx.x, [=](int i) { return dj[i].stripe0_merge; });
+  const SdtLoraJob d = jobs[job];
+  const SdtDoraJob x = dj[job];
+  const int c0 = ((int)blockIdx.x - x.stripe0_merge) * LT;
+  const float* A = ab_base + d.a_off;
+  const float* B = ab_base + d.b_off;
+  float qp[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+  for (int r0 = 0; r0 < d.K; r0 += LT) {
+    ab_tile(d, A, B, r0, c0, tile);
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      float v[8];
+      long e;
+      if (merged_run(d, w0_base, tile, threadIdx.x + 256 * it, r0, c0, v, e)) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) qp[j] += v[j] * v[j];
+      }
     }
+    __syncthreads();  // the tile has been consumed
+  }
+#pragma unroll
+  for (int j = 0; j < 8; ++j) red[threadIdx.x >> 3][(threadIdx.x & 7) * 8 + j] = qp[j];
+  __syncthreads();
+  if (threadIdx.x < LT) {
+    const int n = c0 + threadIdx.x;
+    float g = 0.f;
+    if (n < d.N) {
+      float q = 0.f;
+      for (int i = 0; i < 32; ++i) q += red[i][threadIdx.x];
+      const float c = (float)sqrt((double)q);
+      if (INIT) {
+        m_dst[x.m_off + n] = c;
+      } else {
+        g = c == 0.f ? 0.f : (float)((double)ab_base[x.m_off + n] / (double)c);
+        stat_base[x.stat_off + n] = c;
+        stat_base[x.stat_off + d.N + n] = g;
+      }
+    }
+    gcol[threadIdx.x] = g;
+  }
+  if (INIT) return;
+  __syncthreads();
+  for (int r0 = 0; r0 < d.K; r0 += LT) {
+    ab_tile(d, A, B, r0, c0, tile);
+    __syncthreads();
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+      const int g = threadIdx.x + 256 * it;
+      float v[8];
+      long e;
+      if (merged_run(d, w0_base, tile, g, r0, c0, v, e)) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] *= gcol[(g & 7) * 8 + j];
+        store_run(d, w_dst, f_dst, e, v);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// 8 consecutive float32 at p rounded to bf16, times the 8 column factors at gp, rounded to bf16 again (DoRA: the B operand of dA)
+__device__ __forceinline__ bf16x8_t frag_from_f32_scaled(const float* p, const float* gp, bool ok) {
+  uint4 v = {0u, 0u, 0u, 0u};
+  if (ok) {
+    const float4 a = *reinterpret_cast<const float4*>(p), b = *reinterpret_cast<const float4*>(p + 4);
+    const float4 ga = *reinterpret_cast<const float4*>(gp), gb = *reinterpret_cast<const float4*>(gp + 4);
+    uint4 h;
+    h.x = pack2bf(a.x, a.y); h.y = pack2bf(a.z, a.w); h.z = pack2bf(b.x, b.y); h.w = pack2bf(b.z, b.w);
+    float f[8];
+    unpack8(h, f);
+    f[0] *= ga.x; f[1] *= ga.y; f[2] *= ga.z; f[3] *= ga.w; f[4] *= gb.x; f[5] *= gb.y; f[6] *= gb.z; f[7] *= gb.w;
+    v = pack8(f);
+  }
+  return __builtin_bit_cast(bf16x8_t, v);
+}
+__device__ __forceinline__ float bf_round(float x) { return __uint_as_float(pack2bf(x, 0.f) << 16); }
+
+// what a DoRA projection has beyond the LoRA one: W0 of the leaf, its column statistics c and g, the destination of dm and the
+// LDS the column reductions pass through
+struct DoraCols {
+  const float* W0;
+  const float* c;
+  const float* g;
+  float* gm;
+  float (*red)[LT];
+};
+
+// the end of a DoRA dB stripe: dB, the two column reductions and dm (acc = P of this lane: q = 16 b + 4 (lane >> 4) + i, one column)
+template <int RB>
+__device__ __forceinline__ void dora_db_tail(const SdtLoraJob& d, int c0, const float* __restrict__ B, float* __restrict__ gB,
+                                             const f32x4_t* acc, const float* gw, const DoraCols& x) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const int r = d.r, N = d.N;
+  const float s = d.scale;
+  const int n = c0 + 16 * wave + l15;
+  const float gn = n < N ? x.g[n] : 0.f;
+  float t2 = 0.f;  // this lane's share of sum_q bf16(B[q][n]) * P[q][n], its q ascending (a column's four lanes are added below)
+#pragma unroll
+  for (int b = 0; b < RB; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int q = 16 * b + 4 * lq + i;
+      if (q < r && n < N) {
+        t2 += bf_round(B[(long)q * N + n]) * acc[b][i];
+        gB[(long)q * N + n] = (s * acc[b][i]) * gn;
+      }
+    }
+  const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) x.red[srow][scol + j] = gw[j];
+  __syncthreads();
+  float t1 = 0.f;
+  if (threadIdx.x < LT)
+    for (int i = 0; i < 32; ++i) t1 += x.red[i][threadIdx.x];
+  __syncthreads();
+  x.red[lq][16 * wave + l15] = t2;
+  __syncthreads();
+  if (threadIdx.x < LT && c0 + (int)threadIdx.x < N) {
+    const int col = c0 + threadIdx.x;
+    const float p = ((x.red[0][threadIdx.x] + x.red[1][threadIdx.x]) + x.red[2][threadIdx.x]) + x.red[3][threadIdx.x];
+    const float u = t1 + s * p;
+    const float c = x.c[col];
+    x.gm[col] = c == 0.f ? 0.f : (float)((double)u / (double)c);  // (double, rounded once: the correctly rounded fp32 quotient)
   }
 }
 
 // ---- project: the first tiles_da tiles of a job are 64-row stripes of dA (a wave owns 16 rows and walks all of N), the others
 // 64-column stripes of dB (a wave owns 16 columns and walks all of K; dW passes through LDS so that it is read with 16-byte loads) --
-template <int RB>  // RB = ceil(r / 16) blocks of 16 adapter columns
+// DORA (include/sdt.h "DoRA"): the dA stripes scale the B fragment by g as they load it; the dB stripes also read W0 where they stage
+// dW, sum G * W0 per column (each staging thread its 8 columns over the rows it stages, top to bottom; the 32 partials of a column in
+// row order by one thread), form u = sum_k G W0 + s * sum_q bf16(B) P from their own accumulators and write dB = (s P) g and dm = u / c.
+template <int RB, bool DORA>  // RB = ceil(r / 16) blocks of 16 adapter columns
 __device__ __forceinline__ void project_tile(const SdtLoraJob& d, int tl, const bf16_t* __restrict__ dW, const float* __restrict__ A,
                                              const float* __restrict__ B, float* __restrict__ gA, float* __restrict__ gB,
-                                             bf16_t (*stage)[LT + 8]) {
+                                             bf16_t (*stage)[LT + 8], const DoraCols& x) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
   const int r = d.r, K = d.K, N = d.N;
   const float s = d.scale;
@@ -126,7 +292,8 @@ __device__ __forceinline__ void project_tile(const SdtLoraJob& d, int tl, const 
 #pragma unroll
       for (int b = 0; b < RB; ++b) {
         const int q = 16 * b + l15;
-        const bf16x8_t bb = frag_from_f32(B + (long)q * N + n, q < r && n < N);
+        const bf16x8_t bb = DORA ? frag_from_f32_scaled(B + (long)q * N + n, x.g + n, q < r && n < N)
+                                 : frag_from_f32(B + (long)q * N + n, q < r && n < N);
         acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, acc[b], 0, 0, 0);
       }
     }
@@ -142,9 +309,20 @@ __device__ __forceinline__ void project_tile(const SdtLoraJob& d, int tl, const 
   // dB[q][n] = s * sum_k bf16(A[k][q]) * dW[k][n]: A operand A^T (gathered), B operand dW columns out of the staged 32 x 64 block
   const int c0 = (tl - d.tiles_da) * LT;
   const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;  // one 16-byte load per thread stages 32 rows x 64 columns
+  float gw[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (DORA) sum over the staged rows of G * W0, per staged column
   for (int k0 = 0; k0 < K; k0 += 32) {
     uint4 v = {0u, 0u, 0u, 0u};
-    if (k0 + srow < K && c0 + scol < N) v = *reinterpret_cast<const uint4*>(dW + (long)(k0 + srow) * N + c0 + scol);
+    if (k0 + srow < K && c0 + scol < N) {
+      v = *reinterpret_cast<const uint4*>(dW + (long)(k0 + srow) * N + c0 + scol);
+      if constexpr (DORA) {
+        const float* wp = x.W0 + (long)(k0 + srow) * N + c0 + scol;
+        const float4 w0 = *reinterpret_cast<const float4*>(wp), w1 = *reinterpret_cast<const float4*>(wp + 4);
+        float gf[8];
+        unpack8(v, gf);
+        gw[0] += gf[0] * w0.x; gw[1] += gf[1] * w0.y; gw[2] += gf[2] * w0.z; gw[3] += gf[3] * w0.w;
+        gw[4] += gf[4] * w1.x; gw[5] += gf[5] * w1.y; gw[6] += gf[6] * w1.z; gw[7] += gf[7] * w1.w;
+      }
+    }
     __syncthreads();  // the previous block has been consumed
     *reinterpret_cast<uint4*>(&stage[srow][scol]) = v;
     __syncthreads();
@@ -158,6 +336,10 @@ __device__ __forceinline__ void project_tile(const SdtLoraJob& d, int tl, const 
       const bf16x8_t a = frag_from_f32_strided(A + (long)k * r + q, r, k, K, q < r);
       acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, acc[b], 0, 0, 0);
     }
+  }
+  if constexpr (DORA) {
+    dora_db_tail<RB>(d, c0, B, gB, acc, gw, x);
+    return;
   }
 #pragma unroll
   for (int b = 0; b < RB; ++b)
@@ -178,11 +360,36 @@ __global__ void __launch_bounds__(256) lora_project_kernel(const bf16_t* __restr
   const float* B = ab_base + d.b_off;
   float* gA = grad_base + d.ga_off;
   float* gB = grad_base + d.gb_off;
+  const DoraCols none = {nullptr, nullptr, nullptr, nullptr, nullptr};
   switch ((d.r + 15) / 16) {  // (workgroup-uniform)
-    case 1: project_tile<1>(d, tl, dW, A, B, gA, gB, stage); break;
-    case 2: project_tile<2>(d, tl, dW, A, B, gA, gB, stage); break;
-    case 4: project_tile<4>(d, tl, dW, A, B, gA, gB, stage); break;
-    default: project_tile<8>(d, tl, dW, A, B, gA, gB, stage); break;
+    case 1: project_tile<1, false>(d, tl, dW, A, B, gA, gB, stage, none); break;
+    case 2: project_tile<2, false>(d, tl, dW, A, B, gA, gB, stage, none); break;
+    case 4: project_tile<4, false>(d, tl, dW, A, B, gA, gB, stage, none); break;
+    default: project_tile<8, false>(d, tl, dW, A, B, gA, gB, stage, none); break;
+  }
+}
+
+__global__ void __launch_bounds__(256) dora_project_kernel(const bf16_t* __restrict__ dw_base, const float* __restrict__ w0_base,
+                                                           const float* __restrict__ ab_base, float* __restrict__ grad_base,
+                                                           const float* __restrict__ stat_base, const SdtLoraJob* __restrict__ jobs,
+                                                           const SdtDoraJob* __restrict__ dj, int njobs) {
+  __shared__ __attribute__((aligned(16))) bf16_t stage[32][LT + 8];
+  __shared__ float red[32][LT];
+  const int job = find_job_index(jobs, njobs, blockIdx.x, true);  // (the DoRA table runs beside the job table, index by index)
+  const SdtLoraJob d = jobs[job];
+  const SdtDoraJob j = dj[job];
+  const int tl = blockIdx.x - d.tile0_project;
+  const bf16_t* dW = dw_base + d.dw_off;
+  const float* A = ab_base + d.a_off;
+  const float* B = ab_base + d.b_off;
+  float* gA = grad_base + d.ga_off;
+  float* gB = grad_base + d.gb_off;
+  const DoraCols x = {w0_base + d.w0_off, stat_base + j.stat_off, stat_base + j.stat_off + d.N, grad_base + j.gm_off, red};
+  switch ((d.r + 15) / 16) {  // (workgroup-uniform)
+    case 1: project_tile<1, true>(d, tl, dW, A, B, gA, gB, stage, x); break;
+    case 2: project_tile<2, true>(d, tl, dW, A, B, gA, gB, stage, x); break;
+    case 4: project_tile<4, true>(d, tl, dW, A, B, gA, gB, stage, x); break;
+    default: project_tile<8, true>(d, tl, dW, A, B, gA, gB, stage, x); break;
   }
 }
 
@@ -221,11 +428,39 @@ long check_jobs(const char* name, const SdtLoraJob* h, int n, bool project) {
   return tiles;
 }
 
+// The DoRA table beside the job table (host copies).  Returns the number of merge stripes or -1.
+long check_dora_jobs(const char* name, const SdtLoraJob* h, const SdtDoraJob* x, int n) {
+  long stripes = 0;
+  for (int i = 0; i < n; ++i) {
+    if (x[i].N != h[i].N) {
+      sdt_set_error("%s: job %d: the DoRA table names N=%d, the job table N=%d (mismatched tables)", name, i, x[i].N, h[i].N);
+      return -1;
+    }
+    const int64_t offs[3] = {x[i].m_off, x[i].gm_off, x[i].stat_off};
+    for (int o = 0; o < 3; ++o)
+      if (offs[o] < 0 || offs[o] % 8) {
+        sdt_set_error("%s: job %d: DoRA offsets must be non-negative multiples of 8 elements", name, i);
+        return -1;
+      }
+    if (x[i].stripe0_merge != stripes) {
+      sdt_set_error("%s: job %d: stripe0_merge does not continue the running stripe count", name, i);
+      return -1;
+    }
+    stripes += (h[i].N + LT - 1) / LT;
+    if (stripes >= (1L << 31)) {
+      sdt_set_error("%s: too many stripes", name);
+      return -1;
+    }
+  }
+  return stripes;
+}
+
 }  // namespace
 
 extern "C" {
 
 int sdt_lora_job_size(void) { return (int)sizeof(SdtLoraJob); }
+int sdt_dora_job_size(void) { return (int)sizeof(SdtDoraJob); }
 
 int sdt_lora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, const SdtLoraJob* jobs_host,
                    const void* jobs_device, int n, hipStream_t stream) {
@@ -257,6 +492,59 @@ int sdt_lora_project(const uint16_t* dw_base, const float* ab_base, float* grad_
   hipLaunchKernelGGL(lora_project_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
                      (const SdtLoraJob*)jobs_device, n);
   SDT_LAUNCH_CHECK("sdt_lora_project");
+  return SDT_OK;
+}
+
+int sdt_dora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, float* stat_base,
+                   const SdtLoraJob* jobs_host, const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n,
+                   hipStream_t stream) {
+  SDT_CHECK_ARG(n >= 0, "sdt_dora_merge: negative job count");
+  if (n == 0) return SDT_OK;
+  SDT_CHECK_ARG(jobs_host && jobs_device && dora_host && dora_device, "sdt_dora_merge: null job table");
+  SDT_CHECK_ARG(w0_base && ab_base && stat_base, "sdt_dora_merge: null pointer");
+  SDT_CHECK_ARG(w_bf16 || f32_dst, "sdt_dora_merge: no destination");
+  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)w_bf16 | (uintptr_t)f32_dst | (uintptr_t)stat_base) & 15) == 0,
+                "sdt_dora_merge: pointers must be 16-byte aligned");
+  if (check_jobs("sdt_dora_merge", jobs_host, n, false) < 0) return SDT_ERR_INVALID_ARG;
+  const long stripes = check_dora_jobs("sdt_dora_merge", jobs_host, dora_host, n);
+  if (stripes < 0) return SDT_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(dora_merge_kernel<false>, dim3((unsigned)stripes), dim3(256), 0, stream, w0_base, ab_base, (bf16_t*)w_bf16, f32_dst,
+                     stat_base, (float*)nullptr, (const SdtLoraJob*)jobs_device, (const SdtDoraJob*)dora_device, n);
+  SDT_LAUNCH_CHECK("sdt_dora_merge");
+  return SDT_OK;
+}
+
+int sdt_dora_init_magnitude(const float* w0_base, const float* ab_base, float* m_base, const SdtLoraJob* jobs_host,
+                            const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n, hipStream_t stream) {
+  SDT_CHECK_ARG(n >= 0, "sdt_dora_init_magnitude: negative job count");
+  if (n == 0) return SDT_OK;
+  SDT_CHECK_ARG(jobs_host && jobs_device && dora_host && dora_device, "sdt_dora_init_magnitude: null job table");
+  SDT_CHECK_ARG(w0_base && ab_base && m_base, "sdt_dora_init_magnitude: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)m_base) & 15) == 0,
+                "sdt_dora_init_magnitude: pointers must be 16-byte aligned");
+  if (check_jobs("sdt_dora_init_magnitude", jobs_host, n, false) < 0) return SDT_ERR_INVALID_ARG;
+  const long stripes = check_dora_jobs("sdt_dora_init_magnitude", jobs_host, dora_host, n);
+  if (stripes < 0) return SDT_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(dora_merge_kernel<true>, dim3((unsigned)stripes), dim3(256), 0, stream, w0_base, ab_base, (bf16_t*)nullptr,
+                     (float*)nullptr, (float*)nullptr, m_base, (const SdtLoraJob*)jobs_device, (const SdtDoraJob*)dora_device, n);
+  SDT_LAUNCH_CHECK("sdt_dora_init_magnitude");
+  return SDT_OK;
+}
+
+int sdt_dora_project(const uint16_t* dw_base, const float* w0_base, const float* ab_base, float* grad_base, const float* stat_base,
+                     const SdtLoraJob* jobs_host, const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n,
+                     hipStream_t stream) {
+  SDT_CHECK_ARG(n >= 0, "sdt_dora_project: negative job count");
+  if (n == 0) return SDT_OK;
+  SDT_CHECK_ARG(jobs_host && jobs_device && dora_host && dora_device, "sdt_dora_project: null job table");
+  SDT_CHECK_ARG(dw_base && w0_base && ab_base && grad_base && stat_base, "sdt_dora_project: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)dw_base | (uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)grad_base | (uintptr_t)stat_base) & 15) == 0,
+                "sdt_dora_project: pointers must be 16-byte aligned");
+  const long tiles = check_jobs("sdt_dora_project", jobs_host, n, true);
+  if (tiles < 0 || check_dora_jobs("sdt_dora_project", jobs_host, dora_host, n) < 0) return SDT_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(dora_project_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, w0_base, ab_base, grad_base,
+                     stat_base, (const SdtLoraJob*)jobs_device, (const SdtDoraJob*)dora_device, n);
+  SDT_LAUNCH_CHECK("sdt_dora_project");
   return SDT_OK;
 }
 

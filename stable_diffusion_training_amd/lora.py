@@ -7,6 +7,10 @@ fp32), the step runs as it stands - merged GEMMs, packed attention, HIP graphs -
 of the adapted leaves in the adapter's scratch, and ONE launch projects dA = s * dW @ B^T, dB = s * A^T @ dW into the gradient buffer
 of the adapter's store, which then takes the optimizer step like any other store (Lion / AdamW, 8-bit or fp32 moments, EMA, schedules,
 clipping, checkpoints, micro-batch accumulation).
+
+DoRA (LoraConfig(dora=True); include/sdt.h "DoRA"): a third trained leaf m [N] per adapted kernel, W' = v * (m / ||v||_column) with
+v = W0 + s * A @ B.  The column norm is one more reduction inside the merge launch and the magnitude gradient one more inside the
+projection launch, so the step between them is the LoRA step, launch for launch.
 """
 import bisect
 import json
@@ -27,11 +31,12 @@ CLIP_TARGETS = ("q_proj", "k_proj", "v_proj", "out_proj")
 @dataclass(frozen=True)
 class LoraConfig:
     """rank in RANKS; the delta is (alpha / rank) * A @ B; targets are matched against path components (as params.create_mask does);
-    seed draws A (B starts at zero)."""
+    seed draws A (B starts at zero); dora adds the trained magnitude leaf <dense>/lora_m (it starts at the column norms of W0)."""
     rank: int
     alpha: float
     targets: tuple = UNET_TARGETS
     seed: int = 0
+    dora: bool = False
 
     def __post_init__(self):
         object.__setattr__(self, "targets", tuple(self.targets))
@@ -41,6 +46,8 @@ class LoraConfig:
             raise ValueError(f"LoraConfig: targets must be a non-empty tuple of path components, not {self.targets!r}")
         if not math.isfinite(float(self.alpha)):
             raise ValueError(f"LoraConfig: alpha must be finite, not {self.alpha!r}")
+        if not isinstance(self.dora, bool):
+            raise ValueError(f"LoraConfig: dora must be a bool, not {self.dora!r}")
 
     @property
     def scale(self):
@@ -67,13 +74,16 @@ def select_leaves(spec, cfg):
 
 
 def adapter_spec(spec, cfg):
-    """[(<dense path>/lora_a, (K, r)), (<dense path>/lora_b, (r, N))] for the adapted kernels of `spec`, in its order."""
+    """[(<dense path>/lora_a, (K, r)), (<dense path>/lora_b, (r, N))] for the adapted kernels of `spec`, in its order; with cfg.dora
+    each pair is followed by (<dense path>/lora_m, (N,))."""
     shapes = dict((p, tuple(s)) for p, s in spec)
     out = []
     for path in select_leaves(spec, cfg):
         K, N = shapes[path]
         dense = path[: -len("/kernel")]
         out += [(dense + "/lora_a", (K, cfg.rank)), (dense + "/lora_b", (cfg.rank, N))]
+        if cfg.dora:
+            out.append((dense + "/lora_m", (N,)))
     return out
 
 
@@ -102,7 +112,8 @@ def scratch_runs(leaves, adapted):
 
 
 class LoraAdapter:
-    """What attach() hangs on a frozen store: the trained A / B leaves (self.store), the bf16 dW scratch and the job table."""
+    """What attach() hangs on a frozen store: the trained A / B (/ m) leaves (self.store), the bf16 dW scratch and the job table; for
+    DoRA also the parallel SdtDoraJob table and the column statistics (c, g of every adapted leaf) the merge leaves for the projection."""
 
     def __init__(self, base, cfg, store_kwargs):
         if base.trainable:
@@ -116,9 +127,16 @@ class LoraAdapter:
             lf = base.leaves[p]
             if (lf.R, lf.C) != (lf.Rp, lf.Cp) or lf.w_off != lf.offset:
                 raise ValueError(f"LoRA: {p} is a padded leaf and cannot carry an adapter")
-        self.adapted = {p: (p[: -len("kernel")] + "lora_a", p[: -len("kernel")] + "lora_b") for p in self.paths}
+        self.adapted = {p: tuple(p[: -len("kernel")] + n for n in (("lora_a", "lora_b", "lora_m") if cfg.dora else ("lora_a", "lora_b")))
+                        for p in self.paths}
         kw = dict(store_kwargs)
         kw.setdefault("device", base.device)
+        if cfg.dora:  # a magnitude keeps fp32 moments and takes no weight decay
+            if kw.get("quant_mask") is not None or kw.get("decay_mask") is not None:
+                raise ValueError("DoRA: configure the adapter store with quant_excluded / wd_excluded patterns, not with explicit quant_mask / "
+                                 "decay_mask trees (they would override the exclusion of lora_m from quantisation and weight decay)")
+            for k in ("quant_excluded", "wd_excluded"):
+                kw[k] = tuple(kw.get(k, ())) + ("lora_m",)
         self.store = ParamStore(adapter_spec(base_spec, cfg), trainable=True, **kw)
         self.store.lora_of = self  # (checkpoint.params_to_tree folds an EmaView of this store into the base)
         if self.store.grad16 is not None or self.store.g32_base:
@@ -128,18 +146,28 @@ class LoraAdapter:
         dev = base.device
         # dW of every adapted leaf (and of the non-adapted members of a merged group, computed and ignored): scratch_runs' layout
         self.scratch = torch.zeros(size, dtype=torch.bfloat16, device=dev)
-        jobs, tm, tp = [], 0, 0
+        jobs, dora, tm, tp, sm, so = [], [], 0, 0, 0, 0
         for p in self.paths:
             lf = base.leaves[p]
-            la, lb = (self.store.leaves[q] for q in self.adapted[p])
+            la, lb = (self.store.leaves[q] for q in self.adapted[p][:2])
             K, N = lf.shape
             ta = (K + 63) // 64
             jobs.append(_lib.SdtLoraJob(lf.offset, la.offset, lb.offset, lf.w_off, lf.offset, self.scratch_offset(lf.offset, lf.offset + lf.numel), la.offset, lb.offset,
                                         K, N, cfg.rank, cfg.scale, tm, tp, ta, 0))
             tm += ta * ((N + 63) // 64)
             tp += ta + (N + 63) // 64
+            if cfg.dora:
+                lm = self.store.leaves[self.adapted[p][2]]
+                dora.append(_lib.SdtDoraJob(lm.offset, lm.offset, so, N, sm))
+                sm += (N + 63) // 64
+                so += 2 * N  # c [N], then g [N]
         self.jobs_host = (_lib.SdtLoraJob * len(jobs))(*jobs)
         self.jobs_dev = torch.frombuffer(bytearray(bytes(self.jobs_host)), dtype=torch.uint8).to(dev)
+        self.dora_host = self.dora_dev = self.stats = None
+        if cfg.dora:
+            self.dora_host = (_lib.SdtDoraJob * len(dora))(*dora)
+            self.dora_dev = torch.frombuffer(bytearray(bytes(self.dora_host)), dtype=torch.uint8).to(dev)
+            self.stats = torch.zeros(so, dtype=torch.float32, device=dev)
         self.init_weights()
         base.adapter = self
         if dev.type == "cuda":
@@ -147,15 +175,42 @@ class LoraAdapter:
 
     # ------------------------------------------------------------------ parameters
     def init_weights(self):
-        """A: Kaiming-uniform (a = sqrt(5): U(-1/sqrt(K), 1/sqrt(K))) drawn on the host from cfg.seed in leaf order; B: zero."""
+        """A: Kaiming-uniform (a = sqrt(5): U(-1/sqrt(K), 1/sqrt(K))) drawn on the host from cfg.seed in leaf order; B: zero; m (DoRA):
+        the column norms of W0 + s * A @ B = W0 by the merge kernel's own reduction, so that the first merge finds g == 1.0f exactly."""
         g = torch.Generator().manual_seed(int(self.cfg.seed))
         tree = {}
         for p in self.paths:
-            a, b = self.adapted[p]
+            a, b = self.adapted[p][:2]
             K, r = self.store.leaves[a].shape
             tree[a] = (torch.rand(K, r, generator=g) * 2 - 1) / math.sqrt(K)
             tree[b] = torch.zeros(self.store.leaves[b].shape)
+            if self.cfg.dora:
+                tree[self.adapted[p][2]] = torch.zeros(self.store.leaves[self.adapted[p][2]].shape)
         self.store.load(tree)
+        if self.cfg.dora:
+            self.init_magnitude()
+
+    def init_magnitude(self):
+        """m = the column norms of W0 + s * A @ B at the master's current A and B.  On a GPU store by sdt_dora_init_magnitude; on a CPU
+        store (host-logic tests only) by a float64 norm rounded to fp32.  Like ParamStore.load, it writes the master from outside a
+        step: the EMA's m (when the store keeps one) becomes the master's - an EMA that started at m = 0 would merge adapted kernels
+        with a gain near zero for its first thousands of steps - and the store's bf16 copies are refreshed."""
+        self.store.begin_external_write()
+        if self.base.device.type == "cuda":
+            _lib.call("sdt_dora_init_magnitude", self.base.master.data_ptr(), self.store.master.data_ptr(), self.store.master.data_ptr(),
+                      self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(), self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
+        else:
+            bf = lambda t: t.to(torch.bfloat16).double()
+            for p in self.paths:
+                a, b, m = self.adapted[p]
+                v = self.base.p(p).double() + self.cfg.scale * (bf(self.store.p(a)) @ bf(self.store.p(b)))
+                self.store.p(m).copy_(v.pow(2).sum(0).sqrt().float())
+        if self.store.ema is not None:
+            for p in self.paths:
+                lm = self.store.leaves[self.adapted[p][2]]
+                self.store.ema[lm.offset: lm.offset + lm.numel].copy_(self.store.master[lm.offset: lm.offset + lm.numel])
+        if self.base.device.type == "cuda":
+            self.store.prepare(full=True)  # whoever writes the master refreshes the bf16 copies
 
     def scratch_offset(self, a, b):
         """The scratch element of master element a; [a, b) must lie inside one run of scratch_runs."""
@@ -188,14 +243,23 @@ class LoraAdapter:
         if ab is None:
             raise ValueError("merge(source='ema'): the adapter store keeps no EMA")
         self.source = source
+        if self.cfg.dora:  # also leaves c and g of every leaf in self.stats, for project()
+            _lib.call("sdt_dora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.stats.data_ptr(),
+                      self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(), self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
+            return
         _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.jobs_host,
                   self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
 
     def project(self):
         """dA, dB of every adapted leaf from the dW scratch into the adapter store's gradient (one launch; written, not accumulated)."""
         from . import ops
-        _lib.call("sdt_lora_project", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), self.jobs_host,
-                  self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
+        if self.cfg.dora:  # also dm, from the c and g the step's merge left in self.stats
+            _lib.call("sdt_dora_project", self.scratch.data_ptr(), self.base.master.data_ptr(), self.store.master.data_ptr(),
+                      self.store.grad.data_ptr(), self.stats.data_ptr(), self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(),
+                      self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
+        else:
+            _lib.call("sdt_lora_project", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), self.jobs_host,
+                      self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
         for p in self.paths:
             ops._ready(self.store, *self.adapted[p])
 
@@ -206,17 +270,26 @@ class LoraAdapter:
         if ab is None:
             raise ValueError("folded(source='ema'): the adapter store keeps no EMA")
         buf = self.base.master.clone()
-        _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), self.jobs_host,
-                  self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
+        if self.cfg.dora:  # (statistics of its own: self.stats stays what the last merge into the mirror left)
+            stats = torch.empty_like(self.stats)  # (bound to a name until the call has been enqueued)
+            _lib.call("sdt_dora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), stats.data_ptr(),
+                      self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(), self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
+        else:
+            _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), self.jobs_host,
+                      self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
         return {p: buf[lf.offset: lf.offset + lf.numel].view(lf.shape) for p, lf in self.base.leaves.items()}
 
     # ------------------------------------------------------------------ adapter file
     def _meta(self):
-        return dict(rank=int(self.cfg.rank), alpha=float(self.cfg.alpha), targets=list(self.cfg.targets),
+        meta = dict(rank=int(self.cfg.rank), alpha=float(self.cfg.alpha), targets=list(self.cfg.targets),
                     base_shapes={p: list(self.base.leaves[p].shape) for p in self.paths})
+        if self.cfg.dora:  # (a LoRA file stays byte for byte what it was)
+            meta["dora"] = True
+        return meta
 
     def save(self, path, which="master"):
-        """One .npz: the A / B leaves (fp32) and __meta__ (JSON: rank, alpha, targets, the adapted base kernels' shapes)."""
+        """One .npz: the A / B (/ m) leaves (fp32) and __meta__ (JSON: rank, alpha, targets, the adapted base kernels' shapes, and
+        "dora": true for a DoRA adapter)."""
         tree = self.store.export_host(which)
         with open(path, "wb") as f:
             np.savez(f, __meta__=np.frombuffer(json.dumps(self._meta()).encode(), dtype=np.uint8), **{p: np.asarray(v) for p, v in tree.items()})
@@ -228,6 +301,10 @@ class LoraAdapter:
                 raise ValueError(f"{path}: not an adapter file (no __meta__)")
             meta = json.loads(bytes(z["__meta__"]).decode())
             mine = self._meta()
+            if bool(meta.get("dora", False)) != bool(mine.get("dora", False)):
+                kind = lambda m: "DoRA" if m.get("dora", False) else "LoRA"
+                raise ValueError(f"{path}: a {kind(meta)} adapter file, this adapter is a {kind(mine)} adapter (attach with dora="
+                                 f"{bool(meta.get('dora', False))})")
             if meta["rank"] != mine["rank"]:
                 raise ValueError(f"{path}: adapter of rank {meta['rank']}, this adapter has rank {mine['rank']}")
             if list(meta["targets"]) != mine["targets"]:

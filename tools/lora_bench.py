@@ -3,7 +3,8 @@ For each configuration of bench.py it times the step bench.py times (bench.build
 and batch - rank 16, the default UNet targets, text encoder frozen - as tools/latent_cache_bench.py does: three set-up calls (two eager,
 capture + first replay), then timed graph replays.  The adapter's two launches (merge, project) and its optimizer step are timed by
 events around eager calls.
-usage: python tools/lora_bench.py [--config sd15_512 sd21_768 sdxl_1024] [--steps 8] [--warmup 2] [--rank 16]"""
+--dora times the DoRA step (LoraConfig(dora=True): the column-stripe merge and the projection with the magnitude gradient) in its place.
+usage: python tools/lora_bench.py [--config sd15_512 sd21_768 sdxl_1024] [--steps 8] [--warmup 2] [--rank 16] [--dora]"""
 import argparse
 import json
 import os
@@ -22,6 +23,7 @@ ap.add_argument("--config", nargs="+", choices=sorted(bench.CONFIGS), default=so
 ap.add_argument("--steps", type=int, default=8)
 ap.add_argument("--warmup", type=int, default=2)
 ap.add_argument("--rank", type=int, default=16)
+ap.add_argument("--dora", action="store_true")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 
@@ -60,7 +62,7 @@ for config in args.config:
     tc, cfgs, weights, (us, ts, ue, te, vae, sched, _) = bench.build_states(dev, B, config=config)
     kw = dict(strip_bos_eos_token=False, ema_rate=tc.ema_rate, vae_scale=c["vae_scale"])
     batch = bench.synthetic_batch(dev, B, 0, config)
-    res = {"config": config, "batch": B, "rank": args.rank}
+    res = {"config": config, "batch": B, "rank": args.rank, "dora": args.dora}
     step = tu._GraphedStep(lambda *a, **k: tu.train_step(*a, **kw, **k))
     ms, ips, loss = time_steps(step, (us, ts, ue, te, vae, sched), batch, B)
     res["full"] = {"ms_per_step": round(ms, 3), "images_per_sec": round(ips, 2), "loss": loss}
@@ -71,12 +73,12 @@ for config in args.config:
     models = {"unet": {"unet_params": weights["unet"], "config": cfgs["unet"]}, "vae": {"vae_params": weights["vae"], "config": cfgs["vae"]},
               "text_encoder": {"text_encoder_params": weights["clip"], "config": cfgs["clip"]}}
     us, ts, ue, te, vae, sched, _ = tu.on_device_model_training_state(
-        tc, models, device=dev, lora=dict(unet=lora.LoraConfig(args.rank, float(args.rank)), text_encoder="frozen"))
+        tc, models, device=dev, lora=dict(unet=lora.LoraConfig(args.rank, float(args.rank), dora=args.dora), text_encoder="frozen"))
     ad = us.adapter
     step = tu._GraphedStep(lambda *a, **k: tu.train_step(*a, **kw, **k))
     ms, ips, loss = time_steps(step, (us, ts, ue, te, vae, sched), batch, B)
     res["lora"] = {"ms_per_step": round(ms, 3), "images_per_sec": round(ips, 2), "loss": loss}
-    print(f"{config}  lora: {ms:.2f} ms/step, {ips:.1f} images/sec, loss {loss:.4f}", flush=True)
+    print(f"{config}  {'dora' if args.dora else 'lora'}: {ms:.2f} ms/step, {ips:.1f} images/sec, loss {loss:.4f}", flush=True)
     adapted = sum(us.store.leaves[p].numel for p in ad.paths)
     res["adapter"] = {"leaves": len(ad.paths), "adapted_params": adapted, "trained_params": sum(lf.numel for lf in ad.store.leaves.values()),
                       "scratch_bytes": 2 * ad.scratch.numel(), "merge_ms": round(event_ms(ad.merge), 4),
