@@ -13,6 +13,7 @@ from tests import adamw_reference as AR
 from tests import kernel_checks as kc
 from tests.helpers import make_case, to_dev
 from tests.kernel_checks import BF, assert_equal_bits
+from tests.step_matrix import STEP_HP, _check_store, _reference_store_step  # (shared with tests/test_gpu_step_combinations.py)
 from tests.test_gpu_kernel_exact import _stream, _workspace
 from tests.test_gpu_reduce_optim_exact import _flat_in, _flat_io, _flat_out, _lion8_run, _lion_inputs, _np, _thresholds, _ws_args
 
@@ -252,40 +253,7 @@ def test_adamw_select_forty_launches_and_a_restored_count(dev):
 
 
 # ------------------------------------------------------------------------------------------------ ParamStore.optimizer_step
-STEP_HP = dict(lr=1e-3, wd=0.07, eps=1e-8, max_norm=1.0)
 STATE = ("master", "w", "codes", "inv_scale", "codes2", "inv_scale2", "mom", "mom2", "ema", "adam_step", "adam_prod", "adam_cur")
-
-
-def _reference_store_step(st, ref, g_flat, cur):
-    """One restatement step of every leaf of `st` on ref = dict(p, m (path -> state), ema): g_flat the float32 gradient in master order as
-    the sweep reads it."""
-    sq = float(np.sum(g_flat.astype(np.float64) ** 2))
-    b1, b2 = st.adam_betas
-    for path, lf in st.leaves.items():
-        g = g_flat[lf.offset: lf.offset + lf.numel]
-        kw = dict(wd=STEP_HP["wd"] if lf.decayed else 0.0, b1=b1, b2=b2, eps=STEP_HP["eps"], max_norm=STEP_HP["max_norm"], sq=sq)
-        if lf.quantised:
-            ref["p"][path], ref["m"][path] = AR.step8(ref["p"][path], g, ref["m"][path], cur, bs=st.block_size, **kw)
-        else:
-            ref["p"][path], m, v = AR.step32(ref["p"][path], g, *ref["m"][path], cur, **kw)
-            ref["m"][path] = (m, v)
-        ref["ema"][path] = AR.ema_update(ref["ema"][path], ref["p"][path], cur)
-
-
-def _check_store(st, ref, tag):
-    master, ema = st.export("master"), st.export("ema")
-    mm, ss = st.export_momentum("m"), st.export_momentum("s")
-    for path, lf in st.leaves.items():
-        assert_equal_bits(master[path].reshape(-1).cpu(), torch.from_numpy(ref["p"][path]), f"{tag}: {path} master")
-        assert_equal_bits(ema[path].reshape(-1).cpu(), torch.from_numpy(ref["ema"][path]), f"{tag}: {path} ema")
-        assert_equal_bits(st.w[lf.offset: lf.offset + lf.numel].cpu(), torch.from_numpy(ref["p"][path]).to(BF), f"{tag}: {path} bf16 mirror")
-        if lf.quantised:
-            for name, (c, i), wc, wi in (("m", mm[path], *ref["m"][path][:2]), ("s", ss[path], *ref["m"][path][2:])):
-                msg = kc.lion_state_report(c.cpu().numpy(), i.cpu().numpy(), wc, wi, f"{tag}: {path} {name}")
-                assert msg is None, msg
-        else:
-            assert_equal_bits(mm[path].reshape(-1).cpu(), torch.from_numpy(ref["m"][path][0]), f"{tag}: {path} m")
-            assert_equal_bits(ss[path].reshape(-1).cpu(), torch.from_numpy(ref["m"][path][1]), f"{tag}: {path} v")
 
 
 @pytest.mark.parametrize("mode", ["grad", "acc", "scheduled"])

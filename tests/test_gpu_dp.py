@@ -460,3 +460,258 @@ def test_eight_way_slices_of_the_sharded_sweep_equal_the_replicated_sweep():
                 n = ref.total if name != "inv_scale" else b_.numel()
                 assert torch.equal(a_[:n].view(torch.int16 if name == "w" else a_.dtype), b_[:n].view(torch.int16 if name == "w" else b_.dtype)), (step, name)
             assert abs(st.grad_norm() - ref.grad_norm()) <= 1e-6 * ref.grad_norm()
+
+
+# ------------------------------------------------------------------------------------------------ AdamW
+ADAMW_BUFFERS = ("master", "ema", "codes", "inv_scale", "codes2", "inv_scale2", "mom", "mom2", "w", "adam_step", "adam_prod")
+
+
+def _adamw_snap(stores):
+    """Clones of every AdamW state buffer of the stores (bf16 mirror as int16) and their sha256 digests, for the other rank."""
+    import hashlib
+    torch.cuda.synchronize()
+    snap, dig = {}, {}
+    for i, st in enumerate(stores):
+        for b in ADAMW_BUFFERS:
+            t = getattr(st, b).detach().clone()
+            t = t.view(torch.int16) if t.dtype == torch.bfloat16 else t
+            snap[f"{i}.{b}"] = t
+            dig[f"{i}.{b}"] = hashlib.sha256(t.cpu().contiguous().view(torch.uint8).numpy().tobytes()).hexdigest()
+    return snap, dig
+
+
+def _differing(a, b):
+    return [k for k in a if not torch.equal(a[k], b[k])]
+
+
+def _adamw_shard_worker(rank, world, port, q, path):
+    """_shard_worker for AdamW stores (UNet and text tower in one reducer): replicated, then sharded with a gather after every step so
+    that the whole state can be compared; rank 0 saves the gathered state and continues it in a store of its own, without a reducer."""
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    try:
+        import sys
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from stable_diffusion_training_amd import dp, nets, params
+        from stable_diffusion_training_amd import training_utils as tu
+        torch.cuda.set_device(0)
+        dev = torch.device("cuda:0")
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        specs = [nets.unet_spec(nets.unet_config("tiny")), nets.clip_text_spec(nets.clip_config("tiny"))]
+        weights = [nets.init_params(spec, 1 + i) for i, spec in enumerate(specs)]
+        hp = dict(lr=1e-3, wd=1e-2, eps=1e-8, ema_rate=0.999)
+
+        def make():
+            out = []
+            for spec, w in zip(specs, weights):
+                st = params.ParamStore(spec, device=dev, quantise=True, quant_excluded=("bias", "scale", "embedding"), wd_excluded=("bias", "scale"),
+                                       block_size=16, with_ema=True, optimizer="adamw")
+                st.load(w)
+                out.append(st)
+            return out
+
+        def grads(stores, step, r):
+            return [torch.randn(st.total, generator=torch.Generator().manual_seed(1000 * step + 10 * i + r)) * (0.3 if step else 1e-4)
+                    for i, st in enumerate(stores)]  # below, then above the clip norm
+
+        res = {"digests": {}, "problems": []}
+        snaps = {}
+        for shard in (False, True):
+            stores = make()
+            red = dp.GradReducer(stores, bucket_bytes=1 << 16, shard=shard)
+            assert red.shard == shard and len(red.buckets) > 4
+            if shard:
+                assert any(b["scatter"] for b in red.buckets) and any(not b["scatter"] for b in red.buckets)
+            for step in range(3 if shard else 4):  # (the replicated run goes one step on: what the resumed store has to continue)
+                for st, g in zip(stores, grads(stores, step, rank)):
+                    st.set_grad_flat(g)
+                red.begin_step()
+                for st in stores:
+                    for p in st.leaves:
+                        st.grad_ready(p)
+                red.finish()
+                for st in stores:
+                    st.optimizer_step(shard=red.shard_pieces(st), **hp)
+                red.after_optimizer()
+                red.wait_gathered()
+                for st in stores:
+                    st.prepare()
+                if shard:
+                    assert not stores[0].state_whole
+                    red.gather_state()
+                    assert all(st.state_whole for st in stores)
+                snaps[shard, step], res["digests"][shard, step] = _adamw_snap(stores)
+                if shard:
+                    bad = _differing(snaps[False, step], snaps[True, step])
+                    if bad:
+                        res["problems"].append(f"step {step}: sharded != replicated in {bad}")
+                elif step == 3:
+                    mean_grads = [st.grad_flat().detach().clone() for st in stores]  # the exchanged mean both ranks stepped on
+            if shard:
+                assert all(int(st.adam_step.item()) == 3 and st.count == 3 for st in stores)
+                if rank == 0:
+                    tu.save_training_state(path, stores[0], stores[1])
+        dist.barrier()
+        if rank == 0:  # one process, no reducer: load the gathered state and take step 4 on the mean gradient of the replicated run
+            single = make()
+            tu.load_training_state(path, single[0], single[1])
+            assert all(st.count == 3 and int(st.adam_step.item()) == 3 for st in single)
+            for st, g in zip(single, mean_grads):
+                st.set_grad_flat(g)
+                assert torch.equal(st.grad_flat(), g), "the exchanged gradient is not representable in the store's gradient buffers"
+                st.optimizer_step(**hp)
+                st.prepare()  # (as the ranks do after a step: the zero-padded compute copies behind the mirror follow the masters)
+            bad = _differing(snaps[False, 3], _adamw_snap(single)[0])
+            if bad:
+                res["problems"].append(f"step 4 of the loaded single process != the replicated rank's in {bad}")
+        q.put((rank, "ok", res))
+        dist.barrier()
+    except Exception as e:  # pragma: no cover
+        import traceback
+        q.put((rank, "ERR " + repr(e) + traceback.format_exc()[-1500:], None))
+    finally:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def test_sharded_adamw_equals_replicated_two_ranks_one_gpu(tmp_path):
+    """The AdamW twin of test_sharded_optimizer_equals_replicated_two_ranks_one_gpu: 8-bit moments, EMA, three carried steps on per-rank
+    gradients.  After every step, on both ranks, masters, EMA, both code and scale streams, both fp32 moments, the bf16 mirror, the
+    device step counter and the running products equal the replicated two-rank run bit for bit and each other across ranks; then
+    gather_state, save_training_state on rank 0, and a single process that loads the file takes step 4 exactly as a replicated rank."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = 43500 + (os.getpid() % 2000)
+    procs = [ctx.Process(target=_adamw_shard_worker, args=(r, 2, port, q, str(tmp_path / "adamw_state.safetensors"))) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=600) for _ in procs], key=lambda r: r[0])
+    for p in procs:
+        p.join(120)
+    assert all(r[1] == "ok" for r in res), [r[1] for r in res]
+    r0, r1 = res[0][2], res[1][2]
+    assert not r0["problems"] and not r1["problems"], r0["problems"] + r1["problems"]
+    assert sorted(r0["digests"]) == sorted(r1["digests"]) == [(False, 0), (False, 1), (False, 2), (False, 3), (True, 0), (True, 1), (True, 2)]
+    for key in r0["digests"]:
+        bad = [k for k in r0["digests"][key] if r0["digests"][key][k] != r1["digests"][key][k]]
+        assert not bad, f"{'sharded' if key[0] else 'replicated'} step {key[1]}: the ranks differ in {bad}"
+    assert len(r0["digests"][True, 0]) == 2 * len(ADAMW_BUFFERS)
+    assert r0["digests"][True, 0]["0.codes2"] != r0["digests"][True, 2]["0.codes2"], "the second moments never moved"
+
+
+def _adamw_step_worker(rank, world, port, q):
+    """train_step with AdamW, the replicated reducer and micro_batches=2: eager and captured (two graphs around the exchange)."""
+    os.environ["MASTER_ADDR"] = "127.0.0.1"
+    os.environ["MASTER_PORT"] = str(port)
+    try:
+        import sys
+        sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+        from stable_diffusion_training_amd import dp
+        from stable_diffusion_training_amd import training_utils as tu
+        from tests.helpers import build_hip_states, make_case, to_dev
+        from tests.test_gpu_adamw import _states
+        torch.cuda.set_device(0)
+        dev = torch.device("cuda:0")
+        dist.init_process_group("gloo", rank=rank, world_size=world)
+        case = make_case("tiny", B=4, image=64)
+        sl = slice(2 * rank, 2 * rank + 2)  # two micro-batches of one sample per rank
+        batch = to_dev({k: v[sl] for k, v in case["batch"].items()}, dev)
+        rand = to_dev({k: v[sl] for k, v in case["rand"].items()}, dev)
+        res = {"digests": {}, "problems": []}
+        snaps = {}
+        for mode in ("eager", "graph"):
+            tc, (us, ts, ue, te, vae, sc, _) = _states(case, dev)
+            stores = [us.store, ts.store]
+            assert all(st.optimizer == "adamw" and st.codes2 is not None for st in stores)
+            red = dp.GradReducer(stores, bucket_bytes=1 << 16)
+            assert red.active and not red.shard and len(red.buckets) > 4
+
+            def bound(us, ts, ue, te, batch, rng, vae, sched, **extra):
+                return tu.train_step(us, ts, ue, te, batch, rng, vae, sched, strip_bos_eos_token=False, ema_rate=0.999, reducer=red,
+                                     micro_batches=2, **extra)
+
+            step = tu._GraphedStep(bound, warmup=1, reducer=red) if mode == "graph" else bound
+            rng = torch.Generator(device=dev)
+            for i in range(4):  # graph: 1 eager warm-up, then capture + 3 replays
+                out = step(us, ts, ue, te, batch, rng, vae, sc, rand=rand)
+                snap, res["digests"][mode, i] = _adamw_snap(stores)
+                snap["loss"] = out[4]["loss"].detach().clone().reshape(1)
+                snaps[mode, i] = snap
+                if i == 0 and mode == "eager":
+                    g = us.store.grad_flat().detach().cpu().clone()  # the mean over both ranks' micro-batches the optimizer consumed
+                    loss = float(out[4]["loss"].item())
+                if mode == "graph":
+                    bad = _differing(snaps["eager", i], snap)
+                    if bad:
+                        res["problems"].append(f"step {i}: captured != eager in {bad}")
+            if mode == "graph":
+                assert step.graph_b is not None and not step.disabled and all(st.count == 4 and int(st.adam_step.item()) == 4 for st in stores)
+        if rank == 0:
+            def gates(kw, floor):
+                """test_dp_two_ranks_one_gpu's comparison of g with the float32, exchange-free gradient of a single-process step over all
+                four samples: (cosine, worst kernel-leaf cosine, that leaf, worst relative norm error, the step's loss) over the kernel
+                leaves of size whose reference gradient exceeds floor x the reference's norm."""
+                tc2, (us2, ts2, _, _, vae2, sc2, _) = build_hip_states(case, dev, quantize=False)
+                out2 = tu.train_step(us2, ts2, None, None, to_dev(case["batch"], dev), torch.Generator(device=dev), vae2, sc2,
+                                     strip_bos_eos_token=False, rand=to_dev(case["rand"], dev), **kw)
+                torch.cuda.synchronize()
+                g2, st1, st2 = us2.store.grad_flat().detach().cpu(), stores[0], us2.store
+                # (a quantised store lays its leaves out in other segments than an unquantised one: compare leaf by leaf, same order)
+                ga = torch.cat([g[lf.offset: lf.offset + lf.numel] for lf in st1.leaves.values()])
+                gb = torch.cat([g2[st2.leaves[pth].offset: st2.leaves[pth].offset + lf.numel] for pth, lf in st1.leaves.items()])
+                worst_cos, worst_leaf, worst_norm = 1.0, None, 0.0
+                for pth, lf in st1.leaves.items():
+                    lf2 = st2.leaves[pth]
+                    a, b = g[lf.offset: lf.offset + lf.numel], g2[lf2.offset: lf2.offset + lf2.numel]
+                    if lf.numel >= 256 and float(b.norm()) > floor * float(g2.norm()):
+                        c = float(torch.dot(a, b) / (a.norm() * b.norm()))
+                        worst_cos, worst_leaf = (c, pth) if c < worst_cos else (worst_cos, worst_leaf)
+                        worst_norm = max(worst_norm, abs(float(a.norm() / b.norm()) - 1.0))
+                return float(torch.dot(ga, gb) / (ga.norm() * gb.norm())), worst_cos, worst_leaf, worst_norm, float(out2[4]["loss"].item())
+
+            tight = 1e-3 / len(stores[0].leaves) ** 0.5  # test_dp_two_ranks_one_gpu's leaf selection
+            res["gates"] = dict(loss=loss, same_passes=gates(dict(micro_batches=4), tight), one_pass=gates({}, 1e-3),
+                                one_pass_tight=gates({}, tight))  # (the last for the record: printed, not asserted)
+        q.put((rank, "ok", res))
+        dist.barrier()
+    except Exception as e:  # pragma: no cover
+        import traceback
+        q.put((rank, "ERR " + repr(e) + traceback.format_exc()[-1500:], None))
+    finally:
+        if dist.is_initialized():
+            dist.destroy_process_group()
+
+
+def test_dp_adamw_captured_and_accumulated():
+    """AdamW under the replicated reducer with micro_batches=2, eager and through _GraphedStep(reducer=): the captured run equals the
+    eager two-rank run bit for bit in every state buffer and the loss after each of four steps, both ranks end every step identical,
+    and the averaged gradient passes test_dp_two_ranks_one_gpu's gates against the single-process step of the whole batch."""
+    ctx = mp.get_context("spawn")
+    q = ctx.Queue()
+    port = 45500 + (os.getpid() % 2000)
+    procs = [ctx.Process(target=_adamw_step_worker, args=(r, 2, port, q)) for r in range(2)]
+    for p in procs:
+        p.start()
+    res = sorted([q.get(timeout=900) for _ in procs], key=lambda r: r[0])
+    for p in procs:
+        p.join(120)
+    assert all(r[1] == "ok" for r in res), [r[1] for r in res]
+    r0, r1 = res[0][2], res[1][2]
+    assert not r0["problems"] and not r1["problems"], r0["problems"] + r1["problems"]
+    assert len(r0["digests"]) == 8
+    for key in r0["digests"]:
+        bad = [k for k in r0["digests"][key] if r0["digests"][key][k] != r1["digests"][key][k]]
+        assert not bad, f"{key[0]} step {key[1]}: the ranks differ in {bad}"
+    assert r0["digests"]["eager", 0]["0.master"] != r0["digests"]["eager", 3]["0.master"]
+    # test_dp_two_ranks_one_gpu's gates and thresholds against the single-process step of the whole batch taken as the same four passes
+    # of one sample (float32 gradients, no exchange), and against its one pass over the four samples at the leaf selection of
+    # test_tiny_train_step_parity (leaves above 1e-3 of the norm), as test_two_ranks_accumulate_and_exchange_fp32_sums does for Lion:
+    # below that, down_blocks_0/resnets_0/time_emb_proj/kernel (1e-4 of the norm, a sum over the latent pixels that cancels to bf16
+    # noise) differs between one pass over 4 samples and passes over fewer whatever the optimizer or the exchange (cosine 0.33 here too)
+    gt = r0["gates"]
+    print(f"[adamw dp accumulated] {gt}")
+    for name in ("same_passes", "one_pass"):
+        cos, worst_cos, worst_leaf, worst_norm, loss2 = gt[name]
+        assert cos > 0.999, f"{name}: DP-averaged accumulated gradient vs single-process gradient cosine {cos}"
+        assert worst_cos > 0.995 and worst_norm < 0.03, f"{name}: worst kernel leaf {worst_leaf}: cosine {worst_cos}, norm off by {worst_norm}"
+        assert abs(gt["loss"] - loss2) / loss2 < 1e-2
