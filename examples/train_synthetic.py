@@ -191,8 +191,10 @@ def main(config_dict, models=None, tokenizer=None, log=print):
                 start = time.time()
                 train_metrics = []
                 if rank == 0:
+                    opt_store = unet_state.opt_store  # Prodigy: lr multiplies the estimated d, which is worth a look beside the loss
+                    d = f', unet d {float(opt_store.prodigy_d().item()):.4e}' if opt_store.optimizer == "prodigy" else ""
                     log(f'at steps {count}, avg loss for {config_dict["loss_logging_interval"]} steps: {loss}, took {elapsed} second(s), '
-                        f'unet lr {current_lr(unet_state):.4e}')
+                        f'unet lr {current_lr(unet_state):.4e}{d}')
                     with open(config_dict["loss_csv"], "a") as f:
                         f.write(f'\n{count},{config_dict["loss_logging_interval"]},{loss},{elapsed},{config_dict["chunk_steps"]},{config_dict["master_seed"]}')
         rng_states = gather_rng_states(train_rngs)  # every rank resumes ITS noise / timestep stream (collective)
@@ -218,8 +220,9 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("config", nargs="?", default="model_properties.json")
     ap.add_argument("--micro-batches", type=int, default=None, help="gradient accumulation over K micro-batches per step")
-    ap.add_argument("--optimizer", choices=("lion", "adamw"), default=None,
-                    help="lion (the reference's, default) or adamw: learning rates taken as given, 8-bit moments where the config quantises")
+    ap.add_argument("--optimizer", choices=("lion", "adamw", "prodigy"), default=None,
+                    help="lion (the reference's, default); adamw: learning rates taken as given, 8-bit moments where the config quantises; "
+                         "prodigy: learning-rate-free (the config's rates are not used, lr = 1 multiplies the estimated d, fp32 state)")
     ap.add_argument("--cache-latents", metavar="DIR", default=None,
                     help="encode the run's chunks once into a latent cache under DIR, drop the VAE and train from the cache")
     ap.add_argument("--lora", metavar="RANK", type=int, default=None,

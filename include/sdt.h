@@ -198,6 +198,48 @@ int sdt_adamw8_step(float* p, const void* g, int g_bf16, int8_t* m_codes, float*
                     double max_norm, const float* cur, double wd, double b1, double b2, double eps, hipStream_t stream);
 int sdt_adamw32_step(float* p, const float* g, float* m, float* v, float* ema, uint16_t* w_bf16, int64_t n, const double* sqnorm,
                      double max_norm, const float* cur, double wd, double b1, double b2, double eps, hipStream_t stream);
+/* Prodigy (Mishchenko & Defazio, arXiv:2306.06101), the Adam-style form with decoupled decay, as a third optimizer: it estimates the
+ * distance-to-solution scale d while it trains and steps by d * lr, so lr is a multiplier (1 by default).  One d per store.  All element
+ * state is float32 (m, v, s, and p0 = the parameters at the store's first step); every float32 operation below is rounded on its own,
+ * division and square root correctly rounded; gc is the clipped gradient (same clip as the other sweeps).  Per step, on one stream:
+ *   sdt_prodigy_select, sdt_prodigy_moments_step over every piece of the store, sdt_prodigy_finish, sdt_prodigy_apply_step over every piece.
+ * state: ten doubles, 8-byte aligned: {d, d_max, numer, P1, P2, dot, l1, q, lr_t, 0}; before the first step {d0, d0, 0, 1, 1, 0, 0, 0, 0, 0}.
+ * cur: the step's scalar block, eight floats, 16-byte aligned: {neg_dlr, r, 1 - r, first, c_m, c_v, c_s, d_eps}.
+ * sdt_prodigy_select: one lane.  t = *step.  In double:
+ *     P1 = P1 * b1;  P2 = P2 * b2;  bc = use_bias_correction ? sqrt(1 - P2) / (1 - P1) : 1;
+ *     lr_t = lr, or -(double)lr_tab[min(t, n_lr - 1)] with tables (sdt_opt_schedule_select's: lr_tab holds -lr_t, ema_tab (r, 1 - r) pairs);
+ *     dlr = (d * lr_t) * bc;  q = (d / d0) * dlr;
+ *   and each float of cur rounded once from its double: neg_dlr = -dlr, c_m = d * (1 - b1), c_v = (d * d) * (1 - b2),
+ *   c_s = safeguard_warmup ? (d / d0) * d : q, first = (t == 0) as 1.0 / 0.0, d_eps = 0; r, 1 - r as sdt_adamw_select forms them.
+ *   Then dot = l1 = 0, q and lr_t are kept in state, *step = t + 1.
+ * sdt_prodigy_moments_step: element-wise over n (g float32 or bf16 as in sdt_lion8_step), with b1, b2, beta3 rounded to float32:
+ *     if first: p0 = p;   m' = b1 m + c_m gc;   v' = b2 v + c_v (gc gc);   s' = beta3 s + c_s gc;
+ *     dot += (double)gc * (double)(float)(p0 - p)   (exact products);   l1 += (double)|s'|
+ *   the two sums in double by ordered partials under sdt_sqnorm_accumulate's partition (each workgroup's threads walk float4s, x and z
+ *   into one accumulator, y and w into a second, the n & 3 tail in workgroup 0), accumulated into state across launches in launch order.
+ *   workspace: sdt_prodigy_workspace_bytes() bytes under the split-workspace contract.
+ * sdt_prodigy_finish: one lane, in double:
+ *     numer = beta3 * numer + q * dot;
+ *     if l1 != 0 and lr_t > 0:  d_hat = (d_coef * numer) / l1;  if d == d0: d = max(d, d_hat);  d_max = max(d_max, d_hat);
+ *                               d = min(d_max, d * growth_rate);
+ *     d_eps = (float)(d * eps)   (the new d; max(a, b) = b > a ? b : a, min(a, b) = b < a ? b : a; growth_rate may be +inf).
+ * sdt_prodigy_apply_step: element-wise, wd rounded to float32:
+ *     if wd != 0: p = p + (neg_dlr * wd) p;   p' = p + neg_dlr * (m' / (sqrtf(v') + d_eps));   ema' = r ema + (1 - r) p';   w_bf16 = bf16(p').
+ *   The step size is the dlr of the OLD d; only d_eps sees the new one.  lr_t == 0 moves nothing in p and leaves d alone.
+ * Refusals, before any HIP call: null pointers (ema, w_bf16, sqnorm and the tables may be NULL), buffers not 16-byte aligned (bf16 g and
+ * w_bf16: 8, state and step: 8), n < 0, non-finite hyper-parameters (growth_rate: NaN), d0 <= 0, b1 / b2 / beta3 outside [0, 1).  n == 0
+ * launches nothing. */
+int sdt_prodigy_select(int64_t* step, double* state, const float* lr_tab, int64_t n_lr, const float* ema_tab, int64_t n_ema, double lr,
+                       double ema_rate, double b1, double b2, double d0, int use_bias_correction, int safeguard_warmup, float* cur,
+                       hipStream_t stream);
+int sdt_prodigy_moments_step(const float* p, const void* g, int g_bf16, float* p0, float* m, float* v, float* s, int64_t n,
+                             const double* sqnorm, double max_norm, const float* cur, double* state, double b1, double b2, double beta3,
+                             void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int sdt_prodigy_finish(double* state, float* cur, double beta3, double d0, double d_coef, double growth_rate, double eps,
+                       hipStream_t stream);
+int sdt_prodigy_apply_step(float* p, const float* m, const float* v, float* ema, uint16_t* w_bf16, int64_t n, const float* cur, double wd,
+                           hipStream_t stream);
+int64_t sdt_prodigy_workspace_bytes(void);
 int sdt_lion8_quantize(const float* x, int8_t* codes, float* inv_scale, int64_t n, int block_size, const float* thresholds,
                        hipStream_t stream);
 int sdt_lion8_dequantize(const int8_t* codes, const float* inv_scale, float* x, int64_t n, int block_size,

@@ -72,6 +72,10 @@ SIGNATURES = {
     "sdt_adamw_select": [_P, _P, _P, _L, _P, _L, _D, _D, _D, _D, _P, _P],
     "sdt_adamw8_step": [_P, _P, _I, _P, _P, _P, _P, _P, _P, _L, _I, _P, _P, _D, _P, _D, _D, _D, _D, _P],
     "sdt_adamw32_step": [_P, _P, _P, _P, _P, _P, _L, _P, _D, _P, _D, _D, _D, _D, _P],
+    "sdt_prodigy_select": [_P, _P, _P, _L, _P, _L, _D, _D, _D, _D, _D, _I, _I, _P, _P],
+    "sdt_prodigy_moments_step": [_P, _P, _I, _P, _P, _P, _P, _L, _P, _D, _P, _P, _D, _D, _D, _P, _L, _P],
+    "sdt_prodigy_finish": [_P, _P, _D, _D, _D, _D, _D, _P],
+    "sdt_prodigy_apply_step": [_P, _P, _P, _P, _P, _L, _P, _D, _P],
     "sdt_lion8_quantize": [_P, _P, _P, _L, _I, _P, _P],
     "sdt_lion8_dequantize": [_P, _P, _P, _L, _I, _P],
     "sdt_groupnorm_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _I, _P, _L, _P],
@@ -127,7 +131,7 @@ SIGNATURES = {
 WS_QUERY = {"sdt_gemm_nt_workspace_bytes": [_L, _I, _I, _I], "sdt_gemm_tn_workspace_bytes": [_L, _I, _I, _I, _I, _I, _P], "sdt_layernorm_bwd_workspace_bytes": [_L, _I], "sdt_layernorm_bwd_partial_rows": [_L, _I],
             "sdt_groupnorm_bwd_workspace_bytes": [_I, _I, _I],
             "sdt_groupnorm_fwd_workspace_bytes": [_I, _I, _I, _I], "sdt_attention_bwd_workspace_bytes": [_P],
-            "sdt_gemm_tn_wgrad_group_workspace_bytes": [_P, _I], "sdt_conv_wgrad_group_workspace_bytes": [_P, _I], "sdt_reduce_workspace_bytes": [], "sdt_sqnorm_workspace_bytes": [], "sdt_colsum_workspace_bytes": [_I, _L, _I],
+            "sdt_gemm_tn_wgrad_group_workspace_bytes": [_P, _I], "sdt_conv_wgrad_group_workspace_bytes": [_P, _I], "sdt_reduce_workspace_bytes": [], "sdt_sqnorm_workspace_bytes": [], "sdt_prodigy_workspace_bytes": [], "sdt_colsum_workspace_bytes": [_I, _L, _I],
             "sdt_wgrad_sq_slots": [_I, _I, _I]}
 NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_lora_job_size": _I, "sdt_dora_job_size": _I, "sdt_last_error": ctypes.c_char_p}
 

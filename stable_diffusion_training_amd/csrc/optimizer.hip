@@ -8,6 +8,7 @@
 // Algorithmic bytes per parameter: g 4r + p 4r/4w + code 1r/1w + scale (4r/4w)/block (+ema 4r/4w, +bf16 2w).
 // This translation unit is compiled with -ffp-contract=off so that every multiply/add rounds
 // separately, as the NumPy float32 oracle (and XLA elementwise f32) does.
+#include <cmath>
 #include <type_traits>
 
 #include "sdt_common.h"
@@ -64,29 +65,55 @@ __device__ __forceinline__ void sq_accumulate(const f32x4_t v, double& d0, doubl
 // their double partial sums to `part`; the one that arrives last adds them in workgroup order into *out (no float / double atomics:
 // the result is bitwise reproducible).  PAIRWISE: the workgroup's partial is the tree over its four waves instead of their
 // sequential sum - the association each caller has always had.  Returns in every workgroup but the last early: call it last.
-template <bool PAIRWISE>
-__device__ __forceinline__ void ordered_sum_f64(double dacc, double* __restrict__ out, int* counter, double* __restrict__ part) {
-  for (int o = 32; o > 0; o >>= 1) dacc += __shfl_xor(dacc, o, 64);
-  __shared__ double dsc[16];
+// K sums at once (ordered_sums_f64): one arrival for all of them, `part` holds K runs of `part_stride` doubles and `out` K consecutive
+// doubles; each sum is formed exactly as a single one is.
+template <bool PAIRWISE, int K>
+__device__ __forceinline__ void ordered_sums_f64(double (&dacc)[K], double* __restrict__ out, int* counter, double* __restrict__ part,
+                                                 int part_stride) {
+#pragma unroll
+  for (int k = 0; k < K; ++k)
+    for (int o = 32; o > 0; o >>= 1) dacc[k] += __shfl_xor(dacc[k], o, 64);
+  __shared__ double dsc[K][16];
   __shared__ int s_last;
   const int w = threadIdx.x >> 6, nw = blockDim.x >> 6;
-  if ((threadIdx.x & 63) == 0) dsc[w] = dacc;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) dsc[k][w] = dacc[k];
+  }
   __syncthreads();
   if (threadIdx.x == 0) {
-    double t = 0.0;
-    if (PAIRWISE) t = (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]);
-    else for (int i = 0; i < nw; ++i) t += dsc[i];
-    sdt_store_wt(part + blockIdx.x, t);
+#pragma unroll
+    for (int k = 0; k < K; ++k) {
+      double t = 0.0;
+      if (PAIRWISE) t = (dsc[k][0] + dsc[k][1]) + (dsc[k][2] + dsc[k][3]);
+      else for (int i = 0; i < nw; ++i) t += dsc[k][i];
+      sdt_store_wt(part + (long)k * part_stride + blockIdx.x, t);
+    }
   }
   if (!sdt_arrive_last<true>(counter, (int)gridDim.x, &s_last)) return;
   // last arriver: 256 threads x strided partials, then a fixed tree
-  double t = 0.0;
-  for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t += sdt_load_wt(part + i);
-  for (int o = 32; o > 0; o >>= 1) t += __shfl_xor(t, o, 64);
+  double t[K];
+#pragma unroll
+  for (int k = 0; k < K; ++k) {
+    t[k] = 0.0;
+    for (int i = threadIdx.x; i < (int)gridDim.x; i += 256) t[k] += sdt_load_wt(part + (long)k * part_stride + i);
+    for (int o = 32; o > 0; o >>= 1) t[k] += __shfl_xor(t[k], o, 64);
+  }
   __syncthreads();
-  if ((threadIdx.x & 63) == 0) dsc[w] = t;
+  if ((threadIdx.x & 63) == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) dsc[k][w] = t[k];
+  }
   __syncthreads();
-  if (threadIdx.x == 0) *out += (dsc[0] + dsc[1]) + (dsc[2] + dsc[3]);
+  if (threadIdx.x == 0) {
+#pragma unroll
+    for (int k = 0; k < K; ++k) out[k] += (dsc[k][0] + dsc[k][1]) + (dsc[k][2] + dsc[k][3]);
+  }
+}
+template <bool PAIRWISE>
+__device__ __forceinline__ void ordered_sum_f64(double dacc, double* __restrict__ out, int* counter, double* __restrict__ part) {
+  double a[1] = {dacc};
+  ordered_sums_f64<PAIRWISE, 1>(a, out, counter, part, 0);
 }
 
 // Sum of squares in double: every product of two floats is exact in double and the running sum carries ~1e-16 relative
@@ -461,6 +488,188 @@ __global__ void __launch_bounds__(64) adamw_select_kernel(int64_t* __restrict__ 
   *step = t + 1;
 }
 
+// ------------------------------------------------------------------------------------------------------------- Prodigy
+// Third optimizer (include/sdt.h "Prodigy"): Adam-style moments scaled by the running distance estimate d, which two global sums
+// per step drive - so two sweeps with a one-lane kernel in front of, between and nothing behind them.  All state is float32.
+//   cur = {neg_dlr, ema_r, ema_rm, first, c_m, c_v, c_s, d_eps}  (prodigy_select_kernel; d_eps by prodigy_finish_kernel)
+//   st  = {d, d_max, numer, P1, P2, dot, l1, q, lr_t}             (doubles)
+enum { PRODIGY_D = 0, PRODIGY_DMAX, PRODIGY_NUMER, PRODIGY_P1, PRODIGY_P2, PRODIGY_DOT, PRODIGY_L1, PRODIGY_Q, PRODIGY_LRT };
+
+// The moments pass: the three state streams of one element, and its terms of the two sums.
+struct ProdigyMomentsRule {
+  float c1, c2, c3, c_m, c_v, c_s;
+  static constexpr int NS = 3;  // m, v, s
+  __device__ __forceinline__ void step(float gc, float dx, const float* st, float* ns, double& dot, double& l1) const {
+    ns[0] = c1 * st[0] + c_m * gc;
+    ns[1] = c2 * st[1] + c_v * (gc * gc);
+    ns[2] = c3 * st[2] + c_s * gc;
+    dot = fma((double)gc, (double)dx, dot);  // gc and dx are floats: the product is exact in double
+    l1 += (double)fabsf(ns[2]);
+  }
+};
+// The apply pass: p' from p, m', v'.
+struct ProdigyApplyRule {
+  float neg_dlr, neg_dlr_wd, d_eps;
+  bool decay;
+  __device__ __forceinline__ float step(float p, float m, float v) const {
+    if (decay) p = p + neg_dlr_wd * p;
+    return p + neg_dlr * (m / (sqrtf(v) + d_eps));
+  }
+};
+
+// sqnorm_kernel's partition (one workgroup per 2048 float4s, at most SQNORM_MAX_BLOCKS, a grid-stride loop beyond, the n & 3 tail in
+// workgroup 0) and its walk: the first accumulator of a pair takes x and z, the second y and w.
+template <bool G16>
+__global__ void __launch_bounds__(256) prodigy_moments_kernel(const float* __restrict__ p, const void* __restrict__ gv,
+                                                              float* __restrict__ p0, float* __restrict__ m, float* __restrict__ v,
+                                                              float* __restrict__ s, long n, const double* __restrict__ sqnorm,
+                                                              float max_norm, float c1, float c2, float c3,
+                                                              const float* __restrict__ cur, double* __restrict__ sums, int* counter,
+                                                              double* __restrict__ part, int part_stride) {
+  const Clip clip = clip_prologue(sqnorm, max_norm);
+  const bool first = cur[3] != 0.f;
+  const ProdigyMomentsRule rule = {c1, c2, c3, cur[4], cur[5], cur[6]};
+  const long nv = n >> 2;
+  double dot[2] = {0.0, 0.0}, l1[2] = {0.0, 0.0};
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long)gridDim.x * blockDim.x) {
+    f32x4_t g4;
+    if (G16) {
+      const uint2 h = reinterpret_cast<const uint2*>(gv)[i];
+      g4 = unpack4(h.x, h.y);
+    } else {
+      g4 = reinterpret_cast<const f32x4_t*>(gv)[i];
+    }
+    const f32x4_t p4 = reinterpret_cast<const f32x4_t*>(p)[i];
+    f32x4_t q4 = p4;
+    if (first) reinterpret_cast<f32x4_t*>(p0)[i] = p4;
+    else q4 = reinterpret_cast<const f32x4_t*>(p0)[i];
+    f32x4_t m4 = reinterpret_cast<const f32x4_t*>(m)[i];
+    f32x4_t v4 = reinterpret_cast<const f32x4_t*>(v)[i];
+    f32x4_t s4 = reinterpret_cast<const f32x4_t*>(s)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const float st[3] = {m4[j], v4[j], s4[j]};
+      float ns[3];
+      rule.step(clip(g4[j]), q4[j] - p4[j], st, ns, dot[j & 1], l1[j & 1]);
+      m4[j] = ns[0];
+      v4[j] = ns[1];
+      s4[j] = ns[2];
+    }
+    reinterpret_cast<f32x4_t*>(m)[i] = m4;
+    reinterpret_cast<f32x4_t*>(v)[i] = v4;
+    reinterpret_cast<f32x4_t*>(s)[i] = s4;
+  }
+  double acc[2] = {dot[0] + dot[1], l1[0] + l1[1]};
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {  // the < 4 elements behind the last float4
+    const long j = (nv << 2) + threadIdx.x;
+    const float g = G16 ? bf2f(reinterpret_cast<const bf16_t*>(gv)[j]) : reinterpret_cast<const float*>(gv)[j];
+    const float pj = p[j];
+    float qj = pj;
+    if (first) p0[j] = pj;
+    else qj = p0[j];
+    const float st[3] = {m[j], v[j], s[j]};
+    float ns[3];
+    rule.step(clip(g), qj - pj, st, ns, acc[0], acc[1]);
+    m[j] = ns[0];
+    v[j] = ns[1];
+    s[j] = ns[2];
+  }
+  ordered_sums_f64<false, 2>(acc, sums, counter, part, part_stride);
+}
+
+// A workgroup sweeps LION_SLICES consecutive slices of 256 float4s and the grid covers the buffer once (see sweep8_body).
+__global__ void __launch_bounds__(256) prodigy_apply_kernel(float* __restrict__ p, const float* __restrict__ m, const float* __restrict__ v,
+                                                            float* __restrict__ ema, bf16_t* __restrict__ w_bf16, long n, float wd,
+                                                            const float* __restrict__ cur) {
+  typedef unsigned u2v __attribute__((ext_vector_type(2)));
+  const float neg_dlr = cur[0], ema_r = cur[1], ema_rm = cur[2];
+  const ProdigyApplyRule rule = {neg_dlr, neg_dlr * wd, cur[7], wd != 0.f};
+  const long nv = n >> 2;
+  const long i_end = min(nv, ((long)blockIdx.x + 1) * (LION_SLICES * 256));
+  for (long i = (long)blockIdx.x * (LION_SLICES * 256) + threadIdx.x; i < i_end; i += 256) {
+    f32x4_t p4 = reinterpret_cast<const f32x4_t*>(p)[i];
+    const f32x4_t m4 = reinterpret_cast<const f32x4_t*>(m)[i];
+    const f32x4_t v4 = reinterpret_cast<const f32x4_t*>(v)[i];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) p4[j] = rule.step(p4[j], m4[j], v4[j]);
+    reinterpret_cast<f32x4_t*>(p)[i] = p4;
+    if (ema) {
+      const f32x4_t e4 = reinterpret_cast<const f32x4_t*>(ema)[i];
+      reinterpret_cast<f32x4_t*>(ema)[i] = ema_r * e4 + ema_rm * p4;
+    }
+    if (w_bf16) {
+      const u2v o = {pack2bf(p4.x, p4.y), pack2bf(p4.z, p4.w)};
+      reinterpret_cast<u2v*>(w_bf16)[i] = o;
+    }
+  }
+  if (blockIdx.x == 0 && threadIdx.x < (n & 3)) {
+    const long j = (nv << 2) + threadIdx.x;
+    const float pj = rule.step(p[j], m[j], v[j]);
+    p[j] = pj;
+    if (ema) ema[j] = ema_r * ema[j] + ema_rm * pj;
+    if (w_bf16) w_bf16[j] = f2bf(pj);
+  }
+}
+
+// Per-step scalars of a Prodigy store (include/sdt.h sdt_prodigy_select): one lane, in double, each float rounded once.
+__global__ void __launch_bounds__(64) prodigy_select_kernel(int64_t* __restrict__ step, double* __restrict__ st,
+                                                             const float* __restrict__ lr_tab, long n_lr, const float* __restrict__ ema_tab,
+                                                             long n_ema, double lr, float ema_r, float ema_rm, double b1, double b2, double d0,
+                                                             int bias_correction, int safeguard, float* __restrict__ cur) {
+  if (threadIdx.x != 0) return;
+  const int64_t t = *step;
+  double lr_t = lr;
+  if (lr_tab) {
+    const long tc = t > 0 ? (long)t : 0;
+    const long i = tc < n_lr - 1 ? tc : n_lr - 1;
+    const long j = tc < n_ema - 1 ? tc : n_ema - 1;
+    lr_t = -(double)lr_tab[i];
+    ema_r = ema_tab[2 * j];
+    ema_rm = ema_tab[2 * j + 1];
+  }
+  const double p1 = st[PRODIGY_P1] * b1, p2 = st[PRODIGY_P2] * b2;
+  st[PRODIGY_P1] = p1;
+  st[PRODIGY_P2] = p2;
+  const double bc = bias_correction ? sqrt(1.0 - p2) / (1.0 - p1) : 1.0;
+  const double d = st[PRODIGY_D];
+  const double dlr = (d * lr_t) * bc;
+  const double q = (d / d0) * dlr;
+  cur[0] = (float)(-dlr);
+  cur[1] = ema_r;
+  cur[2] = ema_rm;
+  cur[3] = t == 0 ? 1.f : 0.f;
+  cur[4] = (float)(d * (1.0 - b1));
+  cur[5] = (float)((d * d) * (1.0 - b2));
+  cur[6] = (float)(safeguard ? (d / d0) * d : q);
+  cur[7] = 0.f;
+  st[PRODIGY_DOT] = 0.0;
+  st[PRODIGY_L1] = 0.0;
+  st[PRODIGY_Q] = q;
+  st[PRODIGY_LRT] = lr_t;
+  *step = t + 1;
+}
+
+// The step's new d from the two sums (include/sdt.h sdt_prodigy_finish): one lane, between the moments and the apply sweeps.
+__global__ void __launch_bounds__(64) prodigy_finish_kernel(double* __restrict__ st, float* __restrict__ cur, double beta3, double d0,
+                                                             double d_coef, double growth_rate, double eps) {
+  if (threadIdx.x != 0) return;
+  const double numer = beta3 * st[PRODIGY_NUMER] + st[PRODIGY_Q] * st[PRODIGY_DOT];
+  const double l1 = st[PRODIGY_L1];
+  double d = st[PRODIGY_D];
+  st[PRODIGY_NUMER] = numer;
+  if (l1 != 0.0 && st[PRODIGY_LRT] > 0.0) {
+    const double d_hat = (d_coef * numer) / l1;
+    double d_max = st[PRODIGY_DMAX];
+    if (d == d0) d = d_hat > d ? d_hat : d;
+    d_max = d_hat > d_max ? d_hat : d_max;
+    const double grown = d * growth_rate;
+    d = grown < d_max ? grown : d_max;
+    st[PRODIGY_DMAX] = d_max;
+    st[PRODIGY_D] = d;
+  }
+  cur[7] = (float)(d * eps);
+}
+
 // ----------------------------------------------------------------------------------------------------------- host side
 // The float scalars every sweep and select launch derives from the entry points' doubles.
 struct HostScalars {
@@ -708,6 +917,86 @@ int sdt_adamw32_step(float* p, const float* g, float* m, float* v, float* ema, u
   hipLaunchKernelGGL(adamw32_kernel, dim3(sdt_grid_1d(n, 1024, 1 << 30)), dim3(256), 0, stream, p, g, m, v, ema, (bf16_t*)w_bf16, (long)n,
                      sqnorm, (float)max_norm, (float)wd, h.c1, h.c1m, h.c2, h.c2m, (float)eps, cur);
   SDT_LAUNCH_CHECK("sdt_adamw32_step");
+  return SDT_OK;
+}
+
+int64_t sdt_prodigy_workspace_bytes(void) { return SDT_WS_COUNTER_BYTES + 2 * SQNORM_MAX_BLOCKS * (int64_t)sizeof(double); }
+
+int sdt_prodigy_select(int64_t* step, double* state, const float* lr_tab, int64_t n_lr, const float* ema_tab, int64_t n_ema, double lr,
+                       double ema_rate, double b1, double b2, double d0, int use_bias_correction, int safeguard_warmup, float* cur,
+                       hipStream_t stream) {
+  SDT_CHECK_ARG(step && state && cur, "sdt_prodigy_select: null pointer");
+  SDT_CHECK_ARG((lr_tab != nullptr) == (ema_tab != nullptr), "sdt_prodigy_select: lr_tab and ema_tab come together or not at all");
+  SDT_CHECK_ARG(!lr_tab || (n_lr >= 1 && n_ema >= 1), "sdt_prodigy_select: every table needs at least one entry (n_lr=%ld, n_ema=%ld)",
+                (long)n_lr, (long)n_ema);
+  SDT_CHECK_ARG(std::isfinite(lr) && std::isfinite(ema_rate) && std::isfinite(d0), "sdt_prodigy_select: non-finite lr, ema_rate or d0");
+  SDT_CHECK_ARG(lr >= 0.0, "sdt_prodigy_select: lr must not be negative (got %g)", lr);
+  SDT_CHECK_ARG(d0 > 0.0, "sdt_prodigy_select: d0 must be positive (got %g)", d0);
+  SDT_CHECK_ARG(b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0, "sdt_prodigy_select: b1 and b2 must lie in [0, 1) (got %g, %g)", b1, b2);
+  SDT_CHECK_ARG((((uintptr_t)step | (uintptr_t)state | (uintptr_t)ema_tab) & 7) == 0 && ((uintptr_t)cur & 15) == 0,
+                "sdt_prodigy_select: misaligned step counter, state, table or block");
+  const HostScalars h = host_scalars(b1, b2, lr, ema_rate);
+  hipLaunchKernelGGL(prodigy_select_kernel, dim3(1), dim3(64), 0, stream, step, state, lr_tab, (long)n_lr, ema_tab, (long)n_ema, lr, h.er,
+                     h.erm, b1, b2, d0, use_bias_correction, safeguard_warmup, cur);
+  SDT_LAUNCH_CHECK("sdt_prodigy_select");
+  return SDT_OK;
+}
+
+int sdt_prodigy_moments_step(const float* p, const void* g, int g_bf16, float* p0, float* m, float* v, float* s, int64_t n,
+                             const double* sqnorm, double max_norm, const float* cur, double* state, double b1, double b2, double beta3,
+                             void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  SDT_CHECK_ARG(p && g && p0 && m && v && s && cur && state, "sdt_prodigy_moments_step: null pointer");
+  SDT_CHECK_ARG(n >= 0, "sdt_prodigy_moments_step: negative n (%ld)", (long)n);
+  SDT_CHECK_ARG(std::isfinite(max_norm) && b1 >= 0.0 && b1 < 1.0 && b2 >= 0.0 && b2 < 1.0 && beta3 >= 0.0 && beta3 < 1.0,
+                "sdt_prodigy_moments_step: max_norm must be finite and b1, b2, beta3 lie in [0, 1) (got %g, %g, %g, %g)", max_norm, b1, b2,
+                beta3);
+  SDT_CHECK_ARG((((uintptr_t)p | (uintptr_t)p0 | (uintptr_t)m | (uintptr_t)v | (uintptr_t)s | (uintptr_t)cur) & 15) == 0 &&
+                    ((uintptr_t)g & (g_bf16 ? 7 : 15)) == 0 && ((uintptr_t)state & 7) == 0,
+                "sdt_prodigy_moments_step: misaligned buffer");
+  SDT_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= sdt_prodigy_workspace_bytes(),
+                "sdt_prodigy_moments_step: workspace of sdt_prodigy_workspace_bytes() needed");
+  if (n == 0) return SDT_OK;
+  const dim3 grid(sdt_grid_1d(n >> 2, 256 * 8, SQNORM_MAX_BLOCKS)), block(256);  // sqnorm_kernel's grid: the same partition
+  int* counter = reinterpret_cast<int*>(workspace);
+  double* part = reinterpret_cast<double*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES);
+  const HostScalars h = host_scalars(b1, b2);
+  if (g_bf16)
+    hipLaunchKernelGGL(prodigy_moments_kernel<true>, grid, block, 0, stream, p, g, p0, m, v, s, (long)n, sqnorm, (float)max_norm, h.c1, h.c2,
+                       (float)beta3, cur, state + PRODIGY_DOT, counter, part, SQNORM_MAX_BLOCKS);
+  else
+    hipLaunchKernelGGL(prodigy_moments_kernel<false>, grid, block, 0, stream, p, g, p0, m, v, s, (long)n, sqnorm, (float)max_norm, h.c1, h.c2,
+                       (float)beta3, cur, state + PRODIGY_DOT, counter, part, SQNORM_MAX_BLOCKS);
+  SDT_LAUNCH_CHECK("sdt_prodigy_moments_step");
+  return SDT_OK;
+}
+
+int sdt_prodigy_finish(double* state, float* cur, double beta3, double d0, double d_coef, double growth_rate, double eps,
+                       hipStream_t stream) {
+  SDT_CHECK_ARG(state && cur, "sdt_prodigy_finish: null pointer");
+  SDT_CHECK_ARG(std::isfinite(beta3) && std::isfinite(d0) && std::isfinite(d_coef) && std::isfinite(eps) && !std::isnan(growth_rate),
+                "sdt_prodigy_finish: non-finite beta3, d0, d_coef or eps, or growth_rate is not a number");
+  SDT_CHECK_ARG(d0 > 0.0, "sdt_prodigy_finish: d0 must be positive (got %g)", d0);
+  SDT_CHECK_ARG(beta3 >= 0.0 && beta3 < 1.0, "sdt_prodigy_finish: beta3 must lie in [0, 1) (got %g)", beta3);
+  SDT_CHECK_ARG(growth_rate > 0.0 && d_coef > 0.0 && eps >= 0.0,
+                "sdt_prodigy_finish: growth_rate (+inf allowed) and d_coef must be positive, eps not negative (got %g, %g, %g)", growth_rate,
+                d_coef, eps);
+  SDT_CHECK_ARG(((uintptr_t)state & 7) == 0 && ((uintptr_t)cur & 15) == 0, "sdt_prodigy_finish: misaligned state or block");
+  hipLaunchKernelGGL(prodigy_finish_kernel, dim3(1), dim3(64), 0, stream, state, cur, beta3, d0, d_coef, growth_rate, eps);
+  SDT_LAUNCH_CHECK("sdt_prodigy_finish");
+  return SDT_OK;
+}
+
+int sdt_prodigy_apply_step(float* p, const float* m, const float* v, float* ema, uint16_t* w_bf16, int64_t n, const float* cur, double wd,
+                           hipStream_t stream) {
+  SDT_CHECK_ARG(p && m && v && cur, "sdt_prodigy_apply_step: null pointer");
+  SDT_CHECK_ARG(n >= 0, "sdt_prodigy_apply_step: negative n (%ld)", (long)n);
+  SDT_CHECK_ARG(std::isfinite(wd), "sdt_prodigy_apply_step: non-finite wd");
+  SDT_CHECK_ARG((((uintptr_t)p | (uintptr_t)m | (uintptr_t)v | (uintptr_t)ema | (uintptr_t)cur) & 15) == 0 && ((uintptr_t)w_bf16 & 7) == 0,
+                "sdt_prodigy_apply_step: misaligned buffer");
+  if (n == 0) return SDT_OK;
+  hipLaunchKernelGGL(prodigy_apply_kernel, dim3(sdt_grid_1d(n >> 2, 256 * LION_SLICES, 1 << 30)), dim3(256), 0, stream, p, m, v, ema,
+                     (bf16_t*)w_bf16, (long)n, (float)wd, cur);
+  SDT_LAUNCH_CHECK("sdt_prodigy_apply_step");
   return SDT_OK;
 }
 

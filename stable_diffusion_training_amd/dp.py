@@ -75,6 +75,10 @@ class GradReducer:
         a one-rank all-reduce is the identity, and RCCL's one-rank kernels (a 3.9 GB copy at ~1.2 TB/s beside the backward) say
         nothing about a real exchange; what is left is the cost of the structure itself.
         shard: sharded optimizer (module docstring); needs a world size that divides 8."""
+        stores = list(stores)
+        if shard and any(getattr(st, "optimizer", "lion") == "prodigy" for st in stores):
+            raise ValueError("GradReducer(shard=True): the sharded optimizer is not available for a Prodigy store (its two global sums "
+                             "would need a collective between the two sweeps); use the all-reduce exchange (shard=False)")
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0

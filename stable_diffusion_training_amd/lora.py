@@ -325,7 +325,7 @@ class LoraAdapter:
 
 def attach(base_store, cfg, **store_kwargs):
     """Hang a LoRA adapter on the frozen `base_store`.  store_kwargs configure the adapter's own ParamStore (quantise, quant_excluded,
-    wd_excluded, block_size, with_ema, optimizer, adam_betas).  ValueError: a trained base, a target that matches a convolution or a
+    wd_excluded, block_size, with_ema, optimizer, adam_betas, prodigy).  ValueError: a trained base, a target that matches a convolution or a
     padded kernel, no matching leaf, an invalid rank."""
     if not isinstance(cfg, LoraConfig):
         raise ValueError(f"attach: cfg must be a LoraConfig, not {type(cfg).__name__}")

@@ -18,7 +18,7 @@ import torch
 from . import _lib, lora as lora_mod, nets, ops, trace
 from .checkpoint import load_models, load_training_state, save_model, save_training_state  # noqa: F401  (reference names)
 from .lr_schedule import resolve as resolve_schedule
-from .params import EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
+from .params import PRODIGY_DEFAULTS, EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
 from .schedulers import _PTYPE, DDPMScheduler
 
 
@@ -122,6 +122,10 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
     optimizer: "lion" (the reference's), "adamw", or dict(name=, b1=, b2=, eps=, weight_decay=).  AdamW (8-bit block-quantised or fp32
     moments by the same quantize_* switches) takes the learning rates AS GIVEN - an Adam recipe needs no translation, so
     adam_to_lion_scale_factor does not apply - with wd=1e-2, b1=.9, b2=.999, eps=1e-8 unless the dict says otherwise.
+    "prodigy", or dict(name="prodigy", lr=, b1=, b2=, beta3=, eps=, weight_decay=, d0=, d_coef=, growth_rate=, use_bias_correction=,
+    safeguard_warmup=): the learning-rate-free optimizer (include/sdt.h "Prodigy").  The learning rates above are NOT USED: Prodigy steps
+    by d * lr with d estimated while it trains, lr is a multiplier that defaults to 1 (schedules scale it), weight_decay defaults to 0.
+    Its state is float32 whatever the quantize_* switches say (they still decide which gradients are kept in bf16).
     lora: None, or dict(unet=lora.LoraConfig, text_encoder=lora.LoraConfig | None | "frozen").  The base stores are then built frozen
     (trainable=False) and loaded once; every setting above (quantisation, decay and quantisation exclusions, EMA, optimizer, rates and
     schedules) configures the ADAPTER's store of that model instead (TrainState.adapter.store), which is the one that steps.  A text
@@ -140,20 +144,27 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                              "text_encoder='frozen'")
         lora = {"unet": lora["unet"], "text_encoder": te_l}
     opt = {"name": optimizer} if isinstance(optimizer, str) else dict(optimizer)
-    unknown = set(opt) - {"name", "b1", "b2", "eps", "weight_decay"}
-    if unknown or opt.get("name") not in ("lion", "adamw"):
-        raise ValueError(f"optimizer: 'lion', 'adamw' or dict(name=, b1=, b2=, eps=, weight_decay=), not {optimizer!r}")
+    prodigy = opt.get("name") == "prodigy"
+    allowed = {"name", "b1", "b2", "eps", "weight_decay"} | (({"lr"} | set(PRODIGY_DEFAULTS)) if prodigy else set())
+    unknown = set(opt) - allowed
+    if unknown or opt.get("name") not in ("lion", "adamw", "prodigy"):
+        raise ValueError(f"optimizer: 'lion', 'adamw', 'prodigy' or dict(name=, b1=, b2=, eps=, weight_decay=) (Prodigy's dict also takes "
+                         f"lr= and {sorted(set(PRODIGY_DEFAULTS) - {'b1', 'b2'})}), not {optimizer!r}")
     if opt["name"] == "lion" and len(opt) > 1:
         raise ValueError("optimizer: Lion's hyper-parameters are the reference's (adam_to_lion_scale_factor); the dict form is AdamW's")
     adamw = opt["name"] == "adamw"
 
     def make(spec, weights, cfg, fn, lr, quant, ema, which):
-        if adamw:
+        if prodigy:  # the config's learning rate is not used: lr multiplies the estimated d
+            hyper = dict(lr=opt.get("lr", 1.0), wd=opt.get("weight_decay", 0.0), eps=opt.get("eps", 1e-8), max_norm=1.0)
+        elif adamw:
             hyper = dict(lr=lr, wd=opt.get("weight_decay", 1e-2), b1=opt.get("b1", 0.9), b2=opt.get("b2", 0.999),
                          eps=opt.get("eps", 1e-8), max_norm=1.0)
         else:
             hyper = dict(lr=lr / adam_to_lion_scale_factor, wd=1e-2 * adam_to_lion_scale_factor, b1=0.9, b2=0.99, max_norm=1.0)
         okw = dict(optimizer="adamw", adam_betas=(hyper["b1"], hyper["b2"])) if adamw else {}
+        if prodigy:
+            okw = dict(optimizer="prodigy", prodigy={k: opt[k] for k in PRODIGY_DEFAULTS if k in opt})
         sched = resolve_schedule(lr_scheduler, hyper["lr"], ema_rate, lr_schedule=lr_schedule, ema_schedule=ema_schedule)
         if lora is not None:
             base = ParamStore(spec, device=device, trainable=False)
