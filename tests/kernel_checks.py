@@ -9,7 +9,10 @@ file and the CPU proof share.
 
 The second half serves tests/test_gpu_reduce_optim_exact.py: exact scalar sums with a report that names the missing partial, tail
 element or overwritten destination, mirrors of the reduction launchers' partitions, the optimizer references (oracle/lion8.py itself),
-the posterior-sample and timestep-embedding bounds, and the case tables with the bound that makes each of them exact."""
+the posterior-sample and timestep-embedding bounds, and the case tables with the bound that makes each of them exact.
+
+The last part serves tests/test_gpu_norm_exact.py: balanced norm inputs whose float64 result is exactly representable, the expectation
+with the assertions that make it unique, a mirror of the GroupNorm launch geometry for failure reports, and the case tables."""
 import math
 
 import numpy as np
@@ -24,7 +27,7 @@ _INT_VIEW = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.floa
              torch.int8: torch.int8, torch.int32: torch.int32}
 # what an untouched output element holds: NaN patterns for the float types, so that an element the kernel never wrote also fails
 # the value comparison
-SENTINEL = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.float64: 0x7FF5A5A5A5A5A5A5, torch.int8: 0x5A}
+SENTINEL = {torch.bfloat16: 0x7FA5, torch.float32: 0x7FA5A5A5, torch.float64: 0x7FF5A5A5A5A5A5A5, torch.int8: 0x5A, torch.int32: 0x5A5A5A5A}
 
 
 def bits(t):
@@ -289,6 +292,11 @@ def worst_slices(rel, k=3):
     flat = rel.reshape(-1)
     v, i = flat.topk(min(k, flat.numel()))
     return [(c, float(e)) for c, e in zip(_coords(i.cpu(), tuple(rel.shape)), v.tolist())]
+
+
+# The per-slice rules (attention rows, norm slices, norm parameter-gradient channels): kernel worst slice <= ROW_FACTOR x the worst
+# slice of the rounding-point emulation (what the emulation leaves out: attention_ref_and_emulation)
+ROW_FACTOR = 3.0
 
 
 # ------------------------------------------------------------------------------------------------ selector attention
@@ -1015,3 +1023,328 @@ def exact_case_bounds():
     for D, nseq, pat, vocab in EMB_CASES:
         out.append((f"embedding {(D, nseq, pat)}", 3 * nseq * EMB_S + 100, LIMIT))
     return out
+
+
+# ================================================================================================ norms on balanced inputs
+# (tests/test_gpu_norm_exact.py; their proof on the CPU: tests/test_kernel_checks_cpu.py)
+#
+# A norm divides by a standard deviation, so random inputs have no unique result.  Here every (image, group) - every LayerNorm row -
+# holds only the two values c - s and c + s, equally often: mean c, variance s^2, xhat = +-1, all exact, and with gamma in {+-1, +-2}
+# and an integer beta, |beta| > |gamma|, y = +-gamma + beta is a small non-zero integer.  The kernels' fp32 arithmetic is NOT exact
+# (1 / count rounds, rsqrtf approximates, eps is added), but it moves a value by about 1e-5 relative and a bf16-representable value
+# lies at least 2^-10 relative from the nearest rounding boundary: RNE lands on it, and the float64 result is the unique expectation.
+NORM_COMBOS = [(-2, 1), (-1, 1), (-1, 2), (0, 1), (0, 2), (1, 1), (1, 2), (2, 1)]  # (c, s), |c| + s <= 3; equal c only next to each other
+NORM_DRES_BIG = (128, 255)  # |dres| of every fourth element: dx = +-0.5, +-1.5 plus one of these is a bf16 TIE (ulp 1 from 128 to 256)
+
+
+NORM_COMBO_STEP, NORM_COMBO_IMAGE_STEP = 3, 5  # NORM_COMBOS entries 2, 3 or 5 apart (mod 8) never share c
+
+
+def balanced_norm_inputs(nslices, n, seed, per_image=None):
+    """Per slice (nslices of n elements, n % 4 == 0; images of per_image slices each, default: one image), float32 [nslices][n]:
+      x = c + s * sign, sign = +-1 equally often in a seeded order, (c, s) = NORM_COMBOS[(3 * slice in its image + 5 * image + seed)
+        % 8]: a slice never shares c with its neighbours (the group or row before and after), nor with the same group of the image
+        before or after (index 5 apart) or two images away (10 = 2 apart), whatever the number of groups - so the true {sum, sumsq},
+        mean and mostly rstd (6 index pairs of 8) differ from image to image and another image's statistics show;
+      gdy = a + b * sign + r, what gamma * dy must be: a, b non-zero integers in +-{1, 2} per slice; r non-zero integers in +-{1, 2, 3}
+        laid out as quadruples (u, -u, w, -w) on sign (+, +, -, -), so sum r = sum r * sign = 0 over the slice.
+    Returns dict(x, sign, gdy, r, c, s, a, b) (c, s, a, b: float32 [nslices])."""
+    assert n % 4 == 0, f"a slice of {n} elements cannot be balanced in quadruples"
+    g = torch.Generator().manual_seed(seed)
+    perm = torch.rand(nslices, n, generator=g).argsort(1)
+    h, q = n // 2, n // 4
+    sorted_sign = torch.cat([torch.ones(h), -torch.ones(h)]).expand(nslices, n)
+    pm = lambda shape: torch.randint(0, 2, shape, generator=g).float() * 2 - 1
+    u = torch.randint(1, 4, (nslices, q), generator=g).float() * pm((nslices, q))
+    w = torch.randint(1, 4, (nslices, q), generator=g).float() * pm((nslices, q))
+    sorted_r = torch.cat([u, -u, w, -w], 1)
+    sign = torch.empty(nslices, n).scatter_(1, perm, sorted_sign)
+    r = torch.empty(nslices, n).scatter_(1, perm, sorted_r)
+    per_image = nslices if per_image is None else per_image
+    sl = torch.arange(nslices)
+    k = (NORM_COMBO_STEP * (sl % per_image) + NORM_COMBO_IMAGE_STEP * (sl // per_image) + seed) % 8
+    combos = torch.tensor(NORM_COMBOS, dtype=torch.float32)
+    c, s = combos[k, 0], combos[k, 1]
+    a = torch.randint(1, 3, (nslices,), generator=g).float() * pm((nslices,))
+    b = torch.randint(1, 3, (nslices,), generator=g).float() * pm((nslices,))
+    return dict(x=c[:, None] + s[:, None] * sign, sign=sign, gdy=a[:, None] + b[:, None] * sign + r, r=r, c=c, s=s, a=a, b=b)
+
+
+def balanced_affine(C, seed):
+    """gamma in {+-1, +-2}, beta an integer with |gamma| < |beta| <= |gamma| + 2 (float32 [C]); dgamma / dbeta previous values (non-zero integers)."""
+    g = torch.Generator().manual_seed(seed)
+    pm = lambda: torch.randint(0, 2, (C,), generator=g).float() * 2 - 1
+    gamma = torch.randint(1, 3, (C,), generator=g).float() * pm()
+    beta = (gamma.abs() + torch.randint(1, 3, (C,), generator=g).float()) * pm()
+    prev_g = torch.randint(1, 100, (C,), generator=g).float() * pm()
+    prev_b = torch.randint(1, 100, (C,), generator=g).float() * pm()
+    return gamma, beta, prev_g, prev_b
+
+
+def balanced_dres(shape, seed):
+    """float32 integers: -3..3, and every fourth element (seeded phase) +-(128..255), which turns a half-odd dx into a tie."""
+    g = torch.Generator().manual_seed(seed)
+    d = torch.randint(-3, 4, shape, generator=g).float()
+    big = torch.randint(NORM_DRES_BIG[0], NORM_DRES_BIG[1] + 1, shape, generator=g).float() * (torch.randint(0, 2, shape, generator=g).float() * 2 - 1)
+    return torch.where(torch.randint(0, 4, shape, generator=g) == 0, big, d)
+
+
+def _group_major(t, B, HW, G, cpg):
+    """[B * G][HW * cpg] -> (B, HW, C)"""
+    return t.view(B, G, HW, cpg).permute(0, 2, 1, 3).reshape(B, HW, G * cpg)
+
+
+def groupnorm_balanced_case(B, HW, C, G, seed, dres=False):
+    """dict(x, dy (bf16 (B, HW, C)), gamma, beta, prev_dgamma, prev_dbeta (float32 [C]), c, s, a, b (float32 (B, G)), r (float32 like
+    x), cnt, and with dres: dres (bf16 like x)).  Element order inside a group is the kernels': pixel-major, channel-minor."""
+    cpg = C // G
+    n = HW * cpg
+    sl = balanced_norm_inputs(B * G, n, seed, per_image=G)
+    gamma, beta, pg, pb = balanced_affine(C, seed + 1)
+    gm = lambda t: _group_major(t, B, HW, G, cpg)
+    dy = gm(sl["gdy"]) / gamma
+    out = dict(x=gm(sl["x"]).to(BF), dy=dy.to(BF), gamma=gamma, beta=beta, prev_dgamma=pg, prev_dbeta=pb, r=gm(sl["r"]), cnt=n,
+               **{k: sl[k].view(B, G) for k in ("c", "s", "a", "b")})
+    assert torch.equal(out["dy"].float(), dy), "dy is not exact in bf16"
+    if dres:
+        out["dres"] = balanced_dres((B, HW, C), seed + 2).to(BF)
+    return out
+
+
+def layernorm_balanced_case(M, C, seed, dres=False):
+    """The LayerNorm form of groupnorm_balanced_case: x, dy (M, C); c, s, a, b [M]."""
+    sl = balanced_norm_inputs(M, C, seed)
+    gamma, beta, pg, pb = balanced_affine(C, seed + 1)
+    dy = sl["gdy"] / gamma
+    out = dict(x=sl["x"].to(BF), dy=dy.to(BF), gamma=gamma, beta=beta, prev_dgamma=pg, prev_dbeta=pb, r=sl["r"], cnt=C,
+               **{k: sl[k] for k in ("c", "s", "a", "b")})
+    assert torch.equal(out["dy"].float(), dy), "dy is not exact in bf16"
+    if dres:
+        out["dres"] = balanced_dres((M, C), seed + 2).to(BF)
+    return out
+
+
+def norm_exact_expectation(case, groups, eps_kernel):
+    """The unique results of a balanced case from the ordinary float64 formula with eps = 0 (norm_ref_and_emulation's float64 branch),
+    after asserting what makes them unique: y and dx are bf16-representable and non-zero, every sum is an integer (dgamma / dbeta:
+    a multiple of 1/2) below 2^24.  Nothing of the kernels enters.
+    Returns dict: y, dx (bf16), dx_dres (bf16, with dres: bf16(bf16(dx) + dres), two roundings), stats (float32 (B, G, 2) {sum, sumsq},
+    GroupNorm), mean, rstd (float32 per slice), dgamma, dbeta (float64 sums WITHOUT the previous values), and for the counts that
+    are not powers of two (eps_kernel > 0): ref / emu / terms of dgamma and dbeta at eps_kernel, for the per-channel rule."""
+    x, dy, gamma, beta = case["x"], case["dy"], case["gamma"], case["beta"]
+    ref, _, _ = norm_ref_and_emulation(x, gamma, beta, dy, groups, 0.0, False)
+    out = {}
+    for n in ("y", "dx"):
+        v = ref[n]
+        assert torch.equal(v.float().to(BF).double(), v), f"{n}: the float64 result is not bf16-representable"
+        assert bool((v != 0).all()), f"{n}: a true zero - the kernel's perturbed value would not round to it"
+        out[n] = v.float().to(BF)
+    xd = x.double()
+    if groups:
+        B, HW, C = x.shape
+        xg = xd.view(B, HW, groups, C // groups)
+        stats = torch.stack([xg.sum((1, 3)), (xg * xg).sum((1, 3))], -1)
+        assert float(stats.abs().max()) < LIMIT and torch.equal(stats, stats.round())
+        out["stats"] = stats.float()
+        mean, var = stats[..., 0] / case["cnt"], stats[..., 1] / case["cnt"] - (stats[..., 0] / case["cnt"]) ** 2
+    else:
+        assert float((xd * xd).sum(1).max()) < LIMIT
+        mean, var = xd.mean(1), (xd * xd).mean(1) - xd.mean(1) ** 2
+    assert torch.equal(mean, case["c"].double().view(mean.shape)) and torch.equal(var, (case["s"].double() ** 2).view(var.shape))
+    out["mean"], out["rstd"] = mean.float(), (1.0 / var.sqrt()).float()
+    assert torch.equal(out["rstd"].double() ** 2 * var, torch.ones_like(var))
+    sgn = ((xd.view(-1, case["cnt"]) if not groups else xg.permute(0, 2, 1, 3).reshape(-1, case["cnt"])) - mean.reshape(-1, 1)).sign()
+    rr = case["r"].double() / (case["s"].double().view(-1)[:, None] if not groups
+                                else case["s"].double().repeat_interleave(C // groups, 1)[:, None, :])
+    assert torch.equal(ref["dx"], rr), "dx is not r / s: the construction of dy is off"
+    assert bool((sgn.abs() == 1).all())
+    lead = tuple(range(x.dim() - 1))
+    for n in ("dgamma", "dbeta"):
+        v = ref[n]
+        assert torch.equal(v * 2, (v * 2).round()), f"{n}: not a multiple of 1/2"
+        mag = (dy.double().abs()).sum(lead)
+        assert float(mag.max()) + 100 < LIMIT, f"{n}: partial sums may leave the exact range of fp32"
+        out[n] = v
+    if "dres" in case:
+        out["dx_dres"] = (out["dx"].float() + case["dres"].float()).to(BF)  # fp32 sum of two bf16 values with |.| < 2^9: exact; then RNE
+    if eps_kernel > 0:
+        r2, e2, t2 = norm_ref_and_emulation(x, gamma, beta, dy, groups, eps_kernel, False)
+        out["rule2"] = dict(ref={n: r2[n] for n in ("dgamma", "dbeta")}, emu={n: e2[n] for n in ("dgamma", "dbeta")}, terms=t2)
+    return out
+
+
+def param_grad_rule(got, prev, rule2, name):
+    """The per-channel rule of the per-slice norm test (test_gpu_kernel_exact._norm_slices), for counts that are not powers of two:
+    |got - prev - ref| / sum |terms| of the worst channel <= ROW_FACTOR x the torch fp32 emulation's, floored at 2^-24.
+    Returns (message or None, kernel worst, emulation worst)."""
+    rk = (got.double() - prev.double() - rule2["ref"][name]).abs() / rule2["terms"][name]
+    re = (rule2["emu"][name] - rule2["ref"][name]).abs() / rule2["terms"][name]
+    (ik, wk), (ie, we) = worst_slices(rk, 1)[0], worst_slices(re, 1)[0]
+    ok = wk <= ROW_FACTOR * max(we, 2.0 ** -24)
+    msg = None if ok else f"{name}: kernel worst channel {wk:.3e} at {ik} > {ROW_FACTOR} x max(emulation worst channel {we:.3e}, 2^-24)"
+    return msg, wk, we
+
+
+def is_pow2(n):
+    return n & (n - 1) == 0
+
+
+# ---- mirror of the GroupNorm launch geometry (norm.hip gn_layout, gn_chunks, gn_stat_chunks and the workspace queries)
+GN_FINE_BLOCKS, GN_MAX_INLINE_PARTS, GN_L2_PARTS = 1024, 128, 32
+
+
+def gn_layout(C):
+    """(Cv, TX, TY, J): 8-channel vectors, threads across the vectors, thread rows (pixels in flight), vectors per thread."""
+    Cv = C >> 3
+    TX = min(Cv, 256)
+    return Cv, TX, 256 // TX, -(-Cv // TX)
+
+
+def gn_chunks(B, HW, C, stats):
+    """(chunks per image, pixels per chunk) of the apply kernels (stats False) or of the statistics passes (at most 128 per image)."""
+    target = max(GN_FINE_BLOCKS // B, 1)
+    if stats:
+        target = min(target, GN_MAX_INLINE_PARTS)
+    ty = gn_layout(C)[2]
+    ppb = max(-(-HW // target), 4 * ty)
+    return -(-HW // ppb), ppb
+
+
+def gn_fwd_workspace_bytes(B, HW, C, G):
+    return max(gn_chunks(B, HW, C, True)[0], GN_L2_PARTS) * B * 2 * G * 4
+
+
+def gn_bwd_workspace_bytes(B, HW, C):
+    return gn_chunks(B, HW, C, True)[0] * B * (2 * C + 128) * 4
+
+
+def gn_locate(B, HW, C, G, b, p, ch):
+    """Where element (image b, pixel p, channel ch) is handled, as text for a failure report."""
+    Cv, TX, TY, J = gn_layout(C)
+    cv = ch >> 3
+    out = [f"image {b} group {ch // (C // G)} (pixel {p}, channel {ch}; vector {cv} = thread column {cv % TX}, j = {cv // TX} of {J}, element {ch & 7})"]
+    for stats in (False, True):
+        nch, ppb = gn_chunks(B, HW, C, stats)
+        out.append(f"{'statistics' if stats else 'apply'} pass: chunk {p // ppb} of {nch} ({ppb} pixels each, the last {HW - (nch - 1) * ppb}), "
+                   f"thread row {(p % ppb) % TY} of {TY}")
+    return "; ".join(out)
+
+
+def gn_mismatch_report(got, want, what, B, HW, C, G):
+    """mismatch_report over (B, HW, C) tensors, with the chunk and thread row of the first differing element."""
+    msg = mismatch_report(got.reshape(B, HW, C), want.reshape(B, HW, C), what)
+    if msg is None:
+        return None
+    i = int((bits(got.reshape(-1)) != bits(want.reshape(-1))).nonzero()[0])
+    return msg + "\n  first: " + gn_locate(B, HW, C, G, i // (HW * C), (i // C) % HW, i % C)
+
+
+def gn_parts_decomposition(totals, nparts, seed):
+    """Integer rows [B][nparts][G][2] (float32) that add up to totals (B, G, 2): in every column the magnitudes 1 .. nparts in a seeded
+    order (no two rows alike, so a difference names ONE row) with seeded signs; the last row takes the rest.  sum |rows| <= 2048 * 2049 / 2
+    + |totals| stays below 2^24, so the sum is exact in any order."""
+    g = torch.Generator().manual_seed(seed)
+    B, G, _ = totals.shape
+    mag = torch.rand(B, nparts, G, 2, generator=g).argsort(1).float() + 1
+    rows = mag * (torch.randint(0, 2, (B, nparts, G, 2), generator=g).float() * 2 - 1)
+    rows[:, -1] = totals.float() - rows[:, :-1].sum(1)
+    assert torch.equal(rows.double().sum(1), totals.double()) and float(rows.abs().sum(1).max()) < LIMIT
+    return rows
+
+
+def stats_report(got, want, what, parts=None):
+    """stats (B, G, 2) against the exact totals: None, or sum_report's message for the first differing entry, which names the partial row
+    (parts [B][nparts][G][2]) whose value the difference equals."""
+    bad = (bits(got.float().contiguous()) != bits(want.float().contiguous())).nonzero()
+    if bad.numel() == 0:
+        return None
+    b, g, w = (int(v) for v in bad[0])
+    col = None if parts is None else parts[b, :, g, w]
+    return f"{bad.shape[0]} of {got.numel()} statistics differ; " + sum_report(got[b, g, w], want[b, g, w], f"{what} image {b} group {g} {'sumsq' if w else 'sum'}", parts=col)
+
+
+# ---- case tables (id, B, HW, C, G); the CPU proof holds the branch each id names to the mirror above
+GN_BALANCED_CASES = [
+    ("pow2_cpg2", 2, 64, 64, 32),                    # count 128: exact regime
+    ("pow2_cpg8", 1, 256, 256, 32),                  # count 2048: exact regime
+    ("cpg10_straddle_ty6", 3, 100, 320, 32),         # 8-wide vectors straddle groups, TY = 6 leaves 16 threads idle
+    ("cpg3", 2, 36, 96, 32),
+    ("cpg1_fewer_pixels_than_thread_rows", 1, 8, 32, 32),
+    ("j2_ragged_second_vector", 2, 4, 2560, 32),
+    ("g64_widest_c4096", 1, 60, 4096, 64),
+    ("ty1_128_stat_rows_ragged_last", 2, 636, 2048, 32),  # 127 chunks of 5 pixels and one of 1; the apply pass cuts it in 159 chunks of 4
+    ("g8", 2, 1028, 64, 8),
+    ("g24_2g_not_dividing_256", 1, 16, 48, 24),
+    ("g1", 2, 12, 8, 1),
+]
+# producer statistics: (case id of GN_BALANCED_CASES, nparts); <= 128 rows: the apply prologue; more: gn_group_reduce_kernel first
+GN_PARTS_CASES = [(cid, n) for cid in ("pow2_cpg2", "cpg10_straddle_ty6") for n in (1, 2, 127, 128, 129, 200, 2048)] + [
+    ("g24_2g_not_dividing_256", 7), ("g24_2g_not_dividing_256", 200), ("g64_widest_c4096", 129), ("g1", 200)]
+
+# LayerNorm: (id, M, C)
+LN_BALANCED_CASES = [
+    ("smallest", 1, 8),
+    ("nr4_clamped_tail_row", 5, 48),
+    ("maxv2_nr2_odd_m", 33, 520),
+    ("maxv4", 7, 2048),
+    ("cv129_ragged_third_vector", 3, 1032),
+    ("grid_stride_loop", 16389, 8),
+    ("workload_308x768", 308, 768),
+]
+# CLIP pooling: (D, R, windows, S, eos_id (-1: argmax))
+CLIP_POOL_CASES = [(8, 3, 2, 13, -1), (48, 4, 1, 77, 7), (1032, 3, 2, 11, -1), (2048, 3, 3, 9, 5)]
+
+
+def gn_case(cid):
+    return next(c for c in GN_BALANCED_CASES if c[0] == cid)
+
+
+def ln_case(cid):
+    return next(c for c in LN_BALANCED_CASES if c[0] == cid)
+
+
+def gn_balanced(cid):
+    """The operands of a GN_BALANCED_CASES row (seed: 100 + its place in the table), the same for the GPU file and its CPU proof."""
+    _, B, HW, C, G = gn_case(cid)
+    return groupnorm_balanced_case(B, HW, C, G, 100 + GN_BALANCED_CASES.index(gn_case(cid)), dres=True)
+
+
+def ln_balanced(cid):
+    """The operands of an LN_BALANCED_CASES row (seed: 200 + its place in the table)."""
+    _, M, C = ln_case(cid)
+    return layernorm_balanced_case(M, C, 200 + LN_BALANCED_CASES.index(ln_case(cid)), dres=True)
+
+
+def ln_rows_per_block(C):
+    """norm.hip ln_rows_per_block: rows one workgroup of four waves takes per pass (each wave NR = 4, 2 or 1 rows)."""
+    return 16 if C <= 512 else 8 if C <= 1024 else 4
+
+
+def ln_geometry(M, C):
+    """Text for a failure report: the row split of ln_bwd_kernel (at most 1024 workgroups, grid-stride beyond)."""
+    rpb = ln_rows_per_block(C)
+    return f"rows per wave pass {rpb // 4}, rows per workgroup pass {rpb}, workgroups {min(1024, -(-M // rpb))}"
+
+
+def clip_pool_case(D, R, windows, S, eos_id, seed):
+    """ids (R * windows, S) int32 and the pooled positions: row r * windows has its key (the largest id for eos_id < 0, else eos_id)
+    FIRST at pos[r] and again later where there is room; pos covers position 0, the last one (inside the ragged slab) and one in
+    between; with eos_id >= 0 the last pooled row holds no EOS at all (position 0).  x (R * windows, S, D) bf16: integers in -3..3
+    everywhere, a balanced row at every pooled position.  Returns dict(ids, pos, x, rows = layernorm_balanced_case(R, D))."""
+    g = torch.Generator().manual_seed(seed)
+    ids = torch.randint(10, 1000, (R * windows, S), generator=g).to(torch.int32)
+    pos = torch.tensor([(0, S - 1, S // 2, 1)[r % 4] for r in range(R)], dtype=torch.int32)
+    key = 5000 if eos_id < 0 else eos_id
+    for r in range(R):
+        if eos_id >= 0 and r == R - 1 and R > 1:
+            pos[r] = 0
+            continue
+        p = int(pos[r])
+        ids[r * windows, p] = key
+        if p + 2 < S:
+            ids[r * windows, p + 2] = key
+    rows = layernorm_balanced_case(R, D, seed + 1)
+    x = exact_ints((R * windows, S, D), -3, 3, seed + 2)
+    for r in range(R):
+        x[r * windows, int(pos[r])] = rows["x"][r]
+    return dict(ids=ids, pos=pos, x=x, rows=rows)

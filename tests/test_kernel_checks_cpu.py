@@ -3,7 +3,10 @@ a correct expectation, plant the defects a whole-tensor norm cannot see (one ele
 column that lost its product term, one store outside the output) and assert that the checkers of tests/kernel_checks.py report each
 at the right coordinates.  Plus the arithmetic the exact tests rest on: every exact case keeps sum |a||b| below 2^24.
 The same for tests/test_gpu_reduce_optim_exact.py (second half of this file): a missing workgroup partial, a dropped tail element, = for
-+=, a non-zero counter, a code off by one, a neighbour's inverse scale, an unclipped log-variance, exchanged sin / cos halves."""
++=, a non-zero counter, a code off by one, a neighbour's inverse scale, an unclipped log-variance, exchanged sin / cos halves.
+And for tests/test_gpu_norm_exact.py (the end of this file): the balanced cases have a unique representable result that fp32 arithmetic of
+the kernels' shape lands on, the geometry mirror is the library's, and a neighbour group's mean, a dropped partial row, an early dres
+and = for += are each caught."""
 import math
 
 import numpy as np
@@ -659,3 +662,218 @@ def test_documented_refusals_of_the_reduction_and_optimizer_entry_points(lib):
     for g in (A, B_, O, I8, D64, WS):
         ref = kc.Guarded(8, 64, g.dtype, "cpu")
         assert torch.equal(kc.bits(g.arena), kc.bits(ref.arena)), "a refused call wrote into a buffer"
+
+
+# ================================================================================================ norms on balanced inputs
+# (the checkers, generators and case tables of tests/test_gpu_norm_exact.py)
+def _ulps(t, k):
+    """fp32 tensor moved by k units in the last place."""
+    return (t.contiguous().view(torch.int32) + k).view(torch.float32)
+
+
+def _norm_model(case, G, eps, rstd_ulps=0, fault=None, stats=None):
+    """A torch fp32 restatement of the norm kernels' formulas (norm.hip), NOT used by the GPU tests: it shows that the float64
+    expectation is what fp32 arithmetic of this shape lands on.  GroupNorm (G > 0; gn_apply_kernel, gn_bwd_stats_kernel,
+    gn_bwd_apply_kernel): mean = tot * fl(1 / cnt), var = tot2 * fl(1 / cnt) - mean^2, rstd = fl((var + eps)^-1/2) moved by rstd_ulps
+    (rsqrtf is an approximation), a = rstd * gamma, sh = beta - mean * a, y = bf16(a x + sh); xhat = (x - mean) * rstd, {S1, S2} =
+    sums of gamma dy {1, xhat}, k = rstd * S * fl(1 / cnt), dx = bf16(rstd gamma dy - k1 - xhat k2), with dres bf16(bf16(dx) + dres).
+    LayerNorm (G = 0; ln_fwd_kernel, ln_bwd_kernel): mean = s / C, y = bf16((x - mean) * rstd * gamma + beta), dx = bf16(rstd * (g - s1 -
+    xhat * s2)).  dgamma / dbeta = previous value + fp32 sums.  fault: 'neighbour_mean' (group g normalises with the mean of group
+    g + 1), 'previous_image' (image b normalises, forward and backward, with the statistics of image b - 1; the stats output stays right),
+    'dres_early' (dres added before the first rounding), 'store' (= where += belongs)."""
+    f = torch.float32
+    x, dy, gamma, beta = case["x"].to(f), case["dy"].to(f), case["gamma"], case["beta"]
+    cnt = case["cnt"]
+    if G:
+        B, HW, C = x.shape
+        cpg = C // G
+        xg = x.view(B, HW, G, cpg)
+        tot = torch.stack([xg.sum((1, 3)), (xg * xg).sum((1, 3))], -1) if stats is None else stats
+        inv = torch.tensor(1.0, dtype=f) / torch.tensor(float(cnt), dtype=f)
+        used = tot.roll(1, 0) if fault == "previous_image" else tot
+        mean = used[..., 0] * inv
+        var = (used[..., 1] * inv - mean * mean).clamp_min(0)
+        ex = lambda t: t.repeat_interleave(cpg, 1)[:, None, :]  # (B, G) -> (B, 1, C)
+        red = lambda t: t.view(B, HW, G, cpg).sum((1, 3))
+    else:
+        mean = x.sum(1) / cnt
+        var = ((x * x).sum(1) / cnt - mean * mean).clamp_min(0)
+        ex = lambda t: t[:, None]
+        red = lambda t: t.sum(1)
+        inv = None
+    rstd = _ulps((var.double() + eps).rsqrt().to(f), rstd_ulps)
+    if fault == "neighbour_mean":
+        mean = mean.roll(-1, -1)
+    m, r = ex(mean), ex(rstd)
+    if G:
+        a = r * gamma
+        y = a * x + (beta - m * a)
+    else:
+        y = (x - m) * r * gamma + beta
+    xh = (x - m) * r
+    gd = dy * gamma
+    if G:
+        k1, k2 = ex(rstd * red(gd) * inv), ex(rstd * red(gd * xh) * inv)
+        dx = r * gamma * dy - k1 - xh * k2
+    else:
+        dx = r * (gd - ex(red(gd) / cnt) - xh * ex(red(gd * xh) / cnt))
+    lead = tuple(range(x.dim() - 1))
+    zero = torch.zeros_like(gamma)
+    out = dict(y=y.to(BF), dx=dx.to(BF), stats=tot if G else None, mean=mean, rstd=rstd,
+               dgamma=(zero if fault == "store" else case["prev_dgamma"]) + (dy * xh).sum(lead),
+               dbeta=(zero if fault == "store" else case["prev_dbeta"]) + dy.sum(lead))
+    d = case["dres"].to(f)
+    out["dx_dres"] = (dx + d).to(BF) if fault == "dres_early" else (dx.to(BF).to(f) + d).to(BF)
+    return out
+
+
+def _norm_compare(case, exp, got, shape, G, exact):
+    """What tests/test_gpu_norm_exact.py asserts, as a list of failure messages."""
+    fails = []
+    for n in ("y", "dx", "dx_dres"):
+        msg = kc.gn_mismatch_report(got[n], exp[n], n, *shape, G) if G else kc.mismatch_report(got[n], exp[n], n)
+        fails += [msg] if msg else []
+    if G:
+        msg = kc.stats_report(got["stats"], exp["stats"], "stats")
+        fails += [msg] if msg else []
+    for n in ("dgamma", "dbeta"):
+        if exact:
+            msg = kc.mismatch_report(got[n], (case["prev_" + n].double() + exp[n]).float(), n)
+        else:
+            msg = kc.param_grad_rule(got[n], case["prev_" + n], exp["rule2"], n)[0]
+        fails += [msg] if msg else []
+    return fails
+
+
+def _balanced(kind, c):
+    if kind == "gn":
+        cid, B, HW, C, G = c
+        case = kc.gn_balanced(cid)
+        return case, G, (B, HW, C), kc.is_pow2(case["cnt"])
+    cid, M, C = c
+    return kc.ln_balanced(cid), 0, (M, C), True
+
+
+@pytest.mark.parametrize("kind,c", [("gn", c) for c in kc.GN_BALANCED_CASES] + [("ln", c) for c in kc.LN_BALANCED_CASES], ids=lambda v: v if isinstance(v, str) else v[0])
+def test_balanced_norm_cases_have_a_unique_representable_result_and_fp32_lands_on_it(kind, c):
+    """On the very operands of the GPU file: the float64 results are bf16-representable and non-zero and every sum is an integer below
+    2^24 (asserted inside norm_exact_expectation); inputs are integers in -3..3; the fp32 restatement of the kernels' formulas - with
+    fl(1 / cnt), eps = 1e-5 and rstd one ulp up or down - passes the very comparisons of the GPU file, and with eps = 0 and an exact
+    rstd the fp32 parameter gradients are exact too wherever the GPU file asks for that."""
+    case, G, shape, pow2 = _balanced(kind, c)
+    exact = pow2 or not G
+    exp = kc.norm_exact_expectation(case, G, 0.0 if exact else 1e-5)
+    assert float(case["x"].float().abs().max()) <= 3 and torch.equal(case["x"].float(), case["x"].float().round())
+    assert float(exp["y"].float().abs().min()) >= 1 and float(exp["dx"].float().abs().min()) >= 0.5
+    assert int((exp["dx_dres"].float() != exp["dx"].float() + case["dres"].float()).sum()) > 0 or case["x"].numel() < 64, "no dres tie in this case"
+    if G:
+        assert bool((case["c"][:, 1:] != case["c"][:, :-1]).all()), "neighbouring groups share a mean: a mixed-up group would not show"
+        for d in range(1, shape[0]):  # every pair of images (B <= 3): no group shares (c, s), so none shares {sum, sumsq}, mean or xhat
+            cs = torch.stack([case["c"], case["s"]], -1)
+            assert bool((cs[d:] != cs[:-d]).any(-1).all()) and bool((case["c"][d:] != case["c"][:-d]).all()), f"images {d} apart share (c, s) in a group"
+            assert bool((exp["stats"][d:, :, 0] != exp["stats"][:-d, :, 0]).all()), f"images {d} apart share a group's sum: another image's statistics would not show"
+        if shape[0] > 1:
+            assert bool((case["s"][1:] != case["s"][:-1]).any()) or G == 1, "no group changes its rstd from image to image"
+    if not exact:  # the per-channel rule runs onto zero: its denominator knows nothing of the rounding of (previous value + sum)
+        case["prev_dgamma"], case["prev_dbeta"] = torch.zeros_like(case["gamma"]), torch.zeros_like(case["gamma"])
+    for ulps in (-1, 0, 1):
+        fails = _norm_compare(case, exp, _norm_model(case, G, 1e-5, ulps), shape, G, exact)
+        if exact:  # (fp32 parameter gradients at eps = 0: below)
+            fails = [m for m in fails if not m.startswith(("dgamma", "dbeta"))]
+        assert not fails, "\n".join(fails)
+    if exact:
+        got = _norm_model(case, G, 0.0, 0)
+        fails = _norm_compare(case, exp, got, shape, G, True)
+        assert not fails, "\n".join(fails)
+        assert torch.equal(got["mean"].reshape(-1), exp["mean"].reshape(-1)) and torch.equal(got["rstd"].reshape(-1), exp["rstd"].reshape(-1))
+
+
+def test_planted_norm_faults_are_each_caught():
+    """A neighbour group's mean, the previous image's statistics or partial rows, one partial row dropped out of 200 (named by the
+    report), dres added before the first rounding, and = instead of += on dgamma (where the sums are exact): each fails the comparison
+    it is meant for."""
+    for cid in ("pow2_cpg2", "cpg10_straddle_ty6"):
+        c = kc.gn_case(cid)
+        case, G, shape, pow2 = _balanced("gn", c)
+        exp = kc.norm_exact_expectation(case, G, 0.0 if pow2 else 1e-5)
+        eps = 0.0 if pow2 else 1e-5
+        if not pow2:
+            case["prev_dgamma"], case["prev_dbeta"] = torch.zeros_like(case["gamma"]), torch.zeros_like(case["gamma"])
+        assert not _norm_compare(case, exp, _norm_model(case, G, eps), shape, G, pow2)
+        f = _norm_compare(case, exp, _norm_model(case, G, eps, fault="neighbour_mean"), shape, G, pow2)
+        assert any(m.startswith("y:") and "image 0 group 0" in m and "thread row" in m for m in f) and any(m.startswith("dx:") for m in f), f
+        # the per-slice L2 of the older test would not see it at a realistic size; here every element of the group is wrong
+        # image b with the statistics of image b - 1 (gn_apply_kernel / the backward reading stats + (b - 1) * 2G): stats itself is right
+        f = _norm_compare(case, exp, _norm_model(case, G, eps, fault="previous_image"), shape, G, pow2)
+        assert any(m.startswith("y:") and "image 0 group 0" in m for m in f) and any(m.startswith("dx:") for m in f) and not any("statistics differ" in m for m in f), f
+        f = _norm_compare(case, exp, _norm_model(case, G, 1e-5, 1, fault="dres_early"), shape, G, pow2)
+        assert [m.split(":")[0] for m in f if not m.startswith(("dgamma", "dbeta"))] == ["dx_dres"], f
+        if pow2:  # (+= is proven where the sums are exact; the per-channel rule runs onto zero)
+            f = _norm_compare(case, exp, _norm_model(case, G, eps, fault="store"), shape, G, True)
+            assert sorted(m.split(":")[0] for m in f) == ["dbeta", "dgamma"], f
+        rows = kc.gn_parts_decomposition(exp["stats"], 200, 5)
+        assert kc.stats_report(rows.sum(1), exp["stats"], "stats", parts=rows) is None
+        kept = rows.clone()
+        kept[1, 137] = 0
+        msg = kc.stats_report(kept.sum(1), exp["stats"], "stats", parts=rows)
+        assert msg is not None and "image 1 group 0 sum" in msg and "workgroup [137]" in msg, msg
+        # image b adds up the partial rows of image b - 1 (gn_sum_parts / gn_group_reduce_kernel reading part + (b - 1) * nparts * 2G)
+        msg = kc.stats_report(rows.roll(1, 0).sum(1), exp["stats"], "stats", parts=rows)
+        assert msg is not None and "image 0 group 0 sum" in msg, msg
+        got = _norm_model(case, G, eps, stats=rows.roll(1, 0).sum(1))
+        f = _norm_compare(case, exp, got, shape, G, pow2)
+        assert any(m.startswith("y:") and "image 0 group 0" in m for m in f) and any("statistics differ" in m for m in f), f
+    case, G, shape, _ = _balanced("ln", kc.LN_BALANCED_CASES[1])
+    exp = kc.norm_exact_expectation(case, 0, 0.0)
+    f = _norm_compare(case, exp, _norm_model(case, 0, 1e-5, -1, fault="dres_early"), shape, 0, True)
+    assert "dx_dres" in [m.split(":")[0] for m in f], f
+    f = _norm_compare(case, exp, _norm_model(case, 0, 0.0, fault="store"), shape, 0, True)
+    assert sorted(m.split(":")[0] for m in f) == ["dbeta", "dgamma"], f
+
+
+def test_groupnorm_geometry_mirror_is_the_librarys_and_the_cases_reach_their_branches(lib):
+    """kc.gn_chunks / gn_layout against the workspace queries (host calls), and the branch every case id names."""
+    for cid, B, HW, C, G in kc.GN_BALANCED_CASES:
+        assert lib.sdt_groupnorm_fwd_workspace_bytes(B, HW, C, G) == kc.gn_fwd_workspace_bytes(B, HW, C, G), cid
+        assert lib.sdt_groupnorm_bwd_workspace_bytes(B, HW, C) == kc.gn_bwd_workspace_bytes(B, HW, C), cid
+        assert C % 8 == 0 and C % G == 0 and (HW * C // G) % 4 == 0 and B * HW * C <= 2_700_000, cid
+    for B, HW, C, G in ((2, 4096, 320, 32), (1, 512 * 512, 128, 32), (3, 256, 2560, 32), (16, 64, 1280, 32), (1, 1, 8, 1), (2000, 7, 64, 8)):
+        assert lib.sdt_groupnorm_fwd_workspace_bytes(B, HW, C, G) == kc.gn_fwd_workspace_bytes(B, HW, C, G)
+        assert lib.sdt_groupnorm_bwd_workspace_bytes(B, HW, C) == kc.gn_bwd_workspace_bytes(B, HW, C)
+    geo = {c[0]: (kc.gn_layout(c[3]), kc.gn_chunks(c[1], c[2], c[3], True), kc.gn_chunks(c[1], c[2], c[3], False), c) for c in kc.GN_BALANCED_CASES}
+    pow2 = {cid for cid, B, HW, C, G in kc.GN_BALANCED_CASES if kc.is_pow2(HW * C // G)}
+    assert {"pow2_cpg2", "pow2_cpg8"} <= pow2 and len(pow2) < len(kc.GN_BALANCED_CASES) - 4
+    (Cv, TX, TY, J), _, _, c = geo["cpg10_straddle_ty6"]
+    assert TY == 6 and TX * TY < 256 and (c[3] // c[4]) % 8 != 0 and 8 % (c[3] // c[4]) != 0
+    assert geo["cpg3"][3][3] // geo["cpg3"][3][4] == 3
+    (Cv, TX, TY, J), _, _, c = geo["cpg1_fewer_pixels_than_thread_rows"]
+    assert c[3] == c[4] and c[2] < TY
+    (Cv, TX, TY, J), _, _, c = geo["j2_ragged_second_vector"]
+    assert J == 2 and TY == 1 and Cv % TX != 0
+    (Cv, TX, TY, J), _, _, c = geo["g64_widest_c4096"]
+    assert c[4] == 64 and c[3] == 4096 and J == 2 and Cv == 2 * TX
+    (Cv, TX, TY, J), (ns, ps), (na, pa), c = geo["ty1_128_stat_rows_ragged_last"]
+    assert TY == 1 and ns == kc.GN_MAX_INLINE_PARTS and c[2] % ps != 0 and (na, pa) != (ns, ps)
+    assert geo["g8"][3][4] == 8 and geo["g8"][1][0] > 1 and geo["g8"][3][2] % geo["g8"][1][1] != 0
+    assert 256 % (2 * geo["g24_2g_not_dividing_256"][3][4]) != 0 and geo["g1"][3][4] == 1
+    where = kc.gn_locate(2, 636, 2048, 32, 1, 635, 2047)
+    assert "image 1 group 31" in where and "chunk 127 of 128 (5 pixels each, the last 1)" in where and "chunk 158 of 159" in where, where
+    # producer rows: both sides of the 128-row threshold, a ragged rows_per, and the odd slice splits through gn_group_reduce_kernel
+    ns = {n for _, n in kc.GN_PARTS_CASES}
+    assert {1, 2, 127, 128, 129, 200, 2048} <= ns and -(-200 // kc.GN_L2_PARTS) * kc.GN_L2_PARTS != 200
+    assert any(kc.gn_case(cid)[4] == 24 and n > 128 for cid, n in kc.GN_PARTS_CASES) and any(kc.gn_case(cid)[4] == 64 and n > 128 for cid, n in kc.GN_PARTS_CASES)
+    # LayerNorm: ln_rows_per_block / the 1024-workgroup cap (norm.hip sdt_layernorm_bwd) and the 4096-workgroup forward grid
+    ln = {c[0]: c for c in kc.LN_BALANCED_CASES}
+    for cid, M, C in kc.LN_BALANCED_CASES:
+        assert lib.sdt_layernorm_bwd_partial_rows(M, C) == min(1024, -(-M // kc.ln_rows_per_block(C))), cid
+        assert C % 8 == 0 and C <= 2048
+    assert ln["nr4_clamped_tail_row"][1] % 4 != 0 and ln["maxv2_nr2_odd_m"][1] % 2 == 1 and 512 < ln["maxv2_nr2_odd_m"][2] <= 1024
+    assert ln["maxv4"][2] > 1536 and (ln["cv129_ragged_third_vector"][2] // 8) % 64 == 1
+    assert ln["grid_stride_loop"][1] > 1024 * 16 and ln["grid_stride_loop"][1] > 4096 * 4
+    for D, R, win, S, eos in kc.CLIP_POOL_CASES:
+        cc = kc.clip_pool_case(D, R, win, S, eos, 300 + D)
+        assert S % 8 != 0 and {0, S - 1} <= set(cc["pos"].tolist())
+        ids = cc["ids"].view(R, win, S)[:, 0]
+        want = ids.argmax(1) if eos < 0 else torch.where((ids == eos).any(1), (ids == eos).int().argmax(1), 0)
+        assert torch.equal(want.to(torch.int32), cc["pos"]), (D, want, cc["pos"])
+        kc.norm_exact_expectation(cc["rows"], 0, 0.0)
