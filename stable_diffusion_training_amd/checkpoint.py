@@ -23,7 +23,7 @@ import msgpack
 import numpy as np
 import torch
 
-from . import nets
+from . import nets, optimizers
 from .params import EmaView, ParamStore
 
 DIFFUSERS_VERSION = "0.21.4"  # the version the reference pins
@@ -371,24 +371,18 @@ def _layout_digest(store):
         lf = store.leaves[p]
         h.update(f"{p}:{lf.shape}:{lf.offset}:{int(lf.quantised)}:{int(lf.decayed)};".encode())
     h.update(f"bs={store.block_size};total={store.total}".encode())
-    opt = _optimizer_of(store)
-    if opt != "lion":  # only then: the digests (and files) of Lion stores stay what they were before there was a choice
-        h.update(f";optimizer={opt}".encode())
+    named = store.opt.file_meta().get("optimizer")  # Lion names none: its digests (and files) stay what they were before there was a choice
+    if named is not None:
+        h.update(f";optimizer={named}".encode())
     return h.hexdigest()
 
 
-def _optimizer_of(store):
-    return getattr(store, "optimizer", "lion")
+def _state_buffers(store):
+    """The store attributes a training-state file holds: master, EMA and the saved rows of the optimizer's state table (the optimizer's
+    counter and running products are not among them: ParamStore.set_step rebuilds them from the count)."""
+    return ("master", "ema") + optimizers.saved(store)
 
 
-_STATE_BUFFERS = ("master", "codes", "inv_scale", "mom", "ema")
-# AdamW stores: codes / scales of the second moment's root and the fp32 second moments.  The step counter and the running products of
-# the betas are rebuilt from the count (ParamStore.set_step).
-_ADAMW_BUFFERS = ("codes2", "inv_scale2", "mom2")
-# Prodigy stores: v, s, p0 (m is "mom") and the state block with d, d_max and numer; the counter and the running products in the block
-# are rebuilt from the count as well.
-_PRODIGY_BUFFERS = ("mom2", "prodigy_s", "prodigy_p0", "prodigy_state")
-_EXTRA_BUFFERS = {"lion": (), "adamw": _ADAMW_BUFFERS, "prodigy": _PRODIGY_BUFFERS}
 # -2: flat-buffer layout of round 2 (8-element leaf alignment, segment ends at multiples of 2048, time_emb_proj / cross-attention
 # to_k / to_v grouped per width).  -1 files (round 1) hold the same tensors at other offsets and cannot be re-dealt.
 STATE_FORMAT = "sdt-training-state-2"
@@ -397,9 +391,8 @@ _OLD_FORMATS = {"sdt-training-state-1": "the flat-buffer layout changed after th
 
 
 def _prodigy_meta(store):
-    """A Prodigy store's settings as one string: the recursion a file's d, d_max and numer belong to (the finish kernel branches on
-    d == d0; beta3, d_coef, growth_rate and the two flags shape every later d)."""
-    return ";".join(f"{k}={store.prodigy[k]!r}" for k in sorted(store.prodigy))
+    """A Prodigy store's settings as the string its files carry (optimizers.Prodigy.file_meta)."""
+    return store.opt.file_meta()["prodigy"]
 
 
 def _stepping_store(st):
@@ -431,14 +424,11 @@ def save_training_state(path, unet_state, text_encoder_state, train_rng=None, rn
         if ad is not None:  # LoRA: the adapter store's master, moments, EMA and count
             meta[f"{name}.lora"] = _lora_meta(ad)
         store._gather()  # sharded optimizer: raises unless GradReducer.gather_state() (collective, all ranks) made the state whole
-        for b in _STATE_BUFFERS + _EXTRA_BUFFERS[_optimizer_of(store)]:
+        for b in _state_buffers(store):
             t = getattr(store, b)
             if t is not None:
                 tensors[f"{name}.{b}"] = t.detach().cpu().contiguous()
-        if _optimizer_of(store) != "lion":  # absent: Lion (its files are byte for byte what they were)
-            meta[f"{name}.optimizer"] = _optimizer_of(store)
-        if _optimizer_of(store) == "prodigy":
-            meta[f"{name}.prodigy"] = _prodigy_meta(store)
+        meta.update({f"{name}.{k}": v for k, v in store.opt.file_meta().items()})  # nothing for Lion: its files are byte for byte what they were
         meta[f"{name}.count"] = str(int(store.count))
         meta[f"{name}.layout"] = _layout_digest(store)
     if rng_states is not None:
@@ -489,20 +479,21 @@ def load_training_state(path, unet_state, text_encoder_state, train_rng=None, ra
             if meta.get(f"{name}.lora") != (None if ad is None else _lora_meta(ad)):
                 raise ValueError(f"{path}: {name} state was saved with LoRA settings {meta.get(f'{name}.lora')!r}, this state has "
                                  f"{None if ad is None else _lora_meta(ad)!r}")
-            saved_opt, opt = meta.get(f"{name}.optimizer", "lion"), _optimizer_of(store)
+            saved_opt, opt = meta.get(f"{name}.optimizer", optimizers.FILE_DEFAULT), store.optimizer
             if saved_opt != opt:
                 raise ValueError(f"{path}: {name} state was saved by the {saved_opt} optimizer and this state is built for {opt}: their "
                                  "moments are different quantities; build the state with the optimizer that wrote the file")
-            if opt == "prodigy" and meta.get(f"{name}.prodigy") != _prodigy_meta(store):
+            settings = store.opt.file_meta().get("prodigy")  # (the optimizers agree: both None unless they are Prodigy)
+            if meta.get(f"{name}.prodigy") != settings:
                 raise ValueError(f"{path}: {name} state was saved by a Prodigy store with the settings {meta.get(f'{name}.prodigy')!r} and "
-                                 f"this store has {_prodigy_meta(store)!r}: d, d_max and numer continue one recursion only; build the "
+                                 f"this store has {settings!r}: d, d_max and numer continue one recursion only; build the "
                                  "store with the settings that wrote the file (prodigy=dict(...))")
             if meta.get(f"{name}.layout") != _layout_digest(store):
                 raise ValueError(f"{path}: {name} state was saved for a different parameter layout / quantisation setting "
                                  f"(layout version {STATE_FORMAT}; digest {meta.get(f'{name}.layout', '?')[:12]} != {_layout_digest(store)[:12]}: "
                                  "model config, quantisation / weight-decay exclusion lists and quant_block_size must match)")
             store.begin_external_write()  # sharded optimizer: a mirror all-gather of the last step may still be in flight
-            for b in _STATE_BUFFERS + _EXTRA_BUFFERS[opt]:
+            for b in _state_buffers(store):
                 dst = getattr(store, b)
                 if (dst is not None) != (f"{name}.{b}" in keys):
                     raise ValueError(f"{path}: {name}.{b} present in only one of file / state")

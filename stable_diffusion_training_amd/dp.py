@@ -38,7 +38,7 @@ import os
 import torch
 import torch.distributed as dist
 
-from . import _lib
+from . import _lib, optimizers
 
 
 class _Done:
@@ -76,9 +76,9 @@ class GradReducer:
         nothing about a real exchange; what is left is the cost of the structure itself.
         shard: sharded optimizer (module docstring); needs a world size that divides 8."""
         stores = list(stores)
-        if shard and any(getattr(st, "optimizer", "lion") == "prodigy" for st in stores):
-            raise ValueError("GradReducer(shard=True): the sharded optimizer is not available for a Prodigy store (its two global sums "
-                             "would need a collective between the two sweeps); use the all-reduce exchange (shard=False)")
+        refused = [st.opt.unshardable for st in stores if shard and st.opt.unshardable]
+        if refused:
+            raise ValueError(f"GradReducer(shard=True): {refused[0]} (shard=False)")
         self.group = process_group
         self.world = dist.get_world_size(process_group) if dist.is_initialized() else 1
         self.rank = dist.get_rank(process_group) if dist.is_initialized() else 0
@@ -349,9 +349,7 @@ class GradReducer:
         if not self.shard:
             return
         self.wait_gathered()
-        # (AdamW stores: also the codes and scales of the second moment's root; None for Lion stores and skipped)
-        self._gather_buffers(lambda st: [(st.master, 1), (st.ema, 1), (st.codes, 1), (st.inv_scale, st.block_size),
-                                         (st.codes2, 1), (st.inv_scale2, st.block_size)])
+        self._gather_buffers(lambda st: [(st.master, 1), (st.ema, 1)] + optimizers.gathered(st))  # + the optimizer's codes and scales
         for st in self.stores:
             st.state_whole = True
 

@@ -17,7 +17,8 @@ from dataclasses import dataclass
 
 import torch
 
-from . import _lib, lion_codec
+from . import _lib, lion_codec, optimizers
+from .optimizers import OPTIMIZERS, PRODIGY_DEFAULTS, PRODIGY_STATE_DOUBLES, adam_products, prodigy_settings  # noqa: F401  (their public home)
 
 _THRESHOLDS = {}  # device -> float32[128] decision thresholds of the 8-bit Lion codec (lion_codec.quantization_thresholds)
 
@@ -46,49 +47,6 @@ def _ceil(a, b):
 # Segment ends (and the bucket boundaries of the sharded optimizer) are multiples of this many elements, so that any bucket cut
 # into 1, 2, 4 or 8 equal slices gives slices that are whole quantisation blocks (block sizes up to 256) and 64-element aligned
 SEG_ALIGN = 8 * 256
-OPTIMIZERS = ("lion", "adamw", "prodigy")
-# Prodigy's store-level settings (include/sdt.h "Prodigy"): what the device state is built from.  beta3 None: sqrt(b2).  lr, eps and
-# the weight decay are arguments of optimizer_step, as for the other optimizers.
-PRODIGY_DEFAULTS = dict(b1=0.9, b2=0.999, beta3=None, d0=1e-6, d_coef=1.0, growth_rate=float("inf"), use_bias_correction=False,
-                        safeguard_warmup=False)
-PRODIGY_STATE_DOUBLES = 10  # {d, d_max, numer, P1, P2, dot, l1, q, lr_t, 0}
-
-
-def prodigy_settings(given):
-    """PRODIGY_DEFAULTS overridden by `given`, checked: ValueError for an unknown key, a non-finite value, d0 <= 0, d_coef <= 0,
-    growth_rate <= 0 or NaN, or a beta outside [0, 1)."""
-    given = dict(given or {})
-    unknown = set(given) - set(PRODIGY_DEFAULTS)
-    if unknown:
-        raise ValueError(f"ParamStore: prodigy= takes {sorted(PRODIGY_DEFAULTS)}, not {sorted(unknown)} (lr, eps and the weight decay "
-                         "are optimizer_step's)")
-    hp = dict(PRODIGY_DEFAULTS, **given)
-    for k in ("b1", "b2", "d0", "d_coef", "growth_rate"):
-        hp[k] = float(hp[k])
-    hp["beta3"] = math.sqrt(hp["b2"]) if hp["beta3"] is None else float(hp["beta3"])
-    for k in ("use_bias_correction", "safeguard_warmup"):
-        hp[k] = bool(hp[k])
-    if not all(math.isfinite(hp[k]) for k in ("b1", "b2", "beta3", "d0", "d_coef")) or math.isnan(hp["growth_rate"]):
-        raise ValueError(f"ParamStore: non-finite Prodigy setting in {hp!r}")
-    if not all(0.0 <= hp[k] < 1.0 for k in ("b1", "b2", "beta3")):
-        raise ValueError(f"ParamStore: Prodigy's b1, b2 and beta3 must lie in [0, 1), got {hp['b1']!r}, {hp['b2']!r}, {hp['beta3']!r}")
-    if hp["d0"] <= 0.0:
-        raise ValueError(f"ParamStore: Prodigy's d0 must be positive, got {hp['d0']!r}")
-    if hp["d_coef"] <= 0.0 or hp["growth_rate"] <= 0.0:
-        raise ValueError(f"ParamStore: Prodigy's d_coef and growth_rate must be positive, got {hp['d_coef']!r}, {hp['growth_rate']!r}")
-    return hp
-
-
-def adam_products(n, b1, b2):
-    """(b1^n, b2^n) as n sequential float64 products from 1.0 - what sdt_adamw_select has carried on the device after n steps, bit for
-    bit (one IEEE multiplication per step, no pow).  Stops once both have underflowed to 0."""
-    p1 = p2 = 1.0
-    for _ in range(int(n)):
-        p1 *= b1
-        p2 *= b2
-        if p1 == 0.0 and p2 == 0.0:
-            break
-    return p1, p2
 
 
 @dataclass
@@ -132,25 +90,14 @@ class ParamStore:
         trees (True = quantise / decay) in place of the exclusion patterns (lion_quant.lion_8bit takes masks).
         grad_bf16=False keeps every gradient float32 (lion_quant's GradientTransformation facade: its caller hands in float32 updates
         and must get the arithmetic of lion_quant.py on exactly those).
-        optimizer: "lion" (the reference's, the default) or "adamw" (include/sdt.h "AdamW": a second set of state buffers - codes2 /
-        inv_scale2 hold the root of the second moment of the quantised leaves, mom2 the second moment of the others - and the device
-        step counter, the two running products of adam_betas and the step's scalar block; a Lion store has None for all of them), or
-        "prodigy" (include/sdt.h "Prodigy"; prodigy=dict(...) overrides PRODIGY_DEFAULTS): ALL of its state is float32 - mom, mom2,
-        prodigy_s and prodigy_p0 (m, v, s, p0) each span the whole store, master order - beside the device state block, step counter and
-        scalar block.  quantise=True does not quantise a Prodigy store's state (there is no 8-bit Prodigy sweep): it only decides, as for the
-        other optimizers, which leaves form the first two segments and keep their gradients in bf16 - the layout stays the store's.
+        optimizer: "lion" (the reference's, the default), "adamw" or "prodigy" (prodigy=dict(...) overrides PRODIGY_DEFAULTS).  The state
+        buffers the store holds for it (codes, inv_scale, mom, codes2, ..., prodigy_cur) are the rows of its table in optimizers.py, where
+        each is described; an attribute the store's optimizer does not use is None.  quantise=True does not quantise a Prodigy store's state
+        (there is no 8-bit Prodigy sweep): it only decides, as for the other optimizers, which leaves form the first two segments and keep
+        their gradients in bf16 - the layout stays the store's.
         adam_betas belongs to AdamW and prodigy= to Prodigy: either one handed to another optimizer's store is refused."""
-        if optimizer not in OPTIMIZERS:
-            raise ValueError(f"ParamStore: optimizer must be one of {OPTIMIZERS}, not {optimizer!r}")
-        self.optimizer = optimizer
-        if optimizer == "prodigy" and adam_betas is not None:
-            raise ValueError("ParamStore: adam_betas belongs to AdamW; a Prodigy store takes its betas in prodigy=dict(b1=, b2=, beta3=)")
-        if optimizer != "prodigy" and prodigy is not None:
-            raise ValueError(f"ParamStore: prodigy= belongs to optimizer='prodigy'; this store's optimizer is {optimizer!r}")
-        self.prodigy = prodigy_settings(prodigy) if optimizer == "prodigy" else None
-        self.adam_betas = tuple(float(b) for b in ((0.9, 0.999) if adam_betas is None else adam_betas))
-        if optimizer == "adamw" and not all(0.0 <= b < 1.0 for b in self.adam_betas):
-            raise ValueError(f"ParamStore: adam_betas must lie in [0, 1), got {adam_betas!r}")
+        self.opt = optimizers.for_store(optimizer, adam_betas, prodigy)  # everything that depends on which optimizer it is
+        self.optimizer, self.adam_betas, self.prodigy = self.opt.name, self.opt.adam_betas, self.opt.prodigy
         self.device = torch.device(device)
         self.block_size = block_size
         self.trainable = trainable
@@ -224,40 +171,14 @@ class ParamStore:
                 self.grad16 = torch.zeros(self.quant_total, dtype=torch.bfloat16, device=dev)
                 self.g32_base = self.quant_total
             self.grad = torch.zeros(max(self.total - self.g32_base, 4), dtype=torch.float32, device=dev)
-            adamw, prod = optimizer == "adamw", optimizer == "prodigy"
-            # Lion: quant(0) == 3 (the codec's offset); AdamW's codec has no offset: zero is code 0
-            self.codes = None if prod else torch.full((max(self.quant_total, 4),), 0 if adamw else 3, dtype=torch.int8, device=dev)
-            self.inv_scale = None if prod else torch.ones(max(self.quant_total // block_size, 1), dtype=torch.float32, device=dev)
-            self.mom = torch.zeros(max(self.total if prod else self.total - self.quant_total, 4), dtype=torch.float32, device=dev)
             self.sqnorm = torch.zeros(1, dtype=torch.float64, device=dev)
-            # arrival counter + per-workgroup double partials of the gradient-norm pass (ordered sum, no atomics; zeroed once); a
-            # Prodigy store's moments sweep carries two sums through the same buffer
-            ws_bytes = 8
-            if dev.type == "cuda":
-                ws_bytes = _lib.load().sdt_prodigy_workspace_bytes() if prod else _lib.load().sdt_sqnorm_workspace_bytes()
+            # arrival counter + per-workgroup double partials of the gradient-norm pass (ordered sum, no atomics; zeroed once)
+            ws_bytes = getattr(_lib.load(), self.opt.workspace)() if dev.type == "cuda" else 8
             self.sq_ws = torch.zeros(ws_bytes, dtype=torch.uint8, device=dev)
             self.ema = torch.zeros(self.total, dtype=torch.float32, device=dev) if with_ema else None
-            self.codes2 = self.inv_scale2 = self.mom2 = self.adam_step = self.adam_prod = self.adam_cur = None
-            if adamw:
-                self.codes2 = torch.zeros_like(self.codes)
-                self.inv_scale2 = torch.ones_like(self.inv_scale)
-                self.mom2 = torch.zeros_like(self.mom)
-                self.adam_step = torch.zeros(1, dtype=torch.int64, device=dev)     # steps taken, advanced by sdt_adamw_select
-                self.adam_prod = torch.ones(2, dtype=torch.float64, device=dev)    # b1^t, b2^t as running products
-                self.adam_cur = torch.zeros(8, dtype=torch.float32, device=dev)    # the step's scalars (include/sdt.h)
-            self.prodigy_s = self.prodigy_p0 = self.prodigy_state = self.prodigy_step = self.prodigy_cur = None
-            if prod:
-                self.mom2 = torch.zeros_like(self.mom)        # v (mom is m)
-                self.prodigy_s = torch.zeros_like(self.mom)   # s
-                self.prodigy_p0 = torch.zeros_like(self.mom)  # p0: written by the sweep of the step that finds the counter at zero
-                self.prodigy_state = torch.zeros(PRODIGY_STATE_DOUBLES, dtype=torch.float64, device=dev)
-                self.prodigy_step = torch.zeros(1, dtype=torch.int64, device=dev)
-                self.prodigy_cur = torch.zeros(8, dtype=torch.float32, device=dev)
-                self.prodigy_state.copy_(torch.tensor(self._prodigy_initial_state(), dtype=torch.float64))
         else:
-            self.grad = self.codes = self.inv_scale = self.mom = self.sqnorm = self.ema = self.sq_ws = None
-            self.codes2 = self.inv_scale2 = self.mom2 = self.adam_step = self.adam_prod = self.adam_cur = None
-            self.prodigy_s = self.prodigy_p0 = self.prodigy_state = self.prodigy_step = self.prodigy_cur = None
+            self.grad = self.sqnorm = self.ema = self.sq_ws = None
+        optimizers.allocate(self, dev)  # codes, inv_scale, mom, ... (optimizers.STATE_NAMES): the optimizer's, or None
         self.count = 0
         self._prep = None
         self._zero = None
@@ -278,10 +199,6 @@ class ParamStore:
         self._sched = None         # dict(step, lr_tab, ema_tab, cur) device tensors; kept for the store's life once allocated
         self._captured = False     # an optimizer step of this store has been captured into a graph (tables must not move)
         self.adapter = None        # lora.attach: a frozen store's low-rank adapter; prepare() then ends with its merge into W
-
-    def _prodigy_initial_state(self):
-        d0 = self.prodigy["d0"]
-        return [d0, d0, 0.0, 1.0, 1.0] + [0.0] * (PRODIGY_STATE_DOUBLES - 5)
 
     def prodigy_d(self):
         """Prodigy's current distance estimate d: a float64 device scalar (a view of the state block; .item() synchronises - logging
@@ -418,11 +335,12 @@ class ParamStore:
         AdamW stores: which="m" the first moment, which="s" the second one - for quantised leaves the codes and scales of its ROOT
         (the codec has no offset: value = (code / 127)^5 / inv_scale), for the others the fp32 second moment itself."""
         self._gather()
-        if self.optimizer == "prodigy":
-            raise ValueError("export_momentum: a prodigy store keeps m, v, s and p0 in float32 over the whole store: export_prodigy_state()")
-        if which not in ("m", "s") or (which == "s" and self.optimizer != "adamw"):
-            raise ValueError(f"export_momentum: which={which!r} (a {self.optimizer} store has {'m and s' if self.optimizer == 'adamw' else 'm only'})")
-        codes, inv, mom = (self.codes, self.inv_scale, self.mom) if which == "m" else (self.codes2, self.inv_scale2, self.mom2)
+        has = self.opt.moments
+        if not has:
+            raise ValueError(f"export_momentum: a {self.optimizer} store keeps m, v, s and p0 in float32 over the whole store: export_prodigy_state()")
+        if which not in has:
+            raise ValueError(f"export_momentum: which={which!r} (a {self.optimizer} store has {' and '.join(has) if len(has) > 1 else 'm only'})")
+        codes, inv, mom = (getattr(self, name) for name in has[which])
         out = {}
         bs = self.block_size
         for p, lf in self.leaves.items():
@@ -437,8 +355,7 @@ class ParamStore:
 
     def state_bytes(self):
         """Bytes of optimizer state this store holds (moments only: codes, scales and fp32 moments; no masters, EMA or gradients)."""
-        bufs = (self.codes, self.inv_scale, self.mom, self.codes2, self.inv_scale2, self.mom2, self.prodigy_s, self.prodigy_p0)
-        return sum(t.numel() * t.element_size() for t in bufs if t is not None)
+        return sum(t.numel() * t.element_size() for t in optimizers.moments(self))
 
     # ------------------------------------------------------------------ bf16 compute copies
     def _build_prep(self):
@@ -644,15 +561,8 @@ class ParamStore:
         self.count = int(n)
         if self._sched is not None:
             self._sched["step"].fill_(self.count)
-        if self.optimizer == "adamw" and self.trainable:
-            # the device carries b1^t and b2^t as running float64 products: rebuild them with the same n multiplications
-            self.adam_step.fill_(self.count)
-            self.adam_prod.copy_(torch.tensor(adam_products(self.count, *self.adam_betas), dtype=torch.float64))
-        if self.optimizer == "prodigy" and self.trainable:
-            # the same for Prodigy's state block; d, d_max and numer stay (a checkpoint carries them).  A counter at zero makes the next
-            # step capture p0 again.
-            self.prodigy_step.fill_(self.count)
-            self.prodigy_state[3:5].copy_(torch.tensor(adam_products(self.count, self.prodigy["b1"], self.prodigy["b2"]), dtype=torch.float64))
+        if self.trainable:
+            self.opt.set_step(self, self.count)  # the optimizer's own device counter and running products
 
     def optimizer_step(self, *, lr, wd, b1=None, b2=None, max_norm=1.0, ema_rate=0.0, stream=None, shard=None, sq_partials=None,
                        grad_source="grad", eps=None):
@@ -676,29 +586,7 @@ class ParamStore:
         passes, then sdt_prodigy_select, the moments sweeps over the pieces (which leave the step's two sums on the device),
         sdt_prodigy_finish (the new d) and the apply sweeps.  b1 / b2 are the store's (prodigy=dict(...)); the sharded optimizer is
         refused: the two sums would need a collective between the sweeps."""
-        adamw, prod = self.optimizer == "adamw", self.optimizer == "prodigy"
-        if prod:
-            hp = self.prodigy
-            if shard is not None:
-                raise ValueError("optimizer_step: the sharded optimizer is not available for a Prodigy store (its two global sums would "
-                                 "need a collective between the two sweeps); use the all-reduce exchange")
-            if (b1 is not None and float(b1) != hp["b1"]) or (b2 is not None and float(b2) != hp["b2"]):
-                raise ValueError(f"optimizer_step: b1={b1!r}, b2={b2!r} but the store carries the running products of b1={hp['b1']!r}, "
-                                 f"b2={hp['b2']!r} (set them when the store is built: prodigy=dict(b1=, b2=))")
-            b1, b2 = hp["b1"], hp["b2"]
-            eps = 1e-8 if eps is None else eps
-        elif adamw:
-            b1 = self.adam_betas[0] if b1 is None else b1
-            b2 = self.adam_betas[1] if b2 is None else b2
-            if (float(b1), float(b2)) != self.adam_betas:
-                raise ValueError(f"optimizer_step: b1={b1!r}, b2={b2!r} but the store carries the running products of adam_betas="
-                                 f"{self.adam_betas!r} (set them when the store is built)")
-            eps = 1e-8 if eps is None else eps
-        else:
-            if eps is not None:
-                raise ValueError("optimizer_step: eps belongs to AdamW; this store's optimizer is Lion (ParamStore(optimizer='adamw'))")
-            b1 = 0.9 if b1 is None else b1
-            b2 = 0.99 if b2 is None else b2
+        b1, b2, eps = self.opt.step_args(b1, b2, eps, shard)
         s = stream if stream is not None else torch.cuda.current_stream().cuda_stream
         sq_ptr = None
         from_acc = grad_source == "acc"
@@ -743,30 +631,10 @@ class ParamStore:
                                  "change the base rate)")
             if ema_on and ema_rate != emas.ema_rate:
                 raise ValueError(f"optimizer_step: ema_rate={ema_rate!r} but the installed EMA schedule is built for {emas.ema_rate!r}")
-            if torch.cuda.is_current_stream_capturing():
-                self._captured = True
-            cur = sc["cur"].data_ptr()
-            if not (adamw or prod):
-                _lib.call("sdt_opt_schedule_select", sc["step"].data_ptr(), sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(),
-                          sc["ema_tab"].data_ptr(), sc["ema_tab"].numel() // 2, cur, s)
-        if adamw:
-            if torch.cuda.is_current_stream_capturing():
-                self._captured = True
-            # one counter for both: adam_step indexes the schedule's tables too (the schedule's own counter and block stay unused)
-            cur = self.adam_cur.data_ptr()
-            tabs = (None, 0, None, 0) if sc is None else (sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(), sc["ema_tab"].data_ptr(),
-                                                          sc["ema_tab"].numel() // 2)
-            _lib.call("sdt_adamw_select", self.adam_step.data_ptr(), self.adam_prod.data_ptr(), *tabs, lr, er, b1, b2, cur, s)
-
-        if prod:
-            if torch.cuda.is_current_stream_capturing():
-                self._captured = True
-            # as for AdamW: the store's own counter indexes the schedule's tables
-            cur, state = self.prodigy_cur.data_ptr(), self.prodigy_state.data_ptr()
-            tabs = (None, 0, None, 0) if sc is None else (sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(), sc["ema_tab"].data_ptr(),
-                                                          sc["ema_tab"].numel() // 2)
-            _lib.call("sdt_prodigy_select", self.prodigy_step.data_ptr(), state, *tabs, lr, er, b1, b2, hp["d0"],
-                      int(hp["use_bias_correction"]), int(hp["safeguard_warmup"]), cur, s)
+        if (sc is not None or self.opt.always_selects) and torch.cuda.is_current_stream_capturing():
+            self._captured = True  # the graph holds the tables' addresses (or that there are none)
+        tabs = (None, 0, None, 0) if sc is None else (sc["lr_tab"].data_ptr(), sc["lr_tab"].numel(), sc["ema_tab"].data_ptr(),
+                                                      sc["ema_tab"].numel() // 2)
 
         def piece(a, quant):
             """Pointers of the piece that starts at element a: master, gradient (+ whether it is bf16), EMA, bf16 mirror."""
@@ -780,57 +648,8 @@ class ParamStore:
             return (self.master.data_ptr() + 4 * a, gp, int(g16), self.ema.data_ptr() + 4 * a if ema_on else None,
                     self.w.data_ptr() + 2 * a)
 
-        if prod:
-            def runs(key):
-                """The non-empty pieces, neighbours with the same key joined: [a, b, key, quantised]."""
-                out = []
-                for (a, b, quant, decay) in pieces:
-                    if b > a and out and out[-1][1] == a and out[-1][2] == key(quant, decay):
-                        out[-1][1] = b
-                    elif b > a:
-                        out.append([a, b, key(quant, decay), quant])
-                return out
-
-            # a sweep per run of pieces that differ in nothing it reads: the moments sweep only cares which gradient buffer a piece lies
-            # in (two launches, one from gacc), the apply sweep only about its decay (one launch without weight decay)
-            for (a, b, _, quant) in runs(lambda quant, decay: quant and self.grad16 is not None and not from_acc):
-                mp, gp, g16, ema_ptr, wp = piece(a, quant)
-                _lib.call("sdt_prodigy_moments_step", mp, gp, g16, self.prodigy_p0.data_ptr() + 4 * a, self.mom.data_ptr() + 4 * a,
-                          self.mom2.data_ptr() + 4 * a, self.prodigy_s.data_ptr() + 4 * a, b - a, sq_ptr, max_norm, cur, state, b1, b2,
-                          hp["beta3"], self.sq_ws.data_ptr(), self.sq_ws.numel(), s)
-            _lib.call("sdt_prodigy_finish", state, cur, hp["beta3"], hp["d0"], hp["d_coef"], hp["growth_rate"], eps, s)
-            for (a, b, wd_eff, quant) in runs(lambda quant, decay: wd if decay else 0.0):
-                mp, gp, g16, ema_ptr, wp = piece(a, quant)
-                _lib.call("sdt_prodigy_apply_step", mp, self.mom.data_ptr() + 4 * a, self.mom2.data_ptr() + 4 * a, ema_ptr, wp, b - a, cur,
-                          wd_eff, s)
-            pieces = []
-        for (a, b, quant, decay) in pieces:
-            n = b - a
-            if n == 0:
-                continue
-            mp, gp, g16, ema_ptr, wp = piece(a, quant)
-            wd_eff = wd if decay else 0.0
-            blk = 4 * (a // self.block_size)  # the 8-bit streams: one code per element, one float scale per block
-            o = 4 * (a - self.quant_total)    # the fp32 state buffers start behind the quantised segments
-            thr = self.thresholds.data_ptr()
-            if adamw and quant:
-                _lib.call("sdt_adamw8_step", mp, gp, g16, self.codes.data_ptr() + a, self.inv_scale.data_ptr() + blk,
-                          self.codes2.data_ptr() + a, self.inv_scale2.data_ptr() + blk, ema_ptr, wp, n, self.block_size, sq_ptr, thr,
-                          max_norm, cur, wd_eff, b1, b2, eps, s)
-            elif adamw:
-                _lib.call("sdt_adamw32_step", mp, gp, self.mom.data_ptr() + o, self.mom2.data_ptr() + o, ema_ptr, wp, n, sq_ptr, max_norm,
-                          cur, wd_eff, b1, b2, eps, s)
-            elif quant and sc is not None:
-                _lib.call("sdt_lion8_step_scheduled", mp, gp, g16, self.codes.data_ptr() + a, self.inv_scale.data_ptr() + blk, ema_ptr, wp,
-                          n, self.block_size, sq_ptr, thr, max_norm, cur, wd_eff, b1, b2, s)
-            elif quant:
-                _lib.call("sdt_lion8_step", mp, gp, g16, self.codes.data_ptr() + a, self.inv_scale.data_ptr() + blk, ema_ptr, wp, n,
-                          self.block_size, sq_ptr, thr, max_norm, lr, wd_eff, b1, b2, er, s)
-            elif sc is not None:
-                _lib.call("sdt_lion32_step_scheduled", mp, gp, self.mom.data_ptr() + o, ema_ptr, wp, n, sq_ptr, max_norm, cur, wd_eff, b1,
-                          b2, s)
-            else:
-                _lib.call("sdt_lion32_step", mp, gp, self.mom.data_ptr() + o, ema_ptr, wp, n, sq_ptr, max_norm, lr, wd_eff, b1, b2, er, s)
+        self.opt.step(self, pieces, piece, lr=lr, wd=wd, b1=b1, b2=b2, eps=eps, er=er, sq_ptr=sq_ptr, max_norm=max_norm, sc=sc, tabs=tabs,
+                      s=s)
         self.count += 1
         self._written = None
         self._grad_is_acc = from_acc

@@ -15,10 +15,10 @@ from typing import Any, Callable
 import numpy as np
 import torch
 
-from . import _lib, lora as lora_mod, nets, ops, trace
+from . import _lib, lora as lora_mod, nets, ops, optimizers, trace
 from .checkpoint import load_models, load_training_state, save_model, save_training_state  # noqa: F401  (reference names)
 from .lr_schedule import resolve as resolve_schedule
-from .params import PRODIGY_DEFAULTS, EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
+from .params import EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
 from .schedulers import _PTYPE, DDPMScheduler
 
 
@@ -143,47 +143,22 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
             raise ValueError("lora: needs both states (train_unet and train_text_encoder); the text encoder is frozen by "
                              "text_encoder='frozen'")
         lora = {"unet": lora["unet"], "text_encoder": te_l}
-    opt = {"name": optimizer} if isinstance(optimizer, str) else dict(optimizer)
-    prodigy = opt.get("name") == "prodigy"
-    allowed = {"name", "b1", "b2", "eps", "weight_decay"} | (({"lr"} | set(PRODIGY_DEFAULTS)) if prodigy else set())
-    unknown = set(opt) - allowed
-    if unknown or opt.get("name") not in ("lion", "adamw", "prodigy"):
-        raise ValueError(f"optimizer: 'lion', 'adamw', 'prodigy' or dict(name=, b1=, b2=, eps=, weight_decay=) (Prodigy's dict also takes "
-                         f"lr= and {sorted(set(PRODIGY_DEFAULTS) - {'b1', 'b2'})}), not {optimizer!r}")
-    if opt["name"] == "lion" and len(opt) > 1:
-        raise ValueError("optimizer: Lion's hyper-parameters are the reference's (adam_to_lion_scale_factor); the dict form is AdamW's")
-    adamw = opt["name"] == "adamw"
+    opt_cls, opt = optimizers.parse(optimizer)
 
     def make(spec, weights, cfg, fn, lr, quant, ema, which):
-        if prodigy:  # the config's learning rate is not used: lr multiplies the estimated d
-            hyper = dict(lr=opt.get("lr", 1.0), wd=opt.get("weight_decay", 0.0), eps=opt.get("eps", 1e-8), max_norm=1.0)
-        elif adamw:
-            hyper = dict(lr=lr, wd=opt.get("weight_decay", 1e-2), b1=opt.get("b1", 0.9), b2=opt.get("b2", 0.999),
-                         eps=opt.get("eps", 1e-8), max_norm=1.0)
-        else:
-            hyper = dict(lr=lr / adam_to_lion_scale_factor, wd=1e-2 * adam_to_lion_scale_factor, b1=0.9, b2=0.99, max_norm=1.0)
-        okw = dict(optimizer="adamw", adam_betas=(hyper["b1"], hyper["b2"])) if adamw else {}
-        if prodigy:
-            okw = dict(optimizer="prodigy", prodigy={k: opt[k] for k in PRODIGY_DEFAULTS if k in opt})
+        hyper, okw = opt_cls.builder(lr, adam_to_lion_scale_factor, opt)
         sched = resolve_schedule(lr_scheduler, hyper["lr"], ema_rate, lr_schedule=lr_schedule, ema_schedule=ema_schedule)
-        if lora is not None:
-            base = ParamStore(spec, device=device, trainable=False)
-            base.load(weights)
-            if lora[which] is None:
-                return TrainState(fn, base, cfg, {})
-            adapter = lora_mod.attach(base, lora[which], quantise=quant, quant_excluded=tuple(excluded_layer_from_quantization),
-                                      wd_excluded=tuple(excluded_layer_pattern_from_weight_decay),
-                                      block_size=lion_8bit_block_size or 16, with_ema=ema, **okw)
-            if sched is not None:
-                adapter.store.set_schedule(lr=sched[0], ema=sched[1])
-            return TrainState(fn, base, cfg, hyper, adapter)
-        store = ParamStore(spec, device=device, quantise=quant, quant_excluded=tuple(excluded_layer_from_quantization),
-                           wd_excluded=tuple(excluded_layer_pattern_from_weight_decay),
-                           block_size=lion_8bit_block_size or 16, with_ema=ema, **okw)
+        okw = dict(okw, quantise=quant, quant_excluded=tuple(excluded_layer_from_quantization),
+                   wd_excluded=tuple(excluded_layer_pattern_from_weight_decay), block_size=lion_8bit_block_size or 16, with_ema=ema)
+        # full fine-tune: the store itself is trained.  LoRA: a frozen base, loaded once, and (unless the model only runs its forward)
+        # an adapter whose own store takes those keywords and the optimizer step
+        store = ParamStore(spec, device=device, **(okw if lora is None else dict(trainable=False)))
         store.load(weights)
-        if sched is not None:
-            store.set_schedule(lr=sched[0], ema=sched[1])
-        return TrainState(fn, store, cfg, hyper)
+        adapter = lora_mod.attach(store, lora[which], **okw) if lora is not None and lora[which] is not None else None
+        state = TrainState(fn, store, cfg, hyper if lora is None or adapter is not None else {}, adapter)
+        if sched is not None and state.opt_store is not None:
+            state.opt_store.set_schedule(lr=sched[0], ema=sched[1])
+        return state
 
     if train_unet:
         m = models["unet"]
@@ -568,26 +543,17 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     # clip -> Lion(8-bit) -> decay -> -lr -> apply -> EMA         (training_utils.py:732-746)
     ur = ema_rate if (ema_rate and unet_ema_params is not None) else 0.0
     tr = ema_rate if (ema_rate and text_encoder_ema_params is not None) else 0.0
-    if lora:
-        with trace.phase("optimizer_clip_lion8_ema"):  # the norm by the ordinary pass over the adapters' few MB
-            for state, rate in ((unet_state, ur), (text_encoder_state, tr)):
-                if state.adapter is not None:
-                    state.adapter.store.optimizer_step(ema_rate=rate, grad_source=grad_source, **state.hyper)
-        ops.gn_arena_end(dev)
-        return (unet_state, text_encoder_state, unet_ema_params if ur else None, text_encoder_ema_params if tr else None,
-                {"loss": loss[0]}, train_rng)
-    with trace.phase("optimizer_clip_lion8_ema"):
-        us.optimizer_step(ema_rate=ur, shard=None if reducer is None else reducer.shard_pieces(us), sq_partials=sq_u,
-                          grad_source=grad_source, **unet_state.hyper)
-        ts.optimizer_step(ema_rate=tr, shard=None if reducer is None else reducer.shard_pieces(ts), sq_partials=sq_t,
-                          grad_source=grad_source, **text_encoder_state.hyper)
+    with trace.phase("optimizer_clip_lion8_ema"):  # (LoRA: no fused partials - the norm by the ordinary pass over the adapters' few MB)
+        for state, rate, sq in ((unet_state, ur, sq_u), (text_encoder_state, tr, sq_t)):
+            store = state.opt_store
+            if store is not None:  # (None: a LoRA run's text encoder without an adapter only ran its forward)
+                store.optimizer_step(ema_rate=rate, shard=None if reducer is None else reducer.shard_pieces(store), sq_partials=sq,
+                                     grad_source=grad_source, **state.hyper)
         if reducer is not None:
             reducer.after_optimizer()  # sharded optimizer: all-gather the bf16 weight mirrors the owners have just written
-
     ops.gn_arena_end(dev)
-    new_unet_ema = unet_ema_params if ur else None
-    new_te_ema = text_encoder_ema_params if tr else None
-    return unet_state, text_encoder_state, new_unet_ema, new_te_ema, {"loss": loss[0]}, train_rng
+    return (unet_state, text_encoder_state, unet_ema_params if ur else None, text_encoder_ema_params if tr else None,
+            {"loss": loss[0]}, train_rng)
 
 
 # Other threads keep making HIP calls while a step is captured (RCCL's watchdog polls events, loaders pin memory): only the
