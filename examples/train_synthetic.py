@@ -13,7 +13,11 @@ ema_rate (diffusers EMAModel), with the optional ema_inv_gamma, ema_power, ema_m
 ema_use_warmup_power (the 1 - (1 + s / inv_gamma) ** -power form).  Both advance once per optimizer step.
 --cache-latents DIR (or "cache_latents" in the config): every chunk the run will visit is encoded once with the frozen VAE into a latent
 cache under DIR (latent_cache.build: one record per batch, at the batch composition it is trained at), the VAE's device store is
-dropped, and the steps train from the cache's readers without a VAE."""
+dropped, and the steps train from the cache's readers without a VAE.
+--masked-loss [FLOOR] (or "masked_loss" in the config: true or the floor): the loader emits a loss mask per image and the loss counts
+each latent position by its pooled mask, at least FLOOR (default 0: only the masked area trains); --normalize-masked-area
+("normalize_masked_area") rescales every sample by area / masked area; --prior-loss-weight W ("prior_loss_weight"): every second sample is a
+class image whose loss counts W times (DreamBooth prior preservation).  A latent cache keeps the pooled masks and the weights."""
 import argparse
 import json
 import os
@@ -81,6 +85,18 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     te_cfg = models["text_encoder"]["config"]
     sdxl = nets.sdxl_conditioning(te_cfg)  # an SDXL directory: two towers, pooled embedding from the text encoder
     vocab = te_cfg["towers"][0]["vocab_size"] if "towers" in te_cfg else te_cfg["vocab_size"]
+    # masked / weighted loss: "masked_loss" is true or the floor (false / absent: off), "prior_loss_weight" a number (absent: off)
+    masked_loss = config_dict.get("masked_loss", False)
+    use_mask = masked_loss is not False and masked_loss is not None
+    prior_w = config_dict.get("prior_loss_weight")
+    if config_dict.get("normalize_masked_area") and not use_mask:
+        raise ValueError("normalize_masked_area needs masked_loss (--masked-loss)")
+    loss_loader_kw = dict(loss_masks=use_mask, prior_every=2 if prior_w is not None else 0,
+                          prior_loss_weight=1.0 if prior_w is None else float(prior_w))
+    loss_overrides = {}
+    if use_mask:
+        loss_overrides = dict(masked_loss_floor=0.0 if masked_loss is True else float(masked_loss),
+                              normalize_masked_area=bool(config_dict.get("normalize_masked_area", False)))
     dataloader = DataLoader(
         tokenizer_obj=tokenizer, config=None, ramdisk_path=config_dict.get("ramdisk_path"),
         training_batch_size=config_dict["batch_size"], repeat_batch=config_dict["repeat_batch"],
@@ -90,7 +106,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         queue_get_timeout=config_dict.get("queue_get_timeout", 60), chunk_number=config_dict["chunk_number"],
         seed=config_dict["master_seed"], context_concatenation_multiplier=config_dict["context_window_concatenation_count"],
         batches_per_chunk=config_dict.get("batches_per_chunk", 100), vocab_size=vocab,
-        rank=rank, world_size=world, device=dev, text_towers=2 if sdxl else 1)
+        rank=rank, world_size=world, device=dev, text_towers=2 if sdxl else 1, **loss_loader_kw)
     dataloader._print_debug = bool(config_dict.get("DEBUG"))
 
     lora_cfg = None
@@ -111,7 +127,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
         reducer=reducer, per_device_batch=config_dict["batch_size"] // (world * micro_batches), micro_batches=micro_batches,
-        step_overrides=dict(vae_scale=models["vae"]["config"].get("scaling_factor", 0.13025)) if sdxl else None)
+        step_overrides=dict(loss_overrides, **(dict(vae_scale=models["vae"]["config"].get("scaling_factor", 0.13025)) if sdxl else {})) or None)
     resume = config_dict.get("resume_training_state")
     if resume and os.path.exists(resume):
         tu.load_training_state(resume, unet_state, text_encoder_state, train_rngs, rank=rank, world=world)
@@ -229,6 +245,12 @@ if __name__ == "__main__":
                     help="train rank-RANK LoRA adapters on the UNet's attention projections (frozen base and text encoder) instead of every weight")
     ap.add_argument("--dora", action="store_true",
                     help="with --lora: DoRA - also train a per-output-feature magnitude of every adapted kernel (weight-decomposed LoRA)")
+    ap.add_argument("--masked-loss", metavar="FLOOR", type=float, nargs="?", const=0.0, default=None,
+                    help="train with a loss mask per image; FLOOR in [0, 1] is the least weight of a position outside the mask (default 0)")
+    ap.add_argument("--normalize-masked-area", action="store_true", default=None,
+                    help="with --masked-loss: rescale each sample's loss by area / masked area")
+    ap.add_argument("--prior-loss-weight", metavar="W", type=float, default=None,
+                    help="every second sample is a class image whose loss counts W times (DreamBooth prior preservation)")
     args = ap.parse_args()
     if args.dora and args.lora is None:
         ap.error("--dora needs --lora RANK")
@@ -244,4 +266,10 @@ if __name__ == "__main__":
         cfg["lora_dora"] = True
     if args.cache_latents is not None:
         cfg["cache_latents"] = args.cache_latents
+    if args.masked_loss is not None:
+        cfg["masked_loss"] = args.masked_loss
+    if args.normalize_masked_area:
+        cfg["normalize_masked_area"] = True
+    if args.prior_loss_weight is not None:
+        cfg["prior_loss_weight"] = args.prior_loss_weight
     main(cfg)

@@ -123,6 +123,41 @@ int sdt_mse_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_nchw, co
                          uint16_t* dpred_nhwc, int B, int C, int H, int W, int cpad, void* workspace, int64_t workspace_bytes,
                          hipStream_t stream);
 int64_t sdt_reduce_workspace_bytes(void);
+/* ---- MASKED LOSS: a loss mask and per-sample loss weights (kohya --masked_loss; OneTrainer masked training with an unmasked weight
+ * and "normalize masked area loss"; DreamBooth prior_loss_weight).  fl() is one fp32 rounding; nothing below is contracted.
+ *   pooled mask     mp[b,y,x] = fl(sum of the f x f block of clamp(m)) * fl(1/f^2): the block is added in row-major order starting
+ *                   from +0, clamp(m) = fminf(fmaxf(m, 0), 1) (a NaN counts as 0); f = 1 is the clamp alone (and -0 becomes +0)
+ *   effective mask  e = fmaxf(mp, floor), floor in [0, 1] (OneTrainer's rule; floor 0 is kohya's plain multiply): no rounding
+ *   sample factor   w_b = fl(snr_weight_b * loss_weight_b) (an absent factor is 1);  S_b = sum_p e[b,p] in the fixed order below;
+ *                   s_b = 1, or with normalisation fl(fl(h*w) / S_b) and 0 where S_b == 0 (a fully masked-out sample adds nothing and
+ *                   never a NaN);  k_b = fl(w_b * s_b)
+ *   loss            (1/count) sum_b k_b sum_{c,p} e[b,p] (target - pred)^2, count = B*C*h*w as in sdt_mse_loss_fwd_bwd
+ *   gradient        dpred[b,p,c] = bf16_rne(fl(fl(fl(-2 * fl(k_b * e)) * diff) * inv_count)), diff = target - pred,
+ *                   inv_count = fl(1 / fl(B*C*h*w)); padding channels are written as zero
+ *   per sample      loss_per_sample[b] = fl(fl(k_b * a_b) * fl(1/(C*h*w))), a_b = sum_{c,p} fl(fl(e * diff) * diff); the mean over b is
+ *                   the loss up to rounding.  loss_accum += fl(T * inv_count), T = the terms fl(k_b * a_b) added in sample order.
+ * EXACT CASE: with e == 1 (or no mask), no normalisation and loss_weight 1, fl(k_b * e) is snr_weight_b (or 1) and the gradient chain
+ * is sdt_mse_loss_fwd_bwd's fl(fl(fl(-2 * w) * diff) * inv_count): every dpred bit is equal, multiplications by 1.0 are the only
+ * difference.  The loss differs from that call's only by the order of its sum (per sample first).
+ * ORDER of the sums: grid (nb, B), nb = min(ceil(h*w / 256), 128, what the scratch holds); workgroup j of sample b owns positions
+ * j*256 + t + i*nb*256; a thread adds its positions in order (channels inside a position in order), the workgroup by block tree,
+ * the nb partials in workgroup order by the workgroup that arrives last.  No float atomics: the same bits on every launch.
+ *
+ * sdt_loss_mask_prepare: mask f32 (B, h*f, w*f), f in {1, 2, 4, 8, 16} -> effective f32 (B,h,w), sums f32 (B) = S_b, and (optional, NULL
+ * to skip) pooled f32 (B,h,w) = mp, the un-floored mask a latent cache stores.  Block rows by 16-byte loads when f >= 4 and the
+ * mask is 16-byte aligned, scalar loads otherwise.
+ * sdt_masked_mse_loss_fwd_bwd: pred bf16 NHWC (B,H,W,cpad) at LATENT size H x W, target f32 NCHW; effective_mask (NULL: all ones),
+ * mask_sums (NULL: no normalisation; needs the mask), snr_weight, loss_weight f32 (B) (NULL: ones); loss_accum accumulated,
+ * loss_per_sample (B) written, dpred optional.  pred / dpred by 16-byte vectors when cpad % 8 == 0 and both are 16-byte aligned (the
+ * padding lanes of pred never enter the arithmetic), element by element otherwise (they are not read).
+ * Both: workspace of sdt_reduce_workspace_bytes() under the split-workspace contract above; B <= 8192.  Refused: null or misaligned
+ * pointers, B <= 0, cpad < C, another f, a floor outside [0, 1], a workspace that is too small. */
+int sdt_loss_mask_prepare(const float* mask, float* effective, float* pooled, float* sums, int B, int h, int w, int f, float floor_value,
+                          void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int sdt_masked_mse_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_nchw, const float* effective_mask, const float* mask_sums,
+                                const float* snr_weight, const float* loss_weight, float* loss_accum, float* loss_per_sample,
+                                uint16_t* dpred_nhwc, int B, int C, int H, int W, int cpad, void* workspace, int64_t workspace_bytes,
+                                hipStream_t stream);
 /* diffusers embeddings_flax.get_sinusoidal_embeddings -> bf16 (B, dim) */
 int sdt_timestep_embedding(const int32_t* timesteps, uint16_t* out, int B, int dim, int flip_sin_to_cos,
                            float freq_shift, hipStream_t stream);

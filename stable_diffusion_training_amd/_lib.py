@@ -60,6 +60,8 @@ SIGNATURES = {
     "sdt_cfg_rescale_factors": [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P],
     "sdt_sampler_cfg_step": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _I, _F, _F, _F, _F, _P],
     "sdt_mse_loss_fwd_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
+    "sdt_loss_mask_prepare": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _L, _P],
+    "sdt_masked_mse_loss_fwd_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
     "sdt_timestep_embedding": [_P, _P, _I, _I, _I, _F, _P],
     "sdt_sqnorm_accumulate": [_P, _L, _P, _P, _L, _P],
     "sdt_sqnorm_accumulate_bf16": [_P, _L, _P, _P, _L, _P],

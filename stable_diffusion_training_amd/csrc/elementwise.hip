@@ -288,6 +288,145 @@ __global__ void __launch_bounds__(256) mse_kernel(const bf16_t* __restrict__ pre
   if (threadIdx.x == 0) *loss += t * inv_count;
 }
 
+// ------------------------------------------------------------------ masked / per-sample weighted loss (include/sdt.h "MASKED LOSS")
+__device__ __forceinline__ float clamp01(float m) { return fminf(fmaxf(m, 0.f), 1.f); }  // a NaN counts as 0
+
+// mask f32 (B, h*F, w*F) -> pooled mask mp (optional) and effective mask e = fmaxf(mp, floor), f32 (B,h,w), and S[b] = sum_p e[b,p].
+// Grid (nb, B): workgroup j of sample b owns the latent positions j*256 + t, + nb*256, ...; one thread per position adds the F x F
+// block of clamped values in row-major order starting from +0 (so F = 1 is the clamp itself), times fl32(1 / F^2).  The sum S: each
+// thread adds its positions in order, block_sum, one partial per workgroup, added in workgroup order by the one that arrives last at
+// the sample's counter.  VEC: the F floats of a block row by 16-byte loads (F % 4 == 0 and a 16-byte aligned mask: every block row
+// then starts on a 16-byte boundary, because the row pitch w*F is a multiple of 4 floats).
+template <int F, bool VEC>
+__global__ void __launch_bounds__(256) loss_mask_prepare_kernel(const float* __restrict__ mask, float floor_v, float* __restrict__ e,
+                                                                float* __restrict__ mp, float* __restrict__ S, int h, int w,
+                                                                int* counters, float* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ float scratch[16];
+  __shared__ int s_last;
+  const int b = blockIdx.y, nb = gridDim.x, hw = h * w;
+  const long Wp = (long)w * F;
+  const float inv = 1.0f / (float)(F * F);
+  const float* mb = mask + (long)b * hw * F * F;
+  float acc = 0.f;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < hw; p += nb * 256) {
+    const int y = p / w, x = p - y * w;
+    const float* src = mb + (long)y * F * Wp + (long)x * F;
+    float s = 0.f;
+#pragma unroll
+    for (int r = 0; r < F; ++r) {
+      const float* row = src + r * Wp;
+      if (VEC) {
+#pragma unroll
+        for (int c = 0; c < F; c += 4) {
+          const float4 v = *reinterpret_cast<const float4*>(row + c);
+          s += clamp01(v.x); s += clamp01(v.y); s += clamp01(v.z); s += clamp01(v.w);
+        }
+      } else {
+#pragma unroll
+        for (int c = 0; c < F; ++c) s += clamp01(row[c]);
+      }
+    }
+    const float m = s * inv;
+    const float ev = fmaxf(m, floor_v);
+    const long o = (long)b * hw + p;
+    if (mp) mp[o] = m;
+    e[o] = ev;
+    acc += ev;
+  }
+  const float t = block_sum(acc, scratch);
+  float* pb = part + (long)b * nb;
+  if (threadIdx.x == 0) sdt_store_wt(pb + blockIdx.x, t);
+  if (!sdt_arrive_last<true>(counters + b, nb, &s_last)) return;
+  float tot = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) tot += sdt_load_wt(pb + i);
+  tot = block_sum(tot, scratch);
+  if (threadIdx.x == 0) S[b] = tot;
+}
+
+// pred bf16 NHWC (B,h,w,cpad), target f32 NCHW (B,C,h,w), e f32 (B,h,w) or null (all ones), S f32 (B) or null (no normalisation),
+// w1 / w2 f32 (B) or null (the min-SNR factor and the loss weight).  Grid (nb, B), the partition of loss_mask_prepare_kernel.
+//   k_b = fl(fl(w1*w2) * s_b),  s_b = 1 | (S_b == 0 ? 0 : fl(fl(HW) / S_b))
+//   dpred = bf16(fl(fl(fl(-2 * fl(k_b*e)) * diff) * inv_count))         (with k_b*e == 1 the chain of mse_kernel)
+//   a_b   = sum e*diff*diff over the sample: per thread in order, block_sum, partials in workgroup order by the last arriver, which
+//   writes loss_per_sample[b] = fl(fl(k_b*a_b) * inv_chw) and the sample's term fl(k_b*a_b); the workgroup that finishes the last sample
+//   adds the B terms in sample order and adds fl(total * inv_count) to *loss.
+// VEC: a position's cpad channels of pred / dpred as 16-byte vectors (cpad % 8 == 0, both aligned); padding lanes of pred are unpacked
+// but never enter the arithmetic, and dpred's are written as zero.
+template <bool VEC>
+__global__ void __launch_bounds__(256) masked_mse_kernel(const bf16_t* __restrict__ pred, const float* __restrict__ target,
+                                                         const float* __restrict__ e, const float* __restrict__ S,
+                                                         const float* __restrict__ w1, const float* __restrict__ w2,
+                                                         float* __restrict__ loss, float* __restrict__ loss_ps,
+                                                         bf16_t* __restrict__ dpred, int B, int C, int HW, int cpad, float inv_count,
+                                                         float inv_chw, int* counters, float* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ float scratch[16];
+  __shared__ int s_last;
+  const int b = blockIdx.y, nb = gridDim.x;
+  float k = (w1 ? w1[b] : 1.f) * (w2 ? w2[b] : 1.f);
+  if (S) {
+    const float sb = S[b];
+    k = k * (sb == 0.f ? 0.f : (float)HW / sb);
+  }
+  const float* tb = target + (long)b * C * HW;
+  float acc = 0.f;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += nb * 256) {
+    const long i = (long)b * HW + p;
+    const float ev = e ? e[i] : 1.f;
+    const float g = -2.f * (k * ev);
+    if (VEC) {
+      const uint4* prow = reinterpret_cast<const uint4*>(pred + i * cpad);
+      for (int c0 = 0; c0 < cpad; c0 += 8) {
+        float d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (c0 < C) {
+          float pv[8];
+          unpack8(prow[c0 >> 3], pv);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            if (c0 + j < C) {
+              const float diff = tb[(long)(c0 + j) * HW + p] - pv[j];
+              acc += ev * diff * diff;
+              d[j] = g * diff * inv_count;
+            }
+          }
+        }
+        if (dpred) *reinterpret_cast<uint4*>(dpred + i * cpad + c0) = pack8(d);
+      }
+    } else {
+      for (int c = 0; c < cpad; ++c) {
+        float d = 0.f;
+        if (c < C) {
+          const float diff = tb[(long)c * HW + p] - bf2f(pred[i * cpad + c]);
+          acc += ev * diff * diff;
+          d = g * diff * inv_count;
+        }
+        if (dpred) dpred[i * cpad + c] = f2bf(d);
+      }
+    }
+  }
+  const float s = block_sum(acc, scratch);
+  float* pb = part + (long)b * nb;   // per-workgroup partials of sample b
+  float* terms = part + (long)B * nb;  // the B finished per-sample terms
+  if (threadIdx.x == 0) sdt_store_wt(pb + blockIdx.x, s);
+  if (!sdt_arrive_last<true>(counters + b, nb, &s_last)) return;
+  float a = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) a += sdt_load_wt(pb + i);
+  a = block_sum(a, scratch);
+  if (threadIdx.x == 0) {
+    const float term = k * a;
+    loss_ps[b] = term * inv_chw;
+    sdt_store_wt(terms + b, term);
+  }
+  // second level: the workgroup that finishes the last sample adds the samples' terms in sample order
+  if (!sdt_arrive_last<true>(counters + B, B, &s_last)) return;
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int i = 0; i < B; ++i) t += sdt_load_wt(terms + i);
+    *loss += t * inv_count;
+  }
+}
+
 // get_sinusoidal_embeddings: out[b] = [cos(t*inv_i) | sin(t*inv_i)] (flip) or [sin|cos]
 __global__ void timestep_embed_kernel(const int* __restrict__ t, bf16_t* __restrict__ out, int B, int dim,
                                       int flip_sin_to_cos, float freq_shift, float max_period) {
@@ -724,6 +863,24 @@ __global__ void __launch_bounds__(256) zero_ranges_kernel(float4* __restrict__ b
   for (long i = threadIdx.x; i < count; i += 256) base[first + i] = make_float4(0.f, 0.f, 0.f, 0.f);
 }
 
+/* Workgroups per sample of the two masked-loss kernels: one per 256 latent positions, at most MASKED_MAX_BLOCKS, and few enough that
+ * the B * nb partials and the B per-sample terms fit the 64 KiB scratch of sdt_reduce_workspace_bytes() (B <= MASKED_MAX_B). */
+#define MASKED_MAX_BLOCKS 128
+#define MASKED_MAX_B 8192
+static int masked_blocks(int B, long hw) {
+  long nb = (hw + 255) / 256, fit = (65536 / (long)sizeof(float) - B) / B;
+  if (nb > MASKED_MAX_BLOCKS) nb = MASKED_MAX_BLOCKS;
+  if (nb > fit) nb = fit;
+  return (int)(nb < 1 ? 1 : nb);
+}
+
+template <int F>
+static void loss_mask_prepare_launch(bool vec, dim3 grid, hipStream_t stream, const float* mask, float floor_v, float* e, float* mp,
+                                     float* S, int h, int w, int* counters, float* part) {
+  if (vec) hipLaunchKernelGGL((loss_mask_prepare_kernel<F, (F >= 4)>), grid, dim3(256), 0, stream, mask, floor_v, e, mp, S, h, w, counters, part);
+  else hipLaunchKernelGGL((loss_mask_prepare_kernel<F, false>), grid, dim3(256), 0, stream, mask, floor_v, e, mp, S, h, w, counters, part);
+}
+
 extern "C" {
 
 int sdt_add_noise_velocity(const float* latents, const float* noise, const int32_t* timesteps,
@@ -840,6 +997,57 @@ int sdt_mse_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_nchw, co
                      (const bf16_t*)pred_nhwc, target_nchw, weight, loss_accum, (bf16_t*)dpred_nhwc, B, C, H * W, cpad,
                      inv_count, reinterpret_cast<int*>(workspace), reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
   SDT_LAUNCH_CHECK("sdt_mse_loss_fwd_bwd");
+  return SDT_OK;
+}
+
+int sdt_loss_mask_prepare(const float* mask, float* effective, float* pooled, float* sums, int B, int h, int w, int f, float floor_value,
+                          void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  SDT_CHECK_ARG(mask && effective && sums, "sdt_loss_mask_prepare: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)mask | (uintptr_t)effective | (uintptr_t)pooled | (uintptr_t)sums) & 3) == 0,
+                "sdt_loss_mask_prepare: misaligned pointer (4 bytes)");
+  SDT_CHECK_ARG(B > 0 && B <= MASKED_MAX_B && h > 0 && w > 0 && (long)h * w <= (1L << 30),
+                "sdt_loss_mask_prepare: bad shape B=%d h=%d w=%d (1 <= B <= %d)", B, h, w, MASKED_MAX_B);
+  SDT_CHECK_ARG(f == 1 || f == 2 || f == 4 || f == 8 || f == 16, "sdt_loss_mask_prepare: f=%d (the mask's scale must be 1, 2, 4, 8 or 16)", f);
+  SDT_CHECK_ARG(floor_value >= 0.f && floor_value <= 1.f, "sdt_loss_mask_prepare: floor %g must lie in [0, 1]", floor_value);
+  SDT_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= sdt_reduce_workspace_bytes(),
+                "sdt_loss_mask_prepare: workspace of sdt_reduce_workspace_bytes() needed");
+  const dim3 grid(masked_blocks(B, (long)h * w), B);
+  const bool vec = f >= 4 && ((uintptr_t)mask & 15) == 0;
+  int* counters = reinterpret_cast<int*>(workspace);
+  float* part = reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES);
+  switch (f) {
+    case 1: loss_mask_prepare_launch<1>(vec, grid, stream, mask, floor_value, effective, pooled, sums, h, w, counters, part); break;
+    case 2: loss_mask_prepare_launch<2>(vec, grid, stream, mask, floor_value, effective, pooled, sums, h, w, counters, part); break;
+    case 4: loss_mask_prepare_launch<4>(vec, grid, stream, mask, floor_value, effective, pooled, sums, h, w, counters, part); break;
+    case 8: loss_mask_prepare_launch<8>(vec, grid, stream, mask, floor_value, effective, pooled, sums, h, w, counters, part); break;
+    default: loss_mask_prepare_launch<16>(vec, grid, stream, mask, floor_value, effective, pooled, sums, h, w, counters, part); break;
+  }
+  SDT_LAUNCH_CHECK("sdt_loss_mask_prepare");
+  return SDT_OK;
+}
+
+int sdt_masked_mse_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_nchw, const float* effective_mask, const float* mask_sums,
+                                const float* snr_weight, const float* loss_weight, float* loss_accum, float* loss_per_sample,
+                                uint16_t* dpred_nhwc, int B, int C, int H, int W, int cpad, void* workspace, int64_t workspace_bytes,
+                                hipStream_t stream) {
+  SDT_CHECK_ARG(pred_nhwc && target_nchw && loss_accum && loss_per_sample, "sdt_masked_mse_loss_fwd_bwd: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)target_nchw | (uintptr_t)effective_mask | (uintptr_t)mask_sums | (uintptr_t)snr_weight | (uintptr_t)loss_weight |
+                  (uintptr_t)loss_accum | (uintptr_t)loss_per_sample) & 3) == 0 && (((uintptr_t)pred_nhwc | (uintptr_t)dpred_nhwc) & 1) == 0,
+                "sdt_masked_mse_loss_fwd_bwd: misaligned pointer (4 bytes, bf16: 2 bytes)");
+  SDT_CHECK_ARG(B > 0 && B <= MASKED_MAX_B && C > 0 && H > 0 && W > 0 && (long)H * W <= (1L << 30),
+                "sdt_masked_mse_loss_fwd_bwd: bad shape B=%d C=%d H=%d W=%d (1 <= B <= %d)", B, C, H, W, MASKED_MAX_B);
+  SDT_CHECK_ARG(cpad >= C, "sdt_masked_mse_loss_fwd_bwd: cpad=%d < C=%d", cpad, C);
+  SDT_CHECK_ARG(effective_mask || !mask_sums, "sdt_masked_mse_loss_fwd_bwd: mask sums (normalisation) need the effective mask");
+  SDT_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= sdt_reduce_workspace_bytes(),
+                "sdt_masked_mse_loss_fwd_bwd: workspace of sdt_reduce_workspace_bytes() needed");
+  const int HW = H * W;
+  const float inv_count = 1.0f / ((float)B * C * H * W), inv_chw = 1.0f / ((float)C * H * W);
+  const bool vec = cpad % 8 == 0 && (((uintptr_t)pred_nhwc | (uintptr_t)dpred_nhwc) & 15) == 0;
+  auto kern = vec ? masked_mse_kernel<true> : masked_mse_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(masked_blocks(B, HW), B), dim3(256), 0, stream, (const bf16_t*)pred_nhwc, target_nchw, effective_mask,
+                     mask_sums, snr_weight, loss_weight, loss_accum, loss_per_sample, (bf16_t*)dpred_nhwc, B, C, HW, cpad, inv_count, inv_chw,
+                     reinterpret_cast<int*>(workspace), reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
+  SDT_LAUNCH_CHECK("sdt_masked_mse_loss_fwd_bwd");
   return SDT_OK;
 }
 

@@ -10,7 +10,10 @@ therefore encodes every batch as the loader delivers it - one record per batch, 
 Layout of a cache directory (plain numpy, nothing compressed):
   index.json          {"format_version": 1, "latent_channels": L, "buckets": [[B, 3, H, W], ...] (training_utils.step_key of each
                       record, in order), "vae_digest": sha256 of the encoder weights the moments came from}
-  record_000000.npz   moments uint16 (B,h,w,2L) (the bf16 bit patterns), input_ids, and time_ids / text_embeds where the batch has them
+  record_000000.npz   moments uint16 (B,h,w,2L) (the bf16 bit patterns), input_ids, and time_ids / text_embeds where the batch has them;
+                      for a batch with a loss_mask, loss_mask float32 (B,h,w): the mask pooled to the latent grid by
+                      sdt_loss_mask_prepare, before the floor (the floor is applied in the step: one cache serves any floor); and
+                      loss_weight float32 (B,) as the batch holds it.  A record of a batch without them is what it was before they existed.
 A cached SD1.5 512x512 sample is 64 KiB; its fp32 pixels are 3 MiB.
 """
 import hashlib
@@ -20,10 +23,12 @@ import os
 import numpy as np
 import torch
 
+from . import _lib, ops
 from .training_utils import encode_latent_moments, step_key
 
 FORMAT_VERSION = 1
 EXTRA_KEYS = ("input_ids", "time_ids", "text_embeds")  # what a record keeps of a batch besides the moments
+LOSS_WEIGHT_KEY, LOSS_MASK_KEY = "loss_weight", "loss_mask"  # kept too: the weight as it is, the mask pooled to the latent grid
 
 
 def vae_digest(frozen_vae):
@@ -60,8 +65,9 @@ class Writer:
         os.makedirs(path, exist_ok=True)
         self.path, self.latent_channels, self.digest, self.buckets = path, int(latent_channels), str(digest), []
 
-    def add(self, moments, batch):
-        """moments: bf16 (B,h,w,2L) tensor of `batch` (any device); batch: the loader's dict, of which EXTRA_KEYS are kept."""
+    def add(self, moments, batch, loss_mask=None):
+        """moments: bf16 (B,h,w,2L) tensor of `batch` (any device); batch: the loader's dict, of which EXTRA_KEYS and loss_weight are
+        kept; loss_mask: the batch's mask at LATENT size, f32 (B,h,w) (pool_loss_mask), or None."""
         if moments.dtype != torch.bfloat16 or moments.dim() != 4 or moments.shape[3] != 2 * self.latent_channels:
             raise ValueError(f"moments must be bfloat16 (B,h,w,{2 * self.latent_channels}), not {moments.dtype} {tuple(moments.shape)}")
         rec = {"moments": moments.detach().contiguous().cpu().view(torch.int16).numpy().view(np.uint16)}
@@ -69,6 +75,13 @@ class Writer:
             if k in batch:
                 v = batch[k].detach().cpu()
                 rec[k] = (v.view(torch.int16).numpy().view(np.uint16) if v.dtype == torch.bfloat16 else v.numpy())
+        if loss_mask is not None:
+            if loss_mask.dtype != torch.float32 or tuple(loss_mask.shape) != tuple(moments.shape[:3]):
+                raise ValueError(f"loss_mask must be float32 {tuple(moments.shape[:3])} (latent size), not {loss_mask.dtype} "
+                                 f"{tuple(loss_mask.shape)}")
+            rec[LOSS_MASK_KEY] = loss_mask.detach().contiguous().cpu().numpy()
+        if LOSS_WEIGHT_KEY in batch:
+            rec[LOSS_WEIGHT_KEY] = batch[LOSS_WEIGHT_KEY].detach().to(torch.float32).contiguous().cpu().numpy()
         with open(_record_path(self.path, len(self.buckets)), "wb") as f:
             np.savez(f, **rec)
         self.buckets.append(list(step_key({"latent_moments": moments})))
@@ -80,15 +93,37 @@ class Writer:
         return self.path
 
 
+def pool_loss_mask(mask, h, w):
+    """A batch's loss_mask f32 (B,H,W) on the GPU -> the pooled mask f32 (B,h,w) of the latent grid, by the kernel the step itself
+    uses (sdt_loss_mask_prepare with floor 0 writes the un-floored pooled mask beside the effective one)."""
+    B, H, W = mask.shape
+    f = H // h
+    if f not in (1, 2, 4, 8, 16) or (H, W) != (h * f, w * f):
+        raise ValueError(f"loss_mask {tuple(mask.shape)} against the latent grid ({h}, {w}): the scale must be the same power of two, "
+                         "at most 16, on both axes")
+    dev = mask.device
+    pooled, eff = torch.empty(B, h, w, dtype=torch.float32, device=dev), torch.empty(B, h, w, dtype=torch.float32, device=dev)
+    sums = torch.empty(B, dtype=torch.float32, device=dev)
+    rws = ops.reduce_workspace(_lib.load().sdt_reduce_workspace_bytes(), dev)
+    _lib.call("sdt_loss_mask_prepare", mask.data_ptr(), eff.data_ptr(), pooled.data_ptr(), sums.data_ptr(), B, h, w, f, 0.0,
+              rws.data_ptr(), rws.numel(), torch.cuda.current_stream().cuda_stream)
+    return pooled
+
+
 @torch.no_grad()
 def build(batches, frozen_vae, path):
     """Encode every batch of `batches` (a loader with grab_next_batch, or an iterable; "end_of_batch" ends it) with the frozen VAE,
-    at the shape it arrives in, into the cache directory `path`.  Returns the number of records."""
+    at the shape it arrives in, into the cache directory `path`.  A batch's loss_mask is stored pooled to the latent grid, its
+    loss_weight as it is.  Returns the number of records."""
     w = Writer(path, frozen_vae.call["latent_channels"], vae_digest(frozen_vae))
     dev = frozen_vae.params.device
     for batch in _walk(batches):
         px = batch["pixel_values"].to(dev, torch.float32).contiguous()
-        w.add(encode_latent_moments(frozen_vae, px), batch)
+        moments = encode_latent_moments(frozen_vae, px)
+        pooled = None
+        if LOSS_MASK_KEY in batch:
+            pooled = pool_loss_mask(batch[LOSS_MASK_KEY].to(dev, torch.float32).contiguous(), moments.shape[1], moments.shape[2])
+        w.add(moments, batch, loss_mask=pooled)
     w.close()
     return len(w.buckets)
 

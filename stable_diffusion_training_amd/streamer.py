@@ -17,7 +17,8 @@ class DataLoader:
     def __init__(self, tokenizer_obj=None, config=None, ramdisk_path=None, training_batch_size=8, repeat_batch=10,
                  maximum_resolution_areas=(512 ** 2,), bucket_lower_bound_resolutions=(256,), numb_of_worker_thread=1,
                  queue_get_timeout=60, chunk_number=0, seed=0, context_concatenation_multiplier=1, *,
-                 batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu", text_towers=1):
+                 batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu", text_towers=1,
+                 loss_masks=False, prior_every=0, prior_loss_weight=1.0):
         if len(maximum_resolution_areas) != len(bucket_lower_bound_resolutions):
             raise ValueError("number of elements in maximum_resolution_areas and bucket_lower_bound_resolutions is not match!")
         if training_batch_size % world_size:
@@ -30,6 +31,9 @@ class DataLoader:
         if text_towers not in (1, 2):
             raise ValueError(f"text_towers={text_towers!r}: 1 (SD1.x / 2.x) or 2 (SDXL)")
         self.text_towers = text_towers
+        if not isinstance(prior_every, int) or prior_every < 0:
+            raise ValueError(f"prior_every={prior_every!r}: 0 (no class images) or n > 0 (every n-th sample is one)")
+        self.loss_masks, self.prior_every, self.prior_loss_weight = bool(loss_masks), prior_every, float(prior_loss_weight)
         self.buckets = [tuple(int(v) for v in b) for area, lo in zip(maximum_resolution_areas, bucket_lower_bound_resolutions)
                         for b in calculate_resolution_array(area, lo, 64)]
         self._batches_per_chunk = batches_per_chunk
@@ -64,7 +68,11 @@ class DataLoader:
         """dict(pixel_values f32 (B,3,bucket[0],bucket[1]) in [-1,1], input_ids / attention_mask int32 (B, k*77)) for this
         rank's shard, or "end_of_batch" when the chunk is exhausted (training.py:195-199).  text_towers=2 (SDXL): input_ids /
         attention_mask (B, k*2*77), which reshape to (B*k, 2, 77) - one row per tower - and time_ids int32 (B, 6) = (bucket height,
-        width, 0, 0, height, width): the uncropped size micro-conditioning."""
+        width, 0, 0, height, width): the uncropped size micro-conditioning.
+        loss_masks=True adds loss_mask f32 (B, bucket[0], bucket[1]): one seeded rectangle of ones per image (the "subject"), zero
+        outside, drawn from a generator of its own - the other entries are what they are without it.  prior_every=n > 0 marks every n-th
+        sample of the global batch (global index % n == n - 1) as a class image and adds loss_weight f32 (B,): 1.0 for instance images,
+        prior_loss_weight for class images (DreamBooth prior preservation).  The defaults add neither."""
         if self._cursor >= len(self._plan):
             return "end_of_batch"
         b0, b1 = self._plan[self._cursor]
@@ -81,6 +89,18 @@ class DataLoader:
         batch = {"pixel_values": px, "input_ids": ids, "attention_mask": torch.ones_like(ids)}
         if self.text_towers == 2:
             batch["time_ids"] = torch.tensor([[b0, b1, 0, 0, b0, b1]] * per_rank, dtype=torch.int32)
+        if self.loss_masks:
+            gm = torch.Generator().manual_seed(((int(self.seed) * 1_000_003 + int(self.chunk_number)) * 1_000_003 + index * 64 + self.rank) ^ 0x5DEECE66D)
+            mask = torch.zeros(per_rank, b0, b1)
+            for i in range(per_rank):  # a rectangle covering between a quarter and the whole of each axis
+                hh, ww = (int(torch.randint(n // 4, n + 1, (1,), generator=gm)) for n in (b0, b1))
+                y0, x0 = int(torch.randint(0, b0 - hh + 1, (1,), generator=gm)), int(torch.randint(0, b1 - ww + 1, (1,), generator=gm))
+                mask[i, y0: y0 + hh, x0: x0 + ww] = 1.0
+            batch["loss_mask"] = mask
+        if self.prior_every:
+            first = self.rank * per_rank  # this shard's first sample in the global batch
+            batch["loss_weight"] = torch.tensor([self.prior_loss_weight if (first + i) % self.prior_every == self.prior_every - 1 else 1.0
+                                                 for i in range(per_rank)], dtype=torch.float32)
         if self.device.type != "cpu":
             batch = {k: v.to(self.device, non_blocking=True) for k, v in batch.items()}
         if self._print_debug:

@@ -265,7 +265,48 @@ def step_key(batch, downscale=8):
     return (int(B), 3, int(h) * downscale, int(w) * downscale)
 
 
-def _check_batch(batch, unet_cfg, frozen_vae_state, device):
+LOSS_KEYS = ("loss_mask", "loss_weight")  # the optional batch entries that select the masked / weighted loss kernels
+
+
+def _on_device(t, device):
+    return t.device.type == device.type and (device.index is None or t.device.index == device.index)
+
+
+def _check_loss_entries(batch, device, masked_loss_floor, normalize_masked_area):
+    """ValueError for loss_mask / loss_weight entries (and their two options) that the masked loss cannot take."""
+    floor = masked_loss_floor
+    if isinstance(floor, bool) or not isinstance(floor, (int, float)) or not 0.0 <= float(floor) <= 1.0:
+        raise ValueError(f"masked_loss_floor={floor!r} must be a number in [0, 1]")
+    mask, weight = batch.get("loss_mask"), batch.get("loss_weight")
+    if normalize_masked_area and mask is None:
+        raise ValueError("normalize_masked_area needs a loss_mask in the batch")
+    image = batch["latent_moments"] if "latent_moments" in batch else batch["pixel_values"]
+    B = int(image.shape[0])
+    if mask is not None:
+        if "latent_moments" in batch:
+            want, where = (B, int(image.shape[1]), int(image.shape[2])), "latent_moments (B,h,w,2L): latent size (B,h,w)"
+        else:
+            want, where = (B, int(image.shape[2]), int(image.shape[3])), "pixel_values (B,3,H,W): pixel size (B,H,W)"
+        if not torch.is_tensor(mask) or mask.dtype != torch.float32:
+            raise ValueError(f"loss_mask must be a float32 tensor, not {getattr(mask, 'dtype', type(mask))}")
+        if not _on_device(mask, device):
+            raise ValueError(f"loss_mask lives on {mask.device}, the step runs on {device}")
+        if tuple(mask.shape) != want:
+            raise ValueError(f"loss_mask has shape {tuple(mask.shape)}; beside {where} = {want}")
+        if not mask.is_contiguous():
+            raise ValueError("loss_mask must be contiguous")
+    if weight is not None:
+        if not torch.is_tensor(weight) or weight.dtype != torch.float32:
+            raise ValueError(f"loss_weight must be a float32 tensor, not {getattr(weight, 'dtype', type(weight))}")
+        if not _on_device(weight, device):
+            raise ValueError(f"loss_weight lives on {weight.device}, the step runs on {device}")
+        if tuple(weight.shape) != (B,):
+            raise ValueError(f"loss_weight has shape {tuple(weight.shape)}: one weight per sample, ({B},)")
+        if not weight.is_contiguous():
+            raise ValueError("loss_weight must be contiguous")
+
+
+def _check_batch(batch, unet_cfg, frozen_vae_state, device, masked_loss_floor=0.0, normalize_masked_area=False):
     """ValueError for a batch train_step cannot run, before any kernel.  Returns whether the batch holds cached moments."""
     has_px, has_mom = "pixel_values" in batch, "latent_moments" in batch
     if has_px and has_mom:
@@ -275,6 +316,7 @@ def _check_batch(batch, unet_cfg, frozen_vae_state, device):
     if has_px:
         if frozen_vae_state is None:
             raise ValueError("pixel_values need the frozen VAE: frozen_vae_state is None (only latent_moments train without it)")
+        _check_loss_entries(batch, device, masked_loss_floor, normalize_masked_area)
         return False
     m = batch["latent_moments"]
     if not torch.is_tensor(m) or m.dtype != torch.bfloat16 or m.dim() != 4:
@@ -291,6 +333,7 @@ def _check_batch(batch, unet_cfg, frozen_vae_state, device):
     if unet_cfg.get("addition_embed_type") == "text_time" and "time_ids" not in batch:
         raise ValueError("a text_time (SDXL) UNet's default time_ids come from the pixel size, which cached latent_moments no longer "
                          "carry: the batch must hold time_ids")
+    _check_loss_entries(batch, device, masked_loss_floor, normalize_masked_area)
     return True
 
 
@@ -300,7 +343,7 @@ _FUSED_NORM = True  # False: always the pass over the gradient buffer (same bits
 def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, batch, train_rng,
                frozen_vae_state, frozen_noise_scheduler_state, strip_bos_eos_token=True, offset_noise_magnitude=0.0,
                min_snr_gamma_magnitude=0.0, perturbation_noise_magnitude=0.0, ema_rate=0.0, *, rand=None, reducer=None,
-               vae_scale=0.18215, aux=None, micro_batches=1):
+               vae_scale=0.18215, aux=None, micro_batches=1, masked_loss_floor=0.0, normalize_masked_area=False):
     """One DDPM training step on this rank's shard of the batch (training_utils.py:504-762), in place.
 
     batch: {"pixel_values": f32 (B,3,H,W) NCHW device tensor, "input_ids": i32 (B*k,77), "attention_mask": unused}.
@@ -324,6 +367,16 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     gradient is skipped - projects dW onto the factors (adapter.project) and steps the adapters' stores; a text encoder without an
     adapter only runs its forward.  A reducer is refused (ValueError): the data-parallel exchange would have to be built over the adapter
     stores.
+    Masked and weighted loss (include/sdt.h "MASKED LOSS"): a batch may hold "loss_mask", f32 contiguous on the step's device - (B,H,W)
+    at pixel size beside pixel_values, (B,h,w) at latent size beside latent_moments - and "loss_weight", f32 (B,).  The mask is pooled to
+    the latent grid (the mean of each block of clamp(m, 0, 1)), floored (masked_loss_floor in [0, 1]: OneTrainer's unmasked weight; 0 is a
+    plain multiply) and multiplies each position's squared error; normalize_masked_area rescales each sample by h*w / (the sum of its
+    effective mask), 0 for a sample that is masked out entirely; loss_weight multiplies the sample's loss (DreamBooth's
+    prior_loss_weight) beside the min-SNR factor.  Neither enters the forward pass, the draws or the target.  With either key the loss
+    runs as sdt_loss_mask_prepare (mask only) + sdt_masked_mse_loss_fwd_bwd and metrics gains "loss_per_sample" (B,) (the micro-batches'
+    concatenated); aux= taps record the effective mask as aux["loss_mask"].  With neither, the step is launch for launch the plain one.
+    ValueError for a mask of another dtype, device, shape or layout, a loss_weight that is not (B,), a floor outside [0, 1] and
+    normalize_masked_area without a mask.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
     text_time = unet_state.config.get("addition_embed_type") == "text_time"
     sdxl = text_time and nets.sdxl_conditioning(text_encoder_state.config)
@@ -344,7 +397,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     opt_stores = [a.store for a in adapters] if lora else [us, ts]
     sched, sched_state = frozen_noise_scheduler_state.call, frozen_noise_scheduler_state.params
     dev = us.device
-    cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev)
+    cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev, masked_loss_floor, normalize_masked_area)
+    masked = any(k in batch for k in LOSS_KEYS)
     image_key = "latent_moments" if cached else "pixel_values"
     stream = torch.cuda.current_stream().cuda_stream
     rand = rand or {}
@@ -364,13 +418,13 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
 
     def forward_backward(k, fused_norm):
         """Micro-batch k (the whole batch when K = 1): VAE encode, draws, CLIP, UNet, MSE, backward into grad / grad16.
-        Returns (loss (1,), squared-norm slots of the two stores or None)."""
+        Returns (loss (1,), squared-norm slots of the two stores or None, loss per sample (B,) or None)."""
         if K == 1:
             mb, rnd = batch, rand
         else:
             sl = slice(k * B, (k + 1) * B)
             kc = batch["input_ids"].shape[0] // N  # text-encoder rows per sample
-            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids")}
+            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids") + LOSS_KEYS}
             mb["input_ids"] = batch["input_ids"][k * B * kc: (k + 1) * B * kc]
             rnd = {n: v[sl] for n, v in rand.items()}
 
@@ -488,9 +542,32 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         dpred = torch.empty_like(pred)
         C_out = unet_state.config["out_channels"]
         rws = ops.reduce_workspace(_lib.load().sdt_reduce_workspace_bytes(), dev)
-        _lib.call("sdt_mse_loss_fwd_bwd", pred.data_ptr(), target.data_ptr(), None if wts is None else wts.data_ptr(),
-                  loss.data_ptr(), dpred.data_ptr(), B, C_out, h, w, pred.shape[3], rws.data_ptr(), rws.numel(), stream)
+        lps = emask = None
+        if masked:
+            # the effective latent mask and its per-sample sums, then the loss per sample first; a batch with loss_weight only passes no mask
+            msum = None
+            mask = mb.get("loss_mask")
+            if mask is not None:
+                f = mask.shape[1] // h
+                if f not in (1, 2, 4, 8, 16) or tuple(mask.shape[1:]) != (h * f, w * f):
+                    raise ValueError(f"loss_mask {tuple(mask.shape)} against the latent grid ({h}, {w}): the scale must be the same power of "
+                                     "two, at most 16, on both axes")
+                emask = torch.empty(B, h, w, dtype=torch.float32, device=dev)
+                msum = torch.empty(B, dtype=torch.float32, device=dev)
+                _lib.call("sdt_loss_mask_prepare", mask.data_ptr(), emask.data_ptr(), None, msum.data_ptr(), B, h, w, f,
+                          float(masked_loss_floor), rws.data_ptr(), rws.numel(), stream)
+            lw = mb.get("loss_weight")
+            lps = torch.empty(B, dtype=torch.float32, device=dev)
+            _lib.call("sdt_masked_mse_loss_fwd_bwd", pred.data_ptr(), target.data_ptr(), None if emask is None else emask.data_ptr(),
+                      msum.data_ptr() if normalize_masked_area else None, None if wts is None else wts.data_ptr(),
+                      None if lw is None else lw.data_ptr(), loss.data_ptr(), lps.data_ptr(), dpred.data_ptr(), B, C_out, h, w,
+                      pred.shape[3], rws.data_ptr(), rws.numel(), stream)
+        else:
+            _lib.call("sdt_mse_loss_fwd_bwd", pred.data_ptr(), target.data_ptr(), None if wts is None else wts.data_ptr(),
+                      loss.data_ptr(), dpred.data_ptr(), B, C_out, h, w, pred.shape[3], rws.data_ptr(), rws.numel(), stream)
         if aux is not None:
+            if emask is not None:
+                aux["loss_mask"] = emask
             aux.update(latents=latents, noisy=noisy_nchw, ctx=ctx.detach(), pred=pred.detach(), target=target, moments=moments)
             if pooled is not None:
                 aux["text_embeds"] = pooled.detach()
@@ -505,12 +582,12 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             ad.project()
         sq_u = ops.sq_end(us) if fused_norm else None
         sq_t = ops.sq_end(ts) if fused_norm else None
-        return loss, sq_u, sq_t
+        return loss, sq_u, sq_t, lps
 
     if K == 1:
         # one process: the norm clip_by_global_norm needs is that of the gradients as the weight-gradient kernels write them - they leave
         # its partial sums behind (ops.sq_begin / sq_end), and the 4-byte-per-parameter pass over the finished buffer is not needed
-        loss, sq_u, sq_t = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora)
+        loss, sq_u, sq_t, lps = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora)
         grad_source = "grad"
         # data-parallel mean of the gradients (implicit all-reduce under GSPMD in the reference)
         if reducer is not None:
@@ -522,14 +599,17 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         # per-sample mean and nothing in the VAE / CLIP / UNet mixes samples.  One process: the last pass (finish) also scales and
         # takes the squared norm.  Data parallel: the last pass is an add, the fp32 sums are all-reduced, then scale + norm.
         exchange = reducer is not None and reducer.active
-        losses = []
+        losses, per_sample = [], []
         for k in range(K):
-            losses.append(forward_backward(k, False)[0])
+            out_k = forward_backward(k, False)
+            losses.append(out_k[0])
+            per_sample.append(out_k[3])
             mode = "init" if k == 0 else ("finish" if k == K - 1 and not exchange else "add")
             with trace.phase("grad_accumulate"):
                 for st in opt_stores:
                     st.accumulate(mode, 1.0 / K if mode == "finish" else 1.0, norm=mode == "finish")
         loss = torch.cat(losses).mean(0, keepdim=True)
+        lps = torch.cat(per_sample) if masked else None
         sq_u = sq_t = None
         grad_source = "acc"
         if exchange:
@@ -552,8 +632,11 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         if reducer is not None:
             reducer.after_optimizer()  # sharded optimizer: all-gather the bf16 weight mirrors the owners have just written
     ops.gn_arena_end(dev)
+    metrics = {"loss": loss[0]}
+    if masked:
+        metrics["loss_per_sample"] = lps  # local to this rank under data parallelism
     return (unet_state, text_encoder_state, unet_ema_params if ur else None, text_encoder_ema_params if tr else None,
-            {"loss": loss[0]}, train_rng)
+            metrics, train_rng)
 
 
 # Other threads keep making HIP calls while a step is captured (RCCL's watchdog polls events, loaders pin memory): only the
@@ -582,7 +665,7 @@ class _GraphedStep:
 
     def __init__(self, fn, warmup=2, reducer=None):
         self.fn, self.warmup, self.calls = fn, warmup, 0
-        self.graph = self.static = self.static_rand = self.out = self.sig = None
+        self.graph = self.static = self.static_rand = self.out = self.sig = self.loss_keys = None
         # multi-rank: graph A (forward + backward) | eager bucketed all-reduce behind per-bucket events | graph B (optimizer)
         self.reducer = reducer if (reducer is not None and reducer.active) else None
         self.graph_b = self.plan = None
@@ -592,6 +675,7 @@ class _GraphedStep:
         self.static = {k: v.clone() for k, v in batch.items() if torch.is_tensor(v)}
         self.static_rand = None if rand is None else {k: v.clone() for k, v in rand.items()}
         self.sig = self._sig(us, ts, ue, te, rng, vae, sched, rand)
+        self.loss_keys = tuple(k in batch for k in LOSS_KEYS)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         if rng is not None and hasattr(g, "register_generator_state"):
@@ -675,6 +759,10 @@ class _GraphedStep:
                 return self.fn(us, ts, ue, te, batch, rng, vae, sched, rand=rand)
         if self.sig != self._sig(us, ts, ue, te, rng, vae, sched, rand):
             raise ValueError("a captured train_step is bound to the state objects (and rand= keys) it was captured with")
+        if self.loss_keys != tuple(k in batch for k in LOSS_KEYS):
+            had = [k for k, on in zip(LOSS_KEYS, self.loss_keys) if on] or "neither"
+            raise ValueError(f"this step was captured with {had} of {list(LOSS_KEYS)} in its batch and replays those launches: a batch that "
+                             "adds or drops one of them needs a step table of its own")
         for k, v in self.static.items():
             v.copy_(batch[k], non_blocking=True)
         if rand is not None:
@@ -693,7 +781,7 @@ class _GraphedStep:
         for st in _stepping_stores(us, ts):
             st.count += 1
         o = self.out
-        return o[0], o[1], o[2], o[3], {"loss": o[4]["loss"].clone()}, o[5]
+        return o[0], o[1], o[2], o[3], {k: v.clone() for k, v in o[4].items()}, o[5]
 
 
 def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params,
@@ -706,7 +794,10 @@ def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_pa
     the bucketed all-reduce, which stays outside the graphs and overlaps graph A bucket by bucket (dp.ExchangePlan).
     micro_batches=K: every step accumulates K micro-batches of per_device_batch (train_step micro_batches); the keys are then the
     batch the loader delivers, (K * per_device_batch, 3, H, W), and one graph (graph A: through the last micro-batch's add pass, with
-    a reducer) holds all K forward / backward passes."""
+    a reducer) holds all K forward / backward passes.
+    step_overrides: keyword options of train_step that TrainingConfig has no field for, e.g. vae_scale, or masked_loss_floor /
+    normalize_masked_area for batches with a loss_mask.  A captured step replays the launches of the batch it was captured with: it
+    raises ValueError for a later batch that adds or drops loss_mask / loss_weight."""
     import os
     B = per_device_batch or training_config.batch_size
     if not isinstance(micro_batches, int) or micro_batches < 1:
