@@ -17,7 +17,9 @@ dropped, and the steps train from the cache's readers without a VAE.
 --masked-loss [FLOOR] (or "masked_loss" in the config: true or the floor): the loader emits a loss mask per image and the loss counts
 each latent position by its pooled mask, at least FLOOR (default 0: only the masked area trains); --normalize-masked-area
 ("normalize_masked_area") rescales every sample by area / masked area; --prior-loss-weight W ("prior_loss_weight"): every second sample is a
-class image whose loss counts W times (DreamBooth prior preservation).  A latent cache keeps the pooled masks and the weights."""
+class image whose loss counts W times (DreamBooth prior preservation).  A latent cache keeps the pooled masks and the weights.
+--loss-type huber | smooth_l1 ("loss_type"; l2 is the default) trains on the pseudo-Huber loss, with --huber-c C ("huber_c", default 0.1)
+and --huber-schedule snr | exponential | constant ("huber_schedule", default snr) for the threshold of each sample's timestep."""
 import argparse
 import json
 import os
@@ -97,6 +99,10 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     if use_mask:
         loss_overrides = dict(masked_loss_floor=0.0 if masked_loss is True else float(masked_loss),
                               normalize_masked_area=bool(config_dict.get("normalize_masked_area", False)))
+    # Huber / smooth-L1: "loss_type" (absent or "l2": the squared error), "huber_c", "huber_schedule"
+    if config_dict.get("loss_type", "l2") != "l2":
+        loss_overrides.update(loss_type=config_dict["loss_type"], huber_c=float(config_dict.get("huber_c", 0.1)),
+                              huber_schedule=config_dict.get("huber_schedule", "snr"))
     dataloader = DataLoader(
         tokenizer_obj=tokenizer, config=None, ramdisk_path=config_dict.get("ramdisk_path"),
         training_batch_size=config_dict["batch_size"], repeat_batch=config_dict["repeat_batch"],
@@ -251,6 +257,11 @@ if __name__ == "__main__":
                     help="with --masked-loss: rescale each sample's loss by area / masked area")
     ap.add_argument("--prior-loss-weight", metavar="W", type=float, default=None,
                     help="every second sample is a class image whose loss counts W times (DreamBooth prior preservation)")
+    ap.add_argument("--loss-type", choices=("l2", "huber", "smooth_l1"), default=None,
+                    help="l2 (default); huber / smooth_l1: the pseudo-Huber losses, robust to outlier images and high-noise timesteps")
+    ap.add_argument("--huber-c", metavar="C", type=float, default=None, help="the Huber threshold the schedule ends at (default 0.1)")
+    ap.add_argument("--huber-schedule", choices=("constant", "exponential", "snr"), default=None,
+                    help="how the threshold follows the timestep: snr (default), exponential or constant")
     args = ap.parse_args()
     if args.dora and args.lora is None:
         ap.error("--dora needs --lora RANK")
@@ -272,4 +283,10 @@ if __name__ == "__main__":
         cfg["normalize_masked_area"] = True
     if args.prior_loss_weight is not None:
         cfg["prior_loss_weight"] = args.prior_loss_weight
+    if args.loss_type is not None:
+        cfg["loss_type"] = args.loss_type
+    if args.huber_c is not None:
+        cfg["huber_c"] = args.huber_c
+    if args.huber_schedule is not None:
+        cfg["huber_schedule"] = args.huber_schedule
     main(cfg)

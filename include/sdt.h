@@ -158,6 +158,35 @@ int sdt_masked_mse_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_n
                                 const float* snr_weight, const float* loss_weight, float* loss_accum, float* loss_per_sample,
                                 uint16_t* dpred_nhwc, int B, int C, int H, int W, int cpad, void* workspace, int64_t workspace_bytes,
                                 hipStream_t stream);
+/* ---- ROBUST LOSS: pseudo-Huber and smooth-L1 in place of the squared error (kohya --loss_type huber | smooth_l1 with --huber_c and
+ * --huber_schedule; the same three options of diffusers' training examples).  Everything around the element is MASKED LOSS above: the
+ * effective mask e, the sample factor k_b (with s_b and S_b), the counts, the order of the sums.  fl() is one fp32 rounding, fl64() one
+ * IEEE double rounding; nothing below is contracted.
+ *   element         diff = fl(target - pred) as in every loss call; c = huber_c[b] >= 0, the sample's threshold (the step reads it
+ *                   from a table over the training timesteps).  With r = sqrt(diff^2 + c^2):
+ *                     huber      rho = 2c(r - c) = 2c diff^2 / (r + c),   d rho / d pred = -2c diff / r
+ *                     smooth_l1  rho = 2(r - c)  = 2 diff^2 / (r + c),    d rho / d pred = -2 diff / r
+ *                   The second form of rho is the one evaluated: r - c cancels when |diff| << c.  As c -> inf huber tends to diff^2.
+ *   element, bits   formed in double from the two fp32 operands and rounded to fp32 once, so that nothing hangs on what a compiler
+ *                   makes of fp32 sqrtf and '/':  dd = diff*diff and c*c are exact in double;  q = fl64(dd + c*c);  r = fl64(sqrt(q));
+ *                   den = fl64(r + c);
+ *                     huber      g = fl(fl64((-2c * diff) / r))   (-2c * diff is exact),  rho = fl(fl64(fl64(2c * dd) / den))
+ *                     smooth_l1  g = fl(fl64((-2 * diff) / r)),                           rho = fl(fl64((2 * dd) / den))   (2 * dd is exact)
+ *                   r == 0 (diff and c both zero): g = rho = 0, never a NaN.  fl() of a double is round-to-nearest-even.
+ *   gradient        dpred[b,p,c] = bf16_rne(fl(fl(fl(k_b * e) * g) * inv_count)), inv_count = fl(1 / fl(B*C*h*w)); padding channels are
+ *                   written as zero.  (g carries the -2 that the squared error's chain multiplies in first.)
+ *   per sample      a_b = sum_{c,p} fl(e * rho) in MASKED LOSS's order (thread, block tree, workgroup partials by the last arriver);
+ *                   loss_per_sample[b] = fl(fl(k_b * a_b) * fl(1/(C*h*w)))
+ *   loss            loss_accum += fl(T * inv_count), T = the terms fl(k_b * a_b) added in sample order.  No float atomics.
+ * sdt_robust_loss_fwd_bwd: the operands of sdt_masked_mse_loss_fwd_bwd (NULL effective_mask / mask_sums / snr_weight / loss_weight mean
+ * what they mean there, so one launch serves plain, weighted and masked batches; sdt_loss_mask_prepare runs first when there is a mask),
+ * huber_c f32 (B), loss_type 1 (huber) or 2 (smooth_l1).  The same grid, partition, workspace (sdt_reduce_workspace_bytes()) and
+ * vector rule (16-byte pred / dpred vectors when cpad % 8 == 0 and both are 16-byte aligned).  Refused: null or misaligned pointers,
+ * another loss_type, B outside 1..8192, cpad < C, mask sums without the mask, a workspace that is too small. */
+int sdt_robust_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_nchw, const float* effective_mask, const float* mask_sums,
+                            const float* snr_weight, const float* loss_weight, const float* huber_c, int loss_type, float* loss_accum,
+                            float* loss_per_sample, uint16_t* dpred_nhwc, int B, int C, int H, int W, int cpad, void* workspace,
+                            int64_t workspace_bytes, hipStream_t stream);
 /* diffusers embeddings_flax.get_sinusoidal_embeddings -> bf16 (B, dim) */
 int sdt_timestep_embedding(const int32_t* timesteps, uint16_t* out, int B, int dim, int flip_sin_to_cos,
                            float freq_shift, hipStream_t stream);

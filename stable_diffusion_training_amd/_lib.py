@@ -62,6 +62,7 @@ SIGNATURES = {
     "sdt_mse_loss_fwd_bwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
     "sdt_loss_mask_prepare": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _L, _P],
     "sdt_masked_mse_loss_fwd_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
+    "sdt_robust_loss_fwd_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
     "sdt_timestep_embedding": [_P, _P, _I, _I, _I, _F, _P],
     "sdt_sqnorm_accumulate": [_P, _L, _P, _P, _L, _P],
     "sdt_sqnorm_accumulate_bf16": [_P, _L, _P, _P, _L, _P],

@@ -344,6 +344,36 @@ __global__ void __launch_bounds__(256) loss_mask_prepare_kernel(const float* __r
   if (threadIdx.x == 0) S[b] = tot;
 }
 
+// ------------------------------------------------------------------ Huber / smooth-L1 loss (include/sdt.h "ROBUST LOSS")
+enum { LOSS_L2 = 0, LOSS_HUBER = 1, LOSS_SMOOTH_L1 = 2 };
+
+// One element of the pseudo-Huber loss: g = d rho / d pred and rho from the fp32 diff = target - pred and the sample's threshold c.
+// Everything between the fp32 operands and the two fp32 results is double and IEEE (add, multiply, sqrt, divide; nothing contracted):
+//   dd = diff*diff and c*c are exact (24-bit factors), q = fl64(dd + c*c), r = fl64(sqrt(q)), den = fl64(r + c)
+//   huber:      g = fl32(fl64((-2c * diff) / r))  (-2c * diff is exact),  rho = fl32(fl64(fl64(2c * dd) / den))
+//   smooth_l1:  g = fl32(fl64((-2 * diff) / r)),                          rho = fl32(fl64((2 * dd) / den))    (2 * dd is exact)
+// rho is 2c(r - c) resp. 2(r - c) without the cancellation; r == 0 (diff and c both zero) gives g = rho = 0, never 0/0.
+template <int TYPE>
+__device__ __forceinline__ void robust_element(float diff, float c, float& g, float& rho) {
+#pragma clang fp contract(off)
+  const double D = (double)diff, Cd = (double)c;
+  const double dd = D * D;
+  const double r = sqrt(dd + Cd * Cd);
+  if (r == 0.0) {
+    g = 0.f;
+    rho = 0.f;
+    return;
+  }
+  const double den = r + Cd;
+  if (TYPE == LOSS_HUBER) {
+    g = (float)(((-2.0 * Cd) * D) / r);
+    rho = (float)(((2.0 * Cd) * dd) / den);
+  } else {
+    g = (float)((-2.0 * D) / r);
+    rho = (float)((2.0 * dd) / den);
+  }
+}
+
 // pred bf16 NHWC (B,h,w,cpad), target f32 NCHW (B,C,h,w), e f32 (B,h,w) or null (all ones), S f32 (B) or null (no normalisation),
 // w1 / w2 f32 (B) or null (the min-SNR factor and the loss weight).  Grid (nb, B), the partition of loss_mask_prepare_kernel.
 //   k_b = fl(fl(w1*w2) * s_b),  s_b = 1 | (S_b == 0 ? 0 : fl(fl(HW) / S_b))
@@ -353,13 +383,16 @@ __global__ void __launch_bounds__(256) loss_mask_prepare_kernel(const float* __r
 //   adds the B terms in sample order and adds fl(total * inv_count) to *loss.
 // VEC: a position's cpad channels of pred / dpred as 16-byte vectors (cpad % 8 == 0, both aligned); padding lanes of pred are unpacked
 // but never enter the arithmetic, and dpred's are written as zero.
-template <bool VEC>
+// TYPE LOSS_HUBER / LOSS_SMOOTH_L1 (hc f32 (B): the samples' thresholds; unused by LOSS_L2): the element above in place of the square,
+//   dpred = bf16(fl(fl(fl(k_b*e) * g) * inv_count)),  a_b = sum fl(e * rho); everything around the element is shared.
+template <bool VEC, int TYPE>
 __global__ void __launch_bounds__(256) masked_mse_kernel(const bf16_t* __restrict__ pred, const float* __restrict__ target,
                                                          const float* __restrict__ e, const float* __restrict__ S,
                                                          const float* __restrict__ w1, const float* __restrict__ w2,
-                                                         float* __restrict__ loss, float* __restrict__ loss_ps,
-                                                         bf16_t* __restrict__ dpred, int B, int C, int HW, int cpad, float inv_count,
-                                                         float inv_chw, int* counters, float* __restrict__ part) {
+                                                         const float* __restrict__ hc, float* __restrict__ loss,
+                                                         float* __restrict__ loss_ps, bf16_t* __restrict__ dpred, int B, int C, int HW,
+                                                         int cpad, float inv_count, float inv_chw, int* counters,
+                                                         float* __restrict__ part) {
 #pragma clang fp contract(off)
   __shared__ float scratch[16];
   __shared__ int s_last;
@@ -369,12 +402,13 @@ __global__ void __launch_bounds__(256) masked_mse_kernel(const bf16_t* __restric
     const float sb = S[b];
     k = k * (sb == 0.f ? 0.f : (float)HW / sb);
   }
+  const float hub = TYPE == LOSS_L2 ? 0.f : hc[b];
   const float* tb = target + (long)b * C * HW;
   float acc = 0.f;
   for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += nb * 256) {
     const long i = (long)b * HW + p;
     const float ev = e ? e[i] : 1.f;
-    const float g = -2.f * (k * ev);
+    const float g = TYPE == LOSS_L2 ? -2.f * (k * ev) : k * ev;
     if (VEC) {
       const uint4* prow = reinterpret_cast<const uint4*>(pred + i * cpad);
       for (int c0 = 0; c0 < cpad; c0 += 8) {
@@ -386,8 +420,15 @@ __global__ void __launch_bounds__(256) masked_mse_kernel(const bf16_t* __restric
           for (int j = 0; j < 8; ++j) {
             if (c0 + j < C) {
               const float diff = tb[(long)(c0 + j) * HW + p] - pv[j];
-              acc += ev * diff * diff;
-              d[j] = g * diff * inv_count;
+              if (TYPE == LOSS_L2) {
+                acc += ev * diff * diff;
+                d[j] = g * diff * inv_count;
+              } else {
+                float ge, rho;
+                robust_element<TYPE>(diff, hub, ge, rho);
+                acc += ev * rho;
+                d[j] = g * ge * inv_count;
+              }
             }
           }
         }
@@ -398,8 +439,15 @@ __global__ void __launch_bounds__(256) masked_mse_kernel(const bf16_t* __restric
         float d = 0.f;
         if (c < C) {
           const float diff = tb[(long)c * HW + p] - bf2f(pred[i * cpad + c]);
-          acc += ev * diff * diff;
-          d = g * diff * inv_count;
+          if (TYPE == LOSS_L2) {
+            acc += ev * diff * diff;
+            d = g * diff * inv_count;
+          } else {
+            float ge, rho;
+            robust_element<TYPE>(diff, hub, ge, rho);
+            acc += ev * rho;
+            d = g * ge * inv_count;
+          }
         }
         if (dpred) dpred[i * cpad + c] = f2bf(d);
       }
@@ -1043,11 +1091,42 @@ int sdt_masked_mse_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_n
   const int HW = H * W;
   const float inv_count = 1.0f / ((float)B * C * H * W), inv_chw = 1.0f / ((float)C * H * W);
   const bool vec = cpad % 8 == 0 && (((uintptr_t)pred_nhwc | (uintptr_t)dpred_nhwc) & 15) == 0;
-  auto kern = vec ? masked_mse_kernel<true> : masked_mse_kernel<false>;
+  auto kern = vec ? masked_mse_kernel<true, LOSS_L2> : masked_mse_kernel<false, LOSS_L2>;
   hipLaunchKernelGGL(kern, dim3(masked_blocks(B, HW), B), dim3(256), 0, stream, (const bf16_t*)pred_nhwc, target_nchw, effective_mask,
-                     mask_sums, snr_weight, loss_weight, loss_accum, loss_per_sample, (bf16_t*)dpred_nhwc, B, C, HW, cpad, inv_count, inv_chw,
-                     reinterpret_cast<int*>(workspace), reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
+                     mask_sums, snr_weight, loss_weight, (const float*)nullptr, loss_accum, loss_per_sample, (bf16_t*)dpred_nhwc, B, C, HW,
+                     cpad, inv_count, inv_chw, reinterpret_cast<int*>(workspace),
+                     reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
   SDT_LAUNCH_CHECK("sdt_masked_mse_loss_fwd_bwd");
+  return SDT_OK;
+}
+
+int sdt_robust_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_nchw, const float* effective_mask, const float* mask_sums,
+                            const float* snr_weight, const float* loss_weight, const float* huber_c, int loss_type, float* loss_accum,
+                            float* loss_per_sample, uint16_t* dpred_nhwc, int B, int C, int H, int W, int cpad, void* workspace,
+                            int64_t workspace_bytes, hipStream_t stream) {
+  SDT_CHECK_ARG(pred_nhwc && target_nchw && huber_c && loss_accum && loss_per_sample, "sdt_robust_loss_fwd_bwd: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)target_nchw | (uintptr_t)effective_mask | (uintptr_t)mask_sums | (uintptr_t)snr_weight | (uintptr_t)loss_weight |
+                  (uintptr_t)huber_c | (uintptr_t)loss_accum | (uintptr_t)loss_per_sample) & 3) == 0 &&
+                    (((uintptr_t)pred_nhwc | (uintptr_t)dpred_nhwc) & 1) == 0,
+                "sdt_robust_loss_fwd_bwd: misaligned pointer (4 bytes, bf16: 2 bytes)");
+  SDT_CHECK_ARG(loss_type == LOSS_HUBER || loss_type == LOSS_SMOOTH_L1, "sdt_robust_loss_fwd_bwd: loss_type %d (1 huber, 2 smooth_l1)",
+                loss_type);
+  SDT_CHECK_ARG(B > 0 && B <= MASKED_MAX_B && C > 0 && H > 0 && W > 0 && (long)H * W <= (1L << 30),
+                "sdt_robust_loss_fwd_bwd: bad shape B=%d C=%d H=%d W=%d (1 <= B <= %d)", B, C, H, W, MASKED_MAX_B);
+  SDT_CHECK_ARG(cpad >= C, "sdt_robust_loss_fwd_bwd: cpad=%d < C=%d", cpad, C);
+  SDT_CHECK_ARG(effective_mask || !mask_sums, "sdt_robust_loss_fwd_bwd: mask sums (normalisation) need the effective mask");
+  SDT_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= sdt_reduce_workspace_bytes(),
+                "sdt_robust_loss_fwd_bwd: workspace of sdt_reduce_workspace_bytes() needed");
+  const int HW = H * W;
+  const float inv_count = 1.0f / ((float)B * C * H * W), inv_chw = 1.0f / ((float)C * H * W);
+  const bool vec = cpad % 8 == 0 && (((uintptr_t)pred_nhwc | (uintptr_t)dpred_nhwc) & 15) == 0;
+  auto kern = loss_type == LOSS_HUBER ? (vec ? masked_mse_kernel<true, LOSS_HUBER> : masked_mse_kernel<false, LOSS_HUBER>)
+                                      : (vec ? masked_mse_kernel<true, LOSS_SMOOTH_L1> : masked_mse_kernel<false, LOSS_SMOOTH_L1>);
+  hipLaunchKernelGGL(kern, dim3(masked_blocks(B, HW), B), dim3(256), 0, stream, (const bf16_t*)pred_nhwc, target_nchw, effective_mask,
+                     mask_sums, snr_weight, loss_weight, huber_c, loss_accum, loss_per_sample, (bf16_t*)dpred_nhwc, B, C, HW, cpad,
+                     inv_count, inv_chw, reinterpret_cast<int*>(workspace),
+                     reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
+  SDT_LAUNCH_CHECK("sdt_robust_loss_fwd_bwd");
   return SDT_OK;
 }
 

@@ -9,6 +9,7 @@ maps pixel_values.shape -> a bound step callable; data parallelism is one proces
 all-reduce of the flat gradient buffer overlapped with backward (dp.GradReducer) instead of GSPMD; parameters,
 optimizer state and EMA live in flat HBM buffers (params.ParamStore) updated in place (the reference donates them).
 """
+import math
 from dataclasses import dataclass, field
 from typing import Any, Callable
 
@@ -226,6 +227,56 @@ def _min_snr_weights(sched_state, timesteps, gamma, prediction_type):
     return (m / (snr + 1) if prediction_type == "v_prediction" else m / snr).to(torch.float32).contiguous()
 
 
+LOSS_TYPES = {"l2": 0, "huber": 1, "smooth_l1": 2}  # the values are sdt_robust_loss_fwd_bwd's loss_type
+HUBER_SCHEDULES = ("constant", "exponential", "snr")
+
+
+def _check_loss_type(loss_type, huber_c, huber_schedule):
+    """ValueError for loss options train_step cannot run (kohya's --loss_type / --huber_c / --huber_schedule)."""
+    if loss_type not in LOSS_TYPES:
+        raise ValueError(f"loss_type={loss_type!r} must be one of {', '.join(LOSS_TYPES)}")
+    if huber_schedule not in HUBER_SCHEDULES:
+        raise ValueError(f"huber_schedule={huber_schedule!r} must be one of {', '.join(HUBER_SCHEDULES)}")
+    c = huber_c
+    if isinstance(c, bool) or not isinstance(c, (int, float)) or not math.isfinite(c) or not c > 0:
+        raise ValueError(f"huber_c={c!r} must be a finite number > 0")
+    if c > 1 and huber_schedule != "constant":
+        raise ValueError(f"huber_c={c!r} > 1: the {huber_schedule} schedule runs from 1 down to huber_c and needs huber_c <= 1")
+
+
+def huber_threshold_table(alphas_cumprod, huber_c, huber_schedule):
+    """The Huber threshold of every training timestep, float32 (T,), computed in float64 and rounded once (include/sdt.h "ROBUST LOSS";
+    kohya / diffusers huber_schedule).  alphas_cumprod: the scheduler's host table (T,).
+      constant     c[t] = huber_c
+      exponential  c[t] = exp(t * ln(huber_c) / T): 1 at t = 0, towards huber_c at high noise
+      snr          sigma = sqrt((1 - abar_t) / abar_t), c[t] = (1 - huber_c) / (1 + sigma)^2 + huber_c.  abar = 0 (zero terminal SNR) gives
+                   sigma = inf and c = huber_c by IEEE division, never 0 * inf."""
+    _check_loss_type("huber", huber_c, huber_schedule)
+    ac = np.asarray(alphas_cumprod, np.float64)
+    T, c = ac.shape[0], float(huber_c)
+    if huber_schedule == "constant":
+        tab = np.full(T, c, np.float64)
+    elif huber_schedule == "exponential":
+        tab = np.exp(np.arange(T, dtype=np.float64) * (math.log(c) / T))
+    else:
+        with np.errstate(divide="ignore"):
+            sigma = np.sqrt((1.0 - ac) / ac)
+            tab = (1.0 - c) / (1.0 + sigma) ** 2 + c
+    return tab.astype(np.float32)
+
+
+def _huber_thresholds(sched_state, timesteps, huber_c, huber_schedule):
+    """c_b of a (micro-)batch, f32 (B,): the table above, built once per scheduler state and option pair and kept on the device (a
+    captured step only gathers from it, as _min_snr_weights gathers from alphas_cumprod)."""
+    tables = sched_state.__dict__.setdefault("_huber_tables", {})
+    key = (huber_schedule, float(huber_c))
+    tab = tables.get(key)
+    if tab is None:
+        ac = sched_state.alphas_cumprod
+        tab = tables[key] = torch.from_numpy(huber_threshold_table(ac.cpu().numpy(), huber_c, huber_schedule)).to(ac.device)
+    return tab[timesteps.long()].contiguous()
+
+
 def assemble_context(hs, batch, strip_bos_eos_token):
     """training_utils.py:643-673: (B*k,77,D) -> (B,k,77,D) -> (B,L,D).  k=1 without stripping is a free view."""
     d = hs.shape[-1]
@@ -343,7 +394,8 @@ _FUSED_NORM = True  # False: always the pass over the gradient buffer (same bits
 def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, batch, train_rng,
                frozen_vae_state, frozen_noise_scheduler_state, strip_bos_eos_token=True, offset_noise_magnitude=0.0,
                min_snr_gamma_magnitude=0.0, perturbation_noise_magnitude=0.0, ema_rate=0.0, *, rand=None, reducer=None,
-               vae_scale=0.18215, aux=None, micro_batches=1, masked_loss_floor=0.0, normalize_masked_area=False):
+               vae_scale=0.18215, aux=None, micro_batches=1, masked_loss_floor=0.0, normalize_masked_area=False, loss_type="l2",
+               huber_c=0.1, huber_schedule="snr"):
     """One DDPM training step on this rank's shard of the batch (training_utils.py:504-762), in place.
 
     batch: {"pixel_values": f32 (B,3,H,W) NCHW device tensor, "input_ids": i32 (B*k,77), "attention_mask": unused}.
@@ -377,7 +429,15 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     concatenated); aux= taps record the effective mask as aux["loss_mask"].  With neither, the step is launch for launch the plain one.
     ValueError for a mask of another dtype, device, shape or layout, a loss_weight that is not (B,), a floor outside [0, 1] and
     normalize_masked_area without a mask.
+    Huber and smooth-L1 loss (include/sdt.h "ROBUST LOSS"): loss_type "huber" or "smooth_l1" replaces the squared error of an element by
+    the pseudo-Huber 2c(sqrt(diff^2 + c^2) - c) or 2(sqrt(diff^2 + c^2) - c); the threshold c of a sample comes from its timestep by
+    huber_schedule ("constant": huber_c; "exponential": from 1 at t = 0 towards huber_c; "snr": from 1 at no noise to huber_c at pure
+    noise; huber_threshold_table).  The loss launch is then sdt_robust_loss_fwd_bwd for every kind of batch (after sdt_loss_mask_prepare
+    when there is a mask): min-SNR, masks, weights and normalisation act as above, metrics always holds "loss_per_sample", and aux= taps
+    record the thresholds as aux["huber_c"] and a copy of d loss / d pred as aux["dpred"].  "l2" (the default) is launch for launch
+    the step described above.  ValueError for an unknown type or schedule, a huber_c that is not finite and > 0, and a huber_c > 1 with the snr or exponential schedule.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
+    _check_loss_type(loss_type, huber_c, huber_schedule)
     text_time = unet_state.config.get("addition_embed_type") == "text_time"
     sdxl = text_time and nets.sdxl_conditioning(text_encoder_state.config)
     if sdxl and "text_embeds" in batch:
@@ -399,6 +459,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     dev = us.device
     cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev, masked_loss_floor, normalize_masked_area)
     masked = any(k in batch for k in LOSS_KEYS)
+    robust = LOSS_TYPES[loss_type]  # 0: the squared error
     image_key = "latent_moments" if cached else "pixel_values"
     stream = torch.cuda.current_stream().cuda_stream
     rand = rand or {}
@@ -542,8 +603,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         dpred = torch.empty_like(pred)
         C_out = unet_state.config["out_channels"]
         rws = ops.reduce_workspace(_lib.load().sdt_reduce_workspace_bytes(), dev)
-        lps = emask = None
-        if masked:
+        lps = emask = hub = None
+        if masked or robust:
             # the effective latent mask and its per-sample sums, then the loss per sample first; a batch with loss_weight only passes no mask
             msum = None
             mask = mb.get("loss_mask")
@@ -558,16 +619,23 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                           float(masked_loss_floor), rws.data_ptr(), rws.numel(), stream)
             lw = mb.get("loss_weight")
             lps = torch.empty(B, dtype=torch.float32, device=dev)
-            _lib.call("sdt_masked_mse_loss_fwd_bwd", pred.data_ptr(), target.data_ptr(), None if emask is None else emask.data_ptr(),
-                      msum.data_ptr() if normalize_masked_area else None, None if wts is None else wts.data_ptr(),
-                      None if lw is None else lw.data_ptr(), loss.data_ptr(), lps.data_ptr(), dpred.data_ptr(), B, C_out, h, w,
-                      pred.shape[3], rws.data_ptr(), rws.numel(), stream)
+            operands = (pred.data_ptr(), target.data_ptr(), None if emask is None else emask.data_ptr(),
+                        msum.data_ptr() if normalize_masked_area else None, None if wts is None else wts.data_ptr(),
+                        None if lw is None else lw.data_ptr())
+            tail = (loss.data_ptr(), lps.data_ptr(), dpred.data_ptr(), B, C_out, h, w, pred.shape[3], rws.data_ptr(), rws.numel(), stream)
+            if robust:  # the sample's threshold from its timestep, then the pseudo-Huber element in place of the square
+                hub = _huber_thresholds(sched_state, timesteps, huber_c, huber_schedule)
+                _lib.call("sdt_robust_loss_fwd_bwd", *operands, hub.data_ptr(), robust, *tail)
+            else:
+                _lib.call("sdt_masked_mse_loss_fwd_bwd", *operands, *tail)
         else:
             _lib.call("sdt_mse_loss_fwd_bwd", pred.data_ptr(), target.data_ptr(), None if wts is None else wts.data_ptr(),
                       loss.data_ptr(), dpred.data_ptr(), B, C_out, h, w, pred.shape[3], rws.data_ptr(), rws.numel(), stream)
         if aux is not None:
             if emask is not None:
                 aux["loss_mask"] = emask
+            if hub is not None:
+                aux.update(huber_c=hub, dpred=dpred.clone())
             aux.update(latents=latents, noisy=noisy_nchw, ctx=ctx.detach(), pred=pred.detach(), target=target, moments=moments)
             if pooled is not None:
                 aux["text_embeds"] = pooled.detach()
@@ -609,7 +677,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                 for st in opt_stores:
                     st.accumulate(mode, 1.0 / K if mode == "finish" else 1.0, norm=mode == "finish")
         loss = torch.cat(losses).mean(0, keepdim=True)
-        lps = torch.cat(per_sample) if masked else None
+        lps = torch.cat(per_sample) if masked or robust else None
         sq_u = sq_t = None
         grad_source = "acc"
         if exchange:
@@ -633,7 +701,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             reducer.after_optimizer()  # sharded optimizer: all-gather the bf16 weight mirrors the owners have just written
     ops.gn_arena_end(dev)
     metrics = {"loss": loss[0]}
-    if masked:
+    if masked or robust:
         metrics["loss_per_sample"] = lps  # local to this rank under data parallelism
     return (unet_state, text_encoder_state, unet_ema_params if ur else None, text_encoder_ema_params if tr else None,
             metrics, train_rng)
@@ -796,7 +864,8 @@ def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_pa
     batch the loader delivers, (K * per_device_batch, 3, H, W), and one graph (graph A: through the last micro-batch's add pass, with
     a reducer) holds all K forward / backward passes.
     step_overrides: keyword options of train_step that TrainingConfig has no field for, e.g. vae_scale, or masked_loss_floor /
-    normalize_masked_area for batches with a loss_mask.  A captured step replays the launches of the batch it was captured with: it
+    normalize_masked_area for batches with a loss_mask, or loss_type / huber_c / huber_schedule.  A captured step replays the launches
+    of the batch it was captured with: it
     raises ValueError for a later batch that adds or drops loss_mask / loss_weight."""
     import os
     B = per_device_batch or training_config.batch_size
