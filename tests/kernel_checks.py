@@ -5,7 +5,8 @@ every product and every partial sum is an integer below 2^24, so fp32 accumulati
 result is unique: the fp32 accumulator equals the float64 reference and the bf16 output is its RNE rounding, bit for bit.  This
 module holds the operand generators, the expectations (float64 reference followed by the kernels' rounding points), the bitwise
 comparison with a report that names the tile edge, guarded allocations, per-slice error norms, and the case tables that the GPU
-file and the CPU proof share.
+file and the CPU proof share.  Attention gets two exact constructions: selector inputs (P one-hot: a gather, dQ = dK = 0) and
+tied pairs (P = 1/2, 1/2: exact nonzero dQ and dK), at every head dim the ABI accepts.
 
 The second half serves tests/test_gpu_reduce_optim_exact.py: exact scalar sums with a report that names the missing partial, tail
 element or overwritten destination, mirrors of the reduction launchers' partitions, the optimizer references (oracle/lion8.py itself),
@@ -368,11 +369,171 @@ def attention_msum(D):
     """Whether the forward kernel takes the softmax row sum from a ones column of the P.V MFMAs (the sum of the ROUNDED
     probabilities) instead of an fp32 sum of the unrounded ones: D <= NB * 32 - 8 for the head dim's instantiation
     (attention.hip:174-176, 702, 745-750)."""
-    nb = 2 if D <= 64 else 3 if D <= 96 else 4 if D <= 128 else 5
-    return D <= nb * 32 - 8
+    return attention_instance(D)[3]
 
 
-def attention_ref_and_emulation(q, k, v, do, H, scale, causal=False, key_weight=None):
+def attention_instance(D):
+    """(DPP, NS, NB, msum): the template instantiation sdt_attention_fwd / _bwd dispatch head dim D to (attention.hip:782-787,
+    822-827) and the forward's row-sum variant (attention_msum; the backward kernels have one variant)."""
+    assert D % 8 == 0 and 8 <= D <= 160
+    dpp, ns, nb = ((64, 3, 2) if D <= 48 else (64, 4, 2) if D <= 64 else (128, 5, 3) if D <= 80 else (128, 6, 3) if D <= 96
+                   else (128, 8, 4) if D <= 128 else (256, 10, 5))
+    return dpp, ns, nb, D <= nb * 32 - 8
+
+
+def attention_qsplit(B, H, Nq, Nk, causal):
+    """(planned, chunk, launched): a mirror of attn_qsplits (attention.hip:695-703) and of launch_bwd (:758-761).  `planned` query
+    chunks size the workspace (1: the dK/dV pass does not split); the chunk is rounded up to whole 64-query tiles, so `launched`
+    chunks of `chunk` queries cover Nq and launched <= planned.  The CPU proof holds `planned` to sdt_attention_bwd_workspace_bytes."""
+    base = -(-Nk // 128) * H * B
+    planned = 1
+    if not causal and base < 128 and Nq >= 1024:
+        planned = max(1, min(-(-256 // base), Nq // 256))
+    chunk = -(-(-(-Nq // planned)) // 64) * 64
+    return planned, chunk, -(-Nq // chunk)
+
+
+def attention_delta_bytes(B, H, Nq):
+    """The `delta` part of the backward workspace: B*H*Nq floats rounded up to four (attention.hip:796-797)."""
+    return 4 * ((B * H * Nq + 3) // 4 * 4)
+
+
+# ------------------------------------------------------------------------------------------------ tied-pair attention
+def pair_case(B, H, Nq, Nk, D, seed, c=32.0, extras=True):
+    """Inputs whose attention is exactly a mean of two V rows, with exact NONZERO dQ and dK.  The Nk keys of (b, h) form
+    ceil(Nk / 2) pairs of twins (the last key of an odd Nk stays alone) laid on a seeded permutation of the key slots, so twins
+    usually sit in different 64-key tiles.  Both twins carry the selector code of their pair (c * (+-1 per bit of a seeded
+    permutation)) on the first nb = ceil(log2(pairs)) features; query i carries the code of its target pair.  Features nb, nb + 2,
+    ... are key extras (each key its own integers in -3..3, every query zero), features nb + 1, nb + 3, ... query extras (each query
+    integers in -3..3, every key zero): they never enter a logit, so the twins tie exactly and lead every other key by
+    >= 2 c^2 / sqrt(D); P is exactly 1/2, 1/2 (1 for the lone key).  V: the pair's base row holds integers in -6..6 and the odd twin
+    differs from it by +-2 in two seeded features; dO integers in -3..3.  extras=False zeroes the extras (the degenerate
+    construction the CPU proof must refuse).
+    Returns dict(q, k, v, dout: bf16 (B, N, H*D); pair: int64 (B, H, Nk), the pair of every key slot; target: int64 (B, H, Nq), the
+    pair every query selects; nbits, c)."""
+    npair = -(-Nk // 2)
+    nb = max(1, math.ceil(math.log2(max(npair, 2))))
+    assert nb + 2 <= D, f"pair_case: {npair} pairs need {nb} code features and two extras, D = {D}"
+    g = torch.Generator().manual_seed(seed)
+    q, k, v = torch.zeros(B, Nq, H, D), torch.zeros(B, Nk, H, D), torch.zeros(B, Nk, H, D)
+    pair = torch.empty(B, H, Nk, dtype=torch.int64)
+    target = torch.empty(B, H, Nq, dtype=torch.int64)
+    sh = torch.arange(nb)
+    kx, qx = torch.arange(nb, D, 2), torch.arange(nb + 1, D, 2)
+    for b in range(B):
+        for h in range(H):
+            s = torch.randperm(npair, generator=g)
+            slot = torch.randperm(Nk, generator=g)
+            pr = torch.empty(Nk, dtype=torch.int64)
+            pr[slot] = torch.arange(Nk) // 2
+            odd = torch.zeros(Nk, dtype=torch.bool)
+            odd[slot] = (torch.arange(Nk) % 2) == 1
+            t = torch.randperm(npair, generator=g)[torch.arange(Nq) % npair]
+            pair[b, h], target[b, h] = pr, t
+            k[b, :, h, :nb] = (((s[pr][:, None] >> sh) & 1) * 2 - 1).float() * c
+            q[b, :, h, :nb] = (((s[t][:, None] >> sh) & 1) * 2 - 1).float() * c
+            kext = torch.randint(-3, 4, (Nk, kx.numel()), generator=g).float()
+            qext = torch.randint(-3, 4, (Nq, qx.numel()), generator=g).float()
+            if extras:
+                k[b, :, h][:, kx] = kext
+                q[b, :, h][:, qx] = qext
+            base = torch.randint(-6, 7, (npair, D), generator=g).float()
+            vh = base[pr]
+            f0 = torch.randint(0, D, (Nk,), generator=g)
+            f1 = (f0 + 1 + torch.randint(0, D - 1, (Nk,), generator=g)) % D   # a second, different feature
+            sg = torch.randint(0, 2, (Nk, 2), generator=g).float() * 4 - 2
+            rows = torch.arange(Nk)[odd]
+            vh[rows, f0[odd]] += sg[odd, 0]
+            vh[rows, f1[odd]] += sg[odd, 1]
+            v[b, :, h] = vh
+    do = torch.randint(-3, 4, (B, Nq, H * D), generator=g).float()
+    return dict(q=q.reshape(B, Nq, H * D).to(BF), k=k.reshape(B, Nk, H * D).to(BF), v=v.reshape(B, Nk, H * D).to(BF), dout=do.to(BF),
+                pair=pair, target=target, nbits=nb, c=c)
+
+
+def pair_expect(case, B, H, Nq, Nk, D, scale, kv_chunk=None, perturb=None, drop_rows=None, scale_twice=False):
+    """The bits sdt_attention_fwd / _bwd must produce on a pair case, in float64 from the IDEAL P (1 / number of tied keys on the
+    target pair's keys, 0 elsewhere - not from a float64 softmax, whose losers do not underflow), rounded where the kernels round:
+      O = RNE_bf16(P.V); dV = RNE_bf16(P^T.dO); dS = P o (dO.V^T - rowsum(dO o O)), exact in bf16;
+      dQ = RNE_bf16(fl32(scale_f32 * (dS.K))) (attention.hip:492-493);
+      dK = RNE_bf16(fl32(scale_f32 * (dS^T.Q))) where the dK/dV pass is one kernel (:657-658).  Where it splits the query range
+        (kv_chunk: the chunk of attention_qsplit) every chunk stores fl32(scale_f32 * (its part of dS^T.Q)) to its fp32 slab
+        (:639-640) and attn_kv_finish_kernel adds the slabs in chunk order in fp32 (:681-688) before the one bf16 rounding:
+        dK = RNE_bf16(fp32 sum over chunks of fl32(scale_f32 * part)), which is not always fl32(scale_f32 * total) rounded when
+        scale is not a power of two.  dV's slabs hold exact fp32 sums, so dV does not depend on the split.
+      lse2 = (winning logit) * log2(e) + log2(number of tied keys), float64.
+    perturb=None asserts that every one of these roundings is exact where it must be (P.V, P^T.dO, dS in bf16, both accumulators
+    in fp32 below 2^24).  perturb=e (the margin proof) scales every probability, the forward's row sum included, by 1 + e and
+    rounds as the kernels do: bf16(P) for P^T.dO, bf16(P (dP - delta)) with delta from the stored O.
+    drop_rows=(lo, hi) leaves the queries lo..hi-1 out of dS^T.Q and scale_twice applies scale twice: the planted faults of the
+    CPU proof.  Returns dict(o, dq, dk, dv: bf16 (B, N, H*D); lse2: float64 (B, H, Nq); ds: float64 (B, H, Nq, Nk); acc_q, acc_k:
+    float64 accumulators (B, N, H*D); p: float64 (B, H, Nq, Nk))."""
+    C = H * D
+    q4, k4, v4 = (case[n].view(B, -1, H, D).transpose(1, 2).double() for n in ("q", "k", "v"))
+    do4 = case["dout"].view(B, Nq, H, D).transpose(1, 2).double()
+    hit = (case["pair"][:, :, None, :] == case["target"][:, :, :, None]).double()  # (B, H, Nq, Nk)
+    ties = hit.sum(-1, keepdim=True)
+    assert (ties >= 1).all() and (ties <= 2).all()
+    p = hit / ties
+    r16 = lambda t: t.to(torch.float32).to(BF).double()
+    f32 = lambda t: t.to(torch.float32).double()
+    exact = perturb is None
+    pk = p if exact else p * (1.0 + perturb)
+
+    def rounded(x, what, to):
+        y = to(x + 0.0)  # (+ 0.0: a sum of -0 terms is +0 in an accumulator that starts at +0)
+        assert not exact or torch.equal(y, x), f"pair_expect: {what} is not exact"
+        return y
+
+    o = rounded(pk @ v4, "P.V in bf16", r16)            # (the perturbed row sum scales every P alike: pk is already P (1 + e))
+    dv = rounded(r16(pk).transpose(-1, -2) @ do4, "P^T.dO in bf16", r16)
+    delta = (do4 * o).sum(-1, keepdim=True)
+    ds = rounded(pk * (do4 @ v4.transpose(-1, -2) - delta), "dS in bf16", r16)
+    scale_f = float(torch.tensor(scale, dtype=torch.float32))
+    if scale_twice:
+        scale_f = scale_f * scale_f
+    acc_q = ds @ k4 + 0.0
+    dsk = ds.clone()
+    if drop_rows is not None:
+        dsk[:, :, drop_rows[0]: drop_rows[1]] = 0
+    chunks = [(0, Nq)] if kv_chunk is None else [(lo, min(lo + kv_chunk, Nq)) for lo in range(0, Nq, kv_chunk)]
+    parts = [dsk[:, :, lo:hi].transpose(-1, -2) @ q4[:, :, lo:hi] + 0.0 for lo, hi in chunks]
+    acc_k = sum(parts)
+    for what, a in [("dS.K", acc_q)] + [("a part of dS^T.Q", a) for a in parts] + [("dS^T.Q", acc_k)]:
+        assert torch.equal(f32(a), a) and float(a.abs().max()) < LIMIT, f"pair_expect: {what} is not exact in fp32 below 2^24"
+    dq = r16(f32(acc_q * scale_f))
+    dk32 = torch.zeros_like(acc_k, dtype=torch.float32)
+    for a in parts:  # the finishing pass: fp32 additions in chunk order (one part: 0 + x = x)
+        dk32 = dk32 + (a * scale_f).to(torch.float32)
+    dk = dk32.to(BF).double()
+    win = (q4[:, :, :, : case["nbits"]] ** 2).sum(-1) * scale_f   # the target's logit: nbits * c^2 * scale
+    lse2 = win * 1.4426950408889634 + torch.log2(ties[..., 0])
+    flat = lambda t, n: t.transpose(1, 2).reshape(B, n, C)
+    return dict(o=flat(o, Nq).to(BF), dq=flat(dq, Nq).to(BF), dk=flat(dk, Nk).to(BF), dv=flat(dv, Nk).to(BF), lse2=lse2, ds=ds,
+                acc_q=flat(acc_q, Nq), acc_k=flat(acc_k, Nk), p=p)
+
+
+def pair_min_gap(case, B, H, Nq, Nk, D, scale):
+    """(largest logit difference between two keys of the target pair, smallest lead of the pair over every other key, largest
+    logit), float64: the tie must be exactly 0."""
+    q4, k4 = (case[n].view(B, -1, H, D).transpose(1, 2).double() for n in ("q", "k"))
+    s = (q4 @ k4.transpose(-1, -2)) * scale
+    hit = case["pair"][:, :, None, :] == case["target"][:, :, :, None]
+    win = s.masked_fill(~hit, float("-inf")).max(-1).values
+    low = s.masked_fill(~hit, float("inf")).min(-1).values
+    rest = s.masked_fill(hit, float("-inf")).max(-1).values
+    return float((win - low).max()), float((win - rest).min()), float(win.max())
+
+
+def pair_reports(got, want, D):
+    """The pair checker: mismatch_report of out, dq, dk and dv (dicts of bf16 (B, N, H*D) tensors) against pair_expect, with the
+    128-row x head tile named; a list of messages, empty when every bit agrees."""
+    names = dict(o="out [batch][query][head * D + feature]", dq="dq [batch][query][head * D + feature]",
+                 dk="dk [batch][key][head * D + feature]", dv="dv [batch][key][head * D + feature]")
+    return [m for m in (mismatch_report(got[n], want[n], what, tile=(128, D)) for n, what in names.items()) if m is not None]
+
+
+def attention_ref_and_emulation(q, k, v, do, H, scale, causal=False, key_weight=None, kv_chunk=None):
     """float64 attention (forward and the three gradients) and a torch emulation of the kernels' rounding points, head by head on
     the tensors' device.  q, do (B, Nq, H*D), k, v (B, Nk, H*D) bf16.  The emulation computes in float64 and rounds where the
     kernels round:
@@ -383,7 +544,10 @@ def attention_ref_and_emulation(q, k, v, do, H, scale, causal=False, key_weight=
         rounded ones through a ones column (:310, attention_msum); O = bf16(acc / l) (:323); lse2 = fp32(m * scale2 + log2 l) (:314).
       backward (:371-390, :414-437, :455; :547-582, :622-627): delta = sum_d dO * O with the STORED bf16 O; P = exp2(s * scale2 -
         lse2) from the stored fp32 lse2; dS = P (dP - delta) rounded to bf16 before dS.K and dS^T.Q; P rounded to bf16 before
-        P^T.dO; dQ = bf16(scale * acc), dK likewise, dV = bf16(acc).
+        P^T.dO; dQ = bf16(fl32(scale * acc)) (:492-493), dV = bf16(acc); dK = bf16(fl32(scale * acc)) (:657-658), except where the
+        dK/dV pass splits the query range (kv_chunk: the chunk of attention_qsplit; None: one kernel): every chunk stores
+        fl32(scale * its acc) to an fp32 slab (:639-640) and attn_kv_finish_kernel adds the slabs in chunk order in fp32 before the
+        bf16 rounding (:681-690) - scale is applied per slab, not to the sum.
     Left out: fp32 accumulation order, the hardware exp2.
     Returns (ref, emu, mag): dicts of float64 tensors o, dq, dk, dv in the input layout; mag holds, per element, the sum of the
     magnitudes of the terms before any cancellation (o: P |V|; dv: P^T |dO|; dq: scale * (P (|dP| + |delta|)) |K|; dk likewise
@@ -459,7 +623,14 @@ def attention_ref_and_emulation(q, k, v, do, H, scale, causal=False, key_weight=
             dsb = r16(pbw * (dp - (doh * ob).sum(-1, keepdim=True)))
             pb = r16(pbw)
             emu["o"][b, :, sl], emu["dv"][b, :, sl] = ob, r16(pb.t() @ doh)
-            emu["dq"][b, :, sl], emu["dk"][b, :, sl] = r16((dsb @ kh) * scale_f), r16((dsb.t() @ qh) * scale_f)
+            emu["dq"][b, :, sl] = r16((dsb @ kh) * scale_f)
+            if kv_chunk is None:
+                emu["dk"][b, :, sl] = r16((dsb.t() @ qh) * scale_f)
+            else:
+                slab = torch.zeros(Nk, D, dtype=torch.float32, device=dev)
+                for lo in range(0, Nq, kv_chunk):
+                    slab = slab + ((dsb[lo: lo + kv_chunk].t() @ qh[lo: lo + kv_chunk]) * scale_f).to(torch.float32)
+                emu["dk"][b, :, sl] = slab.to(BF).double()
             del sr, st, dp, pbw, dsb, pb
     return ref, emu, mag
 
@@ -662,6 +833,62 @@ ATTN_SELECTOR_CASES = [
     (1, 8, 144, 231, 80, False, True, True),
 ]
 
+# ... at every head dim the ABI accepts: Nq = 136 and Nk = 200 are ragged against the 64 and 128 tiles, ceil(log2 200) = 8 code
+# features fit D = 8, and H = 3 puts heads 1 and 2 at column offsets that are no multiple of 64.  packed / key_weights rotate with a
+# period of four, and the head dims that are alone in their (instantiation, row-sum variant) run a second time with both flags
+# inverted: every one of the ten (attention_instance) tuples meets both values of both flags.  Then causal cases, one per tuple but
+# <64,4,2> without the ones column (ATTN_SELECTOR_CASES has it: 77 x 77 at D = 64).
+_HD_FLAGS = [(False, False), (True, True), (False, True), (True, False)]
+ATTN_HEADDIM_CASES = (
+    [(1, 3, 136, 200, D, False) + _HD_FLAGS[i % 4] for i, D in enumerate(range(8, 168, 8))]
+    + [(1, 3, 136, 200, D, False) + tuple(not f for f in _HD_FLAGS[(D // 8 - 1) % 4]) for D in (56, 64, 88, 96, 128, 160)]
+    + [(1, 3, 200, 200, D, True, False, False) for D in (8, 56, 72, 88, 96, 120, 128, 152, 160)])
+
+# ... at the size edges: one query, one key, Nk and Nq at and around the 64 / 128 tile edges, and the query-split planner at its
+# threshold (Nq = 1023 must not split, 1024 must: ATTN_SPLIT_CLAIMS)
+ATTN_EDGE_CASES = (
+    [(1, 1, 1, 1, 8, False, False, False), (1, 2, 1, 77, 40, False, False, False), (1, 2, 77, 1, 64, False, False, False),
+     (2, 1, 1, 1, 160, False, False, False)]
+    + [(1, 2, 136, Nk, D, False, False, False) for D in (64, 88) for Nk in (63, 64, 65, 127, 128, 129)]
+    + [(1, 2, Nq, 200, 96, False, False, False) for Nq in (127, 128, 129)]
+    + [(1, 1, 1023, 77, 40, False, False, False), (1, 1, 1024, 77, 40, False, False, False)])
+
+# attention, tied-pair inputs (pair_case): (B, H, Nq, Nk, D, packed)
+_PAIR_UNSPLIT = (
+    [(1, 2, 136, 200, D, False) for D in (16, 40, 56, 64, 72, 80, 88, 96, 120, 128, 152, 160)]
+    + [(1, 2, 136, 72, 8, False),       # D = 8: six code features and one extra each leave room for 64 pairs at most
+       (2, 3, 130, 77, 96, True)])      # batch strides, an odd Nk (one lone key), packed k|v
+ATTN_PAIR_SPLIT_CASES = [               # the dK/dV pass splits the query range: fp32 slabs and attn_kv_finish_kernel
+    (1, 1, 1600, 77, 40, False),        # plans 6 query chunks, launches 5 of 320
+    (1, 2, 1100, 100, 64, False),
+    (1, 2, 1024, 77, 96, False),
+    (2, 2, 1024, 90, 152, True),
+    (1, 2, 1024, 77, 120, False),       # <128,8,4>, which no other split case reaches
+    (1, 3, 1024, 77, 72, False)]        # <128,5,3>: with these two, the split pass of every instantiation
+ATTN_PAIR_CASES = _PAIR_UNSPLIT + ATTN_PAIR_SPLIT_CASES
+
+# (B, H, Nq, Nk, causal) -> whether sdt_attention_bwd_workspace_bytes must ask for slabs beyond the delta part
+ATTN_SPLIT_CLAIMS = dict(
+    [((B, H, Nq, Nk, False), True) for B, H, Nq, Nk, D, packed in ATTN_PAIR_SPLIT_CASES]
+    + [((B, H, Nq, Nk, False), False) for B, H, Nq, Nk, D, packed in _PAIR_UNSPLIT]
+    + [((1, 1, 1023, 77, False), False), ((1, 1, 1024, 77, False), True), ((2, 8, 2048, 77, False), True),
+       ((1, 4, 1100, 100, False), True), ((4, 8, 1024, 77, False), True), ((1, 8, 1024, 1024, False), True),
+       ((2, 20, 1024, 1024, False), False)])  # (64 key blocks x heads x images leave the chip half idle: split; 320 do not)
+
+# attention, Gaussian inputs judged per row (test_attention_gaussian_inputs_per_row): (B, H, Nq, Nk, D, causal)
+ATTN_ROW_CASES = [
+    # the shapes of test_attention_fwd_bwd
+    (2, 8, 256, 256, 40, False), (1, 8, 1024, 1024, 40, False), (2, 8, 64, 77, 160, False), (2, 8, 256, 77, 80, False),
+    (2, 5, 144, 144, 64, False), (3, 12, 77, 77, 64, True), (1, 3, 77, 77, 16, True), (1, 2, 200, 333, 128, False),
+    (1, 8, 4096, 4096, 40, False), (1, 5, 9216, 9216, 64, False), (1, 10, 2304, 2304, 64, False), (2, 20, 1024, 1024, 64, False),
+    (2, 8, 2048, 77, 40, False), (1, 4, 1100, 100, 64, False), (4, 8, 1024, 77, 80, False)]
+# ... every other head dim at the ragged shape of the D = 128 row, and causal rows for three instantiations more
+ATTN_ROW_HEADDIM_CASES = (
+    [(1, 2, 200, 333, D, False) for D in range(8, 168, 8) if D not in {c[4] for c in ATTN_ROW_CASES}]
+    + [(1, 2, 200, 200, D, True) for D in (56, 96, 152)])
+# ... with the key weights of the clamped chunks (nets.key_chunk_weights: 64 queries x 77 keys)
+ATTN_ROW_KEYWEIGHT_CASES = [(2, 4, 64, 77, 88), (2, 4, 64, 77, 136)]
+
 
 def halo_tile(H, W, Cin, M, k, stride, pad):
     """(images, rows, columns) of the tile conv_halo_plan (gemm.hip:1960-1982) gives a 3x3 / stride 1 / pad 1 convolution, or None
@@ -704,7 +931,7 @@ def exact_reductions():
     for B, H, W, Cin, Cout, k, stride, pad, _ in WGRAD_CONV_CASES:
         OH, OW = conv_out_hw(H, W, k, stride, pad)
         out.append((f"conv wgrad {(B, H, W, Cin, Cout)}", WGRAD_RANGE, WGRAD_RANGE, B * OH * OW))
-    for B, H, Nq, Nk, D, *_ in ATTN_SELECTOR_CASES:
+    for B, H, Nq, Nk, D, *_ in ATTN_SELECTOR_CASES + ATTN_HEADDIM_CASES + ATTN_EDGE_CASES:
         out.append((f"attention dV {(B, H, Nq, Nk, D)}", 3, 1, Nq))
     return out
 

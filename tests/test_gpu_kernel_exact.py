@@ -2,7 +2,7 @@
 tests/test_kernel_checks_cpu.py).
 
 The contraction kernels (sdt_gemm_nt_bf16 plain and gathered, the weight gradients, the GroupNorm statistics of the epilogues) and
-attention on selector inputs run on small-integer operands whose exact answer is known: every output element, and every fp32
+attention on selector and tied-pair inputs run on small-integer operands whose exact answer is known: every output element, and every fp32
 statistic, must hold the bits of the float64 reference rounded at the kernels' documented rounding points.  Outputs sit in guarded
 arenas (tests/kernel_checks.py Guarded: a sentinel in front, behind and in 16 pad columns of every row, checked afterwards),
 inputs in arenas whose guards are NaN, so that an out-of-range operand that reaches the arithmetic surfaces in the result.  Calls go
@@ -436,7 +436,7 @@ def _key_weights(dev, Nq, Nk):
     return w
 
 
-@pytest.mark.parametrize("B,H,Nq,Nk,D,causal,packed,kw", kc.ATTN_SELECTOR_CASES)
+@pytest.mark.parametrize("B,H,Nq,Nk,D,causal,packed,kw", kc.ATTN_SELECTOR_CASES + kc.ATTN_HEADDIM_CASES + kc.ATTN_EDGE_CASES)
 def test_attention_selector_inputs_every_bit(dev, B, H, Nq, Nk, D, causal, packed, kw):
     """Selector inputs (tests/kernel_checks.py selector_case): the winner leads by >= 162 logits, P is exactly one-hot, so out must be
     the selected V row, dV the RNE of the integer sum of the dO rows that selected a key, dQ and dK zero (by value: either sign),
@@ -470,6 +470,9 @@ def test_attention_selector_inputs_every_bit(dev, B, H, Nq, Nk, D, causal, packe
     need = lib.sdt_attention_bwd_workspace_bytes(ctypes.addressof(desc))
     if (Nq >= 1024 and Nk <= 100):
         assert need > 4 * ((B * H * Nq + 3) // 4 * 4), "the dK/dV pass no longer splits the query range for this shape"
+    claim = kc.ATTN_SPLIT_CLAIMS.get((B, H, Nq, Nk, bool(causal)))
+    if claim is not None:  # (Nq = 1023 must get the delta part only, 1024 the slabs as well)
+        assert (need > kc.attention_delta_bytes(B, H, Nq)) == claim, f"workspace {need} bytes: the dK/dV pass must {'split' if claim else 'not split'} here"
     ws = torch.full((need // 4,), float("nan"), dtype=torch.float32, device=dev)
     _lib.call("sdt_attention_bwd", Q.ptr, kptr, vptr, O.ptr, DO.ptr, LSE.ptr, DQ.ptr, dkptr, dvptr, ws.data_ptr(), need, ctypes.addressof(desc), _stream())
     torch.cuda.synchronize()
@@ -489,6 +492,74 @@ def test_attention_selector_inputs_every_bit(dev, B, H, Nq, Nk, D, causal, packe
             g.check(what)
 
 
+def _attention_pairs(dev, B, H, Nq, Nk, D, packed, delta_only):
+    """One tied-pair case (tests/kernel_checks.py pair_case / pair_expect) through sdt_attention_fwd and sdt_attention_bwd on guarded
+    arenas, as the selector test runs its cases: out, dq, dk and dv must hold the expected bits, lse2 the winning logit x log2(e)
+    + log2(ties) to 1e-6 relative.  delta_only: the workspace is the delta part alone, so a shape that would split the query range
+    of the dK/dV pass must be served by the unsplit kernel (attention.hip:819) - with the unsplit expectation."""
+    from stable_diffusion_training_amd import _lib
+    lib = _lib.load()
+    C, scale = H * D, D ** -0.5
+    case = kc.pair_case(B, H, Nq, Nk, D, seed=Nq + Nk + D)
+    planned, chunk, _ = kc.attention_qsplit(B, H, Nq, Nk, False)
+    want = kc.pair_expect(case, B, H, Nq, Nk, D, scale, kv_chunk=chunk if planned > 1 and not delta_only else None)
+    Q, DO, KG, VG, kptr, vptr, ldkv = _attn_arenas(dev, case, B, H, Nq, Nk, D, packed)
+    O, LSE = Guarded(B * Nq, C, BF, dev), Guarded(1, B * H * Nq, torch.float32, dev, pad=0)
+    DQ = Guarded(B * Nq, C, BF, dev)
+    if packed:
+        DKV = Guarded(B * Nk, 2 * C, BF, dev)
+        dkptr, dvptr, ldg = DKV.ptr, DKV.ptr + 2 * C, DKV.ld
+    else:
+        DK, DV = Guarded(B * Nk, C, BF, dev), Guarded(B * Nk, C, BF, dev)
+        dkptr, dvptr, ldg = DK.ptr, DV.ptr, DK.ld
+    desc = _lib.SdtAttnDesc(B, H, Nq, Nk, D, Q.ld, ldkv, ldkv, O.ld, scale, 0, DQ.ld, ldg, ldg, DO.ld, None)
+    _lib.call("sdt_attention_fwd", Q.ptr, kptr, vptr, O.ptr, LSE.ptr, ctypes.addressof(desc), _stream())
+    torch.cuda.synchronize()
+    got = dict(o=O.t.contiguous().cpu().view(B, Nq, C))
+    assert_equal_bits(got["o"], want["o"], "out [batch][query][head * D + feature]", tile=(128, D))
+    O.check("out"); LSE.check("lse")
+    lse = LSE.t.view(B, H, Nq).double().cpu()
+    bad = ~((lse - want["lse2"]).abs() <= 1e-6 * want["lse2"].abs())
+    assert not bad.any(), f"lse2: {int(bad.sum())} rows off, first at {bad.nonzero()[0].tolist()}: got {lse[bad][0].item()!r}, want {want['lse2'][bad][0].item()!r}"
+    need = lib.sdt_attention_bwd_workspace_bytes(ctypes.addressof(desc))
+    claim = kc.ATTN_SPLIT_CLAIMS[(B, H, Nq, Nk, False)]
+    assert (need > kc.attention_delta_bytes(B, H, Nq)) == claim, f"workspace {need} bytes: the dK/dV pass must {'split' if claim else 'not split'} here"
+    if delta_only:
+        assert claim
+        need = kc.attention_delta_bytes(B, H, Nq)
+    ws = torch.full((need // 4,), float("nan"), dtype=torch.float32, device=dev)
+    rc = lib.sdt_attention_bwd(Q.ptr, kptr, vptr, O.ptr, DO.ptr, LSE.ptr, DQ.ptr, dkptr, dvptr, ws.data_ptr(), need, ctypes.addressof(desc), _stream())
+    assert rc == 0, f"sdt_attention_bwd returned {rc}: {lib.sdt_last_error()!r}"
+    torch.cuda.synchronize()
+    if packed:
+        DKV.check("dk | dv")
+        got["dk"], got["dv"] = (t.contiguous().cpu().view(B, Nk, C) for t in (DKV.t[:, :C], DKV.t[:, C:]))
+    else:
+        DK.check("dk"); DV.check("dv")
+        got["dk"], got["dv"] = (g.t.contiguous().cpu().view(B, Nk, C) for g in (DK, DV))
+    DQ.check("dq")
+    got["dq"] = DQ.t.contiguous().cpu().view(B, Nq, C)
+    msgs = kc.pair_reports(got, want, D)
+    assert not msgs, "\n".join(msgs)
+    for what, g in (("q", Q), ("dout", DO), ("k", KG), ("v", VG), ("out", O), ("lse", LSE)):
+        if g is not None:
+            g.check(what)
+
+
+@pytest.mark.parametrize("B,H,Nq,Nk,D,packed", kc.ATTN_PAIR_CASES)
+def test_attention_tied_pairs_every_bit(dev, B, H, Nq, Nk, D, packed):
+    """Tied-pair inputs: every query ties two keys that usually lie in different 64-key tiles, P is exactly 1/2, 1/2, and the
+    extras make dS.K and dS^T.Q nonzero: dQ and dK are exact multiples of scale / 4, pinned in every bit - also through the
+    query-split slabs and attn_kv_finish_kernel (the last four cases)."""
+    _attention_pairs(dev, B, H, Nq, Nk, D, packed, delta_only=False)
+
+
+@pytest.mark.parametrize("B,H,Nq,Nk,D,packed", [kc.ATTN_PAIR_SPLIT_CASES[1], kc.ATTN_PAIR_SPLIT_CASES[2]])
+def test_attention_split_shape_with_delta_only_workspace(dev, B, H, Nq, Nk, D, packed):
+    """A shape that splits the query range, called with workspace_bytes = 4 * ceil4(B * H * Nq): OK, and the exact bits."""
+    _attention_pairs(dev, B, H, Nq, Nk, D, packed, delta_only=True)
+
+
 @pytest.mark.parametrize("B,H,N,D", [(3, 12, 77, 64), (1, 3, 77, 16), (2, 8, 256, 40), (2, 4, 200, 80), (1, 2, 130, 128), (1, 2, 64, 160)])
 def test_attention_causal_row_zero_is_v_row_zero(dev, B, H, N, D):
     """Query 0 of a causal problem sees one key: P = exp2(0) = 1, l = 1, so O[:, 0] == V[:, 0] bit for bit for any Gaussian q, k, v
@@ -506,16 +577,11 @@ def test_attention_causal_row_zero_is_v_row_zero(dev, B, H, N, D):
     O.check("out")
 
 
-ATTN_ROW_CASES = [
-    # B, H, Nq, Nk, D, causal: the shapes of test_attention_fwd_bwd
-    (2, 8, 256, 256, 40, False), (1, 8, 1024, 1024, 40, False), (2, 8, 64, 77, 160, False), (2, 8, 256, 77, 80, False),
-    (2, 5, 144, 144, 64, False), (3, 12, 77, 77, 64, True), (1, 3, 77, 77, 16, True), (1, 2, 200, 333, 128, False),
-    (1, 8, 4096, 4096, 40, False), (1, 5, 9216, 9216, 64, False), (1, 10, 2304, 2304, 64, False), (2, 20, 1024, 1024, 64, False),
-    (2, 8, 2048, 77, 40, False), (1, 4, 1100, 100, 64, False), (4, 8, 1024, 77, 80, False)]
+ATTN_ROW_CASES = kc.ATTN_ROW_CASES + kc.ATTN_ROW_HEADDIM_CASES  # (B, H, Nq, Nk, D, causal)
 ROW_FACTOR = kc.ROW_FACTOR  # kernel worst row <= 3 x emulation worst row (what the emulation leaves out: kernel_checks.attention_ref_and_emulation)
 
 
-def _attention_rows(dev, q, k, v, do, H, D, causal, what):
+def _attention_rows(dev, q, k, v, do, H, D, causal, what, key_weight=None):
     """Per (batch, head, query row) for O and dQ, per (batch, head, key row) for dK and dV: relative L2 error against the float64
     reference; the kernel's worst row must stay within ROW_FACTOR of the worst row of the rounding-point emulation on the same
     inputs.  The figures are printed (DESIGN.md "kernel test tolerances" records them)."""
@@ -523,10 +589,10 @@ def _attention_rows(dev, q, k, v, do, H, D, causal, what):
     B = q.shape[0]
     scale = D ** -0.5
     qg, kg, vg = (t.clone().requires_grad_(True) for t in (q, k, v))
-    o = ops.attention(qg, kg, vg, H, scale, causal)
+    o = ops.attention(qg, kg, vg, H, scale, causal, key_weight)
     o.backward(do)
     torch.cuda.synchronize()
-    ref, emu, mag = kc.attention_ref_and_emulation(q, k, v, do, H, scale, causal)
+    ref, emu, mag = kc.attention_ref_and_emulation(q, k, v, do, H, scale, causal, key_weight)
     got = dict(o=o.detach(), dq=qg.grad, dk=kg.grad, dv=vg.grad)
     fails = []
     for n in ("o", "dq", "dk", "dv"):
@@ -548,6 +614,19 @@ def test_attention_gaussian_inputs_per_row(dev, B, H, Nq, Nk, D, causal):
     q, do = (torch.randn(B, Nq, H * D, generator=g).to(BF).to(dev) for _ in range(2))
     k, v = (torch.randn(B, Nk, H * D, generator=g).to(BF).to(dev) for _ in range(2))
     _attention_rows(dev, q, k, v, do, H, D, causal, f"{(B, H, Nq, Nk, D, causal)}")
+
+
+@pytest.mark.parametrize("B,H,Nq,Nk,D", kc.ATTN_ROW_KEYWEIGHT_CASES)
+def test_attention_gaussian_inputs_per_row_with_key_weights(dev, B, H, Nq, Nk, D):
+    """The same rule with the key weights of the clamped chunks (64 queries x 77 keys: keys 13..63 count twice), at two head dims
+    whose forward takes the row sum from the ones column."""
+    from stable_diffusion_training_amd import nets
+    w = nets.key_chunk_weights(Nq, Nk, dev)
+    assert w is not None and kc.attention_msum(D)
+    g = torch.Generator().manual_seed(Nq + D)
+    q, do = (torch.randn(B, Nq, H * D, generator=g).to(BF).to(dev) for _ in range(2))
+    k, v = (torch.randn(B, Nk, H * D, generator=g).to(BF).to(dev) for _ in range(2))
+    _attention_rows(dev, q, k, v, do, H, D, False, f"{(B, H, Nq, Nk, D)} key weights", key_weight=w)
 
 
 @pytest.mark.parametrize("D", [64, 40, 80])

@@ -2,6 +2,8 @@
 a correct expectation, plant the defects a whole-tensor norm cannot see (one element off by one bf16 ulp, one unwritten row, one
 column that lost its product term, one store outside the output) and assert that the checkers of tests/kernel_checks.py report each
 at the right coordinates.  Plus the arithmetic the exact tests rest on: every exact case keeps sum |a||b| below 2^24.
+For attention: selector inputs make it a gather, tied pairs give dQ and dK exact nonzero values that survive perturbed probabilities,
+five planted gradient faults are reported, and the case tables reach every head dim, instantiation and planner branch they name.
 The same for tests/test_gpu_reduce_optim_exact.py (second half of this file): a missing workgroup partial, a dropped tail element, = for
 +=, a non-zero counter, a code off by one, a neighbour's inverse scale, an unclipped log-variance, exchanged sin / cos halves.
 And for tests/test_gpu_norm_exact.py (the end of this file): the balanced cases have a unique representable result that fp32 arithmetic of
@@ -196,7 +198,7 @@ def test_expected_partial_rows_follow_the_header():
 def test_selector_inputs_make_attention_a_gather():
     """float64 softmax, P rounded to bf16, O rounded to bf16: exactly the gathered V rows, on every selector shape small enough for
     the CPU; the winner leads by >= 2 c^2 / sqrt(D) >= 162 logits and the largest logit is finite in fp32."""
-    for (B, H, Nq, Nk, D, causal, packed, kw) in kc.ATTN_SELECTOR_CASES:
+    for (B, H, Nq, Nk, D, causal, packed, kw) in kc.ATTN_SELECTOR_CASES + kc.ATTN_HEADDIM_CASES + kc.ATTN_EDGE_CASES:
         if Nq * Nk > 300000:
             B, H = 1, 1
         if Nq * Nk > 2000000:
@@ -222,6 +224,143 @@ def test_selector_inputs_make_attention_a_gather():
         assert ((p * (dp - delta)) == 0).all()   # dS = 0: dQ and dK are exactly zero
         lse_ref = torch.logsumexp(s, -1) * 1.4426950408889634
         assert ((lse2 - lse_ref).abs() <= 1e-6 * lse_ref.abs()).all()
+
+
+def _pair(c, **kw):
+    """(case, expectation, kv_chunk) of one ATTN_PAIR_CASES entry, as test_attention_tied_pairs_every_bit builds them."""
+    B, H, Nq, Nk, D, packed = c
+    case = kc.pair_case(B, H, Nq, Nk, D, seed=Nq + Nk + D, **kw)
+    planned, chunk, launched = kc.attention_qsplit(B, H, Nq, Nk, False)
+    kvc = chunk if planned > 1 else None
+    return case, kc.pair_expect(case, B, H, Nq, Nk, D, D ** -0.5, kv_chunk=kvc), kvc
+
+
+def _pair_shares(c, exp):
+    """(nonzero share of the expected dQ, its floor, nonzero share of dK, its floor).  The floors are 1/4 and 1/3, with one
+    derived exception.  dQ is nonzero on the key-extra features only (the twins' codes cancel in dS.K); they make up
+    (D - nb + 1) // 2 of the D features, and within such a column dq = dS (k1 - k2) is nonzero with probability
+    P(dS != 0) P(k1 != k2) = (6/7)^2 = 0.73.  At D = 16 with 100 pairs (7 code features, 5 key extras: ceiling 0.31, expected 0.23)
+    and at D = 8 with 36 pairs (6 code features, ONE key extra: ceiling 0.125, expected 0.09) 1/4 is out of the construction's
+    reach, so the floor is min(1/4, 2/3 of the ceiling): 1/4 for every other case."""
+    D = c[4]
+    nb = max(1, math.ceil(math.log2(max(-(-c[3] // 2), 2))))
+    ceiling = ((D - nb + 1) // 2) / D
+    return (float((exp["dq"] != 0).double().mean()), min(0.25, ceiling * 2 / 3),
+            float((exp["dk"] != 0).double().mean()), 1 / 3)
+
+
+@pytest.mark.parametrize("c", kc.ATTN_PAIR_CASES, ids=lambda c: "x".join(str(int(v)) for v in c))
+def test_tied_pair_cases_are_exact_nonzero_and_keep_their_bits_under_perturbed_probabilities(c):
+    """Every pair case: the twins tie exactly and lead the rest by >= 2 * 32^2 / sqrt(D); dS is exact in bf16 and both accumulators
+    (every query chunk's part included) in fp32 below 2^24 - pair_expect asserts it, and it is asserted again here; dQ and dK cannot
+    degenerate to zeros; the rounding-point emulation lands on the expectation (by value: the sign of a zero in the float64
+    emulation is the BLAS's).  Margin: the kernels' exp2 / log2 are not exact - the error of P is about the fp32 ulp of lse2, 2^-13
+    relative, the bf16 half-ulp is 2^-9 - so the expectation recomputed with every probability (the forward's row sum included)
+    scaled by 1 +- 2^-10 and rounded as the kernels round must keep every bit of O, dS, dQ, dK and dV."""
+    B, H, Nq, Nk, D, packed = c
+    scale = D ** -0.5
+    case, exp, kvc = _pair(c)
+    tie, lead, top = kc.pair_min_gap(case, B, H, Nq, Nk, D, scale)
+    assert tie == 0.0 and lead >= 2 * 32.0 ** 2 / D ** 0.5 - 1e-9 >= 161.9 and top < 3000
+    assert set(exp["p"].unique().tolist()) <= {0.0, 0.5, 1.0} and torch.equal(exp["p"].sum(-1), torch.ones(B, H, Nq, dtype=torch.float64))
+    assert ((exp["p"] == 0.5).sum(-1) == 2).any() and (Nk % 2 == 0) == (not (exp["p"] == 1).any())
+    assert torch.equal(exp["ds"].float().to(BF).double(), exp["ds"]) and float(exp["ds"].abs().max()) <= 3 and (exp["ds"] * 4 == (exp["ds"] * 4).round()).all()
+    for n in ("acc_q", "acc_k"):
+        assert torch.equal(exp[n].float().double(), exp[n]) and float(exp[n].abs().max()) < kc.LIMIT and (exp[n] * 4 == (exp[n] * 4).round()).all(), n
+    sq, fq, sk, fk = _pair_shares(c, exp)
+    assert sq >= fq and sk >= fk, f"dQ nonzero share {sq:.3f} (floor {fq:.3f}), dK {sk:.3f} (floor {fk:.3f})"
+    assert (fq == 0.25) == (D > 16)
+    ref, emu, mag = kc.attention_ref_and_emulation(case["q"], case["k"], case["v"], case["dout"], H, scale, kv_chunk=kvc)
+    for n in ("o", "dq", "dk", "dv"):
+        assert torch.equal(emu[n], exp[n].double()), kc.mismatch_report((emu[n] + 0.0).to(BF), exp[n], f"emulation {n}", tile=(128, D))
+    for e in (2.0 ** -10, -2.0 ** -10):
+        per = kc.pair_expect(case, B, H, Nq, Nk, D, scale, kv_chunk=kvc, perturb=e)
+        assert torch.equal(per["ds"], exp["ds"]), f"dS moves under P (1 {e:+.1e})"
+        msgs = kc.pair_reports(per, exp, D)
+        assert not msgs, f"P (1 {e:+.1e}): " + "\n".join(msgs)
+
+
+def test_degenerate_pair_cases_are_refused():
+    """Without the extras dS.K is zero everywhere and dS^T.Q on the query-extra features: the share floors must say so."""
+    for c in (kc.ATTN_PAIR_CASES[0], kc.ATTN_PAIR_CASES[12], kc.ATTN_PAIR_CASES[15]):
+        case, exp, kvc = _pair(c, extras=False)
+        sq, fq, sk, fk = _pair_shares(c, exp)
+        assert sq == 0.0 and sq < fq, (c, sq)
+        case, exp, kvc = _pair(c)
+        assert _pair_shares(c, exp)[0] >= fq
+
+
+def test_planted_attention_gradient_faults_are_each_reported_with_coordinates():
+    """dq all zero; the dq columns of two heads exchanged; dk without the last query chunk's slab; scale applied twice; dk and dv
+    exchanged: the pair checker names the tensor, the first element and the tiles of each."""
+    c = kc.ATTN_PAIR_CASES[15]
+    B, H, Nq, Nk, D, packed = c
+    assert (B, H, Nq, Nk, D) == (1, 2, 1100, 100, 64)
+    case, exp, kvc = _pair(c)
+    assert kvc == 320
+    good = {n: exp[n].clone() for n in ("o", "dq", "dk", "dv")}
+    assert kc.pair_reports(good, exp, D) == []
+
+    def first_diff(a, b):
+        return tuple(int(v) for v in (kc.bits(a) != kc.bits(b)).nonzero()[0])
+
+    def only(msgs, name, got):
+        assert len(msgs) == 1 and msgs[0].startswith(name + " ["), msgs
+        assert f"at {first_diff(got, exp[name])}:" in msgs[0] and "output tiles (128 x 64) hit" in msgs[0], msgs[0]
+        return msgs[0]
+
+    bad = dict(good, dq=torch.zeros_like(good["dq"]))
+    m = only(kc.pair_reports(bad, exp, D), "dq", bad["dq"])
+    assert f"{int((exp['dq'] != 0).sum())} of {exp['dq'].numel()} elements differ" in m
+    bad = dict(good, dq=torch.cat([good["dq"][..., D:], good["dq"][..., :D]], -1))
+    m = only(kc.pair_reports(bad, exp, D), "dq", bad["dq"])
+    assert "(0, 0)" in m and "(0, 1)" in m  # both heads' column tiles
+    drop = kc.pair_expect(case, B, H, Nq, Nk, D, D ** -0.5, kv_chunk=kvc, drop_rows=(Nq - 320, Nq))
+    bad = dict(good, dk=drop["dk"])
+    m = only(kc.pair_reports(bad, exp, D), "dk", bad["dk"])
+    twice = kc.pair_expect(case, B, H, Nq, Nk, D, D ** -0.5, kv_chunk=kvc, scale_twice=True)
+    bad = dict(good, dq=twice["dq"], dk=twice["dk"])
+    msgs = kc.pair_reports(bad, exp, D)
+    assert [m.split(" [")[0] for m in msgs] == ["dq", "dk"] and f"at {first_diff(bad['dk'], exp['dk'])}:" in msgs[1]
+    assert int((kc.bits(twice["dq"]) != kc.bits(exp["dq"])).sum()) == int((exp["dq"] != 0).sum())  # every nonzero element, no other
+    bad = dict(good, dk=good["dv"], dv=good["dk"])
+    msgs = kc.pair_reports(bad, exp, D)
+    assert [m.split(" [")[0] for m in msgs] == ["dk", "dv"] and f"at {first_diff(bad['dv'], exp['dv'])}:" in msgs[1]
+
+
+def test_attention_tables_reach_every_instantiation():
+    """Over the selector, head-dim, pair, edge and row tables (every case runs the forward, dQ and dK/dV): each of the six
+    instantiations, in each row-sum variant of its forward, occurs causal and not in the bit-for-bit tables and not causal in the
+    row tables (the pair cases, not causal, hold the values of dQ and dK for each); each meets both values of packed and of
+    key_weights; the split dK/dV pass runs on pair inputs in every instantiation; every head dim 8 ... 160 occurs in the head-dim
+    and in the row tables."""
+    every = list(range(8, 168, 8))
+    variants = {kc.attention_instance(D) for D in every}
+    assert len(variants) == 10 and len({v[:3] for v in variants}) == 6
+    assert {v[:3] for v in variants if v[3]} == {v[:3] for v in variants} and len({v[:3] for v in variants if not v[3]}) == 4  # <64,3,2> and <128,5,3>: ones column only
+    assert [kc.attention_msum(D) for D in (48, 56, 64, 80, 88, 96, 120, 128, 152, 160)] == [True, True, False, True, True, False, True, False, True, False]
+    bitwise = kc.ATTN_SELECTOR_CASES + kc.ATTN_HEADDIM_CASES + kc.ATTN_EDGE_CASES
+    rows = kc.ATTN_ROW_CASES + kc.ATTN_ROW_HEADDIM_CASES
+    for causal in (False, True):
+        assert {kc.attention_instance(c[4]) for c in bitwise if bool(c[5]) == causal} == variants, causal
+    assert {kc.attention_instance(c[4]) for c in rows if not c[5]} == variants
+    assert {kc.attention_instance(c[4])[:3] for c in rows if c[5]} == {(64, 3, 2), (64, 4, 2), (128, 6, 3), (256, 10, 5)}
+    assert {kc.attention_instance(c[4]) for c in kc.ATTN_PAIR_CASES} == variants
+    for flag in (6, 7):
+        for value in (False, True):
+            assert {kc.attention_instance(c[4]) for c in kc.ATTN_HEADDIM_CASES if c[flag] == value and not c[5]} == variants, (flag, value)
+    split = lambda tab: {kc.attention_instance(c[4])[:3] for c in tab if kc.attention_qsplit(c[0], c[1], c[2], c[3], len(c) > 6 and c[5] or False)[0] > 1}
+    assert split(kc.ATTN_PAIR_CASES) == {v[:3] for v in variants} and (128, 5, 3) in split(bitwise) and (128, 5, 3) in split(rows)
+    assert all(kc.attention_qsplit(*c[:4], False)[0] > 1 for c in kc.ATTN_PAIR_SPLIT_CASES)
+    assert {c[4] for c in kc.ATTN_HEADDIM_CASES if not c[5] and c[:4] == (1, 3, 136, 200)} == set(every)
+    assert {c[4] for c in rows} == set(every) and {c[4] for c in rows if not c[5]} == set(every) - {16}  # (16: causal only)
+    assert {kc.attention_instance(D)[:3] for B, H, Nq, Nk, D in kc.ATTN_ROW_KEYWEIGHT_CASES} == {(128, 6, 3), (256, 10, 5)}
+    assert len(set(bitwise)) == len(bitwise) and len(set(rows)) == len(rows) and len(set(kc.ATTN_PAIR_CASES)) == len(kc.ATTN_PAIR_CASES)
+    # the size edges the tables name
+    assert {(1, 1), (1, 77), (77, 1)} <= {(c[2], c[3]) for c in kc.ATTN_EDGE_CASES}
+    assert {(D, Nk) for D in (64, 88) for Nk in (63, 64, 65, 127, 128, 129)} <= {(c[4], c[3]) for c in kc.ATTN_EDGE_CASES if c[2] == 136}
+    assert {127, 128, 129} <= {c[2] for c in kc.ATTN_EDGE_CASES if c[4] == 96}
+    assert kc.attention_qsplit(1, 1, 1600, 77, False) == (6, 320, 5) and kc.attention_qsplit(1, 1, 1023, 77, False)[0] == 1 and kc.attention_qsplit(1, 1, 1024, 77, False)[0] == 4
 
 
 def test_per_slice_norm_sees_one_wrong_row():
@@ -288,6 +427,21 @@ def test_case_tables_take_the_planner_branches_they_name(lib):
     for B, H, W, Cin, Cout, G in kc.GN_HALO_CASES:
         geom = _lib.SdtConvGeom(B, H, W, H, W, 3, 3, 1, 1, 1)
         assert lib.sdt_gemm_nt_gn_parts(B * H * W, Cout, Cin, 9, H * W, G, _lib.GATHER_FPROP, ctypes.addressof(geom)) > 0
+    # attention: the split / no-split claims of the tables, and the Python mirror of the query-split planner (kc.attention_qsplit)
+    # for every case of every attention table, against sdt_attention_bwd_workspace_bytes
+    def attn_need(B, H, Nq, Nk, D, causal):
+        d = _lib.SdtAttnDesc(B, H, Nq, Nk, D, H * D, H * D, H * D, H * D, D ** -0.5, int(causal), 0, 0, 0, 0, None)
+        return lib.sdt_attention_bwd_workspace_bytes(ctypes.addressof(d))
+    for (B, H, Nq, Nk, causal), claim in kc.ATTN_SPLIT_CLAIMS.items():
+        assert (attn_need(B, H, Nq, Nk, 64, causal) > kc.attention_delta_bytes(B, H, Nq)) == claim, (B, H, Nq, Nk, causal)
+    shapes = {(c[0], c[1], c[2], c[3], c[4], bool(c[5])) for c in kc.ATTN_SELECTOR_CASES + kc.ATTN_HEADDIM_CASES + kc.ATTN_EDGE_CASES
+              + kc.ATTN_ROW_CASES + kc.ATTN_ROW_HEADDIM_CASES} | {c[:5] + (False,) for c in kc.ATTN_PAIR_CASES}
+    for B, H, Nq, Nk, D, causal in shapes:
+        planned, chunk, launched = kc.attention_qsplit(B, H, Nq, Nk, causal)
+        slabs = planned * 2 * B * Nk * H * D * 4 if planned > 1 else 0
+        assert attn_need(B, H, Nq, Nk, D, causal) == kc.attention_delta_bytes(B, H, Nq) + slabs, (B, H, Nq, Nk, D, causal)
+        assert chunk % 64 == 0 and launched <= planned and (launched - 1) * chunk < Nq <= launched * chunk
+    assert all(kc.ATTN_SPLIT_CLAIMS[c[:4] + (False,)] for c in kc.ATTN_PAIR_SPLIT_CASES)
     # the Python mirror of the halo planner (kc.halo_tile) against the library, for the forward and the input gradient of every
     # convolution case: a one-image halo tiling answers 2 * tiles_x * tiles_y partial rows; a four-image
     # tiling answers 0 (a tile straddles images) where the plain planner would not
