@@ -19,7 +19,10 @@ each latent position by its pooled mask, at least FLOOR (default 0: only the mas
 ("normalize_masked_area") rescales every sample by area / masked area; --prior-loss-weight W ("prior_loss_weight"): every second sample is a
 class image whose loss counts W times (DreamBooth prior preservation).  A latent cache keeps the pooled masks and the weights.
 --loss-type huber | smooth_l1 ("loss_type"; l2 is the default) trains on the pseudo-Huber loss, with --huber-c C ("huber_c", default 0.1)
-and --huber-schedule snr | exponential | constant ("huber_schedule", default snr) for the threshold of each sample's timestep."""
+and --huber-schedule snr | exponential | constant ("huber_schedule", default snr) for the threshold of each sample's timestep.
+--inpaint ("inpaint": true) trains an inpainting UNet: a UNet that is not one already (in_channels != 2 * out_channels + 1) is widened
+with zero conv_in rows (nets.widen_conv_in), the loader emits an inpaint_mask per image, and every step feeds [noisy latents | mask |
+latents of the masked image].  With --cache-latents the cache keeps the masked image's moments and the latent mask."""
 import argparse
 import json
 import os
@@ -84,6 +87,11 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         tokenizer = models["tokenizer"]
         if "tokenizer_2" in models:  # SDXL: save_model writes both
             tokenizer = (tokenizer, models["tokenizer_2"])
+    inpaint = bool(config_dict.get("inpaint"))
+    if inpaint and nets.inpaint_latent_channels(models["unet"]["config"]) is None:
+        ucfg = models["unet"]["config"]
+        params, ucfg = nets.widen_conv_in(models["unet"]["unet_params"], ucfg, 2 * int(ucfg["out_channels"]) + 1)
+        models = dict(models, unet=dict(models["unet"], unet_params=params, config=ucfg))
     te_cfg = models["text_encoder"]["config"]
     sdxl = nets.sdxl_conditioning(te_cfg)  # an SDXL directory: two towers, pooled embedding from the text encoder
     vocab = te_cfg["towers"][0]["vocab_size"] if "towers" in te_cfg else te_cfg["vocab_size"]
@@ -93,7 +101,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     prior_w = config_dict.get("prior_loss_weight")
     if config_dict.get("normalize_masked_area") and not use_mask:
         raise ValueError("normalize_masked_area needs masked_loss (--masked-loss)")
-    loss_loader_kw = dict(loss_masks=use_mask, prior_every=2 if prior_w is not None else 0,
+    loss_loader_kw = dict(inpaint_masks=inpaint, loss_masks=use_mask, prior_every=2 if prior_w is not None else 0,
                           prior_loss_weight=1.0 if prior_w is None else float(prior_w))
     loss_overrides = {}
     if use_mask:
@@ -259,6 +267,8 @@ if __name__ == "__main__":
                     help="every second sample is a class image whose loss counts W times (DreamBooth prior preservation)")
     ap.add_argument("--loss-type", choices=("l2", "huber", "smooth_l1"), default=None,
                     help="l2 (default); huber / smooth_l1: the pseudo-Huber losses, robust to outlier images and high-noise timesteps")
+    ap.add_argument("--inpaint", action="store_true", default=None,
+                    help="train an inpainting UNet (widened from the checkpoint's when it is not one) from batches with an inpaint mask")
     ap.add_argument("--huber-c", metavar="C", type=float, default=None, help="the Huber threshold the schedule ends at (default 0.1)")
     ap.add_argument("--huber-schedule", choices=("constant", "exponential", "snr"), default=None,
                     help="how the threshold follows the timestep: snr (default), exponential or constant")
@@ -285,6 +295,8 @@ if __name__ == "__main__":
         cfg["prior_loss_weight"] = args.prior_loss_weight
     if args.loss_type is not None:
         cfg["loss_type"] = args.loss_type
+    if args.inpaint:
+        cfg["inpaint"] = True
     if args.huber_c is not None:
         cfg["huber_c"] = args.huber_c
     if args.huber_schedule is not None:

@@ -114,6 +114,40 @@ int sdt_latent_noise_target(const uint16_t* moments_nhwc, const float* eps_nhwc,
                             uint16_t* noisy_nhwc_bf16, float* target_nchw, float* latents_nchw, float* noisy_nchw, int B, int L,
                             int H, int W, int moment_stride, int cpad, float scale, float offset_mag, float perturb_mag,
                             int prediction_type, hipStream_t stream);
+/* ---- INPAINTING: the input of a UNet with in_channels = 2L + 1, [noisy latents | mask | VAE latents of the masked image]
+ * (diffusers' inpainting training example and pipeline).  fl() is one fp32 rounding; nothing below is contracted.
+ *   repaint(m) = (m >= 0.5): 1 repaints, 0 keeps, a NaN keeps.
+ *   masked image, at pixel size: repaint ? +0.0 : x - a select, never -0, a NaN pixel under the mask becomes 0.
+ *   latent mask, nearest neighbour: m_lat[b][y][x] = repaint(mask[b][y*f][x*f]) ? 1.0f : 0.0f.
+ *   masked-image latents: xm = fl(fma(exp(0.5*clip(lv,-30,20)), eps_m, mean) * scale), sdt_vae_posterior_sample's arithmetic on the
+ *   masked image's moments with a draw of its own; rounded to bf16 (RNE) where it enters the UNet input.
+ *   UNet input bf16 NHWC (B,h,w,cpad >= 2L+1): [0,L) noisy latents, [L] latent mask, [L+1,2L+1) masked-image latents, rest zero.
+ * None of the three uses atomics or a workspace.
+ * sdt_inpaint_mask_pixels: pixels f32 NCHW (B,C,H,W), mask f32 (B,H,W) -> stacked bf16 NHWC (2B,H,W,cpad): rows [0,B) the image with
+ *   the bits of sdt_nchw_f32_to_nhwc_bf16 (one RNE rounding), rows [B,2B) the masked image (the select in fp32, then the same
+ *   rounding), padding channels zero; latent_mask f32 (B,H/f,W/f) as above.  One pass over the pixels; 16-byte row stores when
+ *   cpad % 8 == 0 and the base is aligned, scalar stores otherwise.  Refused: a NULL pointer, f < 1, H % f or W % f != 0, cpad < C.
+ * sdt_inpaint_noise_target: sdt_latent_noise_target's operands, meaning, NULL rules and - in channels [0,L) of input_nhwc, target,
+ *   latents and noisy - its bits, plus masked_moments bf16 (B,H,W,moment_stride), masked_eps f32 (B,H,W,L), latent_mask f32 (B,H,W)
+ *   (thresholded again with repaint(), idempotent on 0/1) and the optional masked_latents f32 NCHW (B,L,H,W) (xm before the bf16
+ *   rounding).  cpad >= 2L+1.  16-byte moment loads when moment_stride % 8 == 0 and both bases are aligned, 16-byte row stores when
+ *   cpad % 8 == 0 and the base is aligned; each 8-channel group of a row is stored once.
+ * sdt_inpaint_pack_input: the sampler's UNet input.  latents bf16 (R,h,w,cpad_src), masked_latents bf16 (B,h,w,cpad_m), latent_mask
+ *   f32 (B,h,w) -> input bf16 (R,h,w,cpad_dst): row r takes the mask and masked latents of sample r % B (the doubled
+ *   classifier-free-guidance batch); channels [0,L) and [L+1,2L+1) are 16-bit copies (of latents[..., 0:L] and
+ *   masked_latents[..., 0:L]), [L] is repaint(mask) as 1.0 / 0.0, the rest zero.  R % B == 0, cpad_src, cpad_m >= L,
+ *   cpad_dst >= 2L+1. */
+int sdt_inpaint_mask_pixels(const float* pixels_nchw, const float* mask, uint16_t* stacked_nhwc_bf16, float* latent_mask, int B,
+                            int C, int H, int W, int cpad, int f, hipStream_t stream);
+int sdt_inpaint_noise_target(const uint16_t* moments_nhwc, const uint16_t* masked_moments_nhwc, const float* eps_nhwc,
+                             const float* masked_eps_nhwc, const float* latent_mask, const float* noise_nchw, const float* offset,
+                             const float* perturb_nchw, const int32_t* timesteps, const float* alphas_cumprod,
+                             uint16_t* input_nhwc_bf16, float* target_nchw, float* latents_nchw, float* noisy_nchw,
+                             float* masked_latents_nchw, int B, int L, int H, int W, int moment_stride, int cpad, float scale,
+                             float offset_mag, float perturb_mag, int prediction_type, hipStream_t stream);
+int sdt_inpaint_pack_input(const uint16_t* latents_nhwc, const uint16_t* masked_latents_nhwc, const float* latent_mask,
+                           uint16_t* input_nhwc, int R, int B, int L, int H, int W, int cpad_src, int cpad_m, int cpad_dst,
+                           hipStream_t stream);
 /* loss_accum += mean(w_b*(target-pred)^2); dpred = d loss / d pred (bf16 NHWC, cpad channels).
  * REDUCTION WORKSPACES (this call, sdt_sqnorm_accumulate, sdt_colsum_*): sums that cross workgroups use no float atomics - each
  * workgroup stores a partial, the one that arrives last adds them in a fixed order, so results are bitwise reproducible.  They

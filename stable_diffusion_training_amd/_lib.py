@@ -56,6 +56,9 @@ SIGNATURES = {
     "sdt_add_noise_velocity": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "sdt_vae_posterior_sample": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P],
     "sdt_latent_noise_target": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P],
+    "sdt_inpaint_mask_pixels": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
+    "sdt_inpaint_noise_target": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P],
+    "sdt_inpaint_pack_input": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sdt_ddim_cfg_step": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P],
     "sdt_cfg_rescale_factors": [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P],
     "sdt_sampler_cfg_step": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _I, _F, _F, _F, _F, _P],

@@ -186,6 +186,32 @@ __global__ void __launch_bounds__(256) posterior_sample_kernel(const bf16_t* __r
 // kernels above compile to  x0 = fl(fma(e, eps, mean) * scale),  noisy = fma(sa, x0, fl(so * n)),  velocity = fl(sa * n) - fl(so * x0).
 // VEC_IN: a pixel's moments by 16-byte loads (mstride % 8 == 0, L % 4 == 0, 16-byte aligned base: the log-variances then start at
 // a 16- or 8-byte boundary of the row); VEC_OUT: the bf16 row by 16-byte stores (cpad % 8 == 0, aligned base).
+// The posterior sample of one channel with posterior_sample_kernel's bits: fl(fma(exp(0.5 * clip(lv)), eps, mean) * scale).
+__device__ __forceinline__ float posterior_element(float mean, float lv, float eps, float scale) {
+#pragma clang fp contract(off)
+  lv = lv < -30.f ? -30.f : (lv > 20.f ? 20.f : lv);  // keeps a NaN, as posterior_sample_kernel
+  return __fmaf_rn(__expf(0.5f * lv), eps, mean) * scale;
+}
+
+// One latent element of the fused front (latent_noise_target_kernel and inpaint_noise_target_kernel): the sample, the mixed noise,
+// the optional fp32 outputs at `off` (NCHW) and the noisy value that goes into the bf16 row.  bc = b * L + c.
+__device__ __forceinline__ float noise_target_element(float mean, float lv, float eps, long off, int bc, float sa, float so,
+                                                      const float* __restrict__ noise, const float* __restrict__ offset,
+                                                      const float* __restrict__ perturb, float* __restrict__ target,
+                                                      float* __restrict__ lat_nchw, float* __restrict__ noisy_nchw, float scale,
+                                                      float offset_mag, float perturb_mag, int ptype) {
+#pragma clang fp contract(off)
+  const float x0 = posterior_element(mean, lv, eps, scale);
+  float n = noise[off];
+  if (offset) n = n + offset[bc] * offset_mag;
+  if (perturb) n = n + perturb_mag * perturb[off];
+  const float v = __fmaf_rn(sa, x0, so * n);
+  if (lat_nchw) lat_nchw[off] = x0;
+  if (noisy_nchw) noisy_nchw[off] = v;
+  if (target) target[off] = ptype == 2 ? sa * n - so * x0 : n;
+  return v;
+}
+
 template <bool VEC_IN, bool VEC_OUT>
 __global__ void __launch_bounds__(256) latent_noise_target_kernel(
     const bf16_t* __restrict__ mom, const float* __restrict__ eps, const float* __restrict__ noise, const float* __restrict__ offset,
@@ -228,18 +254,8 @@ __global__ void __launch_bounds__(256) latent_noise_target_kernel(
         for (int j = 0; j < 8; ++j) {
           const int c = c0 + j;
           if (c < L) {
-            const long off = ((long)b * L + c) * HW + p;
-            float l = lv[j];
-            l = l < -30.f ? -30.f : (l > 20.f ? 20.f : l);  // keeps a NaN, as posterior_sample_kernel
-            const float x0 = __fmaf_rn(__expf(0.5f * l), eps[i * L + c], mean[j]) * scale;
-            float n = noise[off];
-            if (offset) n = n + offset[b * L + c] * offset_mag;
-            if (perturb) n = n + perturb_mag * perturb[off];
-            const float v = __fmaf_rn(sa, x0, so * n);
-            nz[j] = v;
-            if (lat_nchw) lat_nchw[off] = x0;
-            if (noisy_nchw) noisy_nchw[off] = v;
-            if (target) target[off] = ptype == 2 ? sa * n - so * x0 : n;
+            nz[j] = noise_target_element(mean[j], lv[j], eps[i * L + c], ((long)b * L + c) * HW + p, b * L + c, sa, so, noise, offset,
+                                         perturb, target, lat_nchw, noisy_nchw, scale, offset_mag, perturb_mag, ptype);
           }
         }
       }
@@ -249,6 +265,186 @@ __global__ void __launch_bounds__(256) latent_noise_target_kernel(
 #pragma unroll
         for (int j = 0; j < 8; ++j)
           if (c0 + j < cpad) noisy_nhwc[i * cpad + c0 + j] = f2bf(nz[j]);
+      }
+    }
+  }
+}
+
+// ------------------------------------------------------------------ inpainting (include/sdt.h "INPAINTING")
+// 1 repaints, 0 keeps; a NaN compares false and keeps.
+__device__ __forceinline__ bool repaint(float m) { return m >= 0.5f; }
+
+// Columns [col, col + 8) of a bf16 row as four dwords; col may be any integer (negative too).  Only the columns inside [lo, hi) are
+// meaningful to the caller (the others come back as 0 or as whatever the row holds there).  VEC (stride % 8 == 0, 16-byte aligned
+// row): the one or two aligned 16-byte vectors that hold them, each read only where it lies inside the row and overlaps [lo, hi),
+// then shifted down by col & 7 elements through static selects.  Otherwise element by element.
+template <bool VEC>
+__device__ __forceinline__ uint4 row_cols8(const bf16_t* __restrict__ row, int col, int lo, int hi, int stride) {
+  if (VEC) {
+    const int s = col & 7, a = col - s;
+    uint4 va = make_uint4(0u, 0u, 0u, 0u), vb = va;
+    if (a >= 0 && a + 8 <= stride && a + 8 > lo && a < hi) va = *reinterpret_cast<const uint4*>(row + a);
+    if (s && a + 8 >= 0 && a + 16 <= stride && a + 16 > lo && a + 8 < hi) vb = *reinterpret_cast<const uint4*>(row + a + 8);
+    unsigned d[9] = {va.x, va.y, va.z, va.w, vb.x, vb.y, vb.z, vb.w, 0u};
+    if (s & 4) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) d[k] = k + 2 < 9 ? d[k + 2] : 0u;
+    }
+    if (s & 2) {
+#pragma unroll
+      for (int k = 0; k < 9; ++k) d[k] = k + 1 < 9 ? d[k + 1] : 0u;
+    }
+    if (s & 1) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d[k] = (d[k] >> 16) | (d[k + 1] << 16);
+    }
+    return make_uint4(d[0], d[1], d[2], d[3]);
+  } else {
+    unsigned d[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+      const int c = col + 2 * k;
+      const unsigned e0 = (c >= lo && c < hi) ? row[c] : 0u, e1 = (c + 1 >= lo && c + 1 < hi) ? row[c + 1] : 0u;
+      d[k] = e0 | (e1 << 16);
+    }
+    return make_uint4(d[0], d[1], d[2], d[3]);
+  }
+}
+
+// pixels f32 NCHW (B,C,H,W), mask f32 (B,H,W) -> stacked bf16 NHWC (2B,H,W,cpad): rows [0,B) the image as nchw_to_nhwc_kernel
+// writes it, rows [B,2B) the masked image (repaint ? +0 : x, a select), padding zero; latent_mask f32 (B,H/f,W/f) nearest
+// neighbour (the top-left pixel of each f x f block).  One thread per pixel: the mask and each channel plane are read coalesced
+// along W, the two bf16 rows go out by 16-byte stores (VEC: cpad % 8 == 0, aligned base).
+template <bool VEC>
+__global__ void __launch_bounds__(256) inpaint_mask_pixels_kernel(const float* __restrict__ x, const float* __restrict__ mask,
+                                                                  bf16_t* __restrict__ stacked, float* __restrict__ latent_mask,
+                                                                  int B, int C, int H, int W, int cpad, int f) {
+  const long HW = (long)H * W, total = (long)B * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / HW);
+    const long p = i % HW;
+    const int py = (int)(p / W), px = (int)(p % W);
+    const bool rp = repaint(mask[i]);
+    if (py % f == 0 && px % f == 0) latent_mask[((long)b * (H / f) + py / f) * (W / f) + px / f] = rp ? 1.0f : 0.0f;
+    bf16_t* img = stacked + i * cpad;
+    bf16_t* msk = stacked + (total + i) * cpad;
+    for (int c0 = 0; c0 < cpad; c0 += 8) {
+      float v[8], m[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = c0 + j;
+        v[j] = c < C ? x[((long)b * C + c) * HW + p] : 0.f;
+        m[j] = rp ? 0.f : v[j];
+      }
+      if (VEC) {
+        *reinterpret_cast<uint4*>(img + c0) = pack8(v);
+        *reinterpret_cast<uint4*>(msk + c0) = pack8(m);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (c0 + j < cpad) {
+            img[c0 + j] = f2bf(v[j]);
+            msk[c0 + j] = f2bf(m[j]);
+          }
+      }
+    }
+  }
+}
+
+// latent_noise_target_kernel with an inpainting UNet's input row: channels [0,L) the noisy latents (noise_target_element: the
+// same bits), [L] the thresholded latent mask, [L+1,2L+1) the posterior sample of the masked image's moments with its own draw
+// (posterior_element, rounded to bf16 with the row), the rest zero.  One thread per latent pixel; each 8-channel group of the row
+// is built in registers and stored once.  VEC_IN: both moment rows by 16-byte loads (mstride % 8 == 0, aligned bases).
+template <bool VEC_IN, bool VEC_OUT>
+__global__ void __launch_bounds__(256) inpaint_noise_target_kernel(
+    const bf16_t* __restrict__ mom, const bf16_t* __restrict__ mmom, const float* __restrict__ eps, const float* __restrict__ meps,
+    const float* __restrict__ lmask, const float* __restrict__ noise, const float* __restrict__ offset,
+    const float* __restrict__ perturb, const int* __restrict__ t, const float* __restrict__ acp, bf16_t* __restrict__ input_nhwc,
+    float* __restrict__ target, float* __restrict__ lat_nchw, float* __restrict__ noisy_nchw, float* __restrict__ mlat_nchw, int B,
+    int L, int HW, int mstride, int cpad, float scale, float offset_mag, float perturb_mag, int ptype) {
+#pragma clang fp contract(off)
+  const long total = (long)B * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int b = (int)(i / HW), p = (int)(i % HW);
+    const float a = acp[t[b]];
+    const float sa = sqrtf(a), so = sqrtf(1.0f - a);
+    const float mk = repaint(lmask[i]) ? 1.0f : 0.0f;
+    const bf16_t* row = mom + i * mstride;
+    const bf16_t* mrow = mmom + i * mstride;
+    for (int c0 = 0; c0 < cpad; c0 += 8) {
+      float o[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      if (c0 < L) {  // noisy latents: mean columns from c0, log-variances from L + c0
+        float mean[8], lv[8];
+        unpack8(row_cols8<VEC_IN>(row, c0, 0, L, mstride), mean);
+        unpack8(row_cols8<VEC_IN>(row, L + c0, L, 2 * L, mstride), lv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int c = c0 + j;
+          if (c < L)
+            o[j] = noise_target_element(mean[j], lv[j], eps[i * L + c], ((long)b * L + c) * HW + p, b * L + c, sa, so, noise, offset,
+                                        perturb, target, lat_nchw, noisy_nchw, scale, offset_mag, perturb_mag, ptype);
+        }
+      }
+      if (c0 + 8 > L + 1 && c0 < 2 * L + 1) {  // masked-image latents: channel c holds sample c - L - 1
+        float mean[8], lv[8];
+        unpack8(row_cols8<VEC_IN>(mrow, c0 - L - 1, 0, L, mstride), mean);
+        unpack8(row_cols8<VEC_IN>(mrow, c0 - 1, L, 2 * L, mstride), lv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          const int m = c0 + j - L - 1;
+          if (m >= 0 && m < L) {
+            const float xm = posterior_element(mean[j], lv[j], meps[i * L + m], scale);
+            o[j] = xm;
+            if (mlat_nchw) mlat_nchw[((long)b * L + m) * HW + p] = xm;
+          }
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        if (c0 + j == L) o[j] = mk;
+      if (VEC_OUT) {
+        *reinterpret_cast<uint4*>(input_nhwc + i * cpad + c0) = pack8(o);
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (c0 + j < cpad) input_nhwc[i * cpad + c0 + j] = f2bf(o[j]);
+      }
+    }
+  }
+}
+
+// The sampler's UNet input from the tensor the scheduler kernels write: row r of the (doubled) batch takes channels [0,L) of its own
+// latents row, the mask and the masked latents of sample r % B.  Pure bf16 moves: the values travel as 16-bit words.
+template <bool VEC_IN, bool VEC_OUT>
+__global__ void __launch_bounds__(256) inpaint_pack_input_kernel(const bf16_t* __restrict__ lat, const bf16_t* __restrict__ mlat,
+                                                                 const float* __restrict__ lmask, bf16_t* __restrict__ out, int R,
+                                                                 int B, int L, int HW, int cpad_src, int cpad_m, int cpad_dst) {
+  const long total = (long)R * HW;
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+    const int r = (int)(i / HW);
+    const long q = (long)(r % B) * HW + i % HW;  // the pixel of the sample whose mask and masked latents this row takes
+    const unsigned mk = repaint(lmask[q]) ? 0x3f80u : 0u;  // bf16 1.0
+    const bf16_t* src = lat + i * cpad_src;
+    const bf16_t* msrc = mlat + q * cpad_m;
+    for (int c0 = 0; c0 < cpad_dst; c0 += 8) {
+      uint4 sv = make_uint4(0u, 0u, 0u, 0u), mv = sv;
+      if (c0 < L) sv = row_cols8<VEC_IN>(src, c0, 0, L, cpad_src);
+      if (c0 + 8 > L + 1 && c0 < 2 * L + 1) mv = row_cols8<VEC_IN>(msrc, c0 - L - 1, 0, L, cpad_m);
+      const unsigned sd[4] = {sv.x, sv.y, sv.z, sv.w}, md[4] = {mv.x, mv.y, mv.z, mv.w};
+      unsigned e[8];
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const int c = c0 + j;
+        const unsigned se = (sd[j >> 1] >> (16 * (j & 1))) & 0xffffu, me = (md[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+        e[j] = c < L ? se : (c == L ? mk : (c < 2 * L + 1 ? me : 0u));
+      }
+      if (VEC_OUT) {
+        *reinterpret_cast<uint4*>(out + i * cpad_dst + c0) =
+            make_uint4(e[0] | (e[1] << 16), e[2] | (e[3] << 16), e[4] | (e[5] << 16), e[6] | (e[7] << 16));
+      } else {
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+          if (c0 + j < cpad_dst) out[i * cpad_dst + c0 + j] = (bf16_t)e[j];
       }
     }
   }
@@ -1027,6 +1223,70 @@ int sdt_latent_noise_target(const uint16_t* moments_nhwc, const float* eps_nhwc,
                      noise_nchw, offset, perturb_nchw, timesteps, alphas_cumprod, (bf16_t*)noisy_nhwc_bf16, target_nchw, latents_nchw,
                      noisy_nchw, B, L, H * W, moment_stride, cpad, scale, offset_mag, perturb_mag, prediction_type);
   SDT_LAUNCH_CHECK("sdt_latent_noise_target");
+  return SDT_OK;
+}
+
+int sdt_inpaint_mask_pixels(const float* pixels_nchw, const float* mask, uint16_t* stacked_nhwc_bf16, float* latent_mask, int B,
+                            int C, int H, int W, int cpad, int f, hipStream_t stream) {
+  SDT_CHECK_ARG(pixels_nchw && mask && stacked_nhwc_bf16 && latent_mask, "sdt_inpaint_mask_pixels: null pointer");
+  SDT_CHECK_ARG(f >= 1, "sdt_inpaint_mask_pixels: f=%d must be at least 1", f);
+  SDT_CHECK_ARG(B > 0 && C > 0 && H > 0 && W > 0 && cpad >= C, "sdt_inpaint_mask_pixels: bad shape B=%d C=%d H=%d W=%d cpad=%d (cpad >= C)",
+                B, C, H, W, cpad);
+  SDT_CHECK_ARG(H % f == 0 && W % f == 0, "sdt_inpaint_mask_pixels: H=%d and W=%d must be multiples of f=%d", H, W, f);
+  const bool vec = cpad % 8 == 0 && ((uintptr_t)stacked_nhwc_bf16 & 15) == 0;
+  auto kern = vec ? inpaint_mask_pixels_kernel<true> : inpaint_mask_pixels_kernel<false>;
+  hipLaunchKernelGGL(kern, dim3(sdt_grid_1d((long)B * H * W, 256)), dim3(256), 0, stream, pixels_nchw, mask,
+                     (bf16_t*)stacked_nhwc_bf16, latent_mask, B, C, H, W, cpad, f);
+  SDT_LAUNCH_CHECK("sdt_inpaint_mask_pixels");
+  return SDT_OK;
+}
+
+int sdt_inpaint_noise_target(const uint16_t* moments_nhwc, const uint16_t* masked_moments_nhwc, const float* eps_nhwc,
+                             const float* masked_eps_nhwc, const float* latent_mask, const float* noise_nchw, const float* offset,
+                             const float* perturb_nchw, const int32_t* timesteps, const float* alphas_cumprod,
+                             uint16_t* input_nhwc_bf16, float* target_nchw, float* latents_nchw, float* noisy_nchw,
+                             float* masked_latents_nchw, int B, int L, int H, int W, int moment_stride, int cpad, float scale,
+                             float offset_mag, float perturb_mag, int prediction_type, hipStream_t stream) {
+  SDT_CHECK_ARG(moments_nhwc && masked_moments_nhwc && eps_nhwc && masked_eps_nhwc && latent_mask && noise_nchw && timesteps &&
+                    alphas_cumprod && input_nhwc_bf16,
+                "sdt_inpaint_noise_target: null pointer");
+  SDT_CHECK_ARG(B > 0 && L > 0 && H > 0 && W > 0 && cpad >= 2 * L + 1 && moment_stride >= 2 * L,
+                "sdt_inpaint_noise_target: bad shape B=%d L=%d H=%d W=%d moment_stride=%d cpad=%d (cpad >= 2L+1, moment_stride >= 2L)",
+                B, L, H, W, moment_stride, cpad);
+  SDT_CHECK_ARG(prediction_type == 0 || prediction_type == 2,
+                "sdt_inpaint_noise_target: prediction_type %d (0 epsilon, 2 v_prediction)", prediction_type);
+  SDT_CHECK_ARG(offset || offset_mag == 0.f, "sdt_inpaint_noise_target: offset_mag %g needs the offset noise", offset_mag);
+  SDT_CHECK_ARG(perturb_nchw || perturb_mag == 0.f, "sdt_inpaint_noise_target: perturb_mag %g needs the perturbation noise", perturb_mag);
+  SDT_CHECK_ARG(target_nchw || (prediction_type == 0 && !offset && !perturb_nchw),
+                "sdt_inpaint_noise_target: the target may be NULL only for epsilon without offset or perturbation noise (it is the noise)");
+  const bool vin = moment_stride % 8 == 0 && (((uintptr_t)moments_nhwc | (uintptr_t)masked_moments_nhwc) & 15) == 0;
+  const bool vout = cpad % 8 == 0 && ((uintptr_t)input_nhwc_bf16 & 15) == 0;
+  auto kern = vin ? (vout ? inpaint_noise_target_kernel<true, true> : inpaint_noise_target_kernel<true, false>)
+                  : (vout ? inpaint_noise_target_kernel<false, true> : inpaint_noise_target_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(sdt_grid_1d((long)B * H * W, 256)), dim3(256), 0, stream, (const bf16_t*)moments_nhwc,
+                     (const bf16_t*)masked_moments_nhwc, eps_nhwc, masked_eps_nhwc, latent_mask, noise_nchw, offset, perturb_nchw,
+                     timesteps, alphas_cumprod, (bf16_t*)input_nhwc_bf16, target_nchw, latents_nchw, noisy_nchw, masked_latents_nchw, B,
+                     L, H * W, moment_stride, cpad, scale, offset_mag, perturb_mag, prediction_type);
+  SDT_LAUNCH_CHECK("sdt_inpaint_noise_target");
+  return SDT_OK;
+}
+
+int sdt_inpaint_pack_input(const uint16_t* latents_nhwc, const uint16_t* masked_latents_nhwc, const float* latent_mask,
+                           uint16_t* input_nhwc, int R, int B, int L, int H, int W, int cpad_src, int cpad_m, int cpad_dst,
+                           hipStream_t stream) {
+  SDT_CHECK_ARG(latents_nhwc && masked_latents_nhwc && latent_mask && input_nhwc, "sdt_inpaint_pack_input: null pointer");
+  SDT_CHECK_ARG(R > 0 && B > 0 && L > 0 && H > 0 && W > 0 && R % B == 0,
+                "sdt_inpaint_pack_input: bad shape R=%d B=%d L=%d H=%d W=%d (R a multiple of B)", R, B, L, H, W);
+  SDT_CHECK_ARG(cpad_src >= L && cpad_m >= L && cpad_dst >= 2 * L + 1,
+                "sdt_inpaint_pack_input: cpad_src=%d and cpad_m=%d must hold L=%d channels, cpad_dst=%d must hold 2L+1", cpad_src, cpad_m,
+                L, cpad_dst);
+  const bool vin = cpad_src % 8 == 0 && cpad_m % 8 == 0 && (((uintptr_t)latents_nhwc | (uintptr_t)masked_latents_nhwc) & 15) == 0;
+  const bool vout = cpad_dst % 8 == 0 && ((uintptr_t)input_nhwc & 15) == 0;
+  auto kern = vin ? (vout ? inpaint_pack_input_kernel<true, true> : inpaint_pack_input_kernel<true, false>)
+                  : (vout ? inpaint_pack_input_kernel<false, true> : inpaint_pack_input_kernel<false, false>);
+  hipLaunchKernelGGL(kern, dim3(sdt_grid_1d((long)R * H * W, 256)), dim3(256), 0, stream, (const bf16_t*)latents_nhwc,
+                     (const bf16_t*)masked_latents_nhwc, latent_mask, (bf16_t*)input_nhwc, R, B, L, H * W, cpad_src, cpad_m, cpad_dst);
+  SDT_LAUNCH_CHECK("sdt_inpaint_pack_input");
   return SDT_OK;
 }
 

@@ -14,6 +14,10 @@ Layout of a cache directory (plain numpy, nothing compressed):
                       for a batch with a loss_mask, loss_mask float32 (B,h,w): the mask pooled to the latent grid by
                       sdt_loss_mask_prepare, before the floor (the floor is applied in the step: one cache serves any floor); and
                       loss_weight float32 (B,) as the batch holds it.  A record of a batch without them is what it was before they existed.
+                      For a batch with an inpaint_mask (an inpainting UNet's, include/sdt.h "INPAINTING"): masked_latent_moments uint16
+                      (B,h,w,2L), the moments of the masked image out of the SAME stacked 2B encode the step runs
+                      (training_utils.encode_inpaint_moments: `moments` is then that encode's first half), and inpaint_mask float32
+                      (B,h,w), the nearest-neighbour 0/1 latent mask.  A record without the mask keeps its members and bytes.
 A cached SD1.5 512x512 sample is 64 KiB; its fp32 pixels are 3 MiB.
 """
 import hashlib
@@ -24,11 +28,12 @@ import numpy as np
 import torch
 
 from . import _lib, ops
-from .training_utils import encode_latent_moments, step_key
+from .training_utils import encode_inpaint_moments, encode_latent_moments, step_key
 
 FORMAT_VERSION = 1
 EXTRA_KEYS = ("input_ids", "time_ids", "text_embeds")  # what a record keeps of a batch besides the moments
 LOSS_WEIGHT_KEY, LOSS_MASK_KEY = "loss_weight", "loss_mask"  # kept too: the weight as it is, the mask pooled to the latent grid
+INPAINT_MASK_KEY, MASKED_MOMENTS_KEY = "inpaint_mask", "masked_latent_moments"  # the latent 0/1 mask and the masked image's moments
 
 
 def vae_digest(frozen_vae):
@@ -65,9 +70,10 @@ class Writer:
         os.makedirs(path, exist_ok=True)
         self.path, self.latent_channels, self.digest, self.buckets = path, int(latent_channels), str(digest), []
 
-    def add(self, moments, batch, loss_mask=None):
+    def add(self, moments, batch, loss_mask=None, inpaint=None):
         """moments: bf16 (B,h,w,2L) tensor of `batch` (any device); batch: the loader's dict, of which EXTRA_KEYS and loss_weight are
-        kept; loss_mask: the batch's mask at LATENT size, f32 (B,h,w) (pool_loss_mask), or None."""
+        kept; loss_mask: the batch's mask at LATENT size, f32 (B,h,w) (pool_loss_mask), or None; inpaint: None, or (masked-image
+        moments bf16 (B,h,w,2L), latent inpaint mask f32 (B,h,w)) as encode_inpaint_moments returns them."""
         if moments.dtype != torch.bfloat16 or moments.dim() != 4 or moments.shape[3] != 2 * self.latent_channels:
             raise ValueError(f"moments must be bfloat16 (B,h,w,{2 * self.latent_channels}), not {moments.dtype} {tuple(moments.shape)}")
         rec = {"moments": moments.detach().contiguous().cpu().view(torch.int16).numpy().view(np.uint16)}
@@ -80,6 +86,14 @@ class Writer:
                 raise ValueError(f"loss_mask must be float32 {tuple(moments.shape[:3])} (latent size), not {loss_mask.dtype} "
                                  f"{tuple(loss_mask.shape)}")
             rec[LOSS_MASK_KEY] = loss_mask.detach().contiguous().cpu().numpy()
+        if inpaint is not None:
+            mm, lm = inpaint
+            if mm.dtype != torch.bfloat16 or tuple(mm.shape) != tuple(moments.shape):
+                raise ValueError(f"masked_latent_moments must be bfloat16 {tuple(moments.shape)}, not {mm.dtype} {tuple(mm.shape)}")
+            if lm.dtype != torch.float32 or tuple(lm.shape) != tuple(moments.shape[:3]):
+                raise ValueError(f"inpaint_mask must be float32 {tuple(moments.shape[:3])} (latent size), not {lm.dtype} {tuple(lm.shape)}")
+            rec[MASKED_MOMENTS_KEY] = mm.detach().contiguous().cpu().view(torch.int16).numpy().view(np.uint16)
+            rec[INPAINT_MASK_KEY] = lm.detach().contiguous().cpu().numpy()
         if LOSS_WEIGHT_KEY in batch:
             rec[LOSS_WEIGHT_KEY] = batch[LOSS_WEIGHT_KEY].detach().to(torch.float32).contiguous().cpu().numpy()
         with open(_record_path(self.path, len(self.buckets)), "wb") as f:
@@ -114,16 +128,22 @@ def pool_loss_mask(mask, h, w):
 def build(batches, frozen_vae, path):
     """Encode every batch of `batches` (a loader with grab_next_batch, or an iterable; "end_of_batch" ends it) with the frozen VAE,
     at the shape it arrives in, into the cache directory `path`.  A batch's loss_mask is stored pooled to the latent grid, its
-    loss_weight as it is.  Returns the number of records."""
+    loss_weight as it is.  A batch with an inpaint_mask is encoded as the stack [image | masked image] of 2B the inpainting step
+    encodes, and its record gains masked_latent_moments and the latent-size inpaint_mask.  Returns the number of records."""
     w = Writer(path, frozen_vae.call["latent_channels"], vae_digest(frozen_vae))
     dev = frozen_vae.params.device
     for batch in _walk(batches):
         px = batch["pixel_values"].to(dev, torch.float32).contiguous()
-        moments = encode_latent_moments(frozen_vae, px)
+        inpaint = None
+        if INPAINT_MASK_KEY in batch:
+            moments, mm, lm = encode_inpaint_moments(frozen_vae, px, batch[INPAINT_MASK_KEY].to(dev, torch.float32).contiguous())
+            inpaint = (mm, lm)
+        else:
+            moments = encode_latent_moments(frozen_vae, px)
         pooled = None
         if LOSS_MASK_KEY in batch:
             pooled = pool_loss_mask(batch[LOSS_MASK_KEY].to(dev, torch.float32).contiguous(), moments.shape[1], moments.shape[2])
-        w.add(moments, batch, loss_mask=pooled)
+        w.add(moments, batch, loss_mask=pooled, inpaint=inpaint)
     w.close()
     return len(w.buckets)
 

@@ -77,6 +77,44 @@ def _pad8(c):
     return (c + 7) // 8 * 8
 
 
+def inpaint_latent_channels(cfg):
+    """L for an inpainting UNet - in_channels == 2 * out_channels + 1, the input [noisy latents | mask | masked-image latents]
+    (include/sdt.h "INPAINTING") - else None."""
+    cin, cout = cfg.get("in_channels"), cfg.get("out_channels")
+    if cin is None or cout is None:
+        return None
+    return int(cout) if int(cin) == 2 * int(cout) + 1 else None
+
+
+def widen_conv_in(unet_params, unet_config, in_channels):
+    """A checkpoint with more input channels, the usual way (host side): conv_in/kernel (kh,kw,cin,cout) gains zero rows up to
+    in_channels, so the widened UNet computes what the narrow one did whatever the new channels hold; every other leaf is shared.
+    unet_params: the flat {"a/b/kernel": array} tree or the nested Flax one, torch tensors or numpy arrays.  Returns (params, config)
+    copies with config["in_channels"] = in_channels.  ValueError for a target narrower than the kernel."""
+    nested = "conv_in" in unet_params and isinstance(unet_params["conv_in"], dict)
+    k = unet_params["conv_in"]["kernel"] if nested else unet_params["conv_in/kernel"]
+    cin = int(k.shape[2])
+    if cin != int(unet_config["in_channels"]):
+        raise ValueError(f"conv_in/kernel has {cin} input channels, the config says in_channels={unet_config['in_channels']}")
+    if not isinstance(in_channels, int) or in_channels < cin:
+        raise ValueError(f"widen_conv_in: in_channels={in_channels!r} is narrower than the kernel's {cin}")
+    shape = (k.shape[0], k.shape[1], in_channels, k.shape[3])
+    if torch.is_tensor(k):
+        wide = torch.zeros(shape, dtype=k.dtype)
+        wide[:, :, :cin] = k
+    else:
+        import numpy as np
+        k = np.asarray(k)
+        wide = np.zeros(shape, dtype=k.dtype)
+        wide[:, :, :cin] = k
+    params = dict(unet_params)
+    if nested:
+        params["conv_in"] = dict(unet_params["conv_in"], kernel=wide)
+    else:
+        params["conv_in/kernel"] = wide
+    return params, dict(unet_config, in_channels=in_channels)
+
+
 # ----------------------------------------------------------------------------- parameter specs (forward order)
 class _Spec(list):
     def __init__(self, *a):

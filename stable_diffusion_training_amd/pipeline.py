@@ -34,6 +34,7 @@ class StableDiffusionPipeline:
             vae_params = flatten_tree(vae_params)
         self.vae_decoder.load(vae_params)
         self.vae_decoder.prepare()
+        self.vae_params, self.vae_encoder = vae_params, None  # the encoder store is built on first use (inpainting: _inpaint_conditioning)
         # the reference's placeholder (training_utils.py:998-1004); pass a DDIMScheduler or DPMSolverMultistepScheduler built for the
         # trained schedule instead (a zero-terminal-SNR v-prediction model: timestep_spacing="trailing" or "linspace")
         self.scheduler = scheduler or DDIMScheduler(beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear",
@@ -74,14 +75,56 @@ class StableDiffusionPipeline:
         tid[:, 1::4].fill_(width)
         return ctx.detach(), {"text_embeds": pooled.detach(), "time_ids": tid}
 
+    def _inpaint_conditioning(self, image, mask, masked_eps, generator, L, height, width):
+        """The constant part of an inpainting UNet's input (include/sdt.h "INPAINTING"): the masked image (repaint ? 0 : x) encoded ONCE
+        by the frozen VAE encoder, its latents sampled by sdt_vae_posterior_sample (draw: masked_eps (B,h,w,L), else from `generator`)
+        -> (masked latents bf16 NHWC (B,h,w,pad8(L)), latent mask f32 (B,h,w))."""
+        dev = self.device
+        stream = torch.cuda.current_stream().cuda_stream
+        B, f = image.shape[0], self.vae_scale_factor
+        h, w = height // f, width // f
+        if self.vae_encoder is None:
+            enc = ParamStore(nets.vae_encoder_spec(self.vae_config), device=dev, trainable=False)
+            enc.load(self.vae_params)
+            enc.prepare()
+            self.vae_encoder = enc
+        image = image.to(device=dev, dtype=torch.float32).contiguous()
+        mask = mask.to(device=dev, dtype=torch.float32).contiguous()
+        stacked = torch.empty(2 * B, height, width, 8, dtype=torch.bfloat16, device=dev)
+        lmask = torch.empty(B, h, w, dtype=torch.float32, device=dev)
+        _lib.call("sdt_inpaint_mask_pixels", image.data_ptr(), mask.data_ptr(), stacked.data_ptr(), lmask.data_ptr(), B, image.shape[1],
+                  height, width, 8, f, stream)
+        ops.gn_arena_begin(dev)
+        moments = nets.vae_encode_moments(self.vae_encoder, self.vae_config, stacked[B:])  # the masked half only
+        ops.gn_arena_end(dev)
+        if masked_eps is None:
+            masked_eps = torch.randn(B, h, w, L, device=dev, dtype=torch.float32, generator=generator)
+        elif tuple(masked_eps.shape) != (B, h, w, L):
+            raise ValueError(f"Unexpected masked_eps shape, got {tuple(masked_eps.shape)}, expected {(B, h, w, L)}")
+        masked_eps = masked_eps.to(device=dev, dtype=torch.float32).contiguous()
+        mlat = torch.empty(B, L, h, w, dtype=torch.float32, device=dev)
+        _lib.call("sdt_vae_posterior_sample", moments.data_ptr(), masked_eps.data_ptr(), mlat.data_ptr(), B, L, h, w, moments.shape[3],
+                  self.scaling_factor, stream)
+        cpad = (L + 7) // 8 * 8
+        mlat_nhwc = torch.empty(B, h, w, cpad, dtype=torch.bfloat16, device=dev)
+        _lib.call("sdt_nchw_f32_to_nhwc_bf16", mlat.data_ptr(), mlat_nhwc.data_ptr(), B, L, h, w, cpad, stream)
+        return mlat_nhwc, lmask
+
     @torch.no_grad()
     def generate(self, prompt_ids, num_inference_steps=50, height=512, width=512, guidance_scale=7.5, latents=None,
-                 neg_prompt_ids=None, generator=None, return_latents=False, guidance_rescale=0.0):
+                 neg_prompt_ids=None, generator=None, return_latents=False, guidance_rescale=0.0, image=None, mask=None,
+                 masked_eps=None):
         """_generate (:160-254).  prompt_ids int (B,77) device tensor ((B,2,77) for an SDXL-mode text encoder: _sdxl_conditioning;
         pass scaling_factor=0.13025 for the SDXL VAE); latents optional f32 (B,C,h,w) initial noise; returns the
         image (B,H,W,3) float32 in [0,1] on the device (and the final latents when return_latents).  guidance_rescale in [0, 1]
         rescales the guided prediction (epsilon or v) per sample towards the std of the text prediction (diffusers
-        rescale_noise_cfg, arXiv:2305.08891 §3.4; 0.7 there); 0 leaves it as it is and launches nothing extra."""
+        rescale_noise_cfg, arXiv:2305.08891 §3.4; 0.7 there); 0 leaves it as it is and launches nothing extra.
+        An inpainting UNet (in_channels == 2L + 1, nets.inpaint_latent_channels) needs image f32 (B,3,H,W) in [-1, 1] and mask (B,H,W)
+        (1 = repaint, m >= 0.5): the latents have L channels, the masked image is encoded once (_inpaint_conditioning; after the
+        initial latents, its draw comes from `generator` unless masked_eps (B,h,w,L) is given) and before every UNet call
+        sdt_inpaint_pack_input assembles [latents | mask | masked-image latents] for the doubled batch from the tensor the scheduler
+        kernels write.  The untouched pixels are NOT composited back over the output.  ValueError for image / mask on a plain UNet,
+        their absence on an inpainting one, and wrong shapes."""
         if height % 8 != 0 or width % 8 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
         if not 0.0 <= guidance_rescale <= 1.0:
@@ -89,8 +132,21 @@ class StableDiffusionPipeline:
         dev = self.device
         stream = torch.cuda.current_stream().cuda_stream
         B = prompt_ids.shape[0]
-        C = self.unet_config["in_channels"]
+        L_inp = nets.inpaint_latent_channels(self.unet_config)
+        C = self.unet_config["in_channels"] if L_inp is None else L_inp
         h, w = height // self.vae_scale_factor, width // self.vae_scale_factor
+        if L_inp is None:
+            if image is not None or mask is not None or masked_eps is not None:
+                raise ValueError("image / mask / masked_eps need an inpainting UNet (in_channels == 2 * out_channels + 1); this one has "
+                                 f"in_channels={self.unet_config['in_channels']}")
+        else:
+            if image is None or mask is None:
+                raise ValueError(f"an inpainting UNet (in_channels={self.unet_config['in_channels']}) samples from an image and a mask")
+            if not torch.is_tensor(image) or tuple(image.shape) != (B, self.vae_config["in_channels"], height, width):
+                raise ValueError(f"Unexpected image shape, got {tuple(getattr(image, 'shape', ()))}, expected "
+                                 f"{(B, self.vae_config['in_channels'], height, width)}")
+            if not torch.is_tensor(mask) or tuple(mask.shape) != (B, height, width):
+                raise ValueError(f"Unexpected mask shape, got {tuple(getattr(mask, 'shape', ()))}, expected {(B, height, width)}")
         if latents is None:
             latents = torch.randn(B, C, h, w, device=dev, dtype=torch.float32, generator=generator)
         elif tuple(latents.shape) != (B, C, h, w):
@@ -113,13 +169,20 @@ class StableDiffusionPipeline:
         x_in = torch.empty(2 * B, h, w, cpad, dtype=torch.bfloat16, device=dev)
         for half in (x_in[:B], x_in[B:]):
             _lib.call("sdt_nchw_f32_to_nhwc_bf16", lat.data_ptr(), half.data_ptr(), B, C, h, w, cpad, stream)
+        x_lat = x_in  # what the scheduler kernels write: the latents' channels, doubled
+        if L_inp is not None:
+            mlat_nhwc, lmask = self._inpaint_conditioning(image, mask, masked_eps, generator, L_inp, height, width)
+            x_in = torch.empty(2 * B, h, w, (2 * C + 1 + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)
         t_dev = torch.empty(2 * B, dtype=torch.int32, device=dev)
         for t in self.scheduler.set_timesteps(num_inference_steps):
             t_dev.fill_(int(t))
+            if L_inp is not None:
+                _lib.call("sdt_inpaint_pack_input", x_lat.data_ptr(), mlat_nhwc.data_ptr(), lmask.data_ptr(), x_in.data_ptr(), 2 * B, B, C,
+                          h, w, cpad, mlat_nhwc.shape[3], x_in.shape[3], stream)
             ops.gn_arena_begin(dev)
             pred = nets.unet_forward(self.unet, self.unet_config, x_in, t_dev, context, added)
             ops.gn_arena_end(dev)
-            self.scheduler.cfg_step(pred, lat, x_in, t, guidance_scale, guidance_rescale)  # guidance + x_t -> x_{t-1} + next input
+            self.scheduler.cfg_step(pred, lat, x_lat, t, guidance_scale, guidance_rescale)  # guidance + x_t -> x_{t-1} + next input
 
         z = torch.empty(B, h, w, cpad, dtype=torch.bfloat16, device=dev)
         scaled = lat * (1.0 / self.scaling_factor)

@@ -18,7 +18,7 @@ class DataLoader:
                  maximum_resolution_areas=(512 ** 2,), bucket_lower_bound_resolutions=(256,), numb_of_worker_thread=1,
                  queue_get_timeout=60, chunk_number=0, seed=0, context_concatenation_multiplier=1, *,
                  batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu", text_towers=1,
-                 loss_masks=False, prior_every=0, prior_loss_weight=1.0):
+                 loss_masks=False, prior_every=0, prior_loss_weight=1.0, inpaint_masks=False):
         if len(maximum_resolution_areas) != len(bucket_lower_bound_resolutions):
             raise ValueError("number of elements in maximum_resolution_areas and bucket_lower_bound_resolutions is not match!")
         if training_batch_size % world_size:
@@ -34,6 +34,7 @@ class DataLoader:
         if not isinstance(prior_every, int) or prior_every < 0:
             raise ValueError(f"prior_every={prior_every!r}: 0 (no class images) or n > 0 (every n-th sample is one)")
         self.loss_masks, self.prior_every, self.prior_loss_weight = bool(loss_masks), prior_every, float(prior_loss_weight)
+        self.inpaint_masks = bool(inpaint_masks)
         self.buckets = [tuple(int(v) for v in b) for area, lo in zip(maximum_resolution_areas, bucket_lower_bound_resolutions)
                         for b in calculate_resolution_array(area, lo, 64)]
         self._batches_per_chunk = batches_per_chunk
@@ -72,7 +73,9 @@ class DataLoader:
         loss_masks=True adds loss_mask f32 (B, bucket[0], bucket[1]): one seeded rectangle of ones per image (the "subject"), zero
         outside, drawn from a generator of its own - the other entries are what they are without it.  prior_every=n > 0 marks every n-th
         sample of the global batch (global index % n == n - 1) as a class image and adds loss_weight f32 (B,): 1.0 for instance images,
-        prior_loss_weight for class images (DreamBooth prior preservation).  The defaults add neither."""
+        prior_loss_weight for class images (DreamBooth prior preservation).  inpaint_masks=True adds inpaint_mask f32 (B, bucket[0],
+        bucket[1]) for an inpainting UNet: one seeded rectangle of ones (the region to repaint) per image, from a third generator of its
+        own.  The defaults add none of them."""
         if self._cursor >= len(self._plan):
             return "end_of_batch"
         b0, b1 = self._plan[self._cursor]
@@ -97,6 +100,14 @@ class DataLoader:
                 y0, x0 = int(torch.randint(0, b0 - hh + 1, (1,), generator=gm)), int(torch.randint(0, b1 - ww + 1, (1,), generator=gm))
                 mask[i, y0: y0 + hh, x0: x0 + ww] = 1.0
             batch["loss_mask"] = mask
+        if self.inpaint_masks:
+            gi = torch.Generator().manual_seed(((int(self.seed) * 1_000_003 + int(self.chunk_number)) * 1_000_003 + index * 64 + self.rank) ^ 0x2545F4914F6CDD1D)
+            mask = torch.zeros(per_rank, b0, b1)
+            for i in range(per_rank):  # a rectangle covering between a quarter and three quarters of each axis
+                hh, ww = (int(torch.randint(n // 4, 3 * n // 4 + 1, (1,), generator=gi)) for n in (b0, b1))
+                y0, x0 = int(torch.randint(0, b0 - hh + 1, (1,), generator=gi)), int(torch.randint(0, b1 - ww + 1, (1,), generator=gi))
+                mask[i, y0: y0 + hh, x0: x0 + ww] = 1.0
+            batch["inpaint_mask"] = mask
         if self.prior_every:
             first = self.rank * per_rank  # this shard's first sample in the global batch
             batch["loss_weight"] = torch.tensor([self.prior_loss_weight if (first + i) % self.prior_every == self.prior_every - 1 else 1.0

@@ -307,6 +307,33 @@ def encode_latent_moments(frozen_vae, pixel_values):
             ops.gn_arena_end(dev)
 
 
+def encode_inpaint_moments(frozen_vae, pixel_values, inpaint_mask):
+    """The pixel front of an inpainting step: f32 NCHW (B,3,H,W) pixels and the f32 (B,H,W) repaint mask -> (moments, masked-image
+    moments, latent mask): one sdt_inpaint_mask_pixels launch writes the image and the masked image (repaint ? 0 : x) as one bf16 stack
+    of 2B rows plus the nearest-neighbour latent mask f32 (B,H/f,W/f), and ONE encoder pass over the stack gives both halves' moments,
+    bf16 (B,H/f,W/f,2L) each (contiguous views of the stacked result).  latent_cache.build stores exactly these."""
+    vae_store, vae_cfg = frozen_vae.params, frozen_vae.call
+    dev = vae_store.device
+    B, C_in, H, W = pixel_values.shape
+    f = 2 ** (len(vae_cfg["block_out_channels"]) - 1)
+    if H % f or W % f:
+        raise ValueError(f"pixel_values {tuple(pixel_values.shape)}: height and width must be multiples of the VAE's downscale {f}")
+    own_arena = not ops.gn_arena_active(dev)
+    if own_arena:
+        ops.gn_arena_begin(dev)
+    try:
+        pix = torch.empty(2 * B, H, W, 8, dtype=torch.bfloat16, device=dev)
+        lmask = torch.empty(B, H // f, W // f, dtype=torch.float32, device=dev)
+        _lib.call("sdt_inpaint_mask_pixels", pixel_values.data_ptr(), inpaint_mask.data_ptr(), pix.data_ptr(), lmask.data_ptr(), B, C_in,
+                  H, W, 8, f, torch.cuda.current_stream().cuda_stream)
+        with trace.phase("vae_encode"):
+            both = nets.vae_encode_moments(vae_store, vae_cfg, pix)
+        return both[:B], both[B:], lmask
+    finally:
+        if own_arena:
+            ops.gn_arena_end(dev)
+
+
 def step_key(batch, downscale=8):
     """The key of dp_compile_all_unique_resolution's table for a loader batch of either kind: pixel_values' shape (B,3,H,W), or
     the shape of the pixels that cached latent_moments (B,h,w,2L) were encoded from, (B,3,h*downscale,w*downscale)."""
@@ -357,9 +384,54 @@ def _check_loss_entries(batch, device, masked_loss_floor, normalize_masked_area)
             raise ValueError("loss_weight must be contiguous")
 
 
+INPAINT_KEYS = ("inpaint_mask",)  # the batch entry that selects the inpainting front of the step (include/sdt.h "INPAINTING")
+
+
+def _check_inpaint_entries(batch, unet_cfg, device):
+    """ValueError for inpaint_mask / masked_latent_moments entries that do not fit the UNet or the batch's image (which _check_batch
+    has validated).  An inpainting UNet (nets.inpaint_latent_channels) needs the mask, a plain one refuses both keys."""
+    L = nets.inpaint_latent_channels(unet_cfg)
+    mask, mm = batch.get("inpaint_mask"), batch.get("masked_latent_moments")
+    if L is None:
+        if mask is not None or mm is not None:
+            raise ValueError(f"inpaint_mask / masked_latent_moments need an inpainting UNet (in_channels == 2 * out_channels + 1); this one "
+                             f"has in_channels={unet_cfg.get('in_channels')}, out_channels={unet_cfg.get('out_channels')}")
+        return
+    if mask is None:
+        raise ValueError(f"an inpainting UNet (in_channels={unet_cfg['in_channels']} = 2 * {L} + 1) needs inpaint_mask in the batch")
+    cached = "latent_moments" in batch
+    image = batch["latent_moments"] if cached else batch["pixel_values"]
+    B = int(image.shape[0])
+    if cached:
+        want, where = (B, int(image.shape[1]), int(image.shape[2])), "latent_moments (B,h,w,2L): latent size (B,h,w)"
+    else:
+        want, where = (B, int(image.shape[2]), int(image.shape[3])), "pixel_values (B,3,H,W): pixel size (B,H,W)"
+    if not torch.is_tensor(mask) or mask.dtype != torch.float32:
+        raise ValueError(f"inpaint_mask must be a float32 tensor, not {getattr(mask, 'dtype', type(mask))}")
+    if not _on_device(mask, device):
+        raise ValueError(f"inpaint_mask lives on {mask.device}, the step runs on {device}")
+    if tuple(mask.shape) != want:
+        raise ValueError(f"inpaint_mask has shape {tuple(mask.shape)}; beside {where} = {want}")
+    if not mask.is_contiguous():
+        raise ValueError("inpaint_mask must be contiguous")
+    if cached:
+        if mm is None:
+            raise ValueError("a cached batch for an inpainting UNet needs masked_latent_moments (bf16 (B,h,w,2L)) beside latent_moments")
+        if not torch.is_tensor(mm) or mm.dtype != torch.bfloat16:
+            raise ValueError(f"masked_latent_moments must be a bfloat16 tensor, not {getattr(mm, 'dtype', type(mm))}")
+        if not _on_device(mm, device):
+            raise ValueError(f"masked_latent_moments live on {mm.device}, the step runs on {device}")
+        if tuple(mm.shape) != tuple(image.shape):
+            raise ValueError(f"masked_latent_moments have shape {tuple(mm.shape)}; latent_moments {tuple(image.shape)}")
+        if not mm.is_contiguous():
+            raise ValueError("masked_latent_moments must be contiguous")
+
+
 def _check_batch(batch, unet_cfg, frozen_vae_state, device, masked_loss_floor=0.0, normalize_masked_area=False):
     """ValueError for a batch train_step cannot run, before any kernel.  Returns whether the batch holds cached moments."""
     has_px, has_mom = "pixel_values" in batch, "latent_moments" in batch
+    if "masked_latent_moments" in batch and (has_px or not has_mom):
+        raise ValueError("masked_latent_moments go beside latent_moments (a cached inpainting batch), not beside pixel_values or alone")
     if has_px and has_mom:
         raise ValueError("a batch holds either pixel_values or latent_moments, not both")
     if not has_px and not has_mom:
@@ -367,6 +439,7 @@ def _check_batch(batch, unet_cfg, frozen_vae_state, device, masked_loss_floor=0.
     if has_px:
         if frozen_vae_state is None:
             raise ValueError("pixel_values need the frozen VAE: frozen_vae_state is None (only latent_moments train without it)")
+        _check_inpaint_entries(batch, unet_cfg, device)
         _check_loss_entries(batch, device, masked_loss_floor, normalize_masked_area)
         return False
     m = batch["latent_moments"]
@@ -379,11 +452,16 @@ def _check_batch(batch, unet_cfg, frozen_vae_state, device, masked_loss_floor=0.
         raise ValueError(f"latent_moments' last dimension holds mean | log-variance and must be even, not {m.shape[3]}")
     if not m.is_contiguous():
         raise ValueError("latent_moments must be contiguous")
-    if m.shape[3] // 2 != unet_cfg["in_channels"]:
+    Li = nets.inpaint_latent_channels(unet_cfg)
+    if Li is not None:
+        if m.shape[3] // 2 != Li:
+            raise ValueError(f"latent_moments hold {m.shape[3] // 2} latent channels, the inpainting UNet's out_channels is {Li}")
+    elif m.shape[3] // 2 != unet_cfg["in_channels"]:
         raise ValueError(f"latent_moments hold {m.shape[3] // 2} latent channels, the UNet's in_channels is {unet_cfg['in_channels']}")
     if unet_cfg.get("addition_embed_type") == "text_time" and "time_ids" not in batch:
         raise ValueError("a text_time (SDXL) UNet's default time_ids come from the pixel size, which cached latent_moments no longer "
                          "carry: the batch must hold time_ids")
+    _check_inpaint_entries(batch, unet_cfg, device)
     _check_loss_entries(batch, device, masked_loss_floor, normalize_masked_area)
     return True
 
@@ -436,6 +514,16 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     when there is a mask): min-SNR, masks, weights and normalisation act as above, metrics always holds "loss_per_sample", and aux= taps
     record the thresholds as aux["huber_c"] and a copy of d loss / d pred as aux["dpred"].  "l2" (the default) is launch for launch
     the step described above.  ValueError for an unknown type or schedule, a huber_c that is not finite and > 0, and a huber_c > 1 with the snr or exponential schedule.
+    Inpainting (include/sdt.h "INPAINTING"): a UNet with in_channels == 2L + 1 (nets.inpaint_latent_channels) reads [noisy latents | mask |
+    VAE latents of the masked image], and its batch must hold "inpaint_mask", f32 contiguous on the step's device, 1 = repaint (m >= 0.5),
+    0 = keep: (B,H,W) beside pixel_values - one sdt_inpaint_mask_pixels launch, then ONE VAE pass over the stack [image | masked image]
+    of 2B (encode_inpaint_moments) - or (B,h,w) at latent size beside latent_moments, together with "masked_latent_moments" bf16
+    (B,h,w,2L).  Either way the front is one sdt_inpaint_noise_target launch.  The masked image's posterior draw, rand
+    ["masked_posterior_eps"] (B,h,w,L), is taken from train_rng after the plain step's draws of the (micro-)batch.  Noise, timesteps,
+    target and the loss with all its options are the plain step's: the loss compares pred (L channels) with the target over the whole
+    image, and loss_mask stays independent of inpaint_mask.  aux= taps gain "inpaint_mask" (latent size, 0/1), "masked_latents" (f32
+    NCHW), "masked_moments" and "unet_input" (the bf16 tensor handed to the UNet).  ValueError for an inpainting UNet without the mask,
+    either key on a plain UNet, a wrong dtype, device, shape or layout, and masked_latent_moments without latent_moments.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
     _check_loss_type(loss_type, huber_c, huber_schedule)
     text_time = unet_state.config.get("addition_embed_type") == "text_time"
@@ -459,6 +547,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     dev = us.device
     cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev, masked_loss_floor, normalize_masked_area)
     masked = any(k in batch for k in LOSS_KEYS)
+    inpaint = "inpaint_mask" in batch  # (_check_batch: exactly the batches of an inpainting UNet)
     robust = LOSS_TYPES[loss_type]  # 0: the squared error
     image_key = "latent_moments" if cached else "pixel_values"
     stream = torch.cuda.current_stream().cuda_stream
@@ -485,24 +574,29 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         else:
             sl = slice(k * B, (k + 1) * B)
             kc = batch["input_ids"].shape[0] // N  # text-encoder rows per sample
-            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids") + LOSS_KEYS}
+            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids", "masked_latent_moments") + LOSS_KEYS + INPAINT_KEYS}
             mb["input_ids"] = batch["input_ids"][k * B * kc: (k + 1) * B * kc]
             rnd = {n: v[sl] for n, v in rand.items()}
 
         ops.gn_arena_begin(dev)  # GroupNorm statistics accumulated by producer epilogues: one memset per (micro-)batch
 
         # VAE encode -> posterior sample -> NCHW * 0.18215           (training_utils.py:574-586)
+        mmoments = lmask = None
         if cached:
-            moments = mb["latent_moments"]
+            moments, mmoments, lmask = mb["latent_moments"], mb.get("masked_latent_moments"), mb.get("inpaint_mask")
             H = W = None  # the pixel size is not known (and not needed: a text_time batch carries its time_ids)
         else:
             H, W = mb["pixel_values"].shape[2:]
-            moments = encode_latent_moments(frozen_vae_state, mb["pixel_values"])
+            if inpaint:  # the image and the masked image through the VAE as one stack of 2B
+                moments, mmoments, lmask = encode_inpaint_moments(frozen_vae_state, mb["pixel_values"], mb["inpaint_mask"])
+            else:
+                moments = encode_latent_moments(frozen_vae_state, mb["pixel_values"])
+        fused = cached or inpaint  # the front is one launch: sdt_latent_noise_target / sdt_inpaint_noise_target
         h, w = moments.shape[1], moments.shape[2]
         eps = rnd.get("posterior_eps")
         if eps is None:
             eps = torch.randn(B, h, w, L, device=dev, generator=train_rng)
-        if not cached:
+        if not fused:
             latents = torch.empty(B, L, h, w, dtype=torch.float32, device=dev)
             _lib.call("sdt_vae_posterior_sample", moments.data_ptr(), eps.data_ptr(), latents.data_ptr(), B, L, h, w,
                       moments.shape[3], vae_scale, stream)
@@ -530,26 +624,32 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             off = rnd.get("offset_noise")
             if off is None:
                 off = torch.randn(B, L, 1, 1, device=dev, generator=train_rng)
-            if not cached:
+            if not fused:
                 noise = noise + off * offset_noise_magnitude
         if perturbation_noise_magnitude:
             pn = rnd.get("perturb_noise")
             if pn is None:
                 pn = torch.randn(B, L, h, w, device=dev, generator=train_rng)
-            if not cached:
+            if not fused:
                 noise = noise + perturbation_noise_magnitude * pn
         noise = noise.contiguous()
         timesteps = rnd.get("timesteps")
         if timesteps is None:
             timesteps = torch.randint(0, sched.num_train_timesteps, (B,), device=dev, generator=train_rng)
         timesteps = timesteps.to(torch.int32).contiguous()
+        meps = mlat = None
+        if inpaint:  # the masked image's own posterior draw, after the plain step's draws so that those keep their positions
+            meps = rnd.get("masked_posterior_eps")
+            if meps is None:
+                meps = torch.randn(B, h, w, L, device=dev, generator=train_rng)
+            meps = meps.contiguous()
 
         # forward diffusion (+ v target)                              (training_utils.py:628-633, 688-701)
-        if cached:
+        if fused:
             # posterior sample, the mixing above, add_noise and the target in one launch, with the bits of the pixel path's chain
             if sched.prediction_type not in ("epsilon", "v_prediction"):
                 raise ValueError(f"Unknown prediction type {sched.prediction_type}")  # training_utils.py:697-701
-            cpad = -(-L // 8) * 8
+            cpad = -(-(2 * L + 1 if inpaint else L) // 8) * 8
             eps = eps.contiguous()
             off = None if off is None else off.contiguous()
             pn = None if pn is None else pn.contiguous()
@@ -559,11 +659,17 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             latents = torch.empty(B, L, h, w, dtype=torch.float32, device=dev) if aux is not None else None
             noisy_nchw = torch.empty(B, L, h, w, dtype=torch.float32, device=dev) if aux is not None else None
             ptr = lambda t: None if t is None else t.data_ptr()
-            _lib.call("sdt_latent_noise_target", moments.data_ptr(), eps.data_ptr(), noise.data_ptr(), ptr(off), ptr(pn),
-                      timesteps.data_ptr(), sched_state.alphas_cumprod.data_ptr(), noisy.data_ptr(), None if plain else target.data_ptr(),
-                      ptr(latents), ptr(noisy_nchw), B, L, h, w, moments.shape[3], cpad, vae_scale,
-                      offset_noise_magnitude if off is not None else 0.0, perturbation_noise_magnitude if pn is not None else 0.0,
-                      _PTYPE[sched.prediction_type], stream)
+            tail = (B, L, h, w, moments.shape[3], cpad, vae_scale, offset_noise_magnitude if off is not None else 0.0,
+                    perturbation_noise_magnitude if pn is not None else 0.0, _PTYPE[sched.prediction_type], stream)
+            if inpaint:  # the same front plus the mask and masked-image latent channels of the UNet input (`noisy` is that input)
+                mlat = torch.empty(B, L, h, w, dtype=torch.float32, device=dev) if aux is not None else None
+                _lib.call("sdt_inpaint_noise_target", moments.data_ptr(), mmoments.data_ptr(), eps.data_ptr(), meps.data_ptr(),
+                          lmask.data_ptr(), noise.data_ptr(), ptr(off), ptr(pn), timesteps.data_ptr(), sched_state.alphas_cumprod.data_ptr(),
+                          noisy.data_ptr(), None if plain else target.data_ptr(), ptr(latents), ptr(noisy_nchw), ptr(mlat), *tail)
+            else:
+                _lib.call("sdt_latent_noise_target", moments.data_ptr(), eps.data_ptr(), noise.data_ptr(), ptr(off), ptr(pn),
+                          timesteps.data_ptr(), sched_state.alphas_cumprod.data_ptr(), noisy.data_ptr(), None if plain else target.data_ptr(),
+                          ptr(latents), ptr(noisy_nchw), *tail)
         else:
             noisy, target, noisy_nchw = sched.add_noise_and_target(sched_state, latents, noise, timesteps, cpad=8,
                                                                    want_noisy_nchw=aux is not None)
@@ -639,6 +745,9 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             aux.update(latents=latents, noisy=noisy_nchw, ctx=ctx.detach(), pred=pred.detach(), target=target, moments=moments)
             if pooled is not None:
                 aux["text_embeds"] = pooled.detach()
+            if inpaint:
+                aux.update(inpaint_mask=(lmask >= 0.5).to(torch.float32), masked_latents=mlat, unet_input=noisy.detach(),
+                           masked_moments=mmoments)
 
         # reverse mode through UNet and text encoder                  (training_utils.py:719-729)
         if fused_norm:
@@ -733,7 +842,7 @@ class _GraphedStep:
 
     def __init__(self, fn, warmup=2, reducer=None):
         self.fn, self.warmup, self.calls = fn, warmup, 0
-        self.graph = self.static = self.static_rand = self.out = self.sig = self.loss_keys = None
+        self.graph = self.static = self.static_rand = self.out = self.sig = self.loss_keys = self.inpaint_keys = None
         # multi-rank: graph A (forward + backward) | eager bucketed all-reduce behind per-bucket events | graph B (optimizer)
         self.reducer = reducer if (reducer is not None and reducer.active) else None
         self.graph_b = self.plan = None
@@ -744,6 +853,7 @@ class _GraphedStep:
         self.static_rand = None if rand is None else {k: v.clone() for k, v in rand.items()}
         self.sig = self._sig(us, ts, ue, te, rng, vae, sched, rand)
         self.loss_keys = tuple(k in batch for k in LOSS_KEYS)
+        self.inpaint_keys = tuple(k in batch for k in INPAINT_KEYS)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         if rng is not None and hasattr(g, "register_generator_state"):
@@ -831,6 +941,9 @@ class _GraphedStep:
             had = [k for k, on in zip(LOSS_KEYS, self.loss_keys) if on] or "neither"
             raise ValueError(f"this step was captured with {had} of {list(LOSS_KEYS)} in its batch and replays those launches: a batch that "
                              "adds or drops one of them needs a step table of its own")
+        if self.inpaint_keys != tuple(k in batch for k in INPAINT_KEYS):
+            raise ValueError(f"this step was captured {'with' if self.inpaint_keys[0] else 'without'} inpaint_mask in its batch and replays "
+                             "those launches: a batch that adds or drops it needs a step table of its own")
         for k, v in self.static.items():
             v.copy_(batch[k], non_blocking=True)
         if rand is not None:
@@ -866,7 +979,8 @@ def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_pa
     step_overrides: keyword options of train_step that TrainingConfig has no field for, e.g. vae_scale, or masked_loss_floor /
     normalize_masked_area for batches with a loss_mask, or loss_type / huber_c / huber_schedule.  A captured step replays the launches
     of the batch it was captured with: it
-    raises ValueError for a later batch that adds or drops loss_mask / loss_weight."""
+    raises ValueError for a later batch that adds or drops loss_mask / loss_weight, or inpaint_mask (an inpainting UNet's batches
+    always carry it; the static buffers take the mask and, for cached batches, masked_latent_moments like any other tensor key)."""
     import os
     B = per_device_batch or training_config.batch_size
     if not isinstance(micro_batches, int) or micro_batches < 1:
