@@ -22,7 +22,12 @@ class image whose loss counts W times (DreamBooth prior preservation).  A latent
 and --huber-schedule snr | exponential | constant ("huber_schedule", default snr) for the threshold of each sample's timestep.
 --inpaint ("inpaint": true) trains an inpainting UNet: a UNet that is not one already (in_channels != 2 * out_channels + 1) is widened
 with zero conv_in rows (nets.widen_conv_in), the loader emits an inpaint_mask per image, and every step feeds [noisy latents | mask |
-latents of the masked image].  With --cache-latents the cache keeps the masked image's moments and the latent mask."""
+latents of the masked image].  With --cache-latents the cache keeps the masked image's moments and the latent mask.
+--new-tokens N [--init-token ID] [--retract] ("new_tokens", "new_tokens_init_id", "new_tokens_retract"): textual inversion - N placeholder
+tokens are trained on the frozen text encoder (tokens.TokenConfig; rows copied from token ID, else seeded noise at the table's scale;
+--retract rescales them towards the table's standard deviation after every step), the loader puts their ids after BOS in every caption,
+the text encoder's rate / optimizer / EMA settings configure the token store, and the saves hold the resized text encoder plus
+<model>-tokens.npz.  Alone the UNet stays frozen; with --lora RANK the UNet's adapter trains beside the tokens (pivotal tuning)."""
 import argparse
 import json
 import os
@@ -34,7 +39,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
 import torch.distributed as dist
 
-from stable_diffusion_training_amd import dp, latent_cache, lora, nets
+from stable_diffusion_training_amd import dp, latent_cache, lora, nets, tokens
 from stable_diffusion_training_amd import training_utils as tu
 from stable_diffusion_training_amd.checkpoint import gather_rng_states
 from stable_diffusion_training_amd.streamer import DataLoader
@@ -64,6 +69,8 @@ def schedule_kwargs(config_dict):
 
 def current_lr(state):
     """The learning rate of the store's last optimizer step (the schedule's value, or the constant rate)."""
+    if state.opt_store is None:  # a frozen model (the UNet of a tokens-only run)
+        return 0.0
     sched = state.opt_store.schedule
     return sched[0].rate(max(state.step - 1, 0)) if sched else state.hyper["lr"]
 
@@ -111,6 +118,15 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     if config_dict.get("loss_type", "l2") != "l2":
         loss_overrides.update(loss_type=config_dict["loss_type"], huber_c=float(config_dict.get("huber_c", 0.1)),
                               huber_schedule=config_dict.get("huber_schedule", "snr"))
+    token_cfg = None
+    if config_dict.get("new_tokens"):  # textual inversion: placeholder j is id vocab + j of every tower
+        if world > 1:
+            raise ValueError("new_tokens: token training runs on one GPU (train_step refuses a reducer with new tokens)")
+        init = config_dict.get("new_tokens_init_id")
+        token_cfg = tokens.TokenConfig(int(config_dict["new_tokens"]), init_ids=None if init is None else int(init),
+                                       seed=int(config_dict["master_seed"]), retract=bool(config_dict.get("new_tokens_retract", False)))
+        towers = te_cfg["towers"] if "towers" in te_cfg else [te_cfg]
+        loss_loader_kw["placeholder_ids"] = [[t["vocab_size"] + j for j in range(token_cfg.num_tokens)] for t in towers][: 2 if sdxl else 1]
     dataloader = DataLoader(
         tokenizer_obj=tokenizer, config=None, ramdisk_path=config_dict.get("ramdisk_path"),
         training_batch_size=config_dict["batch_size"], repeat_batch=config_dict["repeat_batch"],
@@ -136,7 +152,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     train_rngs.manual_seed(config_dict["master_seed"] * 1009 + rank)  # different noise / timesteps on every shard
     (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers,
      model_object_dict) = tu.on_device_model_training_state(training_config, models, device=dev, optimizer=config_dict.get("optimizer", "lion"),
-                                                           **schedule_kwargs(config_dict), lora=lora_cfg)
+                                                           **schedule_kwargs(config_dict), lora=lora_cfg, new_tokens=token_cfg)
     reducer = dp.GradReducer([unet_state.store, text_encoder_state.store]) if world > 1 else None
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
@@ -222,7 +238,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
                 train_metrics = []
                 if rank == 0:
                     opt_store = unet_state.opt_store  # Prodigy: lr multiplies the estimated d, which is worth a look beside the loss
-                    d = f', unet d {float(opt_store.prodigy_d().item()):.4e}' if opt_store.optimizer == "prodigy" else ""
+                    d = f', unet d {float(opt_store.prodigy_d().item()):.4e}' if opt_store is not None and opt_store.optimizer == "prodigy" else ""
                     log(f'at steps {count}, avg loss for {config_dict["loss_logging_interval"]} steps: {loss}, took {elapsed} second(s), '
                         f'unet lr {current_lr(unet_state):.4e}{d}')
                     with open(config_dict["loss_csv"], "a") as f:
@@ -238,6 +254,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
             tu.save_training_state(state_path, unet_state, text_encoder_state, rng_states=rng_states)
             if unet_state.adapter is not None:  # the adapter alone (the saves above hold the base with the adapter folded in)
                 unet_state.adapter.save(config_dict["model_path"].split("@")[0] + "-lora.npz")
+            if text_encoder_state.tokens is not None:  # the trained rows alone (the saves above hold the resized text encoder)
+                text_encoder_state.tokens.save(config_dict["model_path"].split("@")[0] + "-tokens.npz")
         config_dict["model_path"] = f'{config_dict["model_path"].split("@")[0]}@{config_dict["chunk_steps"]}'  # training.py:301-304
         config_dict["chunk_number"] += 1
         config_dict["chunk_steps"] += 1
@@ -259,6 +277,10 @@ if __name__ == "__main__":
                     help="train rank-RANK LoRA adapters on the UNet's attention projections (frozen base and text encoder) instead of every weight")
     ap.add_argument("--dora", action="store_true",
                     help="with --lora: DoRA - also train a per-output-feature magnitude of every adapted kernel (weight-decomposed LoRA)")
+    ap.add_argument("--new-tokens", metavar="N", type=int, default=None,
+                    help="textual inversion: train N placeholder-token embeddings on the frozen text encoder (alone, or beside --lora)")
+    ap.add_argument("--init-token", metavar="ID", type=int, default=None, help="with --new-tokens: start every new row as a copy of token ID")
+    ap.add_argument("--retract", action="store_true", help="with --new-tokens: rescale the rows towards the table's std after every step")
     ap.add_argument("--masked-loss", metavar="FLOOR", type=float, nargs="?", const=0.0, default=None,
                     help="train with a loss mask per image; FLOOR in [0, 1] is the least weight of a position outside the mask (default 0)")
     ap.add_argument("--normalize-masked-area", action="store_true", default=None,
@@ -275,6 +297,8 @@ if __name__ == "__main__":
     args = ap.parse_args()
     if args.dora and args.lora is None:
         ap.error("--dora needs --lora RANK")
+    if (args.init_token is not None or args.retract) and args.new_tokens is None:
+        ap.error("--init-token / --retract need --new-tokens N")
     with open(args.config) as f:
         cfg = json.load(f)
     if args.micro_batches is not None:
@@ -285,6 +309,12 @@ if __name__ == "__main__":
         cfg["lora_rank"] = args.lora
     if args.dora:
         cfg["lora_dora"] = True
+    if args.new_tokens is not None:
+        cfg["new_tokens"] = args.new_tokens
+    if args.init_token is not None:
+        cfg["new_tokens_init_id"] = args.init_token
+    if args.retract:
+        cfg["new_tokens_retract"] = True
     if args.cache_latents is not None:
         cfg["cache_latents"] = args.cache_latents
     if args.masked_loss is not None:

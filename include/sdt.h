@@ -549,6 +549,34 @@ int sdt_embedding_fwd(const int32_t* ids, const float* tok, const float* pos, ui
 int sdt_embedding_bwd(const int32_t* ids, const uint16_t* dout, float* dtok, float* dpos, int64_t rows, int S, int D,
                       hipStream_t stream);
 
+/* ---- NEW TOKENS: textual inversion (no reference counterpart; DESIGN.md "New tokens") ----
+ * The frozen token table tok f32 (V, D) is continued by n_ext (1..256) trained rows ext f32 (n_ext, D): placeholder j is id V + j.
+ * All three calls: no atomics, one writer per element, one fixed summation order, never a read outside a buffer.  Refused with
+ * SDT_ERR_INVALID_ARG before any HIP call: a null pointer or one not aligned to its element, rows / S / D / V <= 0, n_ext outside
+ * 1..256.
+ *
+ * Forward.  out[r][c] = bf16_rne(fl32(t[c] + pos[r % S][c])), one fp32 add rounded once to bf16, with
+ *   t = tok[id]      for 0 <= id < V          (the bits of sdt_embedding_fwd)
+ *   t = ext[id - V]  for V <= id < V + n_ext
+ *   t = +0.0         for every other id, negatives included: no table is read (a bad id must not fault)
+ * pos f32 (S, D).  D % 4 == 0 with tok / ext / pos 16-byte and out 8-byte aligned: 16-byte table loads and 8-byte stores; otherwise
+ * a column per lane.  Both paths give the same bits. */
+int sdt_embedding_ext_fwd(const int32_t* ids, const float* tok, const float* ext, const float* pos, uint16_t* out, int64_t rows, int S,
+                          int D, int V, int n_ext, hipStream_t stream);
+/* dext[j][c] = the fp32 sum, started at +0 and taken in increasing r with one rounding per add, of bf2f(dout[r][c]) over the rows
+ * with ids[r] == V + j; WRITTEN, not accumulated: a token no row carries gets +0.0 and the destination needs no zero fill.  One
+ * workgroup per (token, 256-column slice).  No gradient for tok or pos. */
+int sdt_embedding_ext_bwd(const int32_t* ids, const uint16_t* dout, float* dext, int64_t rows, int D, int V, int n_ext,
+                          hipStream_t stream);
+/* diffusers' advanced DreamBooth-LoRA retract_embeddings over all n = n_ext * D values of ext, in place, by one workgroup of 256:
+ *   mean   = (sum x) / n               double; thread t adds elements t, t + 256, ... in increasing order, then a block tree
+ *                                      (stride 128, 64, ..., 1: partial[t] += partial[t + stride])
+ *   std    = sqrt(sum (x - mean)^2 / (n - 1))   double, a second pass in the same order; 0 when n == 1
+ *   factor = (float) pow(target_std / std, power), the pow in double rounded once to fp32; 1.0f when std == 0
+ *   ext[i] = fl32(ext[i] * factor)     one fp32 multiply
+ * stats receives {mean, std, (double) factor}.  Also refused: target_std not finite or <= 0, power not finite. */
+int sdt_embedding_retract(float* ext, int n_ext, int D, double target_std, double power, double* stats, hipStream_t stream);
+
 /* ---- LoRA: low-rank adapters in weight space (no reference counterpart; DESIGN.md "LoRA") ----
  * An adapted Dense kernel W0 [K][N] (fp32 master of a frozen store) carries A [K][r] and B [r][N] (fp32 leaves of the adapter's
  * own store).  Before a step the merge writes the bf16 mirror W = RNE(W0 + s * A * B) the GEMMs read; after its backward the

@@ -130,6 +130,9 @@ SIGNATURES = {
     "sdt_dora_project": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "sdt_embedding_fwd": [_P, _P, _P, _P, _L, _I, _I, _P],
     "sdt_embedding_bwd": [_P, _P, _P, _P, _L, _I, _I, _P],
+    "sdt_embedding_ext_fwd": [_P, _P, _P, _P, _P, _L, _I, _I, _I, _I, _P],
+    "sdt_embedding_ext_bwd": [_P, _P, _P, _L, _I, _I, _I, _P],
+    "sdt_embedding_retract": [_P, _I, _I, _D, _D, _P, _P],
     "sdt_ff_geglu_fwd": [_P, _P, _P, _P, _P, _L, _I, _I, _P],
     "sdt_ff_geglu_supported": [_L, _I, _I],
     "sdt_conv_halo_set_tile_width": [_I],  # test hook: returns the previous width

@@ -185,8 +185,12 @@ def params_to_tree(params):
         flat = flatten_tree(params.full_tree)  # frozen VAE: the device store holds the encoder half only
     elif isinstance(params, EmaView) and getattr(params.store, "lora_of", None) is not None:
         flat = params.store.lora_of.folded(source="ema")  # the EMA of a LoRA adapter, folded into its frozen base
+    elif isinstance(params, EmaView) and getattr(params.store, "tokens_of", None) is not None:
+        flat = params.store.tokens_of.resized_tree("ema")  # the EMA of the new tokens behind the frozen base's token table
     elif isinstance(params, EmaView):
         flat = params.store.export_host("ema")
+    elif isinstance(params, ParamStore) and getattr(params, "tokens", None) is not None:
+        flat = params.tokens.resized_tree("master")  # a frozen text encoder with its new tokens: the (V + n)-row table
     elif isinstance(params, ParamStore) and getattr(params, "adapter", None) is not None:
         flat = params.adapter.folded()  # a frozen base with its LoRA adapter folded in: an ordinary checkpoint
     elif isinstance(params, ParamStore):
@@ -240,11 +244,32 @@ def _model_config(model_object_dict, key):
     return dict(getattr(m, "config"))
 
 
+def _tokens_of(params):
+    """The tokens.TokenAdapter behind what save_model was handed as text_encoder_params (a TrainState, its frozen store, or the EmaView
+    of the token store), or None."""
+    if isinstance(params, EmaView):
+        return getattr(params.store, "tokens_of", None)
+    store = params.store if hasattr(params, "store") and isinstance(params.store, ParamStore) else params
+    return getattr(store, "tokens", None) if isinstance(store, ParamStore) else None
+
+
+def _resized_text_config(te_cfg, tk):
+    """The text-encoder config with vocab_size = V + n, as after transformers' resize_token_embeddings (every tower of a two-tower one),
+    and num_new_tokens = n: the tokenizer's special ids stay where they were, below the new rows (pipeline._uncond_ids)."""
+    n = tk.num_tokens
+    grow = lambda t: dict(t, vocab_size=t["vocab_size"] + n, num_new_tokens=t.get("num_new_tokens", 0) + n)
+    if "towers" in te_cfg:
+        return dict(te_cfg, towers=[grow(t) for t in te_cfg["towers"]])
+    return grow(te_cfg)
+
+
 # ----------------------------------------------------------------------------- the reference's two entry points
 def save_model(model_object_dict, tokenizer_object, unet_params, text_encoder_params, vae_params, output_dir):
     """training_utils.py:986-1025: write a FlaxStableDiffusionPipeline directory (a FlaxStableDiffusionXLPipeline one when the text
     encoder has two towers: _save_sdxl).  The scheduler entry is the reference's hard-coded DDIM placeholder (scaled_linear,
-    v_prediction, :998-1004), whatever the run trained with."""
+    v_prediction, :998-1004), whatever the run trained with.
+    A text encoder that carries new tokens (tokens.attach) is written resized: its token table holds the V base rows followed by the n
+    trained ones and its config's vocab_size is V + n, so the directory loads into a plain store of this project."""
     os.makedirs(output_dir, exist_ok=True)
     dv = {"_diffusers_version": DIFFUSERS_VERSION}
     _write_submodel(output_dir, "unet", _model_config(model_object_dict, "unet"),
@@ -252,6 +277,9 @@ def save_model(model_object_dict, tokenizer_object, unet_params, text_encoder_pa
     _write_submodel(output_dir, "vae", _model_config(model_object_dict, "vae"),
                     {"_class_name": "FlaxAutoencoderKL", **dv}, UNET_WEIGHTS, vae_params)
     te_cfg = _model_config(model_object_dict, "text_encoder")
+    tk = _tokens_of(text_encoder_params)
+    if tk is not None:
+        te_cfg = _resized_text_config(te_cfg, tk)
     if "towers" not in te_cfg:
         _write_submodel(output_dir, "text_encoder", te_cfg,
                         {"architectures": ["CLIPTextModel"], "model_type": "clip_text_model"}, CLIP_WEIGHTS, text_encoder_params)
@@ -402,7 +430,20 @@ def _stepping_store(st):
     ad = getattr(st, "adapter", None)
     if ad is not None:
         return ad.store, ad
+    tk = getattr(st, "tokens", None)
+    if tk is not None:  # new tokens: the token store (the frozen text encoder under it is not written)
+        return tk.store, None
     return (store if getattr(store, "trainable", True) else None), None
+
+
+def _tokens_meta(st):
+    """The new-token settings a training-state file carries for a state (None without tokens)."""
+    tk = getattr(st, "tokens", None)
+    if tk is None:
+        return None
+    c = tk.cfg
+    return (f"num_tokens={c.num_tokens};geometry={','.join(f'{V}x{D}' for V, D in tk.geometry)};retract={int(c.retract)};"
+            f"retract_power={float(c.retract_power)!r}")
 
 
 def _lora_meta(ad):
@@ -423,6 +464,8 @@ def save_training_state(path, unet_state, text_encoder_state, train_rng=None, rn
             continue
         if ad is not None:  # LoRA: the adapter store's master, moments, EMA and count
             meta[f"{name}.lora"] = _lora_meta(ad)
+        if _tokens_meta(st) is not None:  # new tokens: the token store's master, moments, EMA and count
+            meta[f"{name}.tokens"] = _tokens_meta(st)
         store._gather()  # sharded optimizer: raises unless GradReducer.gather_state() (collective, all ranks) made the state whole
         for b in _state_buffers(store):
             t = getattr(store, b)
@@ -479,6 +522,9 @@ def load_training_state(path, unet_state, text_encoder_state, train_rng=None, ra
             if meta.get(f"{name}.lora") != (None if ad is None else _lora_meta(ad)):
                 raise ValueError(f"{path}: {name} state was saved with LoRA settings {meta.get(f'{name}.lora')!r}, this state has "
                                  f"{None if ad is None else _lora_meta(ad)!r}")
+            if meta.get(f"{name}.tokens") != _tokens_meta(st):
+                raise ValueError(f"{path}: {name} state was saved with new-token settings {meta.get(f'{name}.tokens')!r}, this state has "
+                                 f"{_tokens_meta(st)!r}")
             saved_opt, opt = meta.get(f"{name}.optimizer", optimizers.FILE_DEFAULT), store.optimizer
             if saved_opt != opt:
                 raise ValueError(f"{path}: {name} state was saved by the {saved_opt} optimizer and this state is built for {opt}: their "

@@ -1011,6 +1011,92 @@ __global__ void __launch_bounds__(256) embedding_bwd_kernel(const int* __restric
   }
 }
 
+// ---- new tokens (textual inversion; include/sdt.h "NEW TOKENS"): the token table continued by a few trained rows `ext`
+// The row an id selects: tok[id] for 0 <= id < V, ext[id - V] for V <= id < V + n_ext, nullptr (a row of +0.0) for every other
+// id - nothing is ever read outside the two tables.
+__device__ __forceinline__ const float* embedding_ext_row(int id, const float* tok, const float* ext, int D, int V, int n_ext) {
+  if (id >= 0 && id < V) return tok + (long)id * D;
+  const long e = (long)id - V;
+  if (e >= 0 && e < n_ext) return ext + e * D;
+  return nullptr;
+}
+// VEC: 4 columns per lane - 16-byte table loads, one 8-byte store (D % 4 == 0, bases aligned: the host decides); else a column per lane.
+template <bool VEC>
+__global__ void __launch_bounds__(256) embedding_ext_fwd_kernel(const int* __restrict__ ids, const float* __restrict__ tok,
+                                                                const float* __restrict__ ext, const float* __restrict__ pos,
+                                                                bf16_t* __restrict__ out, long rows, int S, int D, int V, int n_ext) {
+  if (VEC) {
+    const int dv = D >> 2;
+    const long total = rows * dv;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const long r = i / dv;
+      const int c = (int)(i % dv) << 2;
+      const float* t = embedding_ext_row(ids[r], tok, ext, D, V, n_ext);
+      const float4 a = t ? *reinterpret_cast<const float4*>(t + c) : make_float4(0.f, 0.f, 0.f, 0.f);
+      const float4 p = *reinterpret_cast<const float4*>(pos + (long)(r % S) * D + c);
+      uint2 o;
+      o.x = (unsigned)f2bf(a.x + p.x) | ((unsigned)f2bf(a.y + p.y) << 16);
+      o.y = (unsigned)f2bf(a.z + p.z) | ((unsigned)f2bf(a.w + p.w) << 16);
+      *reinterpret_cast<uint2*>(out + r * D + c) = o;
+    }
+  } else {
+    const long total = rows * D;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+      const long r = i / D;
+      const int c = (int)(i % D);
+      const float* t = embedding_ext_row(ids[r], tok, ext, D, V, n_ext);
+      out[i] = f2bf((t ? t[c] : 0.f) + pos[(long)(r % S) * D + c]);
+    }
+  }
+}
+// Workgroup (j, y) owns columns [256 y, 256 y + 256) of new token j: every lane walks the rows in increasing order - ids[r] is the same
+// address for the whole wave (a uniform load) - and adds the rows that carry id V + j to a sum that starts at +0; the sum is written.
+__global__ void __launch_bounds__(256) embedding_ext_bwd_kernel(const int* __restrict__ ids, const bf16_t* __restrict__ dout,
+                                                                float* __restrict__ dext, long rows, int D, int V) {
+  const int j = blockIdx.x;
+  const int c = blockIdx.y * 256 + threadIdx.x;
+  const long want = (long)V + j;
+  if (c >= D) return;
+  float g = 0.f;
+  for (long r = 0; r < rows; ++r)
+    if ((long)ids[r] == want) g += bf2f(dout[r * D + c]);
+  dext[(long)j * D + c] = g;
+}
+// One workgroup: mean and unbiased standard deviation of the n values in double, two passes, thread t owns t, t + 256, ... in
+// increasing order, then a block tree (256 -> 1, stride halving); every element is then scaled by the fp32 factor.
+__device__ __forceinline__ double block_tree_sum_256(double v, double* sm) {
+  const int t = threadIdx.x;
+  __syncthreads();  // (sm may still be read from the previous sum)
+  sm[t] = v;
+  __syncthreads();
+  for (int s = 128; s > 0; s >>= 1) {
+    if (t < s) sm[t] += sm[t + s];
+    __syncthreads();
+  }
+  return sm[0];
+}
+__global__ void __launch_bounds__(256) embedding_retract_kernel(float* __restrict__ ext, long n, double target_std, double power,
+                                                                double* __restrict__ stats) {
+  __shared__ double sm[256];
+  double s = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) s += (double)ext[i];
+  const double mean = block_tree_sum_256(s, sm) / (double)n;
+  double q = 0.0;
+  for (long i = threadIdx.x; i < n; i += 256) {
+    const double d = (double)ext[i] - mean;
+    q += d * d;
+  }
+  const double ss = block_tree_sum_256(q, sm);
+  const double sd = n > 1 ? sqrt(ss / (double)(n - 1)) : 0.0;
+  const float factor = sd == 0.0 ? 1.0f : (float)pow(target_std / sd, power);
+  for (long i = threadIdx.x; i < n; i += 256) ext[i] = ext[i] * factor;
+  if (threadIdx.x == 0) {
+    stats[0] = mean;
+    stats[1] = sd;
+    stats[2] = (double)factor;
+  }
+}
+
 // column sums: out[b][n] (+)= sum over the rows of batch slice b of dy[m][n].  Workgroup (x, y, z) sums rows_per_block rows of 256
 // columns of slice z into its own partial row; the workgroup that arrives last at (x, z) adds the partial rows in y order (no
 // float atomics) and writes the result: += into the fp32 db, or rounded into the bf16 out_bf (the per-image row-bias gradient).
@@ -1592,6 +1678,48 @@ int sdt_embedding_bwd(const int32_t* ids, const uint16_t* dout, float* dtok, flo
   hipLaunchKernelGGL(embedding_bwd_kernel, dim3((unsigned)(rows + S)), dim3(256), 0, stream, ids,
                      (const bf16_t*)dout, dtok, dpos, (long)rows, S, D);
   SDT_LAUNCH_CHECK("sdt_embedding_bwd");
+  return SDT_OK;
+}
+
+static inline bool sdt_aligned(const void* p, uintptr_t a) { return p && ((uintptr_t)p & (a - 1)) == 0; }
+
+int sdt_embedding_ext_fwd(const int32_t* ids, const float* tok, const float* ext, const float* pos, uint16_t* out, int64_t rows, int S,
+                          int D, int V, int n_ext, hipStream_t stream) {
+  SDT_CHECK_ARG(sdt_aligned(ids, 4) && sdt_aligned(tok, 4) && sdt_aligned(ext, 4) && sdt_aligned(pos, 4) && sdt_aligned(out, 2),
+                "sdt_embedding_ext_fwd: null or misaligned pointer");
+  SDT_CHECK_ARG(rows > 0 && S > 0 && D > 0 && V > 0, "sdt_embedding_ext_fwd: rows=%ld S=%d D=%d V=%d must be positive", (long)rows, S, D, V);
+  SDT_CHECK_ARG(n_ext >= 1 && n_ext <= 256, "sdt_embedding_ext_fwd: n_ext=%d outside 1..256", n_ext);
+  const bool vec = D % 4 == 0 && sdt_aligned(tok, 16) && sdt_aligned(ext, 16) && sdt_aligned(pos, 16) && sdt_aligned(out, 8);
+  if (vec)
+    hipLaunchKernelGGL(embedding_ext_fwd_kernel<true>, dim3(sdt_grid_1d(rows * (D / 4), 256)), dim3(256), 0, stream, ids, tok, ext, pos,
+                       (bf16_t*)out, (long)rows, S, D, V, n_ext);
+  else
+    hipLaunchKernelGGL(embedding_ext_fwd_kernel<false>, dim3(sdt_grid_1d(rows * D, 256)), dim3(256), 0, stream, ids, tok, ext, pos,
+                       (bf16_t*)out, (long)rows, S, D, V, n_ext);
+  SDT_LAUNCH_CHECK("sdt_embedding_ext_fwd");
+  return SDT_OK;
+}
+
+int sdt_embedding_ext_bwd(const int32_t* ids, const uint16_t* dout, float* dext, int64_t rows, int D, int V, int n_ext,
+                          hipStream_t stream) {
+  SDT_CHECK_ARG(sdt_aligned(ids, 4) && sdt_aligned(dout, 2) && sdt_aligned(dext, 4), "sdt_embedding_ext_bwd: null or misaligned pointer");
+  SDT_CHECK_ARG(rows > 0 && D > 0 && V > 0, "sdt_embedding_ext_bwd: rows=%ld D=%d V=%d must be positive", (long)rows, D, V);
+  SDT_CHECK_ARG(n_ext >= 1 && n_ext <= 256, "sdt_embedding_ext_bwd: n_ext=%d outside 1..256", n_ext);
+  SDT_CHECK_ARG((D + 255) / 256 <= 65535, "sdt_embedding_ext_bwd: D=%d too wide", D);
+  hipLaunchKernelGGL(embedding_ext_bwd_kernel, dim3(n_ext, (D + 255) / 256), dim3(256), 0, stream, ids, (const bf16_t*)dout, dext,
+                     (long)rows, D, V);
+  SDT_LAUNCH_CHECK("sdt_embedding_ext_bwd");
+  return SDT_OK;
+}
+
+int sdt_embedding_retract(float* ext, int n_ext, int D, double target_std, double power, double* stats, hipStream_t stream) {
+  SDT_CHECK_ARG(sdt_aligned(ext, 4) && sdt_aligned(stats, 8), "sdt_embedding_retract: null or misaligned pointer");
+  SDT_CHECK_ARG(D > 0, "sdt_embedding_retract: D=%d must be positive", D);
+  SDT_CHECK_ARG(n_ext >= 1 && n_ext <= 256, "sdt_embedding_retract: n_ext=%d outside 1..256", n_ext);
+  SDT_CHECK_ARG(target_std > 0.0 && target_std <= 3.4e38 && power == power && power >= -1e6 && power <= 1e6,
+                "sdt_embedding_retract: target_std=%g must be finite and > 0, power=%g finite", target_std, power);
+  hipLaunchKernelGGL(embedding_retract_kernel, dim3(1), dim3(256), 0, stream, ext, (long)n_ext * D, target_std, power, stats);
+  SDT_LAUNCH_CHECK("sdt_embedding_retract");
   return SDT_OK;
 }
 

@@ -120,6 +120,8 @@ class LoraAdapter:
             raise ValueError("LoRA: the base store must be frozen (ParamStore(trainable=False)); a trained store takes no adapter")
         if getattr(base, "adapter", None) is not None:
             raise ValueError("LoRA: the store already carries an adapter")
+        if getattr(base, "tokens", None) is not None:
+            raise ValueError("LoRA: the store carries new tokens (tokens.attach); a text-encoder LoRA together with new tokens is not supported")
         self.base, self.cfg, self.source = base, cfg, "master"
         base_spec = [(p, base.leaves[p].shape) for p in base.order]
         self.paths = select_leaves(base_spec, cfg)

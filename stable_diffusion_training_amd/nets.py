@@ -648,8 +648,10 @@ def _clip_encoder(st, cfg, input_ids, anchor, prefix, n_layers, tap=None):
     Bk, S = input_ids.shape
     d, heads, eps = cfg["hidden_size"], cfg["num_attention_heads"], cfg["layer_norm_eps"]
     if anchor is None:
-        # (a frozen tower that carries a LoRA adapter still needs its backward: the adapted leaves' weight gradients come from it)
-        anchor = torch.zeros(1, device=input_ids.device, requires_grad=st.trainable or getattr(st, "adapter", None) is not None)
+        # (a frozen tower that carries a LoRA adapter still needs its backward: the adapted leaves' weight gradients come from it;
+        # so does one that carries new tokens: their gradient is the embedding's)
+        anchor = torch.zeros(1, device=input_ids.device, requires_grad=st.trainable or getattr(st, "adapter", None) is not None
+                             or getattr(st, "tokens", None) is not None)
     x = ops.embedding(input_ids.contiguous(), st, prefix + "text_model/embeddings/token_embedding/embedding",
                       prefix + "text_model/embeddings/position_embedding/embedding", S, anchor)
     act = ops.quick_gelu if cfg["hidden_act"] == "quick_gelu" else ops.gelu_erf

@@ -1169,7 +1169,13 @@ class _Embedding(Function):
         D = tok.shape[1]
         rows = ids.numel()
         out = torch.empty(*ids.shape, D, dtype=BF16, device=ids.device)
-        call("sdt_embedding_fwd", ids.data_ptr(), tok.data_ptr(), pos.data_ptr(), out.data_ptr(), rows, S, D, _stream())
+        tk = getattr(store, "tokens", None)
+        if tk is not None:  # new tokens (tokens.attach): ids V + j read the trained rows that continue the frozen table
+            ext = tk.rows(tok_path)
+            call("sdt_embedding_ext_fwd", ids.data_ptr(), tok.data_ptr(), ext.data_ptr(), pos.data_ptr(), out.data_ptr(), rows, S, D,
+                 tok.shape[0], ext.shape[0], _stream())
+        else:
+            call("sdt_embedding_fwd", ids.data_ptr(), tok.data_ptr(), pos.data_ptr(), out.data_ptr(), rows, S, D, _stream())
         ctx.save_for_backward(ids)
         ctx.meta = (store, tok_path, pos_path, S, D)
         return out
@@ -1178,7 +1184,13 @@ class _Embedding(Function):
     def backward(ctx, dout):
         (ids,) = ctx.saved_tensors
         store, tok_path, pos_path, S, D = ctx.meta
-        if store.trainable:
+        tk = getattr(store, "tokens", None)
+        if tk is not None:  # the gradient of the new rows only, written into the token store's float32 gradient
+            dout = dout.contiguous()
+            call("sdt_embedding_ext_bwd", ids.data_ptr(), dout.data_ptr(), tk.grad(tok_path).data_ptr(), ids.numel(), D,
+                 store.leaves[tok_path].shape[0], tk.num_tokens, _stream())
+            _ready(tk.store, tk.new_paths[tok_path])
+        elif store.trainable:
             dout = dout.contiguous()
             call("sdt_embedding_bwd", ids.data_ptr(), dout.data_ptr(), store.g(tok_path).data_ptr(),
                  store.g(pos_path).data_ptr(), ids.numel(), S, D, _stream())

@@ -199,6 +199,7 @@ class ParamStore:
         self._sched = None         # dict(step, lr_tab, ema_tab, cur) device tensors; kept for the store's life once allocated
         self._captured = False     # an optimizer step of this store has been captured into a graph (tables must not move)
         self.adapter = None        # lora.attach: a frozen store's low-rank adapter; prepare() then ends with its merge into W
+        self.tokens = None         # tokens.attach: a frozen text-encoder store's trained new-token rows (ops.embedding reads them)
 
     def prodigy_d(self):
         """Prodigy's current distance estimate d: a float64 device scalar (a view of the state block; .item() synchronises - logging

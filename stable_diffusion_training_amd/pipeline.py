@@ -44,7 +44,8 @@ class StableDiffusionPipeline:
 
     def _uncond_ids(self, batch, length):
         """tokenizer([""] * batch, padding="max_length") for CLIP: <|startoftext|>, then <|endoftext|> (also the pad token)."""
-        v = self.text_encoder_config["vocab_size"]
+        # (a checkpoint saved with trained new tokens has a resized table: the tokenizer's ids end below the num_new_tokens new rows)
+        v = self.text_encoder_config["vocab_size"] - self.text_encoder_config.get("num_new_tokens", 0)
         ids = torch.full((batch, length), v - 1, dtype=torch.int32, device=self.device)
         ids[:, 0] = v - 2
         return ids

@@ -18,7 +18,7 @@ class DataLoader:
                  maximum_resolution_areas=(512 ** 2,), bucket_lower_bound_resolutions=(256,), numb_of_worker_thread=1,
                  queue_get_timeout=60, chunk_number=0, seed=0, context_concatenation_multiplier=1, *,
                  batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu", text_towers=1,
-                 loss_masks=False, prior_every=0, prior_loss_weight=1.0, inpaint_masks=False):
+                 loss_masks=False, prior_every=0, prior_loss_weight=1.0, inpaint_masks=False, placeholder_ids=None):
         if len(maximum_resolution_areas) != len(bucket_lower_bound_resolutions):
             raise ValueError("number of elements in maximum_resolution_areas and bucket_lower_bound_resolutions is not match!")
         if training_batch_size % world_size:
@@ -35,12 +35,29 @@ class DataLoader:
             raise ValueError(f"prior_every={prior_every!r}: 0 (no class images) or n > 0 (every n-th sample is one)")
         self.loss_masks, self.prior_every, self.prior_loss_weight = bool(loss_masks), prior_every, float(prior_loss_weight)
         self.inpaint_masks = bool(inpaint_masks)
+        self.placeholder_ids = self._check_placeholders(placeholder_ids, text_towers, context_window)
         self.buckets = [tuple(int(v) for v in b) for area, lo in zip(maximum_resolution_areas, bucket_lower_bound_resolutions)
                         for b in calculate_resolution_array(area, lo, 64)]
         self._batches_per_chunk = batches_per_chunk
         self._bulk_batch_count, self._first_batch_count = 0, 0
         self._print_debug = True
         self._plan, self._cursor = [], 0
+
+    @staticmethod
+    def _check_placeholders(ids, towers, window):
+        """None, or one list of placeholder ids per tower (a flat list serves every tower): the ids a tokenizer would emit for the
+        trained new tokens (tokens.TokenAdapter.placeholder_ids)."""
+        if ids is None:
+            return None
+        ids = list(ids)
+        if ids and not isinstance(ids[0], (list, tuple)):
+            ids = [ids] * towers
+        ids = [[int(i) for i in t] for t in ids]
+        if len(ids) != towers or not ids[0] or any(len(t) != len(ids[0]) for t in ids):
+            raise ValueError(f"placeholder_ids: a non-empty list of ids, or one such list of the same length per tower ({towers}), not {ids!r}")
+        if len(ids[0]) > window - 2:
+            raise ValueError(f"placeholder_ids: {len(ids[0])} ids do not fit a caption window of {window} between BOS and EOS")
+        return ids
 
     # ---- chunk bookkeeping the loop calls (no files behind it here)
     def delete_prev_chunks(self, prev_chunk):
@@ -75,7 +92,9 @@ class DataLoader:
         sample of the global batch (global index % n == n - 1) as a class image and adds loss_weight f32 (B,): 1.0 for instance images,
         prior_loss_weight for class images (DreamBooth prior preservation).  inpaint_masks=True adds inpaint_mask f32 (B, bucket[0],
         bucket[1]) for an inpainting UNet: one seeded rectangle of ones (the region to repaint) per image, from a third generator of its
-        own.  The defaults add none of them."""
+        own.  The defaults add none of them.
+        placeholder_ids (a list of ids, or one list per tower for text_towers=2) overwrites the positions after BOS of every caption
+        window with those ids - the caption "<sks> ..." of a textual-inversion run; the other entries keep their values."""
         if self._cursor >= len(self._plan):
             return "end_of_batch"
         b0, b1 = self._plan[self._cursor]
@@ -88,6 +107,13 @@ class DataLoader:
         ids = torch.randint(0, self.vocab_size - 2, shape, generator=g, dtype=torch.int32)
         ids[..., 0] = self.vocab_size - 2   # <|startoftext|>
         ids[..., -1] = self.vocab_size - 1  # <|endoftext|>
+        if self.placeholder_ids is not None:
+            for t, pl in enumerate(self.placeholder_ids):
+                row = torch.tensor(pl, dtype=torch.int32)
+                if self.text_towers == 1:
+                    ids[..., 1: 1 + len(pl)] = row
+                else:
+                    ids[:, :, t, 1: 1 + len(pl)] = row
         ids = ids.reshape(per_rank, -1)
         batch = {"pixel_values": px, "input_ids": ids, "attention_mask": torch.ones_like(ids)}
         if self.text_towers == 2:

@@ -16,7 +16,7 @@ from typing import Any, Callable
 import numpy as np
 import torch
 
-from . import _lib, lora as lora_mod, nets, ops, optimizers, trace
+from . import _lib, lora as lora_mod, nets, ops, optimizers, tokens as tokens_mod, trace
 from .checkpoint import load_models, load_training_state, save_model, save_training_state  # noqa: F401  (reference names)
 from .lr_schedule import resolve as resolve_schedule
 from .params import EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
@@ -86,18 +86,24 @@ class FrozenModel:
 class TrainState:
     """Stand-in for flax TrainState (training_utils.py:383-387): apply_fn + params + optimizer, all in `store`.
     LoRA (lora=): `store` stays the network's - frozen - weight store, `adapter` is the lora.LoraAdapter whose own store holds the trained
-    leaves and takes the optimizer step (None with an empty hyper: a frozen text encoder that only runs its forward)."""
+    leaves and takes the optimizer step (None with an empty hyper: a frozen text encoder that only runs its forward).
+    New tokens (new_tokens=): the text state's `tokens` is the tokens.TokenAdapter hung on its frozen store; its store of trained rows
+    takes the optimizer step."""
     apply_fn: Callable
     store: ParamStore
     config: dict
     hyper: dict = field(default_factory=dict)
     adapter: Any = None
+    tokens: Any = None
 
     @property
     def opt_store(self):
-        """The store that takes the optimizer step: the weight store itself, the adapter's store, or None (frozen, no adapter)."""
+        """The store that takes the optimizer step: the weight store itself, the adapter's store, the token store, or None (frozen,
+        neither adapter nor tokens)."""
         if self.adapter is not None:
             return self.adapter.store
+        if self.tokens is not None:
+            return self.tokens.store
         return self.store if self.store.trainable else None
 
     @property
@@ -115,7 +121,7 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                                  excluded_layer_pattern_from_weight_decay=(), excluded_layer_from_quantization=(),
                                  lion_8bit_block_size=None, quantize_unet_state=False, quantize_text_encoder_state=False,
                                  with_unet_ema=False, with_text_encoder_ema=False, device="cuda", lr_scheduler="constant",
-                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0, optimizer="lion", lora=None):
+                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0, optimizer="lion", lora=None, new_tokens=None):
     """training_utils.py:281-427.  lr = learning_rate / adam_to_lion_scale_factor, wd = 1e-2 * scale, b1=.9, b2=.99,
     chain(clip_by_global_norm(1), lion_8bit | lion).  Builds the flat HBM stores and loads the weights.
     lr_scheduler / lr_schedule / ema_schedule / ema_rate: the per-step schedules of lr_schedule.resolve, installed in each trained store
@@ -130,8 +136,21 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
     lora: None, or dict(unet=lora.LoraConfig, text_encoder=lora.LoraConfig | None | "frozen").  The base stores are then built frozen
     (trainable=False) and loaded once; every setting above (quantisation, decay and quantisation exclusions, EMA, optimizer, rates and
     schedules) configures the ADAPTER's store of that model instead (TrainState.adapter.store), which is the one that steps.  A text
-    encoder without a LoraConfig only runs its forward.  Mixed modes - one model fully fine-tuned, the other adapted - are refused."""
+    encoder without a LoraConfig only runs its forward.  Mixed modes - one model fully fine-tuned, the other adapted - are refused.
+    new_tokens: None, or a tokens.TokenConfig (textual inversion).  Both base stores are built frozen; the text encoder's store carries
+    the trained rows (TrainState.tokens, tokens.attach), and the text encoder's settings above - rate, optimizer, quantisation switches,
+    schedules, EMA - configure the TOKEN store.  Alone, the UNet has no adapter and steps nothing; with lora=dict(unet=LoraConfig,
+    text_encoder=None | "frozen") the UNet's adapter trains beside the tokens (pivotal tuning).  A text-encoder LoraConfig beside new
+    tokens is refused."""
     out = {"unet_state": None, "text_encoder_state": None}
+    if new_tokens is not None:
+        if not isinstance(new_tokens, tokens_mod.TokenConfig):
+            raise ValueError(f"new_tokens: None or a tokens.TokenConfig, not {new_tokens!r}")
+        if not (train_unet and train_text_encoder):
+            raise ValueError("new_tokens: needs both states (train_unet and train_text_encoder)")
+        if isinstance(lora, dict) and isinstance(lora.get("text_encoder"), lora_mod.LoraConfig):
+            raise ValueError("new_tokens: a text-encoder LoRA together with new tokens is not supported (lora['text_encoder'] must be "
+                             "None or 'frozen')")
     if lora is not None:
         if not isinstance(lora, dict) or set(lora) - {"unet", "text_encoder"}:
             raise ValueError(f"lora: None or dict(unet=LoraConfig, text_encoder=LoraConfig | None | 'frozen'), not {lora!r}")
@@ -144,6 +163,7 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
             raise ValueError("lora: needs both states (train_unet and train_text_encoder); the text encoder is frozen by "
                              "text_encoder='frozen'")
         lora = {"unet": lora["unet"], "text_encoder": te_l}
+    frozen = lora is not None or new_tokens is not None  # the base stores only run; adapters' / the tokens' own stores step
     opt_cls, opt = optimizers.parse(optimizer)
 
     def make(spec, weights, cfg, fn, lr, quant, ema, which):
@@ -153,10 +173,11 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                    wd_excluded=tuple(excluded_layer_pattern_from_weight_decay), block_size=lion_8bit_block_size or 16, with_ema=ema)
         # full fine-tune: the store itself is trained.  LoRA: a frozen base, loaded once, and (unless the model only runs its forward)
         # an adapter whose own store takes those keywords and the optimizer step
-        store = ParamStore(spec, device=device, **(okw if lora is None else dict(trainable=False)))
+        store = ParamStore(spec, device=device, **(dict(trainable=False) if frozen else okw))
         store.load(weights)
         adapter = lora_mod.attach(store, lora[which], **okw) if lora is not None and lora[which] is not None else None
-        state = TrainState(fn, store, cfg, hyper if lora is None or adapter is not None else {}, adapter)
+        toks = tokens_mod.attach(store, new_tokens, **okw) if new_tokens is not None and which == "text_encoder" else None
+        state = TrainState(fn, store, cfg, hyper if not frozen or adapter is not None or toks is not None else {}, adapter, toks)
         if sched is not None and state.opt_store is not None:
             state.opt_store.set_schedule(lr=sched[0], ema=sched[1])
         return state
@@ -175,7 +196,7 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
 
 
 def on_device_model_training_state(training_config: TrainingConfig, models=None, device="cuda", *, lr_schedule=None,
-                                   ema_schedule=None, optimizer="lion", lora=None):
+                                   ema_schedule=None, optimizer="lion", lora=None, new_tokens=None):
     """training_utils.py:430-501.  `models`: load_models' result - host weight trees + configs
     ({"unet": {"unet_params", "config"}, "vae": {"vae_params", "config"}, "text_encoder": {...}}); None reads the
     diffusers directory at training_config.model_path (checkpoint.load_models).  Note the reference passes NEITHER learning
@@ -187,7 +208,10 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
     optimizer: create_lion_optimizer_states' (TrainingConfig has no field for it).
     lora: create_lion_optimizer_states' - dict(unet=lora.LoraConfig(rank, alpha), text_encoder=LoraConfig | None | "frozen") trains low-rank
     adapters on frozen base weights.  The tuple keeps its shape: the states' `store` are the frozen weight stores, `adapter` the adapters,
-    and the EMA views wrap the adapters' stores (None for a text encoder without an adapter)."""
+    and the EMA views wrap the adapters' stores (None for a text encoder without an adapter).
+    new_tokens: create_lion_optimizer_states' - a tokens.TokenConfig trains placeholder-token embeddings on the frozen text encoder, alone or
+    beside a UNet LoRA.  The text state's `tokens` is the TokenAdapter and its EMA view wraps the token store; a UNet without an adapter
+    has no EMA view (None)."""
     _lib.require_device()
     if models is None:
         models = load_models(training_config)
@@ -200,7 +224,7 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
         quantize_text_encoder_state=training_config.quantize_text_encoder_state,
         with_unet_ema=training_config.accumulate_unet_ema, with_text_encoder_ema=training_config.accumulate_text_encoder_ema,
         device=device, lr_scheduler=training_config.lr_scheduler, lr_schedule=lr_schedule, ema_schedule=ema_schedule,
-        ema_rate=training_config.ema_rate, optimizer=optimizer, lora=lora)
+        ema_rate=training_config.ema_rate, optimizer=optimizer, lora=lora, new_tokens=new_tokens)
     vae_cfg = models["vae"]["config"]
     vae_store = ParamStore(nets.vae_encoder_spec(vae_cfg), device=device, trainable=False)
     vae_store.load(models["vae"]["vae_params"])
@@ -213,7 +237,7 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
                           num_train_timesteps=1000, prediction_type=training_config.prediction_type)  # :223-230
     frozen_sched = FrozenModel(call=sched, params=sched.create_state(device))
     unet_state, te_state = states["unet_state"], states["text_encoder_state"]
-    unet_ema = EmaView(unet_state.opt_store) if training_config.accumulate_unet_ema else None
+    unet_ema = EmaView(unet_state.opt_store) if (training_config.accumulate_unet_ema and unet_state.opt_store is not None) else None
     te_ema = EmaView(te_state.opt_store) if (training_config.accumulate_text_encoder_ema and te_state.opt_store is not None) else None
     model_object_dict = {"unet": unet_state.config, "vae": vae_cfg, "text_encoder": te_state.config, "schedulers": sched}
     return unet_state, te_state, unet_ema, te_ema, frozen_vae, frozen_sched, model_object_dict
@@ -497,6 +521,14 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     gradient is skipped - projects dW onto the factors (adapter.project) and steps the adapters' stores; a text encoder without an
     adapter only runs its forward.  A reducer is refused (ValueError): the data-parallel exchange would have to be built over the adapter
     stores.
+    New tokens (TrainState.tokens on the text state; include/sdt.h "NEW TOKENS"): input_ids may hold the placeholder ids V + j.  Both base
+    stores are frozen; the stores that step are the UNet adapter's (pivotal tuning), if there is one, and the token store - a frozen UNet
+    without an adapter steps nothing.  The backward runs through the UNet's input-gradient chain and the frozen text encoder down to the
+    embedding, whose backward writes the gradient of the new rows (sdt_embedding_ext_bwd); weight gradients are skipped wherever no
+    adapter takes them.  With TokenConfig(retract=True) the rows are rescaled after the token store's optimizer step
+    (TokenAdapter.retract): it acts on the MASTER; the EMA, which the optimizer sweep updated from the un-retracted value, keeps the
+    sweep's value.  ValueError for a reducer and for mixed modes (a trained base store, a text-encoder LoRA, tokens on the store
+    without the state's `tokens`).
     Masked and weighted loss (include/sdt.h "MASKED LOSS"): a batch may hold "loss_mask", f32 contiguous on the step's device - (B,H,W)
     at pixel size beside pixel_values, (B,h,w) at latent size beside latent_moments - and "loss_weight", f32 (B,).  The mask is pooled to
     the latent grid (the mean of each block of clamp(m, 0, 1)), floored (masked_loss_floor in [0, 1]: OneTrainer's unmasked weight; 0 is a
@@ -533,16 +565,27 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                          "not carry text_embeds")
     us, ts = unet_state.store, text_encoder_state.store
     adapters = [a for a in (getattr(unet_state, "adapter", None), getattr(text_encoder_state, "adapter", None)) if a is not None]
-    lora = bool(adapters)
-    if lora:
+    tk = getattr(text_encoder_state, "tokens", None)
+    if tk is not None:
+        if us.trainable or ts.trainable or getattr(text_encoder_state, "adapter", None) is not None or tk is not getattr(ts, "tokens", None):
+            raise ValueError("new tokens: mixed modes are not supported - both base stores are frozen, the text encoder's store carries "
+                             "the tokens and no LoRA adapter (the UNet trains through an adapter of its own or not at all)")
+        if reducer is not None:
+            raise ValueError("new tokens: data-parallel training is not supported - the GradReducer would have to be built over the "
+                             "token store (TrainState.tokens.store)")
+    elif getattr(unet_state, "tokens", None) is not None or getattr(ts, "tokens", None) is not None or getattr(us, "tokens", None) is not None:
+        raise ValueError("new tokens: the text-encoder state must carry the TokenAdapter its store carries (TrainState.tokens; "
+                         "create_lion_optimizer_states(new_tokens=) builds both)")
+    lora = bool(adapters) or tk is not None  # the frozen-base step: adapters' and / or the tokens' own stores are the ones that step
+    if adapters:
         if us.trainable or ts.trainable or unet_state.adapter is None:
             raise ValueError("LoRA: mixed modes are not supported - the UNet carries the adapter and both base stores are frozen "
                              "(a text encoder trains through an adapter of its own or not at all)")
         if reducer is not None:
             raise ValueError("LoRA: data-parallel training of adapter states is not supported yet - the follow-up is to build the "
                              "GradReducer over the adapter stores (TrainState.adapter.store) instead of the frozen weight stores")
-    # the stores that are zeroed, accumulated into and stepped: the weight stores themselves, or the adapters' own
-    opt_stores = [a.store for a in adapters] if lora else [us, ts]
+    # the stores that are zeroed, accumulated into and stepped: the weight stores themselves, or the adapters' / the tokens' own
+    opt_stores = ([a.store for a in adapters] + ([tk.store] if tk is not None else [])) if lora else [us, ts]
     sched, sched_state = frozen_noise_scheduler_state.call, frozen_noise_scheduler_state.params
     dev = us.device
     cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev, masked_loss_floor, normalize_masked_area)
@@ -609,6 +652,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             if k == 0 and lora:
                 for ad in adapters:  # the frozen mirrors stay as the load left them: only the adapted leaves are rewritten
                     ad.merge("master")
+                if tk is not None:
+                    tk.select("master")  # (no launch: the embedding reads the trained rows where they are)
             elif k == 0:
                 us.prepare()
                 ts.prepare()
@@ -806,6 +851,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             if store is not None:  # (None: a LoRA run's text encoder without an adapter only ran its forward)
                 store.optimizer_step(ema_rate=rate, shard=None if reducer is None else reducer.shard_pieces(store), sq_partials=sq,
                                      grad_source=grad_source, **state.hyper)
+        if tk is not None and tk.cfg.retract:
+            tk.retract()  # on the stepped master; the EMA keeps the value the sweep gave it
         if reducer is not None:
             reducer.after_optimizer()  # sharded optimizer: all-gather the bf16 weight mirrors the owners have just written
     ops.gn_arena_end(dev)
