@@ -27,7 +27,11 @@ latents of the masked image].  With --cache-latents the cache keeps the masked i
 tokens are trained on the frozen text encoder (tokens.TokenConfig; rows copied from token ID, else seeded noise at the table's scale;
 --retract rescales them towards the table's standard deviation after every step), the loader puts their ids after BOS in every caption,
 the text encoder's rate / optimizer / EMA settings configure the token store, and the saves hold the resized text encoder plus
-<model>-tokens.npz.  Alone the UNet stays frozen; with --lora RANK the UNet's adapter trains beside the tokens (pivotal tuning)."""
+<model>-tokens.npz.  Alone the UNet stays frozen; with --lora RANK the UNet's adapter trains beside the tokens (pivotal tuning).
+--controlnet [DIR] ("controlnet": true or a directory): trains a ControlNet on the frozen UNet and text encoder - loaded from DIR
+(checkpoint.load_controlnet) or initialised from the UNet (nets.controlnet_from_unet; "controlnet_channels" sets the embedder's widths) -
+from batches with a conditioning image per sample; the UNet's rate / optimizer / EMA settings configure its store, every chunk writes
+<model>-controlnet (and -controlnet-EMA), and --cache-latents keeps the conditioning images beside the moments."""
 import argparse
 import json
 import os
@@ -41,7 +45,7 @@ import torch.distributed as dist
 
 from stable_diffusion_training_amd import dp, latent_cache, lora, nets, tokens
 from stable_diffusion_training_amd import training_utils as tu
-from stable_diffusion_training_amd.checkpoint import gather_rng_states
+from stable_diffusion_training_amd.checkpoint import gather_rng_states, load_controlnet, save_controlnet
 from stable_diffusion_training_amd.streamer import DataLoader
 
 
@@ -108,7 +112,18 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     prior_w = config_dict.get("prior_loss_weight")
     if config_dict.get("normalize_masked_area") and not use_mask:
         raise ValueError("normalize_masked_area needs masked_loss (--masked-loss)")
-    loss_loader_kw = dict(inpaint_masks=inpaint, loss_masks=use_mask, prior_every=2 if prior_w is not None else 0,
+    control = None
+    if config_dict.get("controlnet"):  # a ControlNet on the frozen UNet: loaded from a directory, or initialised from the UNet
+        if world > 1:
+            raise ValueError("controlnet: ControlNet training runs on one GPU (train_step refuses a reducer with a ControlNet)")
+        if isinstance(config_dict["controlnet"], str):
+            control = load_controlnet(config_dict["controlnet"])
+        else:
+            f = 2 ** (len(models["vae"]["config"]["block_out_channels"]) - 1)
+            control = dict(config=nets.controlnet_config(models["unet"]["config"], tuple(config_dict.get("controlnet_channels", (16, 32, 96, 256))),
+                                                         vae_downscale=f))
+    loss_loader_kw = dict(inpaint_masks=inpaint, loss_masks=use_mask,
+                          conditioning_images=int(control["config"]["conditioning_channels"]) if control is not None else False, prior_every=2 if prior_w is not None else 0,
                           prior_loss_weight=1.0 if prior_w is None else float(prior_w))
     loss_overrides = {}
     if use_mask:
@@ -152,7 +167,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     train_rngs.manual_seed(config_dict["master_seed"] * 1009 + rank)  # different noise / timesteps on every shard
     (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers,
      model_object_dict) = tu.on_device_model_training_state(training_config, models, device=dev, optimizer=config_dict.get("optimizer", "lion"),
-                                                           **schedule_kwargs(config_dict), lora=lora_cfg, new_tokens=token_cfg)
+                                                           **schedule_kwargs(config_dict), lora=lora_cfg, new_tokens=token_cfg, controlnet=control)
     reducer = dp.GradReducer([unet_state.store, text_encoder_state.store]) if world > 1 else None
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
@@ -189,6 +204,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         base = config_dict["model_path"].split("@")[0] + ("-EMA" if ema else "")
         # (a model without an EMA view - accumulate_*_ema off, or a text encoder frozen under LoRA - is saved as it stands)
         up = unet_ema_params if (ema and config_dict["accumulate_unet_ema"] and unet_ema_params is not None) else unet_state.params
+        if unet_state.controlnet is not None:
+            up = unet_state.params  # the UNet EMA view wraps the ControlNet's store: the pipeline directory holds the frozen base either way
         tp = (text_encoder_ema_params if (ema and config_dict["accumulate_text_encoder_ema"] and text_encoder_ema_params is not None)
               else text_encoder_state.params)
         tu.save_model(model_object_dict, tokenizer, up, tp, vae_params, f'{base}@{config_dict["chunk_steps"]}')
@@ -252,6 +269,11 @@ def main(config_dict, models=None, tokenizer=None, log=print):
                 save(ema=True)
             state_path = config_dict["model_path"].split("@")[0] + "-state.safetensors"
             tu.save_training_state(state_path, unet_state, text_encoder_state, rng_states=rng_states)
+            if unet_state.controlnet is not None:  # the ControlNet as a submodel directory of its own; its EMA, when there is one, beside it
+                cbase = config_dict["model_path"].split("@")[0] + "-controlnet"
+                save_controlnet(cbase, unet_state.controlnet, unet_state.controlnet.config)
+                if config_dict["ema_rate"] and unet_ema_params is not None:
+                    save_controlnet(cbase + "-EMA", unet_ema_params, unet_state.controlnet.config)
             if unet_state.adapter is not None:  # the adapter alone (the saves above hold the base with the adapter folded in)
                 unet_state.adapter.save(config_dict["model_path"].split("@")[0] + "-lora.npz")
             if text_encoder_state.tokens is not None:  # the trained rows alone (the saves above hold the resized text encoder)
@@ -291,6 +313,8 @@ if __name__ == "__main__":
                     help="l2 (default); huber / smooth_l1: the pseudo-Huber losses, robust to outlier images and high-noise timesteps")
     ap.add_argument("--inpaint", action="store_true", default=None,
                     help="train an inpainting UNet (widened from the checkpoint's when it is not one) from batches with an inpaint mask")
+    ap.add_argument("--controlnet", metavar="DIR", nargs="?", const=True, default=None,
+                    help="train a ControlNet on the frozen UNet from batches with a conditioning image (DIR: continue a saved one)")
     ap.add_argument("--huber-c", metavar="C", type=float, default=None, help="the Huber threshold the schedule ends at (default 0.1)")
     ap.add_argument("--huber-schedule", choices=("constant", "exponential", "snr"), default=None,
                     help="how the threshold follows the timestep: snr (default), exponential or constant")
@@ -327,6 +351,8 @@ if __name__ == "__main__":
         cfg["loss_type"] = args.loss_type
     if args.inpaint:
         cfg["inpaint"] = True
+    if args.controlnet is not None:
+        cfg["controlnet"] = args.controlnet
     if args.huber_c is not None:
         cfg["huber_c"] = args.huber_c
     if args.huber_schedule is not None:

@@ -148,6 +148,17 @@ int sdt_inpaint_noise_target(const uint16_t* moments_nhwc, const uint16_t* maske
 int sdt_inpaint_pack_input(const uint16_t* latents_nhwc, const uint16_t* masked_latents_nhwc, const float* latent_mask,
                            uint16_t* input_nhwc, int R, int B, int L, int H, int W, int cpad_src, int cpad_m, int cpad_dst,
                            hipStream_t stream);
+/* ---- CONTROLNET: the injection of a ControlNet's residuals into the frozen UNet (no reference counterpart; DESIGN.md "ControlNet").
+ * sdt_control_concat_add: a bf16 (rows, Ca) or NULL, skip and res bf16 (rows, Cb), scale f32 (rows / rows_per_sample) or NULL (= 1)
+ *   -> wide bf16 (rows, Ca + Cb): columns [0, Ca) are 16-bit copies of a, column Ca + j is
+ *   bf16_rne((double)skip + (double)scale[row / rows_per_sample] * (double)res): the product is exact in double, the sum is IEEE double
+ *   (nothing contracted) and is rounded to bf16 ONCE, to nearest even (a NaN sum gives the quiet NaN 0x7fc0).  No
+ *   shortcut for a zero scale: 0 * NaN and 0 * inf are NaN.  a NULL needs Ca == 0: the mid-block form, wide = skip + scale * res.
+ *   No atomics, no workspace, 64-bit element counts.  Rows move 16 bytes at a time when Ca % 8 == 0, Cb % 8 == 0 and every base is
+ *   16-byte aligned; one element per thread otherwise.  Refused: a NULL skip, res or wide; Cb < 1; Ca < 0; Ca > 0 with a NULL a;
+ *   rows_per_sample < 1; rows % rows_per_sample != 0. */
+int sdt_control_concat_add(const uint16_t* a, const uint16_t* skip, const uint16_t* res, const float* scale, uint16_t* wide,
+                           int64_t rows, int64_t rows_per_sample, int Ca, int Cb, hipStream_t stream);
 /* loss_accum += mean(w_b*(target-pred)^2); dpred = d loss / d pred (bf16 NHWC, cpad channels).
  * REDUCTION WORKSPACES (this call, sdt_sqnorm_accumulate, sdt_colsum_*): sums that cross workgroups use no float atomics - each
  * workgroup stores a partial, the one that arrives last adds them in a fixed order, so results are bitwise reproducible.  They

@@ -59,6 +59,7 @@ SIGNATURES = {
     "sdt_inpaint_mask_pixels": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P],
     "sdt_inpaint_noise_target": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P],
     "sdt_inpaint_pack_input": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
+    "sdt_control_concat_add": [_P, _P, _P, _P, _P, _L, _L, _I, _I, _P],
     "sdt_ddim_cfg_step": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P],
     "sdt_cfg_rescale_factors": [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P],
     "sdt_sampler_cfg_step": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _I, _F, _F, _F, _F, _P],

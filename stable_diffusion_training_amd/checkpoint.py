@@ -270,6 +270,10 @@ def save_model(model_object_dict, tokenizer_object, unet_params, text_encoder_pa
     v_prediction, :998-1004), whatever the run trained with.
     A text encoder that carries new tokens (tokens.attach) is written resized: its token table holds the V base rows followed by the n
     trained ones and its config's vocab_size is V + n, so the directory loads into a plain store of this project."""
+    ustore = unet_params.store if hasattr(unet_params, "store") else unet_params
+    if getattr(ustore, "controlnet_config", None) is not None:
+        raise ValueError("save_model: unet_params is (the EMA view of) a ControlNet's store, not a UNet: pass the frozen UNet "
+                         "(unet_state.params) here and write the ControlNet with save_controlnet")
     os.makedirs(output_dir, exist_ok=True)
     dv = {"_diffusers_version": DIFFUSERS_VERSION}
     _write_submodel(output_dir, "unet", _model_config(model_object_dict, "unet"),
@@ -301,6 +305,28 @@ def save_model(model_object_dict, tokenizer_object, unet_params, text_encoder_pa
         tokenizer_object.save_pretrained(os.path.join(output_dir, "tokenizer"))
     _write_json(os.path.join(output_dir, "model_index.json"), index)
     print("f model saved ")  # the reference's message, verbatim (training_utils.py:1025)
+
+
+def save_controlnet(output_dir, controlnet, config):
+    """A diffusers-Flax ControlNet submodel directory: config.json (FlaxControlNetModel) and the msgpack weights file.  controlnet: a
+    nets.ControlNet, its ParamStore, the EmaView over it (the EMA weights) or a flat / nested host tree; config: nets.controlnet_config."""
+    _write_submodel(output_dir, "", config, {"_class_name": "FlaxControlNetModel", "_diffusers_version": DIFFUSERS_VERSION},
+                    UNET_WEIGHTS, controlnet)
+
+
+def load_controlnet(directory):
+    """Inverse of save_controlnet: dict(config=, params=flat {"path": float32 tensor} host tree), what
+    on_device_model_training_state(controlnet=) and StableDiffusionPipeline(controlnet=) build their stores from."""
+    cfg = _read_config(os.path.join(directory, "config.json"), nets._UNET_DEFAULTS)
+    for k in ("conditioning_embedding_out_channels", "conditioning_channels"):
+        if k not in cfg:
+            raise ValueError(f"{directory}: config.json has no {k}: not a ControlNet directory")
+    path = os.path.join(directory, UNET_WEIGHTS)
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path}: expected the ControlNet's Flax weights")
+    with open(path, "rb") as f:
+        flat = flatten_tree(flax_from_bytes(f.read()))
+    return {"config": cfg, "params": {p: torch.from_numpy(np.array(v, dtype=np.float32)) for p, v in flat.items()}}
 
 
 # keys of a tower config that describe how this project runs it, not the transformers model: not written to config.json
@@ -427,6 +453,9 @@ def _stepping_store(st):
     """The store of a state whose buffers a training-state file holds: the state's own store, the store of its LoRA adapter (the frozen
     base under it is not written: it is the checkpoint the run started from), or None for a frozen model without an adapter."""
     store = st.store if hasattr(st, "store") else st
+    cn = getattr(st, "controlnet", None)
+    if cn is not None:  # a ControlNet on the frozen UNet: the ControlNet's store (the layout digest tells it from the UNet's)
+        return cn.store, None
     ad = getattr(st, "adapter", None)
     if ad is not None:
         return ad.store, ad

@@ -450,6 +450,85 @@ __global__ void __launch_bounds__(256) inpaint_pack_input_kernel(const bf16_t* _
   }
 }
 
+// ------------------------------------------------------------------ ControlNet injection (include/sdt.h "CONTROLNET")
+// A double rounded to bf16 once, to nearest even, in integer arithmetic on its bits (a conversion through float would round twice).
+// NaN -> the quiet NaN 0x7fc0; a magnitude of 2^128 or more, and one that rounds up to it, -> inf; below half the
+// smallest bf16 subnormal (2^-134) -> a signed zero.
+__device__ __forceinline__ bf16_t double_to_bf16_rne(double d) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(d);
+  const unsigned sign = (unsigned)(b >> 48) & 0x8000u;
+  const unsigned long long mag = b & 0x7fffffffffffffffULL;
+  if (mag > 0x7ff0000000000000ULL) return (bf16_t)0x7fc0u;  // (the sign of a NaN that arithmetic produced is not specified)
+  const int e = (int)(mag >> 52);
+  if (e == 0) return (bf16_t)sign;  // zero or a double subnormal
+  const int eb = e - 1023 + 127;    // the bf16 exponent field of a normal result
+  if (eb >= 255) return (bf16_t)(sign | 0x7f80u);
+  const unsigned long long m = (mag & 0xfffffffffffffULL) | (1ULL << 52);
+  const int shift = eb > 0 ? 45 : 46 - eb;  // 52 - 7 fraction bits; one more for every step below the normal range
+  if (shift > 54) return (bf16_t)sign;      // m < 2^53 is less than half a unit
+  unsigned q = (unsigned)(m >> shift);
+  const unsigned long long rem = m & ((1ULL << shift) - 1), half = 1ULL << (shift - 1);
+  if (rem > half || (rem == half && (q & 1u))) ++q;
+  // normal: q in [128, 256] holds the implicit one, so (eb - 1) << 7 plus q carries into the exponent by itself (up to inf);
+  // subnormal: q in [0, 128] is the field, 128 being the smallest normal
+  return (bf16_t)(sign | ((eb > 0 ? (unsigned)(eb - 1) << 7 : 0u) + q));
+}
+
+__device__ __forceinline__ bf16_t control_add_element(bf16_t skip, bf16_t res, float scale) {
+#pragma clang fp contract(off)
+  // scale (24 bits) * res (8 bits) is exact in double; the sum rounds to double, then once to bf16
+  return double_to_bf16_rne((double)bf2f(skip) + (double)scale * (double)bf2f(res));
+}
+
+// The sample of a row.  rows_per_sample <= rows, so both fit 32 bits whenever rows does, and the division is then a 32-bit one
+// (64-bit integer division is emulated on CDNA); the condition is uniform over the launch.
+__device__ __forceinline__ long control_sample(long r, long rows, long rows_per_sample) {
+  return rows <= 0x7fffffffL ? (long)((unsigned)r / (unsigned)rows_per_sample) : r / rows_per_sample;
+}
+
+// wide (rows, Ca + Cb) = [a | skip + scale[row / rows_per_sample] * res].  Block (cx, 256 / cx): threadIdx.x walks the 16-byte chunks
+// of a row, threadIdx.y and the grid walk the rows, so no index is divided by the row width; cx is a power of two >= the chunks of a
+// row (at most 256), and consecutive lanes touch consecutive chunks of consecutive rows.
+__global__ void __launch_bounds__(256) control_concat_add_vec_kernel(const uint4* __restrict__ a, const uint4* __restrict__ skip,
+                                                                     const uint4* __restrict__ res, const float* __restrict__ scale,
+                                                                     uint4* __restrict__ wide, long rows, long rows_per_sample, int Cav,
+                                                                     int Cbv) {
+  const int Wv = Cav + Cbv;
+  for (long r = (long)blockIdx.x * blockDim.y + threadIdx.y; r < rows; r += (long)gridDim.x * blockDim.y) {
+    const float s = scale ? scale[control_sample(r, rows, rows_per_sample)] : 1.f;
+    for (int c = threadIdx.x; c < Wv; c += blockDim.x) {
+      if (c < Cav) {
+        wide[r * Wv + c] = a[r * Cav + c];
+        continue;
+      }
+      const long j = r * Cbv + (c - Cav);
+      const uint4 sv = skip[j], rv = res[j];
+      const unsigned si[4] = {sv.x, sv.y, sv.z, sv.w}, ri[4] = {rv.x, rv.y, rv.z, rv.w};
+      unsigned o[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const unsigned lo = control_add_element((bf16_t)(si[k] & 0xffffu), (bf16_t)(ri[k] & 0xffffu), s);
+        const unsigned hi = control_add_element((bf16_t)(si[k] >> 16), (bf16_t)(ri[k] >> 16), s);
+        o[k] = lo | (hi << 16);
+      }
+      wide[r * Wv + c] = make_uint4(o[0], o[1], o[2], o[3]);
+    }
+  }
+}
+
+// the same with threadIdx.x walking single elements: any widths, any 2-byte alignment
+__global__ void __launch_bounds__(256) control_concat_add_scalar_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ skip,
+                                                                        const bf16_t* __restrict__ res, const float* __restrict__ scale,
+                                                                        bf16_t* __restrict__ wide, long rows, long rows_per_sample, int Ca,
+                                                                        int Cb) {
+  const int Wd = Ca + Cb;
+  for (long r = (long)blockIdx.x * blockDim.y + threadIdx.y; r < rows; r += (long)gridDim.x * blockDim.y) {
+    const float s = scale ? scale[control_sample(r, rows, rows_per_sample)] : 1.f;
+    for (int c = threadIdx.x; c < Wd; c += blockDim.x)
+      wide[r * Wd + c] = c < Ca ? a[r * Ca + c] : control_add_element(skip[r * Cb + (c - Ca)], res[r * Cb + (c - Ca)], s);
+  }
+}
+
 // pred bf16 NHWC (B,h,w,cpad), target f32 NCHW (B,C,h,w), w f32 (B) or null.
 // loss_sum += sum w*(t-p)^2 * inv_count ; dpred (bf16 NHWC cpad) = -2*w*(t-p)*inv_count
 __global__ void __launch_bounds__(256) mse_kernel(const bf16_t* __restrict__ pred, const float* __restrict__ target,
@@ -1373,6 +1452,32 @@ int sdt_inpaint_pack_input(const uint16_t* latents_nhwc, const uint16_t* masked_
   hipLaunchKernelGGL(kern, dim3(sdt_grid_1d((long)R * H * W, 256)), dim3(256), 0, stream, (const bf16_t*)latents_nhwc,
                      (const bf16_t*)masked_latents_nhwc, latent_mask, (bf16_t*)input_nhwc, R, B, L, H * W, cpad_src, cpad_m, cpad_dst);
   SDT_LAUNCH_CHECK("sdt_inpaint_pack_input");
+  return SDT_OK;
+}
+
+int sdt_control_concat_add(const uint16_t* a, const uint16_t* skip, const uint16_t* res, const float* scale, uint16_t* wide,
+                           int64_t rows, int64_t rows_per_sample, int Ca, int Cb, hipStream_t stream) {
+  SDT_CHECK_ARG(skip && res && wide, "sdt_control_concat_add: null pointer (skip, res and wide are required)");
+  SDT_CHECK_ARG(Cb >= 1 && Ca >= 0, "sdt_control_concat_add: bad widths Ca=%d Cb=%d (Ca >= 0, Cb >= 1)", Ca, Cb);
+  SDT_CHECK_ARG(a || Ca == 0, "sdt_control_concat_add: Ca=%d needs the left part (a is null)", Ca);
+  SDT_CHECK_ARG(rows_per_sample >= 1, "sdt_control_concat_add: rows_per_sample=%ld must be at least 1", (long)rows_per_sample);
+  SDT_CHECK_ARG(rows >= 0 && rows % rows_per_sample == 0, "sdt_control_concat_add: rows=%ld is not a multiple of rows_per_sample=%ld",
+                (long)rows, (long)rows_per_sample);
+  if (rows == 0) return SDT_OK;
+  const uintptr_t bases = (uintptr_t)skip | (uintptr_t)res | (uintptr_t)wide | (Ca ? (uintptr_t)a : 0);
+  const bool vec = Ca % 8 == 0 && Cb % 8 == 0 && (bases & 15) == 0;
+  const int width = vec ? (Ca + Cb) / 8 : Ca + Cb;  // what threadIdx.x walks: 16-byte chunks or elements of a row
+  int cx = 1;
+  while (cx < width && cx < 256) cx <<= 1;
+  const dim3 block(cx, 256 / cx), grid(sdt_grid_1d((long)rows, 256 / cx));
+  if (vec) {
+    hipLaunchKernelGGL(control_concat_add_vec_kernel, grid, block, 0, stream, (const uint4*)a, (const uint4*)skip, (const uint4*)res, scale,
+                       (uint4*)wide, (long)rows, (long)rows_per_sample, Ca / 8, Cb / 8);
+  } else {
+    hipLaunchKernelGGL(control_concat_add_scalar_kernel, grid, block, 0, stream, (const bf16_t*)a, (const bf16_t*)skip, (const bf16_t*)res,
+                       scale, (bf16_t*)wide, (long)rows, (long)rows_per_sample, Ca, Cb);
+  }
+  SDT_LAUNCH_CHECK("sdt_control_concat_add");
   return SDT_OK;
 }
 

@@ -18,7 +18,9 @@ Layout of a cache directory (plain numpy, nothing compressed):
                       (B,h,w,2L), the moments of the masked image out of the SAME stacked 2B encode the step runs
                       (training_utils.encode_inpaint_moments: `moments` is then that encode's first half), and inpaint_mask float32
                       (B,h,w), the nearest-neighbour 0/1 latent mask.  A record without the mask keeps its members and bytes.
-A cached SD1.5 512x512 sample is 64 KiB; its fp32 pixels are 3 MiB.
+                      For a ControlNet batch: conditioning_pixel_values float32 (B,C,H,W) as the batch holds them (the hint stays at
+                      pixel size: the ControlNet's embedder, which is trained, reads it every step).
+A cached SD1.5 512x512 sample is 64 KiB; its fp32 pixels are 3 MiB (as is a ControlNet batch's conditioning image, which is kept).
 """
 import hashlib
 import json
@@ -31,7 +33,8 @@ from . import _lib, ops
 from .training_utils import encode_inpaint_moments, encode_latent_moments, step_key
 
 FORMAT_VERSION = 1
-EXTRA_KEYS = ("input_ids", "time_ids", "text_embeds")  # what a record keeps of a batch besides the moments
+# what a record keeps of a batch besides the moments (conditioning_pixel_values: a ControlNet batch's hint, float32 at pixel size)
+EXTRA_KEYS = ("input_ids", "time_ids", "text_embeds", "conditioning_pixel_values")
 LOSS_WEIGHT_KEY, LOSS_MASK_KEY = "loss_weight", "loss_mask"  # kept too: the weight as it is, the mask pooled to the latent grid
 INPAINT_MASK_KEY, MASKED_MOMENTS_KEY = "inpaint_mask", "masked_latent_moments"  # the latent 0/1 mask and the masked image's moments
 

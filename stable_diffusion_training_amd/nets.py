@@ -10,6 +10,7 @@ checkpoints stay drop-in.  `*_spec(cfg)` return the leaves as an ordered (path, 
 order: the flat gradient buffer is laid out in that order, so backward completes all-reduce buckets back to front.
 Activations are NHWC bf16 with channels padded to a multiple of 8 (4-channel latents / 3-channel pixels -> 8).
 """
+import contextlib
 import math
 
 import torch
@@ -187,17 +188,23 @@ class _Spec(list):
             self.conv(p + "/proj_out", c, c, k=1)
 
 
-def unet_spec(cfg):
-    s = _Spec()
+def _spec_time_embedding(s, cfg):
+    """time_embedding (and add_embedding for text_time): the first leaves of a UNet and of a ControlNet."""
     boc = cfg["block_out_channels"]
-    nb, lpb, ctx, lin = len(boc), cfg["layers_per_block"], cfg["cross_attention_dim"], cfg["use_linear_projection"]
     temb = boc[0] * 4
-    depth = _per_block(cfg["transformer_layers_per_block"], nb)
     s.dense("time_embedding/linear_1", boc[0], temb)
     s.dense("time_embedding/linear_2", temb, temb)
     if cfg["addition_embed_type"] == "text_time":
         s.dense("add_embedding/linear_1", cfg["projection_class_embeddings_input_dim"], temb)
         s.dense("add_embedding/linear_2", temb, temb)
+
+
+def _spec_encoder(s, cfg):
+    """conv_in, the down blocks and the mid block in forward order: the part of the UNet a ControlNet repeats under the same names."""
+    boc = cfg["block_out_channels"]
+    nb, lpb, ctx, lin = len(boc), cfg["layers_per_block"], cfg["cross_attention_dim"], cfg["use_linear_projection"]
+    temb = boc[0] * 4
+    depth = _per_block(cfg["transformer_layers_per_block"], nb)
     s.conv("conv_in", cfg["in_channels"], boc[0])
     out_ch = boc[0]
     for i, t in enumerate(cfg["down_block_types"]):
@@ -212,6 +219,16 @@ def unet_spec(cfg):
     s.resnet("mid_block/resnets_0", mid, mid, temb)
     s.transformer("mid_block/attentions_0", mid, ctx, depth[-1], lin)
     s.resnet("mid_block/resnets_1", mid, mid, temb)
+
+
+def unet_spec(cfg):
+    s = _Spec()
+    boc = cfg["block_out_channels"]
+    nb, lpb, ctx, lin = len(boc), cfg["layers_per_block"], cfg["cross_attention_dim"], cfg["use_linear_projection"]
+    temb = boc[0] * 4
+    depth = _per_block(cfg["transformer_layers_per_block"], nb)
+    _spec_time_embedding(s, cfg)
+    _spec_encoder(s, cfg)
     rev, rdepth = list(reversed(boc)), list(reversed(depth))
     out_ch = rev[0]
     for i, t in enumerate(cfg["up_block_types"]):
@@ -227,6 +244,101 @@ def unet_spec(cfg):
     s.norm("conv_norm_out", boc[0])
     s.conv("conv_out", boc[0], cfg["out_channels"])
     return s.finish()
+
+
+class ControlNet:
+    """A ControlNet as the training state and the sampling pipeline hold it: its ParamStore and its config (controlnet_config)."""
+
+    def __init__(self, store, config):
+        self.store, self.config = store, config
+
+
+def controlnet_config(unet_cfg, conditioning_embedding_out_channels=(16, 32, 96, 256), conditioning_channels=3, vae_downscale=8):
+    """The UNet's config plus diffusers' two ControlNet keys.  The conditioning image is at pixel size and the embedder halves it once
+    per entry after the first, down to the latent grid: len(conditioning_embedding_out_channels) - 1 must be log2(vae_downscale) (3 for
+    every VAE here).  Entries are activation widths and must be multiples of 8.  ValueError otherwise, and for an inpainting UNet."""
+    ch = tuple(int(c) for c in conditioning_embedding_out_channels)
+    halvings = int(vae_downscale).bit_length() - 1
+    if vae_downscale < 1 or 2 ** halvings != vae_downscale:
+        raise ValueError(f"controlnet_config: vae_downscale={vae_downscale!r} must be a power of two")
+    if len(ch) - 1 != halvings:
+        raise ValueError(f"controlnet_config: conditioning_embedding_out_channels has {len(ch)} entries; the embedder halves the "
+                         f"conditioning image {len(ch) - 1} times and the VAE's downscale {vae_downscale} needs {halvings} ({halvings + 1} entries)")
+    if any(c < 8 or c % 8 for c in ch):
+        raise ValueError(f"controlnet_config: conditioning_embedding_out_channels={ch} must be positive multiples of 8")
+    if not isinstance(conditioning_channels, int) or conditioning_channels < 1:
+        raise ValueError(f"controlnet_config: conditioning_channels={conditioning_channels!r} must be a positive integer")
+    if inpaint_latent_channels(unet_cfg) is not None:
+        raise ValueError("controlnet_config: a ControlNet on an inpainting UNet is not supported")
+    return dict(unet_cfg, conditioning_embedding_out_channels=ch, conditioning_channels=conditioning_channels)
+
+
+def skip_shapes(cfg, h=1, w=1):
+    """(channels, height, width) of the UNet's skip tensors for (h, w) latents, in the order unet_forward appends them."""
+    boc = cfg["block_out_channels"]
+    out = [(boc[0], h, w)]
+    for i in range(len(boc)):
+        out += [(boc[i], h, w)] * cfg["layers_per_block"]
+        if i != len(boc) - 1:
+            h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1  # the 3x3 stride-2 pad-1 downsampler
+            out.append((boc[i], h, w))
+    return out
+
+
+def _skip_channels(cfg):
+    return [c for c, _, _ in skip_shapes(cfg)]
+
+
+def controlnet_spec(cfg):
+    """Leaves of diffusers' FlaxControlNetModel: the UNet's time embedding, conv_in, down and mid blocks under the UNet's names (the
+    helpers unet_spec itself is built from), the conditioning embedder, one 1x1 zero convolution per skip tensor and one for the mid block."""
+    s = _Spec()
+    boc = cfg["block_out_channels"]
+    _spec_time_embedding(s, cfg)
+    ch = cfg["conditioning_embedding_out_channels"]
+    e = "controlnet_cond_embedding"
+    s.conv(e + "/conv_in", cfg["conditioning_channels"], ch[0])
+    for k in range(len(ch) - 1):
+        s.conv(f"{e}/blocks_{2 * k}", ch[k], ch[k])
+        s.conv(f"{e}/blocks_{2 * k + 1}", ch[k], ch[k + 1])  # stride 2
+    s.conv(e + "/conv_out", ch[-1], boc[0])
+    _spec_encoder(s, cfg)
+    for i, c in enumerate(_skip_channels(cfg)):
+        s.conv(f"controlnet_down_blocks_{i}", c, c, k=1)
+    s.conv("controlnet_mid_block", boc[-1], boc[-1], k=1)
+    return s.finish()
+
+
+def controlnet_zero_leaves(cfg):
+    """The leaves a fresh ControlNet holds as zeros: the embedder's conv_out and every zero convolution, kernels and biases."""
+    heads = ["controlnet_cond_embedding/conv_out", "controlnet_mid_block"] + [f"controlnet_down_blocks_{i}" for i in range(len(_skip_channels(cfg)))]
+    return [f"{h}/{leaf}" for h in heads for leaf in ("kernel", "bias")]
+
+
+def controlnet_from_unet(unet_params, cfg, seed=0):
+    """A fresh ControlNet for a UNet, as diffusers' from_unet builds it (host tree, flat paths): the leaves it shares with the UNet are
+    copies of the UNet's, the embedder's convolutions are seeded random (init_params) and conv_out, every controlnet_down_blocks_* and
+    controlnet_mid_block are zero - so the ControlNet's residuals are zero and the UNet computes what it did without it.
+    unet_params: flat or nested tree, torch tensors or numpy arrays."""
+    if any(isinstance(v, dict) for v in unet_params.values()):
+        from .checkpoint import flatten_tree
+        unet_params = flatten_tree(unet_params)
+    spec = controlnet_spec(cfg)
+    fresh = init_params([(p, shp) for p, shp in spec if p.startswith("controlnet_")], seed)
+    zero = set(controlnet_zero_leaves(cfg))
+    out = {}
+    for p, shp in spec:
+        if p in zero:
+            out[p] = torch.zeros(shp)
+        elif p in fresh:
+            out[p] = fresh[p]
+        else:
+            v = unet_params[p]
+            v = v.detach().to(torch.float32).cpu().clone() if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float32)
+            if tuple(v.shape) != tuple(shp):
+                raise ValueError(f"controlnet_from_unet: {p} has shape {tuple(v.shape)} in the UNet, the ControlNet's config says {tuple(shp)}")
+            out[p] = v
+    return out
 
 
 def time_emb_groups(leaves):
@@ -522,14 +634,9 @@ def _transformer(x, ctx, st, name, heads, depth, lin, groups, xs=None, chunked_k
     return ops.conv2d(h.view(B, H, W, C), st, name + "/proj_out", pad=0, residual=x, gn_groups=groups)
 
 
-def unet_forward(st, cfg, x, timesteps, ctx, added_cond=None):
-    """x: (B,h,w,pad8(in_channels)) bf16 NHWC; timesteps int32 (B,); ctx (B,L,cross_dim) bf16.
-    Returns (B,h,w,pad8(out_channels)) bf16 NHWC (the reference returns NCHW; see train_step)."""
+def _time_embedding(st, cfg, timesteps, added_cond):
+    """The time embedding (plus add_embedding for a text_time config) of a UNet or ControlNet store: (B, 4 * block_out_channels[0])."""
     boc = cfg["block_out_channels"]
-    nb, lpb, lin, g = len(boc), cfg["layers_per_block"], cfg["use_linear_projection"], cfg["norm_num_groups"]
-    heads = _per_block(cfg["attention_head_dim"], nb)  # Flax: attention_head_dim is the head COUNT
-    depth = _per_block(cfg["transformer_layers_per_block"], nb)
-    ck = cfg.get("emulate_key_chunks", True)  # False: exact softmax over the text keys (see key_chunk_weights)
     te = timestep_embedding(timesteps, boc[0], cfg["flip_sin_to_cos"], cfg["freq_shift"]).requires_grad_(True)
     temb = ops.linear(ops.silu(ops.linear(te, st, "time_embedding/linear_1")), st, "time_embedding/linear_2")
     if cfg["addition_embed_type"] == "text_time":
@@ -537,31 +644,126 @@ def unet_forward(st, cfg, x, timesteps, ctx, added_cond=None):
         tide = timestep_embedding(tid.reshape(-1).to(torch.int32), cfg["addition_time_embed_dim"], True, 0.0).view(tid.shape[0], -1)
         a = ops.concat_channels(added_cond["text_embeds"].to(torch.bfloat16).contiguous(), tide).requires_grad_(True)
         temb = ops.add(temb, ops.linear(ops.silu(ops.linear(a, st, "add_embedding/linear_1")), st, "add_embedding/linear_2"))
-    # every resnet consumes silu(temb) and every cross-attention consumes ctx twice: hand out aliases whose gradients are
-    # summed by one launch each instead of a chain of binary adds
-    rowbias = _time_emb_projections(st, ops.silu(temb))  # {resnet path: (B, C_out) row bias of its first convolution}
-    ctx = _context_projections(st, ctx)  # {attn2 path: the block's [k|v] projections}
-    if not x.requires_grad:
-        x = x.detach().requires_grad_(True)  # anchors the autograd tape (weights are not autograd leaves)
-    # (x, xs): every block output travels with the GroupNorm statistics its producing GEMM accumulated (xs None after a concat)
-    x, xs = ops.conv2d(x, st, "conv_in", gn_groups=g)
-    skips = [x]
+    return temb
+
+
+def _down_blocks(st, cfg, x, xs, rowbias, ctx, tap=False):
+    """The down blocks from conv_in's output (x, xs) -> (x, xs, skips).  tap (ControlNet): every skip tensor has a second consumer, its
+    zero convolution, so the list holds aliases (ops.fanout sums the two gradients in one launch)."""
+    boc = cfg["block_out_channels"]
+    nb, lpb, lin, g = len(boc), cfg["layers_per_block"], cfg["use_linear_projection"], cfg["norm_num_groups"]
+    heads = _per_block(cfg["attention_head_dim"], nb)  # Flax: attention_head_dim is the head COUNT
+    depth = _per_block(cfg["transformer_layers_per_block"], nb)
+    ck = cfg.get("emulate_key_chunks", True)  # False: exact softmax over the text keys (see key_chunk_weights)
+    skips = []
+
+    def keep(x):
+        if tap:
+            x, alias = ops.fanout(x, 2)
+            skips.append(alias)
+        else:
+            skips.append(x)
+        return x
+
+    x = keep(x)
     for i, t in enumerate(cfg["down_block_types"]):
         for j in range(lpb):
             x, xs = _resnet(x, rowbias[f"down_blocks_{i}/resnets_{j}"], st, f"down_blocks_{i}/resnets_{j}", g, 1e-5, xs)
             if t == "CrossAttnDownBlock2D":
                 x, xs = _transformer(x, ctx, st, f"down_blocks_{i}/attentions_{j}", heads[i], depth[i], lin, g, xs, ck)
-            skips.append(x)
+            x = keep(x)
         if i != nb - 1:
             x, xs = ops.conv2d(x, st, f"down_blocks_{i}/downsamplers_0/conv", stride=2, pad=1, gn_groups=g)
-            skips.append(x)
+            x = keep(x)
+    return x, xs, skips
+
+
+def _mid_block(st, cfg, x, xs, rowbias, ctx):
+    boc = cfg["block_out_channels"]
+    nb, lin, g = len(boc), cfg["use_linear_projection"], cfg["norm_num_groups"]
+    heads, depth = _per_block(cfg["attention_head_dim"], nb), _per_block(cfg["transformer_layers_per_block"], nb)
     x, xs = _resnet(x, rowbias["mid_block/resnets_0"], st, "mid_block/resnets_0", g, 1e-5, xs)
-    x, xs = _transformer(x, ctx, st, "mid_block/attentions_0", heads[-1], depth[-1], lin, g, xs, ck)
-    x, xs = _resnet(x, rowbias["mid_block/resnets_1"], st, "mid_block/resnets_1", g, 1e-5, xs)
+    x, xs = _transformer(x, ctx, st, "mid_block/attentions_0", heads[-1], depth[-1], lin, g, xs, cfg.get("emulate_key_chunks", True))
+    return _resnet(x, rowbias["mid_block/resnets_1"], st, "mid_block/resnets_1", g, 1e-5, xs)
+
+
+def controlnet_cond_embedding(st, cfg, cond):
+    """The conditioning embedder (diffusers FlaxControlNetConditioningEmbedding): cond bf16 NHWC (B,H,W,pad8(conditioning_channels)) at
+    pixel size -> (B,h,w,block_out_channels[0]) at latent size.  SiLU follows every convolution but conv_out."""
+    e = "controlnet_cond_embedding"
+    if st.trainable and torch.is_grad_enabled() and not cond.requires_grad:
+        cond = cond.detach().requires_grad_(True)  # anchors the tape: the embedder's weight gradients come from its backward
+    h = ops.silu(ops.conv2d(cond, st, e + "/conv_in"))
+    for k in range(len(cfg["conditioning_embedding_out_channels"]) - 1):
+        h = ops.silu(ops.conv2d(h, st, f"{e}/blocks_{2 * k}"))
+        h = ops.silu(ops.conv2d(h, st, f"{e}/blocks_{2 * k + 1}", stride=2, pad=1))
+    return ops.conv2d(h, st, e + "/conv_out")
+
+
+def controlnet_forward_embedded(st, cfg, x, timesteps, ctx, embedding, added_cond=None):
+    """controlnet_forward from an already computed controlnet_cond_embedding (the sampler embeds the hint once per generate call)."""
+    g = cfg["norm_num_groups"]
+    temb = _time_embedding(st, cfg, timesteps, added_cond)
+    rowbias = _time_emb_projections(st, ops.silu(temb))
+    if st.trainable and torch.is_grad_enabled() and not ctx.requires_grad:
+        ctx = ctx.detach().requires_grad_(True)  # a frozen text encoder's context has no tape: anchor the to_k / to_v backward
+    ctx = _context_projections(st, ctx)
+    if not x.requires_grad:
+        x = x.detach().requires_grad_(True)
+    x, xs = ops.conv2d(x, st, "conv_in", residual=embedding, gn_groups=g)
+    x, xs, skips = _down_blocks(st, cfg, x, xs, rowbias, ctx, tap=True)
+    x, xs = _mid_block(st, cfg, x, xs, rowbias, ctx)
+    down = [ops.conv2d(s, st, f"controlnet_down_blocks_{i}", pad=0) for i, s in enumerate(skips)]
+    return down, ops.conv2d(x, st, "controlnet_mid_block", pad=0)
+
+
+def controlnet_forward(st, cfg, x, timesteps, ctx, cond, added_cond=None):
+    """diffusers FlaxControlNetModel.__call__ on a ControlNet store (controlnet_spec): x, timesteps, ctx, added_cond as unet_forward
+    takes them, cond bf16 NHWC (B,H,W,pad8(conditioning_channels)) at pixel size (sdt_nchw_f32_to_nhwc_bf16 of the [0, 1] image).
+    The embedded hint enters as conv_in's residual, the UNet's down and mid blocks run on this store, and a 1x1 convolution follows
+    every skip tensor and the mid block.  Returns (down_residuals: list in the order unet_forward appends its skips, mid_residual)."""
+    return controlnet_forward_embedded(st, cfg, x, timesteps, ctx, controlnet_cond_embedding(st, cfg, cond), added_cond)
+
+
+def unet_forward(st, cfg, x, timesteps, ctx, added_cond=None, control=None):
+    """x: (B,h,w,pad8(in_channels)) bf16 NHWC; timesteps int32 (B,); ctx (B,L,cross_dim) bf16.
+    Returns (B,h,w,pad8(out_channels)) bf16 NHWC (the reference returns NCHW; see train_step).
+    control: None, or (down_residuals, mid_residual[, scale]) from controlnet_forward; scale f32 (B,) per-sample factors or None (1).
+    Every decoder concatenation then reads skip + scale * residual and the mid block x + scale * mid_residual (ops.control_add).  On a
+    store that is not trainable conv_in and the down blocks run without a tape: nothing upstream of the additions is trained."""
+    boc = cfg["block_out_channels"]
+    nb, lpb, lin, g = len(boc), cfg["layers_per_block"], cfg["use_linear_projection"], cfg["norm_num_groups"]
+    heads = _per_block(cfg["attention_head_dim"], nb)  # Flax: attention_head_dim is the head COUNT
+    depth = _per_block(cfg["transformer_layers_per_block"], nb)
+    ck = cfg.get("emulate_key_chunks", True)  # False: exact softmax over the text keys (see key_chunk_weights)
+    temb = _time_embedding(st, cfg, timesteps, added_cond)
+    # every resnet consumes silu(temb) and every cross-attention consumes ctx twice: hand out aliases whose gradients are
+    # summed by one launch each instead of a chain of binary adds
+    rowbias = _time_emb_projections(st, ops.silu(temb))  # {resnet path: (B, C_out) row bias of its first convolution}
+    ctx = _context_projections(st, ctx)  # {attn2 path: the block's [k|v] projections}
+    down_r = mid_r = scale = None
+    if control is not None:
+        down_r, mid_r = list(control[0]), control[1]
+        scale = control[2] if len(control) > 2 else None
+    untaped = control is not None and not st.trainable
+    if not untaped and not x.requires_grad:
+        x = x.detach().requires_grad_(True)  # anchors the autograd tape (weights are not autograd leaves)
+    # (x, xs): every block output travels with the GroupNorm statistics its producing GEMM accumulated (xs None after a concat)
+    with torch.no_grad() if untaped else contextlib.nullcontext():
+        x, xs = ops.conv2d(x, st, "conv_in", gn_groups=g)
+        x, xs, skips = _down_blocks(st, cfg, x, xs, rowbias, ctx)
+    if control is not None:
+        if len(down_r) != len(skips):
+            raise ValueError(f"control: {len(down_r)} down residuals for the UNet's {len(skips)} skip tensors")
+        x, xs = ops.control_add(None, x, mid_r, scale), None  # the statistics described x before the addition
+    x, xs = _mid_block(st, cfg, x, xs, rowbias, ctx)
     rheads, rdepth = list(reversed(heads)), list(reversed(depth))
     for i, t in enumerate(cfg["up_block_types"]):
         for j in range(lpb + 1):
-            x = ops.concat_channels(x, skips.pop())  # statistics of a concatenation: the standalone pass
+            if control is not None:
+                x = ops.control_add(x, skips.pop(), down_r.pop(), scale)
+            else:
+                x = ops.concat_channels(x, skips.pop())  # statistics of a concatenation: the standalone pass
             x, xs = _resnet(x, rowbias[f"up_blocks_{i}/resnets_{j}"], st, f"up_blocks_{i}/resnets_{j}", g, 1e-5, None)
             if t == "CrossAttnUpBlock2D":
                 x, xs = _transformer(x, ctx, st, f"up_blocks_{i}/attentions_{j}", rheads[i], rdepth[i], lin, g, xs, ck)

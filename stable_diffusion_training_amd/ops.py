@@ -1043,6 +1043,62 @@ def concat_channels(a, b):
     return _ConcatChannels.apply(a, b)
 
 
+class _ControlAdd(Function):
+    """[a | skip + scale * res] in one launch (sdt_control_concat_add); a None: skip + scale * res."""
+
+    @staticmethod
+    def forward(ctx, a, skip, res, scale):
+        _check(skip, "control_add skip")
+        _check(res, "control_add res")
+        if skip.shape != res.shape:
+            raise _lib.SdtError(f"control_add: skip {tuple(skip.shape)} and res {tuple(res.shape)} differ")
+        if skip.dim() < 2 or skip.numel() == 0:
+            raise _lib.SdtError(f"control_add: skip {tuple(skip.shape)} must be a non-empty (B, ..., C) tensor")
+        Cb = skip.shape[-1]
+        rows = skip.numel() // Cb
+        Ca = 0
+        if a is not None:
+            _check(a, "control_add a")
+            Ca = a.shape[-1]
+            if a.shape[:-1] != skip.shape[:-1]:
+                raise _lib.SdtError(f"control_add: a {tuple(a.shape)} and skip {tuple(skip.shape)} differ in their rows")
+        if scale is not None and (scale.dtype != torch.float32 or not scale.is_contiguous() or tuple(scale.shape) != (skip.shape[0],)
+                                  or scale.device != skip.device):
+            raise _lib.SdtError(f"control_add: scale must be a contiguous float32 ({skip.shape[0]},) tensor on {skip.device}, got "
+                                f"{scale.dtype} {tuple(scale.shape)} on {scale.device}")
+        if res.device != skip.device or (a is not None and a.device != skip.device):
+            raise _lib.SdtError("control_add: a, skip and res must live on one device")
+        y = torch.empty(*skip.shape[:-1], Ca + Cb, dtype=BF16, device=skip.device)
+        call("sdt_control_concat_add", _ptr(a), skip.data_ptr(), res.data_ptr(), _ptr(scale), y.data_ptr(), rows,
+             rows // skip.shape[0], Ca, Cb, _stream())
+        ctx.meta = (None if a is None else a.shape, skip.shape)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        sa, sb = ctx.meta
+        need_skip, need_res = ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if sa is None:
+            return None, (dy if need_skip else None), (dy if need_res else None), None
+        dy = dy.contiguous()
+        Ca, Cb = sa[-1], sb[-1]
+        rows = dy.numel() // (Ca + Cb)
+        da = torch.empty(sa, dtype=BF16, device=dy.device)
+        db = torch.empty(sb, dtype=BF16, device=dy.device)
+        copy_cols(dy.view(rows, Ca + Cb), [da.view(rows, Ca), db.view(rows, Cb)], [Ca, Cb], rows, False)
+        return da, (db if need_skip else None), (db if need_res else None), None
+
+
+def control_add(a, skip, res, scale=None):
+    """concat(a, skip + scale * res) along the channels (a None: skip + scale * res), the sum formed in double and rounded to bf16 once.
+    scale: f32 (B,) per-sample factors for sampling, None = 1.  The backward is the column split of dy: da the left columns, the right
+    columns the gradient of res and of skip alike.  ValueError for a scale beside a res that requires grad: training runs at unit scale
+    (d res would be scale * dy, which no kernel here computes)."""
+    if scale is not None and res.requires_grad:
+        raise ValueError("control_add: a scale is for sampling only - res requires grad, and training runs at unit scale")
+    return _ControlAdd.apply(a, skip, res, scale)
+
+
 class _Add(Function):
     @staticmethod
     def forward(ctx, a, b):

@@ -23,9 +23,19 @@ class StableDiffusionPipeline:
     vae_params: host tree of the full VAE (decoder + post_quant_conv are loaded into a frozen store); configs as in load_models."""
 
     def __init__(self, unet, text_encoder, vae_params, unet_config, text_encoder_config, vae_config, scheduler=None,
-                 scaling_factor=0.18215, device=None):
+                 scaling_factor=0.18215, device=None, controlnet=None):
+        """controlnet: None, a nets.ControlNet (store + config; a training state's unet_state.controlnet samples in place), or
+        dict(config=, params=) as checkpoint.load_controlnet returns it (loaded into a frozen store)."""
         _lib.require_device()
         self.unet, self.text_encoder = _store_of(unet), _store_of(text_encoder)
+        self.controlnet = controlnet
+        if controlnet is not None and nets.inpaint_latent_channels(unet_config) is not None:
+            raise ValueError("a ControlNet on an inpainting UNet is not supported")
+        if isinstance(controlnet, dict):
+            cstore = ParamStore(nets.controlnet_spec(controlnet["config"]), device=torch.device(device) if device is not None else self.unet.device,
+                                trainable=False)
+            cstore.load(controlnet["params"])
+            self.controlnet = nets.ControlNet(cstore, controlnet["config"])
         self.unet_config, self.text_encoder_config, self.vae_config = unet_config, text_encoder_config, vae_config
         self.device = torch.device(device) if device is not None else self.unet.device
         self.vae_decoder = ParamStore(nets.vae_decoder_spec(vae_config), device=self.device, trainable=False)
@@ -114,7 +124,7 @@ class StableDiffusionPipeline:
     @torch.no_grad()
     def generate(self, prompt_ids, num_inference_steps=50, height=512, width=512, guidance_scale=7.5, latents=None,
                  neg_prompt_ids=None, generator=None, return_latents=False, guidance_rescale=0.0, image=None, mask=None,
-                 masked_eps=None):
+                 masked_eps=None, control_image=None, conditioning_scale=1.0, control_negative=True, aux=None):
         """_generate (:160-254).  prompt_ids int (B,77) device tensor ((B,2,77) for an SDXL-mode text encoder: _sdxl_conditioning;
         pass scaling_factor=0.13025 for the SDXL VAE); latents optional f32 (B,C,h,w) initial noise; returns the
         image (B,H,W,3) float32 in [0,1] on the device (and the final latents when return_latents).  guidance_rescale in [0, 1]
@@ -125,11 +135,29 @@ class StableDiffusionPipeline:
         initial latents, its draw comes from `generator` unless masked_eps (B,h,w,L) is given) and before every UNet call
         sdt_inpaint_pack_input assembles [latents | mask | masked-image latents] for the doubled batch from the tensor the scheduler
         kernels write.  The untouched pixels are NOT composited back over the output.  ValueError for image / mask on a plain UNet,
-        their absence on an inpainting one, and wrong shapes."""
+        their absence on an inpainting one, and wrong shapes.
+        A pipeline built with controlnet= needs control_image, f32 (B, conditioning_channels, H, W) in [0, 1]: it is packed and embedded
+        once (nets.controlnet_cond_embedding) and repeated for the doubled batch; every step runs the ControlNet on the doubled input
+        and hands its residuals to the UNet with the per-sample scale vector f32 (2B,) = conditioning_scale, whose negative half is 0
+        with control_negative=False (control on the prompt half only; diffusers' guess mode without its per-layer ramp).  ValueError for
+        control_image without a ControlNet and the reverse, a wrong shape, and an inpainting UNet.
+        aux: an optional dict that receives the FIRST step's tensors for parity tests - unet_input, timesteps, ctx, pred and, with a
+        ControlNet, control_embedding, control_down, control_mid and control_scale."""
         if height % 8 != 0 or width % 8 != 0:
             raise ValueError(f"`height` and `width` have to be divisible by 8 but are {height} and {width}.")
         if not 0.0 <= guidance_rescale <= 1.0:
             raise ValueError(f"guidance_rescale {guidance_rescale} must lie in [0, 1]")
+        cn = self.controlnet
+        if cn is None and control_image is not None:
+            raise ValueError("control_image needs a pipeline built with controlnet=")
+        if cn is not None:
+            if nets.inpaint_latent_channels(self.unet_config) is not None:
+                raise ValueError("a ControlNet on an inpainting UNet is not supported")
+            if control_image is None:
+                raise ValueError("a pipeline built with controlnet= samples from a control_image")
+            want = (prompt_ids.shape[0], cn.config["conditioning_channels"], height, width)
+            if not torch.is_tensor(control_image) or tuple(control_image.shape) != want:
+                raise ValueError(f"Unexpected control_image shape, got {tuple(getattr(control_image, 'shape', ()))}, expected {want}")
         dev = self.device
         stream = torch.cuda.current_stream().cuda_stream
         B = prompt_ids.shape[0]
@@ -175,14 +203,35 @@ class StableDiffusionPipeline:
             mlat_nhwc, lmask = self._inpaint_conditioning(image, mask, masked_eps, generator, L_inp, height, width)
             x_in = torch.empty(2 * B, h, w, (2 * C + 1 + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)
         t_dev = torch.empty(2 * B, dtype=torch.int32, device=dev)
-        for t in self.scheduler.set_timesteps(num_inference_steps):
+        embedding = scale = None
+        if cn is not None:  # the hint: packed and embedded once, repeated for [negative | prompt]
+            cn.store.prepare()
+            ci = control_image.to(device=dev, dtype=torch.float32).contiguous()
+            hint = torch.empty(B, height, width, (ci.shape[1] + 7) // 8 * 8, dtype=torch.bfloat16, device=dev)
+            _lib.call("sdt_nchw_f32_to_nhwc_bf16", ci.data_ptr(), hint.data_ptr(), B, ci.shape[1], height, width, hint.shape[3], stream)
+            ops.gn_arena_begin(dev)
+            e = nets.controlnet_cond_embedding(cn.store, cn.config, hint)
+            ops.gn_arena_end(dev)
+            embedding = torch.cat([e, e]).contiguous()
+            scale = torch.full((2 * B,), float(conditioning_scale), dtype=torch.float32, device=dev)
+            if not control_negative:
+                scale[:B] = 0.0
+        for step, t in enumerate(self.scheduler.set_timesteps(num_inference_steps)):
             t_dev.fill_(int(t))
             if L_inp is not None:
                 _lib.call("sdt_inpaint_pack_input", x_lat.data_ptr(), mlat_nhwc.data_ptr(), lmask.data_ptr(), x_in.data_ptr(), 2 * B, B, C,
                           h, w, cpad, mlat_nhwc.shape[3], x_in.shape[3], stream)
             ops.gn_arena_begin(dev)
-            pred = nets.unet_forward(self.unet, self.unet_config, x_in, t_dev, context, added)
+            control = None
+            if cn is not None:
+                down, mid = nets.controlnet_forward_embedded(cn.store, cn.config, x_in, t_dev, context, embedding, added)
+                control = (down, mid, scale)
+            pred = nets.unet_forward(self.unet, self.unet_config, x_in, t_dev, context, added, control=control)
             ops.gn_arena_end(dev)
+            if aux is not None and step == 0:  # the first step's tensors, for parity tests
+                aux.update(unet_input=x_in.clone(), timesteps=t_dev.clone(), ctx=context, pred=pred.clone())
+                if cn is not None:
+                    aux.update(control_embedding=embedding, control_down=[d.clone() for d in down], control_mid=mid.clone(), control_scale=scale)
             self.scheduler.cfg_step(pred, lat, x_lat, t, guidance_scale, guidance_rescale)  # guidance + x_t -> x_{t-1} + next input
 
         z = torch.empty(B, h, w, cpad, dtype=torch.bfloat16, device=dev)

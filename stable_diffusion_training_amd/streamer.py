@@ -18,7 +18,7 @@ class DataLoader:
                  maximum_resolution_areas=(512 ** 2,), bucket_lower_bound_resolutions=(256,), numb_of_worker_thread=1,
                  queue_get_timeout=60, chunk_number=0, seed=0, context_concatenation_multiplier=1, *,
                  batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu", text_towers=1,
-                 loss_masks=False, prior_every=0, prior_loss_weight=1.0, inpaint_masks=False, placeholder_ids=None):
+                 loss_masks=False, prior_every=0, prior_loss_weight=1.0, inpaint_masks=False, placeholder_ids=None, conditioning_images=False):
         if len(maximum_resolution_areas) != len(bucket_lower_bound_resolutions):
             raise ValueError("number of elements in maximum_resolution_areas and bucket_lower_bound_resolutions is not match!")
         if training_batch_size % world_size:
@@ -35,6 +35,11 @@ class DataLoader:
             raise ValueError(f"prior_every={prior_every!r}: 0 (no class images) or n > 0 (every n-th sample is one)")
         self.loss_masks, self.prior_every, self.prior_loss_weight = bool(loss_masks), prior_every, float(prior_loss_weight)
         self.inpaint_masks = bool(inpaint_masks)
+        if isinstance(conditioning_images, bool):
+            conditioning_images = 3 if conditioning_images else 0
+        if not isinstance(conditioning_images, int) or conditioning_images < 0:
+            raise ValueError(f"conditioning_images={conditioning_images!r}: False, True (3 channels) or the ControlNet's conditioning_channels")
+        self.conditioning_images = conditioning_images  # channels of the conditioning image, 0: none
         self.placeholder_ids = self._check_placeholders(placeholder_ids, text_towers, context_window)
         self.buckets = [tuple(int(v) for v in b) for area, lo in zip(maximum_resolution_areas, bucket_lower_bound_resolutions)
                         for b in calculate_resolution_array(area, lo, 64)]
@@ -92,7 +97,9 @@ class DataLoader:
         sample of the global batch (global index % n == n - 1) as a class image and adds loss_weight f32 (B,): 1.0 for instance images,
         prior_loss_weight for class images (DreamBooth prior preservation).  inpaint_masks=True adds inpaint_mask f32 (B, bucket[0],
         bucket[1]) for an inpainting UNet: one seeded rectangle of ones (the region to repaint) per image, from a third generator of its
-        own.  The defaults add none of them.
+        own.  conditioning_images=True (3 channels) or n adds conditioning_pixel_values f32 (B, n, bucket[0], bucket[1]) in [0, 1] for a ControlNet: a
+        seeded coarse 8 x 8 pattern per image, nearest-neighbour enlarged to the pixel size, from a fourth generator.  The defaults add
+        none of them.
         placeholder_ids (a list of ids, or one list per tower for text_towers=2) overwrites the positions after BOS of every caption
         window with those ids - the caption "<sks> ..." of a textual-inversion run; the other entries keep their values."""
         if self._cursor >= len(self._plan):
@@ -134,6 +141,11 @@ class DataLoader:
                 y0, x0 = int(torch.randint(0, b0 - hh + 1, (1,), generator=gi)), int(torch.randint(0, b1 - ww + 1, (1,), generator=gi))
                 mask[i, y0: y0 + hh, x0: x0 + ww] = 1.0
             batch["inpaint_mask"] = mask
+        if self.conditioning_images:
+            gc = torch.Generator().manual_seed(((int(self.seed) * 1_000_003 + int(self.chunk_number)) * 1_000_003 + index * 64 + self.rank) ^ 0x1E3779B97F4A7C15)
+            coarse = torch.rand(per_rank, self.conditioning_images, 8, 8, generator=gc)
+            ys, xs = torch.arange(b0) * 8 // b0, torch.arange(b1) * 8 // b1
+            batch["conditioning_pixel_values"] = coarse[:, :, ys][:, :, :, xs].contiguous()
         if self.prior_every:
             first = self.rank * per_rank  # this shard's first sample in the global batch
             batch["loss_weight"] = torch.tensor([self.prior_loss_weight if (first + i) % self.prior_every == self.prior_every - 1 else 1.0

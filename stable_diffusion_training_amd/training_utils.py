@@ -88,6 +88,8 @@ class TrainState:
     LoRA (lora=): `store` stays the network's - frozen - weight store, `adapter` is the lora.LoraAdapter whose own store holds the trained
     leaves and takes the optimizer step (None with an empty hyper: a frozen text encoder that only runs its forward).
     New tokens (new_tokens=): the text state's `tokens` is the tokens.TokenAdapter hung on its frozen store; its store of trained rows
+    takes the optimizer step.
+    ControlNet (controlnet=): the UNet state's `controlnet` is the nets.ControlNet (store + config) trained on the frozen UNet; its store
     takes the optimizer step."""
     apply_fn: Callable
     store: ParamStore
@@ -95,11 +97,14 @@ class TrainState:
     hyper: dict = field(default_factory=dict)
     adapter: Any = None
     tokens: Any = None
+    controlnet: Any = None
 
     @property
     def opt_store(self):
         """The store that takes the optimizer step: the weight store itself, the adapter's store, the token store, or None (frozen,
-        neither adapter nor tokens)."""
+        neither adapter nor tokens); a ControlNet's store on the UNet state that carries one."""
+        if self.controlnet is not None:
+            return self.controlnet.store
         if self.adapter is not None:
             return self.adapter.store
         if self.tokens is not None:
@@ -121,7 +126,8 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                                  excluded_layer_pattern_from_weight_decay=(), excluded_layer_from_quantization=(),
                                  lion_8bit_block_size=None, quantize_unet_state=False, quantize_text_encoder_state=False,
                                  with_unet_ema=False, with_text_encoder_ema=False, device="cuda", lr_scheduler="constant",
-                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0, optimizer="lion", lora=None, new_tokens=None):
+                                 lr_schedule=None, ema_schedule=None, ema_rate=0.0, optimizer="lion", lora=None, new_tokens=None,
+                                 controlnet=None):
     """training_utils.py:281-427.  lr = learning_rate / adam_to_lion_scale_factor, wd = 1e-2 * scale, b1=.9, b2=.99,
     chain(clip_by_global_norm(1), lion_8bit | lion).  Builds the flat HBM stores and loads the weights.
     lr_scheduler / lr_schedule / ema_schedule / ema_rate: the per-step schedules of lr_schedule.resolve, installed in each trained store
@@ -141,8 +147,31 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
     the trained rows (TrainState.tokens, tokens.attach), and the text encoder's settings above - rate, optimizer, quantisation switches,
     schedules, EMA - configure the TOKEN store.  Alone, the UNet has no adapter and steps nothing; with lora=dict(unet=LoraConfig,
     text_encoder=None | "frozen") the UNet's adapter trains beside the tokens (pivotal tuning).  A text-encoder LoraConfig beside new
-    tokens is refused."""
+    tokens is refused.
+    controlnet: None, or dict(config=nets.controlnet_config(...)[, params=host tree]) - a loaded ControlNet, or one initialised from the
+    UNet (nets.controlnet_from_unet).  Both base stores are built frozen; the UNet state's `controlnet` holds the ControlNet's store, which
+    the UNet's settings above configure and which steps; the text encoder only runs its forward.  Refused beside lora= or new_tokens=, on
+    an inpainting UNet, and with a config that does not extend the UNet's."""
     out = {"unet_state": None, "text_encoder_state": None}
+    if controlnet is not None:
+        if not isinstance(controlnet, dict) or "config" not in controlnet or set(controlnet) - {"config", "params"}:
+            raise ValueError(f"controlnet: None or dict(config=nets.controlnet_config(...)[, params=tree]), not {controlnet!r}")
+        if lora is not None or new_tokens is not None:
+            raise ValueError("controlnet: a ControlNet beside a LoRA adapter or new tokens is not supported")
+        if not (train_unet and train_text_encoder):
+            raise ValueError("controlnet: needs both states (train_unet and train_text_encoder)")
+        ccfg, ucfg = controlnet["config"], models["unet"]["config"]
+        if nets.inpaint_latent_channels(ucfg) is not None:
+            raise ValueError("controlnet: a ControlNet on an inpainting UNet is not supported")
+        if "conditioning_embedding_out_channels" not in ccfg or "conditioning_channels" not in ccfg:
+            raise ValueError("controlnet: the config needs conditioning_embedding_out_channels and conditioning_channels "
+                             "(nets.controlnet_config)")
+        f = 2 ** (len(models["vae"]["config"]["block_out_channels"]) - 1) if "vae" in models else 8
+        nets.controlnet_config(ucfg, ccfg["conditioning_embedding_out_channels"], ccfg["conditioning_channels"], vae_downscale=f)
+        for k in ("block_out_channels", "down_block_types", "layers_per_block", "in_channels", "cross_attention_dim", "attention_head_dim",
+                  "use_linear_projection", "transformer_layers_per_block", "norm_num_groups", "addition_embed_type"):
+            if _plain(ccfg.get(k)) != _plain(ucfg.get(k)):
+                raise ValueError(f"controlnet: the config's {k}={ccfg.get(k)!r} differs from the UNet's {ucfg.get(k)!r}")
     if new_tokens is not None:
         if not isinstance(new_tokens, tokens_mod.TokenConfig):
             raise ValueError(f"new_tokens: None or a tokens.TokenConfig, not {new_tokens!r}")
@@ -163,7 +192,8 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
             raise ValueError("lora: needs both states (train_unet and train_text_encoder); the text encoder is frozen by "
                              "text_encoder='frozen'")
         lora = {"unet": lora["unet"], "text_encoder": te_l}
-    frozen = lora is not None or new_tokens is not None  # the base stores only run; adapters' / the tokens' own stores step
+    # the base stores only run; adapters' / the tokens' / the ControlNet's own stores step
+    frozen = lora is not None or new_tokens is not None or controlnet is not None
     opt_cls, opt = optimizers.parse(optimizer)
 
     def make(spec, weights, cfg, fn, lr, quant, ema, which):
@@ -177,7 +207,19 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
         store.load(weights)
         adapter = lora_mod.attach(store, lora[which], **okw) if lora is not None and lora[which] is not None else None
         toks = tokens_mod.attach(store, new_tokens, **okw) if new_tokens is not None and which == "text_encoder" else None
-        state = TrainState(fn, store, cfg, hyper if not frozen or adapter is not None or toks is not None else {}, adapter, toks)
+        cn = None
+        if controlnet is not None and which == "unet":  # the ControlNet's own store takes the UNet's keywords and the optimizer step
+            ccfg = controlnet["config"]
+            cstore = ParamStore(nets.controlnet_spec(ccfg), device=device, **okw)
+            cw = controlnet.get("params")
+            if cw is not None and any(isinstance(v, dict) for v in cw.values()):
+                from .checkpoint import flatten_tree
+                cw = flatten_tree(cw)
+            cstore.load(cw if cw is not None else nets.controlnet_from_unet(weights, ccfg))
+            cstore.controlnet_config = ccfg  # marks the store: save_model refuses it (and its EMA view) as UNet weights
+            cn = nets.ControlNet(cstore, ccfg)
+        state = TrainState(fn, store, cfg, hyper if not frozen or adapter is not None or toks is not None or cn is not None else {},
+                           adapter, toks, cn)
         if sched is not None and state.opt_store is not None:
             state.opt_store.set_schedule(lr=sched[0], ema=sched[1])
         return state
@@ -195,8 +237,12 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
     return out
 
 
+def _plain(v):
+    return list(v) if isinstance(v, (tuple, list)) else v
+
+
 def on_device_model_training_state(training_config: TrainingConfig, models=None, device="cuda", *, lr_schedule=None,
-                                   ema_schedule=None, optimizer="lion", lora=None, new_tokens=None):
+                                   ema_schedule=None, optimizer="lion", lora=None, new_tokens=None, controlnet=None):
     """training_utils.py:430-501.  `models`: load_models' result - host weight trees + configs
     ({"unet": {"unet_params", "config"}, "vae": {"vae_params", "config"}, "text_encoder": {...}}); None reads the
     diffusers directory at training_config.model_path (checkpoint.load_models).  Note the reference passes NEITHER learning
@@ -211,7 +257,9 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
     and the EMA views wrap the adapters' stores (None for a text encoder without an adapter).
     new_tokens: create_lion_optimizer_states' - a tokens.TokenConfig trains placeholder-token embeddings on the frozen text encoder, alone or
     beside a UNet LoRA.  The text state's `tokens` is the TokenAdapter and its EMA view wraps the token store; a UNet without an adapter
-    has no EMA view (None)."""
+    has no EMA view (None).
+    controlnet: create_lion_optimizer_states' - dict(config=[, params=]) trains a ControlNet on the frozen UNet: unet_state.controlnet
+    holds its store and config, the UNet EMA view wraps that store, the text encoder has none."""
     _lib.require_device()
     if models is None:
         models = load_models(training_config)
@@ -224,7 +272,7 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
         quantize_text_encoder_state=training_config.quantize_text_encoder_state,
         with_unet_ema=training_config.accumulate_unet_ema, with_text_encoder_ema=training_config.accumulate_text_encoder_ema,
         device=device, lr_scheduler=training_config.lr_scheduler, lr_schedule=lr_schedule, ema_schedule=ema_schedule,
-        ema_rate=training_config.ema_rate, optimizer=optimizer, lora=lora, new_tokens=new_tokens)
+        ema_rate=training_config.ema_rate, optimizer=optimizer, lora=lora, new_tokens=new_tokens, controlnet=controlnet)
     vae_cfg = models["vae"]["config"]
     vae_store = ParamStore(nets.vae_encoder_spec(vae_cfg), device=device, trainable=False)
     vae_store.load(models["vae"]["vae_params"])
@@ -451,6 +499,39 @@ def _check_inpaint_entries(batch, unet_cfg, device):
             raise ValueError("masked_latent_moments must be contiguous")
 
 
+CONTROL_KEYS = ("conditioning_pixel_values",)  # the batch entry a ControlNet state's step reads (diffusers' name)
+
+
+def _check_control_entries(batch, controlnet, device):
+    """ValueError for a conditioning_pixel_values entry that does not fit the state or the batch's image (which _check_batch has
+    validated): a ControlNet state needs it, f32 NCHW (B, conditioning_channels, H, W) at pixel size - the size of pixel_values, or
+    f times the latent size of latent_moments - contiguous on the step's device; a state without a ControlNet refuses it."""
+    cond = batch.get("conditioning_pixel_values")
+    if controlnet is None:
+        if cond is not None:
+            raise ValueError("conditioning_pixel_values need a ControlNet state (on_device_model_training_state(controlnet=)); this "
+                             "UNet state carries none")
+        return
+    if cond is None:
+        raise ValueError("a ControlNet state's batch needs conditioning_pixel_values (f32 (B, conditioning_channels, H, W) in [0, 1])")
+    cc = int(controlnet.config["conditioning_channels"])
+    if "latent_moments" in batch:
+        m = batch["latent_moments"]
+        f = 2 ** (len(controlnet.config["conditioning_embedding_out_channels"]) - 1)
+        want, where = (int(m.shape[0]), cc, int(m.shape[1]) * f, int(m.shape[2]) * f), f"latent_moments (B,h,w,2L) and the downscale {f}"
+    else:
+        px = batch["pixel_values"]
+        want, where = (int(px.shape[0]), cc, int(px.shape[2]), int(px.shape[3])), "pixel_values (B,3,H,W)"
+    if not torch.is_tensor(cond) or cond.dtype != torch.float32:
+        raise ValueError(f"conditioning_pixel_values must be a float32 tensor, not {getattr(cond, 'dtype', type(cond))}")
+    if not _on_device(cond, device):
+        raise ValueError(f"conditioning_pixel_values live on {cond.device}, the step runs on {device}")
+    if tuple(cond.shape) != want:
+        raise ValueError(f"conditioning_pixel_values have shape {tuple(cond.shape)}; beside {where}: {want}")
+    if not cond.is_contiguous():
+        raise ValueError("conditioning_pixel_values must be contiguous")
+
+
 def _check_batch(batch, unet_cfg, frozen_vae_state, device, masked_loss_floor=0.0, normalize_masked_area=False):
     """ValueError for a batch train_step cannot run, before any kernel.  Returns whether the batch holds cached moments."""
     has_px, has_mom = "pixel_values" in batch, "latent_moments" in batch
@@ -556,6 +637,14 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     image, and loss_mask stays independent of inpaint_mask.  aux= taps gain "inpaint_mask" (latent size, 0/1), "masked_latents" (f32
     NCHW), "masked_moments" and "unet_input" (the bf16 tensor handed to the UNet).  ValueError for an inpainting UNet without the mask,
     either key on a plain UNet, a wrong dtype, device, shape or layout, and masked_latent_moments without latent_moments.
+    ControlNet (TrainState.controlnet on the UNet state; include/sdt.h "CONTROLNET"): the batch must hold
+    "conditioning_pixel_values", f32 NCHW (B, conditioning_channels, H, W) contiguous on the step's device, in [0, 1], at pixel size
+    (pixel_values' size, or f times the latent size of latent_moments).  After the front the image is packed to bf16 NHWC,
+    nets.controlnet_forward runs on the ControlNet's (trained) store, and the frozen UNet takes its residuals at unit scale
+    (unet_forward(control=), ops.control_add); the loss with every option, the clip and the optimizer act on the ControlNet's store
+    alone.  aux= taps gain "control_hint", "control_down" (list) and "control_mid".  ValueError for a batch without the key or with a
+    key of another dtype, device, shape or layout, the key on a state without a ControlNet, a reducer, a LoRA adapter or new tokens
+    beside the ControlNet, an inpainting UNet, and a trainable base store.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
     _check_loss_type(loss_type, huber_c, huber_schedule)
     text_time = unet_state.config.get("addition_embed_type") == "text_time"
@@ -576,6 +665,20 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     elif getattr(unet_state, "tokens", None) is not None or getattr(ts, "tokens", None) is not None or getattr(us, "tokens", None) is not None:
         raise ValueError("new tokens: the text-encoder state must carry the TokenAdapter its store carries (TrainState.tokens; "
                          "create_lion_optimizer_states(new_tokens=) builds both)")
+    cn = getattr(unet_state, "controlnet", None)
+    if cn is not None:
+        if reducer is not None:
+            raise ValueError("ControlNet: data-parallel training is not supported - the GradReducer would have to be built over the "
+                             "ControlNet's store (TrainState.controlnet.store)")
+        if adapters or tk is not None or getattr(us, "adapter", None) is not None or getattr(ts, "tokens", None) is not None:
+            raise ValueError("ControlNet: a LoRA adapter or new tokens beside a ControlNet are not supported")
+        if nets.inpaint_latent_channels(unet_state.config) is not None:
+            raise ValueError("ControlNet: an inpainting UNet is not supported")
+        if us.trainable or ts.trainable:
+            raise ValueError("ControlNet: a trainable base store is not supported - the UNet and the text encoder are frozen and only "
+                             "the ControlNet's store steps")
+    elif getattr(text_encoder_state, "controlnet", None) is not None:
+        raise ValueError("ControlNet: the UNet state carries the ControlNet, not the text-encoder state")
     lora = bool(adapters) or tk is not None  # the frozen-base step: adapters' and / or the tokens' own stores are the ones that step
     if adapters:
         if us.trainable or ts.trainable or unet_state.adapter is None:
@@ -586,9 +689,12 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                              "GradReducer over the adapter stores (TrainState.adapter.store) instead of the frozen weight stores")
     # the stores that are zeroed, accumulated into and stepped: the weight stores themselves, or the adapters' / the tokens' own
     opt_stores = ([a.store for a in adapters] + ([tk.store] if tk is not None else [])) if lora else [us, ts]
+    if cn is not None:
+        opt_stores = [cn.store]
     sched, sched_state = frozen_noise_scheduler_state.call, frozen_noise_scheduler_state.params
     dev = us.device
     cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev, masked_loss_floor, normalize_masked_area)
+    _check_control_entries(batch, cn, dev)
     masked = any(k in batch for k in LOSS_KEYS)
     inpaint = "inpaint_mask" in batch  # (_check_batch: exactly the batches of an inpainting UNet)
     robust = LOSS_TYPES[loss_type]  # 0: the squared error
@@ -617,7 +723,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         else:
             sl = slice(k * B, (k + 1) * B)
             kc = batch["input_ids"].shape[0] // N  # text-encoder rows per sample
-            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids", "masked_latent_moments") + LOSS_KEYS + INPAINT_KEYS}
+            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids", "masked_latent_moments") + LOSS_KEYS + INPAINT_KEYS + CONTROL_KEYS}
             mb["input_ids"] = batch["input_ids"][k * B * kc: (k + 1) * B * kc]
             rnd = {n: v[sl] for n, v in rand.items()}
 
@@ -654,6 +760,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                     ad.merge("master")
                 if tk is not None:
                     tk.select("master")  # (no launch: the embedding reads the trained rows where they are)
+            elif k == 0 and cn is not None:
+                cn.store.prepare()  # (the frozen mirrors stay as the load left them)
             elif k == 0:
                 us.prepare()
                 ts.prepare()
@@ -743,8 +851,21 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                 tid[:, 0::4].fill_(H)
                 tid[:, 1::4].fill_(W)
             added = {"text_embeds": pooled if sdxl else mb["text_embeds"], "time_ids": tid}
+        hint = down_r = mid_r = None
+        if cn is not None:
+            # the conditioning image f32 NCHW in [0, 1] -> bf16 NHWC, then the ControlNet on its own (trained) store; its residuals enter
+            # the frozen UNet at unit scale and the tape starts at those additions
+            cpv = mb["conditioning_pixel_values"]
+            hint = torch.empty(B, cpv.shape[2], cpv.shape[3], -(-cpv.shape[1] // 8) * 8, dtype=torch.bfloat16, device=dev)
+            _lib.call("sdt_nchw_f32_to_nhwc_bf16", cpv.data_ptr(), hint.data_ptr(), B, cpv.shape[1], cpv.shape[2], cpv.shape[3],
+                      hint.shape[3], stream)
+            with trace.phase("controlnet_forward"):
+                down_r, mid_r = nets.controlnet_forward(cn.store, cn.config, noisy, timesteps, ctx, hint, added)
         with trace.phase("unet_forward"):
-            pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added)
+            if cn is not None:
+                pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added, control=(down_r, mid_r))
+            else:
+                pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added)
 
         # MSE (+ min-SNR), forward and d loss / d pred in one launch  (training_utils.py:704-709)
         wts = None
@@ -793,6 +914,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             if inpaint:
                 aux.update(inpaint_mask=(lmask >= 0.5).to(torch.float32), masked_latents=mlat, unet_input=noisy.detach(),
                            masked_moments=mmoments)
+            if cn is not None:
+                aux.update(control_hint=hint, control_down=[r.detach() for r in down_r], control_mid=mid_r.detach())
 
         # reverse mode through UNet and text encoder                  (training_utils.py:719-729)
         if fused_norm:
@@ -809,7 +932,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     if K == 1:
         # one process: the norm clip_by_global_norm needs is that of the gradients as the weight-gradient kernels write them - they leave
         # its partial sums behind (ops.sq_begin / sq_end), and the 4-byte-per-parameter pass over the finished buffer is not needed
-        loss, sq_u, sq_t, lps = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora)
+        loss, sq_u, sq_t, lps = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora and cn is None)
         grad_source = "grad"
         # data-parallel mean of the gradients (implicit all-reduce under GSPMD in the reference)
         if reducer is not None:
@@ -889,7 +1012,7 @@ class _GraphedStep:
 
     def __init__(self, fn, warmup=2, reducer=None):
         self.fn, self.warmup, self.calls = fn, warmup, 0
-        self.graph = self.static = self.static_rand = self.out = self.sig = self.loss_keys = self.inpaint_keys = None
+        self.graph = self.static = self.static_rand = self.out = self.sig = self.loss_keys = self.inpaint_keys = self.control_keys = None
         # multi-rank: graph A (forward + backward) | eager bucketed all-reduce behind per-bucket events | graph B (optimizer)
         self.reducer = reducer if (reducer is not None and reducer.active) else None
         self.graph_b = self.plan = None
@@ -901,6 +1024,7 @@ class _GraphedStep:
         self.sig = self._sig(us, ts, ue, te, rng, vae, sched, rand)
         self.loss_keys = tuple(k in batch for k in LOSS_KEYS)
         self.inpaint_keys = tuple(k in batch for k in INPAINT_KEYS)
+        self.control_keys = tuple(k in batch for k in CONTROL_KEYS)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         if rng is not None and hasattr(g, "register_generator_state"):
@@ -991,6 +1115,9 @@ class _GraphedStep:
         if self.inpaint_keys != tuple(k in batch for k in INPAINT_KEYS):
             raise ValueError(f"this step was captured {'with' if self.inpaint_keys[0] else 'without'} inpaint_mask in its batch and replays "
                              "those launches: a batch that adds or drops it needs a step table of its own")
+        if self.control_keys != tuple(k in batch for k in CONTROL_KEYS):
+            raise ValueError(f"this step was captured {'with' if self.control_keys[0] else 'without'} conditioning_pixel_values in its "
+                             "batch and replays those launches: a batch that adds or drops it needs a step table of its own")
         for k, v in self.static.items():
             v.copy_(batch[k], non_blocking=True)
         if rand is not None:
@@ -1027,7 +1154,8 @@ def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_pa
     normalize_masked_area for batches with a loss_mask, or loss_type / huber_c / huber_schedule.  A captured step replays the launches
     of the batch it was captured with: it
     raises ValueError for a later batch that adds or drops loss_mask / loss_weight, or inpaint_mask (an inpainting UNet's batches
-    always carry it; the static buffers take the mask and, for cached batches, masked_latent_moments like any other tensor key)."""
+    always carry it; the static buffers take the mask and, for cached batches, masked_latent_moments like any other tensor key), or
+    conditioning_pixel_values (a ControlNet state's batches always carry it; CONTROL_KEYS)."""
     import os
     B = per_device_batch or training_config.batch_size
     if not isinstance(micro_batches, int) or micro_batches < 1:
