@@ -31,7 +31,11 @@ the text encoder's rate / optimizer / EMA settings configure the token store, an
 --controlnet [DIR] ("controlnet": true or a directory): trains a ControlNet on the frozen UNet and text encoder - loaded from DIR
 (checkpoint.load_controlnet) or initialised from the UNet (nets.controlnet_from_unet; "controlnet_channels" sets the embedder's widths) -
 from batches with a conditioning image per sample; the UNet's rate / optimizer / EMA settings configure its store, every chunk writes
-<model>-controlnet (and -controlnet-EMA), and --cache-latents keeps the conditioning images beside the moments."""
+<model>-controlnet (and -controlnet-EMA), and --cache-latents keeps the conditioning images beside the moments.
+--ip-adapter [DIR] ("ip_adapter": true or a directory): trains an IP-Adapter on the frozen UNet and text encoder - loaded from DIR
+(checkpoint.load_ip_adapter) or initialised from the UNet (nets.ip_adapter_from_unet; "ip_adapter_embed_dim", "ip_adapter_tokens" and
+"ip_adapter_drop_rate" set the embedding width, the token count and the loader's image-prompt dropout).  The loader adds image_embeds,
+the adapter is written to <model>-ip-adapter (and -ip-adapter-EMA), and --cache-latents keeps the embeddings beside the moments."""
 import argparse
 import json
 import os
@@ -45,7 +49,7 @@ import torch.distributed as dist
 
 from stable_diffusion_training_amd import dp, latent_cache, lora, nets, tokens
 from stable_diffusion_training_amd import training_utils as tu
-from stable_diffusion_training_amd.checkpoint import gather_rng_states, load_controlnet, save_controlnet
+from stable_diffusion_training_amd.checkpoint import gather_rng_states, load_controlnet, load_ip_adapter, save_controlnet, save_ip_adapter
 from stable_diffusion_training_amd.streamer import DataLoader
 
 
@@ -122,9 +126,21 @@ def main(config_dict, models=None, tokenizer=None, log=print):
             f = 2 ** (len(models["vae"]["config"]["block_out_channels"]) - 1)
             control = dict(config=nets.controlnet_config(models["unet"]["config"], tuple(config_dict.get("controlnet_channels", (16, 32, 96, 256))),
                                                          vae_downscale=f))
+    ip_cfg = None
+    if config_dict.get("ip_adapter"):  # an IP-Adapter on the frozen UNet: loaded from a directory, or initialised from the UNet
+        if world > 1:
+            raise ValueError("ip_adapter: IP-Adapter training runs on one GPU (train_step refuses a reducer with an IP-Adapter)")
+        if isinstance(config_dict["ip_adapter"], str):
+            ip_cfg = load_ip_adapter(config_dict["ip_adapter"])
+        else:
+            ip_cfg = dict(config=nets.ip_adapter_config(models["unet"]["config"], int(config_dict.get("ip_adapter_embed_dim", 1024)),
+                                                        int(config_dict.get("ip_adapter_tokens", 4))))
     loss_loader_kw = dict(inpaint_masks=inpaint, loss_masks=use_mask,
                           conditioning_images=int(control["config"]["conditioning_channels"]) if control is not None else False, prior_every=2 if prior_w is not None else 0,
                           prior_loss_weight=1.0 if prior_w is None else float(prior_w))
+    if ip_cfg is not None:
+        loss_loader_kw.update(image_embeds=int(ip_cfg["config"]["image_embed_dim"]),
+                              image_embed_drop_rate=float(config_dict.get("ip_adapter_drop_rate", 0.05)))
     loss_overrides = {}
     if use_mask:
         loss_overrides = dict(masked_loss_floor=0.0 if masked_loss is True else float(masked_loss),
@@ -167,7 +183,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     train_rngs.manual_seed(config_dict["master_seed"] * 1009 + rank)  # different noise / timesteps on every shard
     (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers,
      model_object_dict) = tu.on_device_model_training_state(training_config, models, device=dev, optimizer=config_dict.get("optimizer", "lion"),
-                                                           **schedule_kwargs(config_dict), lora=lora_cfg, new_tokens=token_cfg, controlnet=control)
+                                                           **schedule_kwargs(config_dict), lora=lora_cfg, new_tokens=token_cfg, controlnet=control,
+                                                           ip_adapter=ip_cfg)
     reducer = dp.GradReducer([unet_state.store, text_encoder_state.store]) if world > 1 else None
     train_step_funcs = tu.dp_compile_all_unique_resolution(
         unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers, training_config,
@@ -204,8 +221,8 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         base = config_dict["model_path"].split("@")[0] + ("-EMA" if ema else "")
         # (a model without an EMA view - accumulate_*_ema off, or a text encoder frozen under LoRA - is saved as it stands)
         up = unet_ema_params if (ema and config_dict["accumulate_unet_ema"] and unet_ema_params is not None) else unet_state.params
-        if unet_state.controlnet is not None:
-            up = unet_state.params  # the UNet EMA view wraps the ControlNet's store: the pipeline directory holds the frozen base either way
+        if unet_state.controlnet is not None or unet_state.ip_adapter is not None:
+            up = unet_state.params  # the UNet EMA view wraps the ControlNet's / the IP-Adapter's store: the pipeline directory holds the frozen base either way
         tp = (text_encoder_ema_params if (ema and config_dict["accumulate_text_encoder_ema"] and text_encoder_ema_params is not None)
               else text_encoder_state.params)
         tu.save_model(model_object_dict, tokenizer, up, tp, vae_params, f'{base}@{config_dict["chunk_steps"]}')
@@ -274,6 +291,11 @@ def main(config_dict, models=None, tokenizer=None, log=print):
                 save_controlnet(cbase, unet_state.controlnet, unet_state.controlnet.config)
                 if config_dict["ema_rate"] and unet_ema_params is not None:
                     save_controlnet(cbase + "-EMA", unet_ema_params, unet_state.controlnet.config)
+            if unet_state.ip_adapter is not None:  # the IP-Adapter as a directory of its own; its EMA, when there is one, beside it
+                ibase = config_dict["model_path"].split("@")[0] + "-ip-adapter"
+                save_ip_adapter(ibase, unet_state.ip_adapter, unet_state.ip_adapter.config)
+                if config_dict["ema_rate"] and unet_ema_params is not None:
+                    save_ip_adapter(ibase + "-EMA", unet_ema_params, unet_state.ip_adapter.config)
             if unet_state.adapter is not None:  # the adapter alone (the saves above hold the base with the adapter folded in)
                 unet_state.adapter.save(config_dict["model_path"].split("@")[0] + "-lora.npz")
             if text_encoder_state.tokens is not None:  # the trained rows alone (the saves above hold the resized text encoder)
@@ -315,6 +337,8 @@ if __name__ == "__main__":
                     help="train an inpainting UNet (widened from the checkpoint's when it is not one) from batches with an inpaint mask")
     ap.add_argument("--controlnet", metavar="DIR", nargs="?", const=True, default=None,
                     help="train a ControlNet on the frozen UNet from batches with a conditioning image (DIR: continue a saved one)")
+    ap.add_argument("--ip-adapter", metavar="DIR", nargs="?", const=True, default=None,
+                    help="train an IP-Adapter on the frozen UNet from batches with image embeddings (DIR: continue a saved one)")
     ap.add_argument("--huber-c", metavar="C", type=float, default=None, help="the Huber threshold the schedule ends at (default 0.1)")
     ap.add_argument("--huber-schedule", choices=("constant", "exponential", "snr"), default=None,
                     help="how the threshold follows the timestep: snr (default), exponential or constant")
@@ -353,6 +377,8 @@ if __name__ == "__main__":
         cfg["inpaint"] = True
     if args.controlnet is not None:
         cfg["controlnet"] = args.controlnet
+    if args.ip_adapter is not None:
+        cfg["ip_adapter"] = args.ip_adapter
     if args.huber_c is not None:
         cfg["huber_c"] = args.huber_c
     if args.huber_schedule is not None:

@@ -159,6 +159,47 @@ int sdt_inpaint_pack_input(const uint16_t* latents_nhwc, const uint16_t* masked_
  *   rows_per_sample < 1; rows % rows_per_sample != 0. */
 int sdt_control_concat_add(const uint16_t* a, const uint16_t* skip, const uint16_t* res, const float* scale, uint16_t* wide,
                            int64_t rows, int64_t rows_per_sample, int Ca, int Cb, hipStream_t stream);
+/* ---- IP-ADAPTER: the image-token term of a decoupled cross-attention (Ye et al. 2023, arXiv:2308.06721; no reference counterpart;
+ * DESIGN.md "IP-Adapter"), fused with the add into the text attention's output.  T = 1..16 image tokens do not fill a matrix tile:
+ * these calls run on the vector ALUs.  C = H*D; head h is columns [h*D, h*D + D).  fl() is one fp32 rounding, fmaf one fused
+ * multiply-add (one rounding); the file is compiled without contraction and writes every multiply-add as an explicit fmaf, so the
+ * compiler's contraction setting cannot change a bit of what follows.
+ *   operands   q bf16 (B, Nq, >= C), row stride ldq;  kv bf16 (B, T, >= 2C) packed [k | v] (v at column C), row stride ldkv, image
+ *              stride T*ldkv - it may be a column slice of a wider grouped projection;  o_txt bf16 (B, Nq, C) or NULL (= +0);
+ *              scale_ip f32 (B) or NULL (= 1);  out, dout, dq_in (or NULL = +0), dq bf16 (B, Nq, C);  dkv bf16 (B, T, >= 2C), row
+ *              stride ld_dkv, [dK | dV].
+ *   logits     s[i,t] = fl(scale * dot), dot = the D products q[i,d] * k[t,d] (exact in fp32) added as an fmaf chain from +0 inside
+ *              each 8-element group (4-element in the backward when T > 4), the groups then added in increasing order from +0:
+ *              scale multiplies the finished fp32 sum, once
+ *   softmax    m = max_t s;  e_t = expf(s_t - m);  z = the e_t added in key order from +0;  p_t = e_t / z (IEEE division), all fp32
+ *   forward    acc[i,d] = fmaf chain over t = 0..T-1 from +0 of p_t * v[t,d], fp32;
+ *              out = bf16_rne((double)o_txt + (double)scale_ip[b] * (double)acc): the product is exact in double, the sum is one IEEE
+ *              double rounding, then ONE rounding to bf16 (nearest even, NaN -> 0x7fc0), as sdt_control_concat_add forms its sum.  No
+ *              shortcut for a zero scale.
+ *   backward   the probabilities are recomputed as above (no log-sum-exp is saved).  g = fl(scale_ip[b] * dout) (dout itself without
+ *              scale_ip);  dP_t = g . v[t] summed as the logits' dot;  delta = fmaf chain over t from +0 of p_t * dP_t;
+ *              dS_t = fl(p_t * fl(dP_t - delta));  all fp32, P and dS are never rounded to bf16.
+ *              dq = bf16_rne((double)dq_in + (double)fl(scale * a)), a = fmaf chain over t from +0 of dS_t * k[t,d]: one rounding to
+ *              bf16, the role dres plays in the norm backwards - q's two consumers cost no add launch.
+ *              dK[t,d] = bf16_rne(fl(scale * S)), dV[t,d] = bf16_rne(S'), S = sum_i dS[i,t] q[i,d], S' = sum_i p[i,t] g[i,d] in fp32 in
+ *              this order: the Nq rows of an image are dealt to sdt_ip_attention_bwd's partial slots by the shape alone (never by
+ *              alignment, device or timing); a slot adds its rows in increasing order by fmaf from +0, and a SECOND small launch adds
+ *              the slots in index order from +0.  No float atomics, no hand-off between workgroups: two calls give the same bits.
+ *              The gradient of o_txt is dout itself (no launch).
+ *   workspace  sdt_ip_attention_bwd_workspace_bytes(B, H, Nq, T, D) bytes (-1 for a refused shape), laid out under the split-workspace
+ *              contract of REDUCTION WORKSPACES below: the first 64 KiB are the arrival counters other calls of the stream use - these
+ *              two launches never touch them - the rest holds the fp32 slots, which need no initialisation.
+ *   vectors    16-byte (backward with T > 4: 8-byte) row accesses when every base and row stride allows it, element accesses
+ *              otherwise; both paths give the same bits.
+ * Refused with SDT_ERR_INVALID_ARG before any HIP call: a null q, kv, out / dout, dq, dkv or workspace; B, H or Nq < 1; B > 65535; T
+ * outside 1..16; D not a multiple of 8 in 8..160; H*D > 2048; a row stride narrower than its row; a bf16 pointer off a 2-byte, scale_ip
+ * off a 4-byte or the workspace off a 16-byte boundary; a workspace that is too small. */
+int sdt_ip_attention_fwd(const uint16_t* q, const uint16_t* kv, const uint16_t* o_txt, const float* scale_ip, uint16_t* out, int B, int H,
+                         int Nq, int T, int D, int ldq, int ldkv, float scale, hipStream_t stream);
+int sdt_ip_attention_bwd(const uint16_t* q, const uint16_t* kv, const uint16_t* dout, const float* scale_ip, const uint16_t* dq_in,
+                         uint16_t* dq, uint16_t* dkv, int B, int H, int Nq, int T, int D, int ldq, int ldkv, int ld_dkv, float scale,
+                         void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int64_t sdt_ip_attention_bwd_workspace_bytes(int B, int H, int Nq, int T, int D);
 /* loss_accum += mean(w_b*(target-pred)^2); dpred = d loss / d pred (bf16 NHWC, cpad channels).
  * REDUCTION WORKSPACES (this call, sdt_sqnorm_accumulate, sdt_colsum_*): sums that cross workgroups use no float atomics - each
  * workgroup stores a partial, the one that arrives last adds them in a fixed order, so results are bitwise reproducible.  They

@@ -60,6 +60,8 @@ SIGNATURES = {
     "sdt_inpaint_noise_target": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P],
     "sdt_inpaint_pack_input": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sdt_control_concat_add": [_P, _P, _P, _P, _P, _L, _L, _I, _I, _P],
+    "sdt_ip_attention_fwd": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _F, _P],
+    "sdt_ip_attention_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _F, _P, _L, _P],
     "sdt_ddim_cfg_step": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _I, _P],
     "sdt_cfg_rescale_factors": [_P, _P, _I, _I, _I, _I, _I, _F, _F, _P],
     "sdt_sampler_cfg_step": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _I, _F, _F, _F, _F, _P],
@@ -141,6 +143,7 @@ SIGNATURES = {
 WS_QUERY = {"sdt_gemm_nt_workspace_bytes": [_L, _I, _I, _I], "sdt_gemm_tn_workspace_bytes": [_L, _I, _I, _I, _I, _I, _P], "sdt_layernorm_bwd_workspace_bytes": [_L, _I], "sdt_layernorm_bwd_partial_rows": [_L, _I],
             "sdt_groupnorm_bwd_workspace_bytes": [_I, _I, _I],
             "sdt_groupnorm_fwd_workspace_bytes": [_I, _I, _I, _I], "sdt_attention_bwd_workspace_bytes": [_P],
+            "sdt_ip_attention_bwd_workspace_bytes": [_I, _I, _I, _I, _I],
             "sdt_gemm_tn_wgrad_group_workspace_bytes": [_P, _I], "sdt_conv_wgrad_group_workspace_bytes": [_P, _I], "sdt_reduce_workspace_bytes": [], "sdt_sqnorm_workspace_bytes": [], "sdt_prodigy_workspace_bytes": [], "sdt_colsum_workspace_bytes": [_I, _L, _I],
             "sdt_wgrad_sq_slots": [_I, _I, _I]}
 NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_lora_job_size": _I, "sdt_dora_job_size": _I, "sdt_last_error": ctypes.c_char_p}

@@ -7,9 +7,10 @@ from concurrent.futures import ThreadPoolExecutor
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 LIB = os.path.join(CSRC, "libsdtrain_hip.so")
-SOURCES = ["runtime.hip", "elementwise.hip", "optimizer.hip", "norm.hip", "gemm.hip", "attention.hip", "lora.hip"]
+SOURCES = ["runtime.hip", "elementwise.hip", "optimizer.hip", "norm.hip", "gemm.hip", "attention.hip", "lora.hip", "ip_attention.hip"]
 EXTRA_FLAGS = {"optimizer.hip": ["-ffp-contract=off"],
                "lora.hip": ["-ffp-contract=off"],  # W0 + s * acc: a product rounding and a sum rounding, as include/sdt.h states
+               "ip_attention.hip": ["-ffp-contract=off"],  # every multiply-add is an explicit fmaf; nothing else may fuse (include/sdt.h)
                # attention keeps score tiles and running outputs in arch VGPRs: with the default AGPR form hipcc parks both in the
                # same accumulator registers and moves 96 values per tile through v_accvgpr_read/write
                "attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}

@@ -274,6 +274,9 @@ def save_model(model_object_dict, tokenizer_object, unet_params, text_encoder_pa
     if getattr(ustore, "controlnet_config", None) is not None:
         raise ValueError("save_model: unet_params is (the EMA view of) a ControlNet's store, not a UNet: pass the frozen UNet "
                          "(unet_state.params) here and write the ControlNet with save_controlnet")
+    if getattr(ustore, "ip_adapter_config", None) is not None:
+        raise ValueError("save_model: unet_params is (the EMA view of) an IP-Adapter's store, not a UNet: pass the frozen UNet "
+                         "(unet_state.params) here and write the adapter with save_ip_adapter")
     os.makedirs(output_dir, exist_ok=True)
     dv = {"_diffusers_version": DIFFUSERS_VERSION}
     _write_submodel(output_dir, "unet", _model_config(model_object_dict, "unet"),
@@ -324,6 +327,28 @@ def load_controlnet(directory):
     path = os.path.join(directory, UNET_WEIGHTS)
     if not os.path.exists(path):
         raise FileNotFoundError(f"{path}: expected the ControlNet's Flax weights")
+    with open(path, "rb") as f:
+        flat = flatten_tree(flax_from_bytes(f.read()))
+    return {"config": cfg, "params": {p: torch.from_numpy(np.array(v, dtype=np.float32)) for p, v in flat.items()}}
+
+
+def save_ip_adapter(output_dir, ip_adapter, config):
+    """An IP-Adapter directory in this project's layout: config.json (the UNet's config plus image_embed_dim and num_tokens) and the
+    msgpack weights file under the leaf paths of nets.ip_adapter_spec (DESIGN.md "IP-Adapter" maps them to the published state-dict
+    names).  ip_adapter: a nets.IPAdapter, its ParamStore, the EmaView over it (the EMA weights) or a flat / nested host tree."""
+    _write_submodel(output_dir, "", config, {"_class_name": "IPAdapter", "_diffusers_version": DIFFUSERS_VERSION}, UNET_WEIGHTS, ip_adapter)
+
+
+def load_ip_adapter(directory):
+    """Inverse of save_ip_adapter: dict(config=, params=flat {"path": float32 tensor} host tree), what
+    on_device_model_training_state(ip_adapter=) and StableDiffusionPipeline(ip_adapter=) build their stores from."""
+    cfg = _read_config(os.path.join(directory, "config.json"), nets._UNET_DEFAULTS)
+    for k in ("image_embed_dim", "num_tokens"):
+        if k not in cfg:
+            raise ValueError(f"{directory}: config.json has no {k}: not an IP-Adapter directory")
+    path = os.path.join(directory, UNET_WEIGHTS)
+    if not os.path.exists(path):
+        raise FileNotFoundError(f"{path}: expected the IP-Adapter's weights")
     with open(path, "rb") as f:
         flat = flatten_tree(flax_from_bytes(f.read()))
     return {"config": cfg, "params": {p: torch.from_numpy(np.array(v, dtype=np.float32)) for p, v in flat.items()}}
@@ -456,6 +481,9 @@ def _stepping_store(st):
     cn = getattr(st, "controlnet", None)
     if cn is not None:  # a ControlNet on the frozen UNet: the ControlNet's store (the layout digest tells it from the UNet's)
         return cn.store, None
+    ipa = getattr(st, "ip_adapter", None)
+    if ipa is not None:  # an IP-Adapter on the frozen UNet: the adapter's store, likewise
+        return ipa.store, None
     ad = getattr(st, "adapter", None)
     if ad is not None:
         return ad.store, ad

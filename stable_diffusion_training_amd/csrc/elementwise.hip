@@ -451,29 +451,7 @@ __global__ void __launch_bounds__(256) inpaint_pack_input_kernel(const bf16_t* _
 }
 
 // ------------------------------------------------------------------ ControlNet injection (include/sdt.h "CONTROLNET")
-// A double rounded to bf16 once, to nearest even, in integer arithmetic on its bits (a conversion through float would round twice).
-// NaN -> the quiet NaN 0x7fc0; a magnitude of 2^128 or more, and one that rounds up to it, -> inf; below half the
-// smallest bf16 subnormal (2^-134) -> a signed zero.
-__device__ __forceinline__ bf16_t double_to_bf16_rne(double d) {
-  const unsigned long long b = (unsigned long long)__double_as_longlong(d);
-  const unsigned sign = (unsigned)(b >> 48) & 0x8000u;
-  const unsigned long long mag = b & 0x7fffffffffffffffULL;
-  if (mag > 0x7ff0000000000000ULL) return (bf16_t)0x7fc0u;  // (the sign of a NaN that arithmetic produced is not specified)
-  const int e = (int)(mag >> 52);
-  if (e == 0) return (bf16_t)sign;  // zero or a double subnormal
-  const int eb = e - 1023 + 127;    // the bf16 exponent field of a normal result
-  if (eb >= 255) return (bf16_t)(sign | 0x7f80u);
-  const unsigned long long m = (mag & 0xfffffffffffffULL) | (1ULL << 52);
-  const int shift = eb > 0 ? 45 : 46 - eb;  // 52 - 7 fraction bits; one more for every step below the normal range
-  if (shift > 54) return (bf16_t)sign;      // m < 2^53 is less than half a unit
-  unsigned q = (unsigned)(m >> shift);
-  const unsigned long long rem = m & ((1ULL << shift) - 1), half = 1ULL << (shift - 1);
-  if (rem > half || (rem == half && (q & 1u))) ++q;
-  // normal: q in [128, 256] holds the implicit one, so (eb - 1) << 7 plus q carries into the exponent by itself (up to inf);
-  // subnormal: q in [0, 128] is the field, 128 being the smallest normal
-  return (bf16_t)(sign | ((eb > 0 ? (unsigned)(eb - 1) << 7 : 0u) + q));
-}
-
+// double_to_bf16_rne: sdt_common.h
 __device__ __forceinline__ bf16_t control_add_element(bf16_t skip, bf16_t res, float scale) {
 #pragma clang fp contract(off)
   // scale (24 bits) * res (8 bits) is exact in double; the sum rounds to double, then once to bf16

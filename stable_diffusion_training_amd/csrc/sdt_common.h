@@ -66,6 +66,29 @@ __device__ __forceinline__ float block_sum(float v, float* scratch) {
   return r;
 }
 
+// A double rounded to bf16 once, to nearest even, in integer arithmetic on its bits (a conversion through float would round twice).
+// NaN -> the quiet NaN 0x7fc0; a magnitude of 2^128 or more, and one that rounds up to it, -> inf; below half the
+// smallest bf16 subnormal (2^-134) -> a signed zero.
+__device__ __forceinline__ bf16_t double_to_bf16_rne(double d) {
+  const unsigned long long b = (unsigned long long)__double_as_longlong(d);
+  const unsigned sign = (unsigned)(b >> 48) & 0x8000u;
+  const unsigned long long mag = b & 0x7fffffffffffffffULL;
+  if (mag > 0x7ff0000000000000ULL) return (bf16_t)0x7fc0u;  // (the sign of a NaN that arithmetic produced is not specified)
+  const int e = (int)(mag >> 52);
+  if (e == 0) return (bf16_t)sign;  // zero or a double subnormal
+  const int eb = e - 1023 + 127;    // the bf16 exponent field of a normal result
+  if (eb >= 255) return (bf16_t)(sign | 0x7f80u);
+  const unsigned long long m = (mag & 0xfffffffffffffULL) | (1ULL << 52);
+  const int shift = eb > 0 ? 45 : 46 - eb;  // 52 - 7 fraction bits; one more for every step below the normal range
+  if (shift > 54) return (bf16_t)sign;      // m < 2^53 is less than half a unit
+  unsigned q = (unsigned)(m >> shift);
+  const unsigned long long rem = m & ((1ULL << shift) - 1), half = 1ULL << (shift - 1);
+  if (rem > half || (rem == half && (q & 1u))) ++q;
+  // normal: q in [128, 256] holds the implicit one, so (eb - 1) << 7 plus q carries into the exponent by itself (up to inf);
+  // subnormal: q in [0, 128] is the field, 128 being the smallest normal
+  return (bf16_t)(sign | ((eb > 0 ? (unsigned)(eb - 1) << 7 : 0u) + q));
+}
+
 // ---- ordered cross-workgroup reductions (no float atomics on data) -------------------------------------------------------
 // Workgroups that feed one sum each store a PARTIAL to their own slot (plain stores), then call sdt_arrive_last on the sum's
 // counter: it returns true (workgroup-uniform) in the workgroup that arrived last, which then adds all the partials in a fixed

@@ -20,6 +20,7 @@ Layout of a cache directory (plain numpy, nothing compressed):
                       (B,h,w), the nearest-neighbour 0/1 latent mask.  A record without the mask keeps its members and bytes.
                       For a ControlNet batch: conditioning_pixel_values float32 (B,C,H,W) as the batch holds them (the hint stays at
                       pixel size: the ControlNet's embedder, which is trained, reads it every step).
+                      For an IP-Adapter batch: image_embeds (B,E) as the batch holds them.
 A cached SD1.5 512x512 sample is 64 KiB; its fp32 pixels are 3 MiB (as is a ControlNet batch's conditioning image, which is kept).
 """
 import hashlib
@@ -33,8 +34,9 @@ from . import _lib, ops
 from .training_utils import encode_inpaint_moments, encode_latent_moments, step_key
 
 FORMAT_VERSION = 1
-# what a record keeps of a batch besides the moments (conditioning_pixel_values: a ControlNet batch's hint, float32 at pixel size)
-EXTRA_KEYS = ("input_ids", "time_ids", "text_embeds", "conditioning_pixel_values")
+# what a record keeps of a batch besides the moments (conditioning_pixel_values: a ControlNet batch's hint, float32 at pixel size;
+# image_embeds: an IP-Adapter batch's image embedding (B, E), as the batch holds it)
+EXTRA_KEYS = ("input_ids", "time_ids", "text_embeds", "conditioning_pixel_values", "image_embeds")
 LOSS_WEIGHT_KEY, LOSS_MASK_KEY = "loss_weight", "loss_mask"  # kept too: the weight as it is, the mask pooled to the latent grid
 INPAINT_MASK_KEY, MASKED_MOMENTS_KEY = "inpaint_mask", "masked_latent_moments"  # the latent 0/1 mask and the masked image's moments
 

@@ -341,6 +341,70 @@ def controlnet_from_unet(unet_params, cfg, seed=0):
     return out
 
 
+class IPAdapter:
+    """An IP-Adapter as the training state and the sampling pipeline hold it: its ParamStore and its config (ip_adapter_config)."""
+
+    def __init__(self, store, config):
+        self.store, self.config = store, config
+
+
+def ip_adapter_config(unet_cfg, image_embed_dim=1024, num_tokens=4):
+    """The UNet's config plus the two keys of an IP-Adapter (Ye et al. 2023): image_embed_dim E, the width of the image encoder's pooled
+    embedding (1024 for CLIP ViT-H/14, 1280 for ViT-bigG), and num_tokens T, the image tokens image_proj makes of it (4; 16 for the
+    Plus variants' token count).  ValueError for E not a positive multiple of 8, T outside 1..16 (what sdt_ip_attention_* serve) and
+    an inpainting UNet."""
+    if not isinstance(image_embed_dim, int) or image_embed_dim < 8 or image_embed_dim % 8:
+        raise ValueError(f"ip_adapter_config: image_embed_dim={image_embed_dim!r} must be a positive multiple of 8")
+    if not isinstance(num_tokens, int) or not 1 <= num_tokens <= 16:
+        raise ValueError(f"ip_adapter_config: num_tokens={num_tokens!r} must be 1..16")
+    if inpaint_latent_channels(unet_cfg) is not None:
+        raise ValueError("ip_adapter_config: an IP-Adapter on an inpainting UNet is not supported")
+    return dict(unet_cfg, image_embed_dim=image_embed_dim, num_tokens=num_tokens)
+
+
+def ip_adapter_blocks(cfg):
+    """{width: ["<block>/attn2", ...]} of the UNet's cross-attentions, widths in order of first use, blocks in forward order."""
+    groups = {}
+    for p, shp in unet_spec(cfg):
+        if p.endswith("/attn2/to_k/kernel"):
+            groups.setdefault(shp[1], []).append(p[: -len("/to_k/kernel")])
+    return groups
+
+
+def ip_adapter_spec(cfg):
+    """Leaves of an IP-Adapter: image_proj/proj (E -> T * Dc, with bias) and image_proj/norm (LayerNorm over Dc), then to_k_ip / to_v_ip
+    (Dc -> C, no bias) of every cross-attention, the blocks of one channel width back to back as [k | v] pairs: the image tokens are
+    projected by ONE GEMM per width (ops.linear_multi), as _context_projections does for the text, and each block reads a column slice."""
+    E, T, Dc = cfg["image_embed_dim"], cfg["num_tokens"], cfg["cross_attention_dim"]
+    spec = [("image_proj/proj/kernel", (E, T * Dc)), ("image_proj/proj/bias", (T * Dc,)),
+            ("image_proj/norm/scale", (Dc,)), ("image_proj/norm/bias", (Dc,))]
+    for width, names in ip_adapter_blocks(cfg).items():
+        for n in names:
+            spec += [(n + "/to_k_ip/kernel", (Dc, width)), (n + "/to_v_ip/kernel", (Dc, width))]
+    return spec
+
+
+def ip_adapter_from_unet(unet_params, cfg, seed=0):
+    """A fresh IP-Adapter for a UNet, as the published training script initialises it (host tree, flat paths): to_k_ip / to_v_ip are
+    copies of the UNet's attn2 to_k / to_v, image_proj is drawn from the seed (init_params).  unet_params: flat or nested tree, torch
+    tensors or numpy arrays."""
+    if any(isinstance(v, dict) for v in unet_params.values()):
+        from .checkpoint import flatten_tree
+        unet_params = flatten_tree(unet_params)
+    spec = ip_adapter_spec(cfg)
+    out = init_params([(p, shp) for p, shp in spec if p.startswith("image_proj/")], seed)
+    for p, shp in spec:
+        if p in out:
+            continue
+        src = p.replace("/to_k_ip/", "/to_k/").replace("/to_v_ip/", "/to_v/")
+        v = unet_params[src]
+        v = v.detach().to(torch.float32).cpu().clone() if torch.is_tensor(v) else torch.tensor(v, dtype=torch.float32)
+        if tuple(v.shape) != tuple(shp):
+            raise ValueError(f"ip_adapter_from_unet: {src} has shape {tuple(v.shape)} in the UNet, the adapter's config says {tuple(shp)}")
+        out[p] = v
+    return out
+
+
 def time_emb_groups(leaves):
     """{width: [resnet path, ...]} in buffer order, from the leaves of a UNet parameter store."""
     groups = {}
@@ -545,6 +609,55 @@ def _context_projections(st, ctx):
     return out
 
 
+def ip_adapter_tokens(st, cfg, image_embeds):
+    """image_proj of an IP-Adapter store: image_embeds bf16 (B, E) -> Linear E -> T * Dc, viewed (B, T, Dc), LayerNorm over Dc: the image
+    tokens (B, T, Dc) bf16 every cross-attention attends to."""
+    _require(image_embeds.dim() == 2 and image_embeds.shape[1] == cfg["image_embed_dim"],
+             f"ip_adapter_tokens: image_embeds {tuple(image_embeds.shape)} must be (B, {cfg['image_embed_dim']})")
+    x = image_embeds.to(torch.bfloat16).contiguous()
+    if st.trainable and torch.is_grad_enabled() and not x.requires_grad:
+        x = x.detach().requires_grad_(True)  # anchors the tape: image_proj's weight gradients come from its backward
+    y = ops.linear(x, st, "image_proj/proj")
+    return ops.layer_norm(y.view(x.shape[0], cfg["num_tokens"], cfg["cross_attention_dim"]), st, "image_proj/norm")
+
+
+def _require(cond, msg):
+    if not cond:
+        raise ValueError(msg)
+
+
+class _ImageKV:
+    """What a cross-attention block needs for its image term: the adapter's store, the block's [k|v] of the image tokens as a column
+    slice of the width's grouped projection (kv) or an alias of the tokens to project itself (tokens), and the per-sample scale."""
+
+    def __init__(self, ctx, store, kv, tokens, scale):
+        self.ctx, self.store, self.kv, self.tokens, self.scale = ctx, store, kv, tokens, scale
+        self.shape = ctx.shape
+
+
+def _image_projections(st, tokens, ctx, scale):
+    """to_k_ip / to_v_ip of every cross-attention applied to the image tokens, one GEMM per channel width (ip_adapter_spec lays the
+    leaves out for it), and each entry of ctx (_context_projections) wrapped with its block's share."""
+    groups = {}
+    for p in st.leaves:
+        if p.endswith("/attn2/to_k_ip/kernel"):
+            groups.setdefault(st.leaves[p].shape[1], []).append(p[: -len("/to_k_ip/kernel")])
+    _require(set(n for names in groups.values() for n in names) == set(ctx),
+             "ip: the adapter's cross-attention blocks are not the UNet's (another config?)")
+    acts = iter(ops.fanout(tokens, len(groups)))
+    out = {}
+    for width, names in groups.items():
+        a = next(acts)
+        y = ops.linear_multi(a, st, tuple(n + t for n in names for t in ("/to_k_ip", "/to_v_ip"))) if len(names) > 1 else None
+        if y is not None:
+            for n, kv in zip(names, ops.col_slices(y, len(names))):
+                out[n] = _ImageKV(ctx[n], st, kv, None, scale)
+        else:
+            for n, alias in zip(names, ops.fanout(a, len(names))):
+                out[n] = _ImageKV(ctx[n], st, None, alias, scale)
+    return out
+
+
 def _resnet(x, rb, st, name, groups, eps, xs=None):
     """rb: the block's time-embedding row bias (B, C_out) or None (VAE).  xs: GroupNorm statistics of x when its producer
     accumulated them (ops.conv2d / ops.linear gn_groups=).  Returns (output, statistics of the output for the next GroupNorm, or
@@ -583,6 +696,16 @@ class _PackedKV:
         self.shape = kv.shape
 
 
+def _packed_pair(x, st, kname, vname):
+    """[k | v] = [x @ to_k | x @ to_v] as one packed tensor: one GEMM where the two kernels can share it (ops.linear_multi), otherwise
+    two and a channel concatenation (widths that are no multiple of 64: the tiny test configs)."""
+    kv = ops.linear_multi(x, st, (kname, vname))
+    if kv is None:
+        xk, xv = ops.fanout(x, 2)
+        kv = ops.concat_channels(ops.linear(xk, st, kname), ops.linear(xv, st, vname))
+    return kv
+
+
 def _attn(x, ctx, st, name, heads, residual, chunked_keys=True):
     """ctx None: self-attention; otherwise one alias of the text context (ops.fanout) or the block's precomputed _PackedKV.
     The projections that share an input run as one GEMM (ops.linear_multi) and attention reads / differentiates the packed
@@ -590,6 +713,13 @@ def _attn(x, ctx, st, name, heads, residual, chunked_keys=True):
     c = x.shape[-1]
     scale = (c // heads) ** -0.5
     kw = key_chunk_weights(x.shape[1], ctx.shape[1], x.device) if (ctx is not None and chunked_keys) else None
+    if isinstance(ctx, _ImageKV):  # decoupled cross-attention: the text term's launch, then the image term added into its output
+        ip, ctx = ctx, ctx.ctx
+        q = ops.linear(x, st, name + "/to_q")
+        kv = ctx.kv if isinstance(ctx, _PackedKV) else _packed_pair(ctx, st, name + "/to_k", name + "/to_v")
+        kv_ip = ip.kv if ip.kv is not None else _packed_pair(ip.tokens, ip.store, name + "/to_k_ip", name + "/to_v_ip")
+        o = ops.attention_ip(q, kv, kv_ip, heads, scale, key_weight=kw, scale_ip=ip.scale)
+        return ops.linear(o, st, name + "/to_out_0", residual=residual)
     if isinstance(ctx, _PackedKV):
         o = ops.attention_packed(ops.linear(x, st, name + "/to_q"), ctx.kv, heads, scale, key_weight=kw)
         return ops.linear(o, st, name + "/to_out_0", residual=residual)
@@ -725,12 +855,15 @@ def controlnet_forward(st, cfg, x, timesteps, ctx, cond, added_cond=None):
     return controlnet_forward_embedded(st, cfg, x, timesteps, ctx, controlnet_cond_embedding(st, cfg, cond), added_cond)
 
 
-def unet_forward(st, cfg, x, timesteps, ctx, added_cond=None, control=None):
+def unet_forward(st, cfg, x, timesteps, ctx, added_cond=None, control=None, ip=None):
     """x: (B,h,w,pad8(in_channels)) bf16 NHWC; timesteps int32 (B,); ctx (B,L,cross_dim) bf16.
     Returns (B,h,w,pad8(out_channels)) bf16 NHWC (the reference returns NCHW; see train_step).
     control: None, or (down_residuals, mid_residual[, scale]) from controlnet_forward; scale f32 (B,) per-sample factors or None (1).
     Every decoder concatenation then reads skip + scale * residual and the mid block x + scale * mid_residual (ops.control_add).  On a
-    store that is not trainable conv_in and the down blocks run without a tape: nothing upstream of the additions is trained."""
+    store that is not trainable conv_in and the down blocks run without a tape: nothing upstream of the additions is trained.
+    ip: None, or (adapter_store, image_tokens[, scale_ip]) with the tokens of ip_adapter_tokens and scale_ip f32 (B,) per-sample factors
+    (sampling) or None (1): every attn2 then adds scale_ip * softmax(q K_ip^T) V_ip to its text attention (ops.attention_ip).  With
+    ip=None nothing changes, neither launches nor bits."""
     boc = cfg["block_out_channels"]
     nb, lpb, lin, g = len(boc), cfg["layers_per_block"], cfg["use_linear_projection"], cfg["norm_num_groups"]
     heads = _per_block(cfg["attention_head_dim"], nb)  # Flax: attention_head_dim is the head COUNT
@@ -741,6 +874,8 @@ def unet_forward(st, cfg, x, timesteps, ctx, added_cond=None, control=None):
     # summed by one launch each instead of a chain of binary adds
     rowbias = _time_emb_projections(st, ops.silu(temb))  # {resnet path: (B, C_out) row bias of its first convolution}
     ctx = _context_projections(st, ctx)  # {attn2 path: the block's [k|v] projections}
+    if ip is not None:
+        ctx = _image_projections(ip[0], ip[1], ctx, ip[2] if len(ip) > 2 else None)
     down_r = mid_r = scale = None
     if control is not None:
         down_r, mid_r = list(control[0]), control[1]

@@ -1217,6 +1217,76 @@ def attention_packed(a, b, heads, scale, causal=False, key_weight=None):
     return _AttentionPacked.apply(a, b, heads, scale, causal, key_weight)
 
 
+def _kv_pitch(b, B, C, what):
+    """Row pitch of a packed [k|v] operand (B, N, 2C) that may be a column slice of a wider projection (ops.col_slices)."""
+    if (b.dim() != 3 or b.dtype != BF16 or not b.is_cuda or b.shape[0] != B or b.shape[2] != 2 * C or b.stride(2) != 1 or b.stride(1) % 8
+            or b.stride(1) < 2 * C or (B > 1 and b.stride(0) != b.shape[1] * b.stride(1))):
+        raise _lib.SdtError(f"{what}: expected bf16 ({B}, N, {2 * C}) rows at a constant pitch, got {b.dtype} {tuple(b.shape)} strides {b.stride()}")
+    return b.stride(1)
+
+
+class _AttentionIP(Function):
+    """Decoupled cross-attention (IP-Adapter): softmax(q K_txt^T) V_txt + scale_ip * softmax(q K_ip^T) V_ip.  The text term is the
+    packed attention launch; sdt_ip_attention_fwd adds the image term into its output, and sdt_ip_attention_bwd adds the image term's
+    dQ into the text attention's: q's two consumers cost no add launch."""
+
+    @staticmethod
+    def forward(ctx, q, kv_txt, kv_ip, heads, scale, key_weight, scale_ip):
+        _check(q, "attention_ip q")
+        if q.dim() != 3 or q.shape[2] % heads:
+            raise _lib.SdtError(f"attention_ip: q {tuple(q.shape)} must be (B, Nq, heads * D) with heads = {heads}")
+        B, Nq, C = q.shape
+        ld_txt = _kv_pitch(kv_txt, B, C, "attention_ip kv_txt")
+        ld_ip = _kv_pitch(kv_ip, B, C, "attention_ip kv_ip")
+        Nk, T, D = kv_txt.shape[1], kv_ip.shape[1], C // heads
+        if scale_ip is not None and (scale_ip.dtype != torch.float32 or not scale_ip.is_contiguous() or tuple(scale_ip.shape) != (B,)
+                                     or scale_ip.device != q.device):
+            raise _lib.SdtError(f"attention_ip: scale_ip must be a contiguous float32 ({B},) tensor on {q.device}, got {scale_ip.dtype} "
+                                f"{tuple(scale_ip.shape)} on {scale_ip.device}")
+        desc = SdtAttnDesc(B, heads, Nq, Nk, D, C, ld_txt, ld_txt, C, scale, 0, C, 2 * C, 2 * C, 0, _kw_ptr(key_weight, Nk))
+        ctx.key_weight = key_weight
+        o_txt = torch.empty(B, Nq, C, dtype=BF16, device=q.device)
+        lse = torch.empty(B, heads, Nq, dtype=torch.float32, device=q.device)
+        call("sdt_attention_fwd", q.data_ptr(), kv_txt.data_ptr(), kv_txt.data_ptr() + 2 * C, o_txt.data_ptr(), lse.data_ptr(),
+             _lib.ctypes.addressof(desc), _stream())
+        out = torch.empty_like(o_txt)
+        call("sdt_ip_attention_fwd", q.data_ptr(), kv_ip.data_ptr(), o_txt.data_ptr(), _ptr(scale_ip), out.data_ptr(), B, heads, Nq, T, D,
+             C, ld_ip, scale, _stream())
+        ctx.save_for_backward(q, kv_txt, kv_ip, o_txt, lse, scale_ip)
+        ctx.desc, ctx.dims = desc, (B, heads, Nq, T, D, C, ld_ip, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        q, kv_txt, kv_ip, o_txt, lse, scale_ip = ctx.saved_tensors
+        B, heads, Nq, T, D, C, ld_ip, scale = ctx.dims
+        dout = dout.contiguous()
+        dq_txt = torch.empty_like(q)
+        dkv_txt = torch.empty(kv_txt.shape, dtype=BF16, device=q.device)
+        need = _lib.load().sdt_attention_bwd_workspace_bytes(_lib.ctypes.addressof(ctx.desc))
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+        call("sdt_attention_bwd", q.data_ptr(), kv_txt.data_ptr(), kv_txt.data_ptr() + 2 * C, o_txt.data_ptr(), dout.data_ptr(),
+             lse.data_ptr(), dq_txt.data_ptr(), dkv_txt.data_ptr(), dkv_txt.data_ptr() + 2 * C, ws.data_ptr(), need,
+             _lib.ctypes.addressof(ctx.desc), _stream())
+        dq = torch.empty_like(q)
+        dkv_ip = torch.empty(B, T, 2 * C, dtype=BF16, device=q.device)
+        need = _lib.load().sdt_ip_attention_bwd_workspace_bytes(B, heads, Nq, T, D)
+        ws = torch.empty(need, dtype=torch.uint8, device=q.device)  # the slots need no zero fill and the counters are not touched
+        call("sdt_ip_attention_bwd", q.data_ptr(), kv_ip.data_ptr(), dout.data_ptr(), _ptr(scale_ip), dq_txt.data_ptr(), dq.data_ptr(),
+             dkv_ip.data_ptr(), B, heads, Nq, T, D, C, ld_ip, 2 * C, scale, ws.data_ptr(), need, _stream())
+        return dq, dkv_txt, dkv_ip, None, None, None, None
+
+
+def attention_ip(q, kv_txt, kv_ip, heads, scale, key_weight=None, scale_ip=None):
+    """Cross-attention with image tokens: q (B, Nq, C), kv_txt (B, Nk, 2C) and kv_ip (B, T <= 16, 2C) packed [k|v] (column slices of
+    grouped projections allowed).  key_weight is the text keys' (key_chunk_weights); the image tokens count once each.  scale_ip: f32
+    (B,) per-sample factors of the image term for sampling, None = 1.  ValueError for a scale_ip beside a kv_ip that requires grad:
+    training runs at unit scale, as control_add does."""
+    if scale_ip is not None and kv_ip.requires_grad:
+        raise ValueError("attention_ip: a scale_ip is for sampling only - kv_ip requires grad, and training runs at unit scale")
+    return _AttentionIP.apply(q, kv_txt, kv_ip, heads, scale, key_weight, scale_ip)
+
+
 # ----------------------------------------------------------------------------------------- CLIP embeddings
 class _Embedding(Function):
     @staticmethod

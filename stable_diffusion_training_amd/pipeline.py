@@ -23,8 +23,10 @@ class StableDiffusionPipeline:
     vae_params: host tree of the full VAE (decoder + post_quant_conv are loaded into a frozen store); configs as in load_models."""
 
     def __init__(self, unet, text_encoder, vae_params, unet_config, text_encoder_config, vae_config, scheduler=None,
-                 scaling_factor=0.18215, device=None, controlnet=None):
-        """controlnet: None, a nets.ControlNet (store + config; a training state's unet_state.controlnet samples in place), or
+                 scaling_factor=0.18215, device=None, controlnet=None, ip_adapter=None):
+        """ip_adapter: None, a nets.IPAdapter (store + config; a training state's unet_state.ip_adapter samples in place), or
+        dict(config=, params=) as checkpoint.load_ip_adapter returns it (loaded into a frozen store).
+        controlnet: None, a nets.ControlNet (store + config; a training state's unet_state.controlnet samples in place), or
         dict(config=, params=) as checkpoint.load_controlnet returns it (loaded into a frozen store)."""
         _lib.require_device()
         self.unet, self.text_encoder = _store_of(unet), _store_of(text_encoder)
@@ -36,6 +38,16 @@ class StableDiffusionPipeline:
                                 trainable=False)
             cstore.load(controlnet["params"])
             self.controlnet = nets.ControlNet(cstore, controlnet["config"])
+        self.ip_adapter = ip_adapter
+        if ip_adapter is not None and nets.inpaint_latent_channels(unet_config) is not None:
+            raise ValueError("an IP-Adapter on an inpainting UNet is not supported")
+        if ip_adapter is not None and controlnet is not None:
+            raise ValueError("an IP-Adapter beside a ControlNet is not supported")
+        if isinstance(ip_adapter, dict):
+            istore = ParamStore(nets.ip_adapter_spec(ip_adapter["config"]), device=torch.device(device) if device is not None else self.unet.device,
+                                trainable=False)
+            istore.load(ip_adapter["params"])
+            self.ip_adapter = nets.IPAdapter(istore, ip_adapter["config"])
         self.unet_config, self.text_encoder_config, self.vae_config = unet_config, text_encoder_config, vae_config
         self.device = torch.device(device) if device is not None else self.unet.device
         self.vae_decoder = ParamStore(nets.vae_decoder_spec(vae_config), device=self.device, trainable=False)
@@ -124,7 +136,7 @@ class StableDiffusionPipeline:
     @torch.no_grad()
     def generate(self, prompt_ids, num_inference_steps=50, height=512, width=512, guidance_scale=7.5, latents=None,
                  neg_prompt_ids=None, generator=None, return_latents=False, guidance_rescale=0.0, image=None, mask=None,
-                 masked_eps=None, control_image=None, conditioning_scale=1.0, control_negative=True, aux=None):
+                 masked_eps=None, control_image=None, conditioning_scale=1.0, control_negative=True, image_embeds=None, ip_scale=1.0, aux=None):
         """_generate (:160-254).  prompt_ids int (B,77) device tensor ((B,2,77) for an SDXL-mode text encoder: _sdxl_conditioning;
         pass scaling_factor=0.13025 for the SDXL VAE); latents optional f32 (B,C,h,w) initial noise; returns the
         image (B,H,W,3) float32 in [0,1] on the device (and the final latents when return_latents).  guidance_rescale in [0, 1]
@@ -141,6 +153,11 @@ class StableDiffusionPipeline:
         and hands its residuals to the UNet with the per-sample scale vector f32 (2B,) = conditioning_scale, whose negative half is 0
         with control_negative=False (control on the prompt half only; diffusers' guess mode without its per-layer ramp).  ValueError for
         control_image without a ControlNet and the reverse, a wrong shape, and an inpainting UNet.
+        A pipeline built with ip_adapter= needs image_embeds, f32 or bf16 (B, image_embed_dim): the image encoder's pooled embedding
+        of the image prompt.  image_proj runs once on [zeros | image_embeds] - the unconditional half of the doubled batch uses zero
+        image embeddings through image_proj, the published pipeline's rule - and every attn2 adds its image term with the per-sample
+        scale vector f32 (2B,) = ip_scale (ops.attention_ip scale_ip).  ValueError for image_embeds without an adapter and the reverse,
+        and a wrong shape.
         aux: an optional dict that receives the FIRST step's tensors for parity tests - unet_input, timesteps, ctx, pred and, with a
         ControlNet, control_embedding, control_down, control_mid and control_scale."""
         if height % 8 != 0 or width % 8 != 0:
@@ -158,6 +175,15 @@ class StableDiffusionPipeline:
             want = (prompt_ids.shape[0], cn.config["conditioning_channels"], height, width)
             if not torch.is_tensor(control_image) or tuple(control_image.shape) != want:
                 raise ValueError(f"Unexpected control_image shape, got {tuple(getattr(control_image, 'shape', ()))}, expected {want}")
+        ipa = getattr(self, "ip_adapter", None)
+        if ipa is None and image_embeds is not None:
+            raise ValueError("image_embeds need a pipeline built with ip_adapter=")
+        if ipa is not None:
+            if image_embeds is None:
+                raise ValueError("a pipeline built with ip_adapter= samples from image_embeds")
+            want = (prompt_ids.shape[0], ipa.config["image_embed_dim"])
+            if not torch.is_tensor(image_embeds) or tuple(image_embeds.shape) != want:
+                raise ValueError(f"Unexpected image_embeds shape, got {tuple(getattr(image_embeds, 'shape', ()))}, expected {want}")
         dev = self.device
         stream = torch.cuda.current_stream().cuda_stream
         B = prompt_ids.shape[0]
@@ -216,6 +242,13 @@ class StableDiffusionPipeline:
             scale = torch.full((2 * B,), float(conditioning_scale), dtype=torch.float32, device=dev)
             if not control_negative:
                 scale[:B] = 0.0
+        ip = None
+        if ipa is not None:  # the image tokens: projected once for [zeros | image_embeds]
+            ipa.store.prepare()
+            emb = torch.zeros(2 * B, image_embeds.shape[1], dtype=torch.bfloat16, device=dev)
+            emb[B:].copy_(image_embeds.to(device=dev))
+            ip = (ipa.store, nets.ip_adapter_tokens(ipa.store, ipa.config, emb).detach(),
+                  torch.full((2 * B,), float(ip_scale), dtype=torch.float32, device=dev))
         for step, t in enumerate(self.scheduler.set_timesteps(num_inference_steps)):
             t_dev.fill_(int(t))
             if L_inp is not None:
@@ -226,10 +259,12 @@ class StableDiffusionPipeline:
             if cn is not None:
                 down, mid = nets.controlnet_forward_embedded(cn.store, cn.config, x_in, t_dev, context, embedding, added)
                 control = (down, mid, scale)
-            pred = nets.unet_forward(self.unet, self.unet_config, x_in, t_dev, context, added, control=control)
+            pred = nets.unet_forward(self.unet, self.unet_config, x_in, t_dev, context, added, control=control, ip=ip)
             ops.gn_arena_end(dev)
             if aux is not None and step == 0:  # the first step's tensors, for parity tests
                 aux.update(unet_input=x_in.clone(), timesteps=t_dev.clone(), ctx=context, pred=pred.clone())
+                if ip is not None:
+                    aux.update(ip_tokens=ip[1], ip_scale=ip[2])
                 if cn is not None:
                     aux.update(control_embedding=embedding, control_down=[d.clone() for d in down], control_mid=mid.clone(), control_scale=scale)
             self.scheduler.cfg_step(pred, lat, x_lat, t, guidance_scale, guidance_rescale)  # guidance + x_t -> x_{t-1} + next input

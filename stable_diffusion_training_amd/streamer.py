@@ -18,7 +18,8 @@ class DataLoader:
                  maximum_resolution_areas=(512 ** 2,), bucket_lower_bound_resolutions=(256,), numb_of_worker_thread=1,
                  queue_get_timeout=60, chunk_number=0, seed=0, context_concatenation_multiplier=1, *,
                  batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu", text_towers=1,
-                 loss_masks=False, prior_every=0, prior_loss_weight=1.0, inpaint_masks=False, placeholder_ids=None, conditioning_images=False):
+                 loss_masks=False, prior_every=0, prior_loss_weight=1.0, inpaint_masks=False, placeholder_ids=None, conditioning_images=False,
+                 image_embeds=0, image_embed_drop_rate=0.0):
         if len(maximum_resolution_areas) != len(bucket_lower_bound_resolutions):
             raise ValueError("number of elements in maximum_resolution_areas and bucket_lower_bound_resolutions is not match!")
         if training_batch_size % world_size:
@@ -40,6 +41,11 @@ class DataLoader:
         if not isinstance(conditioning_images, int) or conditioning_images < 0:
             raise ValueError(f"conditioning_images={conditioning_images!r}: False, True (3 channels) or the ControlNet's conditioning_channels")
         self.conditioning_images = conditioning_images  # channels of the conditioning image, 0: none
+        if not isinstance(image_embeds, int) or isinstance(image_embeds, bool) or image_embeds < 0:
+            raise ValueError(f"image_embeds={image_embeds!r}: 0 (none) or the IP-Adapter's image_embed_dim")
+        if not 0.0 <= float(image_embed_drop_rate) <= 1.0:
+            raise ValueError(f"image_embed_drop_rate={image_embed_drop_rate!r} must lie in [0, 1]")
+        self.image_embeds, self.image_embed_drop_rate = image_embeds, float(image_embed_drop_rate)  # width of the embedding, 0: none
         self.placeholder_ids = self._check_placeholders(placeholder_ids, text_towers, context_window)
         self.buckets = [tuple(int(v) for v in b) for area, lo in zip(maximum_resolution_areas, bucket_lower_bound_resolutions)
                         for b in calculate_resolution_array(area, lo, 64)]
@@ -98,8 +104,10 @@ class DataLoader:
         prior_loss_weight for class images (DreamBooth prior preservation).  inpaint_masks=True adds inpaint_mask f32 (B, bucket[0],
         bucket[1]) for an inpainting UNet: one seeded rectangle of ones (the region to repaint) per image, from a third generator of its
         own.  conditioning_images=True (3 channels) or n adds conditioning_pixel_values f32 (B, n, bucket[0], bucket[1]) in [0, 1] for a ControlNet: a
-        seeded coarse 8 x 8 pattern per image, nearest-neighbour enlarged to the pixel size, from a fourth generator.  The defaults add
-        none of them.
+        seeded coarse 8 x 8 pattern per image, nearest-neighbour enlarged to the pixel size, from a fourth generator.  image_embeds=E adds
+        image_embeds f32 (B, E) for an IP-Adapter - a seeded normal vector per image, the stand-in for an image encoder's pooled embedding,
+        from a fifth generator; image_embed_drop_rate=p zeroes a sample's embedding with probability p (the published training script's
+        image-prompt dropout, which lets classifier-free guidance drop the image prompt).  The defaults add none of them.
         placeholder_ids (a list of ids, or one list per tower for text_towers=2) overwrites the positions after BOS of every caption
         window with those ids - the caption "<sks> ..." of a textual-inversion run; the other entries keep their values."""
         if self._cursor >= len(self._plan):
@@ -146,6 +154,12 @@ class DataLoader:
             coarse = torch.rand(per_rank, self.conditioning_images, 8, 8, generator=gc)
             ys, xs = torch.arange(b0) * 8 // b0, torch.arange(b1) * 8 // b1
             batch["conditioning_pixel_values"] = coarse[:, :, ys][:, :, :, xs].contiguous()
+        if self.image_embeds:
+            ge = torch.Generator().manual_seed(((int(self.seed) * 1_000_003 + int(self.chunk_number)) * 1_000_003 + index * 64 + self.rank) ^ 0x3C6EF372FE94F82B)
+            emb = torch.randn(per_rank, self.image_embeds, generator=ge)
+            if self.image_embed_drop_rate:
+                emb[torch.rand(per_rank, generator=ge) < self.image_embed_drop_rate] = 0.0
+            batch["image_embeds"] = emb
         if self.prior_every:
             first = self.rank * per_rank  # this shard's first sample in the global batch
             batch["loss_weight"] = torch.tensor([self.prior_loss_weight if (first + i) % self.prior_every == self.prior_every - 1 else 1.0

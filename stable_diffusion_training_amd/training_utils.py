@@ -90,6 +90,8 @@ class TrainState:
     New tokens (new_tokens=): the text state's `tokens` is the tokens.TokenAdapter hung on its frozen store; its store of trained rows
     takes the optimizer step.
     ControlNet (controlnet=): the UNet state's `controlnet` is the nets.ControlNet (store + config) trained on the frozen UNet; its store
+    takes the optimizer step.
+    IP-Adapter (ip_adapter=): the UNet state's `ip_adapter` is the nets.IPAdapter (store + config) trained on the frozen UNet; its store
     takes the optimizer step."""
     apply_fn: Callable
     store: ParamStore
@@ -98,6 +100,7 @@ class TrainState:
     adapter: Any = None
     tokens: Any = None
     controlnet: Any = None
+    ip_adapter: Any = None
 
     @property
     def opt_store(self):
@@ -105,6 +108,8 @@ class TrainState:
         neither adapter nor tokens); a ControlNet's store on the UNet state that carries one."""
         if self.controlnet is not None:
             return self.controlnet.store
+        if self.ip_adapter is not None:
+            return self.ip_adapter.store
         if self.adapter is not None:
             return self.adapter.store
         if self.tokens is not None:
@@ -127,7 +132,7 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                                  lion_8bit_block_size=None, quantize_unet_state=False, quantize_text_encoder_state=False,
                                  with_unet_ema=False, with_text_encoder_ema=False, device="cuda", lr_scheduler="constant",
                                  lr_schedule=None, ema_schedule=None, ema_rate=0.0, optimizer="lion", lora=None, new_tokens=None,
-                                 controlnet=None):
+                                 controlnet=None, ip_adapter=None):
     """training_utils.py:281-427.  lr = learning_rate / adam_to_lion_scale_factor, wd = 1e-2 * scale, b1=.9, b2=.99,
     chain(clip_by_global_norm(1), lion_8bit | lion).  Builds the flat HBM stores and loads the weights.
     lr_scheduler / lr_schedule / ema_schedule / ema_rate: the per-step schedules of lr_schedule.resolve, installed in each trained store
@@ -151,8 +156,33 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
     controlnet: None, or dict(config=nets.controlnet_config(...)[, params=host tree]) - a loaded ControlNet, or one initialised from the
     UNet (nets.controlnet_from_unet).  Both base stores are built frozen; the UNet state's `controlnet` holds the ControlNet's store, which
     the UNet's settings above configure and which steps; the text encoder only runs its forward.  Refused beside lora= or new_tokens=, on
-    an inpainting UNet, and with a config that does not extend the UNet's."""
+    an inpainting UNet, and with a config that does not extend the UNet's.
+    ip_adapter: None, or dict(config=nets.ip_adapter_config(...)[, params=host tree]) - a loaded IP-Adapter, or one initialised from the
+    UNet (nets.ip_adapter_from_unet).  As controlnet=: both base stores are built frozen, the UNet state's `ip_adapter` holds the adapter's
+    store, which the UNet's settings configure and which steps.  Refused beside lora=, new_tokens= and controlnet=, on an inpainting UNet,
+    and with a config that does not extend the UNet's."""
     out = {"unet_state": None, "text_encoder_state": None}
+    if ip_adapter is not None:
+        if not isinstance(ip_adapter, dict) or "config" not in ip_adapter or set(ip_adapter) - {"config", "params"}:
+            raise ValueError(f"ip_adapter: None or dict(config=nets.ip_adapter_config(...)[, params=tree]), not {ip_adapter!r}")
+        if lora is not None:
+            raise ValueError("ip_adapter: an IP-Adapter beside a LoRA adapter is not supported")
+        if new_tokens is not None:
+            raise ValueError("ip_adapter: an IP-Adapter beside new tokens is not supported")
+        if controlnet is not None:
+            raise ValueError("ip_adapter: an IP-Adapter beside a ControlNet is not supported")
+        if not (train_unet and train_text_encoder):
+            raise ValueError("ip_adapter: needs both states (train_unet and train_text_encoder)")
+        icfg, ucfg = ip_adapter["config"], models["unet"]["config"]
+        if nets.inpaint_latent_channels(ucfg) is not None:
+            raise ValueError("ip_adapter: an IP-Adapter on an inpainting UNet is not supported")
+        if "image_embed_dim" not in icfg or "num_tokens" not in icfg:
+            raise ValueError("ip_adapter: the config needs image_embed_dim and num_tokens (nets.ip_adapter_config)")
+        nets.ip_adapter_config(ucfg, icfg["image_embed_dim"], icfg["num_tokens"])
+        for k in ("block_out_channels", "down_block_types", "up_block_types", "layers_per_block", "cross_attention_dim",
+                  "attention_head_dim", "transformer_layers_per_block"):
+            if _plain(icfg.get(k)) != _plain(ucfg.get(k)):
+                raise ValueError(f"ip_adapter: the config's {k}={icfg.get(k)!r} differs from the UNet's {ucfg.get(k)!r}")
     if controlnet is not None:
         if not isinstance(controlnet, dict) or "config" not in controlnet or set(controlnet) - {"config", "params"}:
             raise ValueError(f"controlnet: None or dict(config=nets.controlnet_config(...)[, params=tree]), not {controlnet!r}")
@@ -193,7 +223,7 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
                              "text_encoder='frozen'")
         lora = {"unet": lora["unet"], "text_encoder": te_l}
     # the base stores only run; adapters' / the tokens' / the ControlNet's own stores step
-    frozen = lora is not None or new_tokens is not None or controlnet is not None
+    frozen = lora is not None or new_tokens is not None or controlnet is not None or ip_adapter is not None
     opt_cls, opt = optimizers.parse(optimizer)
 
     def make(spec, weights, cfg, fn, lr, quant, ema, which):
@@ -218,8 +248,19 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
             cstore.load(cw if cw is not None else nets.controlnet_from_unet(weights, ccfg))
             cstore.controlnet_config = ccfg  # marks the store: save_model refuses it (and its EMA view) as UNet weights
             cn = nets.ControlNet(cstore, ccfg)
-        state = TrainState(fn, store, cfg, hyper if not frozen or adapter is not None or toks is not None or cn is not None else {},
-                           adapter, toks, cn)
+        ipa = None
+        if ip_adapter is not None and which == "unet":  # the adapter's own store takes the UNet's keywords and the optimizer step
+            icfg = ip_adapter["config"]
+            istore = ParamStore(nets.ip_adapter_spec(icfg), device=device, **okw)
+            iw = ip_adapter.get("params")
+            if iw is not None and any(isinstance(v, dict) for v in iw.values()):
+                from .checkpoint import flatten_tree
+                iw = flatten_tree(iw)
+            istore.load(iw if iw is not None else nets.ip_adapter_from_unet(weights, icfg))
+            istore.ip_adapter_config = icfg  # marks the store: save_model refuses it (and its EMA view) as UNet weights
+            ipa = nets.IPAdapter(istore, icfg)
+        trained = not frozen or adapter is not None or toks is not None or cn is not None or ipa is not None
+        state = TrainState(fn, store, cfg, hyper if trained else {}, adapter, toks, cn, ipa)
         if sched is not None and state.opt_store is not None:
             state.opt_store.set_schedule(lr=sched[0], ema=sched[1])
         return state
@@ -242,7 +283,7 @@ def _plain(v):
 
 
 def on_device_model_training_state(training_config: TrainingConfig, models=None, device="cuda", *, lr_schedule=None,
-                                   ema_schedule=None, optimizer="lion", lora=None, new_tokens=None, controlnet=None):
+                                   ema_schedule=None, optimizer="lion", lora=None, new_tokens=None, controlnet=None, ip_adapter=None):
     """training_utils.py:430-501.  `models`: load_models' result - host weight trees + configs
     ({"unet": {"unet_params", "config"}, "vae": {"vae_params", "config"}, "text_encoder": {...}}); None reads the
     diffusers directory at training_config.model_path (checkpoint.load_models).  Note the reference passes NEITHER learning
@@ -259,7 +300,9 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
     beside a UNet LoRA.  The text state's `tokens` is the TokenAdapter and its EMA view wraps the token store; a UNet without an adapter
     has no EMA view (None).
     controlnet: create_lion_optimizer_states' - dict(config=[, params=]) trains a ControlNet on the frozen UNet: unet_state.controlnet
-    holds its store and config, the UNet EMA view wraps that store, the text encoder has none."""
+    holds its store and config, the UNet EMA view wraps that store, the text encoder has none.
+    ip_adapter: create_lion_optimizer_states' - dict(config=[, params=]) trains an IP-Adapter on the frozen UNet the same way:
+    unet_state.ip_adapter holds its store and config; batches carry image_embeds."""
     _lib.require_device()
     if models is None:
         models = load_models(training_config)
@@ -272,7 +315,8 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
         quantize_text_encoder_state=training_config.quantize_text_encoder_state,
         with_unet_ema=training_config.accumulate_unet_ema, with_text_encoder_ema=training_config.accumulate_text_encoder_ema,
         device=device, lr_scheduler=training_config.lr_scheduler, lr_schedule=lr_schedule, ema_schedule=ema_schedule,
-        ema_rate=training_config.ema_rate, optimizer=optimizer, lora=lora, new_tokens=new_tokens, controlnet=controlnet)
+        ema_rate=training_config.ema_rate, optimizer=optimizer, lora=lora, new_tokens=new_tokens, controlnet=controlnet,
+        ip_adapter=ip_adapter)
     vae_cfg = models["vae"]["config"]
     vae_store = ParamStore(nets.vae_encoder_spec(vae_cfg), device=device, trainable=False)
     vae_store.load(models["vae"]["vae_params"])
@@ -502,6 +546,32 @@ def _check_inpaint_entries(batch, unet_cfg, device):
 CONTROL_KEYS = ("conditioning_pixel_values",)  # the batch entry a ControlNet state's step reads (diffusers' name)
 
 
+IP_KEYS = ("image_embeds",)  # the batch entry an IP-Adapter state's step reads (the published training script's name)
+
+
+def _check_ip_entries(batch, ip_adapter, device, rows):
+    """ValueError for an image_embeds entry that does not fit the state or the batch: an IP-Adapter state needs it, f32 or bf16 (B, E)
+    with E = the config's image_embed_dim, contiguous on the step's device; a state without an IP-Adapter refuses it."""
+    emb = batch.get("image_embeds")
+    if ip_adapter is None:
+        if emb is not None:
+            raise ValueError("image_embeds need an IP-Adapter state (on_device_model_training_state(ip_adapter=)); this UNet state "
+                             "carries none")
+        return
+    E = int(ip_adapter.config["image_embed_dim"])
+    if emb is None:
+        raise ValueError(f"an IP-Adapter state's batch needs image_embeds (f32 or bf16 (B, {E}): the image encoder's pooled embedding)")
+    if not torch.is_tensor(emb) or emb.dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"image_embeds must be a float32 or bfloat16 tensor, not {getattr(emb, 'dtype', type(emb))}")
+    if not _on_device(emb, device):
+        raise ValueError(f"image_embeds live on {emb.device}, the step runs on {device}")
+    if tuple(emb.shape) != (rows, E):
+        raise ValueError(f"image_embeds have shape {tuple(emb.shape)}; the batch has {rows} samples and the adapter's image_embed_dim is "
+                         f"{E}: ({rows}, {E})")
+    if not emb.is_contiguous():
+        raise ValueError("image_embeds must be contiguous")
+
+
 def _check_control_entries(batch, controlnet, device):
     """ValueError for a conditioning_pixel_values entry that does not fit the state or the batch's image (which _check_batch has
     validated): a ControlNet state needs it, f32 NCHW (B, conditioning_channels, H, W) at pixel size - the size of pixel_values, or
@@ -679,6 +749,22 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                              "the ControlNet's store steps")
     elif getattr(text_encoder_state, "controlnet", None) is not None:
         raise ValueError("ControlNet: the UNet state carries the ControlNet, not the text-encoder state")
+    ipa = getattr(unet_state, "ip_adapter", None)
+    if ipa is not None:
+        if reducer is not None:
+            raise ValueError("IP-Adapter: data-parallel training is not supported - the GradReducer would have to be built over the "
+                             "adapter's store (TrainState.ip_adapter.store)")
+        if adapters or tk is not None or getattr(us, "adapter", None) is not None or getattr(ts, "tokens", None) is not None:
+            raise ValueError("IP-Adapter: a LoRA adapter or new tokens beside an IP-Adapter are not supported")
+        if cn is not None:
+            raise ValueError("IP-Adapter: a ControlNet beside an IP-Adapter is not supported")
+        if nets.inpaint_latent_channels(unet_state.config) is not None:
+            raise ValueError("IP-Adapter: an inpainting UNet is not supported")
+        if us.trainable or ts.trainable:
+            raise ValueError("IP-Adapter: a trainable base store is not supported - the UNet and the text encoder are frozen and only "
+                             "the adapter's store steps")
+    elif getattr(text_encoder_state, "ip_adapter", None) is not None:
+        raise ValueError("IP-Adapter: the UNet state carries the IP-Adapter, not the text-encoder state")
     lora = bool(adapters) or tk is not None  # the frozen-base step: adapters' and / or the tokens' own stores are the ones that step
     if adapters:
         if us.trainable or ts.trainable or unet_state.adapter is None:
@@ -691,10 +777,13 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     opt_stores = ([a.store for a in adapters] + ([tk.store] if tk is not None else [])) if lora else [us, ts]
     if cn is not None:
         opt_stores = [cn.store]
+    if ipa is not None:
+        opt_stores = [ipa.store]
     sched, sched_state = frozen_noise_scheduler_state.call, frozen_noise_scheduler_state.params
     dev = us.device
     cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev, masked_loss_floor, normalize_masked_area)
     _check_control_entries(batch, cn, dev)
+    _check_ip_entries(batch, ipa, dev, int(batch["latent_moments" if cached else "pixel_values"].shape[0]))
     masked = any(k in batch for k in LOSS_KEYS)
     inpaint = "inpaint_mask" in batch  # (_check_batch: exactly the batches of an inpainting UNet)
     robust = LOSS_TYPES[loss_type]  # 0: the squared error
@@ -723,7 +812,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         else:
             sl = slice(k * B, (k + 1) * B)
             kc = batch["input_ids"].shape[0] // N  # text-encoder rows per sample
-            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids", "masked_latent_moments") + LOSS_KEYS + INPAINT_KEYS + CONTROL_KEYS}
+            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids", "masked_latent_moments") + LOSS_KEYS + INPAINT_KEYS + CONTROL_KEYS + IP_KEYS}
             mb["input_ids"] = batch["input_ids"][k * B * kc: (k + 1) * B * kc]
             rnd = {n: v[sl] for n, v in rand.items()}
 
@@ -760,8 +849,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                     ad.merge("master")
                 if tk is not None:
                     tk.select("master")  # (no launch: the embedding reads the trained rows where they are)
-            elif k == 0 and cn is not None:
-                cn.store.prepare()  # (the frozen mirrors stay as the load left them)
+            elif k == 0 and (cn is not None or ipa is not None):
+                (cn or ipa).store.prepare()  # (the frozen mirrors stay as the load left them)
             elif k == 0:
                 us.prepare()
                 ts.prepare()
@@ -862,7 +951,12 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             with trace.phase("controlnet_forward"):
                 down_r, mid_r = nets.controlnet_forward(cn.store, cn.config, noisy, timesteps, ctx, hint, added)
         with trace.phase("unet_forward"):
-            if cn is not None:
+            ip_tokens = None
+            if ipa is not None:
+                # image_proj on the adapter's (trained) store, then every attn2 of the frozen UNet adds its image term at unit scale
+                ip_tokens = nets.ip_adapter_tokens(ipa.store, ipa.config, mb["image_embeds"])
+                pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added, ip=(ipa.store, ip_tokens))
+            elif cn is not None:
                 pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added, control=(down_r, mid_r))
             else:
                 pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx, added)
@@ -914,6 +1008,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             if inpaint:
                 aux.update(inpaint_mask=(lmask >= 0.5).to(torch.float32), masked_latents=mlat, unet_input=noisy.detach(),
                            masked_moments=mmoments)
+            if ip_tokens is not None:
+                aux["ip_tokens"] = ip_tokens.detach()
             if cn is not None:
                 aux.update(control_hint=hint, control_down=[r.detach() for r in down_r], control_mid=mid_r.detach())
 
@@ -932,7 +1028,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     if K == 1:
         # one process: the norm clip_by_global_norm needs is that of the gradients as the weight-gradient kernels write them - they leave
         # its partial sums behind (ops.sq_begin / sq_end), and the 4-byte-per-parameter pass over the finished buffer is not needed
-        loss, sq_u, sq_t, lps = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora and cn is None)
+        loss, sq_u, sq_t, lps = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora and cn is None and ipa is None)
         grad_source = "grad"
         # data-parallel mean of the gradients (implicit all-reduce under GSPMD in the reference)
         if reducer is not None:
@@ -1012,7 +1108,7 @@ class _GraphedStep:
 
     def __init__(self, fn, warmup=2, reducer=None):
         self.fn, self.warmup, self.calls = fn, warmup, 0
-        self.graph = self.static = self.static_rand = self.out = self.sig = self.loss_keys = self.inpaint_keys = self.control_keys = None
+        self.graph = self.static = self.static_rand = self.out = self.sig = self.loss_keys = self.inpaint_keys = self.control_keys = self.ip_keys = None
         # multi-rank: graph A (forward + backward) | eager bucketed all-reduce behind per-bucket events | graph B (optimizer)
         self.reducer = reducer if (reducer is not None and reducer.active) else None
         self.graph_b = self.plan = None
@@ -1025,6 +1121,7 @@ class _GraphedStep:
         self.loss_keys = tuple(k in batch for k in LOSS_KEYS)
         self.inpaint_keys = tuple(k in batch for k in INPAINT_KEYS)
         self.control_keys = tuple(k in batch for k in CONTROL_KEYS)
+        self.ip_keys = tuple(k in batch for k in IP_KEYS)
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         if rng is not None and hasattr(g, "register_generator_state"):
@@ -1118,6 +1215,9 @@ class _GraphedStep:
         if self.control_keys != tuple(k in batch for k in CONTROL_KEYS):
             raise ValueError(f"this step was captured {'with' if self.control_keys[0] else 'without'} conditioning_pixel_values in its "
                              "batch and replays those launches: a batch that adds or drops it needs a step table of its own")
+        if self.ip_keys != tuple(k in batch for k in IP_KEYS):
+            raise ValueError(f"this step was captured {'with' if self.ip_keys[0] else 'without'} image_embeds in its batch and replays "
+                             "those launches: a batch that adds or drops it needs a step table of its own")
         for k, v in self.static.items():
             v.copy_(batch[k], non_blocking=True)
         if rand is not None:
@@ -1155,7 +1255,7 @@ def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_pa
     of the batch it was captured with: it
     raises ValueError for a later batch that adds or drops loss_mask / loss_weight, or inpaint_mask (an inpainting UNet's batches
     always carry it; the static buffers take the mask and, for cached batches, masked_latent_moments like any other tensor key), or
-    conditioning_pixel_values (a ControlNet state's batches always carry it; CONTROL_KEYS)."""
+    conditioning_pixel_values (a ControlNet state's batches always carry it; CONTROL_KEYS), or image_embeds (an IP-Adapter state's; IP_KEYS)."""
     import os
     B = per_device_batch or training_config.batch_size
     if not isinstance(micro_batches, int) or micro_batches < 1:
