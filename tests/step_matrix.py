@@ -39,7 +39,9 @@ EMA_SCHEDULE = dict(kind="warmup")
 WD_EXCLUDED = ["bias", "scale", "embedding", "lora_b"]
 QUANT_EXCLUDED = ["bias", "scale", "embedding", "conv_in", "conv_out", "time_embedding", "embeddings", "time_emb_proj", "to_out_0", "out_proj"]
 RANK, ALPHA = 8, 4.0
-STATE = ("master", "w", "codes", "inv_scale", "codes2", "inv_scale2", "mom", "mom2", "ema", "adam_step", "adam_prod", "adam_cur", "sqnorm")
+# (a store holds None for the buffers of another optimizer: Prodigy's are skipped by a Lion / AdamW store and the reverse)
+STATE = ("master", "w", "codes", "inv_scale", "codes2", "inv_scale2", "mom", "mom2", "ema", "adam_step", "adam_prod", "adam_cur", "sqnorm",
+         "prodigy_s", "prodigy_p0", "prodigy_state", "prodigy_step", "prodigy_cur")
 STEP_HP = dict(lr=1e-3, wd=0.07, eps=1e-8, max_norm=1.0)  # tests/test_gpu_adamw.py's store-level steps
 WORKERS = 8  # threads the harness's reference step spreads a store's leaves over
 
@@ -138,8 +140,9 @@ def _lion_reference_store_step(st, ref, g_flat, lr, ema_rate, hp, workers=1):
     _leaves(st, leaf, workers)
 
 
-def _check_store(st, ref, tag):
-    """Master, EMA, bf16 mirror and the moment states of every leaf of `st` against ref, in every bit."""
+def _check_store(st, ref, tag, mirror_of=None):
+    """Master, EMA, bf16 mirror and the moment states of every leaf of `st` against ref, in every bit.  mirror_of: {path: the values
+    the sweep mirrored} where something rewrote the master after the sweep (a token store's retraction); None: the master's."""
     adamw = st.optimizer == "adamw"
     master, ema = st.export("master"), (st.export("ema") if st.ema is not None else None)
     mm, ss = st.export_momentum("m"), (st.export_momentum("s") if adamw else None)
@@ -147,7 +150,8 @@ def _check_store(st, ref, tag):
         assert_equal_bits(master[path].reshape(-1).cpu(), torch.from_numpy(ref["p"][path]), f"{tag}: {path} master")
         if ema is not None:
             assert_equal_bits(ema[path].reshape(-1).cpu(), torch.from_numpy(ref["ema"][path]), f"{tag}: {path} ema")
-        assert_equal_bits(st.w[lf.offset: lf.offset + lf.numel].cpu(), torch.from_numpy(ref["p"][path]).to(BF), f"{tag}: {path} bf16 mirror")
+        mirrored = ref["p"][path] if mirror_of is None else mirror_of[path]
+        assert_equal_bits(st.w[lf.offset: lf.offset + lf.numel].cpu(), torch.from_numpy(mirrored).to(BF), f"{tag}: {path} bf16 mirror")
         if lf.quantised and adamw:
             for name, (c, i), wc, wi in (("m", mm[path], *ref["m"][path][:2]), ("s", ss[path], *ref["m"][path][2:])):
                 msg = kc.lion_state_report(c.cpu().numpy(), i.cpu().numpy(), wc, wi, f"{tag}: {path} {name}")
@@ -207,9 +211,9 @@ def reference_store_step(st, ref, g_flat, hp, ema_rate, schedule=None):
     return None
 
 
-def check_store(st, ref, cur, tag):
+def check_store(st, ref, cur, tag, mirror_of=None):
     """_check_store plus the optimizer's scalars: host count, and for AdamW the device counter, products and scalar block."""
-    _check_store(st, ref, tag)
+    _check_store(st, ref, tag, mirror_of)
     assert st.count == ref["t"], f"{tag}: host step count {st.count}, expected {ref['t']}"
     if st.optimizer == "adamw":
         assert_equal_bits(st.adam_cur.cpu(), torch.from_numpy(cur), f"{tag}: scalar block")
