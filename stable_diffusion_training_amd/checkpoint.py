@@ -156,6 +156,11 @@ def flatten_tree(tree, prefix=""):
     return out
 
 
+def flatten_if_nested(tree):
+    """A parameter tree in the path form, whichever form it came in (flat trees pass through as they are)."""
+    return flatten_tree(tree) if any(isinstance(v, dict) for v in tree.values()) else tree
+
+
 def unflatten_tree(flat):
     out = {}
     for p, v in flat.items():
@@ -271,12 +276,10 @@ def save_model(model_object_dict, tokenizer_object, unet_params, text_encoder_pa
     A text encoder that carries new tokens (tokens.attach) is written resized: its token table holds the V base rows followed by the n
     trained ones and its config's vocab_size is V + n, so the directory loads into a plain store of this project."""
     ustore = unet_params.store if hasattr(unet_params, "store") else unet_params
-    if getattr(ustore, "controlnet_config", None) is not None:
-        raise ValueError("save_model: unet_params is (the EMA view of) a ControlNet's store, not a UNet: pass the frozen UNet "
-                         "(unet_state.params) here and write the ControlNet with save_controlnet")
-    if getattr(ustore, "ip_adapter_config", None) is not None:
-        raise ValueError("save_model: unet_params is (the EMA view of) an IP-Adapter's store, not a UNet: pass the frozen UNet "
-                         "(unet_state.params) here and write the adapter with save_ip_adapter")
+    for net in nets.SIDE_NETWORKS:
+        if getattr(ustore, net.marker, None) is not None:
+            raise ValueError(f"save_model: unet_params is (the EMA view of) {net.article}'s store, not a UNet: pass the frozen UNet "
+                             f"(unet_state.params) here and write {net.the} with save_{net.name}")
     os.makedirs(output_dir, exist_ok=True)
     dv = {"_diffusers_version": DIFFUSERS_VERSION}
     _write_submodel(output_dir, "unet", _model_config(model_object_dict, "unet"),
@@ -475,22 +478,11 @@ def _prodigy_meta(store):
 
 
 def _stepping_store(st):
-    """The store of a state whose buffers a training-state file holds: the state's own store, the store of its LoRA adapter (the frozen
-    base under it is not written: it is the checkpoint the run started from), or None for a frozen model without an adapter."""
-    store = st.store if hasattr(st, "store") else st
-    cn = getattr(st, "controlnet", None)
-    if cn is not None:  # a ControlNet on the frozen UNet: the ControlNet's store (the layout digest tells it from the UNet's)
-        return cn.store, None
-    ipa = getattr(st, "ip_adapter", None)
-    if ipa is not None:  # an IP-Adapter on the frozen UNet: the adapter's store, likewise
-        return ipa.store, None
-    ad = getattr(st, "adapter", None)
-    if ad is not None:
-        return ad.store, ad
-    tk = getattr(st, "tokens", None)
-    if tk is not None:  # new tokens: the token store (the frozen text encoder under it is not written)
-        return tk.store, None
-    return (store if getattr(store, "trainable", True) else None), None
+    """The store of a state (or a bare store) whose buffers a training-state file holds, and its LoRA adapter if that is what steps:
+    TrainState.stepping_of.  The frozen base under an adapter, new tokens or a side network is not written: it is the checkpoint the
+    run started from (a side network's layout digest tells its file from the UNet's)."""
+    from .training_utils import TrainState
+    return TrainState.stepping_of(st)
 
 
 def _tokens_meta(st):

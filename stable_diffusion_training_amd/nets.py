@@ -12,6 +12,7 @@ Activations are NHWC bf16 with channels padded to a multiple of 8 (4-channel lat
 """
 import contextlib
 import math
+from typing import Callable, NamedTuple
 
 import torch
 
@@ -320,10 +321,8 @@ def controlnet_from_unet(unet_params, cfg, seed=0):
     copies of the UNet's, the embedder's convolutions are seeded random (init_params) and conv_out, every controlnet_down_blocks_* and
     controlnet_mid_block are zero - so the ControlNet's residuals are zero and the UNet computes what it did without it.
     unet_params: flat or nested tree, torch tensors or numpy arrays."""
-    if any(isinstance(v, dict) for v in unet_params.values()):
-        from .checkpoint import flatten_tree
-        unet_params = flatten_tree(unet_params)
-    spec = controlnet_spec(cfg)
+    from .checkpoint import flatten_if_nested
+    spec, unet_params = controlnet_spec(cfg), flatten_if_nested(unet_params)
     fresh = init_params([(p, shp) for p, shp in spec if p.startswith("controlnet_")], seed)
     zero = set(controlnet_zero_leaves(cfg))
     out = {}
@@ -388,10 +387,8 @@ def ip_adapter_from_unet(unet_params, cfg, seed=0):
     """A fresh IP-Adapter for a UNet, as the published training script initialises it (host tree, flat paths): to_k_ip / to_v_ip are
     copies of the UNet's attn2 to_k / to_v, image_proj is drawn from the seed (init_params).  unet_params: flat or nested tree, torch
     tensors or numpy arrays."""
-    if any(isinstance(v, dict) for v in unet_params.values()):
-        from .checkpoint import flatten_tree
-        unet_params = flatten_tree(unet_params)
-    spec = ip_adapter_spec(cfg)
+    from .checkpoint import flatten_if_nested
+    spec, unet_params = ip_adapter_spec(cfg), flatten_if_nested(unet_params)
     out = init_params([(p, shp) for p, shp in spec if p.startswith("image_proj/")], seed)
     for p, shp in spec:
         if p in out:
@@ -403,6 +400,56 @@ def ip_adapter_from_unet(unet_params, cfg, seed=0):
             raise ValueError(f"ip_adapter_from_unet: {src} has shape {tuple(v.shape)} in the UNet, the adapter's config says {tuple(shp)}")
         out[p] = v
     return out
+
+
+class SideNetwork(NamedTuple):
+    """What the training layer, save_model and the sampling pipeline need to know of a network with a ParamStore of its own that is
+    trained on the frozen UNet and selected by one batch key.  Everything that handles such a network is written once over this
+    description (training_utils: the builder's argument, the store it builds, train_step's refusals and prepare(); checkpoint.save_model;
+    StableDiffusionPipeline); the forward call and the aux taps differ in kind and stay explicit in train_step.
+    The rules, for a network `name`: the builder takes name=None or dict(config=nets.<name>_config(...)[, params=host tree]) - a loaded
+    network, or one initialised from the UNet (from_unet).  Both base stores are built frozen; the UNet state's field `name` holds the
+    wrapper (store + config), whose store the UNet's settings configure and which steps; the text encoder only runs its forward.
+    Refused beside lora=, new_tokens= and another side network, on an inpainting UNet, with a reducer, and with a config that does not
+    add the keys `adds` to the UNet's or differs from it in one of `same`.  The batches of such a state carry batch_key."""
+    name: str            # the TrainState / pipeline field, the builder's and the pipeline's argument
+    label: str           # "ControlNet": the head of train_step's messages
+    article: str         # "a ControlNet"
+    the: str             # "the ControlNet": how messages name the network once it is known
+    batch_key: str       # the batch entry its step reads
+    adds: tuple          # the config keys beyond the UNet's, in the order <name>_config takes them
+    same: tuple          # the config keys that must equal the UNet's
+    config: Callable     # <name>_config(unet_cfg, *(cfg[k] for k in adds), **config_kwargs(models)): ValueError for a bad config
+    config_kwargs: Callable
+    spec: Callable       # <name>_spec(cfg)
+    from_unet: Callable  # <name>_from_unet(unet weights, cfg)
+    wrapper: type        # (store, config)
+    marker: str          # the attribute of a trained store that holds the config: save_model refuses such a store as UNet weights
+    beside: tuple        # the builder's refusals of other arguments: ((argument names, message), ...), in order
+
+
+def _controlnet_config_kwargs(models):
+    return dict(vae_downscale=2 ** (len(models["vae"]["config"]["block_out_channels"]) - 1) if "vae" in models else 8)
+
+
+CONTROLNET = SideNetwork(
+    "controlnet", "ControlNet", "a ControlNet", "the ControlNet", "conditioning_pixel_values",
+    ("conditioning_embedding_out_channels", "conditioning_channels"),
+    ("block_out_channels", "down_block_types", "layers_per_block", "in_channels", "cross_attention_dim", "attention_head_dim",
+     "use_linear_projection", "transformer_layers_per_block", "norm_num_groups", "addition_embed_type"),
+    controlnet_config, _controlnet_config_kwargs, controlnet_spec, controlnet_from_unet, ControlNet, "controlnet_config",
+    ((("lora", "new_tokens"), "controlnet: a ControlNet beside a LoRA adapter or new tokens is not supported"),))
+IP_ADAPTER = SideNetwork(
+    "ip_adapter", "IP-Adapter", "an IP-Adapter", "the adapter", "image_embeds", ("image_embed_dim", "num_tokens"),
+    ("block_out_channels", "down_block_types", "up_block_types", "layers_per_block", "cross_attention_dim", "attention_head_dim",
+     "transformer_layers_per_block"),
+    ip_adapter_config, lambda models: {}, ip_adapter_spec, ip_adapter_from_unet, IPAdapter, "ip_adapter_config",
+    ((("lora",), "ip_adapter: an IP-Adapter beside a LoRA adapter is not supported"),
+     (("new_tokens",), "ip_adapter: an IP-Adapter beside new tokens is not supported"),
+     (("controlnet",), "ip_adapter: an IP-Adapter beside a ControlNet is not supported")))
+# in the order a state is searched for them (TrainState.stepping) and train_step refuses them; a later one names the earlier ones it
+# cannot stand beside
+SIDE_NETWORKS = (CONTROLNET, IP_ADAPTER)
 
 
 def time_emb_groups(leaves):

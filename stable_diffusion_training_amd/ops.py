@@ -7,6 +7,7 @@ straight into the owning ParamStore's flat gradient buffers (the all-reduce payl
 leaves, fp32 for everything else; ParamStore.grad_view) as a side effect of backward; `store.grad_ready(path)` lets
 the data-parallel reducer launch a bucket as soon as it is complete.
 """
+import contextlib
 import os
 
 import torch
@@ -186,6 +187,19 @@ def gn_arena_active(device):
     """Whether a step's arena is open on this device (gn_arena_begin without its gn_arena_end)."""
     a = _GN_ARENA.get(device)
     return a is not None and a[2]
+
+
+@contextlib.contextmanager
+def gn_arena(device):
+    """The step's arena where one is open on this device, else an arena opened for this block and closed after it."""
+    own = not gn_arena_active(device)
+    if own:
+        gn_arena_begin(device)
+    try:
+        yield
+    finally:
+        if own:
+            gn_arena_end(device)
 
 
 def _arena_zeros(n, device):

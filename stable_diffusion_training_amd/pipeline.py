@@ -30,30 +30,24 @@ class StableDiffusionPipeline:
         dict(config=, params=) as checkpoint.load_controlnet returns it (loaded into a frozen store)."""
         _lib.require_device()
         self.unet, self.text_encoder = _store_of(unet), _store_of(text_encoder)
-        self.controlnet = controlnet
-        if controlnet is not None and nets.inpaint_latent_channels(unet_config) is not None:
-            raise ValueError("a ControlNet on an inpainting UNet is not supported")
-        if isinstance(controlnet, dict):
-            cstore = ParamStore(nets.controlnet_spec(controlnet["config"]), device=torch.device(device) if device is not None else self.unet.device,
-                                trainable=False)
-            cstore.load(controlnet["params"])
-            self.controlnet = nets.ControlNet(cstore, controlnet["config"])
-        self.ip_adapter = ip_adapter
-        if ip_adapter is not None and nets.inpaint_latent_channels(unet_config) is not None:
-            raise ValueError("an IP-Adapter on an inpainting UNet is not supported")
-        if ip_adapter is not None and controlnet is not None:
-            raise ValueError("an IP-Adapter beside a ControlNet is not supported")
-        if isinstance(ip_adapter, dict):
-            istore = ParamStore(nets.ip_adapter_spec(ip_adapter["config"]), device=torch.device(device) if device is not None else self.unet.device,
-                                trainable=False)
-            istore.load(ip_adapter["params"])
-            self.ip_adapter = nets.IPAdapter(istore, ip_adapter["config"])
         self.unet_config, self.text_encoder_config, self.vae_config = unet_config, text_encoder_config, vae_config
         self.device = torch.device(device) if device is not None else self.unet.device
+        given = dict(controlnet=controlnet, ip_adapter=ip_adapter)
+        for i, net in enumerate(nets.SIDE_NETWORKS):  # self.controlnet, self.ip_adapter: None or the wrapper (nets.SideNetwork)
+            side = given[net.name]
+            if side is not None and nets.inpaint_latent_channels(unet_config) is not None:
+                raise ValueError(f"{net.article} on an inpainting UNet is not supported")
+            for other in nets.SIDE_NETWORKS[:i]:
+                if side is not None and given[other.name] is not None:
+                    raise ValueError(f"{net.article} beside {other.article} is not supported")
+            if isinstance(side, dict):
+                store = ParamStore(net.spec(side["config"]), device=self.device, trainable=False)
+                store.load(side["params"])
+                side = net.wrapper(store, side["config"])
+            setattr(self, net.name, side)
         self.vae_decoder = ParamStore(nets.vae_decoder_spec(vae_config), device=self.device, trainable=False)
-        if any(isinstance(v, dict) for v in vae_params.values()):  # nested Flax tree -> "a/b/kernel" paths
-            from .checkpoint import flatten_tree
-            vae_params = flatten_tree(vae_params)
+        from .checkpoint import flatten_if_nested
+        vae_params = flatten_if_nested(vae_params)  # nested Flax tree -> "a/b/kernel" paths
         self.vae_decoder.load(vae_params)
         self.vae_decoder.prepare()
         self.vae_params, self.vae_encoder = vae_params, None  # the encoder store is built on first use (inpainting: _inpaint_conditioning)

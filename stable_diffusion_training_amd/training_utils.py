@@ -17,7 +17,7 @@ import numpy as np
 import torch
 
 from . import _lib, lora as lora_mod, nets, ops, optimizers, tokens as tokens_mod, trace
-from .checkpoint import load_models, load_training_state, save_model, save_training_state  # noqa: F401  (reference names)
+from .checkpoint import flatten_if_nested, load_models, load_training_state, save_model, save_training_state  # noqa: F401  (reference names)
 from .lr_schedule import resolve as resolve_schedule
 from .params import EmaView, ParamStore, create_mask  # noqa: F401  (create_mask re-exported, reference name)
 from .schedulers import _PTYPE, DDPMScheduler
@@ -89,10 +89,8 @@ class TrainState:
     leaves and takes the optimizer step (None with an empty hyper: a frozen text encoder that only runs its forward).
     New tokens (new_tokens=): the text state's `tokens` is the tokens.TokenAdapter hung on its frozen store; its store of trained rows
     takes the optimizer step.
-    ControlNet (controlnet=): the UNet state's `controlnet` is the nets.ControlNet (store + config) trained on the frozen UNet; its store
-    takes the optimizer step.
-    IP-Adapter (ip_adapter=): the UNet state's `ip_adapter` is the nets.IPAdapter (store + config) trained on the frozen UNet; its store
-    takes the optimizer step."""
+    Side networks (controlnet=, ip_adapter=; nets.SIDE_NETWORKS): the UNet state's `controlnet` is the nets.ControlNet, its `ip_adapter`
+    the nets.IPAdapter (store + config) trained on the frozen UNet; that store takes the optimizer step."""
     apply_fn: Callable
     store: ParamStore
     config: dict
@@ -102,19 +100,31 @@ class TrainState:
     controlnet: Any = None
     ip_adapter: Any = None
 
+    @staticmethod
+    def stepping_of(state):
+        """(the store that takes the optimizer step, the LoRA adapter if it is the adapter's store) of a state - or of a stand-in that
+        lacks some of the fields, or of a bare store.  The one place that knows the precedence: a side network's store, the adapter's,
+        the token store, the weight store itself, or None (frozen, with nothing hung on it)."""
+        for net in nets.SIDE_NETWORKS:
+            side = getattr(state, net.name, None)
+            if side is not None:
+                return side.store, None
+        adapter, toks = getattr(state, "adapter", None), getattr(state, "tokens", None)
+        if adapter is not None:
+            return adapter.store, adapter
+        if toks is not None:
+            return toks.store, None
+        store = getattr(state, "store", state)
+        return (store if getattr(store, "trainable", True) else None), None
+
+    @property
+    def stepping(self):
+        return TrainState.stepping_of(self)
+
     @property
     def opt_store(self):
-        """The store that takes the optimizer step: the weight store itself, the adapter's store, the token store, or None (frozen,
-        neither adapter nor tokens); a ControlNet's store on the UNet state that carries one."""
-        if self.controlnet is not None:
-            return self.controlnet.store
-        if self.ip_adapter is not None:
-            return self.ip_adapter.store
-        if self.adapter is not None:
-            return self.adapter.store
-        if self.tokens is not None:
-            return self.tokens.store
-        return self.store if self.store.trainable else None
+        """The store that takes the optimizer step, or None (stepping_of)."""
+        return self.stepping[0]
 
     @property
     def step(self):
@@ -124,6 +134,13 @@ class TrainState:
     @property
     def params(self):
         return self.store
+
+
+def _stepping_stores(*states):
+    """The stores whose optimizer steps a train_step of these states takes (TrainState.opt_store): their host step counts follow the
+    replays of a captured step."""
+    stores = [TrainState.stepping_of(st)[0] for st in states]
+    return [st for st in stores if st is not None]
 
 
 def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=True, adam_to_lion_scale_factor=7,
@@ -153,55 +170,33 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
     schedules, EMA - configure the TOKEN store.  Alone, the UNet has no adapter and steps nothing; with lora=dict(unet=LoraConfig,
     text_encoder=None | "frozen") the UNet's adapter trains beside the tokens (pivotal tuning).  A text-encoder LoraConfig beside new
     tokens is refused.
-    controlnet: None, or dict(config=nets.controlnet_config(...)[, params=host tree]) - a loaded ControlNet, or one initialised from the
-    UNet (nets.controlnet_from_unet).  Both base stores are built frozen; the UNet state's `controlnet` holds the ControlNet's store, which
-    the UNet's settings above configure and which steps; the text encoder only runs its forward.  Refused beside lora= or new_tokens=, on
-    an inpainting UNet, and with a config that does not extend the UNet's.
-    ip_adapter: None, or dict(config=nets.ip_adapter_config(...)[, params=host tree]) - a loaded IP-Adapter, or one initialised from the
-    UNet (nets.ip_adapter_from_unet).  As controlnet=: both base stores are built frozen, the UNet state's `ip_adapter` holds the adapter's
-    store, which the UNet's settings configure and which steps.  Refused beside lora=, new_tokens= and controlnet=, on an inpainting UNet,
-    and with a config that does not extend the UNet's."""
+    controlnet, ip_adapter: None, or dict(config=nets.controlnet_config(...) / nets.ip_adapter_config(...)[, params=host tree]) - a loaded
+    ControlNet / IP-Adapter, or one initialised from the UNet (nets.controlnet_from_unet, nets.ip_adapter_from_unet).  Both follow the
+    rules of nets.SideNetwork: frozen base stores, the UNet state's field of that name holds the network's store, which the UNet's
+    settings above configure and which steps; refused beside lora=, new_tokens= and each other, on an inpainting UNet, and with a
+    config that does not extend the UNet's."""
     out = {"unet_state": None, "text_encoder_state": None}
-    if ip_adapter is not None:
-        if not isinstance(ip_adapter, dict) or "config" not in ip_adapter or set(ip_adapter) - {"config", "params"}:
-            raise ValueError(f"ip_adapter: None or dict(config=nets.ip_adapter_config(...)[, params=tree]), not {ip_adapter!r}")
-        if lora is not None:
-            raise ValueError("ip_adapter: an IP-Adapter beside a LoRA adapter is not supported")
-        if new_tokens is not None:
-            raise ValueError("ip_adapter: an IP-Adapter beside new tokens is not supported")
-        if controlnet is not None:
-            raise ValueError("ip_adapter: an IP-Adapter beside a ControlNet is not supported")
+    given = dict(lora=lora, new_tokens=new_tokens, controlnet=controlnet, ip_adapter=ip_adapter)
+    for net in reversed(nets.SIDE_NETWORKS):  # (ip_adapter= is validated before controlnet=)
+        side, name = given[net.name], net.name
+        if side is None:
+            continue
+        if not isinstance(side, dict) or "config" not in side or set(side) - {"config", "params"}:
+            raise ValueError(f"{name}: None or dict(config=nets.{name}_config(...)[, params=tree]), not {side!r}")
+        for others, message in net.beside:
+            if any(given[o] is not None for o in others):
+                raise ValueError(message)
         if not (train_unet and train_text_encoder):
-            raise ValueError("ip_adapter: needs both states (train_unet and train_text_encoder)")
-        icfg, ucfg = ip_adapter["config"], models["unet"]["config"]
+            raise ValueError(f"{name}: needs both states (train_unet and train_text_encoder)")
+        scfg, ucfg = side["config"], models["unet"]["config"]
         if nets.inpaint_latent_channels(ucfg) is not None:
-            raise ValueError("ip_adapter: an IP-Adapter on an inpainting UNet is not supported")
-        if "image_embed_dim" not in icfg or "num_tokens" not in icfg:
-            raise ValueError("ip_adapter: the config needs image_embed_dim and num_tokens (nets.ip_adapter_config)")
-        nets.ip_adapter_config(ucfg, icfg["image_embed_dim"], icfg["num_tokens"])
-        for k in ("block_out_channels", "down_block_types", "up_block_types", "layers_per_block", "cross_attention_dim",
-                  "attention_head_dim", "transformer_layers_per_block"):
-            if _plain(icfg.get(k)) != _plain(ucfg.get(k)):
-                raise ValueError(f"ip_adapter: the config's {k}={icfg.get(k)!r} differs from the UNet's {ucfg.get(k)!r}")
-    if controlnet is not None:
-        if not isinstance(controlnet, dict) or "config" not in controlnet or set(controlnet) - {"config", "params"}:
-            raise ValueError(f"controlnet: None or dict(config=nets.controlnet_config(...)[, params=tree]), not {controlnet!r}")
-        if lora is not None or new_tokens is not None:
-            raise ValueError("controlnet: a ControlNet beside a LoRA adapter or new tokens is not supported")
-        if not (train_unet and train_text_encoder):
-            raise ValueError("controlnet: needs both states (train_unet and train_text_encoder)")
-        ccfg, ucfg = controlnet["config"], models["unet"]["config"]
-        if nets.inpaint_latent_channels(ucfg) is not None:
-            raise ValueError("controlnet: a ControlNet on an inpainting UNet is not supported")
-        if "conditioning_embedding_out_channels" not in ccfg or "conditioning_channels" not in ccfg:
-            raise ValueError("controlnet: the config needs conditioning_embedding_out_channels and conditioning_channels "
-                             "(nets.controlnet_config)")
-        f = 2 ** (len(models["vae"]["config"]["block_out_channels"]) - 1) if "vae" in models else 8
-        nets.controlnet_config(ucfg, ccfg["conditioning_embedding_out_channels"], ccfg["conditioning_channels"], vae_downscale=f)
-        for k in ("block_out_channels", "down_block_types", "layers_per_block", "in_channels", "cross_attention_dim", "attention_head_dim",
-                  "use_linear_projection", "transformer_layers_per_block", "norm_num_groups", "addition_embed_type"):
-            if _plain(ccfg.get(k)) != _plain(ucfg.get(k)):
-                raise ValueError(f"controlnet: the config's {k}={ccfg.get(k)!r} differs from the UNet's {ucfg.get(k)!r}")
+            raise ValueError(f"{name}: {net.article} on an inpainting UNet is not supported")
+        if any(k not in scfg for k in net.adds):
+            raise ValueError(f"{name}: the config needs {' and '.join(net.adds)} (nets.{name}_config)")
+        net.config(ucfg, *(scfg[k] for k in net.adds), **net.config_kwargs(models))
+        for k in net.same:
+            if _plain(scfg.get(k)) != _plain(ucfg.get(k)):
+                raise ValueError(f"{name}: the config's {k}={scfg.get(k)!r} differs from the UNet's {ucfg.get(k)!r}")
     if new_tokens is not None:
         if not isinstance(new_tokens, tokens_mod.TokenConfig):
             raise ValueError(f"new_tokens: None or a tokens.TokenConfig, not {new_tokens!r}")
@@ -222,8 +217,8 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
             raise ValueError("lora: needs both states (train_unet and train_text_encoder); the text encoder is frozen by "
                              "text_encoder='frozen'")
         lora = {"unet": lora["unet"], "text_encoder": te_l}
-    # the base stores only run; adapters' / the tokens' / the ControlNet's own stores step
-    frozen = lora is not None or new_tokens is not None or controlnet is not None or ip_adapter is not None
+    # the base stores only run; adapters' / the tokens' / a side network's own stores step
+    frozen = any(v is not None for v in given.values())
     opt_cls, opt = optimizers.parse(optimizer)
 
     def make(spec, weights, cfg, fn, lr, quant, ema, which):
@@ -237,30 +232,18 @@ def create_lion_optimizer_states(models, train_unet=True, train_text_encoder=Tru
         store.load(weights)
         adapter = lora_mod.attach(store, lora[which], **okw) if lora is not None and lora[which] is not None else None
         toks = tokens_mod.attach(store, new_tokens, **okw) if new_tokens is not None and which == "text_encoder" else None
-        cn = None
-        if controlnet is not None and which == "unet":  # the ControlNet's own store takes the UNet's keywords and the optimizer step
-            ccfg = controlnet["config"]
-            cstore = ParamStore(nets.controlnet_spec(ccfg), device=device, **okw)
-            cw = controlnet.get("params")
-            if cw is not None and any(isinstance(v, dict) for v in cw.values()):
-                from .checkpoint import flatten_tree
-                cw = flatten_tree(cw)
-            cstore.load(cw if cw is not None else nets.controlnet_from_unet(weights, ccfg))
-            cstore.controlnet_config = ccfg  # marks the store: save_model refuses it (and its EMA view) as UNet weights
-            cn = nets.ControlNet(cstore, ccfg)
-        ipa = None
-        if ip_adapter is not None and which == "unet":  # the adapter's own store takes the UNet's keywords and the optimizer step
-            icfg = ip_adapter["config"]
-            istore = ParamStore(nets.ip_adapter_spec(icfg), device=device, **okw)
-            iw = ip_adapter.get("params")
-            if iw is not None and any(isinstance(v, dict) for v in iw.values()):
-                from .checkpoint import flatten_tree
-                iw = flatten_tree(iw)
-            istore.load(iw if iw is not None else nets.ip_adapter_from_unet(weights, icfg))
-            istore.ip_adapter_config = icfg  # marks the store: save_model refuses it (and its EMA view) as UNet weights
-            ipa = nets.IPAdapter(istore, icfg)
-        trained = not frozen or adapter is not None or toks is not None or cn is not None or ipa is not None
-        state = TrainState(fn, store, cfg, hyper if trained else {}, adapter, toks, cn, ipa)
+        sides = {}
+        for net in nets.SIDE_NETWORKS:  # a side network's own store takes the UNet's keywords and the optimizer step
+            side = given[net.name]
+            if side is not None and which == "unet":
+                sstore = ParamStore(net.spec(side["config"]), device=device, **okw)
+                tree = side.get("params")
+                sstore.load(flatten_if_nested(tree) if tree is not None else net.from_unet(weights, side["config"]))
+                setattr(sstore, net.marker, side["config"])  # marks the store: save_model refuses it (and its EMA view) as UNet weights
+                sides[net.name] = net.wrapper(sstore, side["config"])
+        state = TrainState(fn, store, cfg, hyper, adapter, toks, **sides)
+        if state.opt_store is None:  # a frozen model with nothing hung on it only runs its forward
+            state.hyper = {}
         if sched is not None and state.opt_store is not None:
             state.opt_store.set_schedule(lr=sched[0], ema=sched[1])
         return state
@@ -299,10 +282,9 @@ def on_device_model_training_state(training_config: TrainingConfig, models=None,
     new_tokens: create_lion_optimizer_states' - a tokens.TokenConfig trains placeholder-token embeddings on the frozen text encoder, alone or
     beside a UNet LoRA.  The text state's `tokens` is the TokenAdapter and its EMA view wraps the token store; a UNet without an adapter
     has no EMA view (None).
-    controlnet: create_lion_optimizer_states' - dict(config=[, params=]) trains a ControlNet on the frozen UNet: unet_state.controlnet
-    holds its store and config, the UNet EMA view wraps that store, the text encoder has none.
-    ip_adapter: create_lion_optimizer_states' - dict(config=[, params=]) trains an IP-Adapter on the frozen UNet the same way:
-    unet_state.ip_adapter holds its store and config; batches carry image_embeds."""
+    controlnet, ip_adapter: create_lion_optimizer_states' - dict(config=[, params=]) trains a ControlNet / an IP-Adapter on the frozen UNet
+    (nets.SideNetwork): unet_state.controlnet / unet_state.ip_adapter holds its store and config, the UNet EMA view wraps that store, the
+    text encoder has none; batches carry conditioning_pixel_values / image_embeds."""
     _lib.require_device()
     if models is None:
         models = load_models(training_config)
@@ -409,18 +391,12 @@ def encode_latent_moments(frozen_vae, pixel_values):
     vae_store, vae_cfg = frozen_vae.params, frozen_vae.call
     dev = vae_store.device
     B, C_in, H, W = pixel_values.shape
-    own_arena = not ops.gn_arena_active(dev)
-    if own_arena:
-        ops.gn_arena_begin(dev)
-    try:
+    with ops.gn_arena(dev):
         pix = torch.empty(B, H, W, 8, dtype=torch.bfloat16, device=dev)
         _lib.call("sdt_nchw_f32_to_nhwc_bf16", pixel_values.data_ptr(), pix.data_ptr(), B, C_in, H, W, 8,
                   torch.cuda.current_stream().cuda_stream)
         with trace.phase("vae_encode"):
             return nets.vae_encode_moments(vae_store, vae_cfg, pix)
-    finally:
-        if own_arena:
-            ops.gn_arena_end(dev)
 
 
 def encode_inpaint_moments(frozen_vae, pixel_values, inpaint_mask):
@@ -434,10 +410,7 @@ def encode_inpaint_moments(frozen_vae, pixel_values, inpaint_mask):
     f = 2 ** (len(vae_cfg["block_out_channels"]) - 1)
     if H % f or W % f:
         raise ValueError(f"pixel_values {tuple(pixel_values.shape)}: height and width must be multiples of the VAE's downscale {f}")
-    own_arena = not ops.gn_arena_active(dev)
-    if own_arena:
-        ops.gn_arena_begin(dev)
-    try:
+    with ops.gn_arena(dev):
         pix = torch.empty(2 * B, H, W, 8, dtype=torch.bfloat16, device=dev)
         lmask = torch.empty(B, H // f, W // f, dtype=torch.float32, device=dev)
         _lib.call("sdt_inpaint_mask_pixels", pixel_values.data_ptr(), inpaint_mask.data_ptr(), pix.data_ptr(), lmask.data_ptr(), B, C_in,
@@ -445,9 +418,6 @@ def encode_inpaint_moments(frozen_vae, pixel_values, inpaint_mask):
         with trace.phase("vae_encode"):
             both = nets.vae_encode_moments(vae_store, vae_cfg, pix)
         return both[:B], both[B:], lmask
-    finally:
-        if own_arena:
-            ops.gn_arena_end(dev)
 
 
 def step_key(batch, downscale=8):
@@ -460,10 +430,48 @@ def step_key(batch, downscale=8):
 
 
 LOSS_KEYS = ("loss_mask", "loss_weight")  # the optional batch entries that select the masked / weighted loss kernels
+INPAINT_KEYS = ("inpaint_mask",)  # the batch entry that selects the inpainting front of the step (include/sdt.h "INPAINTING")
+CONTROL_KEYS = (nets.CONTROLNET.batch_key,)  # "conditioning_pixel_values": what a ControlNet state's step reads (diffusers' name)
+IP_KEYS = (nets.IP_ADAPTER.batch_key,)  # "image_embeds": what an IP-Adapter state's step reads (the published training script's name)
+# every entry with one row per sample besides the image itself: what a micro-batch slices (input_ids hold k rows per sample)
+PER_SAMPLE_KEYS = ("text_embeds", "time_ids", "masked_latent_moments") + LOSS_KEYS + INPAINT_KEYS + CONTROL_KEYS + IP_KEYS
+# the keys whose presence selects launches, in the order a captured step reports a batch that adds or drops one (_GraphedStep)
+LAUNCH_KEYS = LOSS_KEYS + INPAINT_KEYS + CONTROL_KEYS + IP_KEYS
+_DTYPE_NAMES = {torch.float32: "float32", torch.bfloat16: "bfloat16"}
 
 
 def _on_device(t, device):
     return t.device.type == device.type and (device.index is None or t.device.index == device.index)
+
+
+def _check_entry(name, t, dtypes, want, device, tail, plural=False):
+    """ValueError unless batch entry `name` is a contiguous tensor of one of `dtypes` and shape `want` on the step's device, reported in
+    that order: type / dtype, device, shape, layout.  tail: how the shape message ends (what the shape follows from); plural: the
+    name is one ("image_embeds live on")."""
+    if not torch.is_tensor(t) or t.dtype not in dtypes:
+        raise ValueError(f"{name} must be a {' or '.join(_DTYPE_NAMES[d] for d in dtypes)} tensor, not {getattr(t, 'dtype', type(t))}")
+    if not _on_device(t, device):
+        raise ValueError(f"{name} {'live' if plural else 'lives'} on {t.device}, the step runs on {device}")
+    if tuple(t.shape) != tuple(want):
+        raise ValueError(f"{name} {'have' if plural else 'has'} shape {tuple(t.shape)}{tail}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+
+
+def _image_grid(batch, channels=(), scale=1):
+    """(want, where) of an entry at the grid of the batch's image (which _check_batch has validated): pixel size beside pixel_values,
+    latent size - times `scale`, a hint's downscale - beside latent_moments; (B, *channels, height, width) and how to say it."""
+    if "latent_moments" in batch:
+        m = batch["latent_moments"]
+        return (int(m.shape[0]), *channels, int(m.shape[1]) * scale, int(m.shape[2]) * scale), "latent_moments (B,h,w,2L)"
+    px = batch["pixel_values"]
+    return (int(px.shape[0]), *channels, int(px.shape[2]), int(px.shape[3])), "pixel_values (B,3,H,W)"
+
+
+def _mask_grid(batch):
+    """_image_grid for a (B, height, width) mask, with the size named."""
+    want, where = _image_grid(batch)
+    return want, where + (": latent size (B,h,w)" if "latent_moments" in batch else ": pixel size (B,H,W)")
 
 
 def _check_loss_entries(batch, device, masked_loss_floor, normalize_masked_area):
@@ -474,33 +482,12 @@ def _check_loss_entries(batch, device, masked_loss_floor, normalize_masked_area)
     mask, weight = batch.get("loss_mask"), batch.get("loss_weight")
     if normalize_masked_area and mask is None:
         raise ValueError("normalize_masked_area needs a loss_mask in the batch")
-    image = batch["latent_moments"] if "latent_moments" in batch else batch["pixel_values"]
-    B = int(image.shape[0])
     if mask is not None:
-        if "latent_moments" in batch:
-            want, where = (B, int(image.shape[1]), int(image.shape[2])), "latent_moments (B,h,w,2L): latent size (B,h,w)"
-        else:
-            want, where = (B, int(image.shape[2]), int(image.shape[3])), "pixel_values (B,3,H,W): pixel size (B,H,W)"
-        if not torch.is_tensor(mask) or mask.dtype != torch.float32:
-            raise ValueError(f"loss_mask must be a float32 tensor, not {getattr(mask, 'dtype', type(mask))}")
-        if not _on_device(mask, device):
-            raise ValueError(f"loss_mask lives on {mask.device}, the step runs on {device}")
-        if tuple(mask.shape) != want:
-            raise ValueError(f"loss_mask has shape {tuple(mask.shape)}; beside {where} = {want}")
-        if not mask.is_contiguous():
-            raise ValueError("loss_mask must be contiguous")
+        want, where = _mask_grid(batch)
+        _check_entry("loss_mask", mask, (torch.float32,), want, device, f"; beside {where} = {want}")
     if weight is not None:
-        if not torch.is_tensor(weight) or weight.dtype != torch.float32:
-            raise ValueError(f"loss_weight must be a float32 tensor, not {getattr(weight, 'dtype', type(weight))}")
-        if not _on_device(weight, device):
-            raise ValueError(f"loss_weight lives on {weight.device}, the step runs on {device}")
-        if tuple(weight.shape) != (B,):
-            raise ValueError(f"loss_weight has shape {tuple(weight.shape)}: one weight per sample, ({B},)")
-        if not weight.is_contiguous():
-            raise ValueError("loss_weight must be contiguous")
-
-
-INPAINT_KEYS = ("inpaint_mask",)  # the batch entry that selects the inpainting front of the step (include/sdt.h "INPAINTING")
+        B = int(batch["latent_moments" if "latent_moments" in batch else "pixel_values"].shape[0])
+        _check_entry("loss_weight", weight, (torch.float32,), (B,), device, f": one weight per sample, ({B},)")
 
 
 def _check_inpaint_entries(batch, unet_cfg, device):
@@ -515,38 +502,20 @@ def _check_inpaint_entries(batch, unet_cfg, device):
         return
     if mask is None:
         raise ValueError(f"an inpainting UNet (in_channels={unet_cfg['in_channels']} = 2 * {L} + 1) needs inpaint_mask in the batch")
-    cached = "latent_moments" in batch
-    image = batch["latent_moments"] if cached else batch["pixel_values"]
-    B = int(image.shape[0])
-    if cached:
-        want, where = (B, int(image.shape[1]), int(image.shape[2])), "latent_moments (B,h,w,2L): latent size (B,h,w)"
-    else:
-        want, where = (B, int(image.shape[2]), int(image.shape[3])), "pixel_values (B,3,H,W): pixel size (B,H,W)"
-    if not torch.is_tensor(mask) or mask.dtype != torch.float32:
-        raise ValueError(f"inpaint_mask must be a float32 tensor, not {getattr(mask, 'dtype', type(mask))}")
-    if not _on_device(mask, device):
-        raise ValueError(f"inpaint_mask lives on {mask.device}, the step runs on {device}")
-    if tuple(mask.shape) != want:
-        raise ValueError(f"inpaint_mask has shape {tuple(mask.shape)}; beside {where} = {want}")
-    if not mask.is_contiguous():
-        raise ValueError("inpaint_mask must be contiguous")
-    if cached:
+    want, where = _mask_grid(batch)
+    _check_entry("inpaint_mask", mask, (torch.float32,), want, device, f"; beside {where} = {want}")
+    if "latent_moments" in batch:
         if mm is None:
             raise ValueError("a cached batch for an inpainting UNet needs masked_latent_moments (bf16 (B,h,w,2L)) beside latent_moments")
-        if not torch.is_tensor(mm) or mm.dtype != torch.bfloat16:
-            raise ValueError(f"masked_latent_moments must be a bfloat16 tensor, not {getattr(mm, 'dtype', type(mm))}")
-        if not _on_device(mm, device):
-            raise ValueError(f"masked_latent_moments live on {mm.device}, the step runs on {device}")
-        if tuple(mm.shape) != tuple(image.shape):
-            raise ValueError(f"masked_latent_moments have shape {tuple(mm.shape)}; latent_moments {tuple(image.shape)}")
-        if not mm.is_contiguous():
-            raise ValueError("masked_latent_moments must be contiguous")
+        shape = tuple(batch["latent_moments"].shape)
+        _check_entry("masked_latent_moments", mm, (torch.bfloat16,), shape, device, f"; latent_moments {shape}", plural=True)
 
 
-CONTROL_KEYS = ("conditioning_pixel_values",)  # the batch entry a ControlNet state's step reads (diffusers' name)
-
-
-IP_KEYS = ("image_embeds",)  # the batch entry an IP-Adapter state's step reads (the published training script's name)
+def _refuse_without_state(net, entry):
+    """ValueError for a side network's batch entry in a batch whose UNet state carries no such network."""
+    if entry is not None:
+        raise ValueError(f"{net.batch_key} need {net.article} state (on_device_model_training_state({net.name}=)); this UNet state carries "
+                         "none")
 
 
 def _check_ip_entries(batch, ip_adapter, device, rows):
@@ -554,22 +523,12 @@ def _check_ip_entries(batch, ip_adapter, device, rows):
     with E = the config's image_embed_dim, contiguous on the step's device; a state without an IP-Adapter refuses it."""
     emb = batch.get("image_embeds")
     if ip_adapter is None:
-        if emb is not None:
-            raise ValueError("image_embeds need an IP-Adapter state (on_device_model_training_state(ip_adapter=)); this UNet state "
-                             "carries none")
-        return
+        return _refuse_without_state(nets.IP_ADAPTER, emb)
     E = int(ip_adapter.config["image_embed_dim"])
     if emb is None:
         raise ValueError(f"an IP-Adapter state's batch needs image_embeds (f32 or bf16 (B, {E}): the image encoder's pooled embedding)")
-    if not torch.is_tensor(emb) or emb.dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError(f"image_embeds must be a float32 or bfloat16 tensor, not {getattr(emb, 'dtype', type(emb))}")
-    if not _on_device(emb, device):
-        raise ValueError(f"image_embeds live on {emb.device}, the step runs on {device}")
-    if tuple(emb.shape) != (rows, E):
-        raise ValueError(f"image_embeds have shape {tuple(emb.shape)}; the batch has {rows} samples and the adapter's image_embed_dim is "
-                         f"{E}: ({rows}, {E})")
-    if not emb.is_contiguous():
-        raise ValueError("image_embeds must be contiguous")
+    _check_entry("image_embeds", emb, (torch.float32, torch.bfloat16), (rows, E), device,
+                 f"; the batch has {rows} samples and the adapter's image_embed_dim is {E}: ({rows}, {E})", plural=True)
 
 
 def _check_control_entries(batch, controlnet, device):
@@ -578,28 +537,14 @@ def _check_control_entries(batch, controlnet, device):
     f times the latent size of latent_moments - contiguous on the step's device; a state without a ControlNet refuses it."""
     cond = batch.get("conditioning_pixel_values")
     if controlnet is None:
-        if cond is not None:
-            raise ValueError("conditioning_pixel_values need a ControlNet state (on_device_model_training_state(controlnet=)); this "
-                             "UNet state carries none")
-        return
+        return _refuse_without_state(nets.CONTROLNET, cond)
     if cond is None:
         raise ValueError("a ControlNet state's batch needs conditioning_pixel_values (f32 (B, conditioning_channels, H, W) in [0, 1])")
-    cc = int(controlnet.config["conditioning_channels"])
+    f = 2 ** (len(controlnet.config["conditioning_embedding_out_channels"]) - 1)
+    want, where = _image_grid(batch, (int(controlnet.config["conditioning_channels"]),), f)
     if "latent_moments" in batch:
-        m = batch["latent_moments"]
-        f = 2 ** (len(controlnet.config["conditioning_embedding_out_channels"]) - 1)
-        want, where = (int(m.shape[0]), cc, int(m.shape[1]) * f, int(m.shape[2]) * f), f"latent_moments (B,h,w,2L) and the downscale {f}"
-    else:
-        px = batch["pixel_values"]
-        want, where = (int(px.shape[0]), cc, int(px.shape[2]), int(px.shape[3])), "pixel_values (B,3,H,W)"
-    if not torch.is_tensor(cond) or cond.dtype != torch.float32:
-        raise ValueError(f"conditioning_pixel_values must be a float32 tensor, not {getattr(cond, 'dtype', type(cond))}")
-    if not _on_device(cond, device):
-        raise ValueError(f"conditioning_pixel_values live on {cond.device}, the step runs on {device}")
-    if tuple(cond.shape) != want:
-        raise ValueError(f"conditioning_pixel_values have shape {tuple(cond.shape)}; beside {where}: {want}")
-    if not cond.is_contiguous():
-        raise ValueError("conditioning_pixel_values must be contiguous")
+        where += f" and the downscale {f}"
+    _check_entry("conditioning_pixel_values", cond, (torch.float32,), want, device, f"; beside {where}: {want}", plural=True)
 
 
 def _check_batch(batch, unet_cfg, frozen_vae_state, device, masked_loss_floor=0.0, normalize_masked_area=False):
@@ -621,7 +566,7 @@ def _check_batch(batch, unet_cfg, frozen_vae_state, device, masked_loss_floor=0.
     if not torch.is_tensor(m) or m.dtype != torch.bfloat16 or m.dim() != 4:
         raise ValueError(f"latent_moments must be a bfloat16 (B,h,w,2L) tensor, not {getattr(m, 'dtype', type(m))} "
                          f"{tuple(getattr(m, 'shape', ()))}")
-    if m.device.type != device.type or (device.index is not None and m.device.index != device.index):
+    if not _on_device(m, device):
         raise ValueError(f"latent_moments live on {m.device}, the step runs on {device}")
     if m.shape[3] % 2:
         raise ValueError(f"latent_moments' last dimension holds mean | log-variance and must be even, not {m.shape[3]}")
@@ -715,6 +660,9 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     alone.  aux= taps gain "control_hint", "control_down" (list) and "control_mid".  ValueError for a batch without the key or with a
     key of another dtype, device, shape or layout, the key on a state without a ControlNet, a reducer, a LoRA adapter or new tokens
     beside the ControlNet, an inpainting UNet, and a trainable base store.
+    IP-Adapter (TrainState.ip_adapter on the UNet state; nets.SideNetwork): as the ControlNet, with "image_embeds", f32 or bf16 (B,
+    image_embed_dim) - nets.ip_adapter_tokens runs on the adapter's (trained) store and every attn2 of the frozen UNet adds its image
+    term at unit scale (unet_forward(ip=)); aux= taps gain "ip_tokens".  The same ValueErrors, and one for a ControlNet beside it.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
     _check_loss_type(loss_type, huber_c, huber_schedule)
     text_time = unet_state.config.get("addition_embed_type") == "text_time"
@@ -735,36 +683,28 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     elif getattr(unet_state, "tokens", None) is not None or getattr(ts, "tokens", None) is not None or getattr(us, "tokens", None) is not None:
         raise ValueError("new tokens: the text-encoder state must carry the TokenAdapter its store carries (TrainState.tokens; "
                          "create_lion_optimizer_states(new_tokens=) builds both)")
-    cn = getattr(unet_state, "controlnet", None)
-    if cn is not None:
+    sides = {}  # the side networks the UNet state carries (nets.SIDE_NETWORKS): past the refusals, one at the most
+    for i, net in enumerate(nets.SIDE_NETWORKS):
+        side = sides[net.name] = getattr(unet_state, net.name, None)
+        if side is None:
+            if getattr(text_encoder_state, net.name, None) is not None:
+                raise ValueError(f"{net.label}: the UNet state carries the {net.label}, not the text-encoder state")
+            continue
         if reducer is not None:
-            raise ValueError("ControlNet: data-parallel training is not supported - the GradReducer would have to be built over the "
-                             "ControlNet's store (TrainState.controlnet.store)")
+            raise ValueError(f"{net.label}: data-parallel training is not supported - the GradReducer would have to be built over "
+                             f"{net.the}'s store (TrainState.{net.name}.store)")
         if adapters or tk is not None or getattr(us, "adapter", None) is not None or getattr(ts, "tokens", None) is not None:
-            raise ValueError("ControlNet: a LoRA adapter or new tokens beside a ControlNet are not supported")
+            raise ValueError(f"{net.label}: a LoRA adapter or new tokens beside {net.article} are not supported")
+        for other in nets.SIDE_NETWORKS[:i]:
+            if sides[other.name] is not None:
+                raise ValueError(f"{net.label}: {other.article} beside {net.article} is not supported")
         if nets.inpaint_latent_channels(unet_state.config) is not None:
-            raise ValueError("ControlNet: an inpainting UNet is not supported")
+            raise ValueError(f"{net.label}: an inpainting UNet is not supported")
         if us.trainable or ts.trainable:
-            raise ValueError("ControlNet: a trainable base store is not supported - the UNet and the text encoder are frozen and only "
-                             "the ControlNet's store steps")
-    elif getattr(text_encoder_state, "controlnet", None) is not None:
-        raise ValueError("ControlNet: the UNet state carries the ControlNet, not the text-encoder state")
-    ipa = getattr(unet_state, "ip_adapter", None)
-    if ipa is not None:
-        if reducer is not None:
-            raise ValueError("IP-Adapter: data-parallel training is not supported - the GradReducer would have to be built over the "
-                             "adapter's store (TrainState.ip_adapter.store)")
-        if adapters or tk is not None or getattr(us, "adapter", None) is not None or getattr(ts, "tokens", None) is not None:
-            raise ValueError("IP-Adapter: a LoRA adapter or new tokens beside an IP-Adapter are not supported")
-        if cn is not None:
-            raise ValueError("IP-Adapter: a ControlNet beside an IP-Adapter is not supported")
-        if nets.inpaint_latent_channels(unet_state.config) is not None:
-            raise ValueError("IP-Adapter: an inpainting UNet is not supported")
-        if us.trainable or ts.trainable:
-            raise ValueError("IP-Adapter: a trainable base store is not supported - the UNet and the text encoder are frozen and only "
-                             "the adapter's store steps")
-    elif getattr(text_encoder_state, "ip_adapter", None) is not None:
-        raise ValueError("IP-Adapter: the UNet state carries the IP-Adapter, not the text-encoder state")
+            raise ValueError(f"{net.label}: a trainable base store is not supported - the UNet and the text encoder are frozen and only "
+                             f"{net.the}'s store steps")
+    cn, ipa = sides["controlnet"], sides["ip_adapter"]
+    side = cn or ipa  # the side network whose store steps, or None
     lora = bool(adapters) or tk is not None  # the frozen-base step: adapters' and / or the tokens' own stores are the ones that step
     if adapters:
         if us.trainable or ts.trainable or unet_state.adapter is None:
@@ -773,12 +713,9 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         if reducer is not None:
             raise ValueError("LoRA: data-parallel training of adapter states is not supported yet - the follow-up is to build the "
                              "GradReducer over the adapter stores (TrainState.adapter.store) instead of the frozen weight stores")
-    # the stores that are zeroed, accumulated into and stepped: the weight stores themselves, or the adapters' / the tokens' own
-    opt_stores = ([a.store for a in adapters] + ([tk.store] if tk is not None else [])) if lora else [us, ts]
-    if cn is not None:
-        opt_stores = [cn.store]
-    if ipa is not None:
-        opt_stores = [ipa.store]
+    # the stores that are zeroed, accumulated into and stepped: the weight stores themselves, or the adapters' / the tokens' / the side
+    # network's own
+    opt_stores = _stepping_stores(unet_state, text_encoder_state)
     sched, sched_state = frozen_noise_scheduler_state.call, frozen_noise_scheduler_state.params
     dev = us.device
     cached = _check_batch(batch, unet_state.config, frozen_vae_state, dev, masked_loss_floor, normalize_masked_area)
@@ -812,7 +749,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         else:
             sl = slice(k * B, (k + 1) * B)
             kc = batch["input_ids"].shape[0] // N  # text-encoder rows per sample
-            mb = {n: v[sl] for n, v in batch.items() if n in (image_key, "text_embeds", "time_ids", "masked_latent_moments") + LOSS_KEYS + INPAINT_KEYS + CONTROL_KEYS + IP_KEYS}
+            mb = {n: v[sl] for n, v in batch.items() if n == image_key or n in PER_SAMPLE_KEYS}
             mb["input_ids"] = batch["input_ids"][k * B * kc: (k + 1) * B * kc]
             rnd = {n: v[sl] for n, v in rand.items()}
 
@@ -849,8 +786,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                     ad.merge("master")
                 if tk is not None:
                     tk.select("master")  # (no launch: the embedding reads the trained rows where they are)
-            elif k == 0 and (cn is not None or ipa is not None):
-                (cn or ipa).store.prepare()  # (the frozen mirrors stay as the load left them)
+            elif k == 0 and side is not None:
+                side.store.prepare()  # (the frozen mirrors stay as the load left them)
             elif k == 0:
                 us.prepare()
                 ts.prepare()
@@ -1028,7 +965,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     if K == 1:
         # one process: the norm clip_by_global_norm needs is that of the gradients as the weight-gradient kernels write them - they leave
         # its partial sums behind (ops.sq_begin / sq_end), and the 4-byte-per-parameter pass over the finished buffer is not needed
-        loss, sq_u, sq_t, lps = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora and cn is None and ipa is None)
+        loss, sq_u, sq_t, lps = forward_backward(0, reducer is None and _FUSED_NORM and dev.type == "cuda" and not lora and side is None)
         grad_source = "grad"
         # data-parallel mean of the gradients (implicit all-reduce under GSPMD in the reference)
         if reducer is not None:
@@ -1087,13 +1024,6 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
 _CAPTURE_MODE = "thread_local"
 
 
-def _stepping_stores(*states):
-    """The stores whose optimizer steps a train_step of these states takes (TrainState.opt_store): their host step counts follow the
-    replays of a captured step."""
-    stores = [getattr(st, "opt_store", st.store) for st in states]
-    return [st for st in stores if st is not None]
-
-
 class _GraphedStep:
     """One resolution's train_step, captured once into a HIP graph and replayed (the MI355X counterpart of the
     reference jit-compiling train_step per bucket shape, training_utils.py:765-983).
@@ -1108,20 +1038,22 @@ class _GraphedStep:
 
     def __init__(self, fn, warmup=2, reducer=None):
         self.fn, self.warmup, self.calls = fn, warmup, 0
-        self.graph = self.static = self.static_rand = self.out = self.sig = self.loss_keys = self.inpaint_keys = self.control_keys = self.ip_keys = None
+        self.graph = self.static = self.static_rand = self.out = self.sig = self.held = None
         # multi-rank: graph A (forward + backward) | eager bucketed all-reduce behind per-bucket events | graph B (optimizer)
         self.reducer = reducer if (reducer is not None and reducer.active) else None
         self.graph_b = self.plan = None
         self.disabled = False
 
+    @property
+    def loss_keys(self):
+        """Which of LOSS_KEYS the captured batch held, as (mask, weight) flags; None before the capture."""
+        return None if self.held is None else tuple(k in self.held for k in LOSS_KEYS)
+
     def _capture(self, us, ts, ue, te, batch, rng, vae, sched, rand):
         self.static = {k: v.clone() for k, v in batch.items() if torch.is_tensor(v)}
         self.static_rand = None if rand is None else {k: v.clone() for k, v in rand.items()}
         self.sig = self._sig(us, ts, ue, te, rng, vae, sched, rand)
-        self.loss_keys = tuple(k in batch for k in LOSS_KEYS)
-        self.inpaint_keys = tuple(k in batch for k in INPAINT_KEYS)
-        self.control_keys = tuple(k in batch for k in CONTROL_KEYS)
-        self.ip_keys = tuple(k in batch for k in IP_KEYS)
+        self.held = tuple(k for k in LAUNCH_KEYS if k in batch)  # the launch-selecting keys of the captured batch
         torch.cuda.synchronize()
         g = torch.cuda.CUDAGraph()
         if rng is not None and hasattr(g, "register_generator_state"):
@@ -1205,19 +1137,14 @@ class _GraphedStep:
                 return self.fn(us, ts, ue, te, batch, rng, vae, sched, rand=rand)
         if self.sig != self._sig(us, ts, ue, te, rng, vae, sched, rand):
             raise ValueError("a captured train_step is bound to the state objects (and rand= keys) it was captured with")
-        if self.loss_keys != tuple(k in batch for k in LOSS_KEYS):
-            had = [k for k, on in zip(LOSS_KEYS, self.loss_keys) if on] or "neither"
-            raise ValueError(f"this step was captured with {had} of {list(LOSS_KEYS)} in its batch and replays those launches: a batch that "
-                             "adds or drops one of them needs a step table of its own")
-        if self.inpaint_keys != tuple(k in batch for k in INPAINT_KEYS):
-            raise ValueError(f"this step was captured {'with' if self.inpaint_keys[0] else 'without'} inpaint_mask in its batch and replays "
-                             "those launches: a batch that adds or drops it needs a step table of its own")
-        if self.control_keys != tuple(k in batch for k in CONTROL_KEYS):
-            raise ValueError(f"this step was captured {'with' if self.control_keys[0] else 'without'} conditioning_pixel_values in its "
-                             "batch and replays those launches: a batch that adds or drops it needs a step table of its own")
-        if self.ip_keys != tuple(k in batch for k in IP_KEYS):
-            raise ValueError(f"this step was captured {'with' if self.ip_keys[0] else 'without'} image_embeds in its batch and replays "
-                             "those launches: a batch that adds or drops it needs a step table of its own")
+        if self.held != tuple(k for k in LAUNCH_KEYS if k in batch):
+            key = next(k for k in LAUNCH_KEYS if (k in batch) != (k in self.held))  # the first one that was added or dropped
+            if key in LOSS_KEYS:
+                had = [k for k in LOSS_KEYS if k in self.held] or "neither"
+                raise ValueError(f"this step was captured with {had} of {list(LOSS_KEYS)} in its batch and replays those launches: a batch "
+                                 "that adds or drops one of them needs a step table of its own")
+            raise ValueError(f"this step was captured {'with' if key in self.held else 'without'} {key} in its batch and replays those "
+                             "launches: a batch that adds or drops it needs a step table of its own")
         for k, v in self.static.items():
             v.copy_(batch[k], non_blocking=True)
         if rand is not None:
