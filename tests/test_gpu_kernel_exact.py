@@ -16,6 +16,7 @@ import pytest
 import torch
 
 from tests import kernel_checks as kc
+from tests import op_checks as oc
 from tests.kernel_checks import BF, Guarded, assert_equal_bits, exact_ints
 
 pytestmark = pytest.mark.gpu
@@ -764,6 +765,35 @@ def test_geglu_gate_over_every_bf16_value(dev):
         _act_assert(f"geglu backward, d value (dout {dov})", g, dh[:F], y64 * dov, abs(dov))
         _act_assert(f"geglu backward, d gate (value {av}, dout {dov})", g, dh[F:], d64 * (av * dov), abs(av * dov))
         Hg.check("h")
+
+
+@pytest.mark.parametrize("F,K", oc.FF_GEGLU_PAIRS)
+def test_ff_geglu_fused_epilogue_at_ragged_m(dev, F, K):
+    """sdt_ff_geglu_fwd where its last row tile is ragged: the smallest M the fused kernel serves, the smallest served M with
+    M % 128 == 1 and with M % 128 == 127 (asked of sdt_ff_geglu_supported; the CPU proof pins them).  Every M the feed-forward test
+    of tests/test_gpu_kernels.py hands this kernel is a multiple of 128.  x sits in an arena whose rows >= M are NaN, h and out in
+    guarded arenas (the ABI has no pitch for them: pad 0): h must hold the integer GEMM bit for bit, out what sdt_geglu_fwd writes
+    from that h (pinned over every bf16 gate by test_geglu_gate_over_every_bf16_value), and every guard must be intact."""
+    from stable_diffusion_training_amd import _lib
+    lib = _lib.load()
+    Ms = oc.ff_geglu_served(lib.sdt_ff_geglu_supported, F, K)
+    assert Ms == oc.FF_GEGLU_M[(F, K)], f"the planner serves other shapes now: {Ms}"
+    w = exact_ints((K, 2 * F), -kc.GEMM_RANGE, kc.GEMM_RANGE, 7 + F)
+    bias = exact_ints((2 * F,), -kc.EPI_RANGE, kc.EPI_RANGE, 8 + F, dtype=torch.float32)
+    Wg = Guarded(K, 2 * F, BF, dev, data=w, pad=0)
+    Bg = Guarded(1, 2 * F, torch.float32, dev, data=bias, pad=0)
+    for M in sorted(set(Ms)):
+        x = exact_ints((M, K), -kc.GEMM_RANGE, kc.GEMM_RANGE, M)
+        X = Guarded(M, K, BF, dev, data=x, pad=0)
+        H, O, O2 = Guarded(M, 2 * F, BF, dev, pad=0), Guarded(M, F, BF, dev, pad=0), Guarded(M, F, BF, dev, pad=0)
+        _lib.call("sdt_ff_geglu_fwd", X.ptr, Wg.ptr, Bg.ptr, H.ptr, O.ptr, M, F, K, _stream())
+        torch.cuda.synchronize()
+        assert_equal_bits(H.t, kc.expect_gemm_nt(x.to(dev), w.to(dev), bias.to(dev)), f"M {M}: h", tile=(128, 128))
+        _lib.call("sdt_geglu_fwd", H.ptr, O2.ptr, M, F, _stream())
+        torch.cuda.synchronize()
+        assert_equal_bits(O.t, O2.t.clone(), f"M {M}: out against sdt_geglu_fwd of the same h", tile=(128, 64))
+        for what, g in (("h", H), ("out", O), ("separate out", O2), ("x", X), ("W1", Wg), ("bias", Bg)):
+            g.check(f"M {M}: {what}")
 
 
 # ================================================================================================ tail sizes, zero sizes
