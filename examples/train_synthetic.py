@@ -35,7 +35,11 @@ from batches with a conditioning image per sample; the UNet's rate / optimizer /
 --ip-adapter [DIR] ("ip_adapter": true or a directory): trains an IP-Adapter on the frozen UNet and text encoder - loaded from DIR
 (checkpoint.load_ip_adapter) or initialised from the UNet (nets.ip_adapter_from_unet; "ip_adapter_embed_dim", "ip_adapter_tokens" and
 "ip_adapter_drop_rate" set the embedding width, the token count and the loader's image-prompt dropout).  The loader adds image_embeds,
-the adapter is written to <model>-ip-adapter (and -ip-adapter-EMA), and --cache-latents keeps the embeddings beside the moments."""
+the adapter is written to <model>-ip-adapter (and -ip-adapter-EMA), and --cache-latents keeps the embeddings beside the moments.
+--dpo BETA ("dpo_beta"; needs --lora RANK, with or without --dora): Diffusion-DPO preference training - the loader emits interleaved
+(preferred, rejected) pairs under one caption (DataLoader(preference_pairs=True)), every step runs the frozen base as the reference
+model beside the adapted one (train_step dpo_beta=; diffusers trains SD1.5 / SDXL with 5000), and the log shows the loss and
+implicit_acc, the share of pairs the adapter ranks like the data."""
 import argparse
 import json
 import os
@@ -149,6 +153,12 @@ def main(config_dict, models=None, tokenizer=None, log=print):
     if config_dict.get("loss_type", "l2") != "l2":
         loss_overrides.update(loss_type=config_dict["loss_type"], huber_c=float(config_dict.get("huber_c", 0.1)),
                               huber_schedule=config_dict.get("huber_schedule", "snr"))
+    dpo_beta = config_dict.get("dpo_beta")
+    if dpo_beta is not None:  # Diffusion-DPO: pairs from the loader, the frozen base under the adapter as the reference
+        if not config_dict.get("lora_rank"):
+            raise ValueError("dpo_beta: preference training needs a LoRA / DoRA adapter - the frozen base is the reference model (--lora RANK)")
+        loss_overrides["dpo_beta"] = float(dpo_beta)
+        loss_loader_kw["preference_pairs"] = True
     token_cfg = None
     if config_dict.get("new_tokens"):  # textual inversion: placeholder j is id vocab + j of every tower
         if world > 1:
@@ -247,7 +257,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
                           config_dict["test_save_path"])
             delete_file_or_folder(config_dict["test_save_path"])
         start = time.time()
-        train_metrics = []
+        train_metrics, dpo_acc = [], []
         for count in range(int(dataloader._bulk_batch_count + dataloader._first_batch_count)):
             current_batch = batches.grab_next_batch()
             if current_batch == "end_of_batch":
@@ -264,17 +274,22 @@ def main(config_dict, models=None, tokenizer=None, log=print):
                     unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, current_batch, train_rngs,
                     frozen_vae, frozen_schedulers)
             train_metrics.append(train_metric["loss"])  # device scalars: reading them below is the only synchronisation
+            if dpo_beta is not None:
+                dpo_acc.append(train_metric["implicit_acc"])
             if count % config_dict["loss_logging_interval"] == 0:
                 loss = float(sum(train_metrics) / len(train_metrics))
                 losses.append(loss)
                 elapsed = round(time.time() - start, 4)
                 start = time.time()
                 train_metrics = []
+                acc = ""
+                if dpo_acc:
+                    acc, dpo_acc = f", implicit_acc {float(sum(dpo_acc) / len(dpo_acc)):.3f}", []
                 if rank == 0:
                     opt_store = unet_state.opt_store  # Prodigy: lr multiplies the estimated d, which is worth a look beside the loss
                     d = f', unet d {float(opt_store.prodigy_d().item()):.4e}' if opt_store is not None and opt_store.optimizer == "prodigy" else ""
                     log(f'at steps {count}, avg loss for {config_dict["loss_logging_interval"]} steps: {loss}, took {elapsed} second(s), '
-                        f'unet lr {current_lr(unet_state):.4e}{d}')
+                        f'unet lr {current_lr(unet_state):.4e}{d}{acc}')
                     with open(config_dict["loss_csv"], "a") as f:
                         f.write(f'\n{count},{config_dict["loss_logging_interval"]},{loss},{elapsed},{config_dict["chunk_steps"]},{config_dict["master_seed"]}')
         rng_states = gather_rng_states(train_rngs)  # every rank resumes ITS noise / timestep stream (collective)
@@ -321,6 +336,8 @@ if __name__ == "__main__":
                     help="train rank-RANK LoRA adapters on the UNet's attention projections (frozen base and text encoder) instead of every weight")
     ap.add_argument("--dora", action="store_true",
                     help="with --lora: DoRA - also train a per-output-feature magnitude of every adapted kernel (weight-decomposed LoRA)")
+    ap.add_argument("--dpo", metavar="BETA", type=float, default=None,
+                    help="with --lora: Diffusion-DPO preference training on (preferred, rejected) pairs against the frozen base (diffusers: 5000)")
     ap.add_argument("--new-tokens", metavar="N", type=int, default=None,
                     help="textual inversion: train N placeholder-token embeddings on the frozen text encoder (alone, or beside --lora)")
     ap.add_argument("--init-token", metavar="ID", type=int, default=None, help="with --new-tokens: start every new row as a copy of token ID")
@@ -345,6 +362,8 @@ if __name__ == "__main__":
     args = ap.parse_args()
     if args.dora and args.lora is None:
         ap.error("--dora needs --lora RANK")
+    if args.dpo is not None and args.lora is None:
+        ap.error("--dpo needs --lora RANK")
     if (args.init_token is not None or args.retract) and args.new_tokens is None:
         ap.error("--init-token / --retract need --new-tokens N")
     with open(args.config) as f:
@@ -373,6 +392,8 @@ if __name__ == "__main__":
         cfg["prior_loss_weight"] = args.prior_loss_weight
     if args.loss_type is not None:
         cfg["loss_type"] = args.loss_type
+    if args.dpo is not None:
+        cfg["dpo_beta"] = args.dpo
     if args.inpaint:
         cfg["inpaint"] = True
     if args.controlnet is not None:

@@ -705,6 +705,44 @@ int sdt_dora_project(const uint16_t* dw_base, const float* w0_base, const float*
                      const SdtLoraJob* jobs_host, const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n,
                      hipStream_t stream);
 
+/* ---- DPO LOSS: Diffusion-DPO preference loss on (preferred, rejected) pairs against a frozen reference pass (Wallace et al. 2023,
+ * arXiv:2311.12908; diffusers train_diffusion_dpo.py; no reference counterpart; DESIGN.md "Diffusion-DPO").  B = 2P samples: sample 2i
+ * is the preferred image of pair i, sample 2i+1 the rejected one; pred is the trained pass, ref_pred the reference pass over the same
+ * inputs.  fl() is one fp32 rounding, fl64() one IEEE double rounding; nothing below is contracted.
+ *   per sample      for x = pred and x = ref_pred alike: diff = fl(target - x); a_b = sum_{c,p} fl(diff * diff) in MASKED LOSS's order
+ *                   (grid (nb, B), the same partition: thread, block tree, workgroup partials in workgroup order by the last arriver; no
+ *                   float atomics); m_b = fl(a_b * fl(1/(C*h*w))).  sample_mse[0][b] = m_b (trained), sample_mse[1][b] = r_b (reference).
+ *   per pair        in double from the four published fp32 values, w = 2i, l = 2i+1:
+ *                   D = (m_w - m_l) - (r_w - r_l), evaluated left to right;  z64 = fl64(fl64(-0.5 * beta) * D);  logits[i] = fl(z64)
+ *   loss            -logsigmoid(z) in the form that cannot overflow: pair_loss[i] = fl(max(-z64, 0) + log1p(exp(-|z64|)))
+ *   weight          s = sigmoid(-z64):  z64 >= 0: s = e / (1 + e), e = exp(-z64);   z64 < 0: s = 1 / (1 + exp(z64))
+ *   coefficients    coef[2i] = fl(-beta * s),  coef[2i+1] = fl(+beta * s)     (the product in double, rounded once)
+ *   total           loss_accum += fl(T * fl(1/P)), T = the pair_loss terms added in pair order in fp32
+ *   gradient        dpred[b,p,c] = bf16_rne(fl(fl(coef_b * diff) * inv_count)), diff the TRAINED pass's difference,
+ *                   inv_count = fl(1 / fl(P*C*h*w)); padding channels are written as zero.  This is d(mean over pairs of
+ *                   -logsigmoid(z)) / d pred: d m_b / d pred = -2 diff / (C*h*w) and dz/dm_w = -beta/2 = -dz/dm_l.
+ * exp and log1p are the device's double functions (not correctly rounded: pair_loss and coef are within 1 fp32 ulp of a correctly
+ * rounded evaluation from the published sample_mse; every other output follows bit for bit from the published values before it).
+ * sdt_dpo_loss_fwd_bwd: pred, ref_pred bf16 NHWC (B,h,w,cpad), target f32 NCHW (B,C,h,w); loss_accum accumulated; sample_mse f32 (2,B),
+ * logits f32 (P), pair_loss f32 (P), coef f32 (B) and dpred bf16 NHWC written.  ONE call, TWO launches on the stream - the sums, then the
+ * gradient: a gradient element needs the finished sums of four samples.  16-byte pred / ref_pred / dpred vectors when cpad % 8 == 0 and
+ * all three are 16-byte aligned (padding lanes of pred / ref_pred never enter the arithmetic), element by element otherwise (they are
+ * not read).  Workspace: sdt_dpo_loss_workspace_bytes(B, H, W) bytes under the split-workspace contract of REDUCTION WORKSPACES above
+ * (two sets of B * nb partials: sdt_reduce_workspace_bytes() while 2 * B * nb floats fit its 64 KiB of scratch, more beyond; -1 for a
+ * refused shape).  Refused with SDT_ERR_INVALID_ARG before any HIP call: null or misaligned pointers (f32: 4 bytes, bf16: 2 bytes, the
+ * workspace: 16 bytes), B odd or outside 2..8192, C, H or W < 1, cpad < C, beta not finite or <= 0, a workspace that is too small. */
+int sdt_dpo_loss_fwd_bwd(const uint16_t* pred_nhwc, const uint16_t* ref_pred_nhwc, const float* target_nchw, float beta, float* loss_accum,
+                         float* sample_mse, float* logits, float* pair_loss, float* coef, uint16_t* dpred_nhwc, int B, int C, int H, int W,
+                         int cpad, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int64_t sdt_dpo_loss_workspace_bytes(int B, int H, int W);
+/* sdt_lora_restore: the inverse of sdt_lora_merge / sdt_dora_merge as far as the mirror is concerned - w_bf16[leaf] = bf16_rne(W0) for
+ * every adapted leaf of the job table, the bits sdt_param_prepare leaves in those leaves of a store without an adapter: the frozen base
+ * is the DPO reference model, with no second set of weights.  One grouped launch over the merge's 64 x 64 tiles, 2 x 16-byte loads and
+ * one 16-byte store per run of 8 elements; the job table's checks and refusals are sdt_lora_merge's (n == 0 launches nothing; null
+ * w0_base, w_bf16 or job table, pointers off a 16-byte boundary and a bad table are refused).  The factors and f_off are not read. */
+int sdt_lora_restore(const float* w0_base, uint16_t* w_bf16, const SdtLoraJob* jobs_host, const void* jobs_device, int n,
+                     hipStream_t stream);
+
 /* ---- test hooks (not for the training path) ----
  * Output channels per tile of the 3x3 halo convolution inside sdt_gemm_nt_bf16: 64 (the default) or 128 (the reference of the
  * bitwise parity test).  Process-wide, not thread-safe; launches already enqueued keep the width they were planned with.

@@ -69,6 +69,7 @@ SIGNATURES = {
     "sdt_loss_mask_prepare": [_P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _L, _P],
     "sdt_masked_mse_loss_fwd_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
     "sdt_robust_loss_fwd_bwd": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
+    "sdt_dpo_loss_fwd_bwd": [_P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P, _L, _P],
     "sdt_timestep_embedding": [_P, _P, _I, _I, _I, _F, _P],
     "sdt_sqnorm_accumulate": [_P, _L, _P, _P, _L, _P],
     "sdt_sqnorm_accumulate_bf16": [_P, _L, _P, _P, _L, _P],
@@ -127,6 +128,7 @@ SIGNATURES = {
     "sdt_transpose_bf16": [_P, _P, _I, _I, _I, _P],
     "sdt_param_prepare": [_P, _P, _P, _P, _I, _I, _P],
     "sdt_lora_merge": [_P, _P, _P, _P, _P, _P, _I, _P],
+    "sdt_lora_restore": [_P, _P, _P, _P, _I, _P],
     "sdt_lora_project": [_P, _P, _P, _P, _P, _I, _P],
     "sdt_dora_merge": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "sdt_dora_init_magnitude": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
@@ -144,7 +146,7 @@ WS_QUERY = {"sdt_gemm_nt_workspace_bytes": [_L, _I, _I, _I], "sdt_gemm_tn_worksp
             "sdt_groupnorm_bwd_workspace_bytes": [_I, _I, _I],
             "sdt_groupnorm_fwd_workspace_bytes": [_I, _I, _I, _I], "sdt_attention_bwd_workspace_bytes": [_P],
             "sdt_ip_attention_bwd_workspace_bytes": [_I, _I, _I, _I, _I],
-            "sdt_gemm_tn_wgrad_group_workspace_bytes": [_P, _I], "sdt_conv_wgrad_group_workspace_bytes": [_P, _I], "sdt_reduce_workspace_bytes": [], "sdt_sqnorm_workspace_bytes": [], "sdt_prodigy_workspace_bytes": [], "sdt_colsum_workspace_bytes": [_I, _L, _I],
+            "sdt_gemm_tn_wgrad_group_workspace_bytes": [_P, _I], "sdt_conv_wgrad_group_workspace_bytes": [_P, _I], "sdt_reduce_workspace_bytes": [], "sdt_dpo_loss_workspace_bytes": [_I, _I, _I], "sdt_sqnorm_workspace_bytes": [], "sdt_prodigy_workspace_bytes": [], "sdt_colsum_workspace_bytes": [_I, _L, _I],
             "sdt_wgrad_sq_slots": [_I, _I, _I]}
 NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_lora_job_size": _I, "sdt_dora_job_size": _I, "sdt_last_error": ctypes.c_char_p}
 

@@ -728,6 +728,141 @@ __global__ void __launch_bounds__(256) masked_mse_kernel(const bf16_t* __restric
   }
 }
 
+// ------------------------------------------------------------------ Diffusion-DPO loss (include/sdt.h "DPO LOSS")
+// First launch: the per-sample mean squared errors of the trained pass (pred) and the reference pass (ref), then everything per pair.
+// Grid (nb, B) and the partition of masked_mse_kernel; a thread keeps two accumulators, the workgroup stores two partials (part[b*nb + j]
+// trained, part[(B + b)*nb + j] reference), the last arriver of sample b adds each set in workgroup order and publishes
+// sample_mse[b] = fl(a * inv_chw), sample_mse[B + b] likewise.  The workgroup that finishes the last sample evaluates the pairs - one
+// thread per pair, in double from the four published fp32 values - and thread 0 adds the pair losses in pair order.
+template <bool VEC>
+__global__ void __launch_bounds__(256) dpo_sums_kernel(const bf16_t* __restrict__ pred, const bf16_t* __restrict__ ref,
+                                                       const float* __restrict__ target, float beta, float* __restrict__ loss,
+                                                       float* __restrict__ sample_mse, float* __restrict__ logits,
+                                                       float* __restrict__ pair_loss, float* __restrict__ coef, int B, int C, int HW,
+                                                       int cpad, float inv_chw, float inv_pairs, int* counters, float* __restrict__ part) {
+#pragma clang fp contract(off)
+  __shared__ float scratch[16];
+  __shared__ int s_last;
+  const int b = blockIdx.y, nb = gridDim.x;
+  const float* tb = target + (long)b * C * HW;
+  float acc_m = 0.f, acc_r = 0.f;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += nb * 256) {
+    const long i = (long)b * HW + p;
+    if (VEC) {
+      const uint4* prow = reinterpret_cast<const uint4*>(pred + i * cpad);
+      const uint4* rrow = reinterpret_cast<const uint4*>(ref + i * cpad);
+      for (int c0 = 0; c0 < C; c0 += 8) {
+        float pv[8], rv[8];
+        unpack8(prow[c0 >> 3], pv);
+        unpack8(rrow[c0 >> 3], rv);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+          if (c0 + j < C) {
+            const float t = tb[(long)(c0 + j) * HW + p];
+            const float dm = t - pv[j], dr = t - rv[j];
+            acc_m += dm * dm;
+            acc_r += dr * dr;
+          }
+        }
+      }
+    } else {
+      for (int c = 0; c < C; ++c) {
+        const float t = tb[(long)c * HW + p];
+        const float dm = t - bf2f(pred[i * cpad + c]), dr = t - bf2f(ref[i * cpad + c]);
+        acc_m += dm * dm;
+        acc_r += dr * dr;
+      }
+    }
+  }
+  const float sm = block_sum(acc_m, scratch);
+  const float sr = block_sum(acc_r, scratch);
+  float* pm = part + (long)b * nb;        // per-workgroup partials of sample b, trained pass
+  float* pr = part + (long)(B + b) * nb;  // reference pass
+  if (threadIdx.x == 0) {
+    sdt_store_wt(pm + blockIdx.x, sm);
+    sdt_store_wt(pr + blockIdx.x, sr);
+  }
+  if (!sdt_arrive_last<true>(counters + b, nb, &s_last)) return;
+  float am = 0.f, ar = 0.f;
+  for (int i = threadIdx.x; i < nb; i += 256) {
+    am += sdt_load_wt(pm + i);
+    ar += sdt_load_wt(pr + i);
+  }
+  am = block_sum(am, scratch);
+  ar = block_sum(ar, scratch);
+  if (threadIdx.x == 0) {
+    sdt_store_wt(sample_mse + b, am * inv_chw);
+    sdt_store_wt(sample_mse + B + b, ar * inv_chw);
+  }
+  // second level: the workgroup that finishes the last sample evaluates the pairs
+  if (!sdt_arrive_last<true>(counters + B, B, &s_last)) return;
+  const int P = B >> 1;
+  const double bd = (double)beta, hb = -0.5 * bd;
+  for (int i = threadIdx.x; i < P; i += 256) {
+    const double mw = (double)sdt_load_wt(sample_mse + 2 * i), ml = (double)sdt_load_wt(sample_mse + 2 * i + 1);
+    const double rw = (double)sdt_load_wt(sample_mse + B + 2 * i), rl = (double)sdt_load_wt(sample_mse + B + 2 * i + 1);
+    const double dlt = (mw - ml) - (rw - rl);
+    const double z = hb * dlt;
+    // -logsigmoid(z) = max(-z, 0) + log1p(exp(-|z|));  s = sigmoid(-z) from the exponential of a non-positive argument
+    const double e = exp(-fabs(z));
+    const double pl = fmax(-z, 0.0) + log1p(e);
+    const double s = z >= 0.0 ? e / (1.0 + e) : 1.0 / (1.0 + e);
+    logits[i] = (float)z;
+    sdt_store_wt(pair_loss + i, (float)pl);
+    coef[2 * i] = (float)(-bd * s);
+    coef[2 * i + 1] = (float)(bd * s);
+  }
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float t = 0.f;
+    for (int i = 0; i < P; ++i) t += sdt_load_wt(pair_loss + i);
+    *loss += t * inv_pairs;
+  }
+}
+
+// Second launch: dpred = bf16(fl(fl(coef_b * diff) * inv_count)), diff = fl(target - pred), over the same grid and partition; padding
+// channels are written as zero and the padding lanes of pred never enter the arithmetic.
+template <bool VEC>
+__global__ void __launch_bounds__(256) dpo_grad_kernel(const bf16_t* __restrict__ pred, const float* __restrict__ target,
+                                                       const float* __restrict__ coef, bf16_t* __restrict__ dpred, int C, int HW,
+                                                       int cpad, float inv_count) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.y, nb = gridDim.x;
+  const float k = coef[b];
+  const float* tb = target + (long)b * C * HW;
+  for (int p = blockIdx.x * 256 + threadIdx.x; p < HW; p += nb * 256) {
+    const long i = (long)b * HW + p;
+    if (VEC) {
+      const uint4* prow = reinterpret_cast<const uint4*>(pred + i * cpad);
+      for (int c0 = 0; c0 < cpad; c0 += 8) {
+        float d[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        if (c0 < C) {
+          float pv[8];
+          unpack8(prow[c0 >> 3], pv);
+#pragma unroll
+          for (int j = 0; j < 8; ++j) {
+            if (c0 + j < C) {
+              const float diff = tb[(long)(c0 + j) * HW + p] - pv[j];
+              d[j] = k * diff * inv_count;
+            }
+          }
+        }
+        *reinterpret_cast<uint4*>(dpred + i * cpad + c0) = pack8(d);
+      }
+    } else {
+      for (int c = 0; c < cpad; ++c) {
+        float d = 0.f;
+        if (c < C) {
+          const float diff = tb[(long)c * HW + p] - bf2f(pred[i * cpad + c]);
+          d = k * diff * inv_count;
+        }
+        dpred[i * cpad + c] = f2bf(d);
+      }
+    }
+  }
+}
+
 // get_sinusoidal_embeddings: out[b] = [cos(t*inv_i) | sin(t*inv_i)] (flip) or [sin|cos]
 __global__ void timestep_embed_kernel(const int* __restrict__ t, bf16_t* __restrict__ out, int B, int dim,
                                       int flip_sin_to_cos, float freq_shift, float max_period) {
@@ -1556,6 +1691,45 @@ int sdt_robust_loss_fwd_bwd(const uint16_t* pred_nhwc, const float* target_nchw,
                      inv_count, inv_chw, reinterpret_cast<int*>(workspace),
                      reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
   SDT_LAUNCH_CHECK("sdt_robust_loss_fwd_bwd");
+  return SDT_OK;
+}
+
+/* the grid of the masked-loss kernels; the two sets of B * nb partials outgrow the 64 KiB of sdt_reduce_workspace_bytes() only when
+ * B * nb > 8192 floats */
+int64_t sdt_dpo_loss_workspace_bytes(int B, int H, int W) {
+  if (B < 2 || B > MASKED_MAX_B || B % 2 || H <= 0 || W <= 0 || (long)H * W > (1L << 30)) return -1;
+  const int64_t need = SDT_WS_COUNTER_BYTES + 2 * (int64_t)B * masked_blocks(B, (long)H * W) * (int64_t)sizeof(float);
+  return need > sdt_reduce_workspace_bytes() ? need : sdt_reduce_workspace_bytes();
+}
+
+int sdt_dpo_loss_fwd_bwd(const uint16_t* pred_nhwc, const uint16_t* ref_pred_nhwc, const float* target_nchw, float beta, float* loss_accum,
+                         float* sample_mse, float* logits, float* pair_loss, float* coef, uint16_t* dpred_nhwc, int B, int C, int H, int W,
+                         int cpad, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  SDT_CHECK_ARG(pred_nhwc && ref_pred_nhwc && target_nchw && loss_accum && sample_mse && logits && pair_loss && coef && dpred_nhwc,
+                "sdt_dpo_loss_fwd_bwd: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)target_nchw | (uintptr_t)loss_accum | (uintptr_t)sample_mse | (uintptr_t)logits | (uintptr_t)pair_loss |
+                  (uintptr_t)coef) & 3) == 0 && (((uintptr_t)pred_nhwc | (uintptr_t)ref_pred_nhwc | (uintptr_t)dpred_nhwc) & 1) == 0,
+                "sdt_dpo_loss_fwd_bwd: misaligned pointer (4 bytes, bf16: 2 bytes)");
+  SDT_CHECK_ARG(B >= 2 && B <= MASKED_MAX_B && B % 2 == 0,
+                "sdt_dpo_loss_fwd_bwd: B=%d must be even (preferred, rejected pairs) in 2..%d", B, MASKED_MAX_B);
+  SDT_CHECK_ARG(C > 0 && H > 0 && W > 0 && (long)H * W <= (1L << 30), "sdt_dpo_loss_fwd_bwd: bad shape C=%d H=%d W=%d", C, H, W);
+  SDT_CHECK_ARG(cpad >= C, "sdt_dpo_loss_fwd_bwd: cpad=%d < C=%d", cpad, C);
+  SDT_CHECK_ARG(beta > 0.f && beta <= 3.402823466e38f, "sdt_dpo_loss_fwd_bwd: beta=%g must be finite and > 0", (double)beta);
+  SDT_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= sdt_dpo_loss_workspace_bytes(B, H, W),
+                "sdt_dpo_loss_fwd_bwd: workspace of sdt_dpo_loss_workspace_bytes() needed");
+  const int HW = H * W, P = B / 2;
+  const float inv_chw = 1.0f / ((float)C * H * W), inv_pairs = 1.0f / (float)P;
+  const float inv_count = 1.0f / (float)((double)P * C * H * W);
+  const bool vec = cpad % 8 == 0 && (((uintptr_t)pred_nhwc | (uintptr_t)ref_pred_nhwc | (uintptr_t)dpred_nhwc) & 15) == 0;
+  const dim3 grid(masked_blocks(B, HW), B);
+  hipLaunchKernelGGL(vec ? dpo_sums_kernel<true> : dpo_sums_kernel<false>, grid, dim3(256), 0, stream, (const bf16_t*)pred_nhwc,
+                     (const bf16_t*)ref_pred_nhwc, target_nchw, beta, loss_accum, sample_mse, logits, pair_loss, coef, B, C, HW, cpad,
+                     inv_chw, inv_pairs, reinterpret_cast<int*>(workspace),
+                     reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
+  SDT_LAUNCH_CHECK("sdt_dpo_loss_fwd_bwd");
+  hipLaunchKernelGGL(vec ? dpo_grad_kernel<true> : dpo_grad_kernel<false>, grid, dim3(256), 0, stream, (const bf16_t*)pred_nhwc,
+                     target_nchw, (const float*)coef, (bf16_t*)dpred_nhwc, C, HW, cpad, inv_count);
+  SDT_LAUNCH_CHECK("sdt_dpo_loss_fwd_bwd");
   return SDT_OK;
 }
 

@@ -126,6 +126,26 @@ __global__ void __launch_bounds__(256) lora_merge_kernel(const float* __restrict
   }
 }
 
+// ---- restore (include/sdt.h "DPO LOSS"): the merge's tiles and runs, W0 alone - w = bf16(W0), what sdt_param_prepare wrote there --------
+__global__ void __launch_bounds__(256) lora_restore_kernel(const float* __restrict__ w0_base, bf16_t* __restrict__ w_dst,
+                                                           const SdtLoraJob* __restrict__ jobs, int njobs) {
+  const SdtLoraJob d = find_job(jobs, njobs, blockIdx.x, false);
+  const int tl = blockIdx.x - d.tile0_merge;
+  const int tc = (d.N + LT - 1) / LT;
+  const int r0 = (tl / tc) * LT, c0 = (tl % tc) * LT;
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {  // 512 runs of 8 columns; N is a multiple of 8: a run is whole or absent
+    const int g = threadIdx.x + 256 * it;
+    const int row = r0 + (g >> 3), col = c0 + (g & 7) * 8;
+    if (row >= d.K || col >= d.N) continue;
+    const long e = (long)row * d.N + col;
+    const float* src = w0_base + d.w0_off + e;
+    const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
+    const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+    *reinterpret_cast<uint4*>(w_dst + d.w_off + e) = pack8(v);
+  }
+}
+
 // ---- DoRA merge (include/sdt.h "DoRA"): one 64-column stripe of one leaf per workgroup.  First walk over K: v tiles as above, every
 // thread sums v^2 of its 8 columns over the rows it owns (row t >> 3 and 32 below it, of every 64-row block, top to bottom), the 32
 // partials of a column are added in row order by one thread: one fixed order, no atomics.  c = sqrt(q) and g = m / c are formed in
@@ -476,6 +496,21 @@ int sdt_lora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16,
   hipLaunchKernelGGL(lora_merge_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, w0_base, ab_base, (bf16_t*)w_bf16, f32_dst,
                      (const SdtLoraJob*)jobs_device, n);
   SDT_LAUNCH_CHECK("sdt_lora_merge");
+  return SDT_OK;
+}
+
+int sdt_lora_restore(const float* w0_base, uint16_t* w_bf16, const SdtLoraJob* jobs_host, const void* jobs_device, int n,
+                     hipStream_t stream) {
+  SDT_CHECK_ARG(n >= 0, "sdt_lora_restore: negative job count");
+  if (n == 0) return SDT_OK;
+  SDT_CHECK_ARG(jobs_host && jobs_device, "sdt_lora_restore: null job table");
+  SDT_CHECK_ARG(w0_base && w_bf16, "sdt_lora_restore: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)w_bf16) & 15) == 0, "sdt_lora_restore: pointers must be 16-byte aligned");
+  const long tiles = check_jobs("sdt_lora_restore", jobs_host, n, false);
+  if (tiles < 0) return SDT_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(lora_restore_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, w0_base, (bf16_t*)w_bf16,
+                     (const SdtLoraJob*)jobs_device, n);
+  SDT_LAUNCH_CHECK("sdt_lora_restore");
   return SDT_OK;
 }
 

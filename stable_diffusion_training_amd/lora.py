@@ -252,6 +252,13 @@ class LoraAdapter:
         _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.jobs_host,
                   self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
 
+    def restore(self):
+        """w[leaf] = bf16(W0) for every adapted leaf (one launch, sdt_lora_restore): the mirror of the store without its adapter, bit
+        for bit - the reference model of a Diffusion-DPO step.  The inverse of merge() as far as the mirror is concerned; self.source
+        (what a later merge(None) merges) and, for DoRA, self.stats (what project() reads) stay what the last merge left."""
+        _lib.call("sdt_lora_restore", self.base.master.data_ptr(), self.base.w.data_ptr(), self.jobs_host, self.jobs_dev.data_ptr(),
+                  len(self.jobs_host), self._stream())
+
     def project(self):
         """dA, dB of every adapted leaf from the dW scratch into the adapter store's gradient (one launch; written, not accumulated)."""
         from . import ops

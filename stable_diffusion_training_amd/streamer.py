@@ -19,7 +19,7 @@ class DataLoader:
                  queue_get_timeout=60, chunk_number=0, seed=0, context_concatenation_multiplier=1, *,
                  batches_per_chunk=100, vocab_size=49408, context_window=77, rank=0, world_size=1, device="cpu", text_towers=1,
                  loss_masks=False, prior_every=0, prior_loss_weight=1.0, inpaint_masks=False, placeholder_ids=None, conditioning_images=False,
-                 image_embeds=0, image_embed_drop_rate=0.0):
+                 image_embeds=0, image_embed_drop_rate=0.0, preference_pairs=False):
         if len(maximum_resolution_areas) != len(bucket_lower_bound_resolutions):
             raise ValueError("number of elements in maximum_resolution_areas and bucket_lower_bound_resolutions is not match!")
         if training_batch_size % world_size:
@@ -46,6 +46,10 @@ class DataLoader:
         if not 0.0 <= float(image_embed_drop_rate) <= 1.0:
             raise ValueError(f"image_embed_drop_rate={image_embed_drop_rate!r} must lie in [0, 1]")
         self.image_embeds, self.image_embed_drop_rate = image_embeds, float(image_embed_drop_rate)  # width of the embedding, 0: none
+        self.preference_pairs = bool(preference_pairs)
+        if self.preference_pairs and (training_batch_size // world_size) % 2:
+            raise ValueError(f"preference_pairs: every rank's batch ({training_batch_size // world_size}) holds interleaved (preferred, "
+                             "rejected) pairs and must be even")
         self.placeholder_ids = self._check_placeholders(placeholder_ids, text_towers, context_window)
         self.buckets = [tuple(int(v) for v in b) for area, lo in zip(maximum_resolution_areas, bucket_lower_bound_resolutions)
                         for b in calculate_resolution_array(area, lo, 64)]
@@ -109,7 +113,10 @@ class DataLoader:
         from a fifth generator; image_embed_drop_rate=p zeroes a sample's embedding with probability p (the published training script's
         image-prompt dropout, which lets classifier-free guidance drop the image prompt).  The defaults add none of them.
         placeholder_ids (a list of ids, or one list per tower for text_towers=2) overwrites the positions after BOS of every caption
-        window with those ids - the caption "<sks> ..." of a textual-inversion run; the other entries keep their values."""
+        window with those ids - the caption "<sks> ..." of a textual-inversion run; the other entries keep their values.
+        preference_pairs=True (Diffusion-DPO, train_step dpo_beta=): the batch holds interleaved (preferred, rejected) pairs - samples 2i
+        and 2i+1 are two different images under ONE caption: sample 2i+1's input_ids are sample 2i's; every other entry keeps its
+        value."""
         if self._cursor >= len(self._plan):
             return "end_of_batch"
         b0, b1 = self._plan[self._cursor]
@@ -129,6 +136,8 @@ class DataLoader:
                     ids[..., 1: 1 + len(pl)] = row
                 else:
                     ids[:, :, t, 1: 1 + len(pl)] = row
+        if self.preference_pairs:
+            ids[1::2] = ids[0::2]  # a pair shares its caption; its two images stay different
         ids = ids.reshape(per_rank, -1)
         batch = {"pixel_values": px, "input_ids": ids, "attention_mask": torch.ones_like(ids)}
         if self.text_towers == 2:

@@ -342,6 +342,28 @@ def _check_loss_type(loss_type, huber_c, huber_schedule):
         raise ValueError(f"huber_c={c!r} > 1: the {huber_schedule} schedule runs from 1 down to huber_c and needs huber_c <= 1")
 
 
+def _check_dpo(beta, unet_state, text_encoder_state, tokens, side, batch, loss_type, min_snr_gamma, reducer):
+    """ValueError for what a Diffusion-DPO step (train_step dpo_beta=) cannot run; each message names the rule."""
+    if isinstance(beta, bool) or not isinstance(beta, (int, float)) or not math.isfinite(beta) or not beta > 0:
+        raise ValueError(f"dpo_beta={beta!r} must be a finite number > 0 (diffusers trains SD1.5 / SDXL with 5000)")
+    if side is not None or tokens is not None or getattr(unet_state, "adapter", None) is None:
+        raise ValueError("dpo_beta: the UNet state must carry a LoRA / DoRA adapter and nothing else - the frozen base under the adapter "
+                         "is the reference model; full fine-tuning, side networks and new tokens would need a second reference store")
+    if getattr(text_encoder_state, "adapter", None) is not None:
+        raise ValueError("dpo_beta: a text-encoder adapter is not supported - the context would differ between the trained and the "
+                         "reference pass (build the text encoder \"frozen\")")
+    held = [k for k in ("loss_mask", "loss_weight") if k in batch]
+    if held:
+        raise ValueError(f"dpo_beta: {' / '.join(held)} in the batch is not supported - the preference loss has no masked or weighted form")
+    if loss_type != "l2":
+        raise ValueError(f"dpo_beta: loss_type={loss_type!r} is not supported - the preference loss compares squared errors (\"l2\")")
+    if min_snr_gamma:
+        raise ValueError(f"dpo_beta: min_snr_gamma_magnitude={min_snr_gamma!r} is not supported - a pair's samples share one timestep and "
+                         "the loss takes no per-sample weight (it must be 0)")
+    if reducer is not None:
+        raise ValueError("dpo_beta: data-parallel training is not supported - LoRA states take no reducer")
+
+
 def huber_threshold_table(alphas_cumprod, huber_c, huber_schedule):
     """The Huber threshold of every training timestep, float32 (T,), computed in float64 and rounded once (include/sdt.h "ROBUST LOSS";
     kohya / diffusers huber_schedule).  alphas_cumprod: the scheduler's host table (T,).
@@ -593,7 +615,7 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                frozen_vae_state, frozen_noise_scheduler_state, strip_bos_eos_token=True, offset_noise_magnitude=0.0,
                min_snr_gamma_magnitude=0.0, perturbation_noise_magnitude=0.0, ema_rate=0.0, *, rand=None, reducer=None,
                vae_scale=0.18215, aux=None, micro_batches=1, masked_loss_floor=0.0, normalize_masked_area=False, loss_type="l2",
-               huber_c=0.1, huber_schedule="snr"):
+               huber_c=0.1, huber_schedule="snr", dpo_beta=None):
     """One DDPM training step on this rank's shard of the batch (training_utils.py:504-762), in place.
 
     batch: {"pixel_values": f32 (B,3,H,W) NCHW device tensor, "input_ids": i32 (B*k,77), "attention_mask": unused}.
@@ -663,6 +685,22 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     IP-Adapter (TrainState.ip_adapter on the UNet state; nets.SideNetwork): as the ControlNet, with "image_embeds", f32 or bf16 (B,
     image_embed_dim) - nets.ip_adapter_tokens runs on the adapter's (trained) store and every attn2 of the frozen UNet adds its image
     term at unit scale (unet_forward(ip=)); aux= taps gain "ip_tokens".  The same ValueErrors, and one for a ControlNet beside it.
+    Diffusion-DPO (dpo_beta; include/sdt.h "DPO LOSS", DESIGN.md §6 "Diffusion-DPO"): preference training of a LoRA / DoRA UNet state on
+    (preferred, rejected) pairs against the frozen base as the reference model.  The batch is an ordinary batch of N = 2P samples,
+    interleaved (preferred, rejected, preferred, ...); input_ids cover all N samples.  posterior_eps is per sample (N); noise, timesteps,
+    offset_noise and perturb_noise are per PAIR: rand= entries have leading dim P (sliced per micro-batch at pair granularity), and
+    without rand= they are drawn from train_rng at size P in the plain step's order; the step expands them with repeat_interleave(2, 0)
+    in front of the unchanged front kernels.  Per (micro-)batch, after the front and the frozen text encoder: adapter.restore()
+    (sdt_lora_restore: the mirror's adapted leaves are the base's), the UNet forward without a tape -> ref_pred, adapter.merge("master"),
+    the taped forward -> pred, sdt_dpo_loss_fwd_bwd, then the LoRA step's backward, projection and optimizer step.  The context and the
+    SDXL conditioning are computed once for both passes.  When the step returns the mirror holds the merged weights, as after a LoRA
+    step.  metrics: "loss" (the mean over pairs of -logsigmoid(-beta/2 * ((m_w - m_l) - (r_w - r_l)))), "implicit_acc" (the mean of
+    logits > 0, as diffusers logs it), "dpo_logits" (P,), "model_mse" (N,), "ref_mse" (N,) - the micro-batches' concatenated; aux= taps
+    gain "ref_pred", "dpo_coef", "dpo_pair_loss" and "dpred".  diffusers trains SD1.5 / SDXL with beta = 5000.  ValueError for a dpo_beta that is not
+    finite and > 0, a UNet state without a LoRA / DoRA adapter (full fine-tune, side networks and new tokens would need a second
+    reference store), a text-encoder adapter (the context would differ between the passes), an odd batch or micro-batch, loss_mask /
+    loss_weight in the batch, loss_type other than "l2", a min-SNR gamma and a reducer.  dpo_beta=None is launch for launch the step
+    described above.
     Returns the reference's 6-tuple; metrics["loss"] is a device scalar (read it to synchronise, as training.py:238-245)."""
     _check_loss_type(loss_type, huber_c, huber_schedule)
     text_time = unet_state.config.get("addition_embed_type") == "text_time"
@@ -705,6 +743,9 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                              f"{net.the}'s store steps")
     cn, ipa = sides["controlnet"], sides["ip_adapter"]
     side = cn or ipa  # the side network whose store steps, or None
+    dpo = dpo_beta is not None
+    if dpo:
+        _check_dpo(dpo_beta, unet_state, text_encoder_state, tk, side, batch, loss_type, min_snr_gamma_magnitude, reducer)
     lora = bool(adapters) or tk is not None  # the frozen-base step: adapters' and / or the tokens' own stores are the ones that step
     if adapters:
         if us.trainable or ts.trainable or unet_state.adapter is None:
@@ -736,6 +777,10 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
     if K > 1 and reducer is not None and reducer.shard:
         raise ValueError("micro_batches > 1 is not supported with the sharded optimizer (GradReducer(shard=True))")
     B = N // K
+    if dpo and (N % 2 or B % 2):
+        raise ValueError(f"dpo_beta: the batch holds interleaved (preferred, rejected) pairs - the batch ({N}) and every micro-batch "
+                         f"({B}) must be even")
+    Bd = B // 2 if dpo else B  # leading dim of the draws a pair shares (noise, timesteps, offset and perturbation noise)
     L = batch["latent_moments"].shape[3] // 2 if cached else frozen_vae_state.call["latent_channels"]
 
     if reducer is not None:
@@ -751,7 +796,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             kc = batch["input_ids"].shape[0] // N  # text-encoder rows per sample
             mb = {n: v[sl] for n, v in batch.items() if n == image_key or n in PER_SAMPLE_KEYS}
             mb["input_ids"] = batch["input_ids"][k * B * kc: (k + 1) * B * kc]
-            rnd = {n: v[sl] for n, v in rand.items()}
+            psl = slice(k * Bd, (k + 1) * Bd) if dpo else sl  # DPO: everything but the posterior draw is per pair
+            rnd = {n: v[sl if n in ("posterior_eps", "masked_posterior_eps") else psl] for n, v in rand.items()}
 
         ops.gn_arena_begin(dev)  # GroupNorm statistics accumulated by producer epilogues: one memset per (micro-)batch
 
@@ -783,7 +829,8 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         with trace.phase("prepare_weights"):
             if k == 0 and lora:
                 for ad in adapters:  # the frozen mirrors stay as the load left them: only the adapted leaves are rewritten
-                    ad.merge("master")
+                    if not dpo:  # (a DPO step merges after its reference pass, in every micro-batch)
+                        ad.merge("master")
                 if tk is not None:
                     tk.select("master")  # (no launch: the embedding reads the trained rows where they are)
             elif k == 0 and side is not None:
@@ -797,25 +844,29 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         # noise, timesteps                                            (training_utils.py:590-624)
         noise = rnd.get("noise")
         if noise is None:
-            noise = torch.randn(B, L, h, w, device=dev, generator=train_rng)
+            noise = torch.randn(Bd, L, h, w, device=dev, generator=train_rng)
+        pair = (lambda t: t.repeat_interleave(2, 0)) if dpo else (lambda t: t)  # a pair shares its noise and its timestep
+        noise = pair(noise)
         off = pn = None
         if offset_noise_magnitude:
             off = rnd.get("offset_noise")
             if off is None:
-                off = torch.randn(B, L, 1, 1, device=dev, generator=train_rng)
+                off = torch.randn(Bd, L, 1, 1, device=dev, generator=train_rng)
+            off = pair(off)
             if not fused:
                 noise = noise + off * offset_noise_magnitude
         if perturbation_noise_magnitude:
             pn = rnd.get("perturb_noise")
             if pn is None:
-                pn = torch.randn(B, L, h, w, device=dev, generator=train_rng)
+                pn = torch.randn(Bd, L, h, w, device=dev, generator=train_rng)
+            pn = pair(pn)
             if not fused:
                 noise = noise + perturbation_noise_magnitude * pn
         noise = noise.contiguous()
         timesteps = rnd.get("timesteps")
         if timesteps is None:
-            timesteps = torch.randint(0, sched.num_train_timesteps, (B,), device=dev, generator=train_rng)
-        timesteps = timesteps.to(torch.int32).contiguous()
+            timesteps = torch.randint(0, sched.num_train_timesteps, (Bd,), device=dev, generator=train_rng)
+        timesteps = pair(timesteps).to(torch.int32).contiguous()
         meps = mlat = None
         if inpaint:  # the masked image's own posterior draw, after the plain step's draws so that those keep their positions
             meps = rnd.get("masked_posterior_eps")
@@ -887,6 +938,15 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                       hint.shape[3], stream)
             with trace.phase("controlnet_forward"):
                 down_r, mid_r = nets.controlnet_forward(cn.store, cn.config, noisy, timesteps, ctx, hint, added)
+        ref_pred = None
+        if dpo:
+            # the reference pass: the same mirror with the adapted leaves put back to bf16(W0), no tape; then the merge the LoRA step
+            # makes in front of its forward.  ctx and added serve both passes (the text encoder is frozen and carries no adapter).
+            with trace.phase("dpo_reference_forward"):
+                unet_state.adapter.restore()
+                with torch.no_grad():
+                    ref_pred = unet_state.apply_fn(us, unet_state.config, noisy, timesteps, ctx.detach(), added)
+                unet_state.adapter.merge("master")
         with trace.phase("unet_forward"):
             ip_tokens = None
             if ipa is not None:
@@ -907,7 +967,20 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
         C_out = unet_state.config["out_channels"]
         rws = ops.reduce_workspace(_lib.load().sdt_reduce_workspace_bytes(), dev)
         lps = emask = hub = None
-        if masked or robust:
+        if dpo:
+            # per-sample errors of both passes, the pairs' logits, losses and coefficients, then d loss / d pred: one call, two launches
+            Pm = B // 2
+            rws = ops.reduce_workspace(_lib.load().sdt_dpo_loss_workspace_bytes(B, h, w), dev)
+            smse = torch.empty(2, B, dtype=torch.float32, device=dev)
+            dlog, dpl = torch.empty(Pm, dtype=torch.float32, device=dev), torch.empty(Pm, dtype=torch.float32, device=dev)
+            dcoef = torch.empty(B, dtype=torch.float32, device=dev)
+            _lib.call("sdt_dpo_loss_fwd_bwd", pred.data_ptr(), ref_pred.data_ptr(), target.data_ptr(), float(dpo_beta), loss.data_ptr(),
+                      smse.data_ptr(), dlog.data_ptr(), dpl.data_ptr(), dcoef.data_ptr(), dpred.data_ptr(), B, C_out, h, w, pred.shape[3],
+                      rws.data_ptr(), rws.numel(), stream)
+            lps = (dlog, smse[0], smse[1])
+            if aux is not None:
+                aux.update(ref_pred=ref_pred, dpo_coef=dcoef, dpred=dpred.clone(), dpo_pair_loss=dpl)
+        elif masked or robust:
             # the effective latent mask and its per-sample sums, then the loss per sample first; a batch with loss_weight only passes no mask
             msum = None
             mask = mb.get("loss_mask")
@@ -987,7 +1060,10 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
                 for st in opt_stores:
                     st.accumulate(mode, 1.0 / K if mode == "finish" else 1.0, norm=mode == "finish")
         loss = torch.cat(losses).mean(0, keepdim=True)
-        lps = torch.cat(per_sample) if masked or robust else None
+        if dpo:
+            lps = tuple(torch.cat(t) for t in zip(*per_sample))
+        else:
+            lps = torch.cat(per_sample) if masked or robust else None
         sq_u = sq_t = None
         grad_source = "acc"
         if exchange:
@@ -1013,7 +1089,9 @@ def train_step(unet_state, text_encoder_state, unet_ema_params, text_encoder_ema
             reducer.after_optimizer()  # sharded optimizer: all-gather the bf16 weight mirrors the owners have just written
     ops.gn_arena_end(dev)
     metrics = {"loss": loss[0]}
-    if masked or robust:
+    if dpo:
+        metrics.update(implicit_acc=(lps[0] > 0).to(torch.float32).mean(), dpo_logits=lps[0], model_mse=lps[1], ref_mse=lps[2])
+    elif masked or robust:
         metrics["loss_per_sample"] = lps  # local to this rank under data parallelism
     return (unet_state, text_encoder_state, unet_ema_params if ur else None, text_encoder_ema_params if tr else None,
             metrics, train_rng)
@@ -1178,7 +1256,7 @@ def dp_compile_all_unique_resolution(unet_state, text_encoder_state, unet_ema_pa
     batch the loader delivers, (K * per_device_batch, 3, H, W), and one graph (graph A: through the last micro-batch's add pass, with
     a reducer) holds all K forward / backward passes.
     step_overrides: keyword options of train_step that TrainingConfig has no field for, e.g. vae_scale, or masked_loss_floor /
-    normalize_masked_area for batches with a loss_mask, or loss_type / huber_c / huber_schedule.  A captured step replays the launches
+    normalize_masked_area for batches with a loss_mask, or loss_type / huber_c / huber_schedule, or dpo_beta (Diffusion-DPO on LoRA states).  A captured step replays the launches
     of the batch it was captured with: it
     raises ValueError for a later batch that adds or drops loss_mask / loss_weight, or inpaint_mask (an inpainting UNet's batches
     always carry it; the static buffers take the mask and, for cached batches, masked_latent_moments like any other tensor key), or
