@@ -39,7 +39,10 @@ the adapter is written to <model>-ip-adapter (and -ip-adapter-EMA), and --cache-
 --dpo BETA ("dpo_beta"; needs --lora RANK, with or without --dora): Diffusion-DPO preference training - the loader emits interleaved
 (preferred, rejected) pairs under one caption (DataLoader(preference_pairs=True)), every step runs the frozen base as the reference
 model beside the adapted one (train_step dpo_beta=; diffusers trains SD1.5 / SDXL with 5000), and the log shows the loss and
-implicit_acc, the share of pairs the adapter ranks like the data."""
+implicit_acc, the share of pairs the adapter ranks like the data.
+--lora-conv R [--lora-conv-alpha A] ("lora_conv_rank", "lora_conv_alpha"; needs --lora RANK, refused with --dora): LoCon - rank-R adapters
+also on the UNet's convolutions (ResNet conv1 / conv2 / conv_shortcut, the samplers' conv, SD1.5's 1x1 proj_in / proj_out), alpha A
+(default R): kohya's conv_dim / conv_alpha."""
 import argparse
 import json
 import os
@@ -85,6 +88,29 @@ def current_lr(state):
         return 0.0
     sched = state.opt_store.schedule
     return sched[0].rate(max(state.step - 1, 0)) if sched else state.hyper["lr"]
+
+
+def lora_config(config_dict, world=1):
+    """The lora= argument of on_device_model_training_state from "lora_rank" (--lora), "lora_alpha", "lora_dora" (--dora),
+    "lora_conv_rank" (--lora-conv) and "lora_conv_alpha" (--lora-conv-alpha): rank-r adapters on the UNet's attention projections,
+    with lora_conv_rank also LoCon adapters on its convolutions; frozen text encoder; alpha = rank unless given.  None without lora_rank."""
+    if config_dict.get("lora_dora") and not config_dict.get("lora_rank"):
+        raise ValueError("lora_dora: DoRA is a LoRA adapter with a trained magnitude - give lora_rank (--lora RANK --dora)")
+    if (config_dict.get("lora_conv_rank") or config_dict.get("lora_conv_alpha") is not None) and not config_dict.get("lora_rank"):
+        raise ValueError("lora_conv_rank: LoCon adapts the convolutions beside the attention projections - give lora_rank (--lora RANK --lora-conv R)")
+    if config_dict.get("lora_conv_alpha") is not None and not config_dict.get("lora_conv_rank"):
+        raise ValueError("lora_conv_alpha needs lora_conv_rank (--lora-conv R --lora-conv-alpha A)")
+    if not config_dict.get("lora_rank"):
+        return None
+    if world > 1:
+        raise ValueError("lora_rank: adapter training runs on one GPU (train_step refuses a reducer with adapter states)")
+    r = int(config_dict["lora_rank"])
+    conv = {}
+    if config_dict.get("lora_conv_rank"):
+        conv = dict(conv_rank=int(config_dict["lora_conv_rank"]),
+                    conv_alpha=None if config_dict.get("lora_conv_alpha") is None else float(config_dict["lora_conv_alpha"]))
+    return dict(unet=lora.LoraConfig(r, float(config_dict.get("lora_alpha", r)), dora=bool(config_dict.get("lora_dora", False)), **conv),
+                text_encoder="frozen")
 
 
 def main(config_dict, models=None, tokenizer=None, log=print):
@@ -180,15 +206,7 @@ def main(config_dict, models=None, tokenizer=None, log=print):
         rank=rank, world_size=world, device=dev, text_towers=2 if sdxl else 1, **loss_loader_kw)
     dataloader._print_debug = bool(config_dict.get("DEBUG"))
 
-    lora_cfg = None
-    if config_dict.get("lora_dora") and not config_dict.get("lora_rank"):
-        raise ValueError("lora_dora: DoRA is a LoRA adapter with a trained magnitude - give lora_rank (--lora RANK --dora)")
-    if config_dict.get("lora_rank"):  # LoRA: rank-r adapters on the UNet's attention projections, frozen text encoder, alpha = rank
-        if world > 1:
-            raise ValueError("lora_rank: adapter training runs on one GPU (train_step refuses a reducer with adapter states)")
-        r = int(config_dict["lora_rank"])
-        lora_cfg = dict(unet=lora.LoraConfig(r, float(config_dict.get("lora_alpha", r)), dora=bool(config_dict.get("lora_dora", False))),
-                        text_encoder="frozen")
+    lora_cfg = lora_config(config_dict, world)
     train_rngs = torch.Generator(device=dev)
     train_rngs.manual_seed(config_dict["master_seed"] * 1009 + rank)  # different noise / timesteps on every shard
     (unet_state, text_encoder_state, unet_ema_params, text_encoder_ema_params, frozen_vae, frozen_schedulers,
@@ -336,6 +354,9 @@ if __name__ == "__main__":
                     help="train rank-RANK LoRA adapters on the UNet's attention projections (frozen base and text encoder) instead of every weight")
     ap.add_argument("--dora", action="store_true",
                     help="with --lora: DoRA - also train a per-output-feature magnitude of every adapted kernel (weight-decomposed LoRA)")
+    ap.add_argument("--lora-conv", metavar="R", type=int, default=None,
+                    help="with --lora: LoCon - also train rank-R adapters on the UNet's convolutions (kohya conv_dim); not with --dora")
+    ap.add_argument("--lora-conv-alpha", metavar="A", type=float, default=None, help="with --lora-conv: the conv adapters' alpha (default R)")
     ap.add_argument("--dpo", metavar="BETA", type=float, default=None,
                     help="with --lora: Diffusion-DPO preference training on (preferred, rejected) pairs against the frozen base (diffusers: 5000)")
     ap.add_argument("--new-tokens", metavar="N", type=int, default=None,
@@ -362,6 +383,10 @@ if __name__ == "__main__":
     args = ap.parse_args()
     if args.dora and args.lora is None:
         ap.error("--dora needs --lora RANK")
+    if args.lora_conv is not None and args.lora is None:
+        ap.error("--lora-conv needs --lora RANK")
+    if args.lora_conv_alpha is not None and args.lora_conv is None:
+        ap.error("--lora-conv-alpha needs --lora-conv R")
     if args.dpo is not None and args.lora is None:
         ap.error("--dpo needs --lora RANK")
     if (args.init_token is not None or args.retract) and args.new_tokens is None:
@@ -376,6 +401,10 @@ if __name__ == "__main__":
         cfg["lora_rank"] = args.lora
     if args.dora:
         cfg["lora_dora"] = True
+    if args.lora_conv is not None:
+        cfg["lora_conv_rank"] = args.lora_conv
+    if args.lora_conv_alpha is not None:
+        cfg["lora_conv_alpha"] = args.lora_conv_alpha
     if args.new_tokens is not None:
         cfg["new_tokens"] = args.new_tokens
     if args.init_token is not None:

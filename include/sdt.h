@@ -743,6 +743,44 @@ int64_t sdt_dpo_loss_workspace_bytes(int B, int H, int W);
 int sdt_lora_restore(const float* w0_base, uint16_t* w_bf16, const SdtLoraJob* jobs_host, const void* jobs_device, int n,
                      hipStream_t stream);
 
+/* ---- LoCon: LoRA on convolution kernels (kohya conv_dim / LyCORIS LoCon; DESIGN.md "LoCon") ----
+ * A Flax HWIO kernel [kh][kw][Cin][Cout] with Cin, Cout multiples of 8 is one contiguous [K = kh*kw*Cin][N = Cout] matrix in the master
+ * and in the bf16 mirror, and LoCon's delta - a kh x kw convolution down to r channels, then a 1x1 convolution up - is A [K][r] * B [r][N]
+ * in that layout (A[(t*Cin + i)][q] = lora_down[q][i][tap t], B[q][o] = lora_up[o][q][0][0]).  sdt_lora_merge and sdt_lora_restore serve
+ * such a job as they stand.  sdt_lora_project would give each 64-column stripe of dB to ONE workgroup that walks all of K (23040 rows for
+ * an SD1.5 up-block conv1); sdt_lora_project_split is the projection for tall K: same SdtLoraJob table (unchanged, and still valid for
+ * sdt_lora_project), a parallel table of n SdtLoraSplitJob, one launch.
+ *   dA   ceil(K/64) row stripes, the arithmetic of sdt_lora_project bit for bit (one shared device function).
+ *   dB   every 64-column stripe is cut along K into chunks of sdt_lora_project_split_rows() rows - a compile-time constant: the split of
+ *        a job depends on its K alone, never on the device, r, N or the rest of the table.  One workgroup per (stripe, chunk) adds
+ *        sum_k bf16(A[k][q]) * dW[k][n] over its rows, 32 rows per mfma_f32_16x16x32_bf16 step in row order, dW staged through a
+ *        double-buffered LDS block with 16-byte loads (the next block's global load is in flight across the MFMAs).
+ *        chunks == 1: dB = fl(s * acc) is written directly - sdt_lora_project's bits.
+ *        chunks > 1: the workgroup writes its fp32 partial [r][64] into the workspace and takes a ticket at the stripe's INTEGER arrival
+ *        counter; the last arriver adds the stripe's partials in chunk order 0, 1, 2, ... (one thread per element, fp32) and writes
+ *        dB = fl(s * sum).  No float atomics, one summation order per element: the same bits whether the job runs alone or in any
+ *        table, and on every repeated call.
+ * Workspace (16-byte aligned, sdt_lora_project_split_workspace_bytes(jobs_host, n) bytes; -1 for a refused table): one int32 counter
+ * per dB stripe of the table, rounded up to 256 bytes - ZERO on entry, zero again on exit, so the caller zeroes it once - followed by the
+ * partials of the jobs with chunks > 1 (no initialisation needed).  Both host tables are checked before any HIP call: sdt_lora_merge's
+ * checks; K, N equal in both tables; chunks == ceil(K / rows); tile0 the running count of tiles_da + stripes * chunks; cnt0 the running
+ * count of stripes; part_off the running count of partial floats (stripes * chunks * r * 64 for a job with chunks > 1, else 0); the
+ * workspace large enough.  n == 0 launches nothing and returns SDT_OK. */
+typedef struct SdtLoraSplitJob {
+  int64_t part_off;  /* first partial of the job, in floats behind the counters */
+  int32_t K, N;      /* the job's K and N again: a table built for other leaves is refused */
+  int32_t tile0;     /* running count of this launch's workgroups */
+  int32_t chunks;    /* ceil(K / sdt_lora_project_split_rows()) */
+  int32_t cnt0;      /* the job's first arrival counter: running count of ceil(N/64) */
+  int32_t reserved;
+} SdtLoraSplitJob;
+int sdt_lora_split_job_size(void);
+int sdt_lora_project_split_rows(void);
+int64_t sdt_lora_project_split_workspace_bytes(const SdtLoraJob* jobs_host, int n);
+int sdt_lora_project_split(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
+                           const SdtLoraSplitJob* split_host, const void* jobs_device, const void* split_device, int n, void* workspace,
+                           int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- test hooks (not for the training path) ----
  * Output channels per tile of the 3x3 halo convolution inside sdt_gemm_nt_bf16: 64 (the default) or 128 (the reference of the
  * bitwise parity test).  Process-wide, not thread-safe; launches already enqueued keep the width they were planned with.

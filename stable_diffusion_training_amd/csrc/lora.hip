@@ -3,6 +3,8 @@
 // grouped launches over one device job table with running tile counts (like sdt_param_prepare's descriptors), both round A and B to
 // bf16 as they load them (the projection differentiates the function the merge evaluated), both accumulate in fp32 on
 // mfma_f32_16x16x32_bf16 and neither uses an atomic: every output element has one writer and one fixed summation order.
+// The split projection (include/sdt.h "LoCon") serves the tall K of convolution kernels: its dB stripes are cut along K, and the only
+// atomic is the integer arrival counter behind which the last workgroup of a stripe adds the fp32 partials in chunk order.
 //
 // Operand lane maps of mfma_f32_16x16x32_bf16 (lane l): A[row l&15][k = 8(l>>4) + j], B[k = 8(l>>4) + j][col l&15], j = 0..7;
 // C/D col = l&15, row = 4(l>>4) + reg.
@@ -291,41 +293,54 @@ __device__ __forceinline__ void dora_db_tail(const SdtLoraJob& d, int c0, const 
 // DORA (include/sdt.h "DoRA"): the dA stripes scale the B fragment by g as they load it; the dB stripes also read W0 where they stage
 // dW, sum G * W0 per column (each staging thread its 8 columns over the rows it stages, top to bottom; the 32 partials of a column in
 // row order by one thread), form u = sum_k G W0 + s * sum_q bf16(B) P from their own accumulators and write dB = (s P) g and dm = u / c.
+// one 64-row stripe of dA (shared by lora_project_kernel, dora_project_kernel and lora_project_split_kernel: one arithmetic)
 template <int RB, bool DORA>  // RB = ceil(r / 16) blocks of 16 adapter columns
-__device__ __forceinline__ void project_tile(const SdtLoraJob& d, int tl, const bf16_t* __restrict__ dW, const float* __restrict__ A,
-                                             const float* __restrict__ B, float* __restrict__ gA, float* __restrict__ gB,
-                                             bf16_t (*stage)[LT + 8], const DoraCols& x) {
+__device__ __forceinline__ void project_da_stripe(const SdtLoraJob& d, int tl, const bf16_t* __restrict__ dW, const float* __restrict__ B,
+                                                  float* __restrict__ gA, const float* __restrict__ gcol) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
   const int r = d.r, K = d.K, N = d.N;
   const float s = d.scale;
   f32x4_t acc[RB];
 #pragma unroll
   for (int b = 0; b < RB; ++b) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  if (tl < d.tiles_da) {
-    // dA[k][q] = s * sum_n dW[k][n] * bf16(B[q][n]): A operand dW rows, B operand B^T (both contiguous along n)
-    const int row = tl * LT + 16 * wave + l15;
-    for (int n0 = 0; n0 < N; n0 += 32) {
-      const int n = n0 + 8 * lq;
-      uint4 v = {0u, 0u, 0u, 0u};
-      if (row < K && n < N) v = *reinterpret_cast<const uint4*>(dW + (long)row * N + n);
-      const bf16x8_t a = __builtin_bit_cast(bf16x8_t, v);
+  // dA[k][q] = s * sum_n dW[k][n] * bf16(B[q][n]): A operand dW rows, B operand B^T (both contiguous along n)
+  const int row = tl * LT + 16 * wave + l15;
+  for (int n0 = 0; n0 < N; n0 += 32) {
+    const int n = n0 + 8 * lq;
+    uint4 v = {0u, 0u, 0u, 0u};
+    if (row < K && n < N) v = *reinterpret_cast<const uint4*>(dW + (long)row * N + n);
+    const bf16x8_t a = __builtin_bit_cast(bf16x8_t, v);
 #pragma unroll
-      for (int b = 0; b < RB; ++b) {
-        const int q = 16 * b + l15;
-        const bf16x8_t bb = DORA ? frag_from_f32_scaled(B + (long)q * N + n, x.g + n, q < r && n < N)
-                                 : frag_from_f32(B + (long)q * N + n, q < r && n < N);
-        acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, acc[b], 0, 0, 0);
-      }
+    for (int b = 0; b < RB; ++b) {
+      const int q = 16 * b + l15;
+      const bf16x8_t bb = DORA ? frag_from_f32_scaled(B + (long)q * N + n, gcol + n, q < r && n < N)
+                               : frag_from_f32(B + (long)q * N + n, q < r && n < N);
+      acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, acc[b], 0, 0, 0);
     }
+  }
 #pragma unroll
-    for (int b = 0; b < RB; ++b)
+  for (int b = 0; b < RB; ++b)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int k = tl * LT + 16 * wave + 4 * lq + i, q = 16 * b + l15;
-        if (k < K && q < r) gA[(long)k * r + q] = s * acc[b][i];
-      }
+    for (int i = 0; i < 4; ++i) {
+      const int k = tl * LT + 16 * wave + 4 * lq + i, q = 16 * b + l15;
+      if (k < K && q < r) gA[(long)k * r + q] = s * acc[b][i];
+    }
+}
+
+template <int RB, bool DORA>
+__device__ __forceinline__ void project_tile(const SdtLoraJob& d, int tl, const bf16_t* __restrict__ dW, const float* __restrict__ A,
+                                             const float* __restrict__ B, float* __restrict__ gA, float* __restrict__ gB,
+                                             bf16_t (*stage)[LT + 8], const DoraCols& x) {
+  if (tl < d.tiles_da) {
+    project_da_stripe<RB, DORA>(d, tl, dW, B, gA, x.g);
     return;
   }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const int r = d.r, K = d.K, N = d.N;
+  const float s = d.scale;
+  f32x4_t acc[RB];
+#pragma unroll
+  for (int b = 0; b < RB; ++b) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   // dB[q][n] = s * sum_k bf16(A[k][q]) * dW[k][n]: A operand A^T (gathered), B operand dW columns out of the staged 32 x 64 block
   const int c0 = (tl - d.tiles_da) * LT;
   const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;  // one 16-byte load per thread stages 32 rows x 64 columns
@@ -413,6 +428,114 @@ __global__ void __launch_bounds__(256) dora_project_kernel(const bf16_t* __restr
   }
 }
 
+// ---- split projection (include/sdt.h "LoCon"): jobs with tall K.  The dA stripes are project_da_stripe; a dB stripe is cut along K
+// into chunks of SPLIT_ROWS rows, one workgroup per (stripe, chunk).  The staged 32 x 64 block of dW is double-buffered: the next
+// block's 16-byte global load is issued in front of this block's MFMAs and lands in the other buffer behind them, one barrier per
+// block.  A job of one chunk writes dB = s * acc as project_tile does (the same accumulation order: its bits).  Otherwise the
+// workgroup stores its fp32 partial [r][64] (write-through), takes a ticket at the stripe's integer arrival counter, and the last
+// arriver adds the partials in chunk order 0, 1, 2, ... - one thread per element - and writes dB = s * sum.
+constexpr int SPLIT_ROWS = 512;
+
+template <int RB>
+__device__ __forceinline__ void project_db_chunk(const SdtLoraJob& d, const SdtLoraSplitJob& x, int stripe, int chunk,
+                                                 const bf16_t* __restrict__ dW, const float* __restrict__ A, float* __restrict__ gB,
+                                                 int* __restrict__ counters, float* __restrict__ parts, bf16_t (*stage)[32][LT + 8],
+                                                 int* s_flag) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const int r = d.r, K = d.K, N = d.N;
+  const float s = d.scale;
+  const int c0 = stripe * LT;
+  const int kb = chunk * SPLIT_ROWS, ke = min(K, kb + SPLIT_ROWS);
+  const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;  // one 16-byte load per thread stages 32 rows x 64 columns
+  const bool col_ok = c0 + scol < N;
+  f32x4_t acc[RB];
+#pragma unroll
+  for (int b = 0; b < RB; ++b) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  uint4 v = {0u, 0u, 0u, 0u};
+  if (kb + srow < ke && col_ok) v = *reinterpret_cast<const uint4*>(dW + (long)(kb + srow) * N + c0 + scol);
+  *reinterpret_cast<uint4*>(&stage[0][srow][scol]) = v;
+  __syncthreads();
+  int cur = 0;
+  for (int k0 = kb; k0 < ke; k0 += 32, cur ^= 1) {
+    const bool more = k0 + 32 < ke;
+    uint4 nv = {0u, 0u, 0u, 0u};
+    if (more && k0 + 32 + srow < ke && col_ok) nv = *reinterpret_cast<const uint4*>(dW + (long)(k0 + 32 + srow) * N + c0 + scol);
+    const int k = k0 + 8 * lq;
+    bf16x8_t bb;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bb[j] = (short)stage[cur][8 * lq + j][16 * wave + l15];
+#pragma unroll
+    for (int b = 0; b < RB; ++b) {
+      const int q = 16 * b + l15;
+      const bf16x8_t a = frag_from_f32_strided(A + (long)k * r + q, r, k, ke, q < r);
+      acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, acc[b], 0, 0, 0);
+    }
+    if (more) *reinterpret_cast<uint4*>(&stage[cur ^ 1][srow][scol]) = nv;  // (its readers finished in front of the last barrier)
+    __syncthreads();
+  }
+  if (x.chunks == 1) {
+#pragma unroll
+    for (int b = 0; b < RB; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int q = 16 * b + 4 * lq + i, n = c0 + 16 * wave + l15;
+        if (q < r && n < N) gB[(long)q * N + n] = s * acc[b][i];
+      }
+    return;
+  }
+  const long slab = (long)r * LT;  // floats of one partial
+  float* mine = parts + x.part_off + ((long)stripe * x.chunks + chunk) * slab;
+#pragma unroll
+  for (int b = 0; b < RB; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int q = 16 * b + 4 * lq + i;
+      if (q < r) sdt_store_wt(mine + (long)q * LT + 16 * wave + l15, acc[b][i]);
+    }
+  if (!sdt_arrive_last<true>(counters + x.cnt0 + stripe, x.chunks, s_flag)) return;
+  const float* first = parts + x.part_off + (long)stripe * x.chunks * slab;
+  for (int e = threadIdx.x; e < (int)slab; e += 256) {
+    const int q = e >> 6, n = c0 + (e & 63);
+    if (n >= N) continue;
+    float sum = sdt_load_wt(first + e);
+    for (int c = 1; c < x.chunks; ++c) sum += sdt_load_wt(first + c * slab + e);
+    gB[(long)q * N + n] = s * sum;
+  }
+}
+
+__global__ void __launch_bounds__(256) lora_project_split_kernel(const bf16_t* __restrict__ dw_base, const float* __restrict__ ab_base,
+                                                                 float* __restrict__ grad_base, const SdtLoraJob* __restrict__ jobs,
+                                                                 const SdtLoraSplitJob* __restrict__ sj, int njobs,
+                                                                 int* __restrict__ counters, float* __restrict__ parts) {
+  __shared__ __attribute__((aligned(16))) bf16_t stage[2][32][LT + 8];
+  __shared__ int s_flag;
+  const int job = find_index(njobs, blockIdx.x, [=](int i) { return sj[i].tile0; });
+  const SdtLoraJob d = jobs[job];
+  const SdtLoraSplitJob x = sj[job];
+  const int tl = blockIdx.x - x.tile0;
+  const bf16_t* dW = dw_base + d.dw_off;
+  const float* A = ab_base + d.a_off;
+  const float* B = ab_base + d.b_off;
+  float* gA = grad_base + d.ga_off;
+  float* gB = grad_base + d.gb_off;
+  if (tl < d.tiles_da) {
+    switch ((d.r + 15) / 16) {  // (workgroup-uniform)
+      case 1: project_da_stripe<1, false>(d, tl, dW, B, gA, nullptr); break;
+      case 2: project_da_stripe<2, false>(d, tl, dW, B, gA, nullptr); break;
+      case 4: project_da_stripe<4, false>(d, tl, dW, B, gA, nullptr); break;
+      default: project_da_stripe<8, false>(d, tl, dW, B, gA, nullptr); break;
+    }
+    return;
+  }
+  const int t = tl - d.tiles_da, stripe = t / x.chunks, chunk = t % x.chunks;
+  switch ((d.r + 15) / 16) {
+    case 1: project_db_chunk<1>(d, x, stripe, chunk, dW, A, gB, counters, parts, stage, &s_flag); break;
+    case 2: project_db_chunk<2>(d, x, stripe, chunk, dW, A, gB, counters, parts, stage, &s_flag); break;
+    case 4: project_db_chunk<4>(d, x, stripe, chunk, dW, A, gB, counters, parts, stage, &s_flag); break;
+    default: project_db_chunk<8>(d, x, stripe, chunk, dW, A, gB, counters, parts, stage, &s_flag); break;
+  }
+}
+
 // Host check of the table (the host copy; the device copy must hold the same bytes).  Returns the number of tiles or -1.
 long check_jobs(const char* name, const SdtLoraJob* h, int n, bool project) {
   long tiles = 0;
@@ -475,6 +598,43 @@ long check_dora_jobs(const char* name, const SdtLoraJob* h, const SdtDoraJob* x,
   return stripes;
 }
 
+// The split table beside the job table (host copies).  Returns the number of workgroups or -1; *counters = the arrival counters (one
+// per dB stripe), *floats = the partials.
+long check_split_jobs(const char* name, const SdtLoraJob* h, const SdtLoraSplitJob* x, int n, long* counters, long* floats) {
+  long tiles = 0, cnt = 0, part = 0;
+  for (int i = 0; i < n; ++i) {
+    if (x[i].K != h[i].K || x[i].N != h[i].N) {
+      sdt_set_error("%s: job %d: the split table names K=%d N=%d, the job table K=%d N=%d (mismatched tables)", name, i, x[i].K, x[i].N,
+                    h[i].K, h[i].N);
+      return -1;
+    }
+    const long chunks = (h[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (h[i].N + LT - 1) / LT;
+    if (x[i].chunks != chunks) {
+      sdt_set_error("%s: job %d: chunks=%d, K=%d makes %ld chunks of %d rows", name, i, x[i].chunks, h[i].K, chunks, SPLIT_ROWS);
+      return -1;
+    }
+    if (x[i].tile0 != tiles || x[i].cnt0 != cnt) {
+      sdt_set_error("%s: job %d: tile0 / cnt0 do not continue the running tile and stripe counts", name, i);
+      return -1;
+    }
+    if (x[i].part_off != part) {
+      sdt_set_error("%s: job %d: part_off=%lld does not continue the running partial offset %ld", name, i, (long long)x[i].part_off, part);
+      return -1;
+    }
+    tiles += h[i].tiles_da + stripes * chunks;
+    cnt += stripes;
+    if (chunks > 1) part += stripes * chunks * h[i].r * LT;
+    if (tiles >= (1L << 31) || cnt >= (1L << 31)) {
+      sdt_set_error("%s: too many tiles", name);
+      return -1;
+    }
+  }
+  *counters = cnt;
+  *floats = part;
+  return tiles;
+}
+inline long split_counter_bytes(long counters) { return (counters * 4 + 255) / 256 * 256; }
+
 }  // namespace
 
 extern "C" {
@@ -527,6 +687,50 @@ int sdt_lora_project(const uint16_t* dw_base, const float* ab_base, float* grad_
   hipLaunchKernelGGL(lora_project_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
                      (const SdtLoraJob*)jobs_device, n);
   SDT_LAUNCH_CHECK("sdt_lora_project");
+  return SDT_OK;
+}
+
+int sdt_lora_split_job_size(void) { return (int)sizeof(SdtLoraSplitJob); }
+int sdt_lora_project_split_rows(void) { return SPLIT_ROWS; }
+
+int64_t sdt_lora_project_split_workspace_bytes(const SdtLoraJob* jobs_host, int n) {
+  if (n < 0 || (n > 0 && !jobs_host)) {
+    sdt_set_error("sdt_lora_project_split_workspace_bytes: bad job table");
+    return -1;
+  }
+  if (check_jobs("sdt_lora_project_split_workspace_bytes", jobs_host, n, true) < 0) return -1;
+  long cnt = 0, part = 0;
+  for (int i = 0; i < n; ++i) {
+    const long chunks = (jobs_host[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (jobs_host[i].N + LT - 1) / LT;
+    cnt += stripes;
+    if (chunks > 1) part += stripes * chunks * jobs_host[i].r * LT;
+  }
+  return split_counter_bytes(cnt) + 4 * part;
+}
+
+int sdt_lora_project_split(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
+                           const SdtLoraSplitJob* split_host, const void* jobs_device, const void* split_device, int n, void* workspace,
+                           int64_t workspace_bytes, hipStream_t stream) {
+  SDT_CHECK_ARG(n >= 0, "sdt_lora_project_split: negative job count");
+  if (n == 0) return SDT_OK;
+  SDT_CHECK_ARG(jobs_host && jobs_device && split_host && split_device, "sdt_lora_project_split: null job table");
+  SDT_CHECK_ARG(dw_base && ab_base && grad_base && workspace, "sdt_lora_project_split: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)dw_base | (uintptr_t)ab_base | (uintptr_t)grad_base | (uintptr_t)workspace) & 15) == 0,
+                "sdt_lora_project_split: pointers must be 16-byte aligned");
+  if (check_jobs("sdt_lora_project_split", jobs_host, n, true) < 0) return SDT_ERR_INVALID_ARG;
+  long cnt = 0, part = 0;
+  const long tiles = check_split_jobs("sdt_lora_project_split", jobs_host, split_host, n, &cnt, &part);
+  if (tiles < 0) return SDT_ERR_INVALID_ARG;
+  const long need = split_counter_bytes(cnt) + 4 * part;
+  if (workspace_bytes < need) {
+    sdt_set_error("sdt_lora_project_split: the workspace holds %lld bytes, the table needs %ld (counters and partials inside the workspace)",
+                  (long long)workspace_bytes, need);
+    return SDT_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(lora_project_split_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
+                     (const SdtLoraJob*)jobs_device, (const SdtLoraSplitJob*)split_device, n, (int*)workspace,
+                     (float*)((char*)workspace + split_counter_bytes(cnt)));
+  SDT_LAUNCH_CHECK("sdt_lora_project_split");
   return SDT_OK;
 }
 

@@ -8,6 +8,11 @@ of the adapted leaves in the adapter's scratch, and ONE launch projects dA = s *
 of the adapter's store, which then takes the optimizer step like any other store (Lion / AdamW, 8-bit or fp32 moments, EMA, schedules,
 clipping, checkpoints, micro-batch accumulation).
 
+LoCon (LoraConfig(conv_rank=R); include/sdt.h "LoCon"; DESIGN.md "LoCon"): a convolution kernel [kh, kw, Cin, Cout] whose channel counts are
+multiples of 8 is one contiguous [K = kh*kw*Cin, N = Cout] matrix in the master and in the mirror, and LoCon's k x k down-convolution to R
+channels followed by a 1x1 up-convolution is A [K, R] @ B [R, N] in that layout: the same merge, the same scratch, and a projection
+whose dB stripes are split along the tall K (sdt_lora_project_split).
+
 DoRA (LoraConfig(dora=True); include/sdt.h "DoRA"): a third trained leaf m [N] per adapted kernel, W' = v * (m / ||v||_column) with
 v = W0 + s * A @ B.  The column norm is one more reduction inside the merge launch and the magnitude gradient one more inside the
 projection launch, so the step between them is the LoRA step, launch for launch.
@@ -26,17 +31,23 @@ from .params import ParamStore
 RANKS = (4, 8, 16, 32, 64, 128)
 UNET_TARGETS = ("to_q", "to_k", "to_v", "to_out_0")
 CLIP_TARGETS = ("q_proj", "k_proj", "v_proj", "out_proj")
+UNET_CONV_TARGETS = ("conv1", "conv2", "conv_shortcut", "proj_in", "proj_out", "conv")  # "conv": downsamplers_0/conv, upsamplers_0/conv
 
 
 @dataclass(frozen=True)
 class LoraConfig:
     """rank in RANKS; the delta is (alpha / rank) * A @ B; targets are matched against path components (as params.create_mask does);
-    seed draws A (B starts at zero); dora adds the trained magnitude leaf <dense>/lora_m (it starts at the column norms of W0)."""
+    seed draws A (B starts at zero); dora adds the trained magnitude leaf <dense>/lora_m (it starts at the column norms of W0).
+    conv_rank > 0 (LoCon) also adapts the 4-D kernels whose path has a component in conv_targets, at rank conv_rank and scale
+    conv_alpha / conv_rank (conv_alpha None: conv_rank); a conv target that meets a 2-D kernel leaves it to `targets`."""
     rank: int
     alpha: float
     targets: tuple = UNET_TARGETS
     seed: int = 0
     dora: bool = False
+    conv_rank: int = 0
+    conv_alpha: float = None
+    conv_targets: tuple = UNET_CONV_TARGETS
 
     def __post_init__(self):
         object.__setattr__(self, "targets", tuple(self.targets))
@@ -48,40 +59,77 @@ class LoraConfig:
             raise ValueError(f"LoraConfig: alpha must be finite, not {self.alpha!r}")
         if not isinstance(self.dora, bool):
             raise ValueError(f"LoraConfig: dora must be a bool, not {self.dora!r}")
+        object.__setattr__(self, "conv_targets", tuple(self.conv_targets))
+        if isinstance(self.conv_rank, bool) or (self.conv_rank != 0 and self.conv_rank not in RANKS):
+            raise ValueError(f"LoraConfig: conv_rank must be 0 or one of {RANKS}, not {self.conv_rank!r}")
+        if self.conv_alpha is not None and not math.isfinite(float(self.conv_alpha)):
+            raise ValueError(f"LoraConfig: conv_alpha must be finite or None, not {self.conv_alpha!r}")
+        if not self.conv_targets or not all(isinstance(t, str) and t for t in self.conv_targets):
+            raise ValueError(f"LoraConfig: conv_targets must be a non-empty tuple of path components, not {self.conv_targets!r}")
+        if self.conv_rank and self.dora:
+            raise ValueError("LoraConfig: DoRA on convolutions is not supported (dora=True with conv_rank > 0): the DoRA merge walks K "
+                             "twice per column stripe and has no split for a convolution's tall K")
+
+    def __repr__(self):  # (without LoCon the text is what it was: refusal messages quote it)
+        conv = f", conv_rank={self.conv_rank!r}, conv_alpha={self.conv_alpha!r}, conv_targets={self.conv_targets!r}" if self.conv_rank else ""
+        return (f"LoraConfig(rank={self.rank!r}, alpha={self.alpha!r}, targets={self.targets!r}, seed={self.seed!r}, dora={self.dora!r}"
+                f"{conv})")
 
     @property
     def scale(self):
         return float(self.alpha) / self.rank
 
+    @property
+    def conv_scale(self):
+        return float(self.conv_rank if self.conv_alpha is None else self.conv_alpha) / self.conv_rank if self.conv_rank else 0.0
+
 
 def select_leaves(spec, cfg):
     """The kernel paths of `spec` ([(path, shape)], forward order) that `cfg` adapts: '/kernel' leaves with a path component equal to a
-    target.  ValueError for a convolution (4-D) kernel, for a Dense kernel whose dims are not multiples of 8 (its bf16 mirror is a
-    zero-padded copy) and when nothing matches."""
-    out = []
+    target, and with cfg.conv_rank > 0 also the 4-D '/kernel' leaves with a component equal to a conv target.  ValueError for a
+    convolution (4-D) kernel that `targets` matches, for a kernel whose dims are not multiples of 8 (its bf16 mirror is a zero-padded
+    copy), when no Dense kernel matches `targets` and, with cfg.conv_rank > 0, when no 4-D kernel matches `conv_targets`."""
+    out, convs = [], 0
     for path, shape in spec:
-        if not path.endswith("/kernel") or not any(t in path.split("/")[:-1] for t in cfg.targets):
+        if not path.endswith("/kernel"):
             continue
-        shape = tuple(shape)
-        if len(shape) != 2:
-            raise ValueError(f"LoRA: target matches {path} {shape}, which is not a Dense kernel (convolutions are not adapted)")
-        if shape[0] % 8 or shape[1] % 8:
-            raise ValueError(f"LoRA: {path} {shape} is a padded leaf (dims not multiples of 8) and cannot carry an adapter")
-        out.append(path)
-    if not out:
+        parts, shape = path.split("/")[:-1], tuple(shape)
+        if any(t in parts for t in cfg.targets):
+            if len(shape) != 2:
+                raise ValueError(f"LoRA: target matches {path} {shape}, which is not a Dense kernel (convolutions are not adapted"
+                                 + (" by `targets`: name them in conv_targets)" if cfg.conv_rank else ")"))
+            if shape[0] % 8 or shape[1] % 8:
+                raise ValueError(f"LoRA: {path} {shape} is a padded leaf (dims not multiples of 8) and cannot carry an adapter")
+            out.append(path)
+        elif cfg.conv_rank and len(shape) == 4 and any(t in parts for t in cfg.conv_targets):
+            if shape[2] % 8 or shape[3] % 8:
+                raise ValueError(f"LoRA: {path} {shape} is a padded leaf (channel counts not multiples of 8) and cannot carry an adapter")
+            out.append(path)
+            convs += 1
+    if len(out) == convs:
         raise ValueError(f"LoRA: no Dense kernel matches the targets {cfg.targets!r}")
+    if cfg.conv_rank and not convs:
+        raise ValueError(f"LoRA: no convolution kernel matches the conv targets {cfg.conv_targets!r}")
     return out
 
 
+def leaf_factors(shape, cfg):
+    """(K, N, rank, scale) of the adapter of a selected kernel: Dense [K, N] at cfg.rank; HWIO [kh, kw, Cin, Cout] as the matrix
+    [kh*kw*Cin, Cout] at cfg.conv_rank."""
+    if len(shape) == 2:
+        return shape[0], shape[1], cfg.rank, cfg.scale
+    return shape[0] * shape[1] * shape[2], shape[3], cfg.conv_rank, cfg.conv_scale
+
+
 def adapter_spec(spec, cfg):
-    """[(<dense path>/lora_a, (K, r)), (<dense path>/lora_b, (r, N))] for the adapted kernels of `spec`, in its order; with cfg.dora
-    each pair is followed by (<dense path>/lora_m, (N,))."""
+    """[(<layer path>/lora_a, (K, r)), (<layer path>/lora_b, (r, N))] for the adapted kernels of `spec`, in its order (Dense and
+    convolution adapters interleaved as the base runs them); with cfg.dora each pair is followed by (<dense path>/lora_m, (N,))."""
     shapes = dict((p, tuple(s)) for p, s in spec)
     out = []
     for path in select_leaves(spec, cfg):
-        K, N = shapes[path]
+        K, N, r, _ = leaf_factors(shapes[path], cfg)
         dense = path[: -len("/kernel")]
-        out += [(dense + "/lora_a", (K, cfg.rank)), (dense + "/lora_b", (cfg.rank, N))]
+        out += [(dense + "/lora_a", (K, r)), (dense + "/lora_b", (r, N))]
         if cfg.dora:
             out.append((dense + "/lora_m", (N,)))
     return out
@@ -93,10 +141,11 @@ def scratch_runs(leaves, adapted):
     that holds an adapted leaf gets one slot of its own length at `base`, and master element e of the run [start, end) lives at scratch
     element base + e - start: inside a run the masters' distances are kept, a group or a single leaf never straddles two runs, and runs
     without an adapted leaf take no room.  A run that is only partly adapted gets room for all of it (the extra gradients are computed
-    and ignored).  Starts, ends and bases are multiples of 8 elements."""
-    dense = sorted((lf for lf in leaves.values() if lf.path.endswith("/kernel") and lf.batch == 1 and (lf.R, lf.C) == (lf.Rp, lf.Cp)),
-                   key=lambda lf: lf.offset)
-    runs, size = [], 0
+    and ignored).  An adapted convolution kernel (4-D, LoCon) is a run of its own: no merged launch serves convolutions, so it never
+    joins a group.  Starts, ends and bases are multiples of 8 elements; the runs are in master order."""
+    dense = sorted((lf for lf in leaves.values() if lf.path.endswith("/kernel") and len(lf.shape) == 2 and lf.batch == 1
+                    and (lf.R, lf.C) == (lf.Rp, lf.Cp)), key=lambda lf: lf.offset)
+    spans = [(lf.offset, lf.offset + lf.numel) for lf in leaves.values() if len(lf.shape) == 4 and lf.path in adapted]
     i = 0
     while i < len(dense):
         j = i
@@ -104,16 +153,19 @@ def scratch_runs(leaves, adapted):
                and dense[j + 1].offset == dense[j].offset + dense[j].numel):
             j += 1
         if any(lf.path in adapted for lf in dense[i: j + 1]):
-            start, end = dense[i].offset, dense[j].offset + dense[j].numel
-            runs.append((start, end, size))
-            size += (end - start + 7) // 8 * 8
+            spans.append((dense[i].offset, dense[j].offset + dense[j].numel))
         i = j + 1
+    runs, size = [], 0
+    for start, end in sorted(spans):
+        runs.append((start, end, size))
+        size += (end - start + 7) // 8 * 8
     return runs, size
 
 
 class LoraAdapter:
     """What attach() hangs on a frozen store: the trained A / B (/ m) leaves (self.store), the bf16 dW scratch and the job table; for
-    DoRA also the parallel SdtDoraJob table and the column statistics (c, g of every adapted leaf) the merge leaves for the projection."""
+    DoRA also the parallel SdtDoraJob table and the column statistics (c, g of every adapted leaf) the merge leaves for the projection;
+    for LoCon a second job table over the adapted convolution leaves with its SdtLoraSplitJob table and the split projection's workspace."""
 
     def __init__(self, base, cfg, store_kwargs):
         if base.trainable:
@@ -148,14 +200,22 @@ class LoraAdapter:
         dev = base.device
         # dW of every adapted leaf (and of the non-adapted members of a merged group, computed and ignored): scratch_runs' layout
         self.scratch = torch.zeros(size, dtype=torch.bfloat16, device=dev)
-        jobs, dora, tm, tp, sm, so = [], [], 0, 0, 0, 0
-        for p in self.paths:
+        # two job tables: the Dense leaves (self.jobs_host, as without LoCon) and the convolution leaves (self.conv_jobs_host, with the
+        # split table and workspace of sdt_lora_project_split beside it); merge / restore / folded launch once per non-empty table
+        self.dense_paths = [p for p in self.paths if len(base.leaves[p].shape) == 2]
+        self.conv_paths = [p for p in self.paths if len(base.leaves[p].shape) == 4]
+
+        def job(p, tm, tp):
             lf = base.leaves[p]
             la, lb = (self.store.leaves[q] for q in self.adapted[p][:2])
-            K, N = lf.shape
-            ta = (K + 63) // 64
-            jobs.append(_lib.SdtLoraJob(lf.offset, la.offset, lb.offset, lf.w_off, lf.offset, self.scratch_offset(lf.offset, lf.offset + lf.numel), la.offset, lb.offset,
-                                        K, N, cfg.rank, cfg.scale, tm, tp, ta, 0))
+            K, N, r, scale = leaf_factors(lf.shape, cfg)
+            return _lib.SdtLoraJob(lf.offset, la.offset, lb.offset, lf.w_off, lf.offset, self.scratch_offset(lf.offset, lf.offset + lf.numel),
+                                   la.offset, lb.offset, K, N, r, scale, tm, tp, (K + 63) // 64, 0)
+
+        jobs, dora, tm, tp, sm, so = [], [], 0, 0, 0, 0
+        for p in self.dense_paths:
+            jobs.append(job(p, tm, tp))
+            K, N, ta = jobs[-1].K, jobs[-1].N, jobs[-1].tiles_da
             tm += ta * ((N + 63) // 64)
             tp += ta + (N + 63) // 64
             if cfg.dora:
@@ -170,6 +230,29 @@ class LoraAdapter:
             self.dora_host = (_lib.SdtDoraJob * len(dora))(*dora)
             self.dora_dev = torch.frombuffer(bytearray(bytes(self.dora_host)), dtype=torch.uint8).to(dev)
             self.stats = torch.zeros(so, dtype=torch.float32, device=dev)
+        self.conv_jobs_host = self.conv_jobs_dev = self.split_host = self.split_dev = self.split_ws = None
+        if self.conv_paths:
+            rows = _lib.load().sdt_lora_project_split_rows()
+            cjobs, split, tm, tp, ts, cnt, part = [], [], 0, 0, 0, 0, 0
+            for p in self.conv_paths:
+                j = job(p, tm, tp)
+                ta, tb, chunks = j.tiles_da, (j.N + 63) // 64, (j.K + rows - 1) // rows
+                cjobs.append(j)
+                split.append(_lib.SdtLoraSplitJob(part, j.K, j.N, ts, chunks, cnt, 0))
+                tm += ta * tb
+                tp += ta + tb
+                ts += ta + tb * chunks
+                cnt += tb
+                part += tb * chunks * j.r * 64 if chunks > 1 else 0
+            self.conv_jobs_host = (_lib.SdtLoraJob * len(cjobs))(*cjobs)
+            self.split_host = (_lib.SdtLoraSplitJob * len(split))(*split)
+            self.conv_jobs_dev = torch.frombuffer(bytearray(bytes(self.conv_jobs_host)), dtype=torch.uint8).to(dev)
+            self.split_dev = torch.frombuffer(bytearray(bytes(self.split_host)), dtype=torch.uint8).to(dev)
+            need = _lib.load().sdt_lora_project_split_workspace_bytes(self.conv_jobs_host, len(cjobs))
+            if need < 0:
+                raise _lib.SdtError(f"sdt_lora_project_split_workspace_bytes: {_lib.load().sdt_last_error().decode()}")
+            # arrival counters (zero between launches) and partials: allocated once, so that a captured step replays it
+            self.split_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
         self.init_weights()
         base.adapter = self
         if dev.type == "cuda":
@@ -183,7 +266,7 @@ class LoraAdapter:
         tree = {}
         for p in self.paths:
             a, b = self.adapted[p][:2]
-            K, r = self.store.leaves[a].shape
+            K, r = self.store.leaves[a].shape  # (a convolution's K = kh * kw * Cin: the fan-in of its down-convolution)
             tree[a] = (torch.rand(K, r, generator=g) * 2 - 1) / math.sqrt(K)
             tree[b] = torch.zeros(self.store.leaves[b].shape)
             if self.cfg.dora:
@@ -251,6 +334,9 @@ class LoraAdapter:
             return
         _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.jobs_host,
                   self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
+        if self.conv_paths:
+            _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.conv_jobs_host,
+                      self.conv_jobs_dev.data_ptr(), len(self.conv_jobs_host), self._stream())
 
     def restore(self):
         """w[leaf] = bf16(W0) for every adapted leaf (one launch, sdt_lora_restore): the mirror of the store without its adapter, bit
@@ -258,9 +344,13 @@ class LoraAdapter:
         (what a later merge(None) merges) and, for DoRA, self.stats (what project() reads) stay what the last merge left."""
         _lib.call("sdt_lora_restore", self.base.master.data_ptr(), self.base.w.data_ptr(), self.jobs_host, self.jobs_dev.data_ptr(),
                   len(self.jobs_host), self._stream())
+        if self.conv_paths:
+            _lib.call("sdt_lora_restore", self.base.master.data_ptr(), self.base.w.data_ptr(), self.conv_jobs_host,
+                      self.conv_jobs_dev.data_ptr(), len(self.conv_jobs_host), self._stream())
 
     def project(self):
-        """dA, dB of every adapted leaf from the dW scratch into the adapter store's gradient (one launch; written, not accumulated)."""
+        """dA, dB of every adapted leaf from the dW scratch into the adapter store's gradient (one launch; with LoCon a second one,
+        sdt_lora_project_split, for the convolution table; written, not accumulated)."""
         from . import ops
         if self.cfg.dora:  # also dm, from the c and g the step's merge left in self.stats
             _lib.call("sdt_dora_project", self.scratch.data_ptr(), self.base.master.data_ptr(), self.store.master.data_ptr(),
@@ -269,6 +359,10 @@ class LoraAdapter:
         else:
             _lib.call("sdt_lora_project", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), self.jobs_host,
                       self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
+        if self.conv_paths:  # tall K: the dB stripes split along K (include/sdt.h "LoCon")
+            _lib.call("sdt_lora_project_split", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(),
+                      self.conv_jobs_host, self.split_host, self.conv_jobs_dev.data_ptr(), self.split_dev.data_ptr(),
+                      len(self.conv_jobs_host), self.split_ws.data_ptr(), self.split_ws.numel(), self._stream())
         for p in self.paths:
             ops._ready(self.store, *self.adapted[p])
 
@@ -286,6 +380,9 @@ class LoraAdapter:
         else:
             _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), self.jobs_host,
                       self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
+            if self.conv_paths:
+                _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), self.conv_jobs_host,
+                          self.conv_jobs_dev.data_ptr(), len(self.conv_jobs_host), self._stream())
         return {p: buf[lf.offset: lf.offset + lf.numel].view(lf.shape) for p, lf in self.base.leaves.items()}
 
     # ------------------------------------------------------------------ adapter file
@@ -294,17 +391,20 @@ class LoraAdapter:
                     base_shapes={p: list(self.base.leaves[p].shape) for p in self.paths})
         if self.cfg.dora:  # (a LoRA file stays byte for byte what it was)
             meta["dora"] = True
+        if self.cfg.conv_rank:
+            meta.update(conv_rank=int(self.cfg.conv_rank), conv_alpha=float(self.cfg.conv_scale * self.cfg.conv_rank),
+                        conv_targets=list(self.cfg.conv_targets))
         return meta
 
     def save(self, path, which="master"):
         """One .npz: the A / B (/ m) leaves (fp32) and __meta__ (JSON: rank, alpha, targets, the adapted base kernels' shapes, and
-        "dora": true for a DoRA adapter)."""
+        "dora": true for a DoRA adapter, conv_rank / conv_alpha / conv_targets for a LoCon adapter)."""
         tree = self.store.export_host(which)
         with open(path, "wb") as f:
             np.savez(f, __meta__=np.frombuffer(json.dumps(self._meta()).encode(), dtype=np.uint8), **{p: np.asarray(v) for p, v in tree.items()})
 
     def load(self, path):
-        """Inverse of save().  ValueError naming the mismatch for a file of another rank, another alpha, other targets or other base shapes."""
+        """Inverse of save().  ValueError naming the mismatch for a file of another rank, another alpha, other targets, another conv_rank / conv_alpha / conv_targets or other base shapes."""
         with np.load(path) as z:
             if "__meta__" not in z.files:
                 raise ValueError(f"{path}: not an adapter file (no __meta__)")
@@ -321,6 +421,16 @@ class LoraAdapter:
             if float(meta["alpha"]) != mine["alpha"]:
                 raise ValueError(f"{path}: adapter trained with alpha {meta['alpha']}, this adapter has alpha {mine['alpha']} (the factors "
                                  "mean another delta under another scale: attach with the file's alpha)")
+            if int(meta.get("conv_rank", 0)) != mine.get("conv_rank", 0):
+                raise ValueError(f"{path}: adapter of conv_rank {int(meta.get('conv_rank', 0))}, this adapter has conv_rank "
+                                 f"{mine.get('conv_rank', 0)}")
+            if mine.get("conv_rank", 0):
+                if list(meta["conv_targets"]) != mine["conv_targets"]:
+                    raise ValueError(f"{path}: adapter for conv_targets {meta['conv_targets']}, this adapter has conv_targets "
+                                     f"{mine['conv_targets']}")
+                if float(meta["conv_alpha"]) != mine["conv_alpha"]:
+                    raise ValueError(f"{path}: adapter trained with conv_alpha {meta['conv_alpha']}, this adapter has conv_alpha "
+                                     f"{mine['conv_alpha']} (attach with the file's conv_alpha)")
             if meta["base_shapes"] != mine["base_shapes"]:
                 a, b = meta["base_shapes"], mine["base_shapes"]
                 bad = sorted(set(a) ^ set(b)) or [p for p in b if a[p] != b[p]]
@@ -335,7 +445,7 @@ class LoraAdapter:
 def attach(base_store, cfg, **store_kwargs):
     """Hang a LoRA adapter on the frozen `base_store`.  store_kwargs configure the adapter's own ParamStore (quantise, quant_excluded,
     wd_excluded, block_size, with_ema, optimizer, adam_betas, prodigy).  ValueError: a trained base, a target that matches a convolution or a
-    padded kernel, no matching leaf, an invalid rank."""
+    padded kernel, no matching leaf (Dense, or with conv_rank > 0 convolution), an invalid rank."""
     if not isinstance(cfg, LoraConfig):
         raise ValueError(f"attach: cfg must be a LoraConfig, not {type(cfg).__name__}")
     return LoraAdapter(base_store, cfg, store_kwargs)

@@ -445,7 +445,7 @@ def colsum(dy, db, M, N, ld):
 
 
 def _wgrad_dest(store, wpaths):
-    """Where the weight gradient of the Dense kernels `wpaths` (one leaf, or the leaves of a merged launch) goes: None when there is
+    """Where the weight gradient of the kernels `wpaths` (one Dense or convolution leaf, or the Dense leaves of a merged launch) goes: None when there is
     none (a frozen store), else (view, with_bias, book) - view(a, b): the destination of master elements [a, b); with_bias: the biases'
     gradients are produced too; book: the store the launch reports to (squared-norm slots, single-use check, reducer) or None.
     A trained store answers with its own gradient buffers.  A frozen store with a LoRA adapter (lora.attach) answers with the adapter's
@@ -642,12 +642,16 @@ class _Conv2d(Function):
             dx = torch.empty_like(x)
             gemm_nt(dy, W, dx, B * H * Wd, lf.Rp, lf.Cp, taps, lf.Cp, lf.Cp, lf.Rp * lf.Cp,
                     mode=GATHER_PLAIN if plain else GATHER_DGRAD, geom=None if plain else geom)
-        if store.trainable and plain:  # 1x1: a Dense layer over the pixels
-            wgrad_dense(x, dy, store.g(wpath), M_out, lf.Rp, lf.Cp, lf.R, lf.C, lf.Rp, lf.Cp,
-                        dbias=store.g(bpath) if bpath is not None else None, store=store, paths=(wpath, bpath))
-        elif store.trainable:
-            wgrad_conv(x, dy, store.g(wpath), geom, lf, taps, M_out, dbias=store.g(bpath) if bpath is not None else None,
-                       store=store, paths=(wpath, bpath))
+        dest = _wgrad_dest(store, (wpath,))  # a trained store's own gradient, or a LoCon adapter's bf16 scratch (no bias, no bookkeeping)
+        if dest is not None:
+            view, with_bias, book = dest
+            dW = _leaf_grad(view, lf)
+            db = store.g(bpath) if (bpath is not None and with_bias) else None
+            paths = (wpath, bpath) if book is not None else ()
+            if plain:  # 1x1: a Dense layer over the pixels
+                wgrad_dense(x, dy, dW, M_out, lf.Rp, lf.Cp, lf.R, lf.C, lf.Rp, lf.Cp, dbias=db, store=book, paths=paths)
+            else:
+                wgrad_conv(x, dy, dW, geom, lf, taps, M_out, dbias=db, store=book, paths=paths)
         drb = None
         if has_rb:  # gradient of the broadcast (B, Cout) row bias = per-image column sums (ordered partial sums, one launch)
             drb = torch.empty(B, lf.Cp, dtype=BF16, device=x.device)
