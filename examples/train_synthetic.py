@@ -42,7 +42,9 @@ model beside the adapted one (train_step dpo_beta=; diffusers trains SD1.5 / SDX
 implicit_acc, the share of pairs the adapter ranks like the data.
 --lora-conv R [--lora-conv-alpha A] ("lora_conv_rank", "lora_conv_alpha"; needs --lora RANK, refused with --dora): LoCon - rank-R adapters
 also on the UNet's convolutions (ResNet conv1 / conv2 / conv_shortcut, the samplers' conv, SD1.5's 1x1 proj_in / proj_out), alpha A
-(default R): kohya's conv_dim / conv_alpha."""
+(default R): kohya's conv_dim / conv_alpha.
+--loha ("lora_algo": "loha"; needs --lora RANK, optionally --lora-conv R; ranks up to 32; refused with --dora): LoHa - every adapted kernel
+carries four factors and the delta (alpha / rank) * (A1 B1) o (A2 B2), LyCORIS' algo=loha without Tucker."""
 import argparse
 import json
 import os
@@ -100,6 +102,11 @@ def lora_config(config_dict, world=1):
         raise ValueError("lora_conv_rank: LoCon adapts the convolutions beside the attention projections - give lora_rank (--lora RANK --lora-conv R)")
     if config_dict.get("lora_conv_alpha") is not None and not config_dict.get("lora_conv_rank"):
         raise ValueError("lora_conv_alpha needs lora_conv_rank (--lora-conv R --lora-conv-alpha A)")
+    algo = config_dict.get("lora_algo", "lora")
+    if algo != "lora" and not config_dict.get("lora_rank"):
+        raise ValueError("lora_algo: LoHa adapts the kernels --lora names - give lora_rank (--lora RANK --loha)")
+    if algo == "loha" and config_dict.get("lora_dora"):
+        raise ValueError("lora_algo: DoRA combined with LoHa is not supported (--loha with --dora)")
     if not config_dict.get("lora_rank"):
         return None
     if world > 1:
@@ -109,6 +116,8 @@ def lora_config(config_dict, world=1):
     if config_dict.get("lora_conv_rank"):
         conv = dict(conv_rank=int(config_dict["lora_conv_rank"]),
                     conv_alpha=None if config_dict.get("lora_conv_alpha") is None else float(config_dict["lora_conv_alpha"]))
+    if algo != "lora":  # (without it the configuration is what it was)
+        conv["algo"] = algo
     return dict(unet=lora.LoraConfig(r, float(config_dict.get("lora_alpha", r)), dora=bool(config_dict.get("lora_dora", False)), **conv),
                 text_encoder="frozen")
 
@@ -357,6 +366,8 @@ if __name__ == "__main__":
     ap.add_argument("--lora-conv", metavar="R", type=int, default=None,
                     help="with --lora: LoCon - also train rank-R adapters on the UNet's convolutions (kohya conv_dim); not with --dora")
     ap.add_argument("--lora-conv-alpha", metavar="A", type=float, default=None, help="with --lora-conv: the conv adapters' alpha (default R)")
+    ap.add_argument("--loha", action="store_true",
+                    help="with --lora (and --lora-conv): LoHa - Hadamard-product adapters, ranks up to 32 (LyCORIS algo=loha); not with --dora")
     ap.add_argument("--dpo", metavar="BETA", type=float, default=None,
                     help="with --lora: Diffusion-DPO preference training on (preferred, rejected) pairs against the frozen base (diffusers: 5000)")
     ap.add_argument("--new-tokens", metavar="N", type=int, default=None,
@@ -385,6 +396,10 @@ if __name__ == "__main__":
         ap.error("--dora needs --lora RANK")
     if args.lora_conv is not None and args.lora is None:
         ap.error("--lora-conv needs --lora RANK")
+    if args.loha and args.lora is None:
+        ap.error("--loha needs --lora RANK")
+    if args.loha and args.dora:
+        ap.error("--loha is refused beside --dora (DoRA combined with LoHa is not supported)")
     if args.lora_conv_alpha is not None and args.lora_conv is None:
         ap.error("--lora-conv-alpha needs --lora-conv R")
     if args.dpo is not None and args.lora is None:
@@ -403,6 +418,8 @@ if __name__ == "__main__":
         cfg["lora_dora"] = True
     if args.lora_conv is not None:
         cfg["lora_conv_rank"] = args.lora_conv
+    if args.loha:
+        cfg["lora_algo"] = "loha"
     if args.lora_conv_alpha is not None:
         cfg["lora_conv_alpha"] = args.lora_conv_alpha
     if args.new_tokens is not None:

@@ -781,6 +781,49 @@ int sdt_lora_project_split(const uint16_t* dw_base, const float* ab_base, float*
                            const SdtLoraSplitJob* split_host, const void* jobs_device, const void* split_device, int n, void* workspace,
                            int64_t workspace_bytes, hipStream_t stream);
 
+/* ---- LoHa: Hadamard-product adapters (LyCORIS LoHa without Tucker; FedPara, Hyeon-Woo et al. 2021; DESIGN.md "LoHa") ----
+ * An adapted kernel W0 [K][N] - Dense, or an HWIO convolution seen as [kh*kw*Cin][Cout] exactly as LoCon sees it - carries FOUR trained
+ * fp32 leaves, in this order in the adapter store: loha_a1 [K][r], loha_b1 [r][N], loha_a2 [K][r], loha_b2 [r][N], and
+ *   dW = s * (A1 B1) o (A2 B2)          (o element-wise, s = alpha / r; LyCORIS: A_i = hada_w{i}_b^T, B_i = hada_w{i}_a^T)
+ * which reaches rank r^2 and is no low-rank product.  With P_i[k][n] = sum_q bf16(A_i[k][q]) * bf16(B_i[q][n]) - operands rounded RNE as
+ * they are loaded, fp32 accumulation by ONE mfma_f32_16x16x32_bf16 K-step with r padded by zero lanes, hence r in {4, 8, 16, 32}:
+ *   merge    h = fl(P1 * P2);  t = fl(s * h);  v = fl(W0 + t)   - three fp32 roundings in this order, nothing contracted.
+ *            w_bf16 (or NULL) receives RNE(v) with 16-byte stores, f32_dst (or NULL) v itself, as sdt_lora_merge: the folded
+ *            checkpoint's bf16 rounding is the training mirror bit for bit.  sdt_lora_restore serves a LoHa table as it stands.
+ *   project  G1 = bf16_rne(fl(dW * P2)),  G2 = bf16_rne(fl(dW * P1))   (dW bf16; one fp32 product, rounded once more to bf16 because it
+ *            becomes an MFMA operand: unit roundoff 2^-8, the one rounding LoRA's projection does not have)
+ *            dA_i[k][q] = fl(s * sum_n G_i[k][n] * bf16(B_i[q][n]))      dB_i[q][n] = fl(s * sum_k bf16(A_i[k][q]) * G_i[k][n])
+ *            WRITTEN as fp32: the gradient of the function the merge evaluated, the operands' bf16 rounding passed straight through
+ *            as in sdt_lora_project.  P is never written anywhere: a P block leaves the MFMA with its 16 rows standing for the
+ *            contraction elements 8 (m >> 2) + 4 b + (m & 3) (dB) or 2 m + b (dA), b = 0, 1, so that a lane's accumulator registers are
+ *            the eight elements its operand fragment holds, and G is formed in registers.
+ *            dA: ceil(K/64) row stripes walk N.  dB: ALWAYS the LoCon split protocol, for Dense tables too - 64-column stripes cut along K
+ *            into chunks of sdt_lora_project_split_rows() rows, one workgroup per (stripe, chunk) accumulates dB1 and dB2 in row
+ *            order; chunks == 1 writes fl(s * acc) directly, otherwise fp32 partials, the integer arrival counter, and the last
+ *            arriver adds the partials in chunk order 0, 1, 2, ... and writes fl(s * sum).  dW is read twice, as LoRA reads it.
+ * No float atomics, one writer and one summation order per element: the same bits whether a job is alone or anywhere in any table, and
+ * on every repeated call.
+ * Tables: the SdtLoraJob table (unchanged; a_off, b_off, ga_off, gb_off name side 1), the SdtLoraSplitJob table exactly as
+ * sdt_lora_project_split takes it (its part_off keeps LoCon's one-set count and is checked as there, but not used), and a parallel table
+ * of n SdtLohaJob.  All host copies are checked before any HIP call: sdt_lora_merge's checks; r <= 32; K, N equal across the tables;
+ * LoHa offsets non-negative multiples of 8; the running tile, counter and partial counts; the workspace size.  n == 0 launches nothing.
+ * Workspace (16-byte aligned, sdt_loha_project_workspace_bytes(jobs_host, n) bytes; -1 for a refused table): the counters of
+ * sdt_lora_project_split - ZERO on entry, zero again on exit - followed by TWO partial sets per job with chunks > 1:
+ * 2 * stripes * chunks * r * 64 floats, the slab of a (stripe, chunk) being [r][64] of dB1, then [r][64] of dB2. */
+typedef struct SdtLohaJob {
+  int64_t a2_off, b2_off;   /* A2, B2 in ab_base */
+  int64_t ga2_off, gb2_off; /* dA2, dB2 in grad_base */
+  int64_t part_off;         /* first partial of the job, in floats behind the counters: the running count of two-set partials */
+  int32_t K, N;             /* the job's K and N again: a table built for other leaves is refused */
+} SdtLohaJob;
+int sdt_loha_job_size(void);
+int sdt_loha_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, const SdtLoraJob* jobs_host,
+                   const SdtLohaJob* loha_host, const void* jobs_device, const void* loha_device, int n, hipStream_t stream);
+int64_t sdt_loha_project_workspace_bytes(const SdtLoraJob* jobs_host, int n);
+int sdt_loha_project(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
+                     const SdtLoraSplitJob* split_host, const SdtLohaJob* loha_host, const void* jobs_device, const void* split_device,
+                     const void* loha_device, int n, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+
 /* ---- test hooks (not for the training path) ----
  * Output channels per tile of the 3x3 halo convolution inside sdt_gemm_nt_bf16: 64 (the default) or 128 (the reference of the
  * bitwise parity test).  Process-wide, not thread-safe; launches already enqueued keep the width they were planned with.

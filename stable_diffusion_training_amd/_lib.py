@@ -52,6 +52,10 @@ class SdtLoraSplitJob(ctypes.Structure):
     _fields_ = [("part_off", _L), ("K", _I), ("N", _I), ("tile0", _I), ("chunks", _I), ("cnt0", _I), ("reserved", _I)]
 
 
+class SdtLohaJob(ctypes.Structure):
+    _fields_ = [(n, _L) for n in ("a2_off", "b2_off", "ga2_off", "gb2_off", "part_off")] + [("K", _I), ("N", _I)]
+
+
 GATHER_PLAIN, GATHER_FPROP, GATHER_DGRAD = 0, 1, 2
 ACT_SILU, ACT_QUICK_GELU, ACT_GELU_ERF = 0, 1, 2
 
@@ -135,6 +139,8 @@ SIGNATURES = {
     "sdt_lora_restore": [_P, _P, _P, _P, _I, _P],
     "sdt_lora_project": [_P, _P, _P, _P, _P, _I, _P],
     "sdt_lora_project_split": [_P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
+    "sdt_loha_merge": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
+    "sdt_loha_project": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _L, _P],
     "sdt_dora_merge": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
     "sdt_dora_init_magnitude": [_P, _P, _P, _P, _P, _P, _P, _I, _P],
     "sdt_dora_project": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P],
@@ -153,8 +159,9 @@ WS_QUERY = {"sdt_gemm_nt_workspace_bytes": [_L, _I, _I, _I], "sdt_gemm_tn_worksp
             "sdt_ip_attention_bwd_workspace_bytes": [_I, _I, _I, _I, _I],
             "sdt_gemm_tn_wgrad_group_workspace_bytes": [_P, _I], "sdt_conv_wgrad_group_workspace_bytes": [_P, _I], "sdt_reduce_workspace_bytes": [], "sdt_dpo_loss_workspace_bytes": [_I, _I, _I], "sdt_sqnorm_workspace_bytes": [], "sdt_prodigy_workspace_bytes": [], "sdt_colsum_workspace_bytes": [_I, _L, _I],
             "sdt_lora_project_split_workspace_bytes": [_P, _I],
+            "sdt_loha_project_workspace_bytes": [_P, _I],
             "sdt_wgrad_sq_slots": [_I, _I, _I]}
-NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_lora_job_size": _I, "sdt_dora_job_size": _I, "sdt_lora_split_job_size": _I, "sdt_lora_project_split_rows": _I, "sdt_last_error": ctypes.c_char_p}
+NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_lora_job_size": _I, "sdt_dora_job_size": _I, "sdt_lora_split_job_size": _I, "sdt_lora_project_split_rows": _I, "sdt_loha_job_size": _I, "sdt_last_error": ctypes.c_char_p}
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libsdtrain_hip.so")
 if os.environ.get("SDT_LIB"):  # developer A/B of two builds on one box (tools/ab_libs.sh): another in-tree build of the same sources
@@ -198,6 +205,8 @@ def load():
         raise SdtError("SdtDoraJob layout mismatch between _lib.py and the library")
     if lib.sdt_lora_split_job_size() != ctypes.sizeof(SdtLoraSplitJob):
         raise SdtError("SdtLoraSplitJob layout mismatch between _lib.py and the library")
+    if lib.sdt_loha_job_size() != ctypes.sizeof(SdtLohaJob):
+        raise SdtError("SdtLohaJob layout mismatch between _lib.py and the library")
     _lib = lib
     return lib
 

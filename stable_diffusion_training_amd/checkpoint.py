@@ -496,7 +496,8 @@ def _tokens_meta(st):
 
 
 def _lora_meta(ad):
-    return f"rank={ad.cfg.rank};alpha={float(ad.cfg.alpha)!r};targets={','.join(ad.cfg.targets)}" + (";dora=1" if ad.cfg.dora else "")
+    return f"rank={ad.cfg.rank};alpha={float(ad.cfg.alpha)!r};targets={','.join(ad.cfg.targets)}" + (";dora=1" if ad.cfg.dora else "") + (
+        f";algo={ad.cfg.algo}" if ad.cfg.algo != "lora" else "")
 
 
 def save_training_state(path, unet_state, text_encoder_state, train_rng=None, rng_states=None):

@@ -5,6 +5,8 @@
 // mfma_f32_16x16x32_bf16 and neither uses an atomic: every output element has one writer and one fixed summation order.
 // The split projection (include/sdt.h "LoCon") serves the tall K of convolution kernels: its dB stripes are cut along K, and the only
 // atomic is the integer arrival counter behind which the last workgroup of a stripe adds the fp32 partials in chunk order.
+// LoHa (include/sdt.h "LoHa"): the delta s * (A1 B1) o (A2 B2), element-wise - a fused merge and a fused projection that form the rank-r
+// products beside each tile and never write them; its dB stripes always take the split.
 //
 // Operand lane maps of mfma_f32_16x16x32_bf16 (lane l): A[row l&15][k = 8(l>>4) + j], B[k = 8(l>>4) + j][col l&15], j = 0..7;
 // C/D col = l&15, row = 4(l>>4) + reg.
@@ -536,6 +538,260 @@ __global__ void __launch_bounds__(256) lora_project_split_kernel(const bf16_t* _
   }
 }
 
+// ---- LoHa (include/sdt.h "LoHa"): dW = s * (A1 B1) o (A2 B2), r <= 32 so that ONE MFMA K-step forms a 16 x 16 block of P_i = bf16(A_i)
+// bf16(B_i).  The accumulator layout gives a lane 4 rows of one column, the operand layout wants 8 consecutive contraction elements:
+// nothing is moved.  The 16 MFMA rows of a P block are made to stand for contraction elements 8 (m >> 2) + 4 b + (m & 3), b = 0, 1 -
+// the factor rows are gathered in that order - so the accumulator registers i = 0..3 of blocks b = 0, 1 ARE elements 8 (lane >> 4) +
+// 4 b + i of the lane's own row / column: the eight the operand fragment holds.  G_i = bf16(dW * P_other) is formed in registers.
+// rows X[row][8 lq .. 8 lq + 7] of a factor X [rows][r] as an operand fragment (r in {4, 8, 16, 32}; lanes with q >= r are zero)
+__device__ __forceinline__ bf16x8_t loha_rows_frag(const float* __restrict__ X, int r, long row, bool ok, int lq) {
+  return r == 4 ? frag_from_f32x4(X + row * 4, ok && lq == 0) : frag_from_f32(X + row * r + 8 * lq, ok && 8 * lq < r);
+}
+// X[8 lq + j][col], j = 0..7, of a factor X [r][N]
+__device__ __forceinline__ bf16x8_t loha_cols_frag(const float* __restrict__ X, int r, int N, int col, bool ok, int lq) {
+  return frag_from_f32_strided(X + (long)(8 * lq) * N + col, N, 8 * lq, r, ok);
+}
+// X[8 lq + j][col] into f0 and X[8 lq + j][col + 1] into f1, j = 0..7, from 8-byte loads (col even; N a multiple of 8: a pair is whole or
+// absent): the fragments of two P^T blocks whose MFMA rows interleave, row m of block b standing for column col0 + 2 m + b
+__device__ __forceinline__ void loha_col_pairs(const float* __restrict__ X, int r, int N, int col, bool ok, int lq, bf16x8_t& f0,
+                                               bf16x8_t& f1) {
+  float a[8], b[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float2 v = {0.f, 0.f};
+    if (ok && 8 * lq + j < r) v = *reinterpret_cast<const float2*>(X + (long)(8 * lq + j) * N + col);
+    a[j] = v.x;
+    b[j] = v.y;
+  }
+  const uint4 u0 = pack8(a), u1 = pack8(b);
+  f0 = __builtin_bit_cast(bf16x8_t, u0);
+  f1 = __builtin_bit_cast(bf16x8_t, u1);
+}
+__device__ __forceinline__ f32x4_t loha_block(bf16x8_t a, bf16x8_t b) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+}
+
+// merge: lora_merge_kernel's tiles and runs; h = fl(P1 * P2) in registers, then merged_run's v = fl(W0 + fl(s * h))
+__global__ void __launch_bounds__(256) loha_merge_kernel(const float* __restrict__ w0_base, const float* __restrict__ ab_base,
+                                                         bf16_t* __restrict__ w_dst, float* __restrict__ f_dst,
+                                                         const SdtLoraJob* __restrict__ jobs, const SdtLohaJob* __restrict__ xj, int njobs) {
+  __shared__ float tile[LT][LT + 4];
+  const int job = find_job_index(jobs, njobs, blockIdx.x, false);
+  const SdtLoraJob d = jobs[job];
+  const SdtLohaJob x = xj[job];
+  const int tl = blockIdx.x - d.tile0_merge;
+  const int tc = (d.N + LT - 1) / LT;
+  const int r0 = (tl / tc) * LT, c0 = (tl % tc) * LT;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const float *B1 = ab_base + d.b_off, *B2 = ab_base + x.b2_off;
+  const int arow = r0 + 16 * wave + l15;
+  const bf16x8_t a1 = loha_rows_frag(ab_base + d.a_off, d.r, arow, arow < d.K, lq);
+  const bf16x8_t a2 = loha_rows_frag(ab_base + x.a2_off, d.r, arow, arow < d.K, lq);
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const int col = c0 + 16 * c + l15;
+    const f32x4_t p1 = loha_block(a1, loha_cols_frag(B1, d.r, d.N, col, col < d.N, lq));
+    const f32x4_t p2 = loha_block(a2, loha_cols_frag(B2, d.r, d.N, col, col < d.N, lq));
+#pragma unroll
+    for (int i = 0; i < 4; ++i) tile[16 * wave + 4 * lq + i][16 * c + l15] = p1[i] * p2[i];
+  }
+  __syncthreads();
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {  // 512 runs of 8 columns
+    float v[8];
+    long e;
+    if (merged_run(d, w0_base, tile, threadIdx.x + 256 * it, r0, c0, v, e)) store_run(d, w_dst, f_dst, e, v);
+  }
+}
+
+struct LohaSides {
+  const float *A1, *B1, *A2, *B2;
+  float *gA1, *gB1, *gA2, *gB2;
+};
+
+// G1 = bf16(w * p2), G2 = bf16(w * p1) for the lane's eight contraction elements: w = dW widened, p[b][i] element 4 b + i, or with
+// PAIRS (interleaved blocks) element 2 i + b
+template <bool PAIRS>
+__device__ __forceinline__ void loha_g_frags(const float* w, const f32x4_t* p1, const f32x4_t* p2, bf16x8_t& G1, bf16x8_t& G2) {
+  float g1[8], g2[8];
+#pragma unroll
+  for (int b = 0; b < 2; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int j = PAIRS ? 2 * i + b : 4 * b + i;
+      g1[j] = w[j] * p2[b][i];
+      g2[j] = w[j] * p1[b][i];
+    }
+  const uint4 u1 = pack8(g1), u2 = pack8(g2);
+  G1 = __builtin_bit_cast(bf16x8_t, u1);
+  G2 = __builtin_bit_cast(bf16x8_t, u2);
+}
+
+// one 64-row stripe of dA1 and dA2: a wave owns 16 rows and walks N, 32 columns a step.  P^T blocks: A operand the B_i columns (MFMA
+// row m of block b stands for column n0 + 2 m + b - the interleaved form of the trick above: registers i of blocks b are elements 2 i + b
+// of the lane's eight, and a lane fetches both blocks' values with one 8-byte load, 16 lanes a contiguous 128 bytes), B operand the
+// lane's own A_i row, loaded once per stripe.
+template <int RB>
+__device__ __forceinline__ void loha_da_stripe(const SdtLoraJob& d, const LohaSides& o, int tl, const bf16_t* __restrict__ dW) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const int r = d.r, K = d.K, N = d.N;
+  const float s = d.scale;
+  f32x4_t acc1[RB], acc2[RB];
+#pragma unroll
+  for (int b = 0; b < RB; ++b) acc1[b] = acc2[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  const int row = tl * LT + 16 * wave + l15;
+  const bf16x8_t at1 = loha_rows_frag(o.A1, r, row, row < K, lq), at2 = loha_rows_frag(o.A2, r, row, row < K, lq);
+  for (int n0 = 0; n0 < N; n0 += 32) {
+    const int n = n0 + 8 * lq;
+    uint4 v = {0u, 0u, 0u, 0u};
+    if (row < K && n < N) v = *reinterpret_cast<const uint4*>(dW + (long)row * N + n);
+    float w[8];
+    unpack8(v, w);
+    f32x4_t p1[2], p2[2];
+    {
+      const int np = n0 + 2 * l15;
+      bf16x8_t f0, f1;
+      loha_col_pairs(o.B1, r, N, np, np < N, lq, f0, f1);
+      p1[0] = loha_block(f0, at1);
+      p1[1] = loha_block(f1, at1);
+      loha_col_pairs(o.B2, r, N, np, np < N, lq, f0, f1);
+      p2[0] = loha_block(f0, at2);
+      p2[1] = loha_block(f1, at2);
+    }
+    bf16x8_t G1, G2;
+    loha_g_frags<true>(w, p1, p2, G1, G2);
+#pragma unroll
+    for (int b = 0; b < RB; ++b) {
+      const int q = 16 * b + l15;
+      acc1[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(G1, frag_from_f32(o.B1 + (long)q * N + n, q < r && n < N), acc1[b], 0, 0, 0);
+      acc2[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(G2, frag_from_f32(o.B2 + (long)q * N + n, q < r && n < N), acc2[b], 0, 0, 0);
+    }
+  }
+#pragma unroll
+  for (int b = 0; b < RB; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int k = tl * LT + 16 * wave + 4 * lq + i, q = 16 * b + l15;
+      if (k < K && q < r) {
+        o.gA1[(long)k * r + q] = s * acc1[b][i];
+        o.gA2[(long)k * r + q] = s * acc2[b][i];
+      }
+    }
+}
+
+// one (stripe, chunk) of dB1 and dB2: project_db_chunk's staging, chunking and arrival protocol.  P blocks: A operand the A_i rows (MFMA
+// row m stands for row k0 + 8 (m >> 2) + 4 b + (m & 3)), B operand the lane's own B_i column, loaded once per chunk.  A partial slab
+// holds both sets: [r][64] of dB1, then [r][64] of dB2.
+template <int RB>
+__device__ __forceinline__ void loha_db_chunk(const SdtLoraJob& d, const SdtLoraSplitJob& x, const LohaSides& o, long part_off, int stripe,
+                                              int chunk, const bf16_t* __restrict__ dW, int* __restrict__ counters,
+                                              float* __restrict__ parts, bf16_t (*stage)[32][LT + 8], int* s_flag) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const int r = d.r, K = d.K, N = d.N;
+  const float s = d.scale;
+  const int c0 = stripe * LT;
+  const int kb = chunk * SPLIT_ROWS, ke = min(K, kb + SPLIT_ROWS);
+  const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;  // one 16-byte load per thread stages 32 rows x 64 columns
+  const bool col_ok = c0 + scol < N;
+  const int ncol = c0 + 16 * wave + l15;
+  const bf16x8_t bc1 = loha_cols_frag(o.B1, r, N, ncol, ncol < N, lq), bc2 = loha_cols_frag(o.B2, r, N, ncol, ncol < N, lq);
+  const int kl = 8 * (l15 >> 2) + (l15 & 3);
+  f32x4_t acc1[RB], acc2[RB];
+#pragma unroll
+  for (int b = 0; b < RB; ++b) acc1[b] = acc2[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  uint4 v = {0u, 0u, 0u, 0u};
+  if (kb + srow < ke && col_ok) v = *reinterpret_cast<const uint4*>(dW + (long)(kb + srow) * N + c0 + scol);
+  *reinterpret_cast<uint4*>(&stage[0][srow][scol]) = v;
+  __syncthreads();
+  int cur = 0;
+  for (int k0 = kb; k0 < ke; k0 += 32, cur ^= 1) {
+    const bool more = k0 + 32 < ke;
+    uint4 nv = {0u, 0u, 0u, 0u};
+    if (more && k0 + 32 + srow < ke && col_ok) nv = *reinterpret_cast<const uint4*>(dW + (long)(k0 + 32 + srow) * N + c0 + scol);
+    const int k = k0 + 8 * lq;
+    float w[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) w[j] = bf2f(stage[cur][8 * lq + j][16 * wave + l15]);
+    f32x4_t p1[2], p2[2];
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const int kp = k0 + kl + 4 * b;
+      p1[b] = loha_block(loha_rows_frag(o.A1, r, kp, kp < ke, lq), bc1);
+      p2[b] = loha_block(loha_rows_frag(o.A2, r, kp, kp < ke, lq), bc2);
+    }
+    bf16x8_t G1, G2;
+    loha_g_frags<false>(w, p1, p2, G1, G2);
+#pragma unroll
+    for (int b = 0; b < RB; ++b) {
+      const int q = 16 * b + l15;
+      acc1[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_from_f32_strided(o.A1 + (long)k * r + q, r, k, ke, q < r), G1, acc1[b], 0, 0, 0);
+      acc2[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_from_f32_strided(o.A2 + (long)k * r + q, r, k, ke, q < r), G2, acc2[b], 0, 0, 0);
+    }
+    if (more) *reinterpret_cast<uint4*>(&stage[cur ^ 1][srow][scol]) = nv;  // (its readers finished in front of the last barrier)
+    __syncthreads();
+  }
+  if (x.chunks == 1) {
+#pragma unroll
+    for (int b = 0; b < RB; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int q = 16 * b + 4 * lq + i;
+        if (q < r && ncol < N) {
+          o.gB1[(long)q * N + ncol] = s * acc1[b][i];
+          o.gB2[(long)q * N + ncol] = s * acc2[b][i];
+        }
+      }
+    return;
+  }
+  const long side = (long)r * LT, slab = 2 * side;  // floats of one set / of one workgroup's partial
+  float* mine = parts + part_off + ((long)stripe * x.chunks + chunk) * slab;
+#pragma unroll
+  for (int b = 0; b < RB; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int q = 16 * b + 4 * lq + i;
+      if (q < r) {
+        sdt_store_wt(mine + (long)q * LT + 16 * wave + l15, acc1[b][i]);
+        sdt_store_wt(mine + side + (long)q * LT + 16 * wave + l15, acc2[b][i]);
+      }
+    }
+  if (!sdt_arrive_last<true>(counters + x.cnt0 + stripe, x.chunks, s_flag)) return;
+  const float* first = parts + part_off + (long)stripe * x.chunks * slab;
+  for (int e = threadIdx.x; e < (int)slab; e += 256) {
+    const bool two = e >= (int)side;
+    const int ee = two ? e - (int)side : e;
+    const int q = ee >> 6, n = c0 + (ee & 63);
+    if (n >= N) continue;
+    float sum = sdt_load_wt(first + e);
+    for (int c = 1; c < x.chunks; ++c) sum += sdt_load_wt(first + c * slab + e);
+    (two ? o.gB2 : o.gB1)[(long)q * N + n] = s * sum;
+  }
+}
+
+// (4 waves per SIMD: without the request the allocator takes 131 registers where 119 do, and a fourth workgroup per CU hides the gathers)
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) loha_project_kernel(const bf16_t* __restrict__ dw_base, const float* __restrict__ ab_base,
+                                                           float* __restrict__ grad_base, const SdtLoraJob* __restrict__ jobs,
+                                                           const SdtLoraSplitJob* __restrict__ sj, const SdtLohaJob* __restrict__ xj,
+                                                           int njobs, int* __restrict__ counters, float* __restrict__ parts) {
+  __shared__ __attribute__((aligned(16))) bf16_t stage[2][32][LT + 8];
+  __shared__ int s_flag;
+  const int job = find_index(njobs, blockIdx.x, [=](int i) { return sj[i].tile0; });
+  const SdtLoraJob d = jobs[job];
+  const SdtLoraSplitJob x = sj[job];
+  const SdtLohaJob h = xj[job];
+  const int tl = blockIdx.x - x.tile0;
+  const bf16_t* dW = dw_base + d.dw_off;
+  const LohaSides o = {ab_base + d.a_off,    ab_base + d.b_off,    ab_base + h.a2_off,    ab_base + h.b2_off,
+                       grad_base + d.ga_off, grad_base + d.gb_off, grad_base + h.ga2_off, grad_base + h.gb2_off};
+  if (tl < d.tiles_da) {
+    if (d.r <= 16) loha_da_stripe<1>(d, o, tl, dW); else loha_da_stripe<2>(d, o, tl, dW);  // (workgroup-uniform)
+    return;
+  }
+  const int t = tl - d.tiles_da, stripe = t / x.chunks, chunk = t % x.chunks;
+  if (d.r <= 16) loha_db_chunk<1>(d, x, o, h.part_off, stripe, chunk, dW, counters, parts, stage, &s_flag);
+  else loha_db_chunk<2>(d, x, o, h.part_off, stripe, chunk, dW, counters, parts, stage, &s_flag);
+}
+
 // Host check of the table (the host copy; the device copy must hold the same bytes).  Returns the number of tiles or -1.
 long check_jobs(const char* name, const SdtLoraJob* h, int n, bool project) {
   long tiles = 0;
@@ -635,6 +891,37 @@ long check_split_jobs(const char* name, const SdtLoraJob* h, const SdtLoraSplitJ
 }
 inline long split_counter_bytes(long counters) { return (counters * 4 + 255) / 256 * 256; }
 
+// The LoHa table beside the job table (host copies): ranks up to 32, K / N equal, side-2 offsets, the running offset of the two-set
+// partials.  Returns the partial floats or -1.
+long check_loha_jobs(const char* name, const SdtLoraJob* h, const SdtLohaJob* x, int n) {
+  long part = 0;
+  for (int i = 0; i < n; ++i) {
+    if (h[i].r > 32) {
+      sdt_set_error("%s: job %d: rank %d: LoHa takes the ranks 4, 8, 16 and 32 (one MFMA K-step forms a block of A B)", name, i, h[i].r);
+      return -1;
+    }
+    if (x[i].K != h[i].K || x[i].N != h[i].N) {
+      sdt_set_error("%s: job %d: the LoHa table names K=%d N=%d, the job table K=%d N=%d (mismatched tables)", name, i, x[i].K, x[i].N,
+                    h[i].K, h[i].N);
+      return -1;
+    }
+    const int64_t offs[4] = {x[i].a2_off, x[i].b2_off, x[i].ga2_off, x[i].gb2_off};
+    for (int o = 0; o < 4; ++o)
+      if (offs[o] < 0 || offs[o] % 8) {
+        sdt_set_error("%s: job %d: LoHa offsets must be non-negative multiples of 8 elements", name, i);
+        return -1;
+      }
+    if (x[i].part_off != part) {
+      sdt_set_error("%s: job %d: LoHa part_off=%lld does not continue the running partial offset %ld", name, i, (long long)x[i].part_off,
+                    part);
+      return -1;
+    }
+    const long chunks = (h[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (h[i].N + LT - 1) / LT;
+    if (chunks > 1) part += 2 * stripes * chunks * h[i].r * LT;
+  }
+  return part;
+}
+
 }  // namespace
 
 extern "C" {
@@ -731,6 +1018,72 @@ int sdt_lora_project_split(const uint16_t* dw_base, const float* ab_base, float*
                      (const SdtLoraJob*)jobs_device, (const SdtLoraSplitJob*)split_device, n, (int*)workspace,
                      (float*)((char*)workspace + split_counter_bytes(cnt)));
   SDT_LAUNCH_CHECK("sdt_lora_project_split");
+  return SDT_OK;
+}
+
+int sdt_loha_job_size(void) { return (int)sizeof(SdtLohaJob); }
+
+int sdt_loha_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, const SdtLoraJob* jobs_host,
+                   const SdtLohaJob* loha_host, const void* jobs_device, const void* loha_device, int n, hipStream_t stream) {
+  SDT_CHECK_ARG(n >= 0, "sdt_loha_merge: negative job count");
+  if (n == 0) return SDT_OK;
+  SDT_CHECK_ARG(jobs_host && jobs_device && loha_host && loha_device, "sdt_loha_merge: null job table");
+  SDT_CHECK_ARG(w0_base && ab_base, "sdt_loha_merge: null pointer");
+  SDT_CHECK_ARG(w_bf16 || f32_dst, "sdt_loha_merge: no destination");
+  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)w_bf16 | (uintptr_t)f32_dst) & 15) == 0,
+                "sdt_loha_merge: pointers must be 16-byte aligned");
+  const long tiles = check_jobs("sdt_loha_merge", jobs_host, n, false);
+  if (tiles < 0 || check_loha_jobs("sdt_loha_merge", jobs_host, loha_host, n) < 0) return SDT_ERR_INVALID_ARG;
+  hipLaunchKernelGGL(loha_merge_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, w0_base, ab_base, (bf16_t*)w_bf16, f32_dst,
+                     (const SdtLoraJob*)jobs_device, (const SdtLohaJob*)loha_device, n);
+  SDT_LAUNCH_CHECK("sdt_loha_merge");
+  return SDT_OK;
+}
+
+int64_t sdt_loha_project_workspace_bytes(const SdtLoraJob* jobs_host, int n) {
+  if (n < 0 || (n > 0 && !jobs_host)) {
+    sdt_set_error("sdt_loha_project_workspace_bytes: bad job table");
+    return -1;
+  }
+  if (check_jobs("sdt_loha_project_workspace_bytes", jobs_host, n, true) < 0) return -1;
+  long cnt = 0, part = 0;
+  for (int i = 0; i < n; ++i) {
+    if (jobs_host[i].r > 32) {
+      sdt_set_error("sdt_loha_project_workspace_bytes: job %d: rank %d: LoHa takes the ranks 4, 8, 16 and 32", i, jobs_host[i].r);
+      return -1;
+    }
+    const long chunks = (jobs_host[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (jobs_host[i].N + LT - 1) / LT;
+    cnt += stripes;
+    if (chunks > 1) part += 2 * stripes * chunks * jobs_host[i].r * LT;
+  }
+  return split_counter_bytes(cnt) + 4 * part;
+}
+
+int sdt_loha_project(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
+                     const SdtLoraSplitJob* split_host, const SdtLohaJob* loha_host, const void* jobs_device, const void* split_device,
+                     const void* loha_device, int n, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  SDT_CHECK_ARG(n >= 0, "sdt_loha_project: negative job count");
+  if (n == 0) return SDT_OK;
+  SDT_CHECK_ARG(jobs_host && jobs_device && split_host && split_device && loha_host && loha_device, "sdt_loha_project: null job table");
+  SDT_CHECK_ARG(dw_base && ab_base && grad_base && workspace, "sdt_loha_project: null pointer");
+  SDT_CHECK_ARG((((uintptr_t)dw_base | (uintptr_t)ab_base | (uintptr_t)grad_base | (uintptr_t)workspace) & 15) == 0,
+                "sdt_loha_project: pointers must be 16-byte aligned");
+  if (check_jobs("sdt_loha_project", jobs_host, n, true) < 0) return SDT_ERR_INVALID_ARG;
+  const long part = check_loha_jobs("sdt_loha_project", jobs_host, loha_host, n);
+  if (part < 0) return SDT_ERR_INVALID_ARG;
+  long cnt = 0, part1 = 0;
+  const long tiles = check_split_jobs("sdt_loha_project", jobs_host, split_host, n, &cnt, &part1);
+  if (tiles < 0) return SDT_ERR_INVALID_ARG;
+  const long need = split_counter_bytes(cnt) + 4 * part;
+  if (workspace_bytes < need) {
+    sdt_set_error("sdt_loha_project: the workspace holds %lld bytes, the table needs %ld (counters and two sets of partials inside the workspace)",
+                  (long long)workspace_bytes, need);
+    return SDT_ERR_INVALID_ARG;
+  }
+  hipLaunchKernelGGL(loha_project_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
+                     (const SdtLoraJob*)jobs_device, (const SdtLoraSplitJob*)split_device, (const SdtLohaJob*)loha_device, n,
+                     (int*)workspace, (float*)((char*)workspace + split_counter_bytes(cnt)));
+  SDT_LAUNCH_CHECK("sdt_loha_project");
   return SDT_OK;
 }
 

@@ -16,6 +16,11 @@ whose dB stripes are split along the tall K (sdt_lora_project_split).
 DoRA (LoraConfig(dora=True); include/sdt.h "DoRA"): a third trained leaf m [N] per adapted kernel, W' = v * (m / ||v||_column) with
 v = W0 + s * A @ B.  The column norm is one more reduction inside the merge launch and the magnitude gradient one more inside the
 projection launch, so the step between them is the LoRA step, launch for launch.
+
+LoHa (LoraConfig(algo="loha"); include/sdt.h "LoHa"; DESIGN.md "LoHa"): four trained leaves A1, B1, A2, B2 per adapted kernel and the delta
+s * (A1 @ B1) * (A2 @ B2), element-wise - rank r^2 at the parameters of a rank-2r LoRA.  The same interface: one fused merge launch and one
+fused projection launch per job table (sdt_loha_merge / sdt_loha_project; the projection's dB stripes always take LoCon's split), the
+same restore, scratch and step.  With conv_rank > 0 the convolutions carry LoHa adapters too.
 """
 import bisect
 import json
@@ -29,6 +34,8 @@ from . import _lib
 from .params import ParamStore
 
 RANKS = (4, 8, 16, 32, 64, 128)
+ALGOS = ("lora", "loha")
+LOHA_MAX_RANK = 32  # one MFMA K-step forms a block of A_i @ B_i; the effective rank is r^2
 UNET_TARGETS = ("to_q", "to_k", "to_v", "to_out_0")
 CLIP_TARGETS = ("q_proj", "k_proj", "v_proj", "out_proj")
 UNET_CONV_TARGETS = ("conv1", "conv2", "conv_shortcut", "proj_in", "proj_out", "conv")  # "conv": downsamplers_0/conv, upsamplers_0/conv
@@ -39,7 +46,9 @@ class LoraConfig:
     """rank in RANKS; the delta is (alpha / rank) * A @ B; targets are matched against path components (as params.create_mask does);
     seed draws A (B starts at zero); dora adds the trained magnitude leaf <dense>/lora_m (it starts at the column norms of W0).
     conv_rank > 0 (LoCon) also adapts the 4-D kernels whose path has a component in conv_targets, at rank conv_rank and scale
-    conv_alpha / conv_rank (conv_alpha None: conv_rank); a conv target that meets a 2-D kernel leaves it to `targets`."""
+    conv_alpha / conv_rank (conv_alpha None: conv_rank); a conv target that meets a 2-D kernel leaves it to `targets`.
+    algo "loha": every adapted kernel carries loha_a1, loha_b1, loha_a2, loha_b2 and the delta (alpha / rank) * (A1 @ B1) * (A2 @ B2),
+    element-wise, at ranks up to 32 (seed draws A1, B1 and A2; B2 starts at zero); not with dora."""
     rank: int
     alpha: float
     targets: tuple = UNET_TARGETS
@@ -48,6 +57,7 @@ class LoraConfig:
     conv_rank: int = 0
     conv_alpha: float = None
     conv_targets: tuple = UNET_CONV_TARGETS
+    algo: str = "lora"
 
     def __post_init__(self):
         object.__setattr__(self, "targets", tuple(self.targets))
@@ -69,11 +79,21 @@ class LoraConfig:
         if self.conv_rank and self.dora:
             raise ValueError("LoraConfig: DoRA on convolutions is not supported (dora=True with conv_rank > 0): the DoRA merge walks K "
                              "twice per column stripe and has no split for a convolution's tall K")
+        if self.algo not in ALGOS:
+            raise ValueError(f"LoraConfig: algo must be one of {ALGOS}, not {self.algo!r}")
+        if self.algo == "loha":
+            if self.dora:
+                raise ValueError("LoraConfig: DoRA combined with LoHa is not supported (algo='loha' with dora=True): the DoRA merge and "
+                                 "projection are built on the low-rank product")
+            if self.rank > LOHA_MAX_RANK or self.conv_rank > LOHA_MAX_RANK:
+                raise ValueError(f"LoraConfig: algo='loha' takes rank and conv_rank up to {LOHA_MAX_RANK} (the effective rank is the square), "
+                                 f"not rank={self.rank!r}, conv_rank={self.conv_rank!r}")
 
-    def __repr__(self):  # (without LoCon the text is what it was: refusal messages quote it)
+    def __repr__(self):  # (without LoCon / LoHa the text is what it was: refusal messages quote it)
         conv = f", conv_rank={self.conv_rank!r}, conv_alpha={self.conv_alpha!r}, conv_targets={self.conv_targets!r}" if self.conv_rank else ""
+        algo = f", algo={self.algo!r}" if self.algo != "lora" else ""
         return (f"LoraConfig(rank={self.rank!r}, alpha={self.alpha!r}, targets={self.targets!r}, seed={self.seed!r}, dora={self.dora!r}"
-                f"{conv})")
+                f"{conv}{algo})")
 
     @property
     def scale(self):
@@ -121,14 +141,28 @@ def leaf_factors(shape, cfg):
     return shape[0] * shape[1] * shape[2], shape[3], cfg.conv_rank, cfg.conv_scale
 
 
+LOHA_LEAVES = ("loha_a1", "loha_b1", "loha_a2", "loha_b2")
+
+
+def leaf_names(cfg):
+    """The trained leaves of one adapted kernel, in store order."""
+    if cfg.algo == "loha":
+        return LOHA_LEAVES
+    return ("lora_a", "lora_b", "lora_m") if cfg.dora else ("lora_a", "lora_b")
+
+
 def adapter_spec(spec, cfg):
     """[(<layer path>/lora_a, (K, r)), (<layer path>/lora_b, (r, N))] for the adapted kernels of `spec`, in its order (Dense and
-    convolution adapters interleaved as the base runs them); with cfg.dora each pair is followed by (<dense path>/lora_m, (N,))."""
+    convolution adapters interleaved as the base runs them); with cfg.dora each pair is followed by (<dense path>/lora_m, (N,)).
+    algo "loha": loha_a1 (K, r), loha_b1 (r, N), loha_a2 (K, r), loha_b2 (r, N) per kernel."""
     shapes = dict((p, tuple(s)) for p, s in spec)
     out = []
     for path in select_leaves(spec, cfg):
         K, N, r, _ = leaf_factors(shapes[path], cfg)
         dense = path[: -len("/kernel")]
+        if cfg.algo == "loha":
+            out += [(f"{dense}/{n}", (K, r) if "_a" in n else (r, N)) for n in LOHA_LEAVES]
+            continue
         out += [(dense + "/lora_a", (K, r)), (dense + "/lora_b", (r, N))]
         if cfg.dora:
             out.append((dense + "/lora_m", (N,)))
@@ -165,7 +199,8 @@ def scratch_runs(leaves, adapted):
 class LoraAdapter:
     """What attach() hangs on a frozen store: the trained A / B (/ m) leaves (self.store), the bf16 dW scratch and the job table; for
     DoRA also the parallel SdtDoraJob table and the column statistics (c, g of every adapted leaf) the merge leaves for the projection;
-    for LoCon a second job table over the adapted convolution leaves with its SdtLoraSplitJob table and the split projection's workspace."""
+    for LoCon a second job table over the adapted convolution leaves with its SdtLoraSplitJob table and the split projection's workspace;
+    for LoHa, beside every non-empty job table, the SdtLoraSplitJob and SdtLohaJob tables and the workspace of sdt_loha_project (self.loha)."""
 
     def __init__(self, base, cfg, store_kwargs):
         if base.trainable:
@@ -181,8 +216,7 @@ class LoraAdapter:
             lf = base.leaves[p]
             if (lf.R, lf.C) != (lf.Rp, lf.Cp) or lf.w_off != lf.offset:
                 raise ValueError(f"LoRA: {p} is a padded leaf and cannot carry an adapter")
-        self.adapted = {p: tuple(p[: -len("kernel")] + n for n in (("lora_a", "lora_b", "lora_m") if cfg.dora else ("lora_a", "lora_b")))
-                        for p in self.paths}
+        self.adapted = {p: tuple(p[: -len("kernel")] + n for n in leaf_names(cfg)) for p in self.paths}
         kw = dict(store_kwargs)
         kw.setdefault("device", base.device)
         if cfg.dora:  # a magnitude keeps fp32 moments and takes no weight decay
@@ -248,15 +282,45 @@ class LoraAdapter:
             self.split_host = (_lib.SdtLoraSplitJob * len(split))(*split)
             self.conv_jobs_dev = torch.frombuffer(bytearray(bytes(self.conv_jobs_host)), dtype=torch.uint8).to(dev)
             self.split_dev = torch.frombuffer(bytearray(bytes(self.split_host)), dtype=torch.uint8).to(dev)
-            need = _lib.load().sdt_lora_project_split_workspace_bytes(self.conv_jobs_host, len(cjobs))
-            if need < 0:
-                raise _lib.SdtError(f"sdt_lora_project_split_workspace_bytes: {_lib.load().sdt_last_error().decode()}")
-            # arrival counters (zero between launches) and partials: allocated once, so that a captured step replays it
-            self.split_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+            if cfg.algo == "lora":
+                need = _lib.load().sdt_lora_project_split_workspace_bytes(self.conv_jobs_host, len(cjobs))
+                if need < 0:
+                    raise _lib.SdtError(f"sdt_lora_project_split_workspace_bytes: {_lib.load().sdt_last_error().decode()}")
+                # arrival counters (zero between launches) and partials: allocated once, so that a captured step replays it
+                self.split_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+        # LoHa: per non-empty job table (jobs_host, jobs_dev, split_host, split_dev, loha_host, loha_dev, workspace)
+        self.loha = []
+        if cfg.algo == "loha":
+            for paths, jh, jd in ((self.dense_paths, self.jobs_host, self.jobs_dev), (self.conv_paths, self.conv_jobs_host, self.conv_jobs_dev)):
+                if paths:
+                    self.loha.append(self._loha_tables(paths, jh, jd))
         self.init_weights()
         base.adapter = self
         if dev.type == "cuda":
             self.merge()
+
+    def _loha_tables(self, paths, jobs_host, jobs_dev):
+        """The SdtLoraSplitJob and SdtLohaJob tables beside one job table and the workspace of sdt_loha_project: arrival counters (zero
+        between launches) and two partial sets per job of more than one chunk, allocated and zeroed once so that a captured step replays it."""
+        lib, dev = _lib.load(), self.base.device
+        rows = lib.sdt_lora_project_split_rows()
+        split, loha, ts, cnt, part1, part2 = [], [], 0, 0, 0, 0
+        for p, j in zip(paths, jobs_host):
+            la2, lb2 = (self.store.leaves[q] for q in self.adapted[p][2:])
+            tb, chunks = (j.N + 63) // 64, (j.K + rows - 1) // rows
+            split.append(_lib.SdtLoraSplitJob(part1, j.K, j.N, ts, chunks, cnt, 0))
+            loha.append(_lib.SdtLohaJob(la2.offset, lb2.offset, la2.offset, lb2.offset, part2, j.K, j.N))
+            ts += j.tiles_da + tb * chunks
+            cnt += tb
+            part1 += tb * chunks * j.r * 64 if chunks > 1 else 0
+            part2 += 2 * tb * chunks * j.r * 64 if chunks > 1 else 0
+        split_host = (_lib.SdtLoraSplitJob * len(split))(*split)
+        loha_host = (_lib.SdtLohaJob * len(loha))(*loha)
+        to_dev = lambda t: torch.frombuffer(bytearray(bytes(t)), dtype=torch.uint8).to(dev)
+        need = lib.sdt_loha_project_workspace_bytes(jobs_host, len(jobs_host))
+        if need < 0:
+            raise _lib.SdtError(f"sdt_loha_project_workspace_bytes: {lib.sdt_last_error().decode()}")
+        return jobs_host, jobs_dev, split_host, to_dev(split_host), loha_host, to_dev(loha_host), torch.zeros(need, dtype=torch.uint8, device=dev)
 
     # ------------------------------------------------------------------ parameters
     def init_weights(self):
@@ -264,6 +328,16 @@ class LoraAdapter:
         the column norms of W0 + s * A @ B = W0 by the merge kernel's own reduction, so that the first merge finds g == 1.0f exactly."""
         g = torch.Generator().manual_seed(int(self.cfg.seed))
         tree = {}
+        if self.cfg.algo == "loha":  # LyCORIS: A1 ~ N(0, 1), B1 ~ N(0, 0.1^2), A2 ~ N(0, 1), B2 = 0 - the delta starts at exactly zero
+            for p in self.paths:     # and only B2 receives a gradient on the first step; drawn in leaf order
+                a1, b1, a2, b2 = self.adapted[p]
+                (K, r), (_, N) = self.store.leaves[a1].shape, self.store.leaves[b1].shape
+                tree[a1] = torch.randn(K, r, generator=g)
+                tree[b1] = torch.randn(r, N, generator=g) * 0.1
+                tree[a2] = torch.randn(K, r, generator=g)
+                tree[b2] = torch.zeros(r, N)
+            self.store.load(tree)
+            return
         for p in self.paths:
             a, b = self.adapted[p][:2]
             K, r = self.store.leaves[a].shape  # (a convolution's K = kh * kw * Cin: the fan-in of its down-convolution)
@@ -328,6 +402,11 @@ class LoraAdapter:
         if ab is None:
             raise ValueError("merge(source='ema'): the adapter store keeps no EMA")
         self.source = source
+        if self.loha:  # w[leaf] = bf16(W0 + s * (A1 @ B1) * (A2 @ B2)): one launch per table
+            for jh, jd, _, _, xh, xd, _ in self.loha:
+                _lib.call("sdt_loha_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, jh, xh, jd.data_ptr(),
+                          xd.data_ptr(), len(jh), self._stream())
+            return
         if self.cfg.dora:  # also leaves c and g of every leaf in self.stats, for project()
             _lib.call("sdt_dora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.stats.data_ptr(),
                       self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(), self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
@@ -352,14 +431,18 @@ class LoraAdapter:
         """dA, dB of every adapted leaf from the dW scratch into the adapter store's gradient (one launch; with LoCon a second one,
         sdt_lora_project_split, for the convolution table; written, not accumulated)."""
         from . import ops
-        if self.cfg.dora:  # also dm, from the c and g the step's merge left in self.stats
+        if self.loha:  # the four factor gradients of every leaf: one launch per table (include/sdt.h "LoHa")
+            for jh, jd, sh, sd, xh, xd, ws in self.loha:
+                _lib.call("sdt_loha_project", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), jh, sh, xh,
+                          jd.data_ptr(), sd.data_ptr(), xd.data_ptr(), len(jh), ws.data_ptr(), ws.numel(), self._stream())
+        elif self.cfg.dora:  # also dm, from the c and g the step's merge left in self.stats
             _lib.call("sdt_dora_project", self.scratch.data_ptr(), self.base.master.data_ptr(), self.store.master.data_ptr(),
                       self.store.grad.data_ptr(), self.stats.data_ptr(), self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(),
                       self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
         else:
             _lib.call("sdt_lora_project", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), self.jobs_host,
                       self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
-        if self.conv_paths:  # tall K: the dB stripes split along K (include/sdt.h "LoCon")
+        if self.conv_paths and not self.loha:  # tall K: the dB stripes split along K (include/sdt.h "LoCon")
             _lib.call("sdt_lora_project_split", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(),
                       self.conv_jobs_host, self.split_host, self.conv_jobs_dev.data_ptr(), self.split_dev.data_ptr(),
                       len(self.conv_jobs_host), self.split_ws.data_ptr(), self.split_ws.numel(), self._stream())
@@ -373,7 +456,11 @@ class LoraAdapter:
         if ab is None:
             raise ValueError("folded(source='ema'): the adapter store keeps no EMA")
         buf = self.base.master.clone()
-        if self.cfg.dora:  # (statistics of its own: self.stats stays what the last merge into the mirror left)
+        if self.loha:
+            for jh, jd, _, _, xh, xd, _ in self.loha:
+                _lib.call("sdt_loha_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), jh, xh, jd.data_ptr(),
+                          xd.data_ptr(), len(jh), self._stream())
+        elif self.cfg.dora:  # (statistics of its own: self.stats stays what the last merge into the mirror left)
             stats = torch.empty_like(self.stats)  # (bound to a name until the call has been enqueued)
             _lib.call("sdt_dora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), stats.data_ptr(),
                       self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(), self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
@@ -394,11 +481,14 @@ class LoraAdapter:
         if self.cfg.conv_rank:
             meta.update(conv_rank=int(self.cfg.conv_rank), conv_alpha=float(self.cfg.conv_scale * self.cfg.conv_rank),
                         conv_targets=list(self.cfg.conv_targets))
+        if self.cfg.algo != "lora":
+            meta["algo"] = self.cfg.algo
         return meta
 
     def save(self, path, which="master"):
         """One .npz: the A / B (/ m) leaves (fp32) and __meta__ (JSON: rank, alpha, targets, the adapted base kernels' shapes, and
-        "dora": true for a DoRA adapter, conv_rank / conv_alpha / conv_targets for a LoCon adapter)."""
+        "dora": true for a DoRA adapter, conv_rank / conv_alpha / conv_targets for a LoCon adapter, "algo": "loha" for a LoHa adapter,
+        whose leaves are A1 / B1 / A2 / B2)."""
         tree = self.store.export_host(which)
         with open(path, "wb") as f:
             np.savez(f, __meta__=np.frombuffer(json.dumps(self._meta()).encode(), dtype=np.uint8), **{p: np.asarray(v) for p, v in tree.items()})
@@ -410,6 +500,10 @@ class LoraAdapter:
                 raise ValueError(f"{path}: not an adapter file (no __meta__)")
             meta = json.loads(bytes(z["__meta__"]).decode())
             mine = self._meta()
+            if meta.get("algo", "lora") != mine.get("algo", "lora"):
+                kind = lambda m: "LoHa" if m.get("algo", "lora") == "loha" else "DoRA" if m.get("dora", False) else "LoRA"
+                raise ValueError(f"{path}: a {kind(meta)} adapter file, this adapter is a {kind(mine)} adapter (attach with algo="
+                                 f"{meta.get('algo', 'lora')!r})")
             if bool(meta.get("dora", False)) != bool(mine.get("dora", False)):
                 kind = lambda m: "DoRA" if m.get("dora", False) else "LoRA"
                 raise ValueError(f"{path}: a {kind(meta)} adapter file, this adapter is a {kind(mine)} adapter (attach with dora="

@@ -11,8 +11,11 @@ variants alternating: per round, --steps graph replays each of the attention-onl
 between events; then, on the LoCon adapter's convolution table, the split projection (sdt_lora_project_split) against sdt_lora_project on
 the same table, alternating per round.  It prints medians and ranges over --rounds rounds, the merge / restore / project times and the
 scratch and workspace bytes.
+--algo loha times LoHa (LoraConfig(algo="loha")) against the step it extends, in one session with the variants alternating per round:
+the attention-only LoHa step against the LoRA step, or with --conv-rank R the LoHa step on attention and convolutions against the LoCon
+step; then merge / restore / project of both adapters by events, alternating per round, and the scratch and workspace bytes.
 usage: python tools/lora_bench.py [--config sd15_512 sd21_768 sdxl_1024] [--steps 8] [--warmup 2] [--rank 16] [--dora]
-                                  [--optimizer lion adamw prodigy] [--skip-full] [--conv-rank R [--rounds 7]]"""
+                                  [--optimizer lion adamw prodigy] [--skip-full] [--conv-rank R [--rounds 7]] [--algo loha]"""
 import argparse
 import json
 import os
@@ -37,6 +40,7 @@ ap.add_argument("--optimizer", nargs="+", choices=("lion", "adamw", "prodigy"), 
 ap.add_argument("--skip-full", action="store_true")
 ap.add_argument("--conv-rank", type=int, default=0)
 ap.add_argument("--rounds", type=int, default=7)
+ap.add_argument("--algo", choices=lora.ALGOS, default="lora")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
 
@@ -138,6 +142,69 @@ def locon_session(config):
                              "project_ms": round(event_ms(a.project), 4)} for name, a in (("lora", base), ("locon", ad))}
     print(json.dumps(res), flush=True)
 
+
+def loha_session(config):
+    """--algo loha: the LoRA (with --conv-rank: LoCon) step and the LoHa step on the same leaves in one session, alternating."""
+    c = bench.CONFIGS[config]
+    B = c["batch"]
+    tc, cfgs, weights, full = bench.build_states(dev, B, config=config)
+    del full
+    torch.cuda.empty_cache()
+    kw = dict(strip_bos_eos_token=False, ema_rate=tc.ema_rate, vae_scale=c["vae_scale"])
+    batch = bench.synthetic_batch(dev, B, 0, config)
+    models = {"unet": {"unet_params": weights["unet"], "config": cfgs["unet"]}, "vae": {"vae_params": weights["vae"], "config": cfgs["vae"]},
+              "text_encoder": {"text_encoder_params": weights["clip"], "config": cfgs["clip"]}}
+    r, parent = args.rank, "locon" if args.conv_rank else "lora"
+    variants = {}
+    for name, cfg in ((parent, lora.LoraConfig(r, float(r), conv_rank=args.conv_rank)),
+                      ("loha", lora.LoraConfig(r, float(r), conv_rank=args.conv_rank, algo="loha"))):
+        variants[name] = tu.on_device_model_training_state(tc, models, device=dev, optimizer=args.optimizer[0],
+                                                           lora=dict(unet=cfg, text_encoder="frozen"))[:6]
+    steps, rngs = {}, {}
+    for name, st in variants.items():  # two eager set-up steps, capture + first replay, warm-up replays
+        steps[name] = tu._GraphedStep(lambda *a, **k: tu.train_step(*a, **kw, **k))
+        rngs[name] = torch.Generator(device=dev)
+        rngs[name].manual_seed(1000)
+        for _ in range(3 + args.warmup):
+            steps[name](st[0], st[1], st[2], st[3], batch, rngs[name], st[4], st[5])
+        torch.cuda.synchronize()
+        assert steps[name].graph is not None
+    times = {name: [] for name in variants}
+    for _ in range(args.rounds):
+        for name, st in variants.items():
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for _ in range(args.steps):
+                steps[name](st[0], st[1], st[2], st[3], batch, rngs[name], st[4], st[5])
+            e1.record()
+            torch.cuda.synchronize()
+            times[name].append(e0.elapsed_time(e1) / args.steps)
+    res = {"config": config, "batch": B, "rank": r, "conv_rank": args.conv_rank, "rounds": args.rounds, "steps_per_round": args.steps,
+           "step_ms": {name: spread(t) for name, t in times.items()}}
+    launches = {name: {"merge_ms": [], "restore_ms": [], "project_ms": []} for name in variants}
+    for _ in range(args.rounds):
+        for name, st in variants.items():
+            a = st[0].adapter
+            for what, fn in (("merge_ms", a.merge), ("restore_ms", a.restore), ("project_ms", a.project)):
+                launches[name][what].append(event_ms(fn))
+    res["adapter"] = {}
+    for name, st in variants.items():
+        a = st[0].adapter
+        ws = sum(t[6].numel() for t in a.loha) if a.loha else 0 if a.split_ws is None else a.split_ws.numel()
+        res["adapter"][name] = dict({"leaves": len(a.paths), "conv_leaves": len(a.conv_paths),
+                                     "adapted_params": sum(a.base.leaves[p].numel for p in a.paths),
+                                     "trained_params": sum(lf.numel for lf in a.store.leaves.values()), "scratch_bytes": 2 * a.scratch.numel(),
+                                     "workspace_bytes": ws}, **{k: spread(v) for k, v in launches[name].items()})
+    print(json.dumps(res), flush=True)
+
+
+if args.algo == "loha":
+    if args.dora:
+        ap.error("--algo loha is refused beside --dora")
+    for config in args.config:
+        loha_session(config)
+        torch.cuda.empty_cache()
+    sys.exit(0)
 
 if args.conv_rank:
     for config in args.config:
