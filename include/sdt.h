@@ -551,6 +551,19 @@ int sdt_colsum_accumulate(const uint16_t* dy, float* db, int64_t M, int N, int l
 int sdt_colsum_batched_bf16(const uint16_t* dy, uint16_t* out, int batch, int64_t rows_per_batch, int N, int ld, void* workspace,
                             int64_t workspace_bytes, hipStream_t stream);
 int64_t sdt_colsum_workspace_bytes(int batch, int64_t rows_per_batch, int N);
+/* (ABI 5, additive) n <= sdt_colsum_batched_group_max() problems of sdt_colsum_batched_bf16 as one launch.  Each problem keeps the
+ * row partition and the order of additions of its single launch (the same bits); the workspace (split-workspace contract) holds the
+ * counters and partial rows of all of them: sdt_colsum_batched_group_workspace_bytes(problems, n). */
+typedef struct SdtColsumProblem {
+  const uint16_t* dy;
+  uint16_t* out;
+  int batch;
+  int64_t rows_per_batch;
+  int N, ld;
+} SdtColsumProblem;
+int sdt_colsum_batched_group(const SdtColsumProblem* problems, int n, void* workspace, int64_t workspace_bytes, hipStream_t stream);
+int sdt_colsum_batched_group_max(void);
+int64_t sdt_colsum_batched_group_workspace_bytes(const SdtColsumProblem* problems, int n);
 
 /* ================= attention (diffusers attention_flax.py + key_chunk_patch.patch; FlaxCLIPAttention) */
 int sdt_attention_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, uint16_t* out, float* lse,
@@ -561,6 +574,28 @@ int sdt_attention_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, c
                       const float* lse, uint16_t* dq, uint16_t* dk, uint16_t* dv, float* workspace, int64_t workspace_bytes,
                       const SdtAttnDesc* desc, hipStream_t stream);
 int64_t sdt_attention_bwd_workspace_bytes(const SdtAttnDesc* desc);
+/* (ABI 5, additive) The two passes of sdt_attention_bwd as separate calls, for a caller that holds the dK/dV of several attentions
+ * back and issues them together (cross-attention: nothing on the input-gradient chain reads dK/dV, and one such pass alone leaves
+ * most of the chip idle).  sdt_attention_bwd_dq runs the dQ pass alone and writes delta (sdt_attention_bwd_delta_bytes(desc) bytes).
+ * sdt_attention_bwd_dkv_group runs the dK/dV passes of n <= sdt_attention_bwd_dkv_group_max() problems: one launch per kernel
+ * instantiation (head-dim class: D <= 48, 64, 80, 96, 128, 160) present in the table per 8 problems, then one launch for the
+ * finishing passes of up to 8 split problems.  Every problem keeps the plan of the single call with its full workspace (the query
+ * split where that takes it, the order of additions): dk / dv are the single call's bit for bit.  A problem whose plan splits needs
+ * `slabs` of sdt_attention_bwd_slab_bytes(desc) bytes (0: no split, slabs may be NULL) of its own; lse, delta, the slabs and the
+ * operands must stay valid and unchanged until the grouped call has run. */
+typedef struct SdtAttnDkvProblem {
+  const uint16_t *q, *k, *v, *dout;
+  const float *lse, *delta;
+  uint16_t *dk, *dv;
+  float* slabs;
+  SdtAttnDesc desc;
+} SdtAttnDkvProblem;
+int sdt_attention_bwd_dq(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* out, const uint16_t* dout,
+                         const float* lse, uint16_t* dq, float* delta, const SdtAttnDesc* desc, hipStream_t stream);
+int sdt_attention_bwd_dkv_group(const SdtAttnDkvProblem* problems, int n, hipStream_t stream);
+int sdt_attention_bwd_dkv_group_max(void);
+int64_t sdt_attention_bwd_delta_bytes(const SdtAttnDesc* desc);
+int64_t sdt_attention_bwd_slab_bytes(const SdtAttnDesc* desc);
 int sdt_softmax_rows_inplace(uint16_t* x, int64_t rows, int n, float scale, hipStream_t stream);
 
 /* ================= elementwise / data movement */

@@ -29,6 +29,15 @@ class SdtNormGradJob(ctypes.Structure):
     _fields_ = [("partial", _P), ("dgamma", _P), ("dbeta", _P), ("nrows", _I), ("C", _I)]
 
 
+class SdtAttnDkvProblem(ctypes.Structure):
+    _fields_ = [("q", _P), ("k", _P), ("v", _P), ("dout", _P), ("lse", _P), ("delta", _P), ("dk", _P), ("dv", _P), ("slabs", _P),
+                ("desc", SdtAttnDesc)]
+
+
+class SdtColsumProblem(ctypes.Structure):
+    _fields_ = [("dy", _P), ("out", _P), ("batch", _I), ("rows_per_batch", _L), ("N", _I), ("ld", _I)]
+
+
 class SdtConvWgradProblem(ctypes.Structure):
     _fields_ = [("A", _P), ("dY", _P), ("dW", _P), ("dbias", _P), ("geom", SdtConvGeom), ("K1", _I), ("N", _I), ("K1_valid", _I),
                 ("N_valid", _I), ("lda", _I), ("ldb", _I), ("sq_slots", _P), ("dw_bf16", _I)]
@@ -118,8 +127,11 @@ SIGNATURES = {
     "sdt_zero_ranges": [_P, _P, _I, _P],
     "sdt_colsum_accumulate": [_P, _P, _L, _I, _I, _P, _L, _P],
     "sdt_colsum_batched_bf16": [_P, _P, _I, _L, _I, _I, _P, _L, _P],
+    "sdt_colsum_batched_group": [_P, _I, _P, _L, _P],
     "sdt_attention_fwd": [_P, _P, _P, _P, _P, _P, _P],
     "sdt_attention_bwd": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _L, _P, _P],
+    "sdt_attention_bwd_dq": [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "sdt_attention_bwd_dkv_group": [_P, _I, _P],
     "sdt_softmax_rows_inplace": [_P, _L, _I, _F, _P],
     "sdt_act_fwd": [_P, _P, _L, _I, _P],
     "sdt_act_bwd": [_P, _P, _P, _L, _I, _P],
@@ -156,12 +168,13 @@ SIGNATURES = {
 WS_QUERY = {"sdt_gemm_nt_workspace_bytes": [_L, _I, _I, _I], "sdt_gemm_tn_workspace_bytes": [_L, _I, _I, _I, _I, _I, _P], "sdt_layernorm_bwd_workspace_bytes": [_L, _I], "sdt_layernorm_bwd_partial_rows": [_L, _I],
             "sdt_groupnorm_bwd_workspace_bytes": [_I, _I, _I],
             "sdt_groupnorm_fwd_workspace_bytes": [_I, _I, _I, _I], "sdt_attention_bwd_workspace_bytes": [_P],
+            "sdt_attention_bwd_delta_bytes": [_P], "sdt_attention_bwd_slab_bytes": [_P], "sdt_colsum_batched_group_workspace_bytes": [_P, _I],
             "sdt_ip_attention_bwd_workspace_bytes": [_I, _I, _I, _I, _I],
             "sdt_gemm_tn_wgrad_group_workspace_bytes": [_P, _I], "sdt_conv_wgrad_group_workspace_bytes": [_P, _I], "sdt_reduce_workspace_bytes": [], "sdt_dpo_loss_workspace_bytes": [_I, _I, _I], "sdt_sqnorm_workspace_bytes": [], "sdt_prodigy_workspace_bytes": [], "sdt_colsum_workspace_bytes": [_I, _L, _I],
             "sdt_lora_project_split_workspace_bytes": [_P, _I],
             "sdt_loha_project_workspace_bytes": [_P, _I],
             "sdt_wgrad_sq_slots": [_I, _I, _I]}
-NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_lora_job_size": _I, "sdt_dora_job_size": _I, "sdt_lora_split_job_size": _I, "sdt_lora_project_split_rows": _I, "sdt_loha_job_size": _I, "sdt_last_error": ctypes.c_char_p}
+NOARG = {"sdt_abi_version": _I, "sdt_gemm_tn_wgrad_group_max": _I, "sdt_norm_param_grads_group_max": _I, "sdt_attention_bwd_dkv_group_max": _I, "sdt_colsum_batched_group_max": _I, "sdt_zero_ranges_chunk": _I, "sdt_device_count": _I, "sdt_param_prepare_desc_size": _I, "sdt_lora_job_size": _I, "sdt_dora_job_size": _I, "sdt_lora_split_job_size": _I, "sdt_lora_project_split_rows": _I, "sdt_loha_job_size": _I, "sdt_last_error": ctypes.c_char_p}
 
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc", "libsdtrain_hip.so")
 if os.environ.get("SDT_LIB"):  # developer A/B of two builds on one box (tools/ab_libs.sh): another in-tree build of the same sources

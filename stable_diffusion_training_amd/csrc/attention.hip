@@ -498,15 +498,15 @@ __global__ void __launch_bounds__(256) attn_bwd_dq_kernel(const AttnParams p) {
 }
 
 // ------------------------------------------------------------------------------------------ backward: dK, dV
+// The workgroup (bx, h, b) of the pass: bx = key block, or with QSPLIT (query chunk, key block) with the key block fastest.  The
+// single-problem kernel takes the three from its grid, the grouped one (attn_bwd_dkv_group_kernel) from its problem table.
 template <int DPP, int NS, int NB, bool QSPLIT>
-__global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const AttnParams p) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+__device__ __forceinline__ void attn_bwd_dkv_body(const AttnParams& p, const int bx, const int h, const int b, unsigned char* smem) {
   using I = Img<DPP>;
   constexpr int STAGE = 2 * I::BYTES + 2 * KT * 4;  // Q image | dO image | lse[KT] | delta[KT]
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, fr = lane & 31, fh = lane >> 5;
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
-  const int b = blockIdx.z, h = blockIdx.y;
-  const int kblk = QSPLIT ? (int)blockIdx.x % p.kblocks : (int)blockIdx.x;
+  const int kblk = QSPLIT ? bx % p.kblocks : bx;
   const int k0 = kblk * 128;
   const int ki = k0 + wave * 32 + fr;  // this lane's key
   const float kwt = p.key_w ? p.key_w[min(ki, p.Nk - 1)] : 1.f;
@@ -525,7 +525,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const AttnParams p) {
   int qstart = 0, qend = p.Nq;
   if (p.causal) qstart = (k0 / KT) * KT;  // queries before the block's first key see none of its keys
   if (QSPLIT) {
-    qstart = ((int)blockIdx.x / p.kblocks) * p.qchunk;
+    qstart = (bx / p.kblocks) * p.qchunk;
     qend = min(p.Nq, qstart + p.qchunk);
   }
   dma.bind(qb, p.ldq, qstart);
@@ -628,7 +628,7 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const AttnParams p) {
     if (ki < p.Nk) {
       const long C = (long)p.H * p.D;
       const long slab = 2 * (long)p.B * p.Nk * C;
-      float* wk = p.kv_ws + ((int)blockIdx.x / p.kblocks) * slab + ((long)b * p.Nk + ki) * C + h * p.D;
+      float* wk = p.kv_ws + (bx / p.kblocks) * slab + ((long)b * p.Nk + ki) * C + h * p.D;
       float* wv = wk + (long)p.B * p.Nk * C;
 #pragma unroll
       for (int i = 0; i < NB; ++i)
@@ -665,13 +665,54 @@ __global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const AttnParams p) {
   }
 }
 
+template <int DPP, int NS, int NB, bool QSPLIT>
+__global__ void __launch_bounds__(256) attn_bwd_dkv_kernel(const AttnParams p) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  attn_bwd_dkv_body<DPP, NS, NB, QSPLIT>(p, (int)blockIdx.x, (int)blockIdx.y, (int)blockIdx.z, smem);
+}
+
+// Several dK/dV problems of one instantiation as ONE launch (sdt_attention_bwd_dkv_group): nothing on the input-gradient chain reads
+// a cross-attention's dK/dV, and one alone is 32 - 256 workgroups.  Workgroups in order (problem, image, head, bx): wg_end is the
+// prefix table, gx[i] the problem's extent in bx.  Every problem keeps its own plan (kv_ws set: query split into its own slabs) and
+// runs the body of the single launch, so its results are those of the single launch bit for bit.
+#define ATTN_GROUP_MAX 8  // problems per launch (kernel-argument space)
+#define ATTN_DKV_GROUP_ABI_MAX 32  // problems per sdt_attention_bwd_dkv_group call
+struct AttnGroupParams {
+  int n;
+  int wg_end[ATTN_GROUP_MAX];
+  int gx[ATTN_GROUP_MAX];  // dK/dV: workgroups per (image, head); finishing pass: the problem's slab count
+  AttnParams prob[ATTN_GROUP_MAX];
+};
+static_assert(sizeof(AttnGroupParams) <= 4096, "the grouped attention launches pass their problem table as kernel arguments");
+
+__device__ __forceinline__ int attn_group_find(const AttnGroupParams& gp, int* local) {
+  const int blk = blockIdx.x;
+  int i = 0;
+  while (i + 1 < gp.n && blk >= gp.wg_end[i]) ++i;  // wave-uniform scalar walk over <= 8 entries
+  *local = blk - (i ? gp.wg_end[i - 1] : 0);
+  return i;
+}
+
+template <int DPP, int NS, int NB>
+__global__ void __launch_bounds__(256) attn_bwd_dkv_group_kernel(const AttnGroupParams gp) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int local;
+  const int i = attn_group_find(gp, &local);
+  const AttnParams p = gp.prob[i];  // by value: fetched once, into scalar registers
+  const int gx = gp.gx[i];
+  const int rest = local / gx, bx = local - rest * gx;
+  const int b = rest / p.H, h = rest - b * p.H;
+  if (p.kv_ws) attn_bwd_dkv_body<DPP, NS, NB, true>(p, bx, h, b, smem);
+  else attn_bwd_dkv_body<DPP, NS, NB, false>(p, bx, h, b, smem);
+}
+
 // fp32 slabs [nsplit][2][B][Nk][C] (one per query chunk) -> bf16 dk / dv (row strides lddk / lddv), 8 columns per thread; the
-// slabs are added in chunk order: bitwise reproducible
-__global__ void __launch_bounds__(256) attn_kv_finish_kernel(const AttnParams p, int nsplit) {
+// slabs are added in chunk order: bitwise reproducible.  Workgroup `bid` of `nblocks`.
+__device__ __forceinline__ void attn_kv_finish_body(const AttnParams& p, const int nsplit, const int bid, const int nblocks) {
   const int C = p.H * p.D, cv = C >> 3;
   const long rows = (long)p.B * p.Nk, total = rows * cv;
   const long slab = 2 * rows * C;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+  for (long i = (long)bid * blockDim.x + threadIdx.x; i < total; i += (long)nblocks * blockDim.x) {
     const long r = i / cv;
     const int c = (int)(i - r * cv) * 8;
     const int b = (int)(r / p.Nk), ki = (int)(r - (long)b * p.Nk);
@@ -690,6 +731,16 @@ __global__ void __launch_bounds__(256) attn_kv_finish_kernel(const AttnParams p,
     *reinterpret_cast<uint4*>(p.dv + (long)b * p.bsdv + (long)ki * p.lddv + c) = pack8(fv);
   }
 }
+__global__ void __launch_bounds__(256) attn_kv_finish_kernel(const AttnParams p, int nsplit) {
+  attn_kv_finish_body(p, nsplit, (int)blockIdx.x, (int)gridDim.x);
+}
+// the finishing passes of several split problems as one launch: each problem keeps the workgroups of its own launch
+__global__ void __launch_bounds__(256) attn_kv_finish_group_kernel(const AttnGroupParams gp) {
+  int local;
+  const int i = attn_group_find(gp, &local);
+  const AttnParams p = gp.prob[i];
+  attn_kv_finish_body(p, gp.gx[i], local, gp.wg_end[i] - (i ? gp.wg_end[i - 1] : 0));
+}
 
 // query split of the dK/dV pass: used when the key blocks alone leave most of the chip idle
 static int attn_qsplits(int B, int H, int Nq, int Nk, int causal) {
@@ -701,6 +752,14 @@ static int attn_qsplits(int B, int H, int Nq, int Nk, int causal) {
   if (s > max_s) s = max_s;
   return s < 2 ? 1 : s;
 }
+// the split plan of a problem whose slabs are at p->kv_ws: key blocks, queries per chunk; returns the number of chunks (= slabs)
+static int attn_split_plan(AttnParams* p) {
+  const int splits = attn_qsplits(p->B, p->H, p->Nq, p->Nk, p->causal);
+  p->kblocks = sdt_ceil_div(p->Nk, 128);
+  p->qchunk = sdt_ceil_div(sdt_ceil_div(p->Nq, splits), KT) * KT;
+  return sdt_ceil_div(p->Nq, p->qchunk);
+}
+static int attn_finish_blocks(const AttnParams& p) { return sdt_grid_1d((long)p.B * p.Nk * p.H * p.D / 8, 256, 1024); }
 
 // ================================================================== C ABI
 static int attn_fill(AttnParams* p, const SdtAttnDesc* d, const char* name) {
@@ -745,7 +804,7 @@ static void launch_fwd(const AttnParams& p, hipStream_t stream) {
   }
 }
 template <int DPP, int NS, int NB>
-static void launch_bwd(const AttnParams& p, hipStream_t stream) {
+static void launch_bwd(const AttnParams& p, bool with_dkv, hipStream_t stream) {  // with_dkv false: the dQ pass (and delta) alone
   static_assert(NB * 32 <= DPP && NS * 16 <= DPP, "image pitch too small");
   static bool set_q = false, set_kv = false;
   const size_t lds_dq = (size_t)2 * 2 * Img<DPP>::BYTES;
@@ -753,19 +812,62 @@ static void launch_bwd(const AttnParams& p, hipStream_t stream) {
   static bool set_kvs = false;
   ensure_lds(attn_bwd_dq_kernel<DPP, NS, NB>, lds_dq, &set_q);
   hipLaunchKernelGGL((attn_bwd_dq_kernel<DPP, NS, NB>), dim3(sdt_ceil_div(p.Nq, 128), p.H, p.B), dim3(256), lds_dq, stream, p);
+  if (!with_dkv) return;
   if (p.kv_ws) {
     AttnParams ps = p;
-    const int splits = attn_qsplits(p.B, p.H, p.Nq, p.Nk, p.causal);
-    ps.kblocks = sdt_ceil_div(p.Nk, 128);
-    ps.qchunk = sdt_ceil_div(sdt_ceil_div(p.Nq, splits), KT) * KT;
-    const int nsplit = sdt_ceil_div(p.Nq, ps.qchunk);
+    const int nsplit = attn_split_plan(&ps);
     ensure_lds(attn_bwd_dkv_kernel<DPP, NS, NB, true>, lds_dkv, &set_kvs);
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<DPP, NS, NB, true>), dim3(ps.kblocks * nsplit, p.H, p.B), dim3(256), lds_dkv, stream, ps);
-    hipLaunchKernelGGL(attn_kv_finish_kernel, dim3(sdt_grid_1d((long)p.B * p.Nk * p.H * p.D / 8, 256, 1024)), dim3(256), 0, stream, ps, nsplit);
+    hipLaunchKernelGGL(attn_kv_finish_kernel, dim3(attn_finish_blocks(p)), dim3(256), 0, stream, ps, nsplit);
   } else {
     ensure_lds(attn_bwd_dkv_kernel<DPP, NS, NB, false>, lds_dkv, &set_kv);
     hipLaunchKernelGGL((attn_bwd_dkv_kernel<DPP, NS, NB, false>), dim3(sdt_ceil_div(p.Nk, 128), p.H, p.B), dim3(256), lds_dkv, stream, p);
   }
+}
+template <int DPP, int NS, int NB>
+static void launch_dkv_group(const AttnGroupParams& gp, hipStream_t stream) {
+  static bool set_g = false;
+  const size_t lds_dkv = (size_t)2 * (2 * Img<DPP>::BYTES + 2 * KT * sizeof(float));
+  ensure_lds(attn_bwd_dkv_group_kernel<DPP, NS, NB>, lds_dkv, &set_g);
+  hipLaunchKernelGGL((attn_bwd_dkv_group_kernel<DPP, NS, NB>), dim3(gp.wg_end[gp.n - 1]), dim3(256), lds_dkv, stream, gp);
+}
+
+// the kernel instantiation <DPP, NS, NB> of a head dim, as an index (attn_bwd_dispatch / attn_dkv_group_dispatch)
+static int attn_class(int D) { return D <= 48 ? 0 : D <= 64 ? 1 : D <= 80 ? 2 : D <= 96 ? 3 : D <= 128 ? 4 : 5; }
+static void attn_bwd_dispatch(const AttnParams& p, bool with_dkv, hipStream_t stream) {
+  switch (attn_class(p.D)) {
+    case 0: launch_bwd<64, 3, 2>(p, with_dkv, stream); break;
+    case 1: launch_bwd<64, 4, 2>(p, with_dkv, stream); break;
+    case 2: launch_bwd<128, 5, 3>(p, with_dkv, stream); break;
+    case 3: launch_bwd<128, 6, 3>(p, with_dkv, stream); break;
+    case 4: launch_bwd<128, 8, 4>(p, with_dkv, stream); break;
+    default: launch_bwd<256, 10, 5>(p, with_dkv, stream); break;
+  }
+}
+static void attn_dkv_group_dispatch(int cls, const AttnGroupParams& gp, hipStream_t stream) {
+  switch (cls) {
+    case 0: launch_dkv_group<64, 3, 2>(gp, stream); break;
+    case 1: launch_dkv_group<64, 4, 2>(gp, stream); break;
+    case 2: launch_dkv_group<128, 5, 3>(gp, stream); break;
+    case 3: launch_dkv_group<128, 6, 3>(gp, stream); break;
+    case 4: launch_dkv_group<128, 8, 4>(gp, stream); break;
+    default: launch_dkv_group<256, 10, 5>(gp, stream); break;
+  }
+}
+// descriptor + operand pointers -> the kernels' parameters (the backward's strides included); kv_ws is left to the caller
+static int attn_fill_bwd(AttnParams* p, const SdtAttnDesc* desc, const char* name, const uint16_t* q, const uint16_t* k, const uint16_t* v,
+                         const uint16_t* out, const uint16_t* dout, const float* lse, const float* delta, uint16_t* dq, uint16_t* dk,
+                         uint16_t* dv) {
+  int rc = attn_fill(p, desc, name);
+  if (rc) return rc;
+  p->q = (const bf16_t*)q; p->k = (const bf16_t*)k; p->v = (const bf16_t*)v; p->o = (const bf16_t*)out;
+  p->dout = (const bf16_t*)dout; p->lse = const_cast<float*>(lse); p->delta = delta;
+  p->dq = (bf16_t*)dq; p->dk = (bf16_t*)dk; p->dv = (bf16_t*)dv;
+  if (desc->ldgrad_q) { p->lddq = desc->ldgrad_q; p->bsdq = (long)p->Nq * p->lddq; }
+  if (desc->ldgrad_k) { p->lddk = desc->ldgrad_k; p->bsdk = (long)p->Nk * p->lddk; }
+  if (desc->ldgrad_v) { p->lddv = desc->ldgrad_v; p->bsdv = (long)p->Nk * p->lddv; }
+  if (desc->ld_dout) { p->lddo = desc->ld_dout; p->bsdo = (long)p->Nq * p->lddo; }
+  return SDT_OK;
 }
 
 extern "C" {
@@ -793,11 +895,17 @@ int sdt_attention_fwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, u
  * query range (each chunk writes its own slab, a finishing pass adds them in order: no atomics) */
 int64_t sdt_attention_bwd_workspace_bytes(const SdtAttnDesc* d) {
   if (!d || d->B <= 0 || d->H <= 0 || d->Nq <= 0 || d->Nk <= 0 || d->D <= 0) return 0;
-  int64_t n = (int64_t)d->B * d->H * d->Nq;
-  n = (n + 3) / 4 * 4;
+  return sdt_attention_bwd_delta_bytes(d) + sdt_attention_bwd_slab_bytes(d);
+}
+/* the two parts of that scratch: delta (rounded up to 16 bytes), and the slabs of the split dK/dV pass (0 when it does not split) */
+int64_t sdt_attention_bwd_delta_bytes(const SdtAttnDesc* d) {
+  if (!d || d->B <= 0 || d->H <= 0 || d->Nq <= 0 || d->Nk <= 0 || d->D <= 0) return 0;
+  return ((int64_t)d->B * d->H * d->Nq + 3) / 4 * 4 * (int64_t)sizeof(float);
+}
+int64_t sdt_attention_bwd_slab_bytes(const SdtAttnDesc* d) {
+  if (!d || d->B <= 0 || d->H <= 0 || d->Nq <= 0 || d->Nk <= 0 || d->D <= 0) return 0;
   const int qs = attn_qsplits(d->B, d->H, d->Nq, d->Nk, d->causal);
-  if (qs > 1) n += (int64_t)qs * 2 * d->B * d->Nk * d->H * d->D;
-  return n * (int64_t)sizeof(float);
+  return qs > 1 ? (int64_t)qs * 2 * d->B * d->Nk * d->H * d->D * (int64_t)sizeof(float) : 0;
 }
 
 // workspace: sdt_attention_bwd_workspace_bytes(desc) bytes (at least B*H*Nq floats: without the rest the query split is not used)
@@ -807,25 +915,86 @@ int sdt_attention_bwd(const uint16_t* q, const uint16_t* k, const uint16_t* v, c
   SDT_CHECK_ARG(q && k && v && out && dout && lse && dq && dk && dv && delta_ws, "sdt_attention_bwd: null pointer");
   SDT_CHECK_ARG(desc && workspace_bytes >= (int64_t)sizeof(float) * desc->B * desc->H * desc->Nq, "sdt_attention_bwd: workspace too small");
   AttnParams p = {};
-  int rc = attn_fill(&p, desc, "sdt_attention_bwd");
+  int rc = attn_fill_bwd(&p, desc, "sdt_attention_bwd", q, k, v, out, dout, lse, delta_ws, dq, dk, dv);
   if (rc) return rc;
-  p.q = (const bf16_t*)q; p.k = (const bf16_t*)k; p.v = (const bf16_t*)v; p.o = (const bf16_t*)out;
-  p.dout = (const bf16_t*)dout; p.lse = const_cast<float*>(lse); p.delta = delta_ws;
-  p.dq = (bf16_t*)dq; p.dk = (bf16_t*)dk; p.dv = (bf16_t*)dv;
-  if (desc->ldgrad_q) { p.lddq = desc->ldgrad_q; p.bsdq = (long)p.Nq * p.lddq; }
-  if (desc->ldgrad_k) { p.lddk = desc->ldgrad_k; p.bsdk = (long)p.Nk * p.lddk; }
-  if (desc->ldgrad_v) { p.lddv = desc->ldgrad_v; p.bsdv = (long)p.Nk * p.lddv; }
-  if (desc->ld_dout) { p.lddo = desc->ld_dout; p.bsdo = (long)p.Nq * p.lddo; }
   if (attn_qsplits(p.B, p.H, p.Nq, p.Nk, p.causal) > 1 && workspace_bytes >= sdt_attention_bwd_workspace_bytes(desc))
     p.kv_ws = delta_ws + ((long)p.B * p.H * p.Nq + 3) / 4 * 4;
-  const int D = p.D;
-  if (D <= 48) launch_bwd<64, 3, 2>(p, stream);
-  else if (D <= 64) launch_bwd<64, 4, 2>(p, stream);
-  else if (D <= 80) launch_bwd<128, 5, 3>(p, stream);
-  else if (D <= 96) launch_bwd<128, 6, 3>(p, stream);
-  else if (D <= 128) launch_bwd<128, 8, 4>(p, stream);
-  else launch_bwd<256, 10, 5>(p, stream);
+  attn_bwd_dispatch(p, true, stream);
   SDT_LAUNCH_CHECK("sdt_attention_bwd");
+  return SDT_OK;
+}
+
+// the dQ pass of sdt_attention_bwd alone: dq, and delta (B*H*Nq floats) for a later sdt_attention_bwd_dkv_group
+int sdt_attention_bwd_dq(const uint16_t* q, const uint16_t* k, const uint16_t* v, const uint16_t* out, const uint16_t* dout,
+                         const float* lse, uint16_t* dq, float* delta, const SdtAttnDesc* desc, hipStream_t stream) {
+  SDT_CHECK_ARG(q && k && v && out && dout && lse && dq && delta && desc, "sdt_attention_bwd_dq: null pointer");
+  AttnParams p = {};
+  int rc = attn_fill_bwd(&p, desc, "sdt_attention_bwd_dq", q, k, v, out, dout, lse, delta, dq, nullptr, nullptr);
+  if (rc) return rc;
+  attn_bwd_dispatch(p, false, stream);
+  SDT_LAUNCH_CHECK("sdt_attention_bwd_dq");
+  return SDT_OK;
+}
+
+int sdt_attention_bwd_dkv_group_max(void) { return ATTN_DKV_GROUP_ABI_MAX; }
+
+int sdt_attention_bwd_dkv_group(const SdtAttnDkvProblem* problems, int n, hipStream_t stream) {
+  SDT_CHECK_ARG(problems && n > 0 && n <= ATTN_DKV_GROUP_ABI_MAX, "sdt_attention_bwd_dkv_group: 1..%d problems", ATTN_DKV_GROUP_ABI_MAX);
+  static thread_local AttnParams ps[ATTN_DKV_GROUP_ABI_MAX];
+  static thread_local int nsplit[ATTN_DKV_GROUP_ABI_MAX], gxs[ATTN_DKV_GROUP_ABI_MAX];
+  long all_wgs = 0;  // every check runs before the first launch: a refused table launches nothing
+  for (int i = 0; i < n; ++i) {
+    const SdtAttnDkvProblem& q = problems[i];
+    SDT_CHECK_ARG(q.q && q.k && q.v && q.dout && q.lse && q.delta && q.dk && q.dv, "sdt_attention_bwd_dkv_group: problem %d: null pointer", i);
+    SDT_CHECK_ARG((((uintptr_t)q.q | (uintptr_t)q.k | (uintptr_t)q.v | (uintptr_t)q.dout | (uintptr_t)q.dk | (uintptr_t)q.dv |
+                    (uintptr_t)q.slabs | (uintptr_t)q.lse | (uintptr_t)q.delta) & 15) == 0,
+                  "sdt_attention_bwd_dkv_group: problem %d: pointers must be 16-byte aligned", i);
+    ps[i] = AttnParams{};
+    int rc = attn_fill_bwd(&ps[i], &q.desc, "sdt_attention_bwd_dkv_group", q.q, q.k, q.v, nullptr, q.dout, q.lse, q.delta, nullptr, q.dk, q.dv);
+    if (rc) return rc;
+    SDT_CHECK_ARG(ps[i].lddk % 8 == 0 && ps[i].lddv % 8 == 0 && ps[i].lddo % 8 == 0,
+                  "sdt_attention_bwd_dkv_group: problem %d: row strides must be multiples of 8", i);
+    nsplit[i] = 0;  // the plan of the single call with its full workspace: split where attn_qsplits says so, into the problem's own slabs
+    if (attn_qsplits(ps[i].B, ps[i].H, ps[i].Nq, ps[i].Nk, ps[i].causal) > 1) {
+      SDT_CHECK_ARG(q.slabs, "sdt_attention_bwd_dkv_group: problem %d: slabs of sdt_attention_bwd_slab_bytes() needed", i);
+      ps[i].kv_ws = q.slabs;
+      nsplit[i] = attn_split_plan(&ps[i]);
+    }
+    gxs[i] = nsplit[i] ? ps[i].kblocks * nsplit[i] : sdt_ceil_div(ps[i].Nk, 128);
+    all_wgs += (long)gxs[i] * ps[i].H * ps[i].B;  // (an upper bound of any one launch's grid)
+    SDT_CHECK_ARG(all_wgs < (1L << 30), "sdt_attention_bwd_dkv_group: too many workgroups");
+  }
+  AttnGroupParams gp;
+  for (int cls = 0; cls < 6; ++cls) {  // one launch per kernel instantiation present (ATTN_GROUP_MAX problems per launch)
+    gp.n = 0;
+    for (int i = 0; i <= n; ++i) {
+      if (i < n && attn_class(ps[i].D) == cls) {
+        const AttnParams& p = ps[i];
+        gp.prob[gp.n] = p;
+        gp.gx[gp.n] = gxs[i];
+        gp.wg_end[gp.n] = gxs[i] * p.H * p.B + (gp.n ? gp.wg_end[gp.n - 1] : 0);
+        ++gp.n;
+      }
+      if (gp.n == ATTN_GROUP_MAX || (i == n && gp.n > 0)) {
+        attn_dkv_group_dispatch(cls, gp, stream);
+        gp.n = 0;
+      }
+    }
+  }
+  gp.n = 0;
+  for (int i = 0; i <= n; ++i) {  // the finishing passes of all split problems
+    if (i < n && nsplit[i]) {
+      gp.prob[gp.n] = ps[i];
+      gp.gx[gp.n] = nsplit[i];
+      gp.wg_end[gp.n] = attn_finish_blocks(ps[i]) + (gp.n ? gp.wg_end[gp.n - 1] : 0);
+      ++gp.n;
+    }
+    if (gp.n == ATTN_GROUP_MAX || (i == n && gp.n > 0)) {
+      hipLaunchKernelGGL(attn_kv_finish_group_kernel, dim3(gp.wg_end[gp.n - 1]), dim3(256), 0, stream, gp);
+      gp.n = 0;
+    }
+  }
+  SDT_LAUNCH_CHECK("sdt_attention_bwd_dkv_group");
   return SDT_OK;
 }
 

@@ -1292,16 +1292,17 @@ __global__ void __launch_bounds__(256) embedding_retract_kernel(float* __restric
 // column sums: out[b][n] (+)= sum over the rows of batch slice b of dy[m][n].  Workgroup (x, y, z) sums rows_per_block rows of 256
 // columns of slice z into its own partial row; the workgroup that arrives last at (x, z) adds the partial rows in y order (no
 // float atomics) and writes the result: += into the fp32 db, or rounded into the bf16 out_bf (the per-image row-bias gradient).
-__global__ void __launch_bounds__(256) colsum_kernel(const bf16_t* __restrict__ dy, float* __restrict__ db, bf16_t* __restrict__ out_bf,
-                                                     long M, int N, int ld, int rows_per_block, long batch_stride_dy,
-                                                     int batch_stride_db, int* counters, float* __restrict__ part) {
-  dy += (long)blockIdx.z * batch_stride_dy;
+// The workgroup (bx, by, bz) of a (gx, gy, batch) grid: the single launch takes them from its grid, the grouped one from its table.
+__device__ __forceinline__ void colsum_body(const bf16_t* __restrict__ dy, float* __restrict__ db, bf16_t* __restrict__ out_bf, long M, int N,
+                                            int ld, int rows_per_block, long batch_stride_dy, int batch_stride_db, int* counters,
+                                            float* __restrict__ part, const int bx, const int by, const int bz, const int gx, const int gy) {
+  dy += (long)bz * batch_stride_dy;
   // thread (tx = column-vector of 8, ty = row lane); blockDim = 256 = 32 x 8
   __shared__ float red[8][32][8];
   __shared__ int s_last;
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
-  const int cv = blockIdx.x * 32 + tx;
-  const long m0 = (long)blockIdx.y * rows_per_block;
+  const int cv = bx * 32 + tx;
+  const long m0 = (long)by * rows_per_block;
   const long m1 = (m0 + rows_per_block < M) ? m0 + rows_per_block : M;
   float acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   if (cv * 8 < N) {
@@ -1315,23 +1316,60 @@ __global__ void __launch_bounds__(256) colsum_kernel(const bf16_t* __restrict__ 
 #pragma unroll
   for (int j = 0; j < 8; ++j) red[ty][tx][j] = acc[j];
   __syncthreads();
-  const int group = blockIdx.z * gridDim.x + blockIdx.x;
-  float* grp = part + (long)group * gridDim.y * 256;
+  const int group = bz * gx + bx;
+  float* grp = part + (long)group * gy * 256;
   {
     const int col = threadIdx.x;  // 256 columns of this workgroup
     float sum = 0.f;
 #pragma unroll
     for (int k = 0; k < 8; ++k) sum += red[k][col >> 3][col & 7];
-    sdt_store_wt(grp + (long)blockIdx.y * 256 + col, sum);
+    sdt_store_wt(grp + (long)by * 256 + col, sum);
   }
-  if (!sdt_arrive_last<true>(counters + group, (int)gridDim.y, &s_last)) return;
-  const int n = blockIdx.x * 256 + threadIdx.x;
+  if (!sdt_arrive_last<true>(counters + group, gy, &s_last)) return;
+  const int n = bx * 256 + threadIdx.x;
   if (n < N) {
     float t = 0.f;
-    for (int y = 0; y < (int)gridDim.y; ++y) t += sdt_load_wt(grp + (long)y * 256 + threadIdx.x);
-    if (out_bf) out_bf[(long)blockIdx.z * batch_stride_db + n] = f2bf(t);
-    else db[(long)blockIdx.z * batch_stride_db + n] += t;
+    for (int y = 0; y < gy; ++y) t += sdt_load_wt(grp + (long)y * 256 + threadIdx.x);
+    if (out_bf) out_bf[(long)bz * batch_stride_db + n] = f2bf(t);
+    else db[(long)bz * batch_stride_db + n] += t;
   }
+}
+__global__ void __launch_bounds__(256) colsum_kernel(const bf16_t* __restrict__ dy, float* __restrict__ db, bf16_t* __restrict__ out_bf,
+                                                     long M, int N, int ld, int rows_per_block, long batch_stride_dy,
+                                                     int batch_stride_db, int* counters, float* __restrict__ part) {
+  colsum_body(dy, db, out_bf, M, N, ld, rows_per_block, batch_stride_dy, batch_stride_db, counters, part, (int)blockIdx.x, (int)blockIdx.y,
+              (int)blockIdx.z, (int)gridDim.x, (int)gridDim.y);
+}
+
+// Several per-image column sums (sdt_colsum_batched_group) as one launch: the row-bias gradients of the ResBlocks are read only at
+// the end of the UNet backward, and one alone is a 12 us launch.  Workgroups in order (problem, image, row block, column block);
+// wg_end is the prefix table.  Each problem has its own counters and partial rows in the shared workspace and keeps the grid of its
+// single launch, so its sums are added in the same order.
+#define COLSUM_GROUP_MAX 32
+struct ColsumGroupItem {
+  const bf16_t* dy;
+  bf16_t* out;
+  long M;
+  int N, ld, rows_per_block, gx, gy;
+  int counter0;  // first counter of the problem
+  long part0;    // first partial-sum float of the problem
+};
+struct ColsumGroupParams {
+  int n;
+  int wg_end[COLSUM_GROUP_MAX];
+  ColsumGroupItem item[COLSUM_GROUP_MAX];
+};
+static_assert(sizeof(ColsumGroupParams) <= 4096, "the grouped column-sum launch passes its problem table as kernel arguments");
+__global__ void __launch_bounds__(256) colsum_group_kernel(const ColsumGroupParams gp, int* counters, float* __restrict__ part) {
+  const int blk = blockIdx.x;
+  int i = 0;
+  while (i + 1 < gp.n && blk >= gp.wg_end[i]) ++i;  // wave-uniform scalar walk
+  const int local = blk - (i ? gp.wg_end[i - 1] : 0);
+  const ColsumGroupItem it = gp.item[i];
+  const int bx = local % it.gx, rest = local / it.gx;
+  const int by = rest % it.gy, bz = rest / it.gy;
+  colsum_body(it.dy, nullptr, it.out, it.M, it.N, it.ld, it.rows_per_block, it.M * it.ld, it.N, counters + it.counter0, part + it.part0, bx, by,
+              bz, it.gx, it.gy);
 }
 
 // row bias gradient for the temb broadcast add: dt[b][n] = sum_{m in batch b} dy[m][n]  -> bf16 (B, N)
@@ -1989,14 +2027,22 @@ int64_t sdt_colsum_workspace_bytes(int batch, int64_t rows_per_batch, int N) {
   return colsum_ws_need(ncb * batch, (int)((rows_per_batch + 63) / 64));
 }
 
-static int colsum_launch(const uint16_t* dy, float* db, uint16_t* out_bf, int batch, int64_t rows, int N, int ld, int want_blocks,
-                         void* workspace, int64_t workspace_bytes, const char* name, hipStream_t stream) {
+// the grid (ncb column blocks, nby row blocks, batch) of a column sum and its rows per block
+static void colsum_plan(int batch, int64_t rows, int N, int want_blocks, int* ncb_out, int* nby_out, int* rpb_out) {
   const int ncb = sdt_ceil_div(sdt_ceil_div(N, 8), 32);
   int nby = (int)((rows + 63) / 64);
   const int want = (want_blocks + ncb * batch - 1) / (ncb * batch);
   if (nby > want) nby = want;
   const int rpb = (int)((rows + nby - 1) / nby);
-  nby = sdt_ceil_div(rows, rpb);
+  *ncb_out = ncb;
+  *nby_out = sdt_ceil_div(rows, rpb);
+  *rpb_out = rpb;
+}
+
+static int colsum_launch(const uint16_t* dy, float* db, uint16_t* out_bf, int batch, int64_t rows, int N, int ld, int want_blocks,
+                         void* workspace, int64_t workspace_bytes, const char* name, hipStream_t stream) {
+  int ncb, nby, rpb;
+  colsum_plan(batch, rows, N, want_blocks, &ncb, &nby, &rpb);
   SDT_CHECK_ARG((int64_t)ncb * batch * (int64_t)sizeof(int) <= SDT_WS_COUNTER_BYTES, "%s: too many column groups", name);
   SDT_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= colsum_ws_need(ncb * batch, nby),
                 "%s: workspace of sdt_colsum_workspace_bytes() needed", name);
@@ -2027,6 +2073,49 @@ int sdt_colsum_batched_bf16(const uint16_t* dy, uint16_t* out, int batch, int64_
   int rc = colsum_launch(dy, nullptr, out, batch, rows_per_batch, N, ld, 512, workspace, workspace_bytes, "sdt_colsum_batched_bf16", stream);
   if (rc) return rc;
   SDT_LAUNCH_CHECK("sdt_colsum_batched_bf16");
+  return SDT_OK;
+}
+
+int sdt_colsum_batched_group_max(void) { return COLSUM_GROUP_MAX; }
+
+static bool colsum_problem_ok(const SdtColsumProblem& q) {
+  return q.dy && q.out && q.batch > 0 && q.batch < 65536 && q.rows_per_batch > 0 && q.N > 0 && q.ld >= q.N && q.ld % 8 == 0 &&
+         ((uintptr_t)q.dy & 15) == 0;
+}
+// the problems' grids, counters and partial rows laid out back to back; returns the workspace bytes (0: a bad table)
+static int64_t colsum_group_plan(const SdtColsumProblem* q, int n, ColsumGroupParams* gp) {
+  if (!q || n <= 0 || n > COLSUM_GROUP_MAX) return 0;
+  long counters = 0, parts = 0, wgs = 0;
+  for (int i = 0; i < n; ++i) {
+    if (!colsum_problem_ok(q[i])) return 0;
+    int ncb, nby, rpb;
+    colsum_plan(q[i].batch, q[i].rows_per_batch, q[i].N, 512, &ncb, &nby, &rpb);  // (512: sdt_colsum_batched_bf16's own)
+    wgs += (long)ncb * nby * q[i].batch;
+    if (wgs >= (1L << 30)) return 0;
+    if (gp) {
+      gp->item[i] = ColsumGroupItem{(const bf16_t*)q[i].dy, (bf16_t*)q[i].out, (long)q[i].rows_per_batch, q[i].N, q[i].ld, rpb, ncb, nby,
+                                    (int)counters, parts};
+      gp->wg_end[i] = (int)wgs;
+    }
+    counters += (long)ncb * q[i].batch;
+    parts += (long)ncb * q[i].batch * nby * 256;
+  }
+  if (counters * (long)sizeof(int) > SDT_WS_COUNTER_BYTES) return 0;
+  if (gp) gp->n = n;
+  return SDT_WS_COUNTER_BYTES + parts * (int64_t)sizeof(float);
+}
+
+int64_t sdt_colsum_batched_group_workspace_bytes(const SdtColsumProblem* problems, int n) { return colsum_group_plan(problems, n, nullptr); }
+
+int sdt_colsum_batched_group(const SdtColsumProblem* problems, int n, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
+  ColsumGroupParams gp;
+  const int64_t need = colsum_group_plan(problems, n, &gp);
+  SDT_CHECK_ARG(need > 0, "sdt_colsum_batched_group: bad args (1..%d problems, each as sdt_colsum_batched_bf16 takes them)", COLSUM_GROUP_MAX);
+  SDT_CHECK_ARG(workspace && ((uintptr_t)workspace & 15) == 0 && workspace_bytes >= need,
+                "sdt_colsum_batched_group: workspace of sdt_colsum_batched_group_workspace_bytes() needed");
+  hipLaunchKernelGGL(colsum_group_kernel, dim3(gp.wg_end[n - 1]), dim3(256), 0, stream, gp, reinterpret_cast<int*>(workspace),
+                     reinterpret_cast<float*>((unsigned char*)workspace + SDT_WS_COUNTER_BYTES));
+  SDT_LAUNCH_CHECK("sdt_colsum_batched_group");
   return SDT_OK;
 }
 

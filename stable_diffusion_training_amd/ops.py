@@ -303,22 +303,86 @@ _CONV_QUEUE = []  # deferred convolution weight gradients (sdt_conv_wgrad_group)
 _NORM_QUEUE = []  # deferred LayerNorm parameter-gradient sums (sdt_norm_param_grads_group): (job, workspace kept alive, store, paths)
 
 
+# Two more families leave the chain the same way (offchain=True, the default): the dK/dV pass of a cross-attention whose [k|v] is a
+# column slice of a grouped projection, and the per-image column sums behind a ResBlock's row bias when that is such a slice.  Their
+# only reader is _ColSlices.backward, which runs after the last block of its width: it flushes both queues first (flush_offchain),
+# and so does the closing context.  sdt_attention_bwd_dkv_group / sdt_colsum_batched_group run every problem with the plan of its
+# single launch, so the step is the same bit for bit.
+_DKV_QUEUE = []     # deferred dK/dV passes: (SdtAttnDkvProblem, tensors kept alive)
+_COLSUM_QUEUE = []  # deferred row-bias column sums: (SdtColsumProblem, tensors kept alive)
+_OFFCHAIN = False
+
+
 class wgrad_grouping:
+    """offchain=False keeps the cross-attention dK/dV passes and the row-bias column sums inline (tests compare the two forms)."""
+
+    def __init__(self, offchain=True):
+        self.offchain = bool(offchain)
+
     def __enter__(self):
-        global _WGRAD_QUEUE
-        self.prev = _WGRAD_QUEUE
+        global _WGRAD_QUEUE, _OFFCHAIN
+        self.prev = (_WGRAD_QUEUE, _OFFCHAIN)
         _WGRAD_QUEUE = []
+        _OFFCHAIN = self.offchain
         return self
 
     def __exit__(self, *exc):
-        global _WGRAD_QUEUE
+        global _WGRAD_QUEUE, _OFFCHAIN
         try:
             if exc[0] is None:
                 flush_wgrads()
+                flush_offchain()
         finally:
-            _WGRAD_QUEUE = self.prev
+            _WGRAD_QUEUE, _OFFCHAIN = self.prev
             del _NORM_QUEUE[:]
             del _CONV_QUEUE[:]
+            del _DKV_QUEUE[:]
+            del _COLSUM_QUEUE[:]
+
+
+def _slice_tag(t):
+    """The use counter of a col_slices() output, counted up: deferring the gradient of `t` needs _ColSlices.backward as its ONLY reader
+    (it flushes first; a second consumer would have autograd add to a gradient that is not written yet).  None for any other tensor.
+    Only the operators that defer count themselves (conv2d's row bias, the packed attentions' [k|v]): nets hands each slice to exactly
+    one of them.  A slice that also feeds an operator that does not count itself is caught where it would do harm: the tag remembers
+    the deferred gradient (_note_deferred) and _ColSlices.backward refuses any other tensor in its place.
+    tag = [uses, the deferred gradient tensor or None], shared with the slice's _ColSlices node."""
+    tag = getattr(t, "_sdt_col_slice", None)
+    if tag is not None:
+        tag[0] += 1
+    return tag
+
+
+def _deferrable(tag):
+    return _OFFCHAIN and _WGRAD_QUEUE is not None and tag is not None and tag[0] == 1
+
+
+def _note_deferred(tag, grad):
+    tag[1] = grad
+
+
+def defer_colsum(dy, out, batch, rows_per_batch, N, ld):
+    _COLSUM_QUEUE.append((_lib.SdtColsumProblem(dy.data_ptr(), out.data_ptr(), batch, rows_per_batch, N, ld), (dy, out)))
+
+
+def flush_offchain():
+    """The queued dK/dV passes (one launch per kernel instantiation, one for the finishing passes) and column sums (one launch)."""
+    if _DKV_QUEUE:
+        step = _lib.load().sdt_attention_bwd_dkv_group_max()
+        for i in range(0, len(_DKV_QUEUE), step):
+            jobs = _DKV_QUEUE[i: i + step]
+            arr = (_lib.SdtAttnDkvProblem * len(jobs))(*[j[0] for j in jobs])
+            call("sdt_attention_bwd_dkv_group", arr, len(jobs), _stream())
+        del _DKV_QUEUE[:]
+    if _COLSUM_QUEUE:
+        lib = _lib.load()
+        step = lib.sdt_colsum_batched_group_max()
+        for i in range(0, len(_COLSUM_QUEUE), step):
+            jobs = _COLSUM_QUEUE[i: i + step]
+            arr = (_lib.SdtColsumProblem * len(jobs))(*[j[0] for j in jobs])
+            ws = reduce_workspace(lib.sdt_colsum_batched_group_workspace_bytes(arr, len(jobs)), jobs[0][1][0].device)
+            call("sdt_colsum_batched_group", arr, len(jobs), ws.data_ptr(), ws.numel(), _stream())
+        del _COLSUM_QUEUE[:]
 
 
 def flush_norm_grads():
@@ -619,6 +683,7 @@ class _Conv2d(Function):
                 gn_stats=stats, gn_groups=gn_groups if stats is not None else 0, b_kmajor=True)  # HWIO kernel: [tap][in][out]
         ctx.save_for_backward(x)
         ctx.meta = (store, wpath, bpath, geom, plain, rowbias is not None, residual is not None)
+        ctx.rb_tag = None if rowbias is None else _slice_tag(rowbias)
         if gn_groups:
             ctx.set_materialize_grads(False)  # no zero-filled "gradient" for the statistics output
             if stats is not None:
@@ -655,9 +720,13 @@ class _Conv2d(Function):
         drb = None
         if has_rb:  # gradient of the broadcast (B, Cout) row bias = per-image column sums (ordered partial sums, one launch)
             drb = torch.empty(B, lf.Cp, dtype=BF16, device=x.device)
-            ws = reduce_workspace(_lib.load().sdt_colsum_workspace_bytes(B, geom.out_h * geom.out_w, lf.Cp), x.device)
-            call("sdt_colsum_batched_bf16", dy.data_ptr(), drb.data_ptr(), B, geom.out_h * geom.out_w, lf.Cp, lf.Cp, ws.data_ptr(),
-                 ws.numel(), _stream())
+            if _deferrable(ctx.rb_tag):  # read only by _ColSlices.backward, at the end of the UNet backward: joins the grouped launch
+                defer_colsum(dy, drb, B, geom.out_h * geom.out_w, lf.Cp, lf.Cp)
+                _note_deferred(ctx.rb_tag, drb)
+            else:
+                ws = reduce_workspace(_lib.load().sdt_colsum_workspace_bytes(B, geom.out_h * geom.out_w, lf.Cp), x.device)
+                call("sdt_colsum_batched_bf16", dy.data_ptr(), drb.data_ptr(), B, geom.out_h * geom.out_w, lf.Cp, lf.Cp, ws.data_ptr(),
+                     ws.numel(), _stream())
         return dx, drb, (dy if has_res else None), None, None, None, None, None, None
 
 
@@ -848,12 +917,20 @@ class _ColSlices(Function):
     def forward(ctx, y, n):
         ctx.set_materialize_grads(False)
         ctx.n = n
+        ctx.tags = [[0, None] for _ in range(n)]  # per slice: uses by deferring operators, the deferred gradient (_slice_tag)
         C = y.shape[-1] // n
         return tuple(y[..., i * C: (i + 1) * C] for i in range(n))
 
     @staticmethod
     def backward(ctx, *grads):
         n = ctx.n
+        flush_offchain()  # the slices' gradients may still be queued (deferred dK/dV passes and column sums): this is their reader
+        for i, (g, tag) in enumerate(zip(grads, ctx.tags)):
+            want, tag[1] = tag[1], None
+            if want is not None and (g is None or g.data_ptr() != want.data_ptr()):
+                # autograd added another consumer's gradient to the deferred one while that was not written yet
+                raise _lib.SdtError(f"col_slices: the gradient of slice {i} was deferred (wgrad_grouping) but the slice has a second consumer; "
+                                    "its sum was formed from an unwritten buffer")
         g0 = next((g for g in grads if g is not None), None)
         if g0 is None:
             return None, None
@@ -865,7 +942,12 @@ class _ColSlices(Function):
 
 
 def col_slices(y, n):
-    return _ColSlices.apply(y, n)
+    out = _ColSlices.apply(y, n)
+    node = out[0].grad_fn  # the Function's ctx (None without a tape: no gradient, nothing to defer or to check)
+    tags = node.tags if node is not None else [[0, None] for _ in range(n)]
+    for t, tag in zip(out, tags):
+        t._sdt_col_slice = tag
+    return out
 
 
 def fanout(x, n):
@@ -1209,6 +1291,7 @@ class _AttentionPacked(Function):
         call("sdt_attention_fwd", q, k, v, out.data_ptr(), lse.data_ptr(), _lib.ctypes.addressof(desc), _stream())
         ctx.save_for_backward(a, b, out, lse)
         ctx.desc, ctx.C = desc, C
+        ctx.kv_tag = None if b is None else _slice_tag(b)
         return out
 
     @staticmethod
@@ -1224,11 +1307,28 @@ class _AttentionPacked(Function):
         else:
             q, k, v = a.data_ptr(), b.data_ptr(), b.data_ptr() + 2 * C
             dq, dk, dv = da.data_ptr(), db.data_ptr(), db.data_ptr() + 2 * C
+        if _deferrable(ctx.kv_tag):
+            _attention_bwd_deferred(ctx.desc, q, k, v, out, dout, lse, dq, dk, dv, (a, b, db, ctx.key_weight))
+            _note_deferred(ctx.kv_tag, db)
+            return da, db, None, None, None, None
         need = _lib.load().sdt_attention_bwd_workspace_bytes(_lib.ctypes.addressof(ctx.desc))
         ws = torch.empty(need, dtype=torch.uint8, device=a.device)
         call("sdt_attention_bwd", q, k, v, out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dq, dk, dv, ws.data_ptr(), need,
              _lib.ctypes.addressof(ctx.desc), _stream())
         return da, db, None, None, None, None
+
+
+def _attention_bwd_deferred(desc, q, k, v, out, dout, lse, dq, dk, dv, keep):
+    """The dQ pass now (it also writes delta); the dK/dV pass is queued for flush_offchain with delta and slabs of its own - the
+    scratch of the inline call would be reused by the next block."""
+    lib = _lib.load()
+    dp = _lib.ctypes.addressof(desc)
+    delta = torch.empty(lib.sdt_attention_bwd_delta_bytes(dp) // 4, dtype=torch.float32, device=out.device)
+    nslab = lib.sdt_attention_bwd_slab_bytes(dp)
+    slabs = torch.empty(nslab // 4, dtype=torch.float32, device=out.device) if nslab else None
+    call("sdt_attention_bwd_dq", q, k, v, out.data_ptr(), dout.data_ptr(), lse.data_ptr(), dq, delta.data_ptr(), dp, _stream())
+    prob = _lib.SdtAttnDkvProblem(q, k, v, dout.data_ptr(), lse.data_ptr(), delta.data_ptr(), dk, dv, _ptr(slabs), desc)
+    _DKV_QUEUE.append((prob, (dout, lse, delta, slabs) + tuple(keep)))
 
 
 def attention_packed(a, b, heads, scale, causal=False, key_weight=None):
@@ -1272,6 +1372,7 @@ class _AttentionIP(Function):
              C, ld_ip, scale, _stream())
         ctx.save_for_backward(q, kv_txt, kv_ip, o_txt, lse, scale_ip)
         ctx.desc, ctx.dims = desc, (B, heads, Nq, T, D, C, ld_ip, scale)
+        ctx.kv_tag = _slice_tag(kv_txt)
         return out
 
     @staticmethod
@@ -1281,11 +1382,16 @@ class _AttentionIP(Function):
         dout = dout.contiguous()
         dq_txt = torch.empty_like(q)
         dkv_txt = torch.empty(kv_txt.shape, dtype=BF16, device=q.device)
-        need = _lib.load().sdt_attention_bwd_workspace_bytes(_lib.ctypes.addressof(ctx.desc))
-        ws = torch.empty(need, dtype=torch.uint8, device=q.device)
-        call("sdt_attention_bwd", q.data_ptr(), kv_txt.data_ptr(), kv_txt.data_ptr() + 2 * C, o_txt.data_ptr(), dout.data_ptr(),
-             lse.data_ptr(), dq_txt.data_ptr(), dkv_txt.data_ptr(), dkv_txt.data_ptr() + 2 * C, ws.data_ptr(), need,
-             _lib.ctypes.addressof(ctx.desc), _stream())
+        if _deferrable(ctx.kv_tag):  # the text term's dK/dV joins the grouped launch; its dQ is needed below
+            _attention_bwd_deferred(ctx.desc, q.data_ptr(), kv_txt.data_ptr(), kv_txt.data_ptr() + 2 * C, o_txt, dout, lse, dq_txt.data_ptr(),
+                                    dkv_txt.data_ptr(), dkv_txt.data_ptr() + 2 * C, (q, kv_txt, dkv_txt, ctx.key_weight))
+            _note_deferred(ctx.kv_tag, dkv_txt)
+        else:
+            need = _lib.load().sdt_attention_bwd_workspace_bytes(_lib.ctypes.addressof(ctx.desc))
+            ws = torch.empty(need, dtype=torch.uint8, device=q.device)
+            call("sdt_attention_bwd", q.data_ptr(), kv_txt.data_ptr(), kv_txt.data_ptr() + 2 * C, o_txt.data_ptr(), dout.data_ptr(),
+                 lse.data_ptr(), dq_txt.data_ptr(), dkv_txt.data_ptr(), dkv_txt.data_ptr() + 2 * C, ws.data_ptr(), need,
+                 _lib.ctypes.addressof(ctx.desc), _stream())
         dq = torch.empty_like(q)
         dkv_ip = torch.empty(B, T, 2 * C, dtype=BF16, device=q.device)
         need = _lib.load().sdt_ip_attention_bwd_workspace_bytes(B, heads, Nq, T, D)
