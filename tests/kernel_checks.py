@@ -13,7 +13,11 @@ element or overwritten destination, mirrors of the reduction launchers' partitio
 the posterior-sample and timestep-embedding bounds, and the case tables with the bound that makes each of them exact.
 
 The last part serves tests/test_gpu_norm_exact.py: balanced norm inputs whose float64 result is exactly representable, the expectation
-with the assertions that make it unique, a mirror of the GroupNorm launch geometry for failure reports, and the case tables."""
+with the assertions that make it unique, a mirror of the GroupNorm launch geometry for failure reports, and the case tables.
+
+The end serves tests/test_gpu_grouped_exact.py: the problem tables of the grouped dK/dV and column-sum launches, mirrors of their
+launch lists, workgroup decode and workspace, and the per-problem expectations."""
+import functools
 import math
 
 import numpy as np
@@ -1575,3 +1579,161 @@ def clip_pool_case(D, R, windows, S, eos_id, seed):
     for r in range(R):
         x[r * windows, int(pos[r])] = rows["x"][r]
     return dict(ids=ids, pos=pos, x=x, rows=rows)
+
+
+# ================================================================================================ grouped off-chain launches
+# (tests/test_gpu_grouped_exact.py; their proof on the CPU: tests/test_kernel_checks_cpu.py)
+# sdt_attention_bwd_dkv_group: (B, H, Nq, Nk, D, kind, packed, key_weights, causal); kind "pair" (pair_case / pair_expect) or
+# "selector" (selector_case / selector_expect).  Operands are seeded with Nq + Nk + D, as the single-launch tables are.
+ATTN_CLASS_TOPS = (48, 64, 80, 96, 128, 160)  # the largest head dim of each instantiation (attention.hip attn_class)
+ATTN_GROUP_LAUNCH = 8                         # problems per grouped launch (attention.hip ATTN_GROUP_MAX)
+ATTN_GROUP_ABI = 32                           # problems per sdt_attention_bwd_dkv_group call
+
+
+def _pair(B, H, Nq, Nk, D, packed=False):
+    return (B, H, Nq, Nk, D, "pair", packed, False, False)
+
+
+def _sel(B, H, Nq, Nk, D, key_weights=False, causal=False):
+    return (B, H, Nq, Nk, D, "selector", False, key_weights, causal)
+
+
+# One table for one call.  The eleven problems with D <= 48 (more than one launch of that instantiation) are spread between the other
+# five instantiations, so the members of a class are picked out of the table, never a run of it.
+DKV_GROUP_MIXED = [
+    _pair(1, 1, 64, 77, 40),               # baseline
+    _pair(1, 2, 64, 77, 64),
+    _pair(3, 2, 70, 77, 40, True),         # ragged Nq, B = 3, halves of packed [k|v] / [dk|dv]
+    _pair(1, 2, 1024, 77, 72, True),       # split
+    _pair(2, 3, 64, 200, 32),              # two key blocks, unsplit (gx = 2), H = 3
+    _pair(1, 2, 64, 77, 160),
+    _pair(1, 2, 1024, 77, 40, True),       # split 4 x 256
+    _pair(1, 2, 64, 77, 96),
+    _pair(1, 1, 1030, 130, 48),            # split with two key blocks, 4 chunks of 320 (the last ragged), B*H*Nq % 4 == 2
+    _sel(2, 2, 77, 77, 64, causal=True),
+    _sel(2, 2, 64, 77, 8, key_weights=True),
+    _pair(1, 2, 1024, 77, 120),            # split
+    _pair(1, 1, 64, 16, 24),
+    _pair(2, 1, 130, 77, 16),
+    _sel(2, 2, 256, 77, 80, key_weights=True),
+    _pair(1, 3, 64, 77, 48),
+    _pair(1, 4, 128, 5, 16),               # odd tiny Nk
+    _pair(1, 1, 64, 300, 152),             # three key blocks, unsplit
+    _pair(1, 1, 64, 1, 8),                 # one key: dK exactly zero
+]
+
+# Ten split problems: nine of the instantiation D <= 48 (a second launch of it) and one of <128,5,3> at table index 1, so the
+# finishing pass (two launches: table indices 0..7 and 8..9) is indexed differently from either dK/dV table.
+DKV_GROUP_SPLITS = [
+    _pair(1, 1, 1024, 16, 8), _pair(1, 2, 1024, 77, 72), _pair(1, 1, 1024, 33, 8), _pair(2, 1, 1024, 16, 8), _pair(1, 2, 1024, 20, 16),
+    _pair(1, 1, 1280, 16, 8), _pair(1, 1, 1024, 77, 8),
+    _pair(1, 1, 1600, 16, 8),              # plans 6 chunks, launches 5 of 320
+    _pair(1, 2, 1024, 5, 8), _pair(1, 1, 1088, 2, 8),
+]
+
+# The ABI limit: 32 tiny pair problems over three instantiations (13 of D <= 48, 7 of D = 64, 12 of D in {72, 80}); B, H, Nq, Nk and D
+# cycle with periods 2, 3, 2 (of three), 4 and 5
+DKV_GROUP_FULL = [_pair(1 + i % 2, 1 + i % 3, (64, 70)[(i // 3) % 2], (2, 5, 16, 77)[i % 4], (8, 64, 80, 24, 72)[i % 5]) for i in range(ATTN_GROUP_ABI)]
+
+
+def attention_class(D):
+    """Index of the instantiation of head dim D (attention.hip attn_class)."""
+    return next(i for i, top in enumerate(ATTN_CLASS_TOPS) if D <= top)
+
+
+def group_key_weights(Nk):
+    """Key weights of the grouped selector problems: 1, 2, 3 and 1/2 in turn (float32 (Nk,))."""
+    return torch.tensor([1.0, 2.0, 3.0, 0.5])[torch.arange(Nk) % 4].contiguous()
+
+
+def dkv_group_plan(spec):
+    """(planned, chunk, launched, kblocks, gx) of one problem: attention_qsplit, the key blocks of 128, and the workgroups per (image,
+    head) of its dK/dV pass (sdt_attention_bwd_dkv_group: kblocks * launched where it splits, else kblocks)."""
+    B, H, Nq, Nk = spec[:4]
+    planned, chunk, launched = attention_qsplit(B, H, Nq, Nk, spec[8])
+    kblocks = -(-Nk // 128)
+    return planned, chunk, launched, kblocks, kblocks * launched if planned > 1 else kblocks
+
+
+def dkv_group_launches(table):
+    """(dkv, finish): the launches of one sdt_attention_bwd_dkv_group call as lists of table indices - per instantiation in class
+    order, ATTN_GROUP_LAUNCH problems each, then the finishing passes of the split problems in table order, eight each."""
+    dkv = []
+    for cls in range(len(ATTN_CLASS_TOPS)):
+        mine = [i for i, s in enumerate(table) if attention_class(s[4]) == cls]
+        dkv += [mine[j: j + ATTN_GROUP_LAUNCH] for j in range(0, len(mine), ATTN_GROUP_LAUNCH)]
+    split = [i for i, s in enumerate(table) if dkv_group_plan(s)[0] > 1]
+    return dkv, [split[j: j + ATTN_GROUP_LAUNCH] for j in range(0, len(split), ATTN_GROUP_LAUNCH)]
+
+
+def dkv_group_cover(table, h_of_first=False):
+    """The workgroups of the grouped dK/dV launches decoded as attn_bwd_dkv_group_kernel decodes them (problem by the prefix table,
+    rest = local / gx, bx = local - rest * gx, b = rest / H, h = rest - b * H): a dict (table index, b, h, bx) -> how many workgroups
+    land there.  h_of_first: the planted fault - every problem decoded with the H of its launch's first problem."""
+    seen = {}
+    for launch in dkv_group_launches(table)[0]:
+        for i in launch:
+            B, H = table[i][:2]
+            gx = dkv_group_plan(table[i])[4]
+            Hd = table[launch[0]][1] if h_of_first else H
+            for local in range(gx * H * B):  # (the host sizes the prefix table with the problem's own B and H)
+                rest, bx = divmod(local, gx)
+                b, h = divmod(rest, Hd)
+                seen[(i, b, h, bx)] = seen.get((i, b, h, bx), 0) + 1
+    return seen
+
+
+@functools.lru_cache(maxsize=None)
+def dkv_group_problem(spec):
+    """(case, want) of one table entry.  want: dict(o, dk, dv bf16; dq bf16 for pair problems, None for selector ones (zero by value,
+    dk too); lse2 float64) - pair_expect with the problem's own query chunk, or selector_expect."""
+    B, H, Nq, Nk, D, kind, packed, kw, causal = spec
+    scale = D ** -0.5
+    if kind == "pair":
+        assert not kw and not causal
+        case = pair_case(B, H, Nq, Nk, D, seed=Nq + Nk + D)
+        planned, chunk, _ = attention_qsplit(B, H, Nq, Nk, False)
+        exp = pair_expect(case, B, H, Nq, Nk, D, scale, kv_chunk=chunk if planned > 1 else None)
+        return case, {n: exp[n] for n in ("o", "dq", "dk", "dv", "lse2")}
+    case = selector_case(B, H, Nq, Nk, D, causal, seed=Nq + Nk + D)
+    o, lse2, dv = selector_expect(case, B, H, Nq, Nk, D, scale, group_key_weights(Nk) if kw else None)
+    return case, dict(o=o, dq=None, dk=torch.zeros_like(dv), dv=dv, lse2=lse2)
+
+
+def dkv_group_expect(table, h_of_first=False):
+    """Per table entry, the (dk, dv) the grouped call leaves: the problem's expectation on every (image, head, block of 128 keys)
+    whose workgroups - one per launched query chunk where the pass splits - each occur exactly once under dkv_group_cover, NaN (an
+    element nobody wrote) elsewhere.  With the true decode this is the expectation itself (the CPU proof asserts it)."""
+    seen = dkv_group_cover(table, h_of_first)
+    out = []
+    for i, spec in enumerate(table):
+        B, H, Nq, Nk, D = spec[:5]
+        planned, chunk, launched, kblocks, gx = dkv_group_plan(spec)
+        want = dkv_group_problem(spec)[1]
+        dk, dv = (torch.full_like(want[n], float("nan")) for n in ("dk", "dv"))
+        for b in range(B):
+            for h in range(H):
+                for kb in range(kblocks):
+                    wgs = [c * kblocks + kb for c in range(launched)] if planned > 1 else [kb]
+                    if all(seen.get((i, b, h, bx), 0) == 1 for bx in wgs):
+                        rows, cols = slice(kb * 128, min(Nk, kb * 128 + 128)), slice(h * D, (h + 1) * D)
+                        dk[b, rows, cols], dv[b, rows, cols] = want["dk"][b, rows, cols], want["dv"][b, rows, cols]
+        out.append((dk, dv))
+    return out
+
+
+# sdt_colsum_batched_group: (N, ld, rows, batch, range) as COLSUM_CASES.  32 problems (the limit of one call): batch, rows, N and the
+# pad of ld cycle with periods 5, 6, 6 (shifted every sixth entry) and 2; |value| <= 200 and rows <= 200 keep every sum below 2^24.
+COLSUM_GROUP_ABI = 32
+COLSUM_GROUP_MAXED = [((8, 13, 250, 256, 264, 520)[(i + i // 6) % 6], -(-(8, 13, 250, 256, 264, 520)[(i + i // 6) % 6] // 8) * 8 + 16 * (i % 2),
+                       (1, 7, 63, 64, 65, 200)[i % 6], 1 + i % 5, 200) for i in range(COLSUM_GROUP_ABI)]
+
+
+def colsum_group_workspace_bytes(table):
+    """sdt_colsum_batched_group_workspace_bytes: the counters and every problem's partial rows (its single launch's: colsum_plan with
+    the batched form's 512 blocks), back to back."""
+    total = CNT_BYTES
+    for N, ld, rows, batch, r in table:
+        ncb, nby, rpb, want = colsum_plan(batch, rows, N, 512)
+        total += 4 * ncb * batch * nby * 256
+    return total

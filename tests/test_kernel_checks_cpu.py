@@ -1031,3 +1031,147 @@ def test_groupnorm_geometry_mirror_is_the_librarys_and_the_cases_reach_their_bra
         want = ids.argmax(1) if eos < 0 else torch.where((ids == eos).any(1), (ids == eos).int().argmax(1), 0)
         assert torch.equal(want.to(torch.int32), cc["pos"]), (D, want, cc["pos"])
         kc.norm_exact_expectation(cc["rows"], 0, 0.0)
+
+
+# ================================================================================================ grouped off-chain launches
+# (the tables and mirrors of tests/test_gpu_grouped_exact.py)
+def _is_a_run(idx):
+    return idx == list(range(idx[0], idx[0] + len(idx)))
+
+
+def _dkv_table_facts(lib, table):
+    """Per entry: (class, planned, launched, kblocks, gx, split), with the mirrors held to the library's byte queries."""
+    from stable_diffusion_training_amd import _lib
+    facts = []
+    for spec in table:
+        B, H, Nq, Nk, D, kind, packed, kw, causal = spec
+        planned, chunk, launched, kblocks, gx = kc.dkv_group_plan(spec)
+        d = _lib.SdtAttnDesc(B, H, Nq, Nk, D, H * D, H * D, H * D, H * D, D ** -0.5, int(causal), 0, 0, 0, 0, None)
+        p = _lib.ctypes.addressof(d)
+        assert lib.sdt_attention_bwd_delta_bytes(p) == kc.attention_delta_bytes(B, H, Nq), spec
+        assert lib.sdt_attention_bwd_slab_bytes(p) == (planned * 2 * B * Nk * H * D * 4 if planned > 1 else 0), spec
+        assert launched <= planned and (launched - 1) * chunk < Nq <= launched * chunk and chunk % 64 == 0
+        assert kc.attention_instance(D)[:3] == kc.attention_instance(kc.ATTN_CLASS_TOPS[kc.attention_class(D)])[:3]
+        facts.append((kc.attention_class(D), planned, launched, kblocks, gx, planned > 1))
+    return facts
+
+
+def _dkv_inputs_are_exact(spec):
+    """A pair problem: pair_expect's own asserts ran in kc.dkv_group_problem; the tie is exactly 0, the lead at least 160 logits, dQ and
+    dK nonzero wherever there is more than one key (and exactly zero where there is one).  A selector problem: the lead
+    test_attention_selector_inputs_every_bit asserts - key weights of 1/2 .. 3 take at most ln 6 < 1.8 logits of it."""
+    B, H, Nq, Nk, D, kind, packed, kw, causal = spec
+    case, want = kc.dkv_group_problem(spec)
+    if kind == "pair":
+        tie, lead, top = kc.pair_min_gap(case, B, H, Nq, Nk, D, D ** -0.5)
+        assert tie == 0.0 and lead >= 2 * 32.0 ** 2 / D ** 0.5 - 1e-9 >= 161.9 and lead >= 160 and top < 3000, spec
+        for n in ("dq", "dk"):
+            for b in range(B):
+                for h in range(H):
+                    blk = want[n][b, :, h * D: (h + 1) * D]
+                    assert bool((blk != 0).any()) == (Nk > 1), (spec, n, b, h)
+        assert bool((want["dv"] != 0).any())
+    else:
+        gap, top = kc.selector_min_gap(case, B, H, Nq, Nk, D, D ** -0.5)
+        assert gap >= 2 * 32.0 ** 2 / D ** 0.5 - 1e-9 >= 161.9 and top < 3000, spec
+        assert gap - math.log(6.0) >= 160
+        if kw:
+            w = kc.group_key_weights(Nk)
+            assert set(w.tolist()) == {0.5, 1.0, 2.0, 3.0} if Nk >= 4 else True
+        if causal:
+            assert (case["target"] <= torch.arange(Nq)).all()
+
+
+def test_grouped_dkv_tables_hold_what_they_are_listed_for(lib):
+    from collections import Counter
+    assert lib.sdt_attention_bwd_dkv_group_max() == kc.ATTN_GROUP_ABI
+    # ---- DKV_GROUP_MIXED
+    tab = kc.DKV_GROUP_MIXED
+    facts = _dkv_table_facts(lib, tab)
+    per_class = Counter(f[0] for f in facts)
+    assert dict(per_class) == {0: 11, 1: 2, 2: 2, 3: 1, 4: 1, 5: 2} and len(tab) == len(set(tab)) == 19
+    for cls, n in per_class.items():
+        if n > 1:
+            assert not _is_a_run([i for i, f in enumerate(facts) if f[0] == cls]), f"class {cls} is one run of the table"
+    dkv, finish = kc.dkv_group_launches(tab)
+    assert [len(l) for l in dkv] == [8, 3, 2, 2, 1, 1, 2] and [len(l) for l in finish] == [4]
+    assert len({tab[i][0] for i in dkv[0]}) > 1 and len({tab[i][1] for i in dkv[0]}) > 1 and len({facts[i][4] for i in dkv[0]}) > 2  # B, H, gx differ inside one launch
+    assert any(not f[5] and f[4] > 1 for f in facts), "an unsplit problem with gx > 1"
+    assert any(not f[5] and f[3] == 3 for f in facts) and any(f[5] and f[3] > 1 for f in facts), "three key blocks unsplit; a split problem with kblocks > 1"
+    assert any(f[5] and s[2] % kc.attention_qsplit(*s[:4], False)[1] for f, s in zip(facts, tab)), "a ragged last query chunk"
+    assert any(s[0] * s[1] * s[2] % 4 for s in tab) and any(s[2] % 64 for s in tab if not kc.dkv_group_plan(s)[0] > 1)
+    assert sum(s[6] for s in tab) == 3 and any(s[6] and f[5] for f, s in zip(facts, tab)) and any(s[6] and not f[5] for f, s in zip(facts, tab))
+    assert [s[:5] for s in tab if s[5] == "selector"] == [(2, 2, 77, 77, 64), (2, 2, 64, 77, 8), (2, 2, 256, 77, 80)]
+    assert sum(s[8] for s in tab) == 1 and sum(s[7] for s in tab) == 2 and any(s[3] < 8 and s[3] % 2 for s in tab) and any(s[3] == 1 for s in tab)
+    assert {s[0] for s in tab} == {1, 2, 3} and {s[1] for s in tab} == {1, 2, 3, 4}
+    # ---- DKV_GROUP_SPLITS
+    tab = kc.DKV_GROUP_SPLITS
+    facts = _dkv_table_facts(lib, tab)
+    assert len(tab) == len(set(tab)) == 10 and all(f[5] for f in facts) and len({f[0] for f in facts}) == 2
+    assert sum(s[4] == 8 and s[2] >= 1024 and s[3] <= 77 for s in tab) == 8 and Counter(f[0] for f in facts) == {0: 9, 2: 1}
+    dkv, finish = kc.dkv_group_launches(tab)
+    assert [len(l) for l in dkv] == [8, 1, 1] and [len(l) for l in finish] == [8, 2]
+    assert all(f != d for f in finish for d in dkv), "the finishing tables are indexed as a dK/dV table is"
+    assert len({facts[i][0] for i in finish[0]}) == 2 and len({facts[i][2] for i in finish[0]}) > 1  # both classes, several slab counts in one launch
+    assert any(f[2] < f[1] for f in facts) and kc.dkv_group_plan(kc._pair(1, 1, 1600, 16, 8))[:3] == (6, 320, 5)
+    # ---- DKV_GROUP_FULL
+    tab = kc.DKV_GROUP_FULL
+    facts = _dkv_table_facts(lib, tab)
+    assert len(tab) == len(set(tab)) == kc.ATTN_GROUP_ABI and all(s[5] == "pair" and not f[5] for f, s in zip(facts, tab))
+    assert {s[2] for s in tab} == {64, 70} and {s[3] for s in tab} == {2, 5, 16, 77}
+    assert Counter(f[0] for f in facts) == {0: 13, 1: 7, 2: 12} and [len(l) for l in kc.dkv_group_launches(tab)[0]] == [8, 5, 7, 8, 4]
+
+
+@pytest.mark.parametrize("name", ["DKV_GROUP_MIXED", "DKV_GROUP_SPLITS", "DKV_GROUP_FULL"])
+def test_grouped_dkv_inputs_are_exact_and_a_decode_with_the_first_problems_heads_is_seen(name):
+    """Every problem's inputs are exact (pair: tie 0, lead, nonzero dQ / dK; selector: lead).  The mirror of the grouped kernel's
+    workgroup decode covers every (image, head, key block, query chunk) of every problem exactly once, so the grouped expectation
+    is each problem's own; decoded with the H of the launch's first problem - a kernel that took H from problem 0 - every problem
+    whose H differs from it loses or doubles workgroups, and the expectation says so for each of them."""
+    tab = getattr(kc, name)
+    for spec in tab:
+        _dkv_inputs_are_exact(spec)
+    seen = kc.dkv_group_cover(tab)
+    assert set(seen.values()) == {1}
+    for i, spec in enumerate(tab):
+        gx = kc.dkv_group_plan(spec)[4]
+        assert {k[1:] for k in seen if k[0] == i} == {(b, h, bx) for b in range(spec[0]) for h in range(spec[1]) for bx in range(gx)}, spec
+    true, planted = kc.dkv_group_expect(tab), kc.dkv_group_expect(tab, h_of_first=True)
+    first_h = {i: tab[l[0]][1] for l in kc.dkv_group_launches(tab)[0] for i in l}
+    differ = 0
+    for i, spec in enumerate(tab):
+        want = kc.dkv_group_problem(spec)[1]
+        for j, n in enumerate(("dk", "dv")):
+            assert torch.equal(kc.bits(true[i][j]), kc.bits(want[n])), (spec, n)
+            same = torch.equal(kc.bits(planted[i][j]), kc.bits(want[n]))
+            # (one image decoded with MORE heads than it has: rest / H' = 0, rest % H' = rest - the one wrong H that changes nothing)
+            assert same == (spec[1] == first_h[i] or (spec[0] == 1 and first_h[i] > spec[1])), (spec, n, first_h[i])
+            differ += not same
+            if not same:
+                assert kc.mismatch_report(planted[i][j], want[n], n, tile=(128, spec[4])).startswith(f"{n}: ")
+    assert differ >= 4
+
+
+def test_grouped_column_sum_tables_hold_what_they_are_listed_for(lib):
+    assert lib.sdt_colsum_batched_group_max() == kc.COLSUM_GROUP_ABI == len(kc.COLSUM_GROUP_MAXED) == len(set(kc.COLSUM_GROUP_MAXED))
+    assert len(kc.COLSUM_CASES) <= kc.COLSUM_GROUP_ABI
+    for N, ld, rows, batch, r in kc.COLSUM_GROUP_MAXED:
+        assert 1 <= batch <= 5 and rows in (1, 7, 63, 64, 65, 200) and N in (8, 13, 250, 256, 264, 520)
+        assert ld - -(-N // 8) * 8 in (0, 16) and rows * r < kc.LIMIT
+    for col, n in ((0, 6), (2, 6), (3, 5)):
+        assert len({c[col] for c in kc.COLSUM_GROUP_MAXED}) == n
+    for name in ("COLSUM_CASES", "COLSUM_GROUP_MAXED"):
+        tab, seen, counters = getattr(kc, name), set(), 0
+        for N, ld, rows, batch, r in tab:
+            ncb, nby, rpb, want = kc.colsum_plan(batch, rows, N, 512)
+            counters += ncb * batch
+            seen |= {"want clamp"} if (rows + 63) // 64 > want else set()
+            seen |= {"ragged last row block"} if rows % rpb else set()
+            seen |= {"several row blocks"} if nby > 1 else set()
+            seen |= {"ld > N"} if ld > N else set()
+            seen |= {"N % 8"} if N % 8 else set()
+            seen |= {"behind a problem with many partial rows"} if counters > ncb * batch and nby == 1 else set()
+        # (rows <= 200 never exceeds the planner's want: the clamp is COLSUM_CASES', which the GPU file also runs as one group)
+        assert seen == {"ragged last row block", "several row blocks", "ld > N", "N % 8", "behind a problem with many partial rows"} | (
+            {"want clamp"} if name == "COLSUM_CASES" else set()), (name, seen)
+        assert counters * 4 <= kc.CNT_BYTES
