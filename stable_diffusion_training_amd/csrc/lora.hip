@@ -8,13 +8,40 @@
 // LoHa (include/sdt.h "LoHa"): the delta s * (A1 B1) o (A2 B2), element-wise - a fused merge and a fused projection that form the rank-r
 // products beside each tile and never write them; its dB stripes always take the split.
 //
+// The kernels are assembled from five shared pieces, each written once:
+//   for_rank_blocks  the rank r -> RB = ceil(r / 16) template argument of every projection (a workgroup-uniform branch)
+//   merge_tile / merge_runs  the head (job, tile origin) and the tail (512 runs of 8 columns, W0 + s * tile or W0 alone) of a merge tile
+//   db_walk          the walk of a dB stripe down rows [kb, ke) of dW: 32 x 64 blocks staged through a double-buffered LDS array; the
+//                    variant's MFMAs are a body called per block, DoRA's sum G * W0 a hook on the vector a thread stages
+//   db_store / db_finish  the end of a dB stripe for one (LoRA, LoCon) or two (LoHa) accumulator sets: dB = s * acc, or the split
+//                    protocol - partial slab, arrival ticket, the last arriver's sum in chunk order
+//   split_count / entry_args (host)  the chunk, stripe, counter and partial arithmetic of a job table; the argument preamble
+//
 // Operand lane maps of mfma_f32_16x16x32_bf16 (lane l): A[row l&15][k = 8(l>>4) + j], B[k = 8(l>>4) + j][col l&15], j = 0..7;
 // C/D col = l&15, row = 4(l>>4) + reg.
+#include <type_traits>
+
 #include "sdt_common.h"
 
 namespace {
 
-constexpr int LT = 64;  // merge: output tile; project: rows of a dA stripe / columns of a dB stripe
+constexpr int LT = 64;           // merge: output tile; project: rows of a dA stripe / columns of a dB stripe
+constexpr int SPLIT_ROWS = 512;  // rows of dW in one chunk of a split dB stripe
+
+// f(std::integral_constant<int, RB>) for the RB = ceil(r / 16) blocks of 16 adapter columns: RB in {1, 2, 4, 8}, up to MAXRB
+// (r is a job's rank: the branch is workgroup-uniform.  check_jobs admits the ranks 4, 8, 16, 32, 64, 128 - check_loha_jobs up to 32 -
+// so ceil(r / 16) is 1, 2, 4 or 8 and the last branch of each chain takes no other value)
+template <int MAXRB, class F>
+__device__ __forceinline__ void for_rank_blocks(int r, F f) {
+  const int rb = (r + 15) / 16;
+  if (rb == 1) {
+    f(std::integral_constant<int, 1>{});
+  } else if (MAXRB == 2 || rb == 2) {
+    f(std::integral_constant<int, 2>{});
+  } else if constexpr (MAXRB > 2) {
+    if (rb == 4) f(std::integral_constant<int, 4>{}); else f(std::integral_constant<int, 8>{});
+  }
+}
 
 // index of the last of n jobs whose first tile - first(i), a running count - is <= tile
 template <class First>
@@ -28,9 +55,6 @@ __device__ __forceinline__ int find_index(int n, int tile, First first) {
 }
 __device__ __forceinline__ int find_job_index(const SdtLoraJob* jobs, int n, int tile, bool project) {
   return find_index(n, tile, [=](int i) { return project ? jobs[i].tile0_project : jobs[i].tile0_merge; });
-}
-__device__ __forceinline__ const SdtLoraJob& find_job(const SdtLoraJob* jobs, int n, int tile, bool project) {
-  return jobs[find_job_index(jobs, n, tile, project)];
 }
 
 // 8 consecutive float32 at p (16-byte aligned) rounded to a bf16 fragment; ok = false gives zero lanes
@@ -87,8 +111,20 @@ __device__ __forceinline__ void ab_tile(const SdtLoraJob& d, const float* __rest
     for (int i = 0; i < 4; ++i) tile[16 * wave + 4 * lq + i][16 * c + l15] = acc[c][i];
 }
 
+// the head of a merge tile: the job of workgroup blockIdx.x and the origin (r0, c0) of its tile in the leaf
+struct MergeTile {
+  int job, r0, c0;
+};
+__device__ __forceinline__ MergeTile merge_tile(const SdtLoraJob* __restrict__ jobs, int njobs) {
+  const int job = find_job_index(jobs, njobs, blockIdx.x, false);
+  const int tl = blockIdx.x - jobs[job].tile0_merge, tc = (jobs[job].N + LT - 1) / LT;
+  return {job, (tl / tc) * LT, (tl % tc) * LT};
+}
+
 // v[0..7] = W0 + s * tile for run g (0..511) of the tile at (r0, c0): row g >> 3, 8 columns from 8 (g & 7); e = the run's element
-// in the leaf.  False when the run lies outside the leaf (N is a multiple of 8: a run is whole or absent).
+// in the leaf.  False when the run lies outside the leaf (N is a multiple of 8: a run is whole or absent).  DELTA = false: W0 alone,
+// `tile` is not read (not W0 + s * 0, which would turn -0.0f into +0.0f).
+template <bool DELTA>
 __device__ __forceinline__ bool merged_run(const SdtLoraJob& d, const float* __restrict__ w0_base, const float (*tile)[LT + 4], int g,
                                            int r0, int c0, float* v, long& e) {
   const int row = r0 + (g >> 3), col = c0 + (g & 7) * 8;
@@ -96,10 +132,11 @@ __device__ __forceinline__ bool merged_run(const SdtLoraJob& d, const float* __r
   e = (long)row * d.N + col;
   const float* src = w0_base + d.w0_off + e;
   const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
-  const float* t = &tile[g >> 3][(g & 7) * 8];
-  const float s = d.scale;
-  v[0] = x0.x + s * t[0]; v[1] = x0.y + s * t[1]; v[2] = x0.z + s * t[2]; v[3] = x0.w + s * t[3];
-  v[4] = x1.x + s * t[4]; v[5] = x1.y + s * t[5]; v[6] = x1.z + s * t[6]; v[7] = x1.w + s * t[7];
+  const float x[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    if constexpr (DELTA) v[j] = x[j] + d.scale * tile[g >> 3][(g & 7) * 8 + j]; else v[j] = x[j];
+  }
   return true;
 }
 
@@ -112,42 +149,34 @@ __device__ __forceinline__ void store_run(const SdtLoraJob& d, bf16_t* __restric
   }
 }
 
+// the tail of a merge tile: its 512 runs of 8 columns, two per thread, into the bf16 mirror and / or the fp32 destination
+template <bool DELTA>
+__device__ __forceinline__ void merge_runs(const SdtLoraJob& d, const float* __restrict__ w0_base, const float (*tile)[LT + 4], int r0,
+                                           int c0, bf16_t* __restrict__ w_dst, float* __restrict__ f_dst) {
+#pragma unroll
+  for (int it = 0; it < 2; ++it) {
+    float v[8];
+    long e;
+    if (merged_run<DELTA>(d, w0_base, tile, threadIdx.x + 256 * it, r0, c0, v, e)) store_run(d, w_dst, f_dst, e, v);
+  }
+}
+
 __global__ void __launch_bounds__(256) lora_merge_kernel(const float* __restrict__ w0_base, const float* __restrict__ ab_base,
                                                          bf16_t* __restrict__ w_dst, float* __restrict__ f_dst,
                                                          const SdtLoraJob* __restrict__ jobs, int njobs) {
   __shared__ float tile[LT][LT + 4];
-  const SdtLoraJob d = find_job(jobs, njobs, blockIdx.x, false);
-  const int tl = blockIdx.x - d.tile0_merge;
-  const int tc = (d.N + LT - 1) / LT;
-  const int r0 = (tl / tc) * LT, c0 = (tl % tc) * LT;
-  ab_tile(d, ab_base + d.a_off, ab_base + d.b_off, r0, c0, tile);
+  const MergeTile t = merge_tile(jobs, njobs);
+  const SdtLoraJob d = jobs[t.job];
+  ab_tile(d, ab_base + d.a_off, ab_base + d.b_off, t.r0, t.c0, tile);
   __syncthreads();
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {  // 512 runs of 8 columns
-    float v[8];
-    long e;
-    if (merged_run(d, w0_base, tile, threadIdx.x + 256 * it, r0, c0, v, e)) store_run(d, w_dst, f_dst, e, v);
-  }
+  merge_runs<true>(d, w0_base, tile, t.r0, t.c0, w_dst, f_dst);
 }
 
 // ---- restore (include/sdt.h "DPO LOSS"): the merge's tiles and runs, W0 alone - w = bf16(W0), what sdt_param_prepare wrote there --------
 __global__ void __launch_bounds__(256) lora_restore_kernel(const float* __restrict__ w0_base, bf16_t* __restrict__ w_dst,
                                                            const SdtLoraJob* __restrict__ jobs, int njobs) {
-  const SdtLoraJob d = find_job(jobs, njobs, blockIdx.x, false);
-  const int tl = blockIdx.x - d.tile0_merge;
-  const int tc = (d.N + LT - 1) / LT;
-  const int r0 = (tl / tc) * LT, c0 = (tl % tc) * LT;
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {  // 512 runs of 8 columns; N is a multiple of 8: a run is whole or absent
-    const int g = threadIdx.x + 256 * it;
-    const int row = r0 + (g >> 3), col = c0 + (g & 7) * 8;
-    if (row >= d.K || col >= d.N) continue;
-    const long e = (long)row * d.N + col;
-    const float* src = w0_base + d.w0_off + e;
-    const float4 x0 = *reinterpret_cast<const float4*>(src), x1 = *reinterpret_cast<const float4*>(src + 4);
-    const float v[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-    *reinterpret_cast<uint4*>(w_dst + d.w_off + e) = pack8(v);
-  }
+  const MergeTile t = merge_tile(jobs, njobs);
+  merge_runs<false>(jobs[t.job], w0_base, nullptr, t.r0, t.c0, w_dst, nullptr);
 }
 
 // ---- DoRA merge (include/sdt.h "DoRA"): one 64-column stripe of one leaf per workgroup.  First walk over K: v tiles as above, every
@@ -177,7 +206,7 @@ __global__ void __launch_bounds__(256) dora_merge_kernel(const float* __restrict
     for (int it = 0; it < 2; ++it) {
       float v[8];
       long e;
-      if (merged_run(d, w0_base, tile, threadIdx.x + 256 * it, r0, c0, v, e)) {
+      if (merged_run<true>(d, w0_base, tile, threadIdx.x + 256 * it, r0, c0, v, e)) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) qp[j] += v[j] * v[j];
       }
@@ -214,7 +243,7 @@ __global__ void __launch_bounds__(256) dora_merge_kernel(const float* __restrict
       const int g = threadIdx.x + 256 * it;
       float v[8];
       long e;
-      if (merged_run(d, w0_base, tile, g, r0, c0, v, e)) {
+      if (merged_run<true>(d, w0_base, tile, g, r0, c0, v, e)) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) v[j] *= gcol[(g & 7) * 8 + j];
         store_run(d, w_dst, f_dst, e, v);
@@ -329,182 +358,171 @@ __device__ __forceinline__ void project_da_stripe(const SdtLoraJob& d, int tl, c
     }
 }
 
-template <int RB, bool DORA>
-__device__ __forceinline__ void project_tile(const SdtLoraJob& d, int tl, const bf16_t* __restrict__ dW, const float* __restrict__ A,
-                                             const float* __restrict__ B, float* __restrict__ gA, float* __restrict__ gB,
-                                             bf16_t (*stage)[LT + 8], const DoraCols& x) {
-  if (tl < d.tiles_da) {
-    project_da_stripe<RB, DORA>(d, tl, dW, B, gA, x.g);
-    return;
-  }
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
-  const int r = d.r, K = d.K, N = d.N;
-  const float s = d.scale;
-  f32x4_t acc[RB];
-#pragma unroll
-  for (int b = 0; b < RB; ++b) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  // dB[q][n] = s * sum_k bf16(A[k][q]) * dW[k][n]: A operand A^T (gathered), B operand dW columns out of the staged 32 x 64 block
-  const int c0 = (tl - d.tiles_da) * LT;
-  const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;  // one 16-byte load per thread stages 32 rows x 64 columns
-  float gw[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (DORA) sum over the staged rows of G * W0, per staged column
-  for (int k0 = 0; k0 < K; k0 += 32) {
+// ---- the walk of a dB stripe (columns c0 .. c0 + 63) down rows [kb, ke) of dW, shared by every projection.  dW passes through LDS so
+// that it is read with 16-byte loads: one load per thread stages a 32 x 64 block.  The block is double-buffered: the next block's global
+// load is issued in front of this block's MFMAs - body(k0, cur), which reads stage[cur] - and lands in the other buffer behind them,
+// one barrier per block.  staged(e, v) sees every vector a thread stages (element e of the leaf, rows top to bottom).  Blocks run
+// ascending, so a body that feeds one MFMA chain per rank block keeps one summation order over K whatever [kb, ke) is.
+struct NoStagedHook {
+  __device__ __forceinline__ void operator()(long, const uint4&) const {}
+};
+
+template <class Staged, class Body>
+__device__ __forceinline__ void db_walk(const bf16_t* __restrict__ dW, int N, int c0, int kb, int ke, bf16_t (*stage)[32][LT + 8],
+                                        Staged staged, Body body) {
+  const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;
+  const bool col_ok = c0 + scol < N;
+  auto load = [&](int k0) {
     uint4 v = {0u, 0u, 0u, 0u};
-    if (k0 + srow < K && c0 + scol < N) {
-      v = *reinterpret_cast<const uint4*>(dW + (long)(k0 + srow) * N + c0 + scol);
-      if constexpr (DORA) {
-        const float* wp = x.W0 + (long)(k0 + srow) * N + c0 + scol;
-        const float4 w0 = *reinterpret_cast<const float4*>(wp), w1 = *reinterpret_cast<const float4*>(wp + 4);
-        float gf[8];
-        unpack8(v, gf);
-        gw[0] += gf[0] * w0.x; gw[1] += gf[1] * w0.y; gw[2] += gf[2] * w0.z; gw[3] += gf[3] * w0.w;
-        gw[4] += gf[4] * w1.x; gw[5] += gf[5] * w1.y; gw[6] += gf[6] * w1.z; gw[7] += gf[7] * w1.w;
-      }
+    if (k0 + srow < ke && col_ok) {
+      const long e = (long)(k0 + srow) * N + c0 + scol;
+      v = *reinterpret_cast<const uint4*>(dW + e);
+      staged(e, v);
     }
-    __syncthreads();  // the previous block has been consumed
-    *reinterpret_cast<uint4*>(&stage[srow][scol]) = v;
+    return v;
+  };
+  *reinterpret_cast<uint4*>(&stage[0][srow][scol]) = load(kb);
+  __syncthreads();
+  int cur = 0;
+  for (int k0 = kb; k0 < ke; k0 += 32, cur ^= 1) {
+    const bool more = k0 + 32 < ke;
+    uint4 nv = {0u, 0u, 0u, 0u};
+    if (more) nv = load(k0 + 32);
+    body(k0, cur);
+    if (more) *reinterpret_cast<uint4*>(&stage[cur ^ 1][srow][scol]) = nv;  // (its readers finished in front of the last barrier)
     __syncthreads();
-    const int k = k0 + 8 * lq;
-    bf16x8_t bb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bb[j] = (short)stage[8 * lq + j][16 * wave + l15];
-#pragma unroll
-    for (int b = 0; b < RB; ++b) {
-      const int q = 16 * b + l15;
-      const bf16x8_t a = frag_from_f32_strided(A + (long)k * r + q, r, k, K, q < r);
-      acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, acc[b], 0, 0, 0);
-    }
   }
-  if constexpr (DORA) {
-    dora_db_tail<RB>(d, c0, B, gB, acc, gw, x);
-    return;
+}
+
+// the LoRA body: dB[q][n] += sum_k bf16(A[k][q]) * dW[k][n] over the block's rows below ke - A operand A^T (gathered), B operand the
+// wave's 16 dW columns out of the staged block
+template <int RB>
+__device__ __forceinline__ void lora_db_block(const float* __restrict__ A, int r, int k0, int ke, const bf16_t (*blk)[LT + 8], f32x4_t* acc) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const int k = k0 + 8 * lq;
+  bf16x8_t bb;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) bb[j] = (short)blk[8 * lq + j][16 * wave + l15];
+#pragma unroll
+  for (int b = 0; b < RB; ++b) {
+    const int q = 16 * b + l15;
+    const bf16x8_t a = frag_from_f32_strided(A + (long)k * r + q, r, k, ke, q < r);
+    acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, acc[b], 0, 0, 0);
   }
+}
+
+// ---- the end of a dB stripe for SIDES accumulator sets (acc[side][b][i]: q = 16 b + 4 (lane >> 4) + i of the lane's column).
+// db_store: dB = s * acc.  db_finish: a stripe of one chunk stores; otherwise the workgroup stores its fp32 partial slab - [r][64] of
+// side 0, then of side 1 - (write-through), takes a ticket at the stripe's integer arrival counter, and the last arriver adds the
+// slabs in chunk order 0, 1, 2, ... - one thread per element - and writes dB = s * sum.
+template <int RB, int SIDES>
+__device__ __forceinline__ void db_store(const SdtLoraJob& d, int c0, float* const (&gB)[SIDES], const f32x4_t (&acc)[SIDES][RB]) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const int n = c0 + 16 * wave + l15;
 #pragma unroll
   for (int b = 0; b < RB; ++b)
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int q = 16 * b + 4 * lq + i, n = c0 + 16 * wave + l15;
-      if (q < r && n < N) gB[(long)q * N + n] = s * acc[b][i];
+      const int q = 16 * b + 4 * lq + i;
+      if (q < d.r && n < d.N) {
+#pragma unroll
+        for (int sd = 0; sd < SIDES; ++sd) gB[sd][(long)q * d.N + n] = d.scale * acc[sd][b][i];
+      }
     }
+}
+
+template <int RB, int SIDES>
+__device__ __forceinline__ void db_finish(const SdtLoraJob& d, const SdtLoraSplitJob& x, long part_off, int stripe, int chunk,
+                                          float* const (&gB)[SIDES], const f32x4_t (&acc)[SIDES][RB], int* __restrict__ counters,
+                                          float* __restrict__ parts, int* s_flag) {
+  const int c0 = stripe * LT;
+  if (x.chunks == 1) {
+    db_store<RB, SIDES>(d, c0, gB, acc);
+    return;
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
+  const int side = d.r * LT;                // floats of one set
+  const long slab = (long)SIDES * side;     // floats of one workgroup's partial
+  float* mine = parts + part_off + ((long)stripe * x.chunks + chunk) * slab;
+#pragma unroll
+  for (int b = 0; b < RB; ++b)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int q = 16 * b + 4 * lq + i;
+      if (q < d.r) {
+#pragma unroll
+        for (int sd = 0; sd < SIDES; ++sd) sdt_store_wt(mine + (long)sd * side + (long)q * LT + 16 * wave + l15, acc[sd][b][i]);
+      }
+    }
+  if (!sdt_arrive_last<true>(counters + x.cnt0 + stripe, x.chunks, s_flag)) return;
+  const float* first = parts + part_off + (long)stripe * x.chunks * slab;
+  for (int e = threadIdx.x; e < (int)slab; e += 256) {
+    const bool two = SIDES == 2 && e >= side;
+    const int ee = two ? e - side : e;
+    const int q = ee >> 6, n = c0 + (ee & 63);
+    if (n >= d.N) continue;
+    float sum = sdt_load_wt(first + e);
+    for (int c = 1; c < x.chunks; ++c) sum += sdt_load_wt(first + c * slab + e);
+    (two ? gB[SIDES - 1] : gB[0])[(long)q * d.N + n] = d.scale * sum;
+  }
+}
+
+// ---- Dense projection: a dB stripe walks all of K in one workgroup (no split: its K is short, and a split would change the order)
+template <int RB, bool DORA>
+__device__ __forceinline__ void project_tile(const SdtLoraJob& d, int tl, const bf16_t* __restrict__ dW, const float* __restrict__ ab_base,
+                                             float* __restrict__ grad_base, bf16_t (*stage)[32][LT + 8], const DoraCols& x) {
+  const float* A = ab_base + d.a_off;
+  const float* B = ab_base + d.b_off;
+  if (tl < d.tiles_da) {
+    project_da_stripe<RB, DORA>(d, tl, dW, B, grad_base + d.ga_off, x.g);
+    return;
+  }
+  const int c0 = (tl - d.tiles_da) * LT;
+  float* const gB[1] = {grad_base + d.gb_off};
+  f32x4_t acc[1][RB];
+#pragma unroll
+  for (int b = 0; b < RB; ++b) acc[0][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  float gw[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // (DORA) sum over the rows a thread stages of G * W0, per staged column
+  db_walk(dW, d.N, c0, 0, d.K, stage,
+          [&](long e, const uint4& v) {
+            if constexpr (DORA) {
+              const float4 w0 = *reinterpret_cast<const float4*>(x.W0 + e), w1 = *reinterpret_cast<const float4*>(x.W0 + e + 4);
+              float gf[8];
+              unpack8(v, gf);
+              gw[0] += gf[0] * w0.x; gw[1] += gf[1] * w0.y; gw[2] += gf[2] * w0.z; gw[3] += gf[3] * w0.w;
+              gw[4] += gf[4] * w1.x; gw[5] += gf[5] * w1.y; gw[6] += gf[6] * w1.z; gw[7] += gf[7] * w1.w;
+            }
+          },
+          [&](int k0, int cur) { lora_db_block<RB>(A, d.r, k0, d.K, stage[cur], acc[0]); });
+  if constexpr (DORA) dora_db_tail<RB>(d, c0, B, gB[0], acc[0], gw, x); else db_store<RB, 1>(d, c0, gB, acc);
 }
 
 __global__ void __launch_bounds__(256) lora_project_kernel(const bf16_t* __restrict__ dw_base, const float* __restrict__ ab_base,
                                                            float* __restrict__ grad_base, const SdtLoraJob* __restrict__ jobs, int njobs) {
-  __shared__ __attribute__((aligned(16))) bf16_t stage[32][LT + 8];
-  const SdtLoraJob d = find_job(jobs, njobs, blockIdx.x, true);
+  __shared__ __attribute__((aligned(16))) bf16_t stage[2][32][LT + 8];
+  const SdtLoraJob d = jobs[find_job_index(jobs, njobs, blockIdx.x, true)];
   const int tl = blockIdx.x - d.tile0_project;
-  const bf16_t* dW = dw_base + d.dw_off;
-  const float* A = ab_base + d.a_off;
-  const float* B = ab_base + d.b_off;
-  float* gA = grad_base + d.ga_off;
-  float* gB = grad_base + d.gb_off;
   const DoraCols none = {nullptr, nullptr, nullptr, nullptr, nullptr};
-  switch ((d.r + 15) / 16) {  // (workgroup-uniform)
-    case 1: project_tile<1, false>(d, tl, dW, A, B, gA, gB, stage, none); break;
-    case 2: project_tile<2, false>(d, tl, dW, A, B, gA, gB, stage, none); break;
-    case 4: project_tile<4, false>(d, tl, dW, A, B, gA, gB, stage, none); break;
-    default: project_tile<8, false>(d, tl, dW, A, B, gA, gB, stage, none); break;
-  }
+  for_rank_blocks<8>(d.r, [&](auto rb) { project_tile<decltype(rb)::value, false>(d, tl, dw_base + d.dw_off, ab_base, grad_base, stage, none); });
 }
 
 __global__ void __launch_bounds__(256) dora_project_kernel(const bf16_t* __restrict__ dw_base, const float* __restrict__ w0_base,
                                                            const float* __restrict__ ab_base, float* __restrict__ grad_base,
                                                            const float* __restrict__ stat_base, const SdtLoraJob* __restrict__ jobs,
                                                            const SdtDoraJob* __restrict__ dj, int njobs) {
-  __shared__ __attribute__((aligned(16))) bf16_t stage[32][LT + 8];
+  __shared__ __attribute__((aligned(16))) bf16_t stage[2][32][LT + 8];
   __shared__ float red[32][LT];
   const int job = find_job_index(jobs, njobs, blockIdx.x, true);  // (the DoRA table runs beside the job table, index by index)
   const SdtLoraJob d = jobs[job];
   const SdtDoraJob j = dj[job];
   const int tl = blockIdx.x - d.tile0_project;
-  const bf16_t* dW = dw_base + d.dw_off;
-  const float* A = ab_base + d.a_off;
-  const float* B = ab_base + d.b_off;
-  float* gA = grad_base + d.ga_off;
-  float* gB = grad_base + d.gb_off;
   const DoraCols x = {w0_base + d.w0_off, stat_base + j.stat_off, stat_base + j.stat_off + d.N, grad_base + j.gm_off, red};
-  switch ((d.r + 15) / 16) {  // (workgroup-uniform)
-    case 1: project_tile<1, true>(d, tl, dW, A, B, gA, gB, stage, x); break;
-    case 2: project_tile<2, true>(d, tl, dW, A, B, gA, gB, stage, x); break;
-    case 4: project_tile<4, true>(d, tl, dW, A, B, gA, gB, stage, x); break;
-    default: project_tile<8, true>(d, tl, dW, A, B, gA, gB, stage, x); break;
-  }
+  for_rank_blocks<8>(d.r, [&](auto rb) { project_tile<decltype(rb)::value, true>(d, tl, dw_base + d.dw_off, ab_base, grad_base, stage, x); });
 }
 
 // ---- split projection (include/sdt.h "LoCon"): jobs with tall K.  The dA stripes are project_da_stripe; a dB stripe is cut along K
-// into chunks of SPLIT_ROWS rows, one workgroup per (stripe, chunk).  The staged 32 x 64 block of dW is double-buffered: the next
-// block's 16-byte global load is issued in front of this block's MFMAs and lands in the other buffer behind them, one barrier per
-// block.  A job of one chunk writes dB = s * acc as project_tile does (the same accumulation order: its bits).  Otherwise the
-// workgroup stores its fp32 partial [r][64] (write-through), takes a ticket at the stripe's integer arrival counter, and the last
-// arriver adds the partials in chunk order 0, 1, 2, ... - one thread per element - and writes dB = s * sum.
-constexpr int SPLIT_ROWS = 512;
-
-template <int RB>
-__device__ __forceinline__ void project_db_chunk(const SdtLoraJob& d, const SdtLoraSplitJob& x, int stripe, int chunk,
-                                                 const bf16_t* __restrict__ dW, const float* __restrict__ A, float* __restrict__ gB,
-                                                 int* __restrict__ counters, float* __restrict__ parts, bf16_t (*stage)[32][LT + 8],
-                                                 int* s_flag) {
-  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
-  const int r = d.r, K = d.K, N = d.N;
-  const float s = d.scale;
-  const int c0 = stripe * LT;
-  const int kb = chunk * SPLIT_ROWS, ke = min(K, kb + SPLIT_ROWS);
-  const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;  // one 16-byte load per thread stages 32 rows x 64 columns
-  const bool col_ok = c0 + scol < N;
-  f32x4_t acc[RB];
-#pragma unroll
-  for (int b = 0; b < RB; ++b) acc[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  uint4 v = {0u, 0u, 0u, 0u};
-  if (kb + srow < ke && col_ok) v = *reinterpret_cast<const uint4*>(dW + (long)(kb + srow) * N + c0 + scol);
-  *reinterpret_cast<uint4*>(&stage[0][srow][scol]) = v;
-  __syncthreads();
-  int cur = 0;
-  for (int k0 = kb; k0 < ke; k0 += 32, cur ^= 1) {
-    const bool more = k0 + 32 < ke;
-    uint4 nv = {0u, 0u, 0u, 0u};
-    if (more && k0 + 32 + srow < ke && col_ok) nv = *reinterpret_cast<const uint4*>(dW + (long)(k0 + 32 + srow) * N + c0 + scol);
-    const int k = k0 + 8 * lq;
-    bf16x8_t bb;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bb[j] = (short)stage[cur][8 * lq + j][16 * wave + l15];
-#pragma unroll
-    for (int b = 0; b < RB; ++b) {
-      const int q = 16 * b + l15;
-      const bf16x8_t a = frag_from_f32_strided(A + (long)k * r + q, r, k, ke, q < r);
-      acc[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bb, acc[b], 0, 0, 0);
-    }
-    if (more) *reinterpret_cast<uint4*>(&stage[cur ^ 1][srow][scol]) = nv;  // (its readers finished in front of the last barrier)
-    __syncthreads();
-  }
-  if (x.chunks == 1) {
-#pragma unroll
-    for (int b = 0; b < RB; ++b)
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int q = 16 * b + 4 * lq + i, n = c0 + 16 * wave + l15;
-        if (q < r && n < N) gB[(long)q * N + n] = s * acc[b][i];
-      }
-    return;
-  }
-  const long slab = (long)r * LT;  // floats of one partial
-  float* mine = parts + x.part_off + ((long)stripe * x.chunks + chunk) * slab;
-#pragma unroll
-  for (int b = 0; b < RB; ++b)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = 16 * b + 4 * lq + i;
-      if (q < r) sdt_store_wt(mine + (long)q * LT + 16 * wave + l15, acc[b][i]);
-    }
-  if (!sdt_arrive_last<true>(counters + x.cnt0 + stripe, x.chunks, s_flag)) return;
-  const float* first = parts + x.part_off + (long)stripe * x.chunks * slab;
-  for (int e = threadIdx.x; e < (int)slab; e += 256) {
-    const int q = e >> 6, n = c0 + (e & 63);
-    if (n >= N) continue;
-    float sum = sdt_load_wt(first + e);
-    for (int c = 1; c < x.chunks; ++c) sum += sdt_load_wt(first + c * slab + e);
-    gB[(long)q * N + n] = s * sum;
-  }
-}
-
+// into chunks of SPLIT_ROWS rows, one workgroup per (stripe, chunk), each a db_walk with the LoRA body over its rows and db_finish
+// behind it.  A job of one chunk writes dB = s * acc as project_tile does (the same accumulation order: its bits).
 __global__ void __launch_bounds__(256) lora_project_split_kernel(const bf16_t* __restrict__ dw_base, const float* __restrict__ ab_base,
                                                                  float* __restrict__ grad_base, const SdtLoraJob* __restrict__ jobs,
                                                                  const SdtLoraSplitJob* __restrict__ sj, int njobs,
@@ -517,25 +535,21 @@ __global__ void __launch_bounds__(256) lora_project_split_kernel(const bf16_t* _
   const int tl = blockIdx.x - x.tile0;
   const bf16_t* dW = dw_base + d.dw_off;
   const float* A = ab_base + d.a_off;
-  const float* B = ab_base + d.b_off;
-  float* gA = grad_base + d.ga_off;
-  float* gB = grad_base + d.gb_off;
-  if (tl < d.tiles_da) {
-    switch ((d.r + 15) / 16) {  // (workgroup-uniform)
-      case 1: project_da_stripe<1, false>(d, tl, dW, B, gA, nullptr); break;
-      case 2: project_da_stripe<2, false>(d, tl, dW, B, gA, nullptr); break;
-      case 4: project_da_stripe<4, false>(d, tl, dW, B, gA, nullptr); break;
-      default: project_da_stripe<8, false>(d, tl, dW, B, gA, nullptr); break;
+  for_rank_blocks<8>(d.r, [&](auto rb) {
+    constexpr int RB = decltype(rb)::value;
+    if (tl < d.tiles_da) {
+      project_da_stripe<RB, false>(d, tl, dW, ab_base + d.b_off, grad_base + d.ga_off, nullptr);
+      return;
     }
-    return;
-  }
-  const int t = tl - d.tiles_da, stripe = t / x.chunks, chunk = t % x.chunks;
-  switch ((d.r + 15) / 16) {
-    case 1: project_db_chunk<1>(d, x, stripe, chunk, dW, A, gB, counters, parts, stage, &s_flag); break;
-    case 2: project_db_chunk<2>(d, x, stripe, chunk, dW, A, gB, counters, parts, stage, &s_flag); break;
-    case 4: project_db_chunk<4>(d, x, stripe, chunk, dW, A, gB, counters, parts, stage, &s_flag); break;
-    default: project_db_chunk<8>(d, x, stripe, chunk, dW, A, gB, counters, parts, stage, &s_flag); break;
-  }
+    const int t = tl - d.tiles_da, stripe = t / x.chunks, chunk = t % x.chunks;
+    const int kb = chunk * SPLIT_ROWS, ke = min(d.K, kb + SPLIT_ROWS);
+    float* const gB[1] = {grad_base + d.gb_off};
+    f32x4_t acc[1][RB];
+#pragma unroll
+    for (int b = 0; b < RB; ++b) acc[0][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+    db_walk(dW, d.N, stripe * LT, kb, ke, stage, NoStagedHook{}, [&](int k0, int cur) { lora_db_block<RB>(A, d.r, k0, ke, stage[cur], acc[0]); });
+    db_finish<RB, 1>(d, x, x.part_off, stripe, chunk, gB, acc, counters, parts, &s_flag);
+  });
 }
 
 // ---- LoHa (include/sdt.h "LoHa"): dW = s * (A1 B1) o (A2 B2), r <= 32 so that ONE MFMA K-step forms a 16 x 16 block of P_i = bf16(A_i)
@@ -543,6 +557,7 @@ __global__ void __launch_bounds__(256) lora_project_split_kernel(const bf16_t* _
 // nothing is moved.  The 16 MFMA rows of a P block are made to stand for contraction elements 8 (m >> 2) + 4 b + (m & 3), b = 0, 1 -
 // the factor rows are gathered in that order - so the accumulator registers i = 0..3 of blocks b = 0, 1 ARE elements 8 (lane >> 4) +
 // 4 b + i of the lane's own row / column: the eight the operand fragment holds.  G_i = bf16(dW * P_other) is formed in registers.
+// The two factor pairs are "sides" 0 and 1: everything per side is an array indexed by it, in loops the compiler unrolls.
 // rows X[row][8 lq .. 8 lq + 7] of a factor X [rows][r] as an operand fragment (r in {4, 8, 16, 32}; lanes with q >= r are zero)
 __device__ __forceinline__ bf16x8_t loha_rows_frag(const float* __restrict__ X, int r, long row, bool ok, int lq) {
   return r == 4 ? frag_from_f32x4(X + row * 4, ok && lq == 0) : frag_from_f32(X + row * r + 8 * lq, ok && 8 * lq < r);
@@ -571,60 +586,54 @@ __device__ __forceinline__ f32x4_t loha_block(bf16x8_t a, bf16x8_t b) {
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, f32x4_t{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
 }
 
+// the factors and their gradients of one job, by side
+struct LohaSides {
+  const float *A[2], *B[2];
+  float *gA[2], *gB[2];
+};
+
 // merge: lora_merge_kernel's tiles and runs; h = fl(P1 * P2) in registers, then merged_run's v = fl(W0 + fl(s * h))
 __global__ void __launch_bounds__(256) loha_merge_kernel(const float* __restrict__ w0_base, const float* __restrict__ ab_base,
                                                          bf16_t* __restrict__ w_dst, float* __restrict__ f_dst,
                                                          const SdtLoraJob* __restrict__ jobs, const SdtLohaJob* __restrict__ xj, int njobs) {
   __shared__ float tile[LT][LT + 4];
-  const int job = find_job_index(jobs, njobs, blockIdx.x, false);
-  const SdtLoraJob d = jobs[job];
-  const SdtLohaJob x = xj[job];
-  const int tl = blockIdx.x - d.tile0_merge;
-  const int tc = (d.N + LT - 1) / LT;
-  const int r0 = (tl / tc) * LT, c0 = (tl % tc) * LT;
+  const MergeTile t = merge_tile(jobs, njobs);
+  const SdtLoraJob d = jobs[t.job];
+  const SdtLohaJob x = xj[t.job];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
   const float *B1 = ab_base + d.b_off, *B2 = ab_base + x.b2_off;
-  const int arow = r0 + 16 * wave + l15;
+  const int arow = t.r0 + 16 * wave + l15;
   const bf16x8_t a1 = loha_rows_frag(ab_base + d.a_off, d.r, arow, arow < d.K, lq);
   const bf16x8_t a2 = loha_rows_frag(ab_base + x.a2_off, d.r, arow, arow < d.K, lq);
 #pragma unroll
   for (int c = 0; c < 4; ++c) {
-    const int col = c0 + 16 * c + l15;
+    const int col = t.c0 + 16 * c + l15;
     const f32x4_t p1 = loha_block(a1, loha_cols_frag(B1, d.r, d.N, col, col < d.N, lq));
     const f32x4_t p2 = loha_block(a2, loha_cols_frag(B2, d.r, d.N, col, col < d.N, lq));
 #pragma unroll
     for (int i = 0; i < 4; ++i) tile[16 * wave + 4 * lq + i][16 * c + l15] = p1[i] * p2[i];
   }
   __syncthreads();
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {  // 512 runs of 8 columns
-    float v[8];
-    long e;
-    if (merged_run(d, w0_base, tile, threadIdx.x + 256 * it, r0, c0, v, e)) store_run(d, w_dst, f_dst, e, v);
-  }
+  merge_runs<true>(d, w0_base, tile, t.r0, t.c0, w_dst, f_dst);
 }
 
-struct LohaSides {
-  const float *A1, *B1, *A2, *B2;
-  float *gA1, *gB1, *gA2, *gB2;
-};
-
-// G1 = bf16(w * p2), G2 = bf16(w * p1) for the lane's eight contraction elements: w = dW widened, p[b][i] element 4 b + i, or with
-// PAIRS (interleaved blocks) element 2 i + b
+// G[0] = bf16(w * p[1]), G[1] = bf16(w * p[0]) for the lane's eight contraction elements: w = dW widened, p[side][b][i] element
+// 4 b + i, or with PAIRS (interleaved blocks) element 2 i + b
 template <bool PAIRS>
-__device__ __forceinline__ void loha_g_frags(const float* w, const f32x4_t* p1, const f32x4_t* p2, bf16x8_t& G1, bf16x8_t& G2) {
-  float g1[8], g2[8];
+__device__ __forceinline__ void loha_g_frags(const float* w, const f32x4_t (&p)[2][2], bf16x8_t (&G)[2]) {
 #pragma unroll
-  for (int b = 0; b < 2; ++b)
+  for (int sd = 0; sd < 2; ++sd) {
+    float g[8];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int j = PAIRS ? 2 * i + b : 4 * b + i;
-      g1[j] = w[j] * p2[b][i];
-      g2[j] = w[j] * p1[b][i];
-    }
-  const uint4 u1 = pack8(g1), u2 = pack8(g2);
-  G1 = __builtin_bit_cast(bf16x8_t, u1);
-  G2 = __builtin_bit_cast(bf16x8_t, u2);
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        const int j = PAIRS ? 2 * i + b : 4 * b + i;
+        g[j] = w[j] * p[sd ^ 1][b][i];
+      }
+    const uint4 u = pack8(g);
+    G[sd] = __builtin_bit_cast(bf16x8_t, u);
+  }
 }
 
 // one 64-row stripe of dA1 and dA2: a wave owns 16 rows and walks N, 32 columns a step.  P^T blocks: A operand the B_i columns (MFMA
@@ -636,36 +645,38 @@ __device__ __forceinline__ void loha_da_stripe(const SdtLoraJob& d, const LohaSi
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
   const int r = d.r, K = d.K, N = d.N;
   const float s = d.scale;
-  f32x4_t acc1[RB], acc2[RB];
-#pragma unroll
-  for (int b = 0; b < RB; ++b) acc1[b] = acc2[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
   const int row = tl * LT + 16 * wave + l15;
-  const bf16x8_t at1 = loha_rows_frag(o.A1, r, row, row < K, lq), at2 = loha_rows_frag(o.A2, r, row, row < K, lq);
+  f32x4_t acc[2][RB];
+  bf16x8_t at[2];
+#pragma unroll
+  for (int sd = 0; sd < 2; ++sd) {
+    at[sd] = loha_rows_frag(o.A[sd], r, row, row < K, lq);
+#pragma unroll
+    for (int b = 0; b < RB; ++b) acc[sd][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
   for (int n0 = 0; n0 < N; n0 += 32) {
-    const int n = n0 + 8 * lq;
+    const int n = n0 + 8 * lq, np = n0 + 2 * l15;
     uint4 v = {0u, 0u, 0u, 0u};
     if (row < K && n < N) v = *reinterpret_cast<const uint4*>(dW + (long)row * N + n);
     float w[8];
     unpack8(v, w);
-    f32x4_t p1[2], p2[2];
-    {
-      const int np = n0 + 2 * l15;
-      bf16x8_t f0, f1;
-      loha_col_pairs(o.B1, r, N, np, np < N, lq, f0, f1);
-      p1[0] = loha_block(f0, at1);
-      p1[1] = loha_block(f1, at1);
-      loha_col_pairs(o.B2, r, N, np, np < N, lq, f0, f1);
-      p2[0] = loha_block(f0, at2);
-      p2[1] = loha_block(f1, at2);
-    }
-    bf16x8_t G1, G2;
-    loha_g_frags<true>(w, p1, p2, G1, G2);
+    f32x4_t p[2][2];
 #pragma unroll
-    for (int b = 0; b < RB; ++b) {
-      const int q = 16 * b + l15;
-      acc1[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(G1, frag_from_f32(o.B1 + (long)q * N + n, q < r && n < N), acc1[b], 0, 0, 0);
-      acc2[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(G2, frag_from_f32(o.B2 + (long)q * N + n, q < r && n < N), acc2[b], 0, 0, 0);
+    for (int sd = 0; sd < 2; ++sd) {
+      bf16x8_t f0, f1;
+      loha_col_pairs(o.B[sd], r, N, np, np < N, lq, f0, f1);
+      p[sd][0] = loha_block(f0, at[sd]);
+      p[sd][1] = loha_block(f1, at[sd]);
     }
+    bf16x8_t G[2];
+    loha_g_frags<true>(w, p, G);
+#pragma unroll
+    for (int b = 0; b < RB; ++b)
+#pragma unroll
+      for (int sd = 0; sd < 2; ++sd) {
+        const int q = 16 * b + l15;
+        acc[sd][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(G[sd], frag_from_f32(o.B[sd] + (long)q * N + n, q < r && n < N), acc[sd][b], 0, 0, 0);
+      }
   }
 #pragma unroll
   for (int b = 0; b < RB; ++b)
@@ -673,102 +684,60 @@ __device__ __forceinline__ void loha_da_stripe(const SdtLoraJob& d, const LohaSi
     for (int i = 0; i < 4; ++i) {
       const int k = tl * LT + 16 * wave + 4 * lq + i, q = 16 * b + l15;
       if (k < K && q < r) {
-        o.gA1[(long)k * r + q] = s * acc1[b][i];
-        o.gA2[(long)k * r + q] = s * acc2[b][i];
+#pragma unroll
+        for (int sd = 0; sd < 2; ++sd) o.gA[sd][(long)k * r + q] = s * acc[sd][b][i];
       }
     }
 }
 
-// one (stripe, chunk) of dB1 and dB2: project_db_chunk's staging, chunking and arrival protocol.  P blocks: A operand the A_i rows (MFMA
-// row m stands for row k0 + 8 (m >> 2) + 4 b + (m & 3)), B operand the lane's own B_i column, loaded once per chunk.  A partial slab
-// holds both sets: [r][64] of dB1, then [r][64] of dB2.
+// one (stripe, chunk) of dB1 and dB2: a db_walk over the chunk's rows and the two-sided db_finish (a stripe always takes the split
+// table).  P blocks: A operand the A_i rows (MFMA row m stands for row k0 + 8 (m >> 2) + 4 b + (m & 3)), B operand the lane's own B_i
+// column, loaded once per chunk.
 template <int RB>
 __device__ __forceinline__ void loha_db_chunk(const SdtLoraJob& d, const SdtLoraSplitJob& x, const LohaSides& o, long part_off, int stripe,
                                               int chunk, const bf16_t* __restrict__ dW, int* __restrict__ counters,
                                               float* __restrict__ parts, bf16_t (*stage)[32][LT + 8], int* s_flag) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, l15 = lane & 15, lq = lane >> 4;
-  const int r = d.r, K = d.K, N = d.N;
-  const float s = d.scale;
-  const int c0 = stripe * LT;
-  const int kb = chunk * SPLIT_ROWS, ke = min(K, kb + SPLIT_ROWS);
-  const int srow = threadIdx.x >> 3, scol = (threadIdx.x & 7) * 8;  // one 16-byte load per thread stages 32 rows x 64 columns
-  const bool col_ok = c0 + scol < N;
-  const int ncol = c0 + 16 * wave + l15;
-  const bf16x8_t bc1 = loha_cols_frag(o.B1, r, N, ncol, ncol < N, lq), bc2 = loha_cols_frag(o.B2, r, N, ncol, ncol < N, lq);
+  const int r = d.r, N = d.N;
+  const int kb = chunk * SPLIT_ROWS, ke = min(d.K, kb + SPLIT_ROWS);
+  const int ncol = stripe * LT + 16 * wave + l15;
   const int kl = 8 * (l15 >> 2) + (l15 & 3);
-  f32x4_t acc1[RB], acc2[RB];
+  f32x4_t acc[2][RB];
+  bf16x8_t bc[2];
 #pragma unroll
-  for (int b = 0; b < RB; ++b) acc1[b] = acc2[b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
-  uint4 v = {0u, 0u, 0u, 0u};
-  if (kb + srow < ke && col_ok) v = *reinterpret_cast<const uint4*>(dW + (long)(kb + srow) * N + c0 + scol);
-  *reinterpret_cast<uint4*>(&stage[0][srow][scol]) = v;
-  __syncthreads();
-  int cur = 0;
-  for (int k0 = kb; k0 < ke; k0 += 32, cur ^= 1) {
-    const bool more = k0 + 32 < ke;
-    uint4 nv = {0u, 0u, 0u, 0u};
-    if (more && k0 + 32 + srow < ke && col_ok) nv = *reinterpret_cast<const uint4*>(dW + (long)(k0 + 32 + srow) * N + c0 + scol);
+  for (int sd = 0; sd < 2; ++sd) {
+    bc[sd] = loha_cols_frag(o.B[sd], r, N, ncol, ncol < N, lq);
+#pragma unroll
+    for (int b = 0; b < RB; ++b) acc[sd][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+  db_walk(dW, N, stripe * LT, kb, ke, stage, NoStagedHook{}, [&](int k0, int cur) {
     const int k = k0 + 8 * lq;
     float w[8];
 #pragma unroll
     for (int j = 0; j < 8; ++j) w[j] = bf2f(stage[cur][8 * lq + j][16 * wave + l15]);
-    f32x4_t p1[2], p2[2];
+    f32x4_t p[2][2];
 #pragma unroll
-    for (int b = 0; b < 2; ++b) {
-      const int kp = k0 + kl + 4 * b;
-      p1[b] = loha_block(loha_rows_frag(o.A1, r, kp, kp < ke, lq), bc1);
-      p2[b] = loha_block(loha_rows_frag(o.A2, r, kp, kp < ke, lq), bc2);
-    }
-    bf16x8_t G1, G2;
-    loha_g_frags<false>(w, p1, p2, G1, G2);
+    for (int b = 0; b < 2; ++b)
 #pragma unroll
-    for (int b = 0; b < RB; ++b) {
-      const int q = 16 * b + l15;
-      acc1[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_from_f32_strided(o.A1 + (long)k * r + q, r, k, ke, q < r), G1, acc1[b], 0, 0, 0);
-      acc2[b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_from_f32_strided(o.A2 + (long)k * r + q, r, k, ke, q < r), G2, acc2[b], 0, 0, 0);
-    }
-    if (more) *reinterpret_cast<uint4*>(&stage[cur ^ 1][srow][scol]) = nv;  // (its readers finished in front of the last barrier)
-    __syncthreads();
-  }
-  if (x.chunks == 1) {
+      for (int sd = 0; sd < 2; ++sd) {
+        const int kp = k0 + kl + 4 * b;
+        p[sd][b] = loha_block(loha_rows_frag(o.A[sd], r, kp, kp < ke, lq), bc[sd]);
+      }
+    bf16x8_t G[2];
+    loha_g_frags<false>(w, p, G);
 #pragma unroll
     for (int b = 0; b < RB; ++b)
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        const int q = 16 * b + 4 * lq + i;
-        if (q < r && ncol < N) {
-          o.gB1[(long)q * N + ncol] = s * acc1[b][i];
-          o.gB2[(long)q * N + ncol] = s * acc2[b][i];
-        }
+      for (int sd = 0; sd < 2; ++sd) {
+        const int q = 16 * b + l15;
+        acc[sd][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(frag_from_f32_strided(o.A[sd] + (long)k * r + q, r, k, ke, q < r), G[sd], acc[sd][b], 0, 0, 0);
       }
-    return;
-  }
-  const long side = (long)r * LT, slab = 2 * side;  // floats of one set / of one workgroup's partial
-  float* mine = parts + part_off + ((long)stripe * x.chunks + chunk) * slab;
-#pragma unroll
-  for (int b = 0; b < RB; ++b)
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int q = 16 * b + 4 * lq + i;
-      if (q < r) {
-        sdt_store_wt(mine + (long)q * LT + 16 * wave + l15, acc1[b][i]);
-        sdt_store_wt(mine + side + (long)q * LT + 16 * wave + l15, acc2[b][i]);
-      }
-    }
-  if (!sdt_arrive_last<true>(counters + x.cnt0 + stripe, x.chunks, s_flag)) return;
-  const float* first = parts + part_off + (long)stripe * x.chunks * slab;
-  for (int e = threadIdx.x; e < (int)slab; e += 256) {
-    const bool two = e >= (int)side;
-    const int ee = two ? e - (int)side : e;
-    const int q = ee >> 6, n = c0 + (ee & 63);
-    if (n >= N) continue;
-    float sum = sdt_load_wt(first + e);
-    for (int c = 1; c < x.chunks; ++c) sum += sdt_load_wt(first + c * slab + e);
-    (two ? o.gB2 : o.gB1)[(long)q * N + n] = s * sum;
-  }
+  });
+  db_finish<RB, 2>(d, x, part_off, stripe, chunk, o.gB, acc, counters, parts, s_flag);
 }
 
-// (4 waves per SIMD: without the request the allocator takes 131 registers where 119 do, and a fourth workgroup per CU hides the gathers)
+// (4 waves per SIMD are requested: a fourth workgroup per CU hides the gathers.  113 VGPRs and no AGPRs with the request; 107 + 16
+// without it, which still fits four - the request pins the occupancy against the next change to the body)
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) loha_project_kernel(const bf16_t* __restrict__ dw_base, const float* __restrict__ ab_base,
                                                            float* __restrict__ grad_base, const SdtLoraJob* __restrict__ jobs,
                                                            const SdtLoraSplitJob* __restrict__ sj, const SdtLohaJob* __restrict__ xj,
@@ -781,15 +750,17 @@ __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) l
   const SdtLohaJob h = xj[job];
   const int tl = blockIdx.x - x.tile0;
   const bf16_t* dW = dw_base + d.dw_off;
-  const LohaSides o = {ab_base + d.a_off,    ab_base + d.b_off,    ab_base + h.a2_off,    ab_base + h.b2_off,
-                       grad_base + d.ga_off, grad_base + d.gb_off, grad_base + h.ga2_off, grad_base + h.gb2_off};
-  if (tl < d.tiles_da) {
-    if (d.r <= 16) loha_da_stripe<1>(d, o, tl, dW); else loha_da_stripe<2>(d, o, tl, dW);  // (workgroup-uniform)
-    return;
-  }
-  const int t = tl - d.tiles_da, stripe = t / x.chunks, chunk = t % x.chunks;
-  if (d.r <= 16) loha_db_chunk<1>(d, x, o, h.part_off, stripe, chunk, dW, counters, parts, stage, &s_flag);
-  else loha_db_chunk<2>(d, x, o, h.part_off, stripe, chunk, dW, counters, parts, stage, &s_flag);
+  const LohaSides o = {{ab_base + d.a_off, ab_base + h.a2_off}, {ab_base + d.b_off, ab_base + h.b2_off},
+                       {grad_base + d.ga_off, grad_base + h.ga2_off}, {grad_base + d.gb_off, grad_base + h.gb2_off}};
+  for_rank_blocks<2>(d.r, [&](auto rb) {
+    constexpr int RB = decltype(rb)::value;
+    if (tl < d.tiles_da) {
+      loha_da_stripe<RB>(d, o, tl, dW);
+      return;
+    }
+    const int t = tl - d.tiles_da;
+    loha_db_chunk<RB>(d, x, o, h.part_off, t / x.chunks, t % x.chunks, dW, counters, parts, stage, &s_flag);
+  });
 }
 
 // Host check of the table (the host copy; the device copy must hold the same bytes).  Returns the number of tiles or -1.
@@ -854,72 +825,115 @@ long check_dora_jobs(const char* name, const SdtLoraJob* h, const SdtDoraJob* x,
   return stripes;
 }
 
-// The split table beside the job table (host copies).  Returns the number of workgroups or -1; *counters = the arrival counters (one
-// per dB stripe), *floats = the partials.
-long check_split_jobs(const char* name, const SdtLoraJob* h, const SdtLoraSplitJob* x, int n, long* counters, long* floats) {
-  long tiles = 0, cnt = 0, part = 0;
+// The chunk and stripe arithmetic of the split projections, once: what a job adds to the workgroups (tiles), the arrival counters (one
+// per dB stripe) and the partial floats (`sides` slabs of [r][64] per stripe and chunk, none for a job of one chunk) of its table.
+struct SplitCount {
+  long tiles = 0, counters = 0, floats = 0;
+  void add(const SdtLoraJob& j, int sides) {
+    const long chunks = (j.K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (j.N + LT - 1) / LT;
+    tiles += j.tiles_da + stripes * chunks;
+    counters += stripes;
+    if (chunks > 1) floats += sides * stripes * chunks * j.r * LT;
+  }
+  long bytes() const { return (counters * 4 + 255) / 256 * 256 + 4 * floats; }  // the workspace: counters, padded to 256 bytes, then partials
+  long counter_bytes() const { return bytes() - 4 * floats; }
+};
+SplitCount split_count(const SdtLoraJob* h, int n, int sides) {
+  SplitCount t;
+  for (int i = 0; i < n; ++i) t.add(h[i], sides);
+  return t;
+}
+
+// The split table beside the job table (host copies; part_off counts one side's partials).  False with the message set for a bad table.
+bool check_split_jobs(const char* name, const SdtLoraJob* h, const SdtLoraSplitJob* x, int n) {
+  SplitCount t;
   for (int i = 0; i < n; ++i) {
     if (x[i].K != h[i].K || x[i].N != h[i].N) {
       sdt_set_error("%s: job %d: the split table names K=%d N=%d, the job table K=%d N=%d (mismatched tables)", name, i, x[i].K, x[i].N,
                     h[i].K, h[i].N);
-      return -1;
+      return false;
     }
-    const long chunks = (h[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (h[i].N + LT - 1) / LT;
+    const long chunks = (h[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS;
     if (x[i].chunks != chunks) {
       sdt_set_error("%s: job %d: chunks=%d, K=%d makes %ld chunks of %d rows", name, i, x[i].chunks, h[i].K, chunks, SPLIT_ROWS);
-      return -1;
+      return false;
     }
-    if (x[i].tile0 != tiles || x[i].cnt0 != cnt) {
+    if (x[i].tile0 != t.tiles || x[i].cnt0 != t.counters) {
       sdt_set_error("%s: job %d: tile0 / cnt0 do not continue the running tile and stripe counts", name, i);
-      return -1;
+      return false;
     }
-    if (x[i].part_off != part) {
-      sdt_set_error("%s: job %d: part_off=%lld does not continue the running partial offset %ld", name, i, (long long)x[i].part_off, part);
-      return -1;
+    if (x[i].part_off != t.floats) {
+      sdt_set_error("%s: job %d: part_off=%lld does not continue the running partial offset %ld", name, i, (long long)x[i].part_off,
+                    t.floats);
+      return false;
     }
-    tiles += h[i].tiles_da + stripes * chunks;
-    cnt += stripes;
-    if (chunks > 1) part += stripes * chunks * h[i].r * LT;
-    if (tiles >= (1L << 31) || cnt >= (1L << 31)) {
+    t.add(h[i], 1);
+    if (t.tiles >= (1L << 31) || t.counters >= (1L << 31)) {
       sdt_set_error("%s: too many tiles", name);
-      return -1;
+      return false;
     }
   }
-  *counters = cnt;
-  *floats = part;
-  return tiles;
+  return true;
 }
-inline long split_counter_bytes(long counters) { return (counters * 4 + 255) / 256 * 256; }
 
 // The LoHa table beside the job table (host copies): ranks up to 32, K / N equal, side-2 offsets, the running offset of the two-set
-// partials.  Returns the partial floats or -1.
-long check_loha_jobs(const char* name, const SdtLoraJob* h, const SdtLohaJob* x, int n) {
-  long part = 0;
+// partials.  False with the message set for a bad table.
+bool check_loha_jobs(const char* name, const SdtLoraJob* h, const SdtLohaJob* x, int n) {
+  SplitCount t;
   for (int i = 0; i < n; ++i) {
     if (h[i].r > 32) {
       sdt_set_error("%s: job %d: rank %d: LoHa takes the ranks 4, 8, 16 and 32 (one MFMA K-step forms a block of A B)", name, i, h[i].r);
-      return -1;
+      return false;
     }
     if (x[i].K != h[i].K || x[i].N != h[i].N) {
       sdt_set_error("%s: job %d: the LoHa table names K=%d N=%d, the job table K=%d N=%d (mismatched tables)", name, i, x[i].K, x[i].N,
                     h[i].K, h[i].N);
-      return -1;
+      return false;
     }
     const int64_t offs[4] = {x[i].a2_off, x[i].b2_off, x[i].ga2_off, x[i].gb2_off};
     for (int o = 0; o < 4; ++o)
       if (offs[o] < 0 || offs[o] % 8) {
         sdt_set_error("%s: job %d: LoHa offsets must be non-negative multiples of 8 elements", name, i);
-        return -1;
+        return false;
       }
-    if (x[i].part_off != part) {
+    if (x[i].part_off != t.floats) {
       sdt_set_error("%s: job %d: LoHa part_off=%lld does not continue the running partial offset %ld", name, i, (long long)x[i].part_off,
-                    part);
+                    t.floats);
+      return false;
+    }
+    t.add(h[i], 2);
+  }
+  return true;
+}
+
+// The preamble of every launching entry point, in this order: n >= 0; n == 0 has nothing to do (SDT_OK, before anything else is looked
+// at); the tables, the pointers and a destination exist; the OR of the addresses is 16-byte aligned.  ENTRY_GO: go on.
+constexpr int ENTRY_GO = 1;
+int entry_args(const char* name, int n, bool tables, bool pointers, bool destination, uintptr_t addresses) {
+  SDT_CHECK_ARG(n >= 0, "%s: negative job count", name);
+  if (n == 0) return SDT_OK;
+  SDT_CHECK_ARG(tables, "%s: null job table", name);
+  SDT_CHECK_ARG(pointers, "%s: null pointer", name);
+  SDT_CHECK_ARG(destination, "%s: no destination", name);
+  SDT_CHECK_ARG((addresses & 15) == 0, "%s: pointers must be 16-byte aligned", name);
+  return ENTRY_GO;
+}
+template <class... P>
+uintptr_t address_bits(P... p) { return (... | (uintptr_t)p); }
+
+// The workspace of a split projection over the table, or -1: counters and `sides` sets of partials.
+int64_t split_workspace_bytes(const char* name, const SdtLoraJob* jobs_host, int n, int sides) {
+  if (n < 0 || (n > 0 && !jobs_host)) {
+    sdt_set_error("%s: bad job table", name);
+    return -1;
+  }
+  if (check_jobs(name, jobs_host, n, true) < 0) return -1;
+  for (int i = 0; sides == 2 && i < n; ++i)
+    if (jobs_host[i].r > 32) {
+      sdt_set_error("%s: job %d: rank %d: LoHa takes the ranks 4, 8, 16 and 32", name, i, jobs_host[i].r);
       return -1;
     }
-    const long chunks = (h[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (h[i].N + LT - 1) / LT;
-    if (chunks > 1) part += 2 * stripes * chunks * h[i].r * LT;
-  }
-  return part;
+  return split_count(jobs_host, n, sides).bytes();
 }
 
 }  // namespace
@@ -928,16 +942,14 @@ extern "C" {
 
 int sdt_lora_job_size(void) { return (int)sizeof(SdtLoraJob); }
 int sdt_dora_job_size(void) { return (int)sizeof(SdtDoraJob); }
+int sdt_lora_split_job_size(void) { return (int)sizeof(SdtLoraSplitJob); }
+int sdt_loha_job_size(void) { return (int)sizeof(SdtLohaJob); }
+int sdt_lora_project_split_rows(void) { return SPLIT_ROWS; }
 
 int sdt_lora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, const SdtLoraJob* jobs_host,
                    const void* jobs_device, int n, hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_lora_merge: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device, "sdt_lora_merge: null job table");
-  SDT_CHECK_ARG(w0_base && ab_base, "sdt_lora_merge: null pointer");
-  SDT_CHECK_ARG(w_bf16 || f32_dst, "sdt_lora_merge: no destination");
-  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)w_bf16 | (uintptr_t)f32_dst) & 15) == 0,
-                "sdt_lora_merge: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_lora_merge", n, jobs_host && jobs_device, w0_base && ab_base, w_bf16 || f32_dst,
+                                address_bits(w0_base, ab_base, w_bf16, f32_dst)); rc != ENTRY_GO) return rc;
   const long tiles = check_jobs("sdt_lora_merge", jobs_host, n, false);
   if (tiles < 0) return SDT_ERR_INVALID_ARG;
   hipLaunchKernelGGL(lora_merge_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, w0_base, ab_base, (bf16_t*)w_bf16, f32_dst,
@@ -948,11 +960,8 @@ int sdt_lora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16,
 
 int sdt_lora_restore(const float* w0_base, uint16_t* w_bf16, const SdtLoraJob* jobs_host, const void* jobs_device, int n,
                      hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_lora_restore: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device, "sdt_lora_restore: null job table");
-  SDT_CHECK_ARG(w0_base && w_bf16, "sdt_lora_restore: null pointer");
-  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)w_bf16) & 15) == 0, "sdt_lora_restore: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_lora_restore", n, jobs_host && jobs_device, w0_base && w_bf16, true, address_bits(w0_base, w_bf16));
+      rc != ENTRY_GO) return rc;
   const long tiles = check_jobs("sdt_lora_restore", jobs_host, n, false);
   if (tiles < 0) return SDT_ERR_INVALID_ARG;
   hipLaunchKernelGGL(lora_restore_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, w0_base, (bf16_t*)w_bf16,
@@ -963,12 +972,8 @@ int sdt_lora_restore(const float* w0_base, uint16_t* w_bf16, const SdtLoraJob* j
 
 int sdt_lora_project(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
                      const void* jobs_device, int n, hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_lora_project: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device, "sdt_lora_project: null job table");
-  SDT_CHECK_ARG(dw_base && ab_base && grad_base, "sdt_lora_project: null pointer");
-  SDT_CHECK_ARG((((uintptr_t)dw_base | (uintptr_t)ab_base | (uintptr_t)grad_base) & 15) == 0,
-                "sdt_lora_project: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_lora_project", n, jobs_host && jobs_device, dw_base && ab_base && grad_base, true,
+                                address_bits(dw_base, ab_base, grad_base)); rc != ENTRY_GO) return rc;
   const long tiles = check_jobs("sdt_lora_project", jobs_host, n, true);
   if (tiles < 0) return SDT_ERR_INVALID_ARG;
   hipLaunchKernelGGL(lora_project_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
@@ -977,63 +982,37 @@ int sdt_lora_project(const uint16_t* dw_base, const float* ab_base, float* grad_
   return SDT_OK;
 }
 
-int sdt_lora_split_job_size(void) { return (int)sizeof(SdtLoraSplitJob); }
-int sdt_lora_project_split_rows(void) { return SPLIT_ROWS; }
-
 int64_t sdt_lora_project_split_workspace_bytes(const SdtLoraJob* jobs_host, int n) {
-  if (n < 0 || (n > 0 && !jobs_host)) {
-    sdt_set_error("sdt_lora_project_split_workspace_bytes: bad job table");
-    return -1;
-  }
-  if (check_jobs("sdt_lora_project_split_workspace_bytes", jobs_host, n, true) < 0) return -1;
-  long cnt = 0, part = 0;
-  for (int i = 0; i < n; ++i) {
-    const long chunks = (jobs_host[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (jobs_host[i].N + LT - 1) / LT;
-    cnt += stripes;
-    if (chunks > 1) part += stripes * chunks * jobs_host[i].r * LT;
-  }
-  return split_counter_bytes(cnt) + 4 * part;
+  return split_workspace_bytes("sdt_lora_project_split_workspace_bytes", jobs_host, n, 1);
 }
 
 int sdt_lora_project_split(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
                            const SdtLoraSplitJob* split_host, const void* jobs_device, const void* split_device, int n, void* workspace,
                            int64_t workspace_bytes, hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_lora_project_split: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device && split_host && split_device, "sdt_lora_project_split: null job table");
-  SDT_CHECK_ARG(dw_base && ab_base && grad_base && workspace, "sdt_lora_project_split: null pointer");
-  SDT_CHECK_ARG((((uintptr_t)dw_base | (uintptr_t)ab_base | (uintptr_t)grad_base | (uintptr_t)workspace) & 15) == 0,
-                "sdt_lora_project_split: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_lora_project_split", n, jobs_host && jobs_device && split_host && split_device,
+                                dw_base && ab_base && grad_base && workspace, true, address_bits(dw_base, ab_base, grad_base, workspace));
+      rc != ENTRY_GO) return rc;
   if (check_jobs("sdt_lora_project_split", jobs_host, n, true) < 0) return SDT_ERR_INVALID_ARG;
-  long cnt = 0, part = 0;
-  const long tiles = check_split_jobs("sdt_lora_project_split", jobs_host, split_host, n, &cnt, &part);
-  if (tiles < 0) return SDT_ERR_INVALID_ARG;
-  const long need = split_counter_bytes(cnt) + 4 * part;
-  if (workspace_bytes < need) {
+  if (!check_split_jobs("sdt_lora_project_split", jobs_host, split_host, n)) return SDT_ERR_INVALID_ARG;
+  const SplitCount t = split_count(jobs_host, n, 1);
+  if (workspace_bytes < t.bytes()) {
     sdt_set_error("sdt_lora_project_split: the workspace holds %lld bytes, the table needs %ld (counters and partials inside the workspace)",
-                  (long long)workspace_bytes, need);
+                  (long long)workspace_bytes, t.bytes());
     return SDT_ERR_INVALID_ARG;
   }
-  hipLaunchKernelGGL(lora_project_split_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
+  hipLaunchKernelGGL(lora_project_split_kernel, dim3((unsigned)t.tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
                      (const SdtLoraJob*)jobs_device, (const SdtLoraSplitJob*)split_device, n, (int*)workspace,
-                     (float*)((char*)workspace + split_counter_bytes(cnt)));
+                     (float*)((char*)workspace + t.counter_bytes()));
   SDT_LAUNCH_CHECK("sdt_lora_project_split");
   return SDT_OK;
 }
 
-int sdt_loha_job_size(void) { return (int)sizeof(SdtLohaJob); }
-
 int sdt_loha_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, const SdtLoraJob* jobs_host,
                    const SdtLohaJob* loha_host, const void* jobs_device, const void* loha_device, int n, hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_loha_merge: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device && loha_host && loha_device, "sdt_loha_merge: null job table");
-  SDT_CHECK_ARG(w0_base && ab_base, "sdt_loha_merge: null pointer");
-  SDT_CHECK_ARG(w_bf16 || f32_dst, "sdt_loha_merge: no destination");
-  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)w_bf16 | (uintptr_t)f32_dst) & 15) == 0,
-                "sdt_loha_merge: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_loha_merge", n, jobs_host && jobs_device && loha_host && loha_device, w0_base && ab_base,
+                                w_bf16 || f32_dst, address_bits(w0_base, ab_base, w_bf16, f32_dst)); rc != ENTRY_GO) return rc;
   const long tiles = check_jobs("sdt_loha_merge", jobs_host, n, false);
-  if (tiles < 0 || check_loha_jobs("sdt_loha_merge", jobs_host, loha_host, n) < 0) return SDT_ERR_INVALID_ARG;
+  if (tiles < 0 || !check_loha_jobs("sdt_loha_merge", jobs_host, loha_host, n)) return SDT_ERR_INVALID_ARG;
   hipLaunchKernelGGL(loha_merge_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, w0_base, ab_base, (bf16_t*)w_bf16, f32_dst,
                      (const SdtLoraJob*)jobs_device, (const SdtLohaJob*)loha_device, n);
   SDT_LAUNCH_CHECK("sdt_loha_merge");
@@ -1041,48 +1020,27 @@ int sdt_loha_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16,
 }
 
 int64_t sdt_loha_project_workspace_bytes(const SdtLoraJob* jobs_host, int n) {
-  if (n < 0 || (n > 0 && !jobs_host)) {
-    sdt_set_error("sdt_loha_project_workspace_bytes: bad job table");
-    return -1;
-  }
-  if (check_jobs("sdt_loha_project_workspace_bytes", jobs_host, n, true) < 0) return -1;
-  long cnt = 0, part = 0;
-  for (int i = 0; i < n; ++i) {
-    if (jobs_host[i].r > 32) {
-      sdt_set_error("sdt_loha_project_workspace_bytes: job %d: rank %d: LoHa takes the ranks 4, 8, 16 and 32", i, jobs_host[i].r);
-      return -1;
-    }
-    const long chunks = (jobs_host[i].K + SPLIT_ROWS - 1) / SPLIT_ROWS, stripes = (jobs_host[i].N + LT - 1) / LT;
-    cnt += stripes;
-    if (chunks > 1) part += 2 * stripes * chunks * jobs_host[i].r * LT;
-  }
-  return split_counter_bytes(cnt) + 4 * part;
+  return split_workspace_bytes("sdt_loha_project_workspace_bytes", jobs_host, n, 2);
 }
 
 int sdt_loha_project(const uint16_t* dw_base, const float* ab_base, float* grad_base, const SdtLoraJob* jobs_host,
                      const SdtLoraSplitJob* split_host, const SdtLohaJob* loha_host, const void* jobs_device, const void* split_device,
                      const void* loha_device, int n, void* workspace, int64_t workspace_bytes, hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_loha_project: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device && split_host && split_device && loha_host && loha_device, "sdt_loha_project: null job table");
-  SDT_CHECK_ARG(dw_base && ab_base && grad_base && workspace, "sdt_loha_project: null pointer");
-  SDT_CHECK_ARG((((uintptr_t)dw_base | (uintptr_t)ab_base | (uintptr_t)grad_base | (uintptr_t)workspace) & 15) == 0,
-                "sdt_loha_project: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_loha_project", n, jobs_host && jobs_device && split_host && split_device && loha_host && loha_device,
+                                dw_base && ab_base && grad_base && workspace, true, address_bits(dw_base, ab_base, grad_base, workspace));
+      rc != ENTRY_GO) return rc;
   if (check_jobs("sdt_loha_project", jobs_host, n, true) < 0) return SDT_ERR_INVALID_ARG;
-  const long part = check_loha_jobs("sdt_loha_project", jobs_host, loha_host, n);
-  if (part < 0) return SDT_ERR_INVALID_ARG;
-  long cnt = 0, part1 = 0;
-  const long tiles = check_split_jobs("sdt_loha_project", jobs_host, split_host, n, &cnt, &part1);
-  if (tiles < 0) return SDT_ERR_INVALID_ARG;
-  const long need = split_counter_bytes(cnt) + 4 * part;
-  if (workspace_bytes < need) {
+  if (!check_loha_jobs("sdt_loha_project", jobs_host, loha_host, n)) return SDT_ERR_INVALID_ARG;
+  if (!check_split_jobs("sdt_loha_project", jobs_host, split_host, n)) return SDT_ERR_INVALID_ARG;
+  const SplitCount t = split_count(jobs_host, n, 2);
+  if (workspace_bytes < t.bytes()) {
     sdt_set_error("sdt_loha_project: the workspace holds %lld bytes, the table needs %ld (counters and two sets of partials inside the workspace)",
-                  (long long)workspace_bytes, need);
+                  (long long)workspace_bytes, t.bytes());
     return SDT_ERR_INVALID_ARG;
   }
-  hipLaunchKernelGGL(loha_project_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
+  hipLaunchKernelGGL(loha_project_kernel, dim3((unsigned)t.tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, ab_base, grad_base,
                      (const SdtLoraJob*)jobs_device, (const SdtLoraSplitJob*)split_device, (const SdtLohaJob*)loha_device, n,
-                     (int*)workspace, (float*)((char*)workspace + split_counter_bytes(cnt)));
+                     (int*)workspace, (float*)((char*)workspace + t.counter_bytes()));
   SDT_LAUNCH_CHECK("sdt_loha_project");
   return SDT_OK;
 }
@@ -1090,13 +1048,8 @@ int sdt_loha_project(const uint16_t* dw_base, const float* ab_base, float* grad_
 int sdt_dora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16, float* f32_dst, float* stat_base,
                    const SdtLoraJob* jobs_host, const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n,
                    hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_dora_merge: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device && dora_host && dora_device, "sdt_dora_merge: null job table");
-  SDT_CHECK_ARG(w0_base && ab_base && stat_base, "sdt_dora_merge: null pointer");
-  SDT_CHECK_ARG(w_bf16 || f32_dst, "sdt_dora_merge: no destination");
-  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)w_bf16 | (uintptr_t)f32_dst | (uintptr_t)stat_base) & 15) == 0,
-                "sdt_dora_merge: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_dora_merge", n, jobs_host && jobs_device && dora_host && dora_device, w0_base && ab_base && stat_base,
+                                w_bf16 || f32_dst, address_bits(w0_base, ab_base, w_bf16, f32_dst, stat_base)); rc != ENTRY_GO) return rc;
   if (check_jobs("sdt_dora_merge", jobs_host, n, false) < 0) return SDT_ERR_INVALID_ARG;
   const long stripes = check_dora_jobs("sdt_dora_merge", jobs_host, dora_host, n);
   if (stripes < 0) return SDT_ERR_INVALID_ARG;
@@ -1108,12 +1061,8 @@ int sdt_dora_merge(const float* w0_base, const float* ab_base, uint16_t* w_bf16,
 
 int sdt_dora_init_magnitude(const float* w0_base, const float* ab_base, float* m_base, const SdtLoraJob* jobs_host,
                             const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n, hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_dora_init_magnitude: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device && dora_host && dora_device, "sdt_dora_init_magnitude: null job table");
-  SDT_CHECK_ARG(w0_base && ab_base && m_base, "sdt_dora_init_magnitude: null pointer");
-  SDT_CHECK_ARG((((uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)m_base) & 15) == 0,
-                "sdt_dora_init_magnitude: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_dora_init_magnitude", n, jobs_host && jobs_device && dora_host && dora_device,
+                                w0_base && ab_base && m_base, true, address_bits(w0_base, ab_base, m_base)); rc != ENTRY_GO) return rc;
   if (check_jobs("sdt_dora_init_magnitude", jobs_host, n, false) < 0) return SDT_ERR_INVALID_ARG;
   const long stripes = check_dora_jobs("sdt_dora_init_magnitude", jobs_host, dora_host, n);
   if (stripes < 0) return SDT_ERR_INVALID_ARG;
@@ -1126,12 +1075,9 @@ int sdt_dora_init_magnitude(const float* w0_base, const float* ab_base, float* m
 int sdt_dora_project(const uint16_t* dw_base, const float* w0_base, const float* ab_base, float* grad_base, const float* stat_base,
                      const SdtLoraJob* jobs_host, const SdtDoraJob* dora_host, const void* jobs_device, const void* dora_device, int n,
                      hipStream_t stream) {
-  SDT_CHECK_ARG(n >= 0, "sdt_dora_project: negative job count");
-  if (n == 0) return SDT_OK;
-  SDT_CHECK_ARG(jobs_host && jobs_device && dora_host && dora_device, "sdt_dora_project: null job table");
-  SDT_CHECK_ARG(dw_base && w0_base && ab_base && grad_base && stat_base, "sdt_dora_project: null pointer");
-  SDT_CHECK_ARG((((uintptr_t)dw_base | (uintptr_t)w0_base | (uintptr_t)ab_base | (uintptr_t)grad_base | (uintptr_t)stat_base) & 15) == 0,
-                "sdt_dora_project: pointers must be 16-byte aligned");
+  if (const int rc = entry_args("sdt_dora_project", n, jobs_host && jobs_device && dora_host && dora_device,
+                                dw_base && w0_base && ab_base && grad_base && stat_base, true,
+                                address_bits(dw_base, w0_base, ab_base, grad_base, stat_base)); rc != ENTRY_GO) return rc;
   const long tiles = check_jobs("sdt_dora_project", jobs_host, n, true);
   if (tiles < 0 || check_dora_jobs("sdt_dora_project", jobs_host, dora_host, n) < 0) return SDT_ERR_INVALID_ARG;
   hipLaunchKernelGGL(dora_project_kernel, dim3((unsigned)tiles), dim3(256), 0, stream, (const bf16_t*)dw_base, w0_base, ab_base, grad_base,

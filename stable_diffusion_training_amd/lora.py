@@ -238,89 +238,85 @@ class LoraAdapter:
         # split table and workspace of sdt_lora_project_split beside it); merge / restore / folded launch once per non-empty table
         self.dense_paths = [p for p in self.paths if len(base.leaves[p].shape) == 2]
         self.conv_paths = [p for p in self.paths if len(base.leaves[p].shape) == 4]
-
-        def job(p, tm, tp):
-            lf = base.leaves[p]
-            la, lb = (self.store.leaves[q] for q in self.adapted[p][:2])
-            K, N, r, scale = leaf_factors(lf.shape, cfg)
-            return _lib.SdtLoraJob(lf.offset, la.offset, lb.offset, lf.w_off, lf.offset, self.scratch_offset(lf.offset, lf.offset + lf.numel),
-                                   la.offset, lb.offset, K, N, r, scale, tm, tp, (K + 63) // 64, 0)
-
-        jobs, dora, tm, tp, sm, so = [], [], 0, 0, 0, 0
-        for p in self.dense_paths:
-            jobs.append(job(p, tm, tp))
-            K, N, ta = jobs[-1].K, jobs[-1].N, jobs[-1].tiles_da
-            tm += ta * ((N + 63) // 64)
-            tp += ta + (N + 63) // 64
-            if cfg.dora:
-                lm = self.store.leaves[self.adapted[p][2]]
-                dora.append(_lib.SdtDoraJob(lm.offset, lm.offset, so, N, sm))
-                sm += (N + 63) // 64
-                so += 2 * N  # c [N], then g [N]
-        self.jobs_host = (_lib.SdtLoraJob * len(jobs))(*jobs)
-        self.jobs_dev = torch.frombuffer(bytearray(bytes(self.jobs_host)), dtype=torch.uint8).to(dev)
+        self.jobs_host = self._job_table(self.dense_paths)
+        self.jobs_dev = self._to_device(self.jobs_host)
+        self._tables = [(self.dense_paths, self.jobs_host, self.jobs_dev)]
         self.dora_host = self.dora_dev = self.stats = None
         if cfg.dora:
+            dora, sm, so = [], 0, 0
+            for p, j in zip(self.dense_paths, self.jobs_host):
+                lm = self.store.leaves[self.adapted[p][2]]
+                dora.append(_lib.SdtDoraJob(lm.offset, lm.offset, so, j.N, sm))
+                sm += (j.N + 63) // 64
+                so += 2 * j.N  # c [N], then g [N]
             self.dora_host = (_lib.SdtDoraJob * len(dora))(*dora)
-            self.dora_dev = torch.frombuffer(bytearray(bytes(self.dora_host)), dtype=torch.uint8).to(dev)
+            self.dora_dev = self._to_device(self.dora_host)
             self.stats = torch.zeros(so, dtype=torch.float32, device=dev)
         self.conv_jobs_host = self.conv_jobs_dev = self.split_host = self.split_dev = self.split_ws = None
         if self.conv_paths:
-            rows = _lib.load().sdt_lora_project_split_rows()
-            cjobs, split, tm, tp, ts, cnt, part = [], [], 0, 0, 0, 0, 0
-            for p in self.conv_paths:
-                j = job(p, tm, tp)
-                ta, tb, chunks = j.tiles_da, (j.N + 63) // 64, (j.K + rows - 1) // rows
-                cjobs.append(j)
-                split.append(_lib.SdtLoraSplitJob(part, j.K, j.N, ts, chunks, cnt, 0))
-                tm += ta * tb
-                tp += ta + tb
-                ts += ta + tb * chunks
-                cnt += tb
-                part += tb * chunks * j.r * 64 if chunks > 1 else 0
-            self.conv_jobs_host = (_lib.SdtLoraJob * len(cjobs))(*cjobs)
-            self.split_host = (_lib.SdtLoraSplitJob * len(split))(*split)
-            self.conv_jobs_dev = torch.frombuffer(bytearray(bytes(self.conv_jobs_host)), dtype=torch.uint8).to(dev)
-            self.split_dev = torch.frombuffer(bytearray(bytes(self.split_host)), dtype=torch.uint8).to(dev)
+            self.conv_jobs_host = self._job_table(self.conv_paths)
+            self.conv_jobs_dev = self._to_device(self.conv_jobs_host)
+            self._tables.append((self.conv_paths, self.conv_jobs_host, self.conv_jobs_dev))
+            self.split_host = self._split_table(self.conv_jobs_host)
+            self.split_dev = self._to_device(self.split_host)
             if cfg.algo == "lora":
-                need = _lib.load().sdt_lora_project_split_workspace_bytes(self.conv_jobs_host, len(cjobs))
-                if need < 0:
-                    raise _lib.SdtError(f"sdt_lora_project_split_workspace_bytes: {_lib.load().sdt_last_error().decode()}")
-                # arrival counters (zero between launches) and partials: allocated once, so that a captured step replays it
-                self.split_ws = torch.zeros(need, dtype=torch.uint8, device=dev)
+                self.split_ws = self._workspace("sdt_lora_project_split_workspace_bytes", self.conv_jobs_host)
         # LoHa: per non-empty job table (jobs_host, jobs_dev, split_host, split_dev, loha_host, loha_dev, workspace)
-        self.loha = []
-        if cfg.algo == "loha":
-            for paths, jh, jd in ((self.dense_paths, self.jobs_host, self.jobs_dev), (self.conv_paths, self.conv_jobs_host, self.conv_jobs_dev)):
-                if paths:
-                    self.loha.append(self._loha_tables(paths, jh, jd))
+        self.loha = [self._loha_tables(*t) for t in self._tables if t[0]] if cfg.algo == "loha" else []
         self.init_weights()
         base.adapter = self
         if dev.type == "cuda":
             self.merge()
 
-    def _loha_tables(self, paths, jobs_host, jobs_dev):
-        """The SdtLoraSplitJob and SdtLohaJob tables beside one job table and the workspace of sdt_loha_project: arrival counters (zero
-        between launches) and two partial sets per job of more than one chunk, allocated and zeroed once so that a captured step replays it."""
-        lib, dev = _lib.load(), self.base.device
-        rows = lib.sdt_lora_project_split_rows()
-        split, loha, ts, cnt, part1, part2 = [], [], 0, 0, 0, 0
-        for p, j in zip(paths, jobs_host):
-            la2, lb2 = (self.store.leaves[q] for q in self.adapted[p][2:])
+    def _to_device(self, table):
+        return torch.frombuffer(bytearray(bytes(table)), dtype=torch.uint8).to(self.base.device)
+
+    def _job_table(self, paths):
+        """The SdtLoraJob table of `paths`, with the running first tiles of its merge and its projection."""
+        jobs, tm, tp = [], 0, 0
+        for p in paths:
+            lf = self.base.leaves[p]
+            la, lb = (self.store.leaves[q] for q in self.adapted[p][:2])
+            K, N, r, scale = leaf_factors(lf.shape, self.cfg)
+            ta, tb = (K + 63) // 64, (N + 63) // 64
+            jobs.append(_lib.SdtLoraJob(lf.offset, la.offset, lb.offset, lf.w_off, lf.offset, self.scratch_offset(lf.offset, lf.offset + lf.numel),
+                                        la.offset, lb.offset, K, N, r, scale, tm, tp, ta, 0))
+            tm += ta * tb
+            tp += ta + tb
+        return (_lib.SdtLoraJob * len(jobs))(*jobs)
+
+    def _split_table(self, jobs_host):
+        """The SdtLoraSplitJob table beside a job table: chunks of sdt_lora_project_split_rows() rows, and the running first workgroup,
+        first arrival counter and (one-sided) partial offset of every job."""
+        rows = _lib.load().sdt_lora_project_split_rows()
+        split, ts, cnt, part = [], 0, 0, 0
+        for j in jobs_host:
             tb, chunks = (j.N + 63) // 64, (j.K + rows - 1) // rows
-            split.append(_lib.SdtLoraSplitJob(part1, j.K, j.N, ts, chunks, cnt, 0))
-            loha.append(_lib.SdtLohaJob(la2.offset, lb2.offset, la2.offset, lb2.offset, part2, j.K, j.N))
+            split.append(_lib.SdtLoraSplitJob(part, j.K, j.N, ts, chunks, cnt, 0))
             ts += j.tiles_da + tb * chunks
             cnt += tb
-            part1 += tb * chunks * j.r * 64 if chunks > 1 else 0
-            part2 += 2 * tb * chunks * j.r * 64 if chunks > 1 else 0
-        split_host = (_lib.SdtLoraSplitJob * len(split))(*split)
-        loha_host = (_lib.SdtLohaJob * len(loha))(*loha)
-        to_dev = lambda t: torch.frombuffer(bytearray(bytes(t)), dtype=torch.uint8).to(dev)
-        need = lib.sdt_loha_project_workspace_bytes(jobs_host, len(jobs_host))
+            part += tb * chunks * j.r * 64 if chunks > 1 else 0
+        return (_lib.SdtLoraSplitJob * len(split))(*split)
+
+    def _workspace(self, sizer, jobs_host):
+        """The workspace `sizer` asks for: arrival counters (zero between launches) and partials, allocated and zeroed once so that a
+        captured step replays it."""
+        need = getattr(_lib.load(), sizer)(jobs_host, len(jobs_host))
         if need < 0:
-            raise _lib.SdtError(f"sdt_loha_project_workspace_bytes: {lib.sdt_last_error().decode()}")
-        return jobs_host, jobs_dev, split_host, to_dev(split_host), loha_host, to_dev(loha_host), torch.zeros(need, dtype=torch.uint8, device=dev)
+            raise _lib.SdtError(f"{sizer}: {_lib.load().sdt_last_error().decode()}")
+        return torch.zeros(need, dtype=torch.uint8, device=self.base.device)
+
+    def _loha_tables(self, paths, jobs_host, jobs_dev):
+        """The SdtLoraSplitJob and SdtLohaJob tables beside one job table and the workspace of sdt_loha_project (two partial sets per
+        job of more than one chunk: a LoHa partial offset is twice the split table's)."""
+        split_host = self._split_table(jobs_host)
+        loha = []
+        for p, j, x in zip(paths, jobs_host, split_host):
+            la2, lb2 = (self.store.leaves[q] for q in self.adapted[p][2:])
+            loha.append(_lib.SdtLohaJob(la2.offset, lb2.offset, la2.offset, lb2.offset, 2 * x.part_off, j.K, j.N))
+        loha_host = (_lib.SdtLohaJob * len(loha))(*loha)
+        return (jobs_host, jobs_dev, split_host, self._to_device(split_host), loha_host, self._to_device(loha_host),
+                self._workspace("sdt_loha_project_workspace_bytes", jobs_host))
 
     # ------------------------------------------------------------------ parameters
     def init_weights(self):
@@ -391,10 +387,24 @@ class LoraAdapter:
     def _stream(self):
         return torch.cuda.current_stream().cuda_stream
 
+    def _merge_into(self, ab, w_ptr, f_ptr, stats):
+        """The merge of every table, factors from `ab`, into the bf16 mirror at w_ptr and / or the fp32 buffer at f_ptr (None: not
+        written).  LoHa: w = bf16(W0 + s * (A1 @ B1) * (A2 @ B2)); DoRA also leaves c and g of every leaf in `stats`."""
+        w0, ab, stream = self.base.master.data_ptr(), ab.data_ptr(), self._stream()
+        if self.loha:
+            for jh, jd, _, _, xh, xd, _ in self.loha:
+                _lib.call("sdt_loha_merge", w0, ab, w_ptr, f_ptr, jh, xh, jd.data_ptr(), xd.data_ptr(), len(jh), stream)
+        elif self.cfg.dora:
+            _lib.call("sdt_dora_merge", w0, ab, w_ptr, f_ptr, stats.data_ptr(), self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(),
+                      self.dora_dev.data_ptr(), len(self.jobs_host), stream)
+        else:
+            for _, jh, jd in self._tables:
+                _lib.call("sdt_lora_merge", w0, ab, w_ptr, f_ptr, jh, jd.data_ptr(), len(jh), stream)
+
     def merge(self, source=None):
-        """w[leaf] = bf16(W0 + s * A @ B) for every adapted leaf (one launch), A / B from the adapter store's master or its EMA.
-        The choice sticks: source=None (ParamStore.prepare, so StableDiffusionPipeline.generate) merges what was merged last; train_step
-        merges "master"."""
+        """w[leaf] = bf16(W0 + s * A @ B) for every adapted leaf (one launch per table), A / B from the adapter store's master or its
+        EMA.  The choice sticks: source=None (ParamStore.prepare, so StableDiffusionPipeline.generate) merges what was merged last;
+        train_step merges "master".  DoRA: self.stats is what project() reads."""
         source = self.source if source is None else source
         if source not in ("master", "ema"):
             raise ValueError(f"merge: source must be 'master' or 'ema', not {source!r}")
@@ -402,50 +412,32 @@ class LoraAdapter:
         if ab is None:
             raise ValueError("merge(source='ema'): the adapter store keeps no EMA")
         self.source = source
-        if self.loha:  # w[leaf] = bf16(W0 + s * (A1 @ B1) * (A2 @ B2)): one launch per table
-            for jh, jd, _, _, xh, xd, _ in self.loha:
-                _lib.call("sdt_loha_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, jh, xh, jd.data_ptr(),
-                          xd.data_ptr(), len(jh), self._stream())
-            return
-        if self.cfg.dora:  # also leaves c and g of every leaf in self.stats, for project()
-            _lib.call("sdt_dora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.stats.data_ptr(),
-                      self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(), self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
-            return
-        _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.jobs_host,
-                  self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
-        if self.conv_paths:
-            _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), self.base.w.data_ptr(), None, self.conv_jobs_host,
-                      self.conv_jobs_dev.data_ptr(), len(self.conv_jobs_host), self._stream())
+        self._merge_into(ab, self.base.w.data_ptr(), None, self.stats)
 
     def restore(self):
-        """w[leaf] = bf16(W0) for every adapted leaf (one launch, sdt_lora_restore): the mirror of the store without its adapter, bit
-        for bit - the reference model of a Diffusion-DPO step.  The inverse of merge() as far as the mirror is concerned; self.source
-        (what a later merge(None) merges) and, for DoRA, self.stats (what project() reads) stay what the last merge left."""
-        _lib.call("sdt_lora_restore", self.base.master.data_ptr(), self.base.w.data_ptr(), self.jobs_host, self.jobs_dev.data_ptr(),
-                  len(self.jobs_host), self._stream())
-        if self.conv_paths:
-            _lib.call("sdt_lora_restore", self.base.master.data_ptr(), self.base.w.data_ptr(), self.conv_jobs_host,
-                      self.conv_jobs_dev.data_ptr(), len(self.conv_jobs_host), self._stream())
+        """w[leaf] = bf16(W0) for every adapted leaf (one launch per table, sdt_lora_restore): the mirror of the store without its
+        adapter, bit for bit - the reference model of a Diffusion-DPO step.  The inverse of merge() as far as the mirror is concerned;
+        self.source (what a later merge(None) merges) and, for DoRA, self.stats (what project() reads) stay what the last merge left."""
+        for _, jh, jd in self._tables:
+            _lib.call("sdt_lora_restore", self.base.master.data_ptr(), self.base.w.data_ptr(), jh, jd.data_ptr(), len(jh), self._stream())
 
     def project(self):
         """dA, dB of every adapted leaf from the dW scratch into the adapter store's gradient (one launch; with LoCon a second one,
         sdt_lora_project_split, for the convolution table; written, not accumulated)."""
         from . import ops
+        dw, ab, grad, stream = self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), self._stream()
         if self.loha:  # the four factor gradients of every leaf: one launch per table (include/sdt.h "LoHa")
             for jh, jd, sh, sd, xh, xd, ws in self.loha:
-                _lib.call("sdt_loha_project", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), jh, sh, xh,
-                          jd.data_ptr(), sd.data_ptr(), xd.data_ptr(), len(jh), ws.data_ptr(), ws.numel(), self._stream())
+                _lib.call("sdt_loha_project", dw, ab, grad, jh, sh, xh, jd.data_ptr(), sd.data_ptr(), xd.data_ptr(), len(jh), ws.data_ptr(),
+                          ws.numel(), stream)
         elif self.cfg.dora:  # also dm, from the c and g the step's merge left in self.stats
-            _lib.call("sdt_dora_project", self.scratch.data_ptr(), self.base.master.data_ptr(), self.store.master.data_ptr(),
-                      self.store.grad.data_ptr(), self.stats.data_ptr(), self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(),
-                      self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
+            _lib.call("sdt_dora_project", dw, self.base.master.data_ptr(), ab, grad, self.stats.data_ptr(), self.jobs_host, self.dora_host,
+                      self.jobs_dev.data_ptr(), self.dora_dev.data_ptr(), len(self.jobs_host), stream)
         else:
-            _lib.call("sdt_lora_project", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(), self.jobs_host,
-                      self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
-        if self.conv_paths and not self.loha:  # tall K: the dB stripes split along K (include/sdt.h "LoCon")
-            _lib.call("sdt_lora_project_split", self.scratch.data_ptr(), self.store.master.data_ptr(), self.store.grad.data_ptr(),
-                      self.conv_jobs_host, self.split_host, self.conv_jobs_dev.data_ptr(), self.split_dev.data_ptr(),
-                      len(self.conv_jobs_host), self.split_ws.data_ptr(), self.split_ws.numel(), self._stream())
+            _lib.call("sdt_lora_project", dw, ab, grad, self.jobs_host, self.jobs_dev.data_ptr(), len(self.jobs_host), stream)
+            if self.conv_paths:  # tall K: the dB stripes split along K (include/sdt.h "LoCon")
+                _lib.call("sdt_lora_project_split", dw, ab, grad, self.conv_jobs_host, self.split_host, self.conv_jobs_dev.data_ptr(),
+                          self.split_dev.data_ptr(), len(self.conv_jobs_host), self.split_ws.data_ptr(), self.split_ws.numel(), stream)
         for p in self.paths:
             ops._ready(self.store, *self.adapted[p])
 
@@ -456,20 +448,10 @@ class LoraAdapter:
         if ab is None:
             raise ValueError("folded(source='ema'): the adapter store keeps no EMA")
         buf = self.base.master.clone()
-        if self.loha:
-            for jh, jd, _, _, xh, xd, _ in self.loha:
-                _lib.call("sdt_loha_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), jh, xh, jd.data_ptr(),
-                          xd.data_ptr(), len(jh), self._stream())
-        elif self.cfg.dora:  # (statistics of its own: self.stats stays what the last merge into the mirror left)
-            stats = torch.empty_like(self.stats)  # (bound to a name until the call has been enqueued)
-            _lib.call("sdt_dora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), stats.data_ptr(),
-                      self.jobs_host, self.dora_host, self.jobs_dev.data_ptr(), self.dora_dev.data_ptr(), len(self.jobs_host), self._stream())
-        else:
-            _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), self.jobs_host,
-                      self.jobs_dev.data_ptr(), len(self.jobs_host), self._stream())
-            if self.conv_paths:
-                _lib.call("sdt_lora_merge", self.base.master.data_ptr(), ab.data_ptr(), None, buf.data_ptr(), self.conv_jobs_host,
-                          self.conv_jobs_dev.data_ptr(), len(self.conv_jobs_host), self._stream())
+        # (DoRA: statistics of its own, bound to a name until the call has been enqueued - self.stats stays what the last merge into
+        # the mirror left)
+        stats = torch.empty_like(self.stats) if self.cfg.dora else None
+        self._merge_into(ab, None, buf.data_ptr(), stats)
         return {p: buf[lf.offset: lf.offset + lf.numel].view(lf.shape) for p, lf in self.base.leaves.items()}
 
     # ------------------------------------------------------------------ adapter file

@@ -243,7 +243,8 @@ for config in args.config:
         adapted = sum(us.store.leaves[p].numel for p in ad.paths)
         res["adapter"] = {"leaves": len(ad.paths), "adapted_params": adapted, "trained_params": sum(lf.numel for lf in ad.store.leaves.values()),
                           "scratch_bytes": 2 * ad.scratch.numel(), "merge_ms": round(event_ms(ad.merge), 4),
-                          "project_ms": round(event_ms(ad.project), 4)}
+                          "restore_ms": round(event_ms(ad.restore), 4), "project_ms": round(event_ms(ad.project), 4)}
+        ad.merge()  # (the mirror the step expects, after the timed restore)
 
         def opt():
             ad.store.zero_grad()
